@@ -10,13 +10,19 @@ K1 anchors / K2 iou_match / K3 fused loss+grad (hand-written HIP) -> backward ->
 all-reduce (N > 1) -> SGD step, on a per-GPU batch of 8 synthetic 3x800x1333 images resident in HBM.
 Weak scaling: per-GPU batch is fixed, `value` = all ranks' images / max-over-ranks wall time.
 
-The JSON line also carries
+A plain run sets up, warms up, times the --steps steps and prints the JSON line (`value`, `ms_per_step`, the workload and
+how the step was launched).  `--dump-outputs DIR` also writes what the last timed step computed as .npy files (see
+dump_train_outputs).  `--full` adds everything else the benchmark measures; the JSON line then also carries
   roofline     -- the dominant dense-head kernel (K3 loss fwd+bwd): algorithmic bytes per launch /
                   its average duration measured with HIP events right around the kernel on the launch stream, in eager
                   replays of the same step run right after the timed region (the timed steps are hipGraph replays), plus
                   the same kernel on cold logits (`frac_cold`);
   cpu_baseline -- the CPU oracle (oracle/rn_oracle.c, OpenMP) timed on this box's host cores on the
-                  same dense-head workload (rank 0, N=1 only; bounded sample).
+                  same dense-head workload (rank 0, N=1 only; bounded sample);
+plus the MFMA shares of the conv kernels, the K3 cold / match + loss / detect-chain / predict lines (N=1 only) and the
+GPU clocks during the timed region.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 import argparse
 import json
@@ -76,7 +82,12 @@ def parse():
                     "the MAX-reduced time) on a box that cannot run RCCL with N ranks -- e.g. with --share-gpu")
     ap.add_argument("--share-gpu", action="store_true", help="every rank uses cuda:0 (RCCL refuses two ranks on one device: needs --backend gloo); "
                     "the line then reports launch-path correctness, its images/sec is N ranks time-slicing one GPU")
-    ap.add_argument("--timing-steps", type=int, default=5, help="eager steps run AFTER the timed region with HIP events around the hand-written kernels (per-kernel figures of the JSON line)")
+    ap.add_argument("--timing-steps", type=int, default=5, help="--full: eager steps run AFTER the timed region with HIP events around the hand-written kernels (per-kernel figures of the JSON line)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: per-kernel events, roofline and MFMA figures, "
+                    "GPU clocks, the CPU baselines and the extra lines (K3 cold, match + loss, detect chain, predict); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                    "(train: the loss dict, a seeded sample of the updated parameters, the BatchNorm running statistics; --mode predict: the "
+                    "detections of the last call)")
     return ap.parse_args()
 
 
@@ -208,6 +219,36 @@ def synth_batch(batch, gt, seed, device):
         b, l = synth.gt_boxes(rng, gt, 800, 1333)
         targets.append({"boxes": torch.from_numpy(b).to(device), "labels": torch.from_numpy(l).to(device)})
     return images, targets
+
+
+DUMP_PARAM_SAMPLE = 1 << 20     # parameters written by --dump-outputs (of ~37 M at R50-FPN, K = 90): 4 MiB
+
+
+def dump_train_outputs(path, losses, net):
+    """--dump-outputs of the train step: what the caller of the step receives (the loss dict) and what the step changed, as fp32 / fp64
+    .npy files (~5 MB): ``params_sample`` = a fixed, seeded sample of all parameters (fp32 masters where the optimizer keeps them)
+    concatenated in ``named_parameters`` order, ``bn_running_stats`` = every BatchNorm running mean / variance concatenated."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "losses.npy"), np.array([float(losses[k]) for k in ("classification_loss", "regression_loss", "loss")], np.float64))
+    flat = torch.cat([getattr(p, "master", p).detach().float().reshape(-1) for p in net.parameters()])
+    n = min(DUMP_PARAM_SAMPLE, flat.numel())
+    idx = np.sort(np.random.default_rng(0).choice(flat.numel(), size=n, replace=False))
+    np.save(os.path.join(path, "params_sample.npy"), flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy())
+    bn = torch.cat([b.detach().float().reshape(-1) for name, b in net.named_buffers() if "running_" in name])
+    np.save(os.path.join(path, "bn_running_stats.npy"), bn.cpu().numpy())
+
+
+def dump_predict_outputs(path, dets, rows=100):
+    """--dump-outputs of --mode predict: the detections of the last predict() call, padded to `rows` per image with NaN."""
+    os.makedirs(path, exist_ok=True)
+    out = {"det_boxes": np.full((len(dets), rows, 4), np.nan, np.float32), "det_scores": np.full((len(dets), rows), np.nan, np.float32),
+           "det_labels": np.full((len(dets), rows), np.nan, np.float32)}
+    for i, d in enumerate(dets):
+        for k in ("boxes", "scores", "labels"):
+            v = d[k].detach().float().cpu().numpy()[:rows]
+            out["det_" + k][i, :len(v)] = v
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def k3_bytes(B, A, K, T, s):
@@ -364,7 +405,7 @@ def detect_chain_line(device, with_cpu, regime="sparse"):
 R101_FWD_GFLOP_1344 = 1124.0   # R101-FPN + heads forward @1344x1344 per image
 
 
-def predict_e2e_line(args, device, with_cpu):
+def predict_e2e_line(args, device, with_cpu, dump=None):
     """BASELINE configs[3] END TO END ("conv stack ... included in an end-to-end figure"; reference path
     retinanet/models.py:245-272): ``Retinanet.predict`` on B synthetic 3 x S x S images resident in HBM -- fused transform ->
     R101-FPN + heads in eval mode (frozen BatchNorm folded into the convolutions) under 16-bit autocast -> per-level
@@ -418,6 +459,8 @@ def predict_e2e_line(args, device, with_cpu):
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
     t = float(np.median(times))
+    if dump:
+        dump_predict_outputs(dump, dets)
     with torch.no_grad(), torch.autocast("cuda", dtype=dt):
         il, _ = net.transform(images[:2], None, **net._batch_layout())
         _, out = net._features(il.tensors)
@@ -666,7 +709,7 @@ def main():
     if args.mode == "predict":
         if world != 1:
             raise SystemExit("bench.py --mode predict is a single-GPU line (images are independent: run N replicas for N GPUs)")
-        line = predict_e2e_line(args, device, not args.no_cpu_baseline)
+        line = predict_e2e_line(args, device, args.full and not args.no_cpu_baseline, dump=args.dump_outputs)
         line.update({"n_gpus": 1, "higher_is_better": True, "vs_baseline": None, "dtype": args.predict_dtype, "data": "synthetic",
                      "config": {"workload": line["workload"]}})
         print(json.dumps(line), flush=True)
@@ -712,7 +755,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     clocks = None
-    if rank == 0:
+    if rank == 0 and args.full:
         pr = torch.cuda.get_device_properties(local_rank)
         pci = "%04x:%02x:%02x.0" % (getattr(pr, "pci_domain_id", 0), getattr(pr, "pci_bus_id", 0), getattr(pr, "pci_device_id", 0))
         clocks = ClockSampler(pci).start()
@@ -728,15 +771,19 @@ def main():
     gpu_state = clocks.stop() if clocks else None
     final_loss = float(out["loss"])
     graph_replays = stepper.replays
-    # per-kernel figures: the same step, enqueued eagerly with a pair of HIP events around every hand-written kernel (events
-    # recorded inside a captured graph are dependency markers, not timestamps), right after the timed region, same data
-    ops.enable_timing(True)
-    for _ in range(max(args.timing_steps, 1)):
-        stepper._step(images, targets)
-    torch.cuda.synchronize()
-    ev = ops.timing_events() or {}
-    ops.enable_timing(False)
-    timing_steps = max(args.timing_steps, 1)
+    if args.dump_outputs and rank == 0:
+        dump_train_outputs(args.dump_outputs, out, net)      # (before the timing steps below move the parameters again)
+    ev, timing_steps = {}, 0
+    if args.full:
+        # per-kernel figures: the same step, enqueued eagerly with a pair of HIP events around every hand-written kernel (events
+        # recorded inside a captured graph are dependency markers, not timestamps), right after the timed region, same data
+        ops.enable_timing(True)
+        for _ in range(max(args.timing_steps, 1)):
+            stepper._step(images, targets)
+        torch.cuda.synchronize()
+        ev = ops.timing_events() or {}
+        ops.enable_timing(False)
+        timing_steps = max(args.timing_steps, 1)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if world > 1:
@@ -826,22 +873,22 @@ def main():
                                    f"{', GradScaler (scale %g at the end)' % scaler.get_scale() if scaler is not None else ''}; random-init weights",
                        "global_batch": world * args.batch, "parallelism": f"dp{world}", "final_loss": round(final_loss, 4),
                        **({"switches_set": args.set} if args.set else {})},
-            "roofline": roof, "roofline_other": roof_other, "conv_mfma": conv_mfma,
+            **({"roofline": roof, "roofline_other": roof_other, "conv_mfma": conv_mfma} if args.full else {}),
             "rccl_ranks": dist.get_world_size() if (dist.is_initialized() and args.backend == "nccl") else 0,
             "exchange_backend": (args.backend + (" (all ranks on cuda:0)" if args.share_gpu else "")) if dist.is_initialized() else None,
             # the gradient exchange of an N-rank run of this model (stage-aligned 32 MiB fp32 buckets: head + FPN | layer4, layer3 |
             # layer2 .. stem): what travels over xGMI per step and rank -- printed at N = 1 too, where nothing is exchanged
             "exchange_plan": ddp.plan() if ddp is not None else P.BucketedGradAllReduce.plan_for(net, stage_of=retinanet_stage_of),
-            "gpu_state_during_timed_region": gpu_state,
+            **({"gpu_state_during_timed_region": gpu_state} if args.full else {}),
             "step_launch": {"mode": ("4 linear hipGraph segments + eager all-reduces between them" if stepper.segmented else "hipGraph replay") if graph_replays else "eager",
                             "graph_replays_in_run": graph_replays, "buckets": ddp.num_buckets if ddp is not None else 0,
                             "graph_nodes": dict(__import__("pytorch_retinanet_amd.graph", fromlist=["LAST_CENSUS"]).LAST_CENSUS),
-                            "per_kernel_events": f"{timing_steps} eager steps after the timed region"},
+                            **({"per_kernel_events": f"{timing_steps} eager steps after the timed region"} if args.full else {})},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, A, K)
             line["cpu_baseline"]["train_step"] = cpu_train_step_baseline(args)
-        if world == 1 and not args.no_detect:
+        if args.full and world == 1 and not args.no_detect:
             del net, optimizer, stepper
             torch.cuda.empty_cache()
             line["roofline"].update(k3_cold_line(device, args.batch, args.gt, nbytes))

@@ -576,9 +576,46 @@ def gen_traj():
     save("traj.npz", **out)
 
 
+CONV_STACK = dict(num_classes=4, backbone_kind="resnet18", pretrained=False, min_size=96, max_size=128)
+
+
+def weights_sha256(sd) -> str:
+    import hashlib
+    h = hashlib.sha256()
+    for k, v in sd.items():
+        h.update(k.encode() + b"\0" + v.detach().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def gen_conv_stack():
+    """The reference's conv stack with THIS package's default-initialised weights (torch.manual_seed(0)): state-dict keys of the R18
+    and R50 models, transform output, FPN maps and head outputs of two small images in eval mode (models.py:245-262, layers.py), run
+    in fp64 and stored in fp32."""
+    print("[conv_stack]  models.py:245-262 transform + backbone + fpn + head (eval)")
+    import pytorch_retinanet_amd as P
+    torch.manual_seed(0)
+    mine = P.Retinanet(**CONV_STACK).eval()
+    ref = R.Retinanet(**CONV_STACK).eval()
+    assert list(ref.state_dict()) == list(mine.state_dict())
+    ref.load_state_dict(mine.state_dict())
+    ref.double()                                          # (fp64: the stored outputs do not depend on the CPU's conv backend)
+    g = torch.Generator().manual_seed(11)
+    imgs = [torch.rand(3, 96, 120, generator=g).double(), torch.rand(3, 80, 128, generator=g).double()]
+    with torch.no_grad():
+        il, _ = ref.transform(imgs, None)
+        fmaps = ref.fpn(ref.backbone(il.tensors))
+        out = ref.retinanet_head(fmaps)
+    r50 = list(R.Retinanet(backbone_kind="resnet50", pretrained=False).state_dict())
+    save("conv_stack.npz", r18_keys=np.array(list(ref.state_dict())), r50_keys=np.array(r50),
+         weights_sha256=np.array(weights_sha256(mine.state_dict())), image_seed=np.int64(11),
+         images=il.tensors.float().numpy(), image_sizes=np.array([list(s) for s in il.image_sizes], np.int64),
+         cls_preds=out["cls_preds"].float().numpy(), bbox_preds=out["bbox_preds"].float().numpy(),
+         **{f"fpn{i}": f.float().numpy() for i, f in enumerate(fmaps)})
+
+
 if __name__ == "__main__":
     oracle.build()
-    which = sys.argv[1:] or ["anchors", "match", "loss", "decode", "detect", "nms", "transform", "e2e", "e2e_r50", "traj"]
+    which = sys.argv[1:] or ["anchors", "match", "loss", "decode", "detect", "nms", "transform", "e2e", "e2e_r50", "traj", "conv_stack"]
     for w in which:
         globals()["gen_" + w]()
     print("done")

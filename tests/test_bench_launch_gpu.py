@@ -24,7 +24,7 @@ def test_bench_two_ranks_through_self_launch_on_one_gpu(amp):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "2", "--warmup", "3",
-           "--no-cpu-baseline", "--no-detect", "--timing-steps", "1", "--amp", amp]      # (a gloo step moves 153 MB through the host: ~7 s)
+           "--no-cpu-baseline", "--no-detect", "--timing-steps", "1", "--amp", amp, "--full"]      # (a gloo step moves 153 MB through the host: ~7 s)
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1800)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.strip().splitlines() if l.strip()]
@@ -52,7 +52,7 @@ def test_bench_fp16_matcher_stress_line_with_the_cpu_baseline():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--amp", "fp16", "--gt", "500", "--steps", "3", "--warmup", "3", "--no-detect",
-           "--cpu-baseline-reps", "2", "--timing-steps", "1"]
+           "--cpu-baseline-reps", "2", "--timing-steps", "1", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=2400)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.strip()][-1])

@@ -8,6 +8,6 @@ rm -rf $db; mkdir -p $db
 cp pytorch_retinanet_amd/miopen_db/* $db/
 export MIOPEN_USER_DB_PATH=$db
 t0=$(date +%s)
-python bench.py --steps 3 --warmup 2 --no-cpu-baseline | tail -1 | cut -c1-200
+python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline | tail -1 | cut -c1-200
 echo "find + bench took $(( $(date +%s) - t0 )) s"
 ls -la $db
