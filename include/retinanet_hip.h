@@ -474,6 +474,21 @@ int rn_conv3x3_narrow_forward(const void *x, const void *w, const float *bias, v
 /* n device-to-device copies (dsts[i] <- srcs[i], nbytes[i] bytes, non-overlapping) in one launch per 64: the inputs of a step
  * into the static buffers of its captured hipGraph (graph.CapturedTrainStep).  srcs / dsts / nbytes are HOST arrays. */
 int rn_copy_many(const void *const *srcs, void *const *dsts, const int64_t *nbytes, int n, void *stream);
+
+/* ---- ragged GT into fixed-size buffers (graph.CapturedTrainStep, GT capacity mode) ----------------------------------------------
+ * rn_gt_stage: the per-image boxes f32 [counts[b]][4] (16-byte aligned) and labels i64 [counts[b]] (8-byte aligned) of B images
+ * into gt_boxes [rows][4] / gt_labels [rows], packed in image order; gt_off [B+1] = prefix of counts, num_fg [B] = 0.  One launch
+ * per 64 images; boxes / labels / counts are HOST arrays (device pointers, passed by value).  Exactly counts[b] rows of each
+ * source are read; rows [sum counts, rows) of the outputs are left untouched.  A count of 0 may come with null pointers.
+ * RN_EINVAL (nothing launched): a negative count, sum counts > rows, B <= 0, a null pointer behind a non-zero count. */
+int rn_gt_stage(const void *const *boxes, const void *const *labels, const int64_t *counts, int B, float *gt_boxes,
+                int64_t *gt_labels, int64_t rows, int32_t *gt_off, int32_t *num_fg, void *stream);
+/* rn_gt_scale_packed: out_boxes[r] = gt_boxes[r] * (rw, rh, rw, rh) for every row r of image b (gt_off, device), fp32 multiplies:
+ * bit-identical to transform.resize_boxes.  ratios: HOST float[2B] = (rh, rw) per image.  Out of place (out_boxes == gt_boxes:
+ * RN_EINVAL); rows outside [gt_off[0], gt_off[B]) of out_boxes are not written.  max_per_image: launch-size hint (an upper
+ * bound is best; any value is correct). */
+int rn_gt_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *ratios, int B, int64_t rows,
+                       int64_t max_per_image, void *stream);
 /* n widening copies dsts[i] (f32) <- srcs[i] (src_dtype: RN_BF16 or RN_F16), counts[i] elements each, one launch per 64: the
  * gather of 16-bit parameter gradients into the fp32 buckets of the gradient exchange (no reference analogue: Lightning's DDP
  * exchanges fp32 gradients of fp32 parameters).  HOST arrays. */

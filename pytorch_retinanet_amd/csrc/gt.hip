@@ -1,0 +1,138 @@
+// Ragged ground truth into fixed-size device buffers (graph.CapturedTrainStep's GT capacity mode).
+//
+// A captured train step reads its GT from static buffers: gt_boxes [R][4], gt_labels [R], gt_off [B+1], num_fg [B].  With a
+// capacity class per entry (R = B x class) one graph serves every batch whose per-image box counts fit; what changes from batch
+// to batch is written here, outside the graph, by ONE launch per 64 images:
+//   rn_gt_stage         gathers the per-image boxes / labels (the user's tensors, pointers and counts passed BY VALUE in the kernel
+//                       argument table, like rn_copy_many), writes gt_off as the prefix of those counts and clears num_fg --
+//                       no host->device copy from pageable memory, no memset node, no synchronisation;
+//   rn_gt_scale_packed  the transform's per-image box resize (transform.resize_boxes: fp32 multiply by the fp32 ratio) on a packed
+//                       buffer, out of place: inside a graph only the device knows which row belongs to which image (gt_off).
+// Both kernels index their argument tables by blockIdx only (a per-lane index into the argument segment becomes a vector load of
+// the table; CHANGELOG, the compiler's treatment of hand-written loops, item 2).
+#include "rn_common.hpp"
+
+namespace {
+
+constexpr int GT_MAX = 64;          // images per launch
+constexpr int GT_BLOCK = 256;
+constexpr int GT_GRID_X = 64;       // row blocks per image at most (a grid-stride loop covers the rest)
+
+struct StageTable {
+    const rn::f32x4 *boxes[GT_MAX];
+    const int64_t *labels[GT_MAX];
+    int32_t count[GT_MAX];
+    int32_t off[GT_MAX];
+};
+
+__global__ __launch_bounds__(GT_BLOCK) void gt_stage_kernel(const StageTable t, rn::f32x4 *__restrict__ gt_boxes,
+                                                           int64_t *__restrict__ gt_labels, int32_t *__restrict__ gt_off,
+                                                           int32_t *__restrict__ num_fg, int base, int last, int32_t end)
+{
+    const int i = blockIdx.y;
+    const rn::f32x4 *__restrict__ sb = t.boxes[i];
+    const int64_t *__restrict__ sl = t.labels[i];
+    const int32_t n = t.count[i], o = t.off[i];
+    // exactly n rows of each source: a one-box label tensor is 8 bytes, so labels go one int64 per lane (no 16-byte pairs)
+    for (int32_t r = (int32_t)blockIdx.x * GT_BLOCK + (int32_t)threadIdx.x; r < n; r += (int32_t)gridDim.x * GT_BLOCK) {
+        gt_boxes[o + r] = sb[r];
+        gt_labels[o + r] = sl[r];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        gt_off[base + i] = o;
+        num_fg[base + i] = 0;
+        if (last && i == (int)gridDim.y - 1) gt_off[base + i + 1] = end;
+    }
+}
+
+struct ScaleTable { float rh[GT_MAX]; float rw[GT_MAX]; };
+
+__global__ __launch_bounds__(GT_BLOCK) void gt_scale_kernel(const ScaleTable t, const rn::f32x4 *__restrict__ in, rn::f32x4 *__restrict__ out,
+                                                           const int32_t *__restrict__ gt_off, int base, int32_t rows)
+{
+    const int i = blockIdx.y;
+    const float rh = t.rh[i], rw = t.rw[i];
+    int32_t lo = gt_off[base + i], hi = gt_off[base + i + 1];
+    // (gt_off is device data: the row range is clamped to the buffer, whatever it holds)
+    lo = lo < 0 ? 0 : (lo > rows ? rows : lo);
+    hi = hi < lo ? lo : (hi > rows ? rows : hi);
+    for (int32_t r = lo + (int32_t)blockIdx.x * GT_BLOCK + (int32_t)threadIdx.x; r < hi; r += (int32_t)gridDim.x * GT_BLOCK) {
+        const rn::f32x4 b = in[r];
+        out[r] = rn::f32x4{b.x * rw, b.y * rh, b.z * rw, b.w * rh};
+    }
+}
+
+int grid_x(int64_t rows_per_image)
+{
+    int64_t bx = (rows_per_image + GT_BLOCK - 1) / GT_BLOCK;
+    return (int)(bx < 1 ? 1 : (bx > GT_GRID_X ? GT_GRID_X : bx));
+}
+
+}  // namespace
+
+RN_API int rn_gt_stage(const void *const *boxes, const void *const *labels, const int64_t *counts, int B, float *gt_boxes,
+                       int64_t *gt_labels, int64_t rows, int32_t *gt_off, int32_t *num_fg, void *stream)
+{
+    if (!boxes || !labels || !counts || B <= 0 || rows < 0 || !gt_off || !num_fg) return RN_EINVAL;
+    if (rows > 0 && (!gt_boxes || !gt_labels)) return RN_EINVAL;
+    if (!rn::aligned(gt_off, 4) || !rn::aligned(num_fg, 4) || (gt_boxes && !rn::aligned(gt_boxes, 16)) || (gt_labels && !rn::aligned(gt_labels, 8)))
+        return RN_EALIGN;
+    // every argument is checked before anything is launched: a rejected call leaves the buffers as they were
+    int64_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t c = counts[b];
+        if (c < 0) return RN_EINVAL;
+        if (c > 0) {
+            if (!boxes[b] || !labels[b]) return RN_EINVAL;
+            if (!rn::aligned(boxes[b], 16) || !rn::aligned(labels[b], 8)) return RN_EALIGN;
+        }
+        total += c;
+        if (total > rows) return RN_EINVAL;
+    }
+    if (total > INT32_MAX) return RN_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    int64_t off = 0;
+    for (int base = 0; base < B; base += GT_MAX) {
+        const int cnt = (B - base) < GT_MAX ? (B - base) : GT_MAX;
+        StageTable t;
+        int64_t most = 0;
+        for (int i = 0; i < GT_MAX; ++i) {
+            const bool on = i < cnt;
+            const int64_t c = on ? counts[base + i] : 0;
+            t.boxes[i] = on && c ? (const rn::f32x4 *)boxes[base + i] : nullptr;
+            t.labels[i] = on && c ? (const int64_t *)labels[base + i] : nullptr;
+            t.count[i] = (int32_t)c;
+            t.off[i] = (int32_t)off;
+            off += c;
+            if (c > most) most = c;
+        }
+        const int last = base + cnt == B;
+        hipLaunchKernelGGL(gt_stage_kernel, dim3((unsigned)grid_x(most), (unsigned)cnt), dim3(GT_BLOCK), 0, st, t, (rn::f32x4 *)gt_boxes,
+                           gt_labels, gt_off, num_fg, base, last, (int32_t)total);
+        RN_LAUNCH_CHECK();
+    }
+    return RN_OK;
+}
+
+RN_API int rn_gt_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *ratios, int B, int64_t rows,
+                              int64_t max_per_image, void *stream)
+{
+    if (!gt_off || !ratios || B <= 0 || rows < 0 || rows > INT32_MAX || max_per_image < 0) return RN_EINVAL;
+    if (rows > 0 && (!gt_boxes || !out_boxes)) return RN_EINVAL;
+    if (rows > 0 && gt_boxes == out_boxes) return RN_EINVAL;           // out of place: a replayed graph would compound an in-place scale
+    if (!rn::aligned(gt_off, 4) || (gt_boxes && !rn::aligned(gt_boxes, 16)) || (out_boxes && !rn::aligned(out_boxes, 16))) return RN_EALIGN;
+    if (rows == 0) return RN_OK;
+    hipStream_t st = (hipStream_t)stream;
+    for (int base = 0; base < B; base += GT_MAX) {
+        const int cnt = (B - base) < GT_MAX ? (B - base) : GT_MAX;
+        ScaleTable t;
+        for (int i = 0; i < GT_MAX; ++i) {
+            t.rh[i] = i < cnt ? ratios[2 * (base + i)] : 1.0f;
+            t.rw[i] = i < cnt ? ratios[2 * (base + i) + 1] : 1.0f;
+        }
+        hipLaunchKernelGGL(gt_scale_kernel, dim3((unsigned)grid_x(max_per_image), (unsigned)cnt), dim3(GT_BLOCK), 0, st, t,
+                           (const rn::f32x4 *)gt_boxes, (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
+        RN_LAUNCH_CHECK();
+    }
+    return RN_OK;
+}

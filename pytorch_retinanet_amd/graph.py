@@ -20,6 +20,14 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
 MIOpen's find, the caches and the optimizer state); the next one captures and replays.  At most ``max_graphs`` signatures
 are kept (least recently used goes first); a capture that fails falls back to eager for that signature.
+
+GT capacity mode (``gt_capacity="auto"`` or a list of classes): real detection data has a different number of boxes in every
+image, so the exact target shapes make nearly every batch a new signature and training never reaches a replay.  With the mode on,
+a batch is keyed by its capacity class -- the smallest class >= its largest per-image box count (``gt_capacity_class``) -- and
+every call, eager ones included, first stages its GT into the entry's fixed-size buffers (``ops.gt_stage``: B x class rows, the
+offsets written on the device); the step then runs on that ``ops.PackedGT``.  The GT kernels read each image's range from the
+device offsets and take the host-side counts only as launch hints, for which the capacity is an upper bound
+(``losses.RetinaNetLosses.forward_levels``).  A batch above the last class keeps the exact-shape key.
 """
 import ctypes as C
 import os
@@ -36,13 +44,53 @@ from .norm import note_raw_write
 
 _log = logging.getLogger(__name__)
 
+GT_CAPACITY_CLASSES = (8, 32, 128, 512)      # gt_capacity="auto"
+
+
+def gt_capacity_classes(value) -> Optional[Tuple[int, ...]]:
+    """``CapturedTrainStep(gt_capacity=...)`` -> the capacity classes: None (off), "auto" (``GT_CAPACITY_CLASSES``) or a strictly
+    increasing sequence of positive ints; ValueError for anything else."""
+    if value is None:
+        return None
+    if isinstance(value, str):
+        if value == "auto":
+            return GT_CAPACITY_CLASSES
+        raise ValueError(f"gt_capacity: expected None, 'auto' or increasing positive ints, got {value!r}")
+    try:
+        classes = tuple(value)
+    except TypeError:
+        raise ValueError(f"gt_capacity: expected None, 'auto' or increasing positive ints, got {value!r}") from None
+    if not classes or any(isinstance(c, bool) or not isinstance(c, int) or c <= 0 for c in classes) \
+            or any(b <= a for a, b in zip(classes, classes[1:])):
+        raise ValueError(f"gt_capacity: expected None, 'auto' or increasing positive ints, got {value!r}")
+    return classes
+
+
+def gt_capacity_class(counts: Sequence[int], classes: Sequence[int]) -> Optional[int]:
+    "The smallest class >= max(counts) (0 for no counts), or None when the largest count exceeds the last class."
+    most = max((int(c) for c in counts), default=0)
+    for c in classes:
+        if most <= c:
+            return int(c)
+    return None
+
+
+def _gt_counts(targets) -> List[int]:
+    return [int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets]
+
+
+def _net_targets(targets):
+    "What the step hands to ``Retinanet.forward``: packed GT as it is, a copy of each target dict otherwise."
+    return targets if isinstance(targets, ops.PackedGT) else [dict(t) for t in targets]
+
 
 class _Entry:
-    __slots__ = ("graph", "images", "targets", "losses", "calls", "failed", "match_state", "segments", "bucket_ids", "pool")
+    __slots__ = ("graph", "images", "targets", "losses", "calls", "failed", "match_state", "segments", "bucket_ids", "pool", "packed")
 
     def __init__(self):
         self.graph, self.images, self.targets, self.losses, self.calls, self.failed, self.match_state = None, None, None, None, 0, False, None
         self.segments, self.bucket_ids, self.pool = None, None, None
+        self.packed = None        # GT capacity mode: this entry's ops.PackedGT (B x class rows), staged before every call
 
 
 class MemsetNodeInGraph(RuntimeError):
@@ -137,14 +185,17 @@ def retinanet_stage_of(name: str) -> int:
 
 class CapturedTrainStep:
     def __init__(self, net, optimizer, ddp=None, amp_dtype: Optional[torch.dtype] = torch.bfloat16, eager_steps: int = 2,
-                 max_graphs: int = 4, enabled: bool = True, segmented: Optional[bool] = None, scaler=None):
+                 max_graphs: int = 4, enabled: bool = True, segmented: Optional[bool] = None, scaler=None, gt_capacity=None):
         """``segmented`` (default: on whenever gradients are exchanged): the step with a gradient exchange as FOUR linear hipGraphs --
         forward + head / FPN backward | layer4, layer3 backward | layer2 .. stem backward | optimizer -- with the finished buckets'
         all-reduces issued EAGERLY on the process group's communication stream between the replays and the wait for them in
         front of the last segment.  Why not one graph: torch's process group runs the collectives on its own stream, a capture
         turns that into forked graph branches, and ROCm replays such a graph slower than Python enqueues the same kernels
         (DESIGN.md section 6); why not eager: ~20 ms of host time per 25 ms step.  The backward pass is cut at C3 / C4 / C5
-        (``backbone.StageCuts``) and run as separate autograd calls, so each segment's capture begins and ends on this thread."""
+        (``backbone.StageCuts``) and run as separate autograd calls, so each segment's capture begins and ends on this thread.
+        ``gt_capacity``: None (default: the exact target shapes are part of the signature), "auto" (classes ``GT_CAPACITY_CLASSES``)
+        or increasing positive ints -- the GT capacity mode of the module docstring."""
+        self.gt_capacity = gt_capacity_classes(gt_capacity)
         self.net, self.optimizer, self.ddp = net, optimizer, ddp
         # fp16 autocast: a torch.amp.GradScaler (the reference's precision=16 run is native AMP, demo.ipynb).  Its scale / growth
         # tracker are device tensors and optim.MasterSGD takes grad_scale / found_inf on the device, so scale -> backward -> step ->
@@ -178,7 +229,7 @@ class CapturedTrainStep:
         try:
             with torch.autocast(images[0].device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None, cache_enabled=False), \
                     grad_prescale(pre):
-                losses = net(list(images), [dict(t) for t in targets])
+                losses = net(list(images), _net_targets(targets))
                 total = losses["classification_loss"] + losses["regression_loss"]
         finally:
             trunk.stage_cuts = None
@@ -227,7 +278,7 @@ class CapturedTrainStep:
         # fp16: the loss kernel multiplies the GradScaler's scale into its gradients before it rounds them to fp16 (losses.grad_prescale)
         pre = scaler_prescale(self.scaler, images[0].device) if images[0].is_cuda else None
         with torch.autocast(dev_type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None, cache_enabled=False), grad_prescale(pre):
-            losses = net(list(images), [dict(t) for t in targets])
+            losses = net(list(images), _net_targets(targets))
             total = losses["classification_loss"] + losses["regression_loss"]
         if self.scaler is not None:
             self.scaler.scale(total).backward()
@@ -251,11 +302,19 @@ class CapturedTrainStep:
         return {"classification_loss": losses["classification_loss"].detach(), "regression_loss": losses["regression_loss"].detach(),
                 "loss": total.detach()}
 
+    def _capacity_of(self, targets) -> Optional[int]:
+        "The batch's capacity class, or None (mode off, or a count above the last class: exact-shape keying)."
+        return None if self.gt_capacity is None else gt_capacity_class(_gt_counts(targets), self.gt_capacity)
+
     def _signature(self, images, targets) -> tuple:
         groups = tuple((g.get("lr"), g.get("momentum"), g.get("weight_decay"), g.get("dampening"), g.get("nesterov"))
                        for g in self.optimizer.param_groups)
         ims = tuple((tuple(im.shape), im.dtype, im.device) for im in images)
-        tgs = tuple(tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in t.items() if isinstance(v, Tensor))) for t in targets)
+        cap = self._capacity_of(targets)
+        if cap is not None:
+            tgs = ("gt_cap", cap)          # (the entry's packed buffers are B x cap rows; B is in the image shapes)
+        else:
+            tgs = tuple(tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in t.items() if isinstance(v, Tensor))) for t in targets)
         mode = tuple(m.training for m in self.net.modules())
         frozen = tuple(p.requires_grad for p in self.net.parameters())       # (freezing / unfreezing layers changes the launch sequence)
         return (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype)
@@ -264,7 +323,8 @@ class CapturedTrainStep:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."
         dev = images[0].device
         e.images = [im.clone() for im in images]
-        e.targets = [{k: (v.clone() if isinstance(v, Tensor) else v) for k, v in t.items()} for t in targets]
+        e.targets = targets if isinstance(targets, ops.PackedGT) else \
+            [{k: (v.clone() if isinstance(v, Tensor) else v) for k, v in t.items()} for t in targets]
         e.match_state = ops.new_match_state(dev)
         e.pool = torch.cuda.graph_pool_handle()
         e.segments, e.bucket_ids = [], []
@@ -345,7 +405,8 @@ class CapturedTrainStep:
         if self.segmented:
             return self._capture_segments(e, images, targets)
         e.images = [im.clone() for im in images]
-        e.targets = [{k: (v.clone() if isinstance(v, Tensor) else v) for k, v in t.items()} for t in targets]
+        e.targets = targets if isinstance(targets, ops.PackedGT) else \
+            [{k: (v.clone() if isinstance(v, Tensor) else v) for k, v in t.items()} for t in targets]
         torch.cuda.synchronize()
         g = _new_graph()
         # the fused loss kernel's state words: zero-filled here, OUTSIDE the capture, and owned by this entry (ops.use_match_state)
@@ -360,14 +421,22 @@ class CapturedTrainStep:
         if not self.enabled or not images or not images[0].is_cuda:
             return self._step(images, targets)
         key = self._signature(images, targets)
+        cap = self._capacity_of(targets)
         e = self._entries.get(key)
         if e is None:
             e = self._entries[key] = _Entry()
+            if cap is not None:
+                e.packed = ops.PackedGT.empty(len(images), cap, images[0].device)
             while len(self._entries) > self.max_graphs:
                 self._entries.popitem(last=False)            # drops the graph and its private memory pool
         else:
             self._entries.move_to_end(key)
         e.calls += 1
+        if e.packed is not None:
+            # GT capacity mode: this batch's GT into the entry's static buffers (one launch, current stream), for eager steps,
+            # the capture and replays alike; the step itself then reads nothing but e.packed
+            ops.gt_stage([t["boxes"] for t in targets], [t["labels"] for t in targets], e.packed)
+            targets = e.packed
         if e.failed or e.calls <= self.eager_steps:
             return self._step(images, targets)
         if e.graph is None and e.segments is None:
@@ -389,7 +458,9 @@ class CapturedTrainStep:
             # the step's inputs into the graph's static buffers: one multi-tensor launch per dtype for what already lives on the
             # device (24 separate copies cost 0.19 ms per step), plain copies for the rest
             dsts, srcs = [], []
-            pairs = list(zip(e.images, images)) + [(dt[k], v) for dt, st in zip(e.targets, targets) for k, v in st.items() if isinstance(v, Tensor)]
+            pairs = list(zip(e.images, images))
+            if e.packed is None:
+                pairs += [(dt[k], v) for dt, st in zip(e.targets, targets) for k, v in st.items() if isinstance(v, Tensor)]
             for dst, src in pairs:
                 if src.device == dst.device and src.dtype == dst.dtype and src.shape == dst.shape and src.is_contiguous() and dst.is_contiguous():
                     dsts.append(dst); srcs.append(src)

@@ -82,6 +82,10 @@ K3_LIST_MIN_GT = 32
 
 
 def k3_form(total_gt: int, B: int) -> int:
+    """The K3 form for ``total_gt`` GT rows over B images.  Packed GT (``ops.PackedGT``, the capture's GT capacity mode) passes its
+    row count R = B x capacity class: the host knows no per-image count there, and any form is exact for any count (the form
+    only decides how the special rows are repaired) -- the classes 8 / 32 / 128 / 512 of ``graph.GT_CAPACITY_CLASSES`` give the
+    chunk form for class 8 and the list form from class 32 on, the rule the measurements above give for images at capacity."""
     if K3_FORM != "auto":
         return int(K3_FORM)
     return ops.LOSS_FORM_LIST if total_gt >= K3_LIST_MIN_GT * max(B, 1) else ops.LOSS_FORM_CHUNKS
@@ -186,6 +190,13 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
         return (None,) * 9 + tuple(outs)
 
 
+def _max_gt_per_image(targets) -> int:
+    "The largest per-image GT count (packed GT: its capacity per image, an upper bound)."
+    if isinstance(targets, ops.PackedGT):
+        return targets.cap_per_image
+    return max([int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets] or [0])
+
+
 def _stack_anchors(anchors) -> Tensor:
     """List of per-image [A,4] tensors -> one shared [A,4] (the usual case: the
     generator hands out the same cached tensor per image) or a stacked [B,A,4]."""
@@ -245,8 +256,9 @@ class RetinaNetLosses(nn.Module):
     @staticmethod
     def fuses_match(targets) -> bool:
         """``RN_FUSE_MATCH=1``: the matcher runs inside the loss kernel (one launch, ``rn_loss_match_fwd_bwd_levels``) when no image has
-        more than 64 GT boxes.  Off by default: measured slower than K2 + K3 (see ``FUSE_MATCH``)."""
-        return FUSE_MATCH and max([int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets] or [0]) <= 64
+        more than 64 GT boxes (packed GT: when its capacity per image is at most 64).  Off by default: measured slower than K2 + K3
+        (see ``FUSE_MATCH``)."""
+        return FUSE_MATCH and _max_gt_per_image(targets) <= 64
 
     def match_ahead(self, targets: List[Dict[str, Tensor]], anchors) -> MatchAhead:
         """Launch K2 (IoU + matcher, box_utils.py:51-80) NOW, on a side stream: it depends only on the anchors and the GT boxes,
@@ -257,14 +269,20 @@ class RetinaNetLosses(nn.Module):
         dev = anchors.device
         h = MatchAhead()
         h.anchors = anchors
-        h.gt_boxes, h.gt_labels, h.gt_off = self._gt_arrays(targets, dev)
-        B = len(targets)
-        h.matches, h.num_fg, h.special = ops.iou_match_outputs(B, int(anchors.shape[-2]), dev)
+        packed = isinstance(targets, ops.PackedGT)
+        if packed:      # the staged arrays as they are; gt_stage zeroed num_fg (no clear launch)
+            h.gt_boxes, h.gt_labels, h.gt_off = targets.gt_boxes, targets.gt_labels, targets.gt_off
+        else:
+            h.gt_boxes, h.gt_labels, h.gt_off = self._gt_arrays(targets, dev)
+        B = targets.B if packed else len(targets)
+        h.matches, h.num_fg, h.special = ops.iou_match_outputs(B, int(anchors.shape[-2]), dev, want_num_fg=not packed)
+        if packed:
+            h.num_fg = targets.num_fg
         main, side = torch.cuda.current_stream(dev), _side_stream(dev)
         side.wait_stream(main)
         with torch.cuda.stream(side):
             ops.iou_match(anchors, h.gt_boxes, h.gt_off, B, IOU_THRESHOLDS_FOREGROUND, IOU_THRESHOLDS_BACKGROUND,
-                          out=(h.matches, h.num_fg, h.special))
+                          out=(h.matches, h.num_fg, h.special), zeroed_num_fg=h.num_fg if packed else None)
             h.done = torch.cuda.Event()
             h.done.record(side)
         # the tensors were allocated on the calling stream but are written / read on the side stream: if the head raises before
@@ -278,15 +296,25 @@ class RetinaNetLosses(nn.Module):
                        anchors, ahead: Optional[MatchAhead] = None) -> Dict[str, Tensor]:
         """Same result as ``forward`` on ``torch.cat(levels, dim=1)``, without materialising the cat
         (the loss kernel reads the per-level conv outputs where they are).  ``ahead``: ``match_ahead``'s
-        handle for these targets / anchors (K2 already in flight on a side stream)."""
+        handle for these targets / anchors (K2 already in flight on a side stream).  ``targets`` may be an ``ops.PackedGT``
+        (``ops.gt_stage``'s buffers; one loss call per staging: K2 adds into its zeroed ``num_fg``)."""
         dev = cls_levels[0].device
+        if isinstance(targets, ops.PackedGT) and targets.B != int(cls_levels[0].shape[0]):
+            raise ValueError(f"packed GT of {targets.B} images for a batch of {int(cls_levels[0].shape[0])}")
         if ahead is not None:
             gt_boxes, gt_labels, gt_off, anchors_t = ahead.gt_boxes, ahead.gt_labels, ahead.gt_off, ahead.anchors
+        elif isinstance(targets, ops.PackedGT):
+            # packed GT (graph.CapturedTrainStep's capacity mode): the staged arrays as they are.  Every host-side GT figure is an
+            # upper bound here: K2's kernel choice sees R rows (ops.iou_match passes gt_boxes.shape[0]), K3's form comes from R
+            # (k3_form), the fused form's max_gt is the capacity per image; the kernels read each image's range from gt_off
+            gt_boxes, gt_labels, gt_off = targets.gt_boxes, targets.gt_labels, targets.gt_off
+            anchors_t = _stack_anchors(anchors)
+            ahead = targets.cap_per_image if (cls_levels[0].is_cuda and self.fuses_match(targets)) else GtPack(targets.num_fg)
         else:
             gt_boxes, gt_labels, gt_off, nfg0 = ops.gt_pack([t["boxes"] for t in targets], [t["labels"] for t in targets], dev)
             anchors_t = _stack_anchors(anchors)
             if cls_levels[0].is_cuda and self.fuses_match(targets):
-                ahead = max([int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets] or [0])      # (an int: see the Function)
+                ahead = _max_gt_per_image(targets)      # (an int: see the Function)
             elif nfg0 is not None:
                 ahead = GtPack(nfg0)
         out = _FusedDenseHeadLossLevels.apply(anchors_t, gt_boxes, gt_labels, gt_off, self._params(),
@@ -303,6 +331,9 @@ class RetinaNetLosses(nn.Module):
     def forward(self, targets: List[Dict[str, Tensor]], head_outputs: Dict[str, Tensor],
                 anchors: List[Tensor]) -> Dict[str, Tensor]:
         "Batch means of the per-image normalised losses (losses.py:113-145)."
+        if isinstance(targets, ops.PackedGT):
+            raise TypeError("RetinaNetLosses.forward / compute_loss take the reference's list of target dicts; packed GT (ops.PackedGT) "
+                            "goes through Retinanet.forward or RetinaNetLosses.forward_levels")
         clas_preds, bbox_preds = head_outputs["cls_preds"], head_outputs["bbox_preds"]
         if len(targets) != clas_preds.shape[0]:
             raise ValueError(f"{len(targets)} targets for a batch of {clas_preds.shape[0]}")

@@ -197,12 +197,18 @@ class SimpleTrainer:
     reaches a monitoring scheduler.  Validation runs in ``eval()`` mode like Lightning's (BN buffers untouched)."""
 
     def __init__(self, max_epochs: int = 1, device: Optional[str] = None, precision: str = "bf16",
-                 channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True):
+                 channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True,
+                 gt_capacity=None):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, no scheduler that changes the learning rate every step (a
         scalar passed by value is part of a graph's signature: each new value would re-capture).  Batches of a new shape run
-        eagerly twice, then replay; the results are the eager step's (``tests/test_graph_gpu.py``)."""
+        eagerly twice, then replay; the results are the eager step's (``tests/test_graph_gpu.py``).  ``gt_capacity``: passed to the
+        ``CapturedTrainStep`` -- "auto" keys batches by GT capacity class instead of by their exact box counts, so data with a
+        different number of boxes per image still replays (None: exact keying)."""
+        from .graph import gt_capacity_classes
+        gt_capacity_classes(gt_capacity)                  # (bad values fail here, not at the first step)
+        self.gt_capacity = gt_capacity
         self.max_epochs, self.max_steps, self.log_every, self.capture = max_epochs, max_steps, log_every, capture
         self.captured_steps = 0
         self.device = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
@@ -235,7 +241,7 @@ class SimpleTrainer:
         if (self.capture and self.device.type == "cuda" and ddp is None and type(model).training_step is RetinaNetModel.training_step
                 and not any(s["interval"] == "step" and "monitor" not in s for s in schedulers)):
             from .graph import CapturedTrainStep
-            stepper = CapturedTrainStep(model.net, optimizer, None, amp_dtype=self.amp_dtype, scaler=scaler)
+            stepper = CapturedTrainStep(model.net, optimizer, None, amp_dtype=self.amp_dtype, scaler=scaler, gt_capacity=self.gt_capacity)
         step = 0
         for epoch in range(self.max_epochs):
             model.train()

@@ -120,7 +120,8 @@ class Retinanet(nn.Module):
     def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None):
         """Losses of the batch (models.py:274-288).  The reference requires `targets`
         (its Lightning wrapper's ``forward`` therefore raises); here
-        ``targets=None`` means inference and returns ``predict(images)``."""
+        ``targets=None`` means inference and returns ``predict(images)``.  ``targets`` may also be packed GT
+        (``ops.PackedGT``, staged by ``ops.gt_stage``: the GT capacity mode of ``graph.CapturedTrainStep``)."""
         if targets is None:
             return self.predict(images)
         images, targets = self.transform(images, targets, **self._batch_layout())

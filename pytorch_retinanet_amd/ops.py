@@ -93,6 +93,12 @@ def _c(t: Tensor) -> Tensor:
     return t
 
 
+def _aligned(t: Tensor, align: int) -> Tensor:
+    "Dense, base pointer a multiple of ``align`` bytes (copied otherwise)."
+    t = t.contiguous()
+    return t.clone() if t.numel() and t.data_ptr() % align else t
+
+
 def _anchor_args(anchors: Tensor, B: int, A: int) -> Tuple[Tensor, int]:
     """anchors [A,4] shared or [B,A,4] per image -> (contiguous fp32 tensor, batch stride in elements)."""
     anchors = _c(anchors)
@@ -184,6 +190,69 @@ def gt_pack(boxes: Sequence[Tensor], labels: Sequence[Tensor], dev: torch.device
     with torch.cuda.device(dev), _timed("gt_pack", dev):
         check(lib.rn_copy_many((C.c_void_p * n)(*srcs), (C.c_void_p * n)(*dsts), (C.c_int64 * n)(*nb), n, _stream(dev)), "rn_copy_many")
     return gt_boxes, gt_labels, gt_off, num_fg
+
+
+class PackedGT:
+    """The GT of a batch in fixed-size device buffers (``graph.CapturedTrainStep``'s GT capacity mode): ``gt_boxes`` f32 [rows, 4],
+    ``gt_labels`` i64 [rows], ``gt_off`` i32 [B + 1] and a zeroed ``num_fg`` i32 [B], as ``gt_stage`` writes them.  Only the device
+    knows the per-image counts; the host knows the bounds: ``rows`` (R) and ``cap_per_image`` (no image has more boxes).  Rows
+    [gt_off[B], rows) hold whatever they held before: no kernel reads them."""
+    __slots__ = ("gt_boxes", "gt_labels", "gt_off", "num_fg", "rows", "cap_per_image", "B")
+
+    def __init__(self, gt_boxes: Tensor, gt_labels: Tensor, gt_off: Tensor, num_fg: Tensor, cap_per_image: int):
+        self.gt_boxes, self.gt_labels, self.gt_off, self.num_fg = gt_boxes, gt_labels, gt_off, num_fg
+        self.rows, self.B, self.cap_per_image = int(gt_boxes.shape[0]), int(num_fg.shape[0]), int(cap_per_image)
+
+    @classmethod
+    def empty(cls, B: int, cap_per_image: int, dev: torch.device) -> "PackedGT":
+        "Buffers for B images of at most ``cap_per_image`` boxes each (uninitialised: ``gt_stage`` fills them)."
+        R = B * cap_per_image
+        return cls(torch.empty((R, 4), dtype=torch.float32, device=dev), torch.empty((R,), dtype=torch.int64, device=dev),
+                   torch.empty((B + 1,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev), cap_per_image)
+
+    def with_boxes(self, gt_boxes: Tensor) -> "PackedGT":
+        return PackedGT(gt_boxes, self.gt_labels, self.gt_off, self.num_fg, self.cap_per_image)
+
+
+def gt_stage(boxes: Sequence[Tensor], labels: Sequence[Tensor], out: PackedGT) -> PackedGT:
+    """The per-image GT (``boxes[b]`` [T_b, 4], ``labels[b]`` [T_b]) into ``out``'s buffers, ``gt_off`` = prefix of the counts,
+    ``num_fg`` = 0: one launch per 64 images (``rn_gt_stage``) on the current stream; no host copy, no synchronisation.  Tensors that
+    are not contiguous, aligned f32 / i64 tensors on ``out``'s device are converted first.  ValueError when the batch does not fit."""
+    dev = out.gt_off.device
+    B = len(boxes)
+    if B != out.B or len(labels) != B:
+        raise ValueError(f"{B} box / {len(labels)} label tensors for packed GT of {out.B} images")
+    bs, ls, counts = [], [], []
+    for b, l in zip(boxes, labels):
+        b, l = b.reshape(-1, 4), l.reshape(-1)
+        if b.shape[0] != l.shape[0]:
+            raise ValueError(f"{b.shape[0]} boxes but {l.shape[0]} labels in one image")
+        if b.shape[0] > out.cap_per_image:
+            raise ValueError(f"an image with {b.shape[0]} boxes does not fit packed GT of {out.cap_per_image} per image")
+        bs.append(_aligned(b.to(device=dev, dtype=torch.float32), 16))
+        ls.append(_aligned(l.to(device=dev, dtype=torch.int64), 8))
+        counts.append(int(b.shape[0]))
+    n = len(counts)
+    with torch.cuda.device(dev), _timed("gt_stage", dev):
+        check(lib.rn_gt_stage((C.c_void_p * n)(*[_ptr(t).value for t in bs]), (C.c_void_p * n)(*[_ptr(t).value for t in ls]),
+                              (C.c_int64 * n)(*counts), n, _ptr(out.gt_boxes), _ptr(out.gt_labels), out.rows, _ptr(out.gt_off),
+                              _ptr(out.num_fg), _stream(dev)), "rn_gt_stage")
+    return out
+
+
+def gt_scale_packed(gt: PackedGT, ratios: Sequence[Tuple[float, float]]) -> PackedGT:
+    """``transform.resize_boxes`` on packed GT, out of place: image b's rows times (rw, rh, rw, rh), ``ratios[b]`` = (rh, rw) fp32
+    values (bit-identical to the per-image path).  -> a PackedGT sharing labels / offsets / num_fg with ``gt``, boxes in a fresh
+    buffer (rows outside the images' ranges unwritten)."""
+    dev = _need_dev(gt.gt_boxes, gt.gt_off)
+    if len(ratios) != gt.B:
+        raise ValueError(f"{len(ratios)} ratio pairs for packed GT of {gt.B} images")
+    out = torch.empty_like(gt.gt_boxes)
+    flat = [float(v) for r in ratios for v in r]
+    with torch.cuda.device(dev), _timed("gt_scale_packed", dev):
+        check(lib.rn_gt_scale_packed(_ptr(gt.gt_boxes), _ptr(out), _ptr(gt.gt_off), (C.c_float * len(flat))(*flat), gt.B, gt.rows,
+                                     gt.cap_per_image, _stream(dev)), "rn_gt_scale_packed")
+    return gt.with_boxes(out)
 
 
 def iou_match(anchors: Tensor, gt_boxes: Tensor, gt_off: Tensor, B: int, fg_thr: float, bg_thr: float,

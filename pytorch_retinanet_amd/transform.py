@@ -36,10 +36,30 @@ class ImageList(object):
         return ImageList(self.tensors.to(device), self.image_sizes)
 
 
-def resize_boxes(boxes: Tensor, original_size: Sequence[int], new_size: Sequence[int]) -> Tensor:
+def _ratios(original_size: Sequence[int], new_size: Sequence[int]) -> Tuple[float, float]:
     # fp32 ratios (as torchvision computes them), applied as host scalars: no H2D copy, no sync
-    rh = float(np.float32(new_size[0]) / np.float32(original_size[0]))
-    rw = float(np.float32(new_size[1]) / np.float32(original_size[1]))
+    return (float(np.float32(new_size[0]) / np.float32(original_size[0])), float(np.float32(new_size[1]) / np.float32(original_size[1])))
+
+
+def _resize_packed(targets, ratios: List[Tuple[float, float]]):
+    """``resize_boxes`` for every image of packed GT (``ops.PackedGT``): one ``rn_gt_scale_packed`` launch into a buffer owned by this
+    call -- never in place on the staged buffer, which a replayed graph reads again at the next step -- or ``targets`` itself when
+    no ratio differs from 1."""
+    if all(r == (1.0, 1.0) for r in ratios):
+        return targets
+    from . import ops
+    return ops.gt_scale_packed(targets, ratios)
+
+
+def _is_packed(targets) -> bool:
+    if targets is None or isinstance(targets, (list, tuple)):
+        return False
+    from .ops import PackedGT
+    return isinstance(targets, PackedGT)
+
+
+def resize_boxes(boxes: Tensor, original_size: Sequence[int], new_size: Sequence[int]) -> Tensor:
+    rh, rw = _ratios(original_size, new_size)
     if rh == 1.0 and rw == 1.0:
         return boxes
     x1, y1, x2, y2 = boxes.unbind(1)
@@ -109,14 +129,19 @@ class GeneralizedRCNNTransform(nn.Module):
 
     def _forward_fused(self, images: List[Tensor], targets, out_dtype: torch.dtype, channels_last: bool):
         from . import ops                       # the HIP library is only needed once a CUDA image shows up
-        sizes = []
+        sizes, ratios = [], []
+        packed = _is_packed(targets)
         for i, im in enumerate(images):
             h, w = int(im.shape[-2]), int(im.shape[-1])
             scale = self._scale_for(h, w, self._target_short_side())       # drawn per image, like torchvision
             new = (int(math.floor(h * scale)), int(math.floor(w * scale)))
             sizes.append(new)
-            if targets is not None:
+            if packed:
+                ratios.append(_ratios((h, w), new))
+            elif targets is not None:
                 targets[i]["boxes"] = resize_boxes(targets[i]["boxes"], (h, w), new)
+        if packed:
+            targets = _resize_packed(targets, ratios)
         d = float(self.size_divisible)
         hp = int(math.ceil(max(s[0] for s in sizes) / d) * d)
         wp = int(math.ceil(max(s[1] for s in sizes) / d) * d)
@@ -127,23 +152,34 @@ class GeneralizedRCNNTransform(nn.Module):
     def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None,
                 out_dtype: Optional[torch.dtype] = None, channels_last: bool = False):
         """``out_dtype`` / ``channels_last``: layout hints for the fused CUDA path (defaults: fp32, NCHW --
-        what torchvision's transform returns); ignored by the PyTorch fallback."""
+        what torchvision's transform returns); ignored by the PyTorch fallback.  ``targets`` may be packed GT (``ops.PackedGT``):
+        its boxes are rescaled per image on the device (``rn_gt_scale_packed``) and a PackedGT comes back."""
         images = list(images)
-        if targets is not None:
+        packed = _is_packed(targets)
+        if packed:
+            if targets.B != len(images):
+                raise ValueError(f"packed GT of {targets.B} images for {len(images)} images")
+        elif targets is not None:
             targets = [dict(t) for t in targets]
         for im in images:
             if im.dim() != 3:
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(im.shape)}")
         if self._fusable(images):
             return self._forward_fused(images, targets, out_dtype or torch.float32, channels_last)
+        ratios = []
         for i, im in enumerate(images):
             if im.dim() != 3:
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(im.shape)}")
-            tgt = targets[i] if targets is not None else None
+            tgt = targets[i] if (targets is not None and not packed) else None
+            hw = (int(im.shape[-2]), int(im.shape[-1]))
             im, tgt = self.resize(self.normalize(im), tgt)
             images[i] = im
+            if packed:
+                ratios.append(_ratios(hw, im.shape[-2:]))
             if tgt is not None:
                 targets[i] = tgt
+        if packed:
+            targets = _resize_packed(targets, ratios)
         sizes = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
         return ImageList(self.batch_images(images), sizes), targets
 

@@ -5,8 +5,10 @@ mapping and the GPU raises a memory access fault (the process aborts) instead of
 ``stem_fwd_kernel`` -- a wave of the last workgroup that owns no tile loaded at a tile index past the last image.
 
 usage: guard_probe.py stem B H W | w3 N H W C | n3 N H W | dense | pw | pool | bottleneck | step KIND MIN MAX | detect DT B H W K [MEAN] |
-       loss DT B H W K T                                                                    (driven by tests/test_guard_gpu.py)
+       loss DT B H W K T | gt                                                               (driven by tests/test_guard_gpu.py;
+       gt: by tests/test_gt_capacity_gpu.py)
 Prints one "ok ..." line per case; a fault kills the process (non-zero exit status, no "ok" line for the case)."""
+import ctypes as C
 import os
 import sys
 
@@ -222,6 +224,42 @@ def main() -> None:
             torch.cuda.synchronize()
             assert out is None or (torch.equal(out[0], loss) and torch.equal(out[4], m))
         print("ok loss", sys.argv[2], B, H, W, K, T, [float(x) for x in loss], flush=True)
+    elif which == "gt":
+        # rn_gt_stage + rn_gt_scale_packed (csrc/gt.hip): every per-image box / label tensor, the packed outputs and the offsets end
+        # EXACTLY at the end of their mappings (a 1-box label tensor is 8 bytes: a 16-byte read of it would fault); B = 70: two launches
+        from pytorch_retinanet_amd import ops
+
+        def exact_end(n: int, dtype, fill=0x7f):
+            nbytes = max(n, 1) * dtype.itemsize
+            tot = (nbytes + GRAN - 1) // GRAN * GRAN
+            base = torch.empty((tot,), dtype=torch.uint8, device=DEV)
+            base.fill_(fill)
+            _KEEP.append(base)
+            return base[tot - n * dtype.itemsize:].view(dtype)
+        B, cap = 70, 9
+        counts = [(i * 7) % (cap + 1) for i in range(B)]
+        counts[3], counts[B - 1] = 1, 1
+        g = torch.Generator(device=DEV).manual_seed(4)
+        boxes, labels = [], []
+        for c in counts:
+            b = exact_end(4 * c, torch.float32).view(c, 4); b.copy_(torch.rand((c, 4), device=DEV, generator=g) * 500)
+            l = exact_end(c, torch.int64); l.copy_(torch.randint(1, 90, (c,), device=DEV, generator=g))
+            boxes.append(b); labels.append(l)
+        R = B * cap
+        out = ops.PackedGT(exact_end(4 * R, torch.float32).view(R, 4), exact_end(R, torch.int64), exact_end(B + 1, torch.int32),
+                           exact_end(B, torch.int32), cap)
+        ops.gt_stage(boxes, labels, out)
+        ratios = [(1.5, 0.75) if i % 2 else (1.0, 2.0) for i in range(B)]
+        dst = exact_end(4 * R, torch.float32).view(R, 4)
+        check(lib.rn_gt_scale_packed(out.gt_boxes.data_ptr(), dst.data_ptr(), out.gt_off.data_ptr(),
+                                     (C.c_float * (2 * B))(*[v for r in ratios for v in r]), B, R, cap, st), "rn_gt_scale_packed")
+        torch.cuda.synchronize()
+        n = sum(counts)
+        assert torch.equal(out.gt_boxes[:n], torch.cat(boxes)) and torch.equal(out.gt_labels[:n], torch.cat(labels))
+        assert out.gt_off.tolist() == [sum(counts[:i]) for i in range(B + 1)] and int(out.num_fg.abs().sum()) == 0
+        sc = torch.tensor([[rw, rh, rw, rh] for (rh, rw), c in zip(ratios, counts) for _ in range(c)], device=DEV)
+        assert torch.equal(dst[:n], out.gt_boxes[:n] * sc)
+        print("ok gt", B, cap, n, flush=True)
     else:
         raise SystemExit(f"unknown probe {which!r}")
 
