@@ -730,6 +730,27 @@ int rn_sgd_master_step_ex(float *const *masters, float *const *momenta, const vo
                           const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
                           float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf, void *stream);
 
+/* ---- optimizer step: Adam / AdamW on fp32 masters with a 16-bit working copy, capturable --------------------
+ * hparams: a DEVICE block of RN_ADAM_HPARAMS doubles per parameter group (8-byte aligned) holding lr, beta1, beta2, eps,
+ * weight_decay (written by rn_adam_hparams_set, the host's only way in), the step counter and two per-step scalars.  Nothing
+ * of the update is passed by value, so a captured step follows whatever the host last wrote into the block.
+ * rn_adam_master_step enqueues, per call: one single-wave prologue that -- unless found_inf[0] != 0 -- advances the step
+ * counter and computes step_size = lr / (1 - beta1^step) and sqrt(1 - beta2^step) in double, then one launch per 40 tensors
+ * of the update of torch.optim.Adam (decoupled == 0: L2, g += weight_decay * w) / AdamW (decoupled != 0: w *= 1 - lr *
+ * weight_decay) in torch's single-tensor fp32 order, with the fused multiply-adds of ATen's kernels (csrc/adam.hip):
+ *   m = lerp(m, g, 1 - beta1);  v = beta2 * v + (1 - beta2) * g * g;  w -= step_size * m / (sqrt(v) / sqrt(bc2) + eps)
+ * (HOST arrays of device pointers / element counts).  masters / exp_avgs / exp_avg_sqs f32, 16-byte aligned; params16[i]
+ * (nullable, 8-byte aligned): the 16-bit copy of tensor i (dtype16 = RN_BF16 or RN_F16), rewritten as round(w); when grads16 != 0
+ * the gradient of a tensor WITH a 16-bit copy is dtype16 (8-byte aligned), every other gradient is f32 (16-byte aligned).
+ * grad_scale / found_inf (nullable DEVICE f32 scalars, torch.amp.GradScaler): every gradient is divided by grad_scale[0] first,
+ * and when found_inf[0] != 0 nothing changes -- no parameter, moment or step counter.  No host synchronisation.
+ * rn_adam_hparams_set: one launch writing lr .. weight_decay into the block, and the step counter too when step >= 0. */
+#define RN_ADAM_HPARAMS 16
+int rn_adam_hparams_set(double *hparams, double lr, double beta1, double beta2, double eps, double weight_decay, double step, void *stream);
+int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
+                        void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
+                        double *hparams, const float *grad_scale, const float *found_inf, void *stream);
+
 /* ---- T1 transform (normalise + resize + pad + batch) -------------------------------------------
  * Replaces torchvision's GeneralizedRCNNTransform as the reference runs it at
  * retinanet/models.py:116 (construction), :262 and :279 (calls): per image (x - mean) / std, bilinear

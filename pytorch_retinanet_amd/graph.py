@@ -15,6 +15,9 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
   * every pointer the kernels receive is a static input buffer, a parameter / optimizer state, or memory allocated from
     the graph's private pool during capture (same address at every replay);
   * scalars passed by value (learning rate, momentum, weight decay) are part of the signature: a change re-captures.
+    Optimizers with device-resident hyperparameters (``optim.MasterAdam`` / ``MasterAdamW``: ``_rn_device_hparams``) are the
+    exception: their kernels read lr / betas / eps / weight_decay from device blocks, which ``sync_device_hparams()`` refreshes
+    before every replay, so those values are left out of the signature and a per-step LR schedule replays one graph.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -257,7 +260,7 @@ class CapturedTrainStep:
         if self.scaler is not None:
             self.scaler.step_exchanged(opt, ddp)                  # found_inf from the exchanged buckets: the same on every rank
             self.scaler.update()
-        elif type(opt).__name__ == "MasterSGD":
+        elif getattr(opt, "_rn_master_weights", False):
             opt.step(grads=ddp.grad_views())
         else:
             opt.step()
@@ -293,7 +296,7 @@ class CapturedTrainStep:
         total.backward()
         if ddp is not None:
             ddp.finish()
-            if type(opt).__name__ == "MasterSGD":
+            if getattr(opt, "_rn_master_weights", False):
                 opt.step(grads=ddp.grad_views())
             else:
                 opt.step()
@@ -307,8 +310,13 @@ class CapturedTrainStep:
         return None if self.gt_capacity is None else gt_capacity_class(_gt_counts(targets), self.gt_capacity)
 
     def _signature(self, images, targets) -> tuple:
-        groups = tuple((g.get("lr"), g.get("momentum"), g.get("weight_decay"), g.get("dampening"), g.get("nesterov"))
-                       for g in self.optimizer.param_groups)
+        if getattr(self.optimizer, "_rn_device_hparams", False):
+            # (optim.MasterAdam / MasterAdamW: the kernels read lr / betas / eps / weight_decay from device blocks that
+            # sync_device_hparams() refreshes before every replay -- a per-step LR schedule keeps one graph)
+            groups = ("device_hparams", len(self.optimizer.param_groups))
+        else:
+            groups = tuple((g.get("lr"), g.get("momentum"), g.get("weight_decay"), g.get("dampening"), g.get("nesterov"))
+                           for g in self.optimizer.param_groups)
         ims = tuple((tuple(im.shape), im.dtype, im.device) for im in images)
         cap = self._capacity_of(targets)
         if cap is not None:
@@ -472,6 +480,8 @@ class CapturedTrainStep:
                 check(lib.rn_copy_many((C.c_void_p * n)(*[t.data_ptr() for t in srcs]), (C.c_void_p * n)(*[t.data_ptr() for t in dsts]),
                                        (C.c_int64 * n)(*[t.numel() * t.element_size() for t in dsts]), n,
                                        torch.cuda.current_stream(dsts[0].device).cuda_stream), "rn_copy_many")
+        if getattr(self.optimizer, "_rn_device_hparams", False):
+            self.optimizer.sync_device_hparams()              # the groups' current lr / betas / eps / weight_decay, read by the graph
         if e.segments is not None:
             self._replay_segments(e)
         else:

@@ -128,8 +128,9 @@ class RetinaNetModel(_Base):
     # -- optimisation ----------------------------------------------------------------------------
     def configure_optimizers(self, *args, **kwargs):
         opt_cls = load_obj(self.conf.optimizer.class_name)
-        if getattr(opt_cls, "__name__", "") == "MasterSGD" and next(self.net.parameters()).is_cuda:
-            # optimizer.class_name: pytorch_retinanet_amd.optim.MasterSGD -- SGD on fp32 masters, conv weights held in bf16
+        if getattr(opt_cls, "_rn_master_weights", False) and next(self.net.parameters()).is_cuda:
+            # optimizer.class_name: pytorch_retinanet_amd.optim.MasterSGD / MasterAdam / MasterAdamW -- the update on fp32 masters,
+            # conv weights held in 16 bits
             from .optim import use_16bit_conv_weights
             use_16bit_conv_weights(self.net, getattr(self, "working_dtype", None) or torch.bfloat16)     # (SimpleTrainer sets it from its precision)
         self.optimizer = opt_cls(self.net.parameters(), **dict(self.conf.optimizer.params))
@@ -201,8 +202,10 @@ class SimpleTrainer:
                  gt_capacity=None):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
-        is the plain one: one GPU, ``training_step`` not overridden, no scheduler that changes the learning rate every step (a
-        scalar passed by value is part of a graph's signature: each new value would re-capture).  Batches of a new shape run
+        is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
+        unless the optimizer reads its hyperparameters on the device (``optim.MasterAdam`` / ``MasterAdamW``: the step reads lr
+        from a device block refreshed before each replay).  ``MasterSGD`` and torch's optimizers take lr by value, which is part of
+        a graph's signature: each new value would re-capture, so a per-step schedule runs them eagerly.  Batches of a new shape run
         eagerly twice, then replay; the results are the eager step's (``tests/test_graph_gpu.py``).  ``gt_capacity``: passed to the
         ``CapturedTrainStep`` -- "auto" keys batches by GT capacity class instead of by their exact box counts, so data with a
         different number of boxes per image still replays (None: exact keying)."""
@@ -239,7 +242,8 @@ class SimpleTrainer:
             if (self.amp_dtype == torch.float16 and self.device.type == "cuda") else None
         stepper = None
         if (self.capture and self.device.type == "cuda" and ddp is None and type(model).training_step is RetinaNetModel.training_step
-                and not any(s["interval"] == "step" and "monitor" not in s for s in schedulers)):
+                and (getattr(optimizer, "_rn_device_hparams", False)
+                     or not any(s["interval"] == "step" and "monitor" not in s for s in schedulers))):
             from .graph import CapturedTrainStep
             stepper = CapturedTrainStep(model.net, optimizer, None, amp_dtype=self.amp_dtype, scaler=scaler, gt_capacity=self.gt_capacity)
         step = 0
@@ -273,7 +277,7 @@ class SimpleTrainer:
                         out["loss"].backward()
                         if ddp:
                             ddp.finish()
-                        if ddp and type(optimizer).__name__ == "MasterSGD":
+                        if ddp and getattr(optimizer, "_rn_master_weights", False):
                             optimizer.step(grads=ddp.grad_views())       # fp32 bucket views of the bf16 working copies
                         else:
                             optimizer.step()

@@ -307,14 +307,14 @@ class ExchangeGradScaler(torch.amp.GradScaler):
 
     ``step_exchanged`` takes found_inf from the EXCHANGED buckets (``BucketedGradAllReduce.found_inf``: identical on every rank, so all
     ranks skip or step together and ``update()`` moves every rank's scale the same way -- one scale per step on every rank without a
-    second collective) and steps on the buckets' views.  With ``optim.MasterSGD`` the unscale and the skip happen on the device
-    (``rn_sgd_master_step_ex`` reads scale and flag): nothing synchronises and the whole sequence captures into the optimizer segment of
+    second collective) and steps on the buckets' views.  With ``optim.MasterSGD`` (or ``MasterAdam`` / ``MasterAdamW``) the unscale and the skip happen on the device
+    (``rn_sgd_master_step_ex`` / ``rn_adam_master_step`` read scale and flag): nothing synchronises and the whole sequence captures into the optimizer segment of
     ``graph.CapturedTrainStep``.  Other optimizers: the buckets are unscaled in place and the flag is read on the host, as the stock
     scaler does."""
 
     def step_exchanged(self, optimizer, ddp: BucketedGradAllReduce):
         if not self._enabled:
-            return optimizer.step(grads=ddp.grad_views()) if type(optimizer).__name__ == "MasterSGD" else optimizer.step()
+            return optimizer.step(grads=ddp.grad_views()) if getattr(optimizer, "_rn_master_weights", False) else optimizer.step()
         from torch.amp.grad_scaler import OptState
         self._check_scale_growth_tracker("step_exchanged")
         state = self._per_optimizer_states[id(optimizer)]
@@ -326,7 +326,7 @@ class ExchangeGradScaler(torch.amp.GradScaler):
         if getattr(optimizer, "_step_supports_amp_scaling", False):
             optimizer.grad_scale, optimizer.found_inf = self._scale, found
             try:
-                retval = optimizer.step(grads=ddp.grad_views()) if type(optimizer).__name__ == "MasterSGD" else optimizer.step()
+                retval = optimizer.step(grads=ddp.grad_views()) if getattr(optimizer, "_rn_master_weights", False) else optimizer.step()
             finally:
                 del optimizer.grad_scale, optimizer.found_inf
         else:

@@ -5,8 +5,8 @@ mapping and the GPU raises a memory access fault (the process aborts) instead of
 ``stem_fwd_kernel`` -- a wave of the last workgroup that owns no tile loaded at a tile index past the last image.
 
 usage: guard_probe.py stem B H W | w3 N H W C | n3 N H W | dense | pw | pool | bottleneck | step KIND MIN MAX | detect DT B H W K [MEAN] |
-       loss DT B H W K T | gt                                                               (driven by tests/test_guard_gpu.py;
-       gt: by tests/test_gt_capacity_gpu.py)
+       loss DT B H W K T | gt | adam [bf16|f16]                                             (driven by tests/test_guard_gpu.py;
+       gt: by tests/test_gt_capacity_gpu.py; adam: by tests/test_master_adam_gpu.py)
 Prints one "ok ..." line per case; a fault kills the process (non-zero exit status, no "ok" line for the case)."""
 import ctypes as C
 import os
@@ -260,6 +260,54 @@ def main() -> None:
         sc = torch.tensor([[rw, rh, rw, rh] for (rh, rw), c in zip(ratios, counts) for _ in range(c)], device=DEV)
         assert torch.equal(dst[:n], out.gt_boxes[:n] * sc)
         print("ok gt", B, cap, n, flush=True)
+    elif which == "adam":
+        # rn_adam_master_step (csrc/adam.hip): 45 tensors (two launches of 40 + 5), every master / moment / gradient / 16-bit copy,
+        # the hparams block and the GradScaler scalars at the end of their own mappings; sizes through the scalar tail path.
+        # Three steps against torch.optim.AdamW(foreach=False) on fp32 copies.
+        from pytorch_retinanet_amd._lib import RN_F16
+        sizes = [1, 3, 4, 5, 1023, 4097, 64 * 3 * 7 * 7 + 2] + [(i * 37) % 301 + 1 for i in range(38)]
+        dt = torch.bfloat16 if len(sys.argv) < 3 or sys.argv[2] == "bf16" else torch.float16
+        g = torch.Generator(device=DEV).manual_seed(9)
+
+        def at_end(src: torch.Tensor) -> torch.Tensor:
+            t = raw_at_end(src.numel() * src.element_size()).view(src.dtype)
+            t.copy_(src.reshape(-1))
+            return t
+        n_t = len(sizes)
+        with16 = [i % 3 != 0 for i in range(n_t)]                       # (BN-like plain fp32 tensors between the 16-bit ones)
+        w32 = [torch.randn(n, device=DEV, generator=g) for n in sizes]
+        masters = [at_end(w) for w in w32]
+        p16 = [at_end(w.to(dt)) if h else None for w, h in zip(w32, with16)]
+        ms = [at_end(torch.zeros(n, device=DEV)) for n in sizes]
+        vs = [at_end(torch.zeros(n, device=DEV)) for n in sizes]
+        hp = at_end(torch.zeros(16, dtype=torch.float64, device=DEV))
+        scale, found = at_end(torch.full((1,), 8.0, device=DEV)), at_end(torch.zeros(1, device=DEV))
+        ref = [w.clone().requires_grad_(False) for w in w32]
+        ropt = torch.optim.AdamW([torch.nn.Parameter(r) for r in ref], lr=1e-2, weight_decay=0.1, foreach=False)
+        for step in range(3):
+            lr = 1e-2 * (1.0 + 0.5 * step)
+            gs = [torch.randn(n, device=DEV, generator=g) for n in sizes]
+            gs16 = [x.to(dt) if h else x for x, h in zip(gs, with16)]
+            gd = [at_end(x * 8.0) for x in gs16]                         # (scaled by the GradScaler's 8: exact)
+            check(lib.rn_adam_hparams_set(hp.data_ptr(), lr, 0.9, 0.999, 1e-8, 0.1, -1.0, st), "rn_adam_hparams_set")
+            ptrs = lambda ts: (C.c_void_p * n_t)(*[t.data_ptr() if t is not None else 0 for t in ts])
+            check(lib.rn_adam_master_step(ptrs(masters), ptrs(ms), ptrs(vs), ptrs(gd), ptrs(p16), (C.c_int64 * n_t)(*sizes), n_t, 1,
+                                          RN_F16 if dt == torch.float16 else RN_BF16, 1, hp.data_ptr(), scale.data_ptr(), found.data_ptr(),
+                                          st), "rn_adam_master_step")
+            for prm, x in zip(ropt.param_groups[0]["params"], gs16):
+                prm.grad = x.float()
+            ropt.param_groups[0]["lr"] = lr
+            ropt.step()
+        torch.cuda.synchronize()
+        worst = 0.0
+        for mst, c16, prm in zip(masters, p16, ropt.param_groups[0]["params"]):
+            d = float(((mst - prm.detach()).abs() / (prm.detach().abs() + 1e-4)).max())
+            worst = max(worst, d)
+            if c16 is not None:
+                assert torch.equal(c16, mst.to(dt)), "16-bit copy != round(master)"
+        assert worst < 1e-4, worst
+        assert float(hp[5]) == 3.0, float(hp[5])
+        print("ok adam", str(dt), n_t, f"{worst:.2e}", flush=True)
     else:
         raise SystemExit(f"unknown probe {which!r}")
 
