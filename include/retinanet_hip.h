@@ -489,6 +489,17 @@ int rn_gt_stage(const void *const *boxes, const void *const *labels, const int64
  * bound is best; any value is correct). */
 int rn_gt_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *ratios, int B, int64_t rows,
                        int64_t max_per_image, void *stream);
+/* The box half of the train-time horizontal flip (augment.RandomHorizontalFlip): for image b with flags[b] != 0 (DEVICE uint8[B], written
+ * by rn_hflip_draw) x1' = W_b - x2, x2' = W_b - x1 in fp32 (W_b = the original width), y unchanged, then the resize multiply of
+ * rn_gt_scale_packed -- bit-identical to transform.resize_boxes of the torch-flipped boxes; unflagged images get the resize alone.
+ * widths: HOST float[B]; ratios: HOST float[2B] = (rh, rw).  Both run whatever the ratios are (1 included).
+ * rn_gt_flip_scale_many: the per-image boxes f32 [counts[b]][4] (HOST arrays of device pointers / counts, 16-byte aligned, a count of 0
+ * may come with a null pointer) into out_boxes [rows][4], packed in image order (rows >= sum counts; rows past it are not written); one
+ * launch per 64 images.  rn_gt_flip_scale_packed: rn_gt_scale_packed with the flip, same rules (out of place, gt_off on the device). */
+int rn_gt_flip_scale_many(const void *const *boxes, const int64_t *counts, int B, const float *widths, const float *ratios,
+                          const uint8_t *flags, float *out_boxes, int64_t rows, void *stream);
+int rn_gt_flip_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const float *ratios,
+                            const uint8_t *flags, int B, int64_t rows, int64_t max_per_image, void *stream);
 /* n widening copies dsts[i] (f32) <- srcs[i] (src_dtype: RN_BF16 or RN_F16), counts[i] elements each, one launch per 64: the
  * gather of 16-bit parameter gradients into the fp32 buckets of the gradient exchange (no reference analogue: Lightning's DDP
  * exchanges fp32 gradients of fp32 parameters).  HOST arrays. */
@@ -762,6 +773,20 @@ int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *co
 int rn_transform_batch(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
                        const float mean[3], const float std[3], int Hp, int Wp,
                        void *out, int out_dtype, int channels_last, void *stream);
+/* The same launch with the train-time horizontal flip folded into the gather: image b with flags[b] != 0 (DEVICE uint8[B]) is read
+ * from the mirrored source columns, so its output is bit-identical to rn_transform_batch on img.flip(-1). */
+int rn_transform_batch_flip(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
+                            const float mean[3], const float std[3], int Hp, int Wp,
+                            void *out, int out_dtype, int channels_last, const uint8_t *flags, void *stream);
+
+/* ---- train-time augmentation: the horizontal-flip decision, drawn on the device ------------------------------------
+ * rn_hflip_state: a DEVICE block (8-byte aligned) owned by augment.RandomHorizontalFlip, written by the host outside any capture.
+ * rn_hflip_draw: one single-wave launch writing flags[b] = u(seed, counter, b) < p for every b < B, then counter += 1, where
+ *   z = seed ^ (counter * 0x9E3779B97F4A7C15) ^ ((b + 1) * 0xD1B54A32D192ED03);  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31;  u = (z >> 40) * 2^-24   (uint64 arithmetic, fp32 compare)
+ * so p = 0 never flips and p = 1 always does.  Captured into a hipGraph, every replay draws anew. */
+typedef struct rn_hflip_state { uint64_t seed; int64_t counter; float p; int32_t reserved; } rn_hflip_state;
+int rn_hflip_draw(rn_hflip_state *state, int B, uint8_t *flags, void *stream);
 
 /* ---- K6 nms (op boundary) ---------------------------------------------------
  * Replaces torchvision.ops.nms as called at retinanet/models.py:210, batched over

@@ -8,7 +8,14 @@
 //                       no host->device copy from pageable memory, no memset node, no synchronisation;
 //   rn_gt_scale_packed  the transform's per-image box resize (transform.resize_boxes: fp32 multiply by the fp32 ratio) on a packed
 //                       buffer, out of place: inside a graph only the device knows which row belongs to which image (gt_off).
-// Both kernels index their argument tables by blockIdx only (a per-lane index into the argument segment becomes a vector load of
+//   rn_gt_flip_scale_many / rn_gt_flip_scale_packed
+//                       the same resize after the train-time horizontal flip (augment.RandomHorizontalFlip): for an image whose
+//                       device flag is set, x1' = W - x2, x2' = W - x1 in fp32 (the reference's coco_transforms formula, W = the
+//                       original width), then the ratio multiply.  The _many form reads the user's per-image tensors (pointers
+//                       and counts by value, like rn_gt_stage) and packs them into a fresh buffer; the _packed form is
+//                       rn_gt_scale_packed plus widths and flags.  The flags are device data written by rn_hflip_draw inside the
+//                       same captured step, so the decision never reaches the host.
+// All kernels index their argument tables by blockIdx only (a per-lane index into the argument segment becomes a vector load of
 // the table; CHANGELOG, the compiler's treatment of hand-written loops, item 2).
 #include "rn_common.hpp"
 
@@ -60,6 +67,47 @@ __global__ __launch_bounds__(GT_BLOCK) void gt_scale_kernel(const ScaleTable t, 
         const rn::f32x4 b = in[r];
         out[r] = rn::f32x4{b.x * rw, b.y * rh, b.z * rw, b.w * rh};
     }
+}
+
+__device__ __forceinline__ rn::f32x4 flip_scale(const rn::f32x4 b, const bool flip, const float w, const float rh, const float rw)
+{
+    const float x1 = flip ? w - b.z : b.x, x2 = flip ? w - b.x : b.z;
+    return rn::f32x4{x1 * rw, b.y * rh, x2 * rw, b.w * rh};
+}
+
+struct FlipManyTable {
+    const rn::f32x4 *boxes[GT_MAX];
+    int32_t count[GT_MAX];
+    int32_t off[GT_MAX];
+    float w[GT_MAX], rh[GT_MAX], rw[GT_MAX];
+};
+
+__global__ __launch_bounds__(GT_BLOCK) void gt_flip_scale_many_kernel(const FlipManyTable t, const uint8_t *__restrict__ flags,
+                                                                     rn::f32x4 *__restrict__ out, int base)
+{
+    const int i = blockIdx.y;
+    const rn::f32x4 *__restrict__ sb = t.boxes[i];
+    const int32_t n = t.count[i], o = t.off[i];
+    const float w = t.w[i], rh = t.rh[i], rw = t.rw[i];
+    const bool flip = flags[base + i] != 0;
+    for (int32_t r = (int32_t)blockIdx.x * GT_BLOCK + (int32_t)threadIdx.x; r < n; r += (int32_t)gridDim.x * GT_BLOCK)
+        out[o + r] = flip_scale(sb[r], flip, w, rh, rw);
+}
+
+struct FlipScaleTable { float w[GT_MAX]; float rh[GT_MAX]; float rw[GT_MAX]; };
+
+__global__ __launch_bounds__(GT_BLOCK) void gt_flip_scale_kernel(const FlipScaleTable t, const uint8_t *__restrict__ flags,
+                                                                const rn::f32x4 *__restrict__ in, rn::f32x4 *__restrict__ out,
+                                                                const int32_t *__restrict__ gt_off, int base, int32_t rows)
+{
+    const int i = blockIdx.y;
+    const float w = t.w[i], rh = t.rh[i], rw = t.rw[i];
+    const bool flip = flags[base + i] != 0;
+    int32_t lo = gt_off[base + i], hi = gt_off[base + i + 1];
+    lo = lo < 0 ? 0 : (lo > rows ? rows : lo);
+    hi = hi < lo ? lo : (hi > rows ? rows : hi);
+    for (int32_t r = lo + (int32_t)blockIdx.x * GT_BLOCK + (int32_t)threadIdx.x; r < hi; r += (int32_t)gridDim.x * GT_BLOCK)
+        out[r] = flip_scale(in[r], flip, w, rh, rw);
 }
 
 int grid_x(int64_t rows_per_image)
@@ -131,6 +179,74 @@ RN_API int rn_gt_scale_packed(const float *gt_boxes, float *out_boxes, const int
             t.rw[i] = i < cnt ? ratios[2 * (base + i) + 1] : 1.0f;
         }
         hipLaunchKernelGGL(gt_scale_kernel, dim3((unsigned)grid_x(max_per_image), (unsigned)cnt), dim3(GT_BLOCK), 0, st, t,
+                           (const rn::f32x4 *)gt_boxes, (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
+        RN_LAUNCH_CHECK();
+    }
+    return RN_OK;
+}
+
+RN_API int rn_gt_flip_scale_many(const void *const *boxes, const int64_t *counts, int B, const float *widths, const float *ratios,
+                                 const uint8_t *flags, float *out_boxes, int64_t rows, void *stream)
+{
+    if (!boxes || !counts || !widths || !ratios || !flags || B <= 0 || rows < 0) return RN_EINVAL;
+    if (rows > 0 && !out_boxes) return RN_EINVAL;
+    if (out_boxes && !rn::aligned(out_boxes, 16)) return RN_EALIGN;
+    int64_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t c = counts[b];
+        if (c < 0) return RN_EINVAL;
+        if (c > 0) {
+            if (!boxes[b]) return RN_EINVAL;
+            if (!rn::aligned(boxes[b], 16)) return RN_EALIGN;
+        }
+        total += c;
+        if (total > rows) return RN_EINVAL;
+    }
+    if (total > INT32_MAX) return RN_EINVAL;
+    if (total == 0) return RN_OK;
+    hipStream_t st = (hipStream_t)stream;
+    int64_t off = 0;
+    for (int base = 0; base < B; base += GT_MAX) {
+        const int cnt = (B - base) < GT_MAX ? (B - base) : GT_MAX;
+        FlipManyTable t;
+        int64_t most = 0;
+        for (int i = 0; i < GT_MAX; ++i) {
+            const bool on = i < cnt;
+            const int64_t c = on ? counts[base + i] : 0;
+            t.boxes[i] = on && c ? (const rn::f32x4 *)boxes[base + i] : nullptr;
+            t.count[i] = (int32_t)c;
+            t.off[i] = (int32_t)off;
+            t.w[i] = on ? widths[base + i] : 0.0f;
+            t.rh[i] = on ? ratios[2 * (base + i)] : 1.0f;
+            t.rw[i] = on ? ratios[2 * (base + i) + 1] : 1.0f;
+            off += c;
+            if (c > most) most = c;
+        }
+        hipLaunchKernelGGL(gt_flip_scale_many_kernel, dim3((unsigned)grid_x(most), (unsigned)cnt), dim3(GT_BLOCK), 0, st, t, flags,
+                           (rn::f32x4 *)out_boxes, base);
+        RN_LAUNCH_CHECK();
+    }
+    return RN_OK;
+}
+
+RN_API int rn_gt_flip_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const float *ratios,
+                                   const uint8_t *flags, int B, int64_t rows, int64_t max_per_image, void *stream)
+{
+    if (!gt_off || !widths || !ratios || !flags || B <= 0 || rows < 0 || rows > INT32_MAX || max_per_image < 0) return RN_EINVAL;
+    if (rows > 0 && (!gt_boxes || !out_boxes)) return RN_EINVAL;
+    if (rows > 0 && gt_boxes == out_boxes) return RN_EINVAL;
+    if (!rn::aligned(gt_off, 4) || (gt_boxes && !rn::aligned(gt_boxes, 16)) || (out_boxes && !rn::aligned(out_boxes, 16))) return RN_EALIGN;
+    if (rows == 0) return RN_OK;
+    hipStream_t st = (hipStream_t)stream;
+    for (int base = 0; base < B; base += GT_MAX) {
+        const int cnt = (B - base) < GT_MAX ? (B - base) : GT_MAX;
+        FlipScaleTable t;
+        for (int i = 0; i < GT_MAX; ++i) {
+            t.w[i] = i < cnt ? widths[base + i] : 0.0f;
+            t.rh[i] = i < cnt ? ratios[2 * (base + i)] : 1.0f;
+            t.rw[i] = i < cnt ? ratios[2 * (base + i) + 1] : 1.0f;
+        }
+        hipLaunchKernelGGL(gt_flip_scale_kernel, dim3((unsigned)grid_x(max_per_image), (unsigned)cnt), dim3(GT_BLOCK), 0, st, t, flags,
                            (const rn::f32x4 *)gt_boxes, (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
         RN_LAUNCH_CHECK();
     }

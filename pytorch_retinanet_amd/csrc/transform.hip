@@ -16,6 +16,10 @@
 // Each thread produces 4 consecutive x of one row for all 3 channels, so every output layout gets
 // 8- or 16-byte stores: NCHW (f32: 3 x 16 B, 16-bit: 3 x 8 B) or channels-last NHWC (f32: 3 x 16 B,
 // 16-bit: 3 x 8 B contiguous).
+//
+// rn_transform_batch_flip is the same launch with a per-image flag (device, uint8[B], rn_hflip_draw writes it inside a captured
+// step): a flagged image's taps are computed as above and then read from the mirrored source columns iw-1-xa / iw-1-xb, i.e.
+// exactly what rn_transform_batch computes on img.flip(-1) (the reference flips the raw image before the model's transform).
 #include "rn_common.hpp"
 
 namespace {
@@ -29,6 +33,7 @@ struct TransformArgs {
     float mean[3], std[3];
     int32_t B, Hp, Wp;
     void *out;                         // first image of this launch
+    const uint8_t *flags;              // FLIP: this launch's first image's flag (device)
 };
 
 __device__ __forceinline__ void tap_axis(const int dst, const int in, const int out, int &i0, int &i1, float &l0, float &l1)
@@ -64,7 +69,7 @@ template <> struct store4<RN_F16> {
     }
 };
 
-template <int DT, bool NHWC>
+template <int DT, bool NHWC, bool FLIP>
 __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArgs a)
 {
     const int b = blockIdx.z;
@@ -72,6 +77,7 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * TB_PX;
     if (x0 >= a.Wp) return;
     const int ih = a.ih[b], iw = a.iw[b], oh = a.oh[b], ow = a.ow[b];
+    const bool flip = FLIP && a.flags[b] != 0;           // source column c of the flipped image is column iw-1-c of img
     float v[3][TB_PX];
 #pragma unroll
     for (int c = 0; c < 3; ++c)
@@ -89,7 +95,7 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
                 const int x = x0 + p;
                 if (x < ow) {
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) v[c][p] = (src[c * plane + (int64_t)y * iw + x] - a.mean[c]) / a.std[c];
+                    for (int c = 0; c < 3; ++c) v[c][p] = (src[c * plane + (int64_t)y * iw + (flip ? iw - 1 - x : x)] - a.mean[c]) / a.std[c];
                 }
             }
         } else {
@@ -99,6 +105,7 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
                 if (x < ow) {
                     int xa, xb; float lx0, lx1;
                     tap_axis(x, iw, ow, xa, xb, lx0, lx1);
+                    if (flip) { xa = iw - 1 - xa; xb = iw - 1 - xb; }
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         const float *pl = src + c * plane;
@@ -124,11 +131,8 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
     }
 }
 
-}  // namespace
-
-RN_API int rn_transform_batch(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
-                              const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype,
-                              int channels_last, void *stream)
+int transform_batch(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B, const float mean[3],
+                    const float std[3], int Hp, int Wp, void *out, int out_dtype, int channels_last, const uint8_t *flags, void *stream)
 {
     if (!images || !in_hw || !out_hw || !mean || !std || !out || B <= 0 || Hp <= 0 || Wp <= 0) return RN_EINVAL;
     if (out_dtype != RN_F32 && out_dtype != RN_BF16 && out_dtype != RN_F16) return RN_EINVAL;
@@ -154,10 +158,16 @@ RN_API int rn_transform_batch(const void *const *images, const int32_t *in_hw, c
         for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std[c]; }
         a.Hp = Hp; a.Wp = Wp;
         a.out = (unsigned char *)out + (size_t)b0 * 3 * Hp * Wp * esz;
+        a.flags = flags ? flags + b0 : nullptr;
         const dim3 blk(256), grid((unsigned)((Wp / TB_PX + 255) / 256), (unsigned)Hp, (unsigned)a.B);
-#define RN_TB_LAUNCH(DT)                                                                                  \
-        if (channels_last) hipLaunchKernelGGL((transform_batch_kernel<DT, true>), grid, blk, 0, st, a);   \
-        else hipLaunchKernelGGL((transform_batch_kernel<DT, false>), grid, blk, 0, st, a)
+#define RN_TB_LAUNCH(DT)                                                                                              \
+        if (flags) {                                                                                                  \
+            if (channels_last) hipLaunchKernelGGL((transform_batch_kernel<DT, true, true>), grid, blk, 0, st, a);     \
+            else hipLaunchKernelGGL((transform_batch_kernel<DT, false, true>), grid, blk, 0, st, a);                  \
+        } else {                                                                                                      \
+            if (channels_last) hipLaunchKernelGGL((transform_batch_kernel<DT, true, false>), grid, blk, 0, st, a);    \
+            else hipLaunchKernelGGL((transform_batch_kernel<DT, false, false>), grid, blk, 0, st, a);                 \
+        }
         switch (out_dtype) {
             case RN_F32: RN_TB_LAUNCH(RN_F32); break;
             case RN_BF16: RN_TB_LAUNCH(RN_BF16); break;
@@ -167,4 +177,21 @@ RN_API int rn_transform_batch(const void *const *images, const int32_t *in_hw, c
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
+}
+
+}  // namespace
+
+RN_API int rn_transform_batch(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
+                              const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype,
+                              int channels_last, void *stream)
+{
+    return transform_batch(images, in_hw, out_hw, B, mean, std, Hp, Wp, out, out_dtype, channels_last, nullptr, stream);
+}
+
+RN_API int rn_transform_batch_flip(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
+                                   const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype,
+                                   int channels_last, const uint8_t *flags, void *stream)
+{
+    if (!flags) return RN_EINVAL;
+    return transform_batch(images, in_hw, out_hw, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags, stream);
 }

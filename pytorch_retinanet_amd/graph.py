@@ -18,6 +18,9 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     Optimizers with device-resident hyperparameters (``optim.MasterAdam`` / ``MasterAdamW``: ``_rn_device_hparams``) are the
     exception: their kernels read lr / betas / eps / weight_decay from device blocks, which ``sync_device_hparams()`` refreshes
     before every replay, so those values are left out of the signature and a per-step LR schedule replays one graph.
+    The train-time flip (``net.transform.hflip``, ``augment.RandomHorizontalFlip``) is keyed by the installed object alone: its
+    decisions are drawn inside the step from the object's device block, so eager steps and replays advance one counter and a
+    new p needs no capture.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -323,9 +326,12 @@ class CapturedTrainStep:
             tgs = ("gt_cap", cap)          # (the entry's packed buffers are B x cap rows; B is in the image shapes)
         else:
             tgs = tuple(tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in t.items() if isinstance(v, Tensor))) for t in targets)
+        # the train-time flip (transform.hflip): the draw is part of the step and reads p / seed / counter from the object's device
+        # block, so only WHICH object is installed matters (the key holds it: its block outlives every graph that reads it)
+        hflip = getattr(getattr(self.net, "transform", None), "hflip", None)
         mode = tuple(m.training for m in self.net.modules())
         frozen = tuple(p.requires_grad for p in self.net.parameters())       # (freezing / unfreezing layers changes the launch sequence)
-        return (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype)
+        return (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype, hflip)
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."

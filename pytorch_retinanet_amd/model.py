@@ -9,7 +9,8 @@ exchanged by ``parallel.BucketedGradAllReduce`` over RCCL).
 
 Data: ``dataset.kind: synthetic`` or ``csv`` (the reference's csv format, ``datasets.py``); the COCO-json /
 Pascal-xml readers and albumentations pipelines of the reference's ``utils/`` are outside this framework's
-scope (``prepare_data`` says so).  ``test_step`` / ``test_epoch_end`` feed the pycocotools-free
+scope (``prepare_data`` says so); the one augmentation the reference trains with, the horizontal flip of the ``transforms``
+block, runs on the GPU inside the model's transform (``augment.RandomHorizontalFlip``, installed by ``prepare_data`` for csv).  ``test_step`` / ``test_epoch_end`` feed the pycocotools-free
 ``coco_eval.CocoEvaluator`` (reference ``utils/coco/coco_eval.py``).
 """
 import argparse
@@ -86,7 +87,11 @@ class RetinaNetModel(_Base):
             self.val_ds = SyntheticDetectionDataset(**{**kw, "seed": kw.get("seed", 0) + 1})
             self.test_ds = SyntheticDetectionDataset(**{**kw, "seed": kw.get("seed", 0) + 2})
         elif d.kind == "csv":             # README.md:103-125: trn_paths / val_paths (optional) / test_paths are csv files
+            from .augment import from_transforms
             from .datasets import CSVDetectionDataset
+            # the training set's transforms (reference model.py:51-52, hparams.yaml:55-58): the horizontal flip runs on the GPU,
+            # inside the model's transform (augment.RandomHorizontalFlip); validation / test never flip (eval mode, no targets)
+            self.net.transform.hflip = from_transforms(self.conf.get("transforms"))
             self.trn_ds = CSVDetectionDataset(d.trn_paths)
             self.val_ds = CSVDetectionDataset(d.val_paths) if d.get("val_paths") else None
             self.test_ds = CSVDetectionDataset(d.test_paths) if d.get("test_paths") else None
@@ -234,6 +239,9 @@ class SimpleTrainer:
         optimizers, schedulers = (opt if isinstance(opt, tuple) else (opt, []))
         optimizer = optimizers[0]
         ddp = BucketedGradAllReduce(model.net) if dist.is_available() and dist.is_initialized() else None
+        hflip = getattr(model.net.transform, "hflip", None)
+        if hflip is not None and ddp is not None:
+            hflip.set_rank(dist.get_rank())               # seed = base seed + rank: each rank flips its own choice of images
         # precision "16" = fp16 autocast WITH dynamic loss scaling, like the reference's native-AMP run (Lightning precision=16):
         # fp16 gradients of a focal loss normalised by num_fg underflow without it
         # (under a gradient exchange: parallel.ExchangeGradScaler -- found_inf from the exchanged buckets, one decision for all ranks)

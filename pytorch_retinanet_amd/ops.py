@@ -6,6 +6,7 @@ the HIP library, never synchronises with the host, and REFUSES CPU tensors --
 there is no CPU implementation of this path in the product.
 """
 import ctypes as C
+import struct
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -559,11 +560,14 @@ def image_hw_tensor(sizes: Sequence[Tuple[int, int]], device: torch.device) -> T
 
 def transform_batch(images: Sequence[Tensor], out_sizes: Sequence[Tuple[int, int]], mean: Sequence[float],
                     std: Sequence[float], Hp: int, Wp: int, out_dtype: torch.dtype = torch.float32,
-                    channels_last: bool = False) -> Tensor:
+                    channels_last: bool = False, flags: Optional[Tensor] = None) -> Tensor:
     """T1: (x - mean) / std -> bilinear resize of image b to out_sizes[b] -> zero-padded batch
     ``[B, 3, Hp, Wp]`` (``out_dtype``; channels_last memory format on request) in one launch.
-    images: CUDA f32 ``[3, h, w]`` tensors; Wp % 4 == 0."""
+    images: CUDA f32 ``[3, h, w]`` tensors; Wp % 4 == 0.  ``flags`` (uint8 [>= B] on the images' device, ``hflip_draw``): image b is
+    horizontally flipped first where flags[b] != 0 (``rn_transform_batch_flip``: bit-identical to the transform of ``img.flip(-1)``)."""
     dev = _need_dev(*images)
+    if flags is not None:
+        _check_flags(flags, len(images), dev)
     B = len(images)
     if B == 0 or len(out_sizes) != B:
         raise ValueError("need one output size per image")
@@ -580,9 +584,105 @@ def transform_batch(images: Sequence[Tensor], out_sizes: Sequence[Tuple[int, int
     in_hw = (C.c_int32 * (2 * B))(*[int(v) for im in imgs for v in im.shape[1:]])
     out_hw = (C.c_int32 * (2 * B))(*[int(v) for s in out_sizes for v in s])
     with torch.cuda.device(dev), _timed("transform_batch", dev):
-        check(lib.rn_transform_batch(ptrs, in_hw, out_hw, B, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(Hp), int(Wp),
-                                     _ptr(out), _DT[out_dtype], int(bool(channels_last)), _stream(dev)), "rn_transform_batch")
+        if flags is None:
+            check(lib.rn_transform_batch(ptrs, in_hw, out_hw, B, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(Hp), int(Wp),
+                                         _ptr(out), _DT[out_dtype], int(bool(channels_last)), _stream(dev)), "rn_transform_batch")
+        else:
+            check(lib.rn_transform_batch_flip(ptrs, in_hw, out_hw, B, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(Hp), int(Wp),
+                                              _ptr(out), _DT[out_dtype], int(bool(channels_last)), _ptr(flags), _stream(dev)),
+                  "rn_transform_batch_flip")
     return out
+
+
+# ---- train-time horizontal flip (augment.RandomHorizontalFlip) ----------------------------------------------------------------
+_HFLIP_FIELDS = {"seed": (0, "<Q"), "counter": (8, "<q"), "p": (16, "<f")}     # include/retinanet_hip.h: rn_hflip_state
+HFLIP_STATE_BYTES = 24
+
+
+def _check_flags(flags: Tensor, B: int, dev: torch.device) -> None:
+    if flags.dtype != torch.uint8 or flags.device != dev or flags.dim() != 1 or flags.numel() < B or not flags.is_contiguous():
+        raise ValueError(f"flags must be a contiguous uint8 vector of >= {B} entries on {dev}, got {tuple(flags.shape)} {flags.dtype} "
+                         f"on {flags.device}")
+
+
+def hflip_state(dev: torch.device, seed: int, counter: int, p: float) -> Tensor:
+    "A new ``rn_hflip_state`` block (uint8 [24]) on ``dev`` holding seed / counter / p: one host->device copy, outside any capture."
+    block = torch.empty((HFLIP_STATE_BYTES,), dtype=torch.uint8, device=dev)
+    block[20:].zero_()
+    hflip_state_write(block, seed=seed, counter=counter, p=p)
+    return block
+
+
+def hflip_state_write(block: Tensor, seed: Optional[int] = None, counter: Optional[int] = None, p: Optional[float] = None) -> None:
+    """Overwrite the given fields of an ``rn_hflip_state`` block (the others keep their device values): host->device copies on the
+    current stream, so they are ordered with the draws around them.  Not inside a capture: the values would be baked into the graph."""
+    _need_dev(block)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("hflip_state_write inside a stream capture")
+    for name, v in (("seed", seed), ("counter", counter), ("p", p)):
+        if v is None:
+            continue
+        off, fmt = _HFLIP_FIELDS[name]
+        raw = struct.pack(fmt, (int(v) & (2 ** 64 - 1)) if name == "seed" else (int(v) if name == "counter" else float(v)))
+        block[off:off + len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+
+
+def hflip_state_read(block: Tensor) -> Tuple[int, int, float]:
+    "(seed, counter, p) of an ``rn_hflip_state`` block: one device->host copy (synchronises)."
+    raw = bytes(block.cpu().numpy().tobytes())
+    return tuple(struct.unpack_from(fmt, raw, off)[0] for off, fmt in _HFLIP_FIELDS.values())
+
+
+def hflip_draw(block: Tensor, B: int) -> Tensor:
+    """``rn_hflip_draw``: flags uint8 [B] (1 = flip image b) drawn from the block's seed / counter / p, then the block's counter advances
+    by one -- one launch on the current stream, no host synchronisation (capturable: each replay draws anew)."""
+    dev = _need_dev(block)
+    if block.dtype != torch.uint8 or block.numel() != HFLIP_STATE_BYTES or block.data_ptr() % 8:
+        raise ValueError("block must be an rn_hflip_state made by hflip_state()")
+    B = int(B)
+    if B <= 0:
+        raise ValueError(f"B must be positive, got {B}")
+    flags = torch.empty((B,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _timed("hflip_draw", dev):
+        check(lib.rn_hflip_draw(_ptr(block), B, _ptr(flags), _stream(dev)), "rn_hflip_draw")
+    return flags
+
+
+def gt_flip_scale_many(boxes: Sequence[Tensor], widths: Sequence[float], ratios: Sequence[Tuple[float, float]], flags: Tensor) -> Tensor:
+    """``resize_boxes`` of every image's boxes after the horizontal flip where ``flags[b]`` is set (x1' = W_b - x2, x2' = W_b - x1, fp32;
+    ``widths[b]`` = W_b, the width before the resize; ``ratios[b]`` = (rh, rw)): ONE launch per 64 images (``rn_gt_flip_scale_many``)
+    into a fresh f32 [sum T_b, 4] buffer, images in order.  Boxes that are not contiguous, aligned f32 on the flags' device are
+    converted first."""
+    dev = _need_dev(flags)
+    B = len(boxes)
+    if B == 0 or len(widths) != B or len(ratios) != B:
+        raise ValueError(f"{B} box tensors, {len(widths)} widths, {len(ratios)} ratio pairs")
+    _check_flags(flags, B, dev)
+    bs = [_aligned(b.reshape(-1, 4).to(device=dev, dtype=torch.float32), 16) for b in boxes]
+    counts = [int(b.shape[0]) for b in bs]
+    out = torch.empty((sum(counts), 4), dtype=torch.float32, device=dev)
+    flat = [float(v) for r in ratios for v in r]
+    with torch.cuda.device(dev), _timed("gt_flip_scale_many", dev):
+        check(lib.rn_gt_flip_scale_many((C.c_void_p * B)(*[_ptr(t).value for t in bs]), (C.c_int64 * B)(*counts), B,
+                                        (C.c_float * B)(*[float(w) for w in widths]), (C.c_float * (2 * B))(*flat), _ptr(flags),
+                                        _ptr(out), int(out.shape[0]), _stream(dev)), "rn_gt_flip_scale_many")
+    return out
+
+
+def gt_flip_scale_packed(gt: PackedGT, widths: Sequence[float], ratios: Sequence[Tuple[float, float]], flags: Tensor) -> PackedGT:
+    """``gt_scale_packed`` with the horizontal flip of ``gt_flip_scale_many`` (``rn_gt_flip_scale_packed``), out of place; it launches
+    whatever the ratios are (a flip changes the boxes at ratio 1 too)."""
+    dev = _need_dev(gt.gt_boxes, gt.gt_off, flags)
+    if len(ratios) != gt.B or len(widths) != gt.B:
+        raise ValueError(f"{len(widths)} widths / {len(ratios)} ratio pairs for packed GT of {gt.B} images")
+    _check_flags(flags, gt.B, dev)
+    out = torch.empty_like(gt.gt_boxes)
+    flat = [float(v) for r in ratios for v in r]
+    with torch.cuda.device(dev), _timed("gt_flip_scale_packed", dev):
+        check(lib.rn_gt_flip_scale_packed(_ptr(gt.gt_boxes), _ptr(out), _ptr(gt.gt_off), (C.c_float * gt.B)(*[float(w) for w in widths]),
+                                          (C.c_float * len(flat))(*flat), _ptr(flags), gt.B, gt.rows, gt.cap_per_image, _stream(dev)),
+              "rn_gt_flip_scale_packed")
+    return gt.with_boxes(out)
 
 
 def decode_clip(deltas: Tensor, anchors: Tensor, image_hw: Optional[Tensor],

@@ -15,6 +15,14 @@ directly in the layout and dtype the conv stack consumes (channels-last, autocas
 per-image elementwise kernels, the batch memset + copies, the ``contiguous(channels_last)`` pass
 and autocast's cast of the conv1 input all disappear.  Anything else (CPU tensors, other dtypes)
 takes the PyTorch ops below, which implement the same arithmetic.
+
+Train-time horizontal flip (``hflip``: an ``augment.RandomHorizontalFlip``, None by default): in training mode and when targets
+are given, each image is flipped with probability p before the normalise / resize, and its boxes with it (x1' = W - x2,
+x2' = W - x1, W = the width before the resize; the reference's ``RandomHorizontalFlip`` / albumentations ``HorizontalFlip``).
+On the fused path the decisions are drawn on the device (``rn_hflip_draw``), the flip is the transform kernel's mirrored
+gather (``rn_transform_batch_flip``) and the boxes' flip + resize one launch (``rn_gt_flip_scale_many`` / ``_packed``), so
+a captured train step draws new flips at every replay.  The PyTorch path does the same with ``img.flip(-1)`` and the box
+formula, selected by the flags with ``torch.where``.  ``hflip`` is a plain attribute: the state-dict keys do not change.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -66,6 +74,22 @@ def resize_boxes(boxes: Tensor, original_size: Sequence[int], new_size: Sequence
     return torch.stack((x1 * rw, y1 * rh, x2 * rw, y2 * rh), dim=1)
 
 
+def hflip_boxes(boxes: Tensor, width: float) -> Tensor:
+    "Boxes of an image of width ``width`` after a horizontal flip: x1' = W - x2, x2' = W - x1 (fp32; the reference's formula)."
+    x1, y1, x2, y2 = boxes.reshape(-1, 4).unbind(1)
+    return torch.stack((width - x2, y1, width - x1, y2), dim=1)
+
+
+def _flip_where(flag: Tensor, image: Tensor, target: Optional[Dict[str, Tensor]]):
+    "The PyTorch path's flip of one image (and its boxes) where ``flag`` (0-dim) is set: no host synchronisation."
+    f = flag.to(device=image.device, dtype=torch.bool)
+    image = torch.where(f, image.flip(-1), image)
+    if target is not None:
+        b = target["boxes"].reshape(-1, 4)
+        target["boxes"] = torch.where(f.to(b.device), hflip_boxes(b, float(image.shape[-1])), b)
+    return image, target
+
+
 class GeneralizedRCNNTransform(nn.Module):
     def __init__(self, min_size, max_size: int, image_mean: Sequence[float], image_std: Sequence[float],
                  size_divisible: int = 32):
@@ -76,6 +100,7 @@ class GeneralizedRCNNTransform(nn.Module):
         self.image_std = list(image_std)
         self.size_divisible = size_divisible
         self._stats = {}
+        self.hflip = None             # augment.RandomHorizontalFlip: the train-time flip (module docstring)
 
     # -- pieces ------------------------------------------------------------------------
     def normalize(self, image: Tensor) -> Tensor:
@@ -127,25 +152,39 @@ class GeneralizedRCNNTransform(nn.Module):
                 all(im.is_cuda and im.dim() == 3 and im.shape[0] == 3 and im.dtype == torch.float32 for im in images)
                 and self.size_divisible % 4 == 0)
 
+    def _flips(self, images: List[Tensor], targets) -> Optional[Tensor]:
+        "This batch's flip decisions (uint8 [B], on the images' device; the flip's counter advances), or None when nothing flips."
+        if self.hflip is None or not self.training or targets is None:
+            return None
+        return self.hflip.next_flags(len(images), images[0].device)
+
     def _forward_fused(self, images: List[Tensor], targets, out_dtype: torch.dtype, channels_last: bool):
         from . import ops                       # the HIP library is only needed once a CUDA image shows up
-        sizes, ratios = [], []
+        flags = self._flips(images, targets)
+        sizes, ratios, widths = [], [], []
         packed = _is_packed(targets)
         for i, im in enumerate(images):
             h, w = int(im.shape[-2]), int(im.shape[-1])
             scale = self._scale_for(h, w, self._target_short_side())       # drawn per image, like torchvision
             new = (int(math.floor(h * scale)), int(math.floor(w * scale)))
             sizes.append(new)
-            if packed:
+            widths.append(float(w))
+            if packed or flags is not None:
                 ratios.append(_ratios((h, w), new))
             elif targets is not None:
                 targets[i]["boxes"] = resize_boxes(targets[i]["boxes"], (h, w), new)
         if packed:
-            targets = _resize_packed(targets, ratios)
+            targets = _resize_packed(targets, ratios) if flags is None else ops.gt_flip_scale_packed(targets, widths, ratios, flags)
+        elif flags is not None:
+            # every image's flip + resize in one launch into one buffer; each target gets its rows as a view
+            counts = [int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets]
+            rows = ops.gt_flip_scale_many([t["boxes"] for t in targets], widths, ratios, flags).split(counts)
+            for t, r in zip(targets, rows):
+                t["boxes"] = r
         d = float(self.size_divisible)
         hp = int(math.ceil(max(s[0] for s in sizes) / d) * d)
         wp = int(math.ceil(max(s[1] for s in sizes) / d) * d)
-        batch = ops.transform_batch(images, sizes, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last)
+        batch = ops.transform_batch(images, sizes, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags)
         return ImageList(batch, sizes), targets
 
     # -- whole transform -----------------------------------------------------------------
@@ -166,12 +205,16 @@ class GeneralizedRCNNTransform(nn.Module):
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(im.shape)}")
         if self._fusable(images):
             return self._forward_fused(images, targets, out_dtype or torch.float32, channels_last)
-        ratios = []
+        flags = self._flips(images, targets)
+        ratios, widths = [], []
         for i, im in enumerate(images):
             if im.dim() != 3:
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(im.shape)}")
             tgt = targets[i] if (targets is not None and not packed) else None
             hw = (int(im.shape[-2]), int(im.shape[-1]))
+            widths.append(float(hw[1]))
+            if flags is not None:
+                im, tgt = _flip_where(flags[i], im, tgt)
             im, tgt = self.resize(self.normalize(im), tgt)
             images[i] = im
             if packed:
@@ -179,7 +222,8 @@ class GeneralizedRCNNTransform(nn.Module):
             if tgt is not None:
                 targets[i] = tgt
         if packed:
-            targets = _resize_packed(targets, ratios)
+            from . import ops
+            targets = _resize_packed(targets, ratios) if flags is None else ops.gt_flip_scale_packed(targets, widths, ratios, flags)
         sizes = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
         return ImageList(self.batch_images(images), sizes), targets
 
