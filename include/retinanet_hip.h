@@ -762,6 +762,41 @@ int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *co
                         void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
                         double *hparams, const float *grad_scale, const float *found_inf, void *stream);
 
+/* ---- global-norm gradient clipping for the master optimizers, capturable (csrc/clip.hip) ---------------------
+ * torch.nn.utils.clip_grad_norm_(norm_type = 2) without a write: rn_grad_norm_clip leaves the norm and the clip coefficient in a
+ * DEVICE block, and the _clip forms of the two optimizer steps multiply every gradient by that coefficient as they read it.
+ * The block: RN_CLIP_STATE doubles (8-byte aligned, zero-filled by its owner before first use), laid out as
+ *   byte  0  f32 max_norm      (written by rn_grad_clip_set, the host's only way in)
+ *   byte  4  f32 total_norm    (the last call's norm of the UNSCALED gradients)
+ *   byte  8  f32 clip_coef     (RN_CLIP_COEF_OFFSET: what the step kernels read)
+ *   byte 16  i64 calls, byte 24 i64 calls with clip_coef < 1, byte 32 i64 calls with a non-finite norm; the rest reserved.
+ * rn_grad_norm_clip: grads / numels are HOST arrays over the tensors of ALL parameter groups (the norm is global); gradient i is
+ * dtype16 (RN_BF16 | RN_F16, 8-byte aligned) when grads16 != 0 and params16 != NULL and params16[i] != NULL -- the convention of
+ * rn_sgd_master_step_ex, params16 itself nullable -- and f32 (16-byte aligned) otherwise.  scratch: f64[scratch_slots] owned by the
+ * caller, scratch_slots >= the sum over tensors of ceil(numels[i] / RN_CLIP_CHUNK) (RN_EINVAL otherwise): one slot per chunk of a
+ * gradient, each written by one workgroup (the squares are summed in double from the first addition on) and then summed in slot
+ * order in double -- no atomics, so the result is the same bits at every call.  total_norm = float(sqrt(sum of squares)) * (1 / grad_scale[0]) (grad_scale: nullable DEVICE f32 scalar, the
+ * GradScaler's), clip_coef = min((1 / (total_norm + 1e-6)) * max_norm, 1) in fp32, which is torch's arithmetic; a non-finite norm
+ * gives torch's 0 or NaN.  One launch per 224 tensors plus one; no host synchronisation, no memset: capturable.
+ * rn_grad_clip_set: one launch writing max_norm (> 0) into the block; a captured step follows the value last written. */
+#define RN_CLIP_STATE 8
+#define RN_CLIP_COEF_OFFSET 8
+#define RN_CLIP_CHUNK 16384
+int rn_grad_clip_set(void *block, float max_norm, void *stream);
+int rn_grad_norm_clip(const void *const *grads, void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16,
+                      const float *grad_scale, double *scratch, int64_t scratch_slots, void *block, void *stream);
+/* rn_sgd_master_step_ex / rn_adam_master_step with the clip: clip_coef (nullable DEVICE f32 scalar, the block's clip_coef) enters as
+ *   g = (float(grad) * (1 / grad_scale[0])) * clip_coef[0]
+ * -- GradScaler.unscale_ followed by clip_grad_norm_ on fp32 gradients, never rounded to 16 bits in between -- before weight decay
+ * touches g.  clip_coef == NULL: the older entry points, which forward here.  Adam's step counter advances in a clipped step. */
+int rn_sgd_master_step_clip(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
+                            const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
+                            float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
+                            const float *clip_coef, void *stream);
+int rn_adam_master_step_clip(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
+                             void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
+                             double *hparams, const float *grad_scale, const float *found_inf, const float *clip_coef, void *stream);
+
 /* ---- T1 transform (normalise + resize + pad + batch) -------------------------------------------
  * Replaces torchvision's GeneralizedRCNNTransform as the reference runs it at
  * retinanet/models.py:116 (construction), :262 and :279 (calls): per image (x - mean) / std, bilinear

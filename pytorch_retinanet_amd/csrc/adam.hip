@@ -35,6 +35,7 @@ struct AdamTable {
     int64_t n[ADAM_MAX_TENSORS];
     const double *hp;
     const float *grad_scale, *found_inf;      // nullable device scalars (torch.amp.GradScaler): 1 / 0
+    const float *clip_coef;                   // nullable device scalar: the global-norm clip coefficient (csrc/clip.hip)
     int grad16;                               // gradients of tensors WITH a 16-bit copy are 16-bit as well (else f32)
 };
 
@@ -91,6 +92,7 @@ __global__ __launch_bounds__(256) void adam_master_kernel(const AdamTable t)
     constexpr int DT = F16 ? RN_F16 : RN_BF16;
     if (t.found_inf && *t.found_inf != 0.0f) return;             // (GradScaler: a non-finite gradient somewhere -> nothing moves)
     const AdamScalars s = adam_scalars(t);
+    const float coef = t.clip_coef ? *t.clip_coef : 1.0f;
     const bool decay = s.wd != 0.0f;
     const int ti = blockIdx.y;
     float *__restrict__ w = t.master[ti];
@@ -116,7 +118,11 @@ __global__ __launch_bounds__(256) void adam_master_kernel(const AdamTable t)
         }
         float ww[4] = {wv.x, wv.y, wv.z, wv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w}, vq[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) adam_one<DECOUPLED>(s, decay, t.grad_scale ? g[j] * s.inv_scale : g[j], ww[j], mm[j], vq[j]);
+        for (int j = 0; j < 4; ++j) {
+            float gj = t.grad_scale ? g[j] * s.inv_scale : g[j];
+            if (t.clip_coef) gj = gj * coef;                     // unscale, then clip: two fp32 products, before weight decay
+            adam_one<DECOUPLED>(s, decay, gj, ww[j], mm[j], vq[j]);
+        }
         ((rn::f32x4 *)w)[q] = rn::f32x4{ww[0], ww[1], ww[2], ww[3]};
         ((rn::f32x4 *)m)[q] = rn::f32x4{mm[0], mm[1], mm[2], mm[3]};
         ((rn::f32x4 *)v)[q] = rn::f32x4{vq[0], vq[1], vq[2], vq[3]};
@@ -132,6 +138,7 @@ __global__ __launch_bounds__(256) void adam_master_kernel(const AdamTable t)
             float wi = w[i], mi = m[i], vi = v[i];
             float g = g16 ? rn::mma<DT>::lo((uint32_t)((const uint16_t *)t.grad[ti])[i]) : ((const float *)t.grad[ti])[i];
             if (t.grad_scale) g *= s.inv_scale;
+            if (t.clip_coef) g *= coef;
             adam_one<DECOUPLED>(s, decay, g, wi, mi, vi);
             w[i] = wi; m[i] = mi; v[i] = vi;
             if (p16) p16[i] = rn::mma<DT>::dn(wi);
@@ -158,9 +165,9 @@ RN_API int rn_adam_hparams_set(double *hparams, double lr, double beta1, double 
     return RN_OK;
 }
 
-RN_API int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
-                               void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
-                               double *hparams, const float *grad_scale, const float *found_inf, void *stream)
+RN_API int rn_adam_master_step_clip(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
+                                    void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
+                                    double *hparams, const float *grad_scale, const float *found_inf, const float *clip_coef, void *stream)
 {
     if (dtype16 != RN_BF16 && dtype16 != RN_F16) return RN_EUNSUPPORTED;
     if (!masters || !exp_avgs || !exp_avg_sqs || !grads || !params16 || !numels || !hparams || n_tensors < 0) return RN_EINVAL;
@@ -183,7 +190,7 @@ RN_API int rn_adam_master_step(float *const *masters, float *const *exp_avgs, fl
             t.grad[i] = grads[base + i]; t.p16[i] = params16[base + i]; t.n[i] = numels[base + i];
             max_n = t.n[i] > max_n ? t.n[i] : max_n;
         }
-        t.hp = hparams; t.grad_scale = grad_scale; t.found_inf = found_inf; t.grad16 = grads16;
+        t.hp = hparams; t.grad_scale = grad_scale; t.found_inf = found_inf; t.clip_coef = clip_coef; t.grad16 = grads16;
         int64_t bx = (max_n / 4 + 255) / 256;                    // one pass over the largest tensor, capped
         if (bx > ADAM_BLOCKS_X) bx = ADAM_BLOCKS_X;
         if (bx < 1) bx = 1;
@@ -198,4 +205,12 @@ RN_API int rn_adam_master_step(float *const *masters, float *const *exp_avgs, fl
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
+}
+
+RN_API int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
+                               void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
+                               double *hparams, const float *grad_scale, const float *found_inf, void *stream)
+{
+    return rn_adam_master_step_clip(masters, exp_avgs, exp_avg_sqs, grads, params16, numels, n_tensors, grads16, dtype16, decoupled, hparams,
+                                    grad_scale, found_inf, nullptr, stream);
 }

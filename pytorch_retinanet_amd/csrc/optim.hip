@@ -27,6 +27,9 @@ struct SgdTable {
     // fp16 autocast with torch.amp.GradScaler (an optimizer with _step_supports_amp_scaling): the gradients are grad_scale[0] times
     // too large, and the whole step is skipped when found_inf[0] != 0 -- both device scalars, so nothing synchronises (null: 1 / 0)
     const float *grad_scale, *found_inf;
+    // global-norm clipping (csrc/clip.hip): the coefficient rn_grad_norm_clip left on the device, multiplied into every unscaled
+    // gradient before weight decay (null: no clip, and no extra instruction on the data)
+    const float *clip_coef;
 };
 
 __device__ __forceinline__ float sgd_one(const SgdTable &t, const float gin, float &wi, float &mi)
@@ -48,6 +51,7 @@ __global__ __launch_bounds__(256) void sgd_master_kernel(const SgdTable t)
     constexpr int DT = F16 ? RN_F16 : RN_BF16;
     if (t.found_inf && *t.found_inf != 0.0f) return;             // (GradScaler: a non-finite gradient somewhere -> no parameter moves)
     const float inv_scale = t.grad_scale ? 1.0f / *t.grad_scale : 1.0f;
+    const float coef = t.clip_coef ? *t.clip_coef : 1.0f;
     const int ti = blockIdx.y;
     float *__restrict__ w = t.master[ti];
     float *__restrict__ m = t.mom[ti];
@@ -73,7 +77,11 @@ __global__ __launch_bounds__(256) void sgd_master_kernel(const SgdTable t)
         }
         float ww[4] = {wv.x, wv.y, wv.z, wv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sgd_one(t, t.grad_scale ? g[j] * inv_scale : g[j], ww[j], mm[j]);
+        for (int j = 0; j < 4; ++j) {
+            float gj = t.grad_scale ? g[j] * inv_scale : g[j];
+            if (t.clip_coef) gj = gj * coef;
+            sgd_one(t, gj, ww[j], mm[j]);
+        }
         wv.x = ww[0]; wv.y = ww[1]; wv.z = ww[2]; wv.w = ww[3];
         mv.x = mm[0]; mv.y = mm[1]; mv.z = mm[2]; mv.w = mm[3];
         ((rn::f32x4 *)w)[v] = wv;
@@ -90,6 +98,7 @@ __global__ __launch_bounds__(256) void sgd_master_kernel(const SgdTable t)
             float wi = w[i], mi = (has_m && !t.first) ? m[i] : 0.0f;
             float g = g16 ? rn::mma<DT>::lo((uint32_t)((const uint16_t *)t.grad[ti])[i]) : ((const float *)t.grad[ti])[i];
             if (t.grad_scale) g *= inv_scale;
+            if (t.clip_coef) g *= coef;
             sgd_one(t, g, wi, mi);
             w[i] = wi;
             if (has_m) m[i] = mi;
@@ -100,10 +109,10 @@ __global__ __launch_bounds__(256) void sgd_master_kernel(const SgdTable t)
 
 }  // namespace
 
-RN_API int rn_sgd_master_step_ex(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
-                                 const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
-                                 float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
-                                 void *stream)
+RN_API int rn_sgd_master_step_clip(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
+                                   const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
+                                   float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
+                                   const float *clip_coef, void *stream)
 {
     if (dtype16 != RN_BF16 && dtype16 != RN_F16) return RN_EUNSUPPORTED;
     if (!masters || !momenta || !grads || !params16 || !numels || n_tensors < 0) return RN_EINVAL;
@@ -122,6 +131,7 @@ RN_API int rn_sgd_master_step_ex(float *const *masters, float *const *momenta, c
         t.lr = lr; t.momentum = momentum; t.dampening = dampening; t.weight_decay = weight_decay;
         t.nesterov = nesterov; t.first = first_step; t.grad16 = grads16;
         t.f16 = dtype16 == RN_F16; t.grad_scale = grad_scale; t.found_inf = found_inf;
+        t.clip_coef = clip_coef;
         int64_t max_n = 1;
         for (int i = 0; i < cnt; ++i) max_n = t.n[i] > max_n ? t.n[i] : max_n;
         int64_t bx = (max_n / 4 + 255) / 256;                    // one pass over the largest tensor, capped
@@ -132,6 +142,15 @@ RN_API int rn_sgd_master_step_ex(float *const *masters, float *const *momenta, c
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
+}
+
+RN_API int rn_sgd_master_step_ex(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
+                                 const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
+                                 float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
+                                 void *stream)
+{
+    return rn_sgd_master_step_clip(masters, momenta, grads, params16, numels, n_tensors, grads16, dtype16, lr, momentum, dampening, weight_decay,
+                                   nesterov, first_step, grad_scale, found_inf, nullptr, stream);
 }
 
 RN_API int rn_sgd_master_step(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,

@@ -20,7 +20,8 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     before every replay, so those values are left out of the signature and a per-step LR schedule replays one graph.
     The train-time flip (``net.transform.hflip``, ``augment.RandomHorizontalFlip``) is keyed by the installed object alone: its
     decisions are drawn inside the step from the object's device block, so eager steps and replays advance one counter and a
-    new p needs no capture.
+    new p needs no capture.  Gradient clipping (``optimizer.grad_clip``, ``optim.GradClip``) is keyed the same way: ``max_norm`` is
+    read from the object's device block, whose first (eager) step creates it.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -329,9 +330,12 @@ class CapturedTrainStep:
         # the train-time flip (transform.hflip): the draw is part of the step and reads p / seed / counter from the object's device
         # block, so only WHICH object is installed matters (the key holds it: its block outlives every graph that reads it)
         hflip = getattr(getattr(self.net, "transform", None), "hflip", None)
+        # global-norm clipping (optim.GradClip on a master optimizer): the norm kernels are part of the step and read max_norm from the
+        # object's device block, so -- as for the flip -- the key holds the object, not its value; installing or removing a clip re-captures
+        clip = getattr(self.optimizer, "grad_clip", None)
         mode = tuple(m.training for m in self.net.modules())
         frozen = tuple(p.requires_grad for p in self.net.parameters())       # (freezing / unfreezing layers changes the launch sequence)
-        return (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype, hflip)
+        return (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype, hflip, clip)
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."

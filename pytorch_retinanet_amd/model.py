@@ -204,7 +204,7 @@ class SimpleTrainer:
 
     def __init__(self, max_epochs: int = 1, device: Optional[str] = None, precision: str = "bf16",
                  channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True,
-                 gt_capacity=None):
+                 gt_capacity=None, gradient_clip_val: float = 0.0):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
@@ -213,8 +213,19 @@ class SimpleTrainer:
         a graph's signature: each new value would re-capture, so a per-step schedule runs them eagerly.  Batches of a new shape run
         eagerly twice, then replay; the results are the eager step's (``tests/test_graph_gpu.py``).  ``gt_capacity``: passed to the
         ``CapturedTrainStep`` -- "auto" keys batches by GT capacity class instead of by their exact box counts, so data with a
-        different number of boxes per image still replays (None: exact keying)."""
+        different number of boxes per image still replays (None: exact keying).
+
+        ``gradient_clip_val`` (Lightning's name and default; 0 = off; left at 0, an optional ``trainer.gradient_clip_val`` in the hparams
+        is honoured): clip the gradients by global L2 norm before every optimizer step.  With ``optim.MasterSGD`` / ``MasterAdam`` /
+        ``MasterAdamW`` the trainer installs an ``optim.GradClip`` on the optimizer (``self.grad_clip``) and nothing else changes: the
+        norm and the scaling run on the device inside the step, capture stays on, and under ``torch.distributed`` the clip sees the
+        exchanged gradients, so every rank computes the same coefficient.  Any other optimizer: one process only, eagerly (capture is
+        turned off for the run, with a log line), ``torch.nn.utils.clip_grad_norm_`` after ``scaler.unscale_``."""
         from .graph import gt_capacity_classes
+        self.gradient_clip_val = float(gradient_clip_val or 0.0)
+        if not self.gradient_clip_val >= 0.0:
+            raise ValueError(f"gradient_clip_val must be >= 0 (0 = off), got {gradient_clip_val}")
+        self.grad_clip = None                             # the optim.GradClip of the last fit() (master optimizers)
         gt_capacity_classes(gt_capacity)                  # (bad values fail here, not at the first step)
         self.gt_capacity = gt_capacity
         self.max_epochs, self.max_steps, self.log_every, self.capture = max_epochs, max_steps, log_every, capture
@@ -223,6 +234,16 @@ class SimpleTrainer:
         self.amp_dtype = {"bf16": torch.bfloat16, "16": torch.float16, "32": None}[str(precision)]
         self.channels_last = channels_last
         self.log = logging.getLogger("lightning")
+
+    def resolve_gradient_clip_val(self, conf) -> float:
+        "The constructor's ``gradient_clip_val`` or, when that is 0, ``trainer.gradient_clip_val`` of the hparams (absent: 0 = off)."
+        if self.gradient_clip_val > 0:
+            return self.gradient_clip_val
+        section = conf.get("trainer") if hasattr(conf, "get") else None
+        value = float((section or {}).get("gradient_clip_val") or 0.0)
+        if not value >= 0.0:
+            raise ValueError(f"trainer.gradient_clip_val must be >= 0 (0 = off), got {value}")
+        return value
 
     def _autocast(self):
         return torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype is not None and self.device.type == "cuda")
@@ -248,8 +269,29 @@ class SimpleTrainer:
         from .parallel import ExchangeGradScaler
         scaler = (ExchangeGradScaler("cuda") if ddp is not None else torch.amp.GradScaler("cuda")) \
             if (self.amp_dtype == torch.float16 and self.device.type == "cuda") else None
+        # gradient clipping: on the device inside the step for the master optimizers, torch's clip_grad_norm_ for the others
+        clip_val = self.resolve_gradient_clip_val(model.conf)
+        torch_clip = False
+        self.grad_clip = getattr(optimizer, "grad_clip", None) if getattr(optimizer, "_rn_grad_clip", False) else None
+        if clip_val > 0:
+            if getattr(optimizer, "_rn_grad_clip", False):
+                from .optim import GradClip
+                if self.grad_clip is None:
+                    self.grad_clip = optimizer.grad_clip = GradClip(clip_val)
+                else:
+                    self.grad_clip.max_norm = clip_val        # (the trainer's value wins over the optimizer's max_grad_norm)
+            elif ddp is not None:
+                raise RuntimeError(f"gradient_clip_val={clip_val} with {type(optimizer).__name__} under torch.distributed is not supported: "
+                                   "the clip has to see the exchanged gradients, which only the master optimizers read "
+                                   "(optimizer.class_name: pytorch_retinanet_amd.optim.MasterSGD / MasterAdam / MasterAdamW)")
+            else:
+                torch_clip = True
+                if self.capture:
+                    self.log.info("gradient_clip_val=%g with %s: torch.nn.utils.clip_grad_norm_ runs eagerly, the step is not captured "
+                                  "(the master optimizers clip inside the captured step)", clip_val, type(optimizer).__name__)
+        grad_norm = None
         stepper = None
-        if (self.capture and self.device.type == "cuda" and ddp is None and type(model).training_step is RetinaNetModel.training_step
+        if (self.capture and not torch_clip and self.device.type == "cuda" and ddp is None and type(model).training_step is RetinaNetModel.training_step
                 and (getattr(optimizer, "_rn_device_hparams", False)
                      or not any(s["interval"] == "step" and "monitor" not in s for s in schedulers))):
             from .graph import CapturedTrainStep
@@ -279,19 +321,28 @@ class SimpleTrainer:
                             ddp.finish()
                             scaler.step_exchanged(optimizer, ddp)
                         else:
+                            if torch_clip:
+                                scaler.unscale_(optimizer)
+                                grad_norm = torch.nn.utils.clip_grad_norm_(model.net.parameters(), clip_val)
                             scaler.step(optimizer)
                         scaler.update()
                     else:
                         out["loss"].backward()
                         if ddp:
                             ddp.finish()
+                        if torch_clip:
+                            grad_norm = torch.nn.utils.clip_grad_norm_(model.net.parameters(), clip_val)
                         if ddp and getattr(optimizer, "_rn_master_weights", False):
                             optimizer.step(grads=ddp.grad_views())       # fp32 bucket views of the bf16 working copies
                         else:
                             optimizer.step()
                 step += 1
                 if step % self.log_every == 0:
-                    self.log.info("epoch %d step %d loss %.4f", epoch, step, float(out["loss"]))
+                    if self.grad_clip is not None or grad_norm is not None:
+                        norm = float(self.grad_clip.total_norm if self.grad_clip is not None else grad_norm)
+                        self.log.info("epoch %d step %d grad_norm %.4f loss %.4f", epoch, step, norm, float(out["loss"]))
+                    else:
+                        self.log.info("epoch %d step %d loss %.4f", epoch, step, float(out["loss"]))
                 for s in schedulers:
                     if s["interval"] == "step" and "monitor" not in s:
                         s["scheduler"].step()

@@ -13,10 +13,16 @@ give and take fp32 checkpoints with the reference's keys.
 
 ``MasterAdam`` / ``MasterAdamW`` do the same for ``torch.optim.Adam`` / ``AdamW`` (``rn_adam_master_step``, ``csrc/adam.hip``), with every
 hyperparameter and the step counter in a device block per parameter group: a captured step follows a per-step LR schedule.
+
+``GradClip`` -- ``torch.nn.utils.clip_grad_norm_`` for the three of them (``rn_grad_norm_clip``, ``csrc/clip.hip``): one read of every
+gradient gives the global L2 norm and the clip coefficient in a device block, and the step kernels multiply the coefficient into each
+gradient as they read it.  No gradient is rewritten, nothing synchronises, and ``max_norm`` lives on the device: the clipped step
+captures like the plain one.
 """
 import ctypes as C
 from typing import Dict, Iterable, List, Optional
 
+import numpy as np
 import torch
 from torch import Tensor, nn
 
@@ -65,6 +71,162 @@ def load_master_state_dict(model: nn.Module, state: Dict[str, Tensor], strict: b
     return out
 
 
+def _is_capturing() -> bool:
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+RN_CLIP_STATE = 8                       # doubles in the clip block (include/retinanet_hip.h)
+RN_CLIP_CHUNK = 16384                   # elements per scratch slot
+_CLIP_COEF_BYTE = 8                     # byte offset of clip_coef in the block
+
+
+class GradClip:
+    """Gradient clipping by global L2 norm for ``MasterSGD`` / ``MasterAdam`` / ``MasterAdamW`` -- what ``torch.nn.utils.clip_grad_norm_``
+    (Lightning's ``gradient_clip_val``) does between backward and the optimizer step, without rewriting a gradient.  Install it as
+    ``optimizer.grad_clip`` (or construct the optimizer with ``max_grad_norm=``); every ``step()`` then makes one ``rn_grad_norm_clip``
+    call over the gradients of all parameter groups and the step kernels scale each gradient by the coefficient they read from this
+    object's device block: ``g = (float(grad) / grad_scale) * clip_coef``, in fp32, before weight decay.
+
+    The block and the scratch buffer of partial sums are created at the first step, on the device of the first gradient -- not
+    inside a capture -- and kept for good (a captured step holds their addresses).  ``max_norm`` lives in the block: assigning it
+    is one tiny launch and the next replay of a captured step clips at the new value.  ``total_norm`` / ``clip_coef`` are views into
+    the block (reading them synchronises, like any device tensor); ``stats()`` reads the three counters.  Under a ``GradScaler``
+    the norm is of the UNSCALED gradients; nobody calls ``unscale_``."""
+
+    def __init__(self, max_norm: float, norm_type: float = 2.0):
+        if float(norm_type) != 2.0:
+            raise ValueError(f"GradClip clips by the global L2 norm only (norm_type=2.0), got norm_type={norm_type}")
+        self._max_norm = self._check_max_norm(max_norm)
+        self._block: Optional[Tensor] = None          # float64[RN_CLIP_STATE] on the device of the first gradient (kept for good)
+        self._scratch: Optional[Tensor] = None        # float64[slots]: one partial sum per RN_CLIP_CHUNK elements of a gradient
+        self._retired: List[Tensor] = []              # outgrown scratch buffers (a captured step may still write into them)
+
+    @staticmethod
+    def _check_max_norm(value) -> float:
+        value = float(value)
+        if not value > 0.0 or value == float("inf"):
+            raise ValueError(f"max_norm must be a positive finite number, got {value}")
+        if float(np.float32(value)) == 0.0 or not np.isfinite(np.float32(value)):
+            raise ValueError(f"max_norm must be representable as a positive fp32 number, got {value}")
+        return value
+
+    def __repr__(self) -> str:
+        return f"GradClip(max_norm={self._max_norm})"
+
+    @staticmethod
+    def coef(total, max_norm) -> float:
+        """Pure-Python fp32 restatement of the coefficient (``csrc/clip.hip`` and ``clip_grad_norm_``): ``min((1 / (total + 1e-6)) *
+        max_norm, 1)`` with every operation rounded to fp32 -- torch divides a scalar by a tensor as reciprocal-then-multiply -- and
+        ``clamp(max=1)``'s treatment of NaN (it stays).  An infinite norm gives 0."""
+        with np.errstate(all="ignore"):
+            t = np.float32(total) + np.float32(1e-6)
+            c = np.float32(np.float32(1.0) / t) * np.float32(max_norm)
+            return float(np.float32(1.0) if c > np.float32(1.0) else c)
+
+    # -- the device side ----------------------------------------------------------------------------------------------
+    @property
+    def max_norm(self) -> float:
+        return self._max_norm
+
+    @max_norm.setter
+    def max_norm(self, value: float) -> None:
+        "A new threshold: written into the device block (no re-capture needed; not inside a capture)."
+        value = self._check_max_norm(value)
+        if self._block is not None:
+            if _is_capturing():
+                raise RuntimeError("GradClip: max_norm cannot be set inside a capture (the write would replay the value of capture time)")
+            self._write_max_norm(value)
+        self._max_norm = value
+
+    def _write_max_norm(self, value: float) -> None:
+        dev = self._block.device
+        with torch.cuda.device(dev):
+            check(lib.rn_grad_clip_set(self._block.data_ptr(), float(value), torch.cuda.current_stream(dev).cuda_stream), "rn_grad_clip_set")
+
+    def _ensure(self, device: torch.device, slots: int) -> None:
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._block is None:
+            if _is_capturing():
+                raise RuntimeError("GradClip: take one step before capturing one: its device block cannot be created inside a capture")
+            self._block = torch.empty(RN_CLIP_STATE, dtype=torch.float64, device=device).fill_(0)      # (a fill kernel, not a memset: graph.py)
+            self._write_max_norm(self._max_norm)
+        elif self._block.device != device:
+            # (a captured step holds the block's address: it is never replaced while this object lives)
+            raise RuntimeError(f"GradClip: its state lives on {self._block.device}, not {device}; use one object per device")
+        if self._scratch is None or self._scratch.numel() < slots:
+            if _is_capturing():
+                raise RuntimeError("GradClip: the set of gradients grew since the last eager step: take one step before capturing one")
+            if self._scratch is not None:
+                self._retired.append(self._scratch)
+            self._scratch = torch.empty(max(slots, 1), dtype=torch.float64, device=device)
+
+    def compute(self, gptrs: List[int], p16s: List[int], ns: List[int], dtype16: int, scale: Optional[Tensor], device: torch.device) -> int:
+        """One ``rn_grad_norm_clip`` call on the current stream over the gradients at ``gptrs`` (``p16s[i] != 0``: gradient i is
+        16-bit, ``dtype16``); returns the device address of the coefficient for the step kernels."""
+        n = len(gptrs)
+        slots = sum((k + RN_CLIP_CHUNK - 1) // RN_CLIP_CHUNK for k in ns)
+        self._ensure(device, slots)
+        with torch.cuda.device(self._block.device):
+            check(lib.rn_grad_norm_clip((C.c_void_p * n)(*gptrs), (C.c_void_p * n)(*p16s), (C.c_int64 * n)(*ns), n, 1, dtype16,
+                                        scale.data_ptr() if scale is not None else None, self._scratch.data_ptr(), self._scratch.numel(),
+                                        self._block.data_ptr(), torch.cuda.current_stream().cuda_stream), "rn_grad_norm_clip")
+        return self._block.data_ptr() + _CLIP_COEF_BYTE
+
+    def _f32(self, i: int) -> Tensor:
+        if self._block is None:
+            raise RuntimeError("GradClip: no step has been taken yet (the device block is created by the first one)")
+        return self._block.view(torch.float32)[i]
+
+    @property
+    def total_norm(self) -> Tensor:
+        "The last step's global norm of the unscaled gradients (device scalar, a view into the block)."
+        return self._f32(1)
+
+    @property
+    def clip_coef(self) -> Tensor:
+        "The last step's coefficient, ``min(max_norm / (total_norm + 1e-6), 1)`` (device scalar, a view into the block)."
+        return self._f32(2)
+
+    def stats(self) -> Dict[str, int]:
+        "Calls so far, calls that clipped (coefficient < 1) and calls with a non-finite norm (reads the block: synchronises)."
+        if self._block is None:
+            return {"calls": 0, "clipped": 0, "nonfinite": 0}
+        calls, clipped, nonfinite = self._block.view(torch.int64)[2:5].tolist()
+        return {"calls": calls, "clipped": clipped, "nonfinite": nonfinite}
+
+
+def _amp_scalars(opt):
+    "``grad_scale`` / ``found_inf`` as torch.amp.GradScaler.step sets them around the call (or None, None)."
+    scale, found = getattr(opt, "grad_scale", None), getattr(opt, "found_inf", None)
+    for t in (scale, found):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
+            raise TypeError("grad_scale / found_inf must be CUDA fp32 scalars (torch.amp.GradScaler)")
+    return scale, found
+
+
+def _clip_coef_ptr(opt, recs: List[dict], scale: Optional[Tensor]) -> Optional[int]:
+    """With ``opt.grad_clip`` installed: the norm of the gradients of every group in ``recs`` (one call: the norm is global) and the
+    device address of the coefficient; None without a clip."""
+    clip = getattr(opt, "grad_clip", None)
+    if clip is None or not recs:
+        return None
+    if not isinstance(clip, GradClip):
+        raise TypeError(f"grad_clip must be an optim.GradClip, not {type(clip).__name__}")
+    dt16s = {r["dt16"] for r in recs if r["dt16"] is not None}
+    if len(dt16s) > 1:
+        raise RuntimeError("the 16-bit working copies of a clipped step must share a dtype")
+    gptrs, is16, ns = [], [], []
+    for r in recs:
+        gptrs += r["gptrs"]; ns += r["ns"]
+        is16 += [p if r["grads16"] else 0 for p in r["p16s"]]      # (a group may hold fp32 gradients for its 16-bit copies: the exchange's views)
+    return clip.compute(gptrs, is16, ns, RN_F16 if torch.float16 in dt16s else RN_BF16, scale, recs[0]["dev"])
+
+
+def _install_clip(opt, max_grad_norm) -> None:
+    opt.grad_clip = GradClip(max_grad_norm) if max_grad_norm is not None else None
+
+
 class MasterSGD(torch.optim.Optimizer):
     # torch.amp.GradScaler.step() hands such an optimizer `grad_scale` / `found_inf` (device scalars) instead of unscaling the gradients
     # and reading found_inf back on the host: the kernel divides and skips on the device (rn_sgd_master_step_ex), nothing synchronises
@@ -72,11 +234,14 @@ class MasterSGD(torch.optim.Optimizer):
     # fp32 masters behind 16-bit conv weights (RetinaNetModel.configure_optimizers converts the model), and step(grads=...) takes the
     # fp32 bucket views of parallel.BucketedGradAllReduce
     _rn_master_weights = True
+    # step() clips by global norm when `grad_clip` holds an optim.GradClip (constructor: max_grad_norm=...)
+    _rn_grad_clip = True
 
     def __init__(self, params: Iterable, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False):
+                 weight_decay: float = 0.0, nesterov: bool = False, max_grad_norm: Optional[float] = None):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        _install_clip(self, max_grad_norm)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov))
 
     @torch.no_grad()
@@ -88,86 +253,88 @@ class MasterSGD(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         note_raw_write()                   # masters, bf16 copies and BN affine parameters change without a _version bump
-        for group in self.param_groups:
-            masters, moms, gptrs, p16s, ns = [], [], [], [], []
-            grads16 = None
-            dt16 = None
-            first = None
-            keep: List[Tensor] = []
-            for p in group["params"]:
-                g = grads.get(p) if grads is not None else None
-                if g is None:
-                    g = p.grad
-                if g is None:
-                    continue
-                has16 = hasattr(p, "master")
-                w = p.master if has16 else p.data
-                if w.dtype != torch.float32 or not p.is_cuda:
-                    raise TypeError("MasterSGD handles CUDA fp32 parameters and bf16 parameters converted by use_bf16_conv_weights")
-                st = self.state[p]
-                if "momentum_buffer" not in st:
-                    # (under a GradScaler the very first step may be SKIPPED by found_inf: the buffer then has to hold zeros, with
-                    # which the next step's momentum * buf + (1 - dampening) * g is torch's first-step buf = g -- for dampening == 0
-                    # only; a fill kernel, not a memset: graph.py)
-                    amp = getattr(self, "found_inf", None) is not None
-                    if amp and group["momentum"] != 0 and group["dampening"] != 0:
-                        raise ValueError("MasterSGD under loss scaling needs dampening == 0: a first step skipped by found_inf leaves a zero "
-                                         "momentum buffer, and the next step's momentum * 0 + (1 - dampening) * g is not torch.optim.SGD's first-step buf = g")
-                    st["momentum_buffer"] = (torch.empty_like(w).fill_(0) if amp else torch.empty_like(w)) if group["momentum"] != 0 else None
-                    st["steps"] = 0
-                if first is None:
-                    first = st["steps"] == 0
-                elif first != (st["steps"] == 0):
-                    raise RuntimeError("parameters of one group must have taken the same number of steps")
-                st["steps"] += 1
-                if has16:
-                    if dt16 is None:
-                        dt16 = p.dtype
-                    elif dt16 != p.dtype:
-                        raise RuntimeError("the 16-bit working copies of one group must share a dtype")
-                    is16 = g.dtype == p.dtype
-                    if not is16 and g.dtype != torch.float32:
-                        raise TypeError(f"unsupported gradient dtype {g.dtype} for a {p.dtype} working copy")
-                    if grads16 is None:
-                        grads16 = is16
-                    elif grads16 != is16:
-                        raise RuntimeError("gradients of the 16-bit parameters must be all 16-bit or all fp32")
-                elif g.dtype != torch.float32:
-                    raise TypeError("fp32 parameters need fp32 gradients")
-                # same memory order for master / momentum / gradient / bf16 copy: all carry the parameter's strides
-                if g.stride() != w.stride():
-                    g = g.contiguous(memory_format=torch.channels_last) if w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last) \
-                        else g.contiguous()
-                    keep.append(g)
-                masters.append(w.data_ptr()); moms.append(st["momentum_buffer"].data_ptr() if st["momentum_buffer"] is not None else 0)
-                gptrs.append(g.data_ptr()); p16s.append(p.data.data_ptr() if has16 else 0); ns.append(w.numel())
-            n = len(masters)
-            if n == 0:
-                continue
-            dev = group["params"][0].device
-            scale, found = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)       # (set by GradScaler.step around this call)
-            for t in (scale, found):
-                if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
-                    raise TypeError("grad_scale / found_inf must be CUDA fp32 scalars (torch.amp.GradScaler)")
-            with torch.cuda.device(dev):
-                check(lib.rn_sgd_master_step_ex((C.c_void_p * n)(*masters), (C.c_void_p * n)(*moms), (C.c_void_p * n)(*gptrs),
-                                                (C.c_void_p * n)(*p16s), (C.c_int64 * n)(*ns), n, int(bool(grads16)),
-                                                RN_F16 if dt16 == torch.float16 else RN_BF16, float(group["lr"]),
-                                                float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]),
-                                                int(group["nesterov"]), int(bool(first)), scale.data_ptr() if scale is not None else None,
-                                                found.data_ptr() if found is not None else None, torch.cuda.current_stream().cuda_stream),
-                      "rn_sgd_master_step_ex")
+        recs = [r for r in (self._collect(group, grads) for group in self.param_groups) if r is not None]
+        scale, found = _amp_scalars(self)                                  # (set by GradScaler.step around this call)
+        coef = _clip_coef_ptr(self, recs, scale)                           # (None without a clip: the calls below are the unclipped ones)
+        for r in recs:
+            group, n = r["group"], len(r["masters"])
+            args = ((C.c_void_p * n)(*r["masters"]), (C.c_void_p * n)(*r["moms"]), (C.c_void_p * n)(*r["gptrs"]),
+                    (C.c_void_p * n)(*r["p16s"]), (C.c_int64 * n)(*r["ns"]), n, int(bool(r["grads16"])),
+                    RN_F16 if r["dt16"] == torch.float16 else RN_BF16, float(group["lr"]),
+                    float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]),
+                    int(group["nesterov"]), int(bool(r["first"])), scale.data_ptr() if scale is not None else None,
+                    found.data_ptr() if found is not None else None)
+            with torch.cuda.device(r["dev"]):
+                if coef is None:
+                    check(lib.rn_sgd_master_step_ex(*args, torch.cuda.current_stream().cuda_stream), "rn_sgd_master_step_ex")
+                else:
+                    check(lib.rn_sgd_master_step_clip(*args, coef, torch.cuda.current_stream().cuda_stream), "rn_sgd_master_step_clip")
         from . import biasact
         biasact.invalidate_dgrad_weights()           # (the kernel wrote the parameters through raw pointers: no version counter moved)
         return loss
 
+    def _collect(self, group, grads: Optional[Dict[Tensor, Tensor]]) -> Optional[dict]:
+        "The pointers of one group's step (state created, dtypes and strides checked); None when no parameter has a gradient."
+        masters, moms, gptrs, p16s, ns = [], [], [], [], []
+        grads16 = None
+        dt16 = None
+        first = None
+        keep: List[Tensor] = []
+        for p in group["params"]:
+            g = grads.get(p) if grads is not None else None
+            if g is None:
+                g = p.grad
+            if g is None:
+                continue
+            has16 = hasattr(p, "master")
+            w = p.master if has16 else p.data
+            if w.dtype != torch.float32 or not p.is_cuda:
+                raise TypeError("MasterSGD handles CUDA fp32 parameters and bf16 parameters converted by use_bf16_conv_weights")
+            st = self.state[p]
+            if "momentum_buffer" not in st:
+                # (under a GradScaler the very first step may be SKIPPED by found_inf: the buffer then has to hold zeros, with
+                # which the next step's momentum * buf + (1 - dampening) * g is torch's first-step buf = g -- for dampening == 0
+                # only; a fill kernel, not a memset: graph.py)
+                amp = getattr(self, "found_inf", None) is not None
+                if amp and group["momentum"] != 0 and group["dampening"] != 0:
+                    raise ValueError("MasterSGD under loss scaling needs dampening == 0: a first step skipped by found_inf leaves a zero "
+                                     "momentum buffer, and the next step's momentum * 0 + (1 - dampening) * g is not torch.optim.SGD's first-step buf = g")
+                st["momentum_buffer"] = (torch.empty_like(w).fill_(0) if amp else torch.empty_like(w)) if group["momentum"] != 0 else None
+                st["steps"] = 0
+            if first is None:
+                first = st["steps"] == 0
+            elif first != (st["steps"] == 0):
+                raise RuntimeError("parameters of one group must have taken the same number of steps")
+            st["steps"] += 1
+            if has16:
+                if dt16 is None:
+                    dt16 = p.dtype
+                elif dt16 != p.dtype:
+                    raise RuntimeError("the 16-bit working copies of one group must share a dtype")
+                is16 = g.dtype == p.dtype
+                if not is16 and g.dtype != torch.float32:
+                    raise TypeError(f"unsupported gradient dtype {g.dtype} for a {p.dtype} working copy")
+                if grads16 is None:
+                    grads16 = is16
+                elif grads16 != is16:
+                    raise RuntimeError("gradients of the 16-bit parameters must be all 16-bit or all fp32")
+            elif g.dtype != torch.float32:
+                raise TypeError("fp32 parameters need fp32 gradients")
+            # same memory order for master / momentum / gradient / bf16 copy: all carry the parameter's strides
+            if g.stride() != w.stride():
+                g = g.contiguous(memory_format=torch.channels_last) if w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last) \
+                    else g.contiguous()
+                keep.append(g)
+            masters.append(w.data_ptr()); moms.append(st["momentum_buffer"].data_ptr() if st["momentum_buffer"] is not None else 0)
+            gptrs.append(g.data_ptr()); p16s.append(p.data.data_ptr() if has16 else 0); ns.append(w.numel())
+        if not masters:
+            return None
+        return dict(group=group, masters=masters, moms=moms, gptrs=gptrs, p16s=p16s, ns=ns, grads16=grads16, dt16=dt16, first=first,
+                    keep=keep, dev=group["params"][0].device)
+
 
 RN_ADAM_HPARAMS = 16                    # doubles per group in the device block (include/retinanet_hip.h)
 _HP_STEP = 5                            # the step counter's slot in it
-
-
-def _is_capturing() -> bool:
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
 class _MasterAdamBase(torch.optim.Optimizer):
@@ -185,10 +352,11 @@ class _MasterAdamBase(torch.optim.Optimizer):
     _step_supports_amp_scaling = True
     _rn_master_weights = True
     _rn_device_hparams = True            # lr / betas / eps / weight_decay are read on the device: no part of a captured graph's key
+    _rn_grad_clip = True                 # step() clips by global norm when `grad_clip` holds an optim.GradClip
     _decoupled = False
 
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 amsgrad: bool = False, *, maximize: bool = False):
+                 amsgrad: bool = False, *, maximize: bool = False, max_grad_norm: Optional[float] = None):
         if isinstance(lr, Tensor) or not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr} (a float >= 0)")
         if not 0.0 <= eps:
@@ -202,6 +370,7 @@ class _MasterAdamBase(torch.optim.Optimizer):
             raise ValueError(f"{type(self).__name__} does not implement AMSGrad (amsgrad=True)")
         if maximize:
             raise ValueError(f"{type(self).__name__} does not implement maximize=True")
+        _install_clip(self, max_grad_norm)
         self._blocks: Dict[int, Tensor] = {}         # group index -> its device block (float64[RN_ADAM_HPARAMS])
         self._written: Dict[int, tuple] = {}         # group index -> the hyperparameters last written into it
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False))
@@ -257,80 +426,86 @@ class _MasterAdamBase(torch.optim.Optimizer):
         if not capturing:
             self.sync_device_hparams()
         note_raw_write()                   # masters, 16-bit copies and BN affine parameters change without a _version bump
-        name = type(self).__name__
-        for gi, group in enumerate(self.param_groups):
-            masters, ms, vs, gptrs, p16s, ns = [], [], [], [], [], []
-            grads16 = None
-            dt16 = None
-            keep: List[Tensor] = []
-            had_state = new_state = False
-            for p in group["params"]:
-                g = grads.get(p) if grads is not None else None
-                if g is None:
-                    g = p.grad
-                if g is None:
-                    if "exp_avg" in self.state.get(p, {}):
-                        raise RuntimeError(f"{name}: a parameter with optimizer state has no gradient in this step: the step counter is "
-                                           "one per group, so every parameter of a group must step together")
-                    continue
-                has16 = hasattr(p, "master")
-                w = p.master if has16 else p.data
-                if w.dtype != torch.float32 or not p.is_cuda:
-                    raise TypeError(f"{name} handles CUDA fp32 parameters and 16-bit parameters converted by use_16bit_conv_weights")
-                st = self.state[p]
-                if "exp_avg" not in st:
-                    if capturing:
-                        raise RuntimeError(f"{name}: take one step before capturing one: the moments cannot be created inside a capture")
-                    # same memory order as the master (empty_like keeps the strides); a fill kernel, not a memset (graph.py)
-                    st["exp_avg"] = torch.empty_like(w).fill_(0)
-                    st["exp_avg_sq"] = torch.empty_like(w).fill_(0)
-                    new_state = True
+        recs = [r for r in (self._collect(gi, group, grads, capturing) for gi, group in enumerate(self.param_groups)) if r is not None]
+        scale, found = _amp_scalars(self)                                  # (set by GradScaler.step around this call)
+        for r in recs:
+            if r["gi"] not in self._blocks:
+                self._block(r["gi"], r["dev"])                             # (raises under capture)
+        coef = _clip_coef_ptr(self, recs, scale)                           # (None without a clip: the calls below are the unclipped ones)
+        for r in recs:
+            n = len(r["masters"])
+            args = ((C.c_void_p * n)(*r["masters"]), (C.c_void_p * n)(*r["ms"]), (C.c_void_p * n)(*r["vs"]),
+                    (C.c_void_p * n)(*r["gptrs"]), (C.c_void_p * n)(*r["p16s"]), (C.c_int64 * n)(*r["ns"]), n,
+                    int(bool(r["grads16"])), RN_F16 if r["dt16"] == torch.float16 else RN_BF16, int(self._decoupled),
+                    self._blocks[r["gi"]].data_ptr(), scale.data_ptr() if scale is not None else None,
+                    found.data_ptr() if found is not None else None)
+            with torch.cuda.device(r["dev"]):
+                if coef is None:
+                    check(lib.rn_adam_master_step(*args, torch.cuda.current_stream().cuda_stream), "rn_adam_master_step")
                 else:
-                    had_state = True
-                if has16:
-                    if dt16 is None:
-                        dt16 = p.dtype
-                    elif dt16 != p.dtype:
-                        raise RuntimeError("the 16-bit working copies of one group must share a dtype")
-                    is16 = g.dtype == p.dtype
-                    if not is16 and g.dtype != torch.float32:
-                        raise TypeError(f"unsupported gradient dtype {g.dtype} for a {p.dtype} working copy")
-                    if grads16 is None:
-                        grads16 = is16
-                    elif grads16 != is16:
-                        raise RuntimeError("gradients of the 16-bit parameters must be all 16-bit or all fp32")
-                elif g.dtype != torch.float32:
-                    raise TypeError("fp32 parameters need fp32 gradients")
-                # same memory order for master / moments / gradient / 16-bit copy: all carry the parameter's strides
-                if g.stride() != w.stride():
-                    g = g.contiguous(memory_format=torch.channels_last) if w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last) \
-                        else g.contiguous()
-                    keep.append(g)
-                masters.append(w.data_ptr()); ms.append(st["exp_avg"].data_ptr()); vs.append(st["exp_avg_sq"].data_ptr())
-                gptrs.append(g.data_ptr()); p16s.append(p.data.data_ptr() if has16 else 0); ns.append(w.numel())
-            if had_state and new_state:
-                raise RuntimeError(f"{name}: a parameter joined a group that has already stepped: the step counter is one per group")
-            n = len(masters)
-            if n == 0:
-                continue
-            dev = group["params"][0].device
-            blk = self._blocks.get(gi)
-            if blk is None:
-                blk = self._block(gi, dev)              # (raises under capture)
-            scale, found = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)       # (set by GradScaler.step around this call)
-            for t in (scale, found):
-                if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
-                    raise TypeError("grad_scale / found_inf must be CUDA fp32 scalars (torch.amp.GradScaler)")
-            with torch.cuda.device(dev):
-                check(lib.rn_adam_master_step((C.c_void_p * n)(*masters), (C.c_void_p * n)(*ms), (C.c_void_p * n)(*vs),
-                                              (C.c_void_p * n)(*gptrs), (C.c_void_p * n)(*p16s), (C.c_int64 * n)(*ns), n,
-                                              int(bool(grads16)), RN_F16 if dt16 == torch.float16 else RN_BF16, int(self._decoupled),
-                                              blk.data_ptr(), scale.data_ptr() if scale is not None else None,
-                                              found.data_ptr() if found is not None else None, torch.cuda.current_stream().cuda_stream),
-                      "rn_adam_master_step")
+                    check(lib.rn_adam_master_step_clip(*args, coef, torch.cuda.current_stream().cuda_stream), "rn_adam_master_step_clip")
         from . import biasact
         biasact.invalidate_dgrad_weights()           # (the kernel wrote the parameters through raw pointers: no version counter moved)
         return loss
+
+    def _collect(self, gi: int, group, grads: Optional[Dict[Tensor, Tensor]], capturing: bool) -> Optional[dict]:
+        "The pointers of one group's step (moments created, dtypes and strides checked); None when no parameter has a gradient."
+        name = type(self).__name__
+        masters, ms, vs, gptrs, p16s, ns = [], [], [], [], [], []
+        grads16 = None
+        dt16 = None
+        keep: List[Tensor] = []
+        had_state = new_state = False
+        for p in group["params"]:
+            g = grads.get(p) if grads is not None else None
+            if g is None:
+                g = p.grad
+            if g is None:
+                if "exp_avg" in self.state.get(p, {}):
+                    raise RuntimeError(f"{name}: a parameter with optimizer state has no gradient in this step: the step counter is "
+                                       "one per group, so every parameter of a group must step together")
+                continue
+            has16 = hasattr(p, "master")
+            w = p.master if has16 else p.data
+            if w.dtype != torch.float32 or not p.is_cuda:
+                raise TypeError(f"{name} handles CUDA fp32 parameters and 16-bit parameters converted by use_16bit_conv_weights")
+            st = self.state[p]
+            if "exp_avg" not in st:
+                if capturing:
+                    raise RuntimeError(f"{name}: take one step before capturing one: the moments cannot be created inside a capture")
+                # same memory order as the master (empty_like keeps the strides); a fill kernel, not a memset (graph.py)
+                st["exp_avg"] = torch.empty_like(w).fill_(0)
+                st["exp_avg_sq"] = torch.empty_like(w).fill_(0)
+                new_state = True
+            else:
+                had_state = True
+            if has16:
+                if dt16 is None:
+                    dt16 = p.dtype
+                elif dt16 != p.dtype:
+                    raise RuntimeError("the 16-bit working copies of one group must share a dtype")
+                is16 = g.dtype == p.dtype
+                if not is16 and g.dtype != torch.float32:
+                    raise TypeError(f"unsupported gradient dtype {g.dtype} for a {p.dtype} working copy")
+                if grads16 is None:
+                    grads16 = is16
+                elif grads16 != is16:
+                    raise RuntimeError("gradients of the 16-bit parameters must be all 16-bit or all fp32")
+            elif g.dtype != torch.float32:
+                raise TypeError("fp32 parameters need fp32 gradients")
+            # same memory order for master / moments / gradient / 16-bit copy: all carry the parameter's strides
+            if g.stride() != w.stride():
+                g = g.contiguous(memory_format=torch.channels_last) if w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last) \
+                    else g.contiguous()
+                keep.append(g)
+            masters.append(w.data_ptr()); ms.append(st["exp_avg"].data_ptr()); vs.append(st["exp_avg_sq"].data_ptr())
+            gptrs.append(g.data_ptr()); p16s.append(p.data.data_ptr() if has16 else 0); ns.append(w.numel())
+        if had_state and new_state:
+            raise RuntimeError(f"{name}: a parameter joined a group that has already stepped: the step counter is one per group")
+        if not masters:
+            return None
+        return dict(gi=gi, group=group, masters=masters, ms=ms, vs=vs, gptrs=gptrs, p16s=p16s, ns=ns, grads16=grads16, dt16=dt16,
+                    keep=keep, dev=group["params"][0].device)
 
     # -- checkpoints in torch's Adam format ------------------------------------------------------------------------
     def group_steps(self) -> List[float]:
@@ -388,8 +563,8 @@ class MasterAdam(_MasterAdamBase):
     "``torch.optim.Adam`` (L2 weight decay: g += weight_decay * w) on fp32 masters, capturable: see ``_MasterAdamBase``."
 
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 amsgrad: bool = False, *, maximize: bool = False):
-        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize)
+                 amsgrad: bool = False, *, maximize: bool = False, max_grad_norm: Optional[float] = None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize, max_grad_norm=max_grad_norm)
 
 
 class MasterAdamW(_MasterAdamBase):
@@ -397,5 +572,5 @@ class MasterAdamW(_MasterAdamBase):
     _decoupled = True
 
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 amsgrad: bool = False, *, maximize: bool = False):
-        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize)
+                 amsgrad: bool = False, *, maximize: bool = False, max_grad_norm: Optional[float] = None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize, max_grad_norm=max_grad_norm)

@@ -5,8 +5,8 @@ mapping and the GPU raises a memory access fault (the process aborts) instead of
 ``stem_fwd_kernel`` -- a wave of the last workgroup that owns no tile loaded at a tile index past the last image.
 
 usage: guard_probe.py stem B H W | w3 N H W C | n3 N H W | dense | pw | pool | bottleneck | step KIND MIN MAX | detect DT B H W K [MEAN] |
-       loss DT B H W K T | gt | adam [bf16|f16]                                             (driven by tests/test_guard_gpu.py;
-       gt: by tests/test_gt_capacity_gpu.py; adam: by tests/test_master_adam_gpu.py)
+       loss DT B H W K T | gt | adam [bf16|f16] | clip [bf16|f16]                           (driven by tests/test_guard_gpu.py;
+       gt: by tests/test_gt_capacity_gpu.py; adam: by tests/test_master_adam_gpu.py; clip: by tests/test_grad_clip_gpu.py)
 Prints one "ok ..." line per case; a fault kills the process (non-zero exit status, no "ok" line for the case)."""
 import ctypes as C
 import os
@@ -308,6 +308,93 @@ def main() -> None:
         assert worst < 1e-4, worst
         assert float(hp[5]) == 3.0, float(hp[5])
         print("ok adam", str(dt), n_t, f"{worst:.2e}", flush=True)
+    elif which == "clip":
+        # rn_grad_norm_clip + rn_sgd_master_step_clip + rn_adam_master_step_clip (csrc/clip.hip, optim.hip, adam.hip): 230 tensors (two
+        # norm launches of 224 + 6), every gradient ENDING at the last byte its alignment contract allows in its own mapping (16-bit
+        # gradients 8-byte aligned: the norm kernel's head path; sizes through the tail paths; one tensor of three chunks), the
+        # scratch buffer of exactly the required slots and the clip block at the end of theirs.  The norm against float64, the two
+        # steps against torch fed g * coef.
+        from pytorch_retinanet_amd._lib import RN_F16
+        from pytorch_retinanet_amd.optim import GradClip
+        sizes = [1, 3, 4, 5, 7, 8, 9, 1023, 4097, 16384, 16385, 2 * 16384 + 11] + [(i * 37) % 301 + 1 for i in range(218)]
+        dt = torch.bfloat16 if len(sys.argv) < 3 or sys.argv[2] == "bf16" else torch.float16
+        dt16 = RN_F16 if dt == torch.float16 else RN_BF16
+        g = torch.Generator(device=DEV).manual_seed(11)
+
+        def at_end(src: torch.Tensor, align: int = 16) -> torch.Tensor:
+            nbytes = src.numel() * src.element_size()
+            tot = (nbytes + GRAN - 1) // GRAN * GRAN
+            base = torch.empty((tot,), dtype=torch.uint8, device=DEV)
+            base.fill_(0x7f)
+            _KEEP.append(base)
+            off = (tot - nbytes) // align * align
+            t = base[off: off + nbytes].view(src.dtype)
+            t.copy_(src.reshape(-1))
+            return t
+        n_t = len(sizes)
+        with16 = [i % 3 != 0 for i in range(n_t)]
+        w32 = [torch.randn(n, device=DEV, generator=g) for n in sizes]
+        gs = [(torch.randn(n, device=DEV, generator=g) * 0.1) for n in sizes]
+        gs = [x.to(dt) if h else x for x, h in zip(gs, with16)]
+        gd = [at_end(x * 8.0, 8 if h else 16) for x, h in zip(gs, with16)]            # (scaled by the GradScaler's 8: exact)
+        slots = sum((n + 16383) // 16384 for n in sizes)
+        scratch = at_end(torch.zeros(slots, dtype=torch.float64, device=DEV), 8)
+        blk = at_end(torch.zeros(8, dtype=torch.float64, device=DEV), 8)
+        scale, found = at_end(torch.full((1,), 8.0, device=DEV), 4), at_end(torch.zeros(1, device=DEV), 4)
+        ptrs = lambda ts: (C.c_void_p * n_t)(*[t.data_ptr() if t is not None else 0 for t in ts])
+        check(lib.rn_grad_clip_set(blk.data_ptr(), 0.5, st), "rn_grad_clip_set")
+        p16_flags = [x if h else None for x, h in zip(gd, with16)]
+        check(lib.rn_grad_norm_clip(ptrs(gd), ptrs(p16_flags), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, scale.data_ptr(), scratch.data_ptr(), slots,
+                                    blk.data_ptr(), st), "rn_grad_norm_clip")
+        torch.cuda.synchronize()
+        f32 = blk.view(torch.float32)
+        total, coef = float(f32[1]), float(f32[2])
+        ref = float(torch.linalg.vector_norm(torch.cat([x.double() for x in gs])))
+        assert abs(total - ref) <= 1e-6 * ref, (total, ref)
+        assert coef == GradClip.coef(total, 0.5) and coef < 1.0, (coef, total)
+        assert blk.view(torch.int64)[2:5].tolist() == [1, 1, 0]
+        coef_ptr = blk.data_ptr() + 8
+        clipped = [x.float() * f32[2] for x in gs]
+        # SGD
+        masters = [at_end(w) for w in w32]
+        p16 = [at_end(w.to(dt), 8) if h else None for w, h in zip(w32, with16)]
+        moms = [at_end(torch.zeros(n, device=DEV)) for n in sizes]
+        gd16 = [at_end(x * 8.0) for x in gs]                                           # (the SGD step wants 16-byte aligned gradients)
+        check(lib.rn_sgd_master_step_clip(ptrs(masters), ptrs(moms), ptrs(gd16), ptrs(p16), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, 0.05, 0.9, 0.0,
+                                          1e-2, 0, 1, scale.data_ptr(), found.data_ptr(), coef_ptr, st), "rn_sgd_master_step_clip")
+        ref_p = [torch.nn.Parameter(w.clone()) for w in w32]
+        ropt = torch.optim.SGD(ref_p, lr=0.05, momentum=0.9, weight_decay=1e-2, foreach=False)
+        for prm, x in zip(ref_p, clipped):
+            prm.grad = x
+        ropt.step()
+        torch.cuda.synchronize()
+        for mst, c16, prm in zip(masters, p16, ref_p):
+            torch.testing.assert_close(mst, prm.detach().reshape(-1), rtol=2e-5, atol=1e-6)
+            if c16 is not None:
+                assert torch.equal(c16, mst.to(dt)), "16-bit copy != round(master)"
+        # AdamW
+        masters = [at_end(w) for w in w32]
+        p16 = [at_end(w.to(dt), 8) if h else None for w, h in zip(w32, with16)]
+        ms = [at_end(torch.zeros(n, device=DEV)) for n in sizes]
+        vs = [at_end(torch.zeros(n, device=DEV)) for n in sizes]
+        hp = at_end(torch.zeros(16, dtype=torch.float64, device=DEV), 8)
+        check(lib.rn_adam_hparams_set(hp.data_ptr(), 1e-2, 0.9, 0.999, 1e-8, 0.1, -1.0, st), "rn_adam_hparams_set")
+        check(lib.rn_adam_master_step_clip(ptrs(masters), ptrs(ms), ptrs(vs), ptrs(gd), ptrs(p16), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, 1,
+                                           hp.data_ptr(), scale.data_ptr(), found.data_ptr(), coef_ptr, st), "rn_adam_master_step_clip")
+        ref_p = [torch.nn.Parameter(w.clone()) for w in w32]
+        ropt = torch.optim.AdamW(ref_p, lr=1e-2, weight_decay=0.1, foreach=False)
+        for prm, x in zip(ref_p, clipped):
+            prm.grad = x
+        ropt.step()
+        torch.cuda.synchronize()
+        worst = 0.0
+        for mst, c16, prm in zip(masters, p16, ref_p):
+            worst = max(worst, float(((mst - prm.detach()).abs() / (prm.detach().abs() + 1e-4)).max()))
+            if c16 is not None:
+                assert torch.equal(c16, mst.to(dt)), "16-bit copy != round(master)"
+        assert worst < 1e-4, worst
+        assert float(hp[5]) == 1.0, float(hp[5])
+        print("ok clip", str(dt), n_t, slots, f"norm {total:.6f} coef {coef:.6f} adam {worst:.2e}", flush=True)
     else:
         raise SystemExit(f"unknown probe {which!r}")
 
