@@ -797,6 +797,35 @@ int rn_adam_master_step_clip(float *const *masters, float *const *exp_avgs, floa
                              void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
                              double *hparams, const float *grad_scale, const float *found_inf, const float *clip_coef, void *stream);
 
+/* ---- gradient accumulation into fp32 accumulators for the master optimizers, capturable (csrc/accum.hip) -----
+ * The gradients of N micro-batches summed in fp32, each weighted 1 / N, with everything that changes from one micro-batch to the
+ * next in a DEVICE block, so one captured graph serves every position of a window and a new N needs no capture.
+ * The block: RN_ACCUM_STATE doubles (8-byte aligned, zero-filled by its owner before first use), laid out as
+ *   byte  0  f32 w          float(1.0 / n) (written with n by rn_grad_accum_set, the host's only way in)
+ *   byte  4  i32 n          micro-batches per window
+ *   byte  8  i32 pos        position in the window: micro-batches accumulated since the last final step
+ *   byte 12  f32 found_inf  (RN_ACCUM_FOUND_INF_OFFSET) 1.0f once a non-finite gradient element was read in this window, else 0
+ *   byte 16  i64 windows completed, byte 24 i64 windows that saw a non-finite value, byte 32 i64 micro-batches; the rest reserved.
+ * rn_grad_accumulate: accs / grads / numels are HOST arrays over the tensors of ALL parameter groups; accs[i] is f32 (16-byte
+ * aligned); gradient i is dtype16 (RN_BF16 | RN_F16, 8-byte aligned) when grads16 != 0 and params16 != NULL and params16[i] != NULL
+ * -- the convention of rn_sgd_master_step_ex, params16 itself nullable -- and f32 (16-byte aligned) otherwise.  Per element, in fp32
+ * with two roundings (no fused multiply-add):
+ *   acc = (pos == 0 ? 0.0f : acc) + (float(g) * w)
+ * At pos == 0 the accumulator is overwritten without being read (no zeroing pass).  found_inf becomes 1.0f when any gradient element
+ * is non-finite (a plain store of one value; no atomic).  One workgroup per RN_ACCUM_CHUNK elements of a tensor, one launch per 160
+ * tensors; nothing is read or written beyond numels[i]; pos and w are only read.  No host synchronisation, no memset: capturable.
+ * rn_grad_accum_advance: one single-wave launch, to be enqueued after rn_grad_accumulate (and, in a final step, after the optimizer
+ * and the loss scaler have read found_inf): final == 0: pos += 1; final != 0: the window is counted (and counted as non-finite when
+ * found_inf != 0), pos = 0 and found_inf = 0 -- the next rn_grad_accumulate starts a window.
+ * rn_grad_accum_set: one launch writing n (>= 1) and w = float(1.0 / n); a captured step follows the values last written. */
+#define RN_ACCUM_STATE 8
+#define RN_ACCUM_FOUND_INF_OFFSET 12
+#define RN_ACCUM_CHUNK 16384
+int rn_grad_accum_set(void *block, int n, void *stream);
+int rn_grad_accum_advance(void *block, int final, void *stream);
+int rn_grad_accumulate(float *const *accs, const void *const *grads, void *const *params16, const int64_t *numels, int n_tensors,
+                       int grads16, int dtype16, void *block, void *stream);
+
 /* ---- T1 transform (normalise + resize + pad + batch) -------------------------------------------
  * Replaces torchvision's GeneralizedRCNNTransform as the reference runs it at
  * retinanet/models.py:116 (construction), :262 and :279 (calls): per image (x - mean) / std, bilinear

@@ -124,6 +124,9 @@ SIGNATURES = {
     "rn_sgd_master_step_clip": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _f32, _f32, _f32, C.c_int, C.c_int, _vp, _vp,
                                           _vp, _vp]),
     "rn_adam_master_step_clip": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "rn_grad_accum_set": (C.c_int, [_vp, C.c_int, _vp]),
+    "rn_grad_accum_advance": (C.c_int, [_vp, C.c_int, _vp]),
+    "rn_grad_accumulate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "rn_conv3x3_canvas_to_levels": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               _vp, _vp]),
     "rn_conv3x3_levels_to_canvas": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -22,6 +22,10 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     decisions are drawn inside the step from the object's device block, so eager steps and replays advance one counter and a
     new p needs no capture.  Gradient clipping (``optimizer.grad_clip``, ``optim.GradClip``) is keyed the same way: ``max_norm`` is
     read from the object's device block, whose first (eager) step creates it.
+    Gradient accumulation (``accumulate=optim.GradAccumulator``) is keyed by the installed object too, and the window position is NOT
+    part of the key: it lives in the object's device block.  A signature then holds up to two graphs -- the micro step (zero_grad ->
+    forward -> backward -> accumulate -> advance) and the final step (the same, plus clip + optimizer step on the accumulators + scaler
+    update, then the window reset) -- each warmed by its own ``eager_steps`` eager calls; ``max_graphs`` still counts signatures.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -92,12 +96,13 @@ def _net_targets(targets):
 
 
 class _Entry:
-    __slots__ = ("graph", "images", "targets", "losses", "calls", "failed", "match_state", "segments", "bucket_ids", "pool", "packed")
+    __slots__ = ("graph", "images", "targets", "losses", "calls", "failed", "match_state", "segments", "bucket_ids", "pool", "packed", "micro")
 
     def __init__(self):
         self.graph, self.images, self.targets, self.losses, self.calls, self.failed, self.match_state = None, None, None, None, 0, False, None
         self.segments, self.bucket_ids, self.pool = None, None, None
         self.packed = None        # GT capacity mode: this entry's ops.PackedGT (B x class rows), staged before every call
+        self.micro = None         # gradient accumulation: the signature's second holder (the micro step's graph, buffers and call count)
 
 
 class MemsetNodeInGraph(RuntimeError):
@@ -192,7 +197,8 @@ def retinanet_stage_of(name: str) -> int:
 
 class CapturedTrainStep:
     def __init__(self, net, optimizer, ddp=None, amp_dtype: Optional[torch.dtype] = torch.bfloat16, eager_steps: int = 2,
-                 max_graphs: int = 4, enabled: bool = True, segmented: Optional[bool] = None, scaler=None, gt_capacity=None):
+                 max_graphs: int = 4, enabled: bool = True, segmented: Optional[bool] = None, scaler=None, gt_capacity=None,
+                 accumulate=None):
         """``segmented`` (default: on whenever gradients are exchanged): the step with a gradient exchange as FOUR linear hipGraphs --
         forward + head / FPN backward | layer4, layer3 backward | layer2 .. stem backward | optimizer -- with the finished buckets'
         all-reduces issued EAGERLY on the process group's communication stream between the replays and the wait for them in
@@ -201,8 +207,25 @@ class CapturedTrainStep:
         (DESIGN.md section 6); why not eager: ~20 ms of host time per 25 ms step.  The backward pass is cut at C3 / C4 / C5
         (``backbone.StageCuts``) and run as separate autograd calls, so each segment's capture begins and ends on this thread.
         ``gt_capacity``: None (default: the exact target shapes are part of the signature), "auto" (classes ``GT_CAPACITY_CLASSES``)
-        or increasing positive ints -- the GT capacity mode of the module docstring."""
+        or increasing positive ints -- the GT capacity mode of the module docstring.
+        ``accumulate``: None (default) or an ``optim.GradAccumulator`` -- gradient accumulation.  A call is then a micro step (forward,
+        backward, accumulate) or a final step (the same, then clip + optimizer step on the accumulators): ``stepper(images, targets,
+        final=...)``, the default being the accumulator's own count (every ``accumulate.n``-th call is final).  Single process only."""
         self.gt_capacity = gt_capacity_classes(gt_capacity)
+        if accumulate is not None:
+            from .optim import GradAccumulator
+            if not isinstance(accumulate, GradAccumulator):
+                raise TypeError(f"accumulate must be an optim.GradAccumulator, not {type(accumulate).__name__}")
+            if ddp is not None:
+                raise ValueError("gradient accumulation is single-process only: accumulate= cannot be combined with a gradient exchange "
+                                 "(ddp=); skipping the exchange on micro steps is not implemented")
+            if not getattr(optimizer, "_rn_master_weights", False):
+                raise ValueError(f"accumulate= needs an optimizer that steps on fp32 gradients handed to step(grads=...) "
+                                 f"(optim.MasterSGD / MasterAdam / MasterAdamW), not {type(optimizer).__name__}")
+            if scaler is not None and not hasattr(scaler, "step_exchanged"):
+                raise ValueError("with accumulate= the loss scaler must be a parallel.ExchangeGradScaler: found_inf has to cover every "
+                                 "micro-batch of the window, which the stock GradScaler's look at param.grad does not")
+        self.accumulate = accumulate
         self.net, self.optimizer, self.ddp = net, optimizer, ddp
         # fp16 autocast: a torch.amp.GradScaler (the reference's precision=16 run is native AMP, demo.ipynb).  Its scale / growth
         # tracker are device tensors and optim.MasterSGD takes grad_scale / found_inf on the device, so scale -> backward -> step ->
@@ -272,8 +295,33 @@ class CapturedTrainStep:
         return {"classification_loss": losses["classification_loss"].detach(), "regression_loss": losses["regression_loss"].detach(),
                 "loss": total.detach()}
 
-    def _step(self, images: Sequence[Tensor], targets: Sequence[Dict[str, Tensor]]) -> Dict[str, Tensor]:
+    def _step_accumulating(self, images, targets, final: bool) -> Dict[str, Tensor]:
+        """One micro-batch of an accumulation window: the plain step up to the backward pass, then the gradients into the fp32
+        accumulators; ``final``: clip + optimizer step on the accumulators (+ scaler update), and the window reset."""
+        net, opt, acc = self.net, self.optimizer, self.accumulate
+        opt.zero_grad(set_to_none=True)
+        from .losses import grad_prescale, scaler_prescale
+        pre = scaler_prescale(self.scaler, images[0].device) if images[0].is_cuda else None
+        with torch.autocast(images[0].device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None, cache_enabled=False), grad_prescale(pre):
+            losses = net(list(images), _net_targets(targets))
+            total = losses["classification_loss"] + losses["regression_loss"]
+        # the UNDIVIDED loss goes backward (and to the caller): the 1 / n of the window is the accumulate kernel's weight
+        (self.scaler.scale(total) if self.scaler is not None else total).backward()
+        acc.accumulate(p for g in opt.param_groups for p in g["params"])
+        if final:
+            if self.scaler is not None:
+                self.scaler.step_exchanged(opt, acc)                  # found_inf of the whole window, from the accumulator's block
+                self.scaler.update()
+            else:
+                opt.step(grads=acc.grad_views())
+        acc.advance(final)
+        return {"classification_loss": losses["classification_loss"].detach(), "regression_loss": losses["regression_loss"].detach(),
+                "loss": total.detach()}
+
+    def _step(self, images: Sequence[Tensor], targets: Sequence[Dict[str, Tensor]], final: bool = True) -> Dict[str, Tensor]:
         net, opt, ddp = self.net, self.optimizer, self.ddp
+        if self.accumulate is not None:
+            return self._step_accumulating(images, targets, final)
         if self.segmented:
             return self._staged(images, targets, lambda i: ddp.issue_ready() if i < 3 else None)
         if ddp is not None:
@@ -335,7 +383,10 @@ class CapturedTrainStep:
         clip = getattr(self.optimizer, "grad_clip", None)
         mode = tuple(m.training for m in self.net.modules())
         frozen = tuple(p.requires_grad for p in self.net.parameters())       # (freezing / unfreezing layers changes the launch sequence)
-        return (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype, hflip, clip)
+        key = (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype, hflip, clip)
+        # gradient accumulation (optim.GradAccumulator): the object, as for the clip -- its window position, 1 / n and found_inf are
+        # read from its device block.  Without one the key is exactly the one above.
+        return key if self.accumulate is None else key + (self.accumulate,)
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."
@@ -419,7 +470,7 @@ class CapturedTrainStep:
         ddp.finish()
         e.segments[3].replay()
 
-    def _capture(self, e: _Entry, images, targets) -> None:
+    def _capture(self, e: _Entry, images, targets, final: bool = True) -> None:
         if self.segmented:
             return self._capture_segments(e, images, targets)
         e.images = [im.clone() for im in images]
@@ -430,14 +481,24 @@ class CapturedTrainStep:
         # the fused loss kernel's state words: zero-filled here, OUTSIDE the capture, and owned by this entry (ops.use_match_state)
         e.match_state = ops.new_match_state(e.images[0].device)
         with ops.use_match_state(e.match_state), torch.cuda.graph(g, capture_error_mode="thread_local"):
-            e.losses = self._step(e.images, e.targets)
+            e.losses = self._step(e.images, e.targets, final)
         _repair_memset_nodes(g)
         e.graph = g
         self.captures += 1
 
-    def __call__(self, images: Sequence[Tensor], targets: Sequence[Dict[str, Tensor]]) -> Dict[str, Tensor]:
+    def __call__(self, images: Sequence[Tensor], targets: Sequence[Dict[str, Tensor]], final: Optional[bool] = None) -> Dict[str, Tensor]:
+        """``final`` (gradient accumulation only): whether this call completes the window and steps the optimizer; None = the
+        accumulator's own count (every ``n``-th call since the last final one).  Without ``accumulate=`` every call is a whole step."""
+        acc = self.accumulate
+        if acc is None:
+            if final is not None and not final:
+                raise ValueError("final=False needs a CapturedTrainStep(accumulate=optim.GradAccumulator(...))")
+            final = True
+        elif final is None:
+            final = acc.next_is_final()
+        final = bool(final)
         if not self.enabled or not images or not images[0].is_cuda:
-            return self._step(images, targets)
+            return self._step(images, targets, final)
         key = self._signature(images, targets)
         cap = self._capacity_of(targets)
         e = self._entries.get(key)
@@ -449,6 +510,13 @@ class CapturedTrainStep:
                 self._entries.popitem(last=False)            # drops the graph and its private memory pool
         else:
             self._entries.move_to_end(key)
+        sig = e                                               # (the signature's entry: GT staging buffers)
+        if acc is not None and not final:
+            # the micro step's graph, static buffers and warm-up count: a second holder inside the signature's entry
+            if sig.micro is None:
+                sig.micro = _Entry()
+                sig.micro.packed = sig.packed
+            e = sig.micro
         e.calls += 1
         if e.packed is not None:
             # GT capacity mode: this batch's GT into the entry's static buffers (one launch, current stream), for eager steps,
@@ -456,10 +524,10 @@ class CapturedTrainStep:
             ops.gt_stage([t["boxes"] for t in targets], [t["labels"] for t in targets], e.packed)
             targets = e.packed
         if e.failed or e.calls <= self.eager_steps:
-            return self._step(images, targets)
+            return self._step(images, targets, final)
         if e.graph is None and e.segments is None:
             try:
-                self._capture(e, images, targets)
+                self._capture(e, images, targets, final)
             except Exception as exc:                          # noqa: BLE001 -- a step that cannot be captured still has to run
                 _log.warning("train-step capture failed (%s: %s); this input signature runs eagerly", type(exc).__name__, exc)
                 e.failed, e.graph, e.images, e.targets, e.losses, e.segments = True, None, None, None, None, None
@@ -471,7 +539,7 @@ class CapturedTrainStep:
                 if stuck is not None:
                     raise CaptureUnwindError(f"the failed capture ({type(exc).__name__}: {exc}) left the device in stream-capture mode "
                                              f"({type(stuck).__name__}: {stuck}); this process cannot run further GPU work") from exc
-                return self._step(images, targets)
+                return self._step(images, targets, final)
         else:
             # the step's inputs into the graph's static buffers: one multi-tensor launch per dtype for what already lives on the
             # device (24 separate copies cost 0.19 ms per step), plain copies for the rest
@@ -496,6 +564,8 @@ class CapturedTrainStep:
             self._replay_segments(e)
         else:
             e.graph.replay()
+        if acc is not None:
+            acc.note_step(final)                              # (the replayed advance moved the device's window position)
         note_raw_write()                                      # parameters and BN statistics changed behind torch's back
         self.replays += 1
         return e.losses

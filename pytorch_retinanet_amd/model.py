@@ -188,6 +188,25 @@ class RetinaNetModel(_Base):
         return {"AP": metric, "log": logs, "progress_bar": logs}
 
 
+def _with_last(loader):
+    "``(index, batch, is_last)`` over ``loader``, one batch ahead (works for loaders without a length)."
+    it = iter(loader)
+    try:
+        nxt = next(it)
+    except StopIteration:
+        return
+    i = 0
+    while True:
+        cur = nxt
+        try:
+            nxt = next(it)
+        except StopIteration:
+            yield i, cur, True
+            return
+        yield i, cur, False
+        i += 1
+
+
 def _to_device(batch, device):
     images, targets, ids = batch
     images = [im.to(device, non_blocking=True) for im in images]
@@ -204,7 +223,7 @@ class SimpleTrainer:
 
     def __init__(self, max_epochs: int = 1, device: Optional[str] = None, precision: str = "bf16",
                  channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True,
-                 gt_capacity=None, gradient_clip_val: float = 0.0):
+                 gt_capacity=None, gradient_clip_val: float = 0.0, accumulate_grad_batches: int = 1):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
@@ -220,8 +239,21 @@ class SimpleTrainer:
         ``MasterAdamW`` the trainer installs an ``optim.GradClip`` on the optimizer (``self.grad_clip``) and nothing else changes: the
         norm and the scaling run on the device inside the step, capture stays on, and under ``torch.distributed`` the clip sees the
         exchanged gradients, so every rank computes the same coefficient.  Any other optimizer: one process only, eagerly (capture is
-        turned off for the run, with a log line), ``torch.nn.utils.clip_grad_norm_`` after ``scaler.unscale_``."""
+        turned off for the run, with a log line), ``torch.nn.utils.clip_grad_norm_`` after ``scaler.unscale_``.
+
+        ``accumulate_grad_batches`` (Lightning's name and default; an int >= 1, dict schedules are refused; left at 1, an optional
+        ``trainer.accumulate_grad_batches`` in the hparams is honoured): N micro-batches per optimizer step, Lightning's semantics --
+        each contributes ``loss / N``, the optimizer steps after every N-th batch of an epoch and after its last batch (with whatever
+        the window holds, still weighted 1 / N), ``interval: step`` schedulers, ``max_steps``, ``log_every`` and the return value of
+        ``fit`` count OPTIMIZER steps, and the loss that is logged is the undivided micro-batch loss.  With a master optimizer on CUDA
+        the trainer installs an ``optim.GradAccumulator`` (``self.grad_accumulator``): the micro-batch gradients are summed in fp32 on
+        the device inside the step and capture stays on (a micro graph and a final graph per batch signature).  Any other optimizer
+        or device: eagerly, ``(loss / N).backward()`` into ``.grad``, then step and zero every N; this composes with the torch clip
+        and the stock ``GradScaler`` (unscaled once, at the step).  Single process only: N > 1 under ``torch.distributed`` raises."""
         from .graph import gt_capacity_classes
+        from .optim import check_accumulate_grad_batches
+        self.accumulate_grad_batches = check_accumulate_grad_batches(accumulate_grad_batches)
+        self.grad_accumulator = None                      # the optim.GradAccumulator of the last fit() (master optimizers on CUDA)
         self.gradient_clip_val = float(gradient_clip_val or 0.0)
         if not self.gradient_clip_val >= 0.0:
             raise ValueError(f"gradient_clip_val must be >= 0 (0 = off), got {gradient_clip_val}")
@@ -245,6 +277,15 @@ class SimpleTrainer:
             raise ValueError(f"trainer.gradient_clip_val must be >= 0 (0 = off), got {value}")
         return value
 
+    def resolve_accumulate_grad_batches(self, conf) -> int:
+        "The constructor's ``accumulate_grad_batches`` or, when that is 1, ``trainer.accumulate_grad_batches`` of the hparams (absent: 1)."
+        from .optim import check_accumulate_grad_batches
+        if self.accumulate_grad_batches > 1:
+            return self.accumulate_grad_batches
+        section = conf.get("trainer") if hasattr(conf, "get") else None
+        value = (section or {}).get("accumulate_grad_batches")
+        return 1 if value is None else check_accumulate_grad_batches(value, "trainer.accumulate_grad_batches")
+
     def _autocast(self):
         return torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype is not None and self.device.type == "cuda")
 
@@ -259,6 +300,10 @@ class SimpleTrainer:
         opt = model.configure_optimizers()
         optimizers, schedulers = (opt if isinstance(opt, tuple) else (opt, []))
         optimizer = optimizers[0]
+        n_acc = self.resolve_accumulate_grad_batches(model.conf)
+        if n_acc > 1 and dist.is_available() and dist.is_initialized():
+            raise ValueError(f"accumulate_grad_batches={n_acc} under torch.distributed is not supported: gradient accumulation is "
+                             "single-process only (skipping the exchange on micro steps is not implemented)")
         ddp = BucketedGradAllReduce(model.net) if dist.is_available() and dist.is_initialized() else None
         hflip = getattr(model.net.transform, "hflip", None)
         if hflip is not None and ddp is not None:
@@ -267,7 +312,15 @@ class SimpleTrainer:
         # fp16 gradients of a focal loss normalised by num_fg underflow without it
         # (under a gradient exchange: parallel.ExchangeGradScaler -- found_inf from the exchanged buckets, one decision for all ranks)
         from .parallel import ExchangeGradScaler
-        scaler = (ExchangeGradScaler("cuda") if ddp is not None else torch.amp.GradScaler("cuda")) \
+        # gradient accumulation: fp32 accumulators on the device for the master optimizers, .grad for everything else
+        device_acc = (n_acc > 1 and self.device.type == "cuda" and getattr(optimizer, "_rn_master_weights", False)
+                      and type(model).training_step is RetinaNetModel.training_step)
+        self.grad_accumulator = None
+        if device_acc:
+            from .optim import GradAccumulator
+            self.grad_accumulator = GradAccumulator(n_acc)
+        # (the accumulator hands found_inf of the whole window to the scaler: ExchangeGradScaler.step_exchanged takes it)
+        scaler = (ExchangeGradScaler("cuda") if ddp is not None or device_acc else torch.amp.GradScaler("cuda")) \
             if (self.amp_dtype == torch.float16 and self.device.type == "cuda") else None
         # gradient clipping: on the device inside the step for the master optimizers, torch's clip_grad_norm_ for the others
         clip_val = self.resolve_gradient_clip_val(model.conf)
@@ -291,25 +344,50 @@ class SimpleTrainer:
                                   "(the master optimizers clip inside the captured step)", clip_val, type(optimizer).__name__)
         grad_norm = None
         stepper = None
-        if (self.capture and not torch_clip and self.device.type == "cuda" and ddp is None and type(model).training_step is RetinaNetModel.training_step
-                and (getattr(optimizer, "_rn_device_hparams", False)
-                     or not any(s["interval"] == "step" and "monitor" not in s for s in schedulers))):
+        capturable = (self.capture and not torch_clip and (n_acc == 1 or device_acc) and self.device.type == "cuda" and ddp is None
+                      and type(model).training_step is RetinaNetModel.training_step
+                      and (getattr(optimizer, "_rn_device_hparams", False)
+                           or not any(s["interval"] == "step" and "monitor" not in s for s in schedulers)))
+        if capturable or device_acc:
             from .graph import CapturedTrainStep
-            stepper = CapturedTrainStep(model.net, optimizer, None, amp_dtype=self.amp_dtype, scaler=scaler, gt_capacity=self.gt_capacity)
+            # (device accumulation without capture: the same step object runs eagerly, so the gradients are still summed in fp32)
+            stepper = CapturedTrainStep(model.net, optimizer, None, amp_dtype=self.amp_dtype, scaler=scaler, gt_capacity=self.gt_capacity,
+                                        accumulate=self.grad_accumulator, enabled=bool(capturable))
         step = 0
         for epoch in range(self.max_epochs):
             model.train()
             loader = model.train_dataloader()
             if hasattr(getattr(loader, "sampler", None), "set_epoch"):
                 loader.sampler.set_epoch(epoch)
-            for i, batch in enumerate(loader):
+            for i, batch, last in (_with_last(loader) if n_acc > 1 else ((j, b, False) for j, b in enumerate(loader))):
                 batch = _to_device(batch, self.device)
+                # accumulation windows restart with every epoch and the last batch of an epoch always steps (Lightning)
+                final = n_acc == 1 or (i + 1) % n_acc == 0 or last
                 if stepper is not None:
                     # the same step (zero_grad -> autocast forward -> loss = sum of the dict -> backward -> optimizer.step) as ONE graph replay
                     images, targets, _ = batch
-                    out = stepper(list(images), [{k: v for k, v in t.items() if isinstance(v, torch.Tensor) and k in ("boxes", "labels")}
-                                                 for t in targets])
+                    tgs = [{k: v for k, v in t.items() if isinstance(v, torch.Tensor) and k in ("boxes", "labels")} for t in targets]
+                    out = stepper(list(images), tgs, final=final) if device_acc else stepper(list(images), tgs)
                     self.captured_steps = stepper.replays
+                elif n_acc > 1:
+                    # the plain thing: every micro-batch adds (loss / N)'s gradients into .grad; step and zero at the end of the window
+                    from .losses import grad_prescale, scaler_prescale
+                    with self._autocast(), grad_prescale(scaler_prescale(scaler, self.device)):
+                        out = model.training_step(batch, i)
+                    if i % n_acc == 0:
+                        optimizer.zero_grad(set_to_none=False)
+                    part = out["loss"] / n_acc
+                    (scaler.scale(part) if scaler is not None else part).backward()
+                    if final:
+                        if torch_clip:
+                            if scaler is not None:
+                                scaler.unscale_(optimizer)
+                            grad_norm = torch.nn.utils.clip_grad_norm_(model.net.parameters(), clip_val)
+                        if scaler is not None:
+                            scaler.step(optimizer)
+                            scaler.update()
+                        else:
+                            optimizer.step()
                 else:
                     from .losses import grad_prescale, scaler_prescale
                     with self._autocast(), grad_prescale(scaler_prescale(scaler, self.device)):
@@ -336,6 +414,8 @@ class SimpleTrainer:
                             optimizer.step(grads=ddp.grad_views())       # fp32 bucket views of the bf16 working copies
                         else:
                             optimizer.step()
+                if not final:
+                    continue                                  # (schedulers, max_steps and the log count optimizer steps)
                 step += 1
                 if step % self.log_every == 0:
                     if self.grad_clip is not None or grad_norm is not None:

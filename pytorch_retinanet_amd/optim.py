@@ -18,6 +18,10 @@ hyperparameter and the step counter in a device block per parameter group: a cap
 gradient gives the global L2 norm and the clip coefficient in a device block, and the step kernels multiply the coefficient into each
 gradient as they read it.  No gradient is rewritten, nothing synchronises, and ``max_norm`` lives on the device: the clipped step
 captures like the plain one.
+
+``GradAccumulator`` -- Lightning's ``accumulate_grad_batches`` for the three of them (``rn_grad_accumulate``, ``csrc/accum.hip``): the
+gradients of N micro-batches summed into fp32 accumulators (never in 16 bits), the window position, 1 / N and found_inf in a device
+block, the optimizer stepping on the accumulators through ``step(grads=...)``: one micro graph and one final graph per batch signature.
 """
 import ctypes as C
 from typing import Dict, Iterable, List, Optional
@@ -194,6 +198,180 @@ class GradClip:
             return {"calls": 0, "clipped": 0, "nonfinite": 0}
         calls, clipped, nonfinite = self._block.view(torch.int64)[2:5].tolist()
         return {"calls": calls, "clipped": clipped, "nonfinite": nonfinite}
+
+
+RN_ACCUM_STATE = 8                      # doubles in the accumulation block (include/retinanet_hip.h)
+_ACCUM_FOUND_INF = 3                    # found_inf's index among the block's 32-bit words (byte 12)
+
+
+def check_accumulate_grad_batches(value, what: str = "accumulate_grad_batches") -> int:
+    "``value`` as a window length: an int >= 1 (Lightning's ``accumulate_grad_batches``); dict schedules and anything else are refused."
+    if isinstance(value, dict):
+        raise ValueError(f"{what}: dict schedules ({{epoch: batches}}) are not supported, pass one int >= 1 (got {value!r})")
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) < 1:
+        raise ValueError(f"{what} must be an int >= 1, got {value!r}")
+    if int(value) >= 1 << 24:
+        raise ValueError(f"{what} must be below 2**24, got {value!r}")
+    return int(value)
+
+
+class GradAccumulator:
+    """Gradient accumulation over ``n`` micro-batches for ``MasterSGD`` / ``MasterAdam`` / ``MasterAdamW`` -- Lightning's
+    ``accumulate_grad_batches`` -- into fp32 accumulators: after every backward pass ``accumulate(params)`` adds ``float(p.grad) *
+    float(1 / n)`` to the parameter's accumulator (one ``rn_grad_accumulate`` call over all of them, ``csrc/accum.hip``; the first
+    micro-batch of a window overwrites, so nothing is ever zeroed) and ``advance(final)`` moves the window on; the final step of a
+    window hands ``grad_views()`` to ``optimizer.step(grads=...)`` first.  The 16-bit gradients of the conv weights are widened before
+    they are added: autograd's own ``.grad +=`` would sum them in bf16 / fp16.
+
+        for i, batch in enumerate(batches):
+            optimizer.zero_grad(set_to_none=True); loss(batch).backward()
+            acc.accumulate(net.parameters())
+            final = acc.next_is_final()                  # or the caller's own rule (the last batch of an epoch)
+            if final:
+                optimizer.step(grads=acc.grad_views())   # (fp16: scaler.step_exchanged(optimizer, acc); scaler.update())
+            acc.advance(final)
+
+    The window position, ``float(1 / n)`` and ``found_inf`` live in a device block that the kernels read: a captured micro step is the
+    same graph at every position, and assigning ``n`` (between windows only) is one tiny launch, no re-capture.  ``found_inf()`` is
+    the block's flag -- 1.0 once any micro-batch of the window held a non-finite gradient element, cleared by the final ``advance`` --
+    and with ``grad_views()`` makes this object what ``parallel.ExchangeGradScaler.step_exchanged`` takes in place of a gradient
+    exchange: the step is skipped and the scale backs off when ANY micro-batch of the window overflowed.  The accumulators and the
+    block are created by the first ``accumulate`` -- not inside a capture -- and kept for good (captured steps hold their addresses).
+    ``position`` / ``stats()`` read the block (they synchronise)."""
+
+    def __init__(self, n: int = 1):
+        self._n = check_accumulate_grad_batches(n, "GradAccumulator: n")
+        self._block: Optional[Tensor] = None          # float64[RN_ACCUM_STATE] on the device of the first gradient (kept for good)
+        self._acc: Dict[Tensor, Tensor] = {}          # parameter -> its fp32 accumulator (the master's / parameter's strides)
+        self._host_pos = 0                            # the host's mirror of the window position (micro steps since the last final one)
+
+    def __repr__(self) -> str:
+        return f"GradAccumulator(n={self._n})"
+
+    # -- the device block ---------------------------------------------------------------------------------------------
+    @property
+    def n(self) -> int:
+        return self._n
+
+    @n.setter
+    def n(self, value: int) -> None:
+        "A new window length: written into the device block (no re-capture needed); between windows only, not inside a capture."
+        value = check_accumulate_grad_batches(value, "GradAccumulator: n")
+        if self._host_pos != 0:
+            raise RuntimeError(f"GradAccumulator: n cannot change in mid-window ({self._host_pos} micro-batch(es) of the current window "
+                               f"are already weighted 1 / {self._n}); finish the window with a final step first")
+        if self._block is not None:
+            if _is_capturing():
+                raise RuntimeError("GradAccumulator: n cannot be set inside a capture (the write would replay the value of capture time)")
+            self._write_n(value)
+        self._n = value
+
+    def _write_n(self, value: int) -> None:
+        dev = self._block.device
+        with torch.cuda.device(dev):
+            check(lib.rn_grad_accum_set(self._block.data_ptr(), int(value), torch.cuda.current_stream(dev).cuda_stream), "rn_grad_accum_set")
+
+    def _ensure_block(self, device: torch.device) -> None:
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._block is None:
+            if _is_capturing():
+                raise RuntimeError("GradAccumulator: take one step before capturing one: its device block cannot be created inside a capture")
+            self._block = torch.empty(RN_ACCUM_STATE, dtype=torch.float64, device=device).fill_(0)     # (a fill kernel, not a memset: graph.py)
+            self._write_n(self._n)
+        elif self._block.device != device:
+            raise RuntimeError(f"GradAccumulator: its state lives on {self._block.device}, not {device}; use one object per device")
+
+    # -- the window -------------------------------------------------------------------------------------------------
+    def next_is_final(self) -> bool:
+        "Whether the micro-batch about to be accumulated completes the window (the host's count of the steps since the last final one)."
+        return self._host_pos + 1 >= self._n
+
+    def note_step(self, final: bool) -> None:
+        "Advance the host's mirror of the window position (``advance`` does it for eager steps, ``graph.CapturedTrainStep`` for replays)."
+        self._host_pos = 0 if final else self._host_pos + 1
+
+    @torch.no_grad()
+    def accumulate(self, params: Iterable[Tensor]) -> int:
+        """One ``rn_grad_accumulate`` call on the current stream over every parameter of ``params`` that has a ``.grad``; returns the
+        number of gradients added.  A parameter met for the first time gets its accumulator here (not inside a capture)."""
+        accs, gptrs, is16, ns = [], [], [], []
+        keep: List[Tensor] = []
+        dt16 = None
+        dev = None
+        for p in params:
+            g = p.grad
+            if g is None:
+                continue
+            if not g.is_cuda:
+                raise RuntimeError("GradAccumulator has no CPU fallback: it accumulates CUDA gradients (SimpleTrainer accumulates into "
+                                   ".grad for every other device)")
+            dev = g.device if dev is None else dev
+            w = p.master if hasattr(p, "master") else p.data
+            if w.dtype != torch.float32:
+                raise TypeError("GradAccumulator handles CUDA fp32 parameters and 16-bit parameters converted by use_16bit_conv_weights")
+            a = self._acc.get(p)
+            if a is None:
+                if _is_capturing():
+                    raise RuntimeError("GradAccumulator: take one step before capturing one: the accumulators cannot be created inside a capture")
+                a = self._acc[p] = torch.empty_like(w)              # the master's strides; overwritten by the window's first micro-batch
+                if self._host_pos != 0:
+                    a.fill_(0)                                      # (a parameter that joins in mid-window starts from zero)
+            if g.dtype in (torch.bfloat16, torch.float16):
+                if dt16 is None:
+                    dt16 = g.dtype
+                elif dt16 != g.dtype:
+                    raise RuntimeError("the 16-bit gradients of one accumulation must share a dtype")
+            elif g.dtype != torch.float32:
+                raise TypeError(f"unsupported gradient dtype {g.dtype}")
+            if g.stride() != a.stride():                            # same memory order for the accumulator and the gradient
+                g = g.contiguous(memory_format=torch.channels_last) if a.dim() == 4 and a.is_contiguous(memory_format=torch.channels_last) \
+                    else g.contiguous()
+                keep.append(g)
+            accs.append(a.data_ptr()); gptrs.append(g.data_ptr()); ns.append(a.numel())
+            is16.append(g.data_ptr() if g.dtype != torch.float32 else 0)
+        if not accs:
+            return 0
+        self._ensure_block(dev)
+        n = len(accs)
+        with torch.cuda.device(self._block.device):
+            check(lib.rn_grad_accumulate((C.c_void_p * n)(*accs), (C.c_void_p * n)(*gptrs), (C.c_void_p * n)(*is16), (C.c_int64 * n)(*ns), n, 1,
+                                         RN_F16 if dt16 == torch.float16 else RN_BF16, self._block.data_ptr(),
+                                         torch.cuda.current_stream().cuda_stream), "rn_grad_accumulate")
+        return n
+
+    def advance(self, final: bool) -> None:
+        """One ``rn_grad_accum_advance`` launch on the current stream, after ``accumulate`` (and, for a final step, after the optimizer
+        and the scaler): a micro step moves the position on; a final one counts the window, resets the position and clears found_inf."""
+        if self._block is None:
+            raise RuntimeError("GradAccumulator: nothing has been accumulated yet (the device block is created by the first accumulate)")
+        with torch.cuda.device(self._block.device):
+            check(lib.rn_grad_accum_advance(self._block.data_ptr(), int(bool(final)), torch.cuda.current_stream().cuda_stream),
+                  "rn_grad_accum_advance")
+        if not _is_capturing():                       # (a captured launch runs at its replays: CapturedTrainStep notes those)
+            self.note_step(final)
+
+    def grad_views(self) -> Dict[Tensor, Tensor]:
+        "``{parameter: its fp32 accumulator}`` -- what ``optimizer.step(grads=...)`` of the master optimizers consumes."
+        return dict(self._acc)
+
+    def found_inf(self) -> Tensor:
+        "The window's flag (device fp32 scalar, a view into the block): 1.0 once a non-finite gradient element was accumulated, else 0."
+        if self._block is None:
+            raise RuntimeError("GradAccumulator: nothing has been accumulated yet (the device block is created by the first accumulate)")
+        return self._block.view(torch.float32)[_ACCUM_FOUND_INF]
+
+    @property
+    def position(self) -> int:
+        "The window position on the device: micro-batches accumulated since the last final step (reads the block: synchronises)."
+        return 0 if self._block is None else int(self._block.view(torch.int32)[2])
+
+    def stats(self) -> Dict[str, int]:
+        "Windows completed, windows that saw a non-finite gradient, and micro-batches accumulated (reads the block: synchronises)."
+        if self._block is None:
+            return {"windows": 0, "nonfinite": 0, "micro_batches": 0}
+        windows, nonfinite, micro = self._block.view(torch.int64)[2:5].tolist()
+        return {"windows": windows, "nonfinite": nonfinite, "micro_batches": micro}
 
 
 def _amp_scalars(opt):

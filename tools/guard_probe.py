@@ -5,8 +5,9 @@ mapping and the GPU raises a memory access fault (the process aborts) instead of
 ``stem_fwd_kernel`` -- a wave of the last workgroup that owns no tile loaded at a tile index past the last image.
 
 usage: guard_probe.py stem B H W | w3 N H W C | n3 N H W | dense | pw | pool | bottleneck | step KIND MIN MAX | detect DT B H W K [MEAN] |
-       loss DT B H W K T | gt | adam [bf16|f16] | clip [bf16|f16]                           (driven by tests/test_guard_gpu.py;
-       gt: by tests/test_gt_capacity_gpu.py; adam: by tests/test_master_adam_gpu.py; clip: by tests/test_grad_clip_gpu.py)
+       loss DT B H W K T | gt | adam [bf16|f16] | clip [bf16|f16] | accum [bf16|f16]        (driven by tests/test_guard_gpu.py;
+       gt: by tests/test_gt_capacity_gpu.py; adam: by tests/test_master_adam_gpu.py; clip: by tests/test_grad_clip_gpu.py;
+       accum: by tests/test_grad_accum_gpu.py)
 Prints one "ok ..." line per case; a fault kills the process (non-zero exit status, no "ok" line for the case)."""
 import ctypes as C
 import os
@@ -395,6 +396,51 @@ def main() -> None:
         assert worst < 1e-4, worst
         assert float(hp[5]) == 1.0, float(hp[5])
         print("ok clip", str(dt), n_t, slots, f"norm {total:.6f} coef {coef:.6f} adam {worst:.2e}", flush=True)
+    elif which == "accum":
+        # rn_grad_accumulate (csrc/accum.hip): 170 tensors (two launches of 160 + 10), every gradient and every accumulator ENDING at
+        # the last byte its alignment contract allows in its own mapping (16-bit gradients 8-byte aligned: the head path; sizes
+        # through the tail paths; one tensor of three chunks), the block at the end of its own.  A window of three micro-batches
+        # (overwrite, then two adds) against the torch restatement, bit for bit.
+        from pytorch_retinanet_amd._lib import RN_F16
+        sizes = [1, 3, 4, 5, 7, 8, 9, 1023, 4097, 16384, 16385, 2 * 16384 + 11] + [(i * 37) % 301 + 1 for i in range(158)]
+        dt = torch.bfloat16 if len(sys.argv) < 3 or sys.argv[2] == "bf16" else torch.float16
+        dt16 = RN_F16 if dt == torch.float16 else RN_BF16
+        g = torch.Generator(device=DEV).manual_seed(13)
+
+        def at_end(src: torch.Tensor, align: int = 16) -> torch.Tensor:
+            nbytes = src.numel() * src.element_size()
+            tot = (nbytes + GRAN - 1) // GRAN * GRAN
+            base = torch.empty((tot,), dtype=torch.uint8, device=DEV)
+            base.fill_(0x7f)
+            _KEEP.append(base)
+            off = (tot - nbytes) // align * align
+            t = base[off: off + nbytes].view(src.dtype)
+            t.copy_(src.reshape(-1))
+            return t
+        n_t = len(sizes)
+        with16 = [i % 3 != 0 for i in range(n_t)]
+        accs = [at_end(torch.full((n,), float("nan"), device=DEV)) for n in sizes]
+        blk = at_end(torch.zeros(8, dtype=torch.float64, device=DEV), 8)
+        ptrs = lambda ts: (C.c_void_p * n_t)(*[t.data_ptr() if t is not None else 0 for t in ts])
+        N = 3
+        check(lib.rn_grad_accum_set(blk.data_ptr(), N, st), "rn_grad_accum_set")
+        w = torch.tensor(1.0 / N, dtype=torch.float32, device=DEV)
+        want = [torch.zeros(n, device=DEV) for n in sizes]
+        for k in range(N):
+            gs = [(torch.randn(n, device=DEV, generator=g) * 0.1) for n in sizes]
+            gs = [x.to(dt) if h else x for x, h in zip(gs, with16)]
+            gd = [at_end(x, 8 if h else 16) for x, h in zip(gs, with16)]
+            flags = [x if h else None for x, h in zip(gd, with16)]
+            check(lib.rn_grad_accumulate(ptrs(accs), ptrs(gd), ptrs(flags), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, blk.data_ptr(), st),
+                  "rn_grad_accumulate")
+            check(lib.rn_grad_accum_advance(blk.data_ptr(), int(k == N - 1), st), "rn_grad_accum_advance")
+            want = [a + x.float() * w for a, x in zip(want, gs)]
+        torch.cuda.synchronize()
+        for a, r in zip(accs, want):
+            assert torch.equal(a, r), "accumulator != restatement"
+        assert blk.view(torch.int32)[1:3].tolist() == [N, 0] and float(blk.view(torch.float32)[3]) == 0.0
+        assert blk.view(torch.int64)[2:5].tolist() == [1, 0, N]
+        print("ok accum", str(dt), n_t, sum(sizes), flush=True)
     else:
         raise SystemExit(f"unknown probe {which!r}")
 
