@@ -726,20 +726,23 @@ int rn_fpn_upsample2x_backward(const void *g, void *dtop, int dtype, int N, int 
  * The update torch.optim.SGD performs (the reference's optimizer, hparams.yaml:63-68), in its order, in fp32:
  *   g = grad + weight_decay * w;  buf = first_step ? g : momentum * buf + (1 - dampening) * g;
  *   g = nesterov ? g + momentum * buf : buf;  w -= lr * g
- * for n_tensors tensors in one launch per 48 (HOST arrays of device pointers / element counts).  params16[i]
- * (nullable): bf16 copy of tensor i, rewritten as bf16(w) -- the conv weights the bf16 forward consumes, so that
- * neither autocast's per-step weight casts nor the bf16 -> fp32 gradient casts are needed; when grads16 != 0 the
- * gradient of a tensor WITH a 16-bit copy is bf16, every other gradient is f32. */
+ * for n_tensors tensors in one launch per 48 (HOST arrays of device pointers / element counts; every tensor is checked before the
+ * first launch, so an invalid argument changes nothing).  masters / momenta (nullable entries when momentum == 0) f32, 16-byte
+ * aligned.  params16[i] (nullable, 8-byte aligned): the 16-bit copy of tensor i (dtype16 = RN_BF16 or RN_F16), rewritten as
+ * round(w) -- the conv weights the 16-bit forward consumes, so that neither autocast's per-step weight casts nor the 16-bit -> fp32
+ * gradient casts are needed; when grads16 != 0 the gradient of a tensor WITH a 16-bit copy is dtype16, every other gradient is f32
+ * (all gradients 16-byte aligned).
+ * grad_scale / found_inf (nullable DEVICE scalars, f32) are what torch.amp.GradScaler hands an optimizer with
+ * `_step_supports_amp_scaling`: every gradient is divided by grad_scale[0] first, and when found_inf[0] != 0 the launch changes
+ * nothing (no parameter, no momentum buffer) -- no host synchronisation, so the step stays capturable.
+ * clip_coef (nullable DEVICE f32 scalar: the clip_coef of rn_grad_norm_clip's block, below) enters as
+ *   g = (float(grad) * (1 / grad_scale[0])) * clip_coef[0]
+ * -- GradScaler.unscale_ followed by clip_grad_norm_ on fp32 gradients, never rounded to 16 bits in between -- before weight decay
+ * touches g.  clip_coef == NULL: the unclipped step. */
 int rn_sgd_master_step(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
-                       const int64_t *numels, int n_tensors, int grads16, float lr, float momentum, float dampening,
-                       float weight_decay, int nesterov, int first_step, void *stream);
-/* The same step for fp16 working copies and for fp16 autocast under a loss scale (ABI 8): dtype16 = RN_BF16 or RN_F16 is the type of
- * params16[i] (and of the 16-bit gradients); grad_scale / found_inf (nullable DEVICE scalars, f32) are what torch.amp.GradScaler hands
- * an optimizer with `_step_supports_amp_scaling`: every gradient is divided by grad_scale[0] first, and when found_inf[0] != 0 the
- * launch changes nothing (no parameter, no momentum buffer) -- no host synchronisation, so the step stays capturable. */
-int rn_sgd_master_step_ex(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
-                          const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
-                          float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf, void *stream);
+                       const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
+                       float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
+                       const float *clip_coef, void *stream);
 
 /* ---- optimizer step: Adam / AdamW on fp32 masters with a 16-bit working copy, capturable --------------------
  * hparams: a DEVICE block of RN_ADAM_HPARAMS doubles per parameter group (8-byte aligned) holding lr, beta1, beta2, eps,
@@ -755,16 +758,17 @@ int rn_sgd_master_step_ex(float *const *masters, float *const *momenta, const vo
  * the gradient of a tensor WITH a 16-bit copy is dtype16 (8-byte aligned), every other gradient is f32 (16-byte aligned).
  * grad_scale / found_inf (nullable DEVICE f32 scalars, torch.amp.GradScaler): every gradient is divided by grad_scale[0] first,
  * and when found_inf[0] != 0 nothing changes -- no parameter, moment or step counter.  No host synchronisation.
+ * clip_coef (nullable DEVICE f32 scalar): as for rn_sgd_master_step; the step counter advances in a clipped step.
  * rn_adam_hparams_set: one launch writing lr .. weight_decay into the block, and the step counter too when step >= 0. */
 #define RN_ADAM_HPARAMS 16
 int rn_adam_hparams_set(double *hparams, double lr, double beta1, double beta2, double eps, double weight_decay, double step, void *stream);
 int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
                         void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
-                        double *hparams, const float *grad_scale, const float *found_inf, void *stream);
+                        double *hparams, const float *grad_scale, const float *found_inf, const float *clip_coef, void *stream);
 
 /* ---- global-norm gradient clipping for the master optimizers, capturable (csrc/clip.hip) ---------------------
  * torch.nn.utils.clip_grad_norm_(norm_type = 2) without a write: rn_grad_norm_clip leaves the norm and the clip coefficient in a
- * DEVICE block, and the _clip forms of the two optimizer steps multiply every gradient by that coefficient as they read it.
+ * DEVICE block, and the two optimizer steps, given its address as clip_coef, multiply every gradient by that coefficient as they read it.
  * The block: RN_CLIP_STATE doubles (8-byte aligned, zero-filled by its owner before first use), laid out as
  *   byte  0  f32 max_norm      (written by rn_grad_clip_set, the host's only way in)
  *   byte  4  f32 total_norm    (the last call's norm of the UNSCALED gradients)
@@ -772,7 +776,7 @@ int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *co
  *   byte 16  i64 calls, byte 24 i64 calls with clip_coef < 1, byte 32 i64 calls with a non-finite norm; the rest reserved.
  * rn_grad_norm_clip: grads / numels are HOST arrays over the tensors of ALL parameter groups (the norm is global); gradient i is
  * dtype16 (RN_BF16 | RN_F16, 8-byte aligned) when grads16 != 0 and params16 != NULL and params16[i] != NULL -- the convention of
- * rn_sgd_master_step_ex, params16 itself nullable -- and f32 (16-byte aligned) otherwise.  scratch: f64[scratch_slots] owned by the
+ * rn_sgd_master_step, params16 itself nullable -- and f32 (16-byte aligned) otherwise.  scratch: f64[scratch_slots] owned by the
  * caller, scratch_slots >= the sum over tensors of ceil(numels[i] / RN_CLIP_CHUNK) (RN_EINVAL otherwise): one slot per chunk of a
  * gradient, each written by one workgroup (the squares are summed in double from the first addition on) and then summed in slot
  * order in double -- no atomics, so the result is the same bits at every call.  total_norm = float(sqrt(sum of squares)) * (1 / grad_scale[0]) (grad_scale: nullable DEVICE f32 scalar, the
@@ -785,18 +789,6 @@ int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *co
 int rn_grad_clip_set(void *block, float max_norm, void *stream);
 int rn_grad_norm_clip(const void *const *grads, void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16,
                       const float *grad_scale, double *scratch, int64_t scratch_slots, void *block, void *stream);
-/* rn_sgd_master_step_ex / rn_adam_master_step with the clip: clip_coef (nullable DEVICE f32 scalar, the block's clip_coef) enters as
- *   g = (float(grad) * (1 / grad_scale[0])) * clip_coef[0]
- * -- GradScaler.unscale_ followed by clip_grad_norm_ on fp32 gradients, never rounded to 16 bits in between -- before weight decay
- * touches g.  clip_coef == NULL: the older entry points, which forward here.  Adam's step counter advances in a clipped step. */
-int rn_sgd_master_step_clip(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
-                            const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
-                            float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
-                            const float *clip_coef, void *stream);
-int rn_adam_master_step_clip(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
-                             void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
-                             double *hparams, const float *grad_scale, const float *found_inf, const float *clip_coef, void *stream);
-
 /* ---- gradient accumulation into fp32 accumulators for the master optimizers, capturable (csrc/accum.hip) -----
  * The gradients of N micro-batches summed in fp32, each weighted 1 / N, with everything that changes from one micro-batch to the
  * next in a DEVICE block, so one captured graph serves every position of a window and a new N needs no capture.
@@ -808,7 +800,7 @@ int rn_adam_master_step_clip(float *const *masters, float *const *exp_avgs, floa
  *   byte 16  i64 windows completed, byte 24 i64 windows that saw a non-finite value, byte 32 i64 micro-batches; the rest reserved.
  * rn_grad_accumulate: accs / grads / numels are HOST arrays over the tensors of ALL parameter groups; accs[i] is f32 (16-byte
  * aligned); gradient i is dtype16 (RN_BF16 | RN_F16, 8-byte aligned) when grads16 != 0 and params16 != NULL and params16[i] != NULL
- * -- the convention of rn_sgd_master_step_ex, params16 itself nullable -- and f32 (16-byte aligned) otherwise.  Per element, in fp32
+ * -- the convention of rn_sgd_master_step, params16 itself nullable -- and f32 (16-byte aligned) otherwise.  Per element, in fp32
  * with two roundings (no fused multiply-add):
  *   acc = (pos == 0 ? 0.0f : acc) + (float(g) * w)
  * At pos == 0 the accumulator is overwritten without being read (no zeroing pass).  found_inf becomes 1.0f when any gradient element
@@ -820,7 +812,7 @@ int rn_adam_master_step_clip(float *const *masters, float *const *exp_avgs, floa
  * rn_grad_accum_set: one launch writing n (>= 1) and w = float(1.0 / n); a captured step follows the values last written. */
 #define RN_ACCUM_STATE 8
 #define RN_ACCUM_FOUND_INF_OFFSET 12
-#define RN_ACCUM_CHUNK 16384
+#define RN_ACCUM_CHUNK 16384                     /* (== RN_CLIP_CHUNK: the two share one chunked map) */
 int rn_grad_accum_set(void *block, int n, void *stream);
 int rn_grad_accum_advance(void *block, int final, void *stream);
 int rn_grad_accumulate(float *const *accs, const void *const *grads, void *const *params16, const int64_t *numels, int n_tensors,

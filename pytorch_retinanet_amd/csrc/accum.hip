@@ -17,14 +17,11 @@
 // The streaming kernel only reads pos and w; nothing but the advance and the setter writes them.
 #include <stddef.h>
 
-#include "rn_common.hpp"
+#include "rn_multi.hpp"
 
 namespace {
 
 constexpr int ACC_MAX_TENSORS = 160;             // 160 x 24 B of tables + 16 B: inside the 4 KiB of kernel arguments
-constexpr int ACC_CHUNK = RN_ACCUM_CHUNK;
-constexpr int64_t ACC_PIECE = (int64_t)1 << 30;  // a tensor above 2^30 elements enters the table in pieces (a multiple of the chunk)
-constexpr uint32_t ACC_IS16 = 0x80000000u;
 
 struct rn_accum_state {                          // RN_ACCUM_STATE doubles (include/retinanet_hip.h)
     float w;                                     // float(1.0 / n)
@@ -35,15 +32,11 @@ struct rn_accum_state {                          // RN_ACCUM_STATE doubles (incl
 };
 static_assert(sizeof(rn_accum_state) == RN_ACCUM_STATE * sizeof(double), "rn_accum_state");
 static_assert(offsetof(rn_accum_state, found_inf) == RN_ACCUM_FOUND_INF_OFFSET, "found_inf offset");
-static_assert(ACC_PIECE % ACC_CHUNK == 0 && ACC_CHUNK % 8 == 0, "chunking");
 
 struct AccTable {
     float *acc[ACC_MAX_TENSORS];
-    const void *grad[ACC_MAX_TENSORS];
-    uint32_t n[ACC_MAX_TENSORS];                 // elements (<= 2^30)
-    uint32_t first[ACC_MAX_TENSORS];             // index of the tensor's first chunk in this launch | ACC_IS16 for a 16-bit gradient
+    rn::ChunkMap<ACC_MAX_TENSORS> map;
     rn_accum_state *blk;
-    int cnt;
 };
 static_assert(sizeof(AccTable) <= 4096, "kernel arguments");
 
@@ -73,30 +66,17 @@ __device__ __forceinline__ bool acc_vec(const float (&g)[VEC], rn::f32x4 *__rest
 template <int DT16>
 __global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccTable t)
 {
-    // the last tensor whose first chunk is <= this workgroup's chunk
-    int lo = 0, hi = t.cnt - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((t.first[mid] & ~ACC_IS16) <= blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const uint32_t first = t.first[lo];
-    const bool is16 = (first & ACC_IS16) != 0;
-    const int64_t off = (int64_t)(blockIdx.x - (first & ~ACC_IS16)) * ACC_CHUNK;
-    const int64_t left = (int64_t)t.n[lo] - off;
-    const int cnt = left < ACC_CHUNK ? (int)left : ACC_CHUNK;             // >= 1: the host counts ceil(n / chunk) chunks per tensor
+    const rn::ChunkLoc c = rn::locate(t.map, blockIdx.x);
     const float w = t.blk->w;
     const bool fresh = t.blk->pos == 0;
-    const int esz = is16 ? 2 : 4, vec = is16 ? 8 : 4;
-    const unsigned char *p = (const unsigned char *)t.grad[lo] + off * esz;
-    float *__restrict__ a = t.acc[lo] + off;
-    // elements in front of the gradient's first 16-byte boundary (a 16-bit gradient may start 8-byte aligned: 4 of them -- 16 bytes of
-    // the accumulator, which stays 16-byte aligned behind them), then whole 16-byte vectors, then the < 8 / < 4 leftover elements
-    int head = (int)(((16 - ((uintptr_t)p & 15)) & 15) / esz);
-    head = head < cnt ? head : cnt;
-    const int nv = (cnt - head) / vec;
-    const rn::u32x4 *__restrict__ pv = (const rn::u32x4 *)(p + (int64_t)head * esz);
-    rn::f32x4 *__restrict__ av = (rn::f32x4 *)(a + head);
+    const bool is16 = c.is16;
+    const unsigned char *p = (const unsigned char *)t.map.grad[c.ti] + c.off * (is16 ? 2 : 4);
+    float *__restrict__ a = t.acc[c.ti] + c.off;
+    // (a 16-bit gradient's head of 4 elements is 16 bytes of the accumulator, which stays 16-byte aligned behind it)
+    const rn::ChunkSplit sp(p, c.cnt, is16);
+    const int nv = sp.nv;
+    const rn::u32x4 *__restrict__ pv = sp.pv;
+    rn::f32x4 *__restrict__ av = (rn::f32x4 *)(a + sp.head);
     bool bad = false;
     if (is16) {
         for (int v = threadIdx.x; v < nv; v += 512) {
@@ -123,11 +103,7 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(const AccTable t)
             }
         }
     }
-    // scalar paths: lanes 0 .. head - 1 take the head, the next lanes the tail (at most 7 + 7 elements)
-    const int tail0 = head + nv * vec, n_tail = cnt - tail0;
-    int e = -1;
-    if ((int)threadIdx.x < head) e = threadIdx.x;
-    else if ((int)threadIdx.x - head < n_tail) e = tail0 + (int)threadIdx.x - head;
+    const int e = sp.scalar_elem(threadIdx.x);
     if (e >= 0) {
         const float g = is16 ? rn::dt<DT16>::ld(p, e) : ((const float *)p)[e];
         const float old = fresh ? 0.0f : a[e];
@@ -189,35 +165,13 @@ RN_API int rn_grad_accumulate(float *const *accs, const void *const *grads, void
     }
     hipStream_t st = (hipStream_t)stream;
     AccTable t;
-    t.cnt = 0;
     t.blk = (rn_accum_state *)block;
-    int64_t chunks = 0;                                          // chunks in the table
-    auto flush = [&]() -> int {
-        if (t.cnt == 0) return RN_OK;
-        for (int i = t.cnt; i < ACC_MAX_TENSORS; ++i) { t.acc[i] = nullptr; t.grad[i] = nullptr; t.n[i] = 0; t.first[i] = 0; }
+    return rn::for_chunk_maps(t.map, grads, params16, numels, n_tensors, grads16, [&](const int slot, const int i, const int64_t off) { t.acc[slot] = accs[i] + off; },
+                              [&](const int64_t chunks) -> int {
+        for (int i = t.map.cnt; i < ACC_MAX_TENSORS; ++i) t.acc[i] = nullptr;
         if (dtype16 == RN_F16) hipLaunchKernelGGL((grad_accumulate_kernel<RN_F16>), dim3((unsigned)chunks), dim3(256), 0, st, t);
         else hipLaunchKernelGGL((grad_accumulate_kernel<RN_BF16>), dim3((unsigned)chunks), dim3(256), 0, st, t);
         RN_LAUNCH_CHECK();
-        chunks = 0;
-        t.cnt = 0;
         return RN_OK;
-    };
-    for (int i = 0; i < n_tensors; ++i) {
-        const bool is16 = grads16 && params16 && params16[i];
-        for (int64_t off = 0; off < numels[i]; off += ACC_PIECE) {
-            const int64_t n = numels[i] - off < ACC_PIECE ? numels[i] - off : ACC_PIECE;
-            const int64_t c = (n + ACC_CHUNK - 1) / ACC_CHUNK;
-            if (t.cnt == ACC_MAX_TENSORS || chunks + c > 0x7fffffff) {
-                const int rc = flush();
-                if (rc != RN_OK) return rc;
-            }
-            t.acc[t.cnt] = accs[i] + off;
-            t.grad[t.cnt] = (const unsigned char *)grads[i] + off * (is16 ? 2 : 4);
-            t.n[t.cnt] = (uint32_t)n;
-            t.first[t.cnt] = (uint32_t)chunks | (is16 ? ACC_IS16 : 0u);
-            ++t.cnt;
-            chunks += c;
-        }
-    }
-    return flush();
+    });
 }

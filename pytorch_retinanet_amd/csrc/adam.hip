@@ -16,12 +16,11 @@
 //   denom = sqrt(v) * (1 / float(bc2_sqrt)) + eps   (ATen divides a tensor by a scalar as a multiply by the scalar's reciprocal)
 //   w = fma(float(-step_size), m / denom, w);  w16 = round(w)
 // The same kernel updates plain fp32 parameters (BN, biases): no 16-bit copy, fp32 gradient.
-#include "rn_common.hpp"
+#include "rn_multi.hpp"
 
 namespace {
 
 constexpr int ADAM_MAX_TENSORS = 40;          // 40 x 48 B: the size of SgdTable's 48 x 40 B
-constexpr int ADAM_BLOCKS_X = 1024;
 
 // the device block, double[RN_ADAM_HPARAMS] (include/retinanet_hip.h)
 enum { HP_LR = 0, HP_BETA1, HP_BETA2, HP_EPS, HP_WD, HP_STEP, HP_STEP_SIZE, HP_BC2_SQRT };
@@ -107,38 +106,22 @@ __global__ __launch_bounds__(256) void adam_master_kernel(const AdamTable t)
         rn::f32x4 wv = ((const rn::f32x4 *)w)[q];
         rn::f32x4 mv = ((const rn::f32x4 *)m)[q];
         rn::f32x4 vv = ((const rn::f32x4 *)v)[q];
-        float g[4];
-        if (g16) {
-            const rn::u32x2 gv = ((const rn::u32x2 *)t.grad[ti])[q];
-            g[0] = rn::mma<DT>::lo(gv.x); g[1] = rn::mma<DT>::hi(gv.x);
-            g[2] = rn::mma<DT>::lo(gv.y); g[3] = rn::mma<DT>::hi(gv.y);
-        } else {
-            const rn::f32x4 gv = ((const rn::f32x4 *)t.grad[ti])[q];
-            g[0] = gv.x; g[1] = gv.y; g[2] = gv.z; g[3] = gv.w;
-        }
+        const rn::f32x4 gv = rn::load_grad4<DT>(t, ti, q, g16);
+        const float g[4] = {gv.x, gv.y, gv.z, gv.w};
         float ww[4] = {wv.x, wv.y, wv.z, wv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w}, vq[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gj = t.grad_scale ? g[j] * s.inv_scale : g[j];
-            if (t.clip_coef) gj = gj * coef;                     // unscale, then clip: two fp32 products, before weight decay
-            adam_one<DECOUPLED>(s, decay, gj, ww[j], mm[j], vq[j]);
-        }
+        for (int j = 0; j < 4; ++j)                              // unscale, then clip: two fp32 products, before weight decay
+            adam_one<DECOUPLED>(s, decay, rn::unscale_clip(g[j], t.grad_scale, s.inv_scale, t.clip_coef, coef), ww[j], mm[j], vq[j]);
         ((rn::f32x4 *)w)[q] = rn::f32x4{ww[0], ww[1], ww[2], ww[3]};
         ((rn::f32x4 *)m)[q] = rn::f32x4{mm[0], mm[1], mm[2], mm[3]};
         ((rn::f32x4 *)v)[q] = rn::f32x4{vq[0], vq[1], vq[2], vq[3]};
-        if (p16) {
-            rn::u32x2 o;
-            o.x = rn::dt<DT>::pk(ww[0], ww[1]); o.y = rn::dt<DT>::pk(ww[2], ww[3]);
-            ((rn::u32x2 *)p16)[q] = o;
-        }
+        if (p16) rn::store16x4<DT>(p16, q, ww);
     }
     if (blockIdx.x == 0) {                                       // < 4 leftover elements
         const int64_t i = n4 * 4 + threadIdx.x;
         if (threadIdx.x < 4 && i < n) {
             float wi = w[i], mi = m[i], vi = v[i];
-            float g = g16 ? rn::mma<DT>::lo((uint32_t)((const uint16_t *)t.grad[ti])[i]) : ((const float *)t.grad[ti])[i];
-            if (t.grad_scale) g *= s.inv_scale;
-            if (t.clip_coef) g *= coef;
+            const float g = rn::unscale_clip(rn::load_grad1<DT>(t, ti, i, g16), t.grad_scale, s.inv_scale, t.clip_coef, coef);
             adam_one<DECOUPLED>(s, decay, g, wi, mi, vi);
             w[i] = wi; m[i] = mi; v[i] = vi;
             if (p16) p16[i] = rn::mma<DT>::dn(wi);
@@ -165,36 +148,27 @@ RN_API int rn_adam_hparams_set(double *hparams, double lr, double beta1, double 
     return RN_OK;
 }
 
-RN_API int rn_adam_master_step_clip(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
-                                    void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
-                                    double *hparams, const float *grad_scale, const float *found_inf, const float *clip_coef, void *stream)
+RN_API int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
+                               void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
+                               double *hparams, const float *grad_scale, const float *found_inf, const float *clip_coef, void *stream)
 {
     if (dtype16 != RN_BF16 && dtype16 != RN_F16) return RN_EUNSUPPORTED;
     if (!masters || !exp_avgs || !exp_avg_sqs || !grads || !params16 || !numels || !hparams || n_tensors < 0) return RN_EINVAL;
     if (!rn::aligned(hparams, 8)) return RN_EALIGN;
-    for (int i = 0; i < n_tensors; ++i) {                        // everything is checked before anything is launched
-        if (!masters[i] || !exp_avgs[i] || !exp_avg_sqs[i] || !grads[i] || numels[i] < 0) return RN_EINVAL;
-        if (!rn::aligned(masters[i], 16) || !rn::aligned(exp_avgs[i], 16) || !rn::aligned(exp_avg_sqs[i], 16) ||
-            !rn::aligned(grads[i], (params16[i] && grads16) ? 8 : 16) || (params16[i] && !rn::aligned(params16[i], 8)))
-            return RN_EALIGN;
-    }
+    const int rc = rn::check_step_tensors<2>(masters, {exp_avgs, exp_avg_sqs}, true, grads, params16, numels, n_tensors, grads16, 8);
+    if (rc != RN_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(adam_prologue_kernel, dim3(1), dim3(64), 0, st, hparams, found_inf);
     RN_LAUNCH_CHECK();
     for (int base = 0; base < n_tensors; base += ADAM_MAX_TENSORS) {
         AdamTable t;
         const int cnt = (n_tensors - base) < ADAM_MAX_TENSORS ? (n_tensors - base) : ADAM_MAX_TENSORS;
-        int64_t max_n = 1;
         for (int i = 0; i < cnt; ++i) {
             t.master[i] = masters[base + i]; t.m[i] = exp_avgs[base + i]; t.v[i] = exp_avg_sqs[base + i];
             t.grad[i] = grads[base + i]; t.p16[i] = params16[base + i]; t.n[i] = numels[base + i];
-            max_n = t.n[i] > max_n ? t.n[i] : max_n;
         }
         t.hp = hparams; t.grad_scale = grad_scale; t.found_inf = found_inf; t.clip_coef = clip_coef; t.grad16 = grads16;
-        int64_t bx = (max_n / 4 + 255) / 256;                    // one pass over the largest tensor, capped
-        if (bx > ADAM_BLOCKS_X) bx = ADAM_BLOCKS_X;
-        if (bx < 1) bx = 1;
-        const dim3 grid((unsigned)bx, (unsigned)cnt);
+        const dim3 grid = rn::step_grid(t.n, cnt);
         if (dtype16 == RN_F16) {
             if (decoupled) hipLaunchKernelGGL((adam_master_kernel<true, true>), grid, dim3(256), 0, st, t);
             else hipLaunchKernelGGL((adam_master_kernel<true, false>), grid, dim3(256), 0, st, t);
@@ -205,12 +179,4 @@ RN_API int rn_adam_master_step_clip(float *const *masters, float *const *exp_avg
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
-}
-
-RN_API int rn_adam_master_step(float *const *masters, float *const *exp_avgs, float *const *exp_avg_sqs, const void *const *grads,
-                               void *const *params16, const int64_t *numels, int n_tensors, int grads16, int dtype16, int decoupled,
-                               double *hparams, const float *grad_scale, const float *found_inf, void *stream)
-{
-    return rn_adam_master_step_clip(masters, exp_avgs, exp_avg_sqs, grads, params16, numels, n_tensors, grads16, dtype16, decoupled, hparams,
-                                    grad_scale, found_inf, nullptr, stream);
 }

@@ -1,5 +1,5 @@
 // Global-norm gradient clipping for the master optimizers, capturable: the L2 norm of every gradient of a step and the clip
-// coefficient of torch.nn.utils.clip_grad_norm_, left in a DEVICE block that rn_sgd_master_step_clip / rn_adam_master_step_clip read.
+// coefficient of torch.nn.utils.clip_grad_norm_, left in a DEVICE block that rn_sgd_master_step / rn_adam_master_step read.
 //
 // optim.GradClip owns the block (rn_clip_state below; include/retinanet_hip.h documents the layout) and a scratch buffer of one
 // float per chunk.  Per call:
@@ -19,17 +19,14 @@
 //           coef = min((1 / (total + 1e-6)) * max_norm, 1)      (max_norm / tensor is reciprocal-then-multiply in torch)
 //           A non-finite norm gives what torch gives (0 or NaN); under a GradScaler found_inf skips that step anyway.
 // The chunk -> (tensor, offset) map is a table of first-chunk indices in the kernel arguments; a workgroup finds its tensor by a
-// binary search of it (8 uniform steps).  No memset and no memcpy node on this path (graph.py).
+// binary search of it (8 uniform steps): rn_multi.hpp.  No memset and no memcpy node on this path (graph.py).
 #include <stddef.h>
 
-#include "rn_common.hpp"
+#include "rn_multi.hpp"
 
 namespace {
 
 constexpr int CLIP_MAX_TENSORS = 224;            // 224 x 16 B of tables + 16 B: inside the 4 KiB of kernel arguments
-constexpr int CLIP_CHUNK = RN_CLIP_CHUNK;
-constexpr int64_t CLIP_PIECE = (int64_t)1 << 30; // a tensor above 2^30 elements enters the table in pieces (a multiple of the chunk)
-constexpr uint32_t CLIP_IS16 = 0x80000000u;
 
 struct rn_clip_state {                           // RN_CLIP_STATE doubles (include/retinanet_hip.h)
     float max_norm, total_norm, clip_coef, reserved;
@@ -38,15 +35,12 @@ struct rn_clip_state {                           // RN_CLIP_STATE doubles (inclu
 };
 static_assert(sizeof(rn_clip_state) == RN_CLIP_STATE * sizeof(double), "rn_clip_state");
 static_assert(offsetof(rn_clip_state, clip_coef) == RN_CLIP_COEF_OFFSET, "clip_coef offset");
-static_assert(CLIP_PIECE % CLIP_CHUNK == 0 && CLIP_CHUNK % 8 == 0, "chunking");
 
 struct ClipTable {
-    const void *grad[CLIP_MAX_TENSORS];
-    uint32_t n[CLIP_MAX_TENSORS];                // elements (<= 2^30)
-    uint32_t first[CLIP_MAX_TENSORS];            // index of the tensor's first chunk in this launch | CLIP_IS16 for a 16-bit gradient
+    rn::ChunkMap<CLIP_MAX_TENSORS> map;
     double *partial;                             // slot of this launch's chunk 0
-    int cnt;
 };
+static_assert(sizeof(ClipTable) <= 4096, "kernel arguments");
 
 template <int DT16>
 __device__ __forceinline__ double sq_sum(const rn::u32x4 q, const bool is16, double acc)
@@ -69,26 +63,12 @@ template <int DT16>
 __global__ __launch_bounds__(256) void grad_sqsum_kernel(const ClipTable t)
 {
     __shared__ double wave_part[4];
-    // the last tensor whose first chunk is <= this workgroup's chunk
-    int lo = 0, hi = t.cnt - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((t.first[mid] & ~CLIP_IS16) <= blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const uint32_t first = t.first[lo];
-    const bool is16 = (first & CLIP_IS16) != 0;
-    const int64_t off = (int64_t)(blockIdx.x - (first & ~CLIP_IS16)) * CLIP_CHUNK;
-    const int64_t left = (int64_t)t.n[lo] - off;
-    const int cnt = left < CLIP_CHUNK ? (int)left : CLIP_CHUNK;           // >= 1: the host counts ceil(n / chunk) chunks per tensor
-    const int esz = is16 ? 2 : 4, vec = is16 ? 8 : 4;
-    const unsigned char *p = (const unsigned char *)t.grad[lo] + off * esz;
-    // elements in front of the first 16-byte boundary (a 16-bit gradient may start 8-byte aligned: 4 of them), then whole 16-byte
-    // vectors, then the < 8 / < 4 leftover elements
-    int head = (int)(((16 - ((uintptr_t)p & 15)) & 15) / esz);
-    head = head < cnt ? head : cnt;
-    const int nv = (cnt - head) / vec;
-    const rn::u32x4 *__restrict__ pv = (const rn::u32x4 *)(p + (int64_t)head * esz);
+    const rn::ChunkLoc c = rn::locate(t.map, blockIdx.x);
+    const unsigned char *p = (const unsigned char *)t.map.grad[c.ti] + c.off * (c.is16 ? 2 : 4);
+    const rn::ChunkSplit sp(p, c.cnt, c.is16);
+    const bool is16 = c.is16;
+    const int nv = sp.nv;
+    const rn::u32x4 *__restrict__ pv = sp.pv;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     for (int v = threadIdx.x; v < nv; v += 1024) {
         rn::u32x4 q[4];
@@ -97,11 +77,7 @@ __global__ __launch_bounds__(256) void grad_sqsum_kernel(const ClipTable t)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = sq_sum<DT16>(q[j], is16, acc[j]);
     }
-    // scalar paths: lanes 0 .. head - 1 take the head, the next lanes the tail (at most 7 + 7 elements)
-    const int tail0 = head + nv * vec, n_tail = cnt - tail0;
-    int e = -1;
-    if ((int)threadIdx.x < head) e = threadIdx.x;
-    else if ((int)threadIdx.x - head < n_tail) e = tail0 + (int)threadIdx.x - head;
+    const int e = sp.scalar_elem(threadIdx.x);
     if (e >= 0) {
         const double d = (double)(is16 ? rn::dt<DT16>::ld(p, e) : ((const float *)p)[e]);
         acc[0] = fma(d, d, acc[0]);
@@ -161,43 +137,20 @@ RN_API int rn_grad_norm_clip(const void *const *grads, void *const *params16, co
         if (!grads[i] || numels[i] < 0) return RN_EINVAL;
         const bool is16 = grads16 && params16 && params16[i];
         if (!rn::aligned(grads[i], is16 ? 8 : 16)) return RN_EALIGN;
-        slots += (numels[i] + CLIP_CHUNK - 1) / CLIP_CHUNK;
+        slots += (numels[i] + rn::CHUNK - 1) / rn::CHUNK;
     }
     if (slots > scratch_slots) return RN_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     ClipTable t;
-    t.cnt = 0;
-    t.partial = scratch;
-    int64_t chunks = 0, done = 0;                                // chunks in the table / slots of the launches before it
-    auto flush = [&]() -> int {
-        if (t.cnt == 0) return RN_OK;
-        for (int i = t.cnt; i < CLIP_MAX_TENSORS; ++i) { t.grad[i] = nullptr; t.n[i] = 0; t.first[i] = 0; }
+    int64_t done = 0;                                            // slots of the launches so far
+    const int rc = rn::for_chunk_maps(t.map, grads, params16, numels, n_tensors, grads16, [](int, int, int64_t) {}, [&](const int64_t chunks) -> int {
+        t.partial = scratch + done;
         if (dtype16 == RN_F16) hipLaunchKernelGGL((grad_sqsum_kernel<RN_F16>), dim3((unsigned)chunks), dim3(256), 0, st, t);
         else hipLaunchKernelGGL((grad_sqsum_kernel<RN_BF16>), dim3((unsigned)chunks), dim3(256), 0, st, t);
         RN_LAUNCH_CHECK();
         done += chunks;
-        chunks = 0;
-        t.cnt = 0;
-        t.partial = scratch + done;
         return RN_OK;
-    };
-    for (int i = 0; i < n_tensors; ++i) {
-        const bool is16 = grads16 && params16 && params16[i];
-        for (int64_t off = 0; off < numels[i]; off += CLIP_PIECE) {
-            const int64_t n = numels[i] - off < CLIP_PIECE ? numels[i] - off : CLIP_PIECE;
-            const int64_t c = (n + CLIP_CHUNK - 1) / CLIP_CHUNK;
-            if (t.cnt == CLIP_MAX_TENSORS || chunks + c > 0x7fffffff) {
-                const int rc = flush();
-                if (rc != RN_OK) return rc;
-            }
-            t.grad[t.cnt] = (const unsigned char *)grads[i] + off * (is16 ? 2 : 4);
-            t.n[t.cnt] = (uint32_t)n;
-            t.first[t.cnt] = (uint32_t)chunks | (is16 ? CLIP_IS16 : 0u);
-            ++t.cnt;
-            chunks += c;
-        }
-    }
-    const int rc = flush();
+    });
     if (rc != RN_OK) return rc;
     hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, st, (const double *)scratch, done, grad_scale, (rn_clip_state *)block);
     RN_LAUNCH_CHECK();

@@ -8,12 +8,11 @@
 //   g = float(grad) + weight_decay * w;  buf = first ? g : momentum * buf + (1 - dampening) * g;
 //   g = nesterov ? g + momentum * buf : buf;  w -= lr * g;  w16 = bf16(w)
 // The same kernel updates plain fp32 parameters (BN, biases): no 16-bit copy, fp32 gradient.
-#include "rn_common.hpp"
+#include "rn_multi.hpp"
 
 namespace {
 
 constexpr int SGD_MAX_TENSORS = 48;
-constexpr int SGD_BLOCKS_X = 1024;
 
 struct SgdTable {
     float *master[SGD_MAX_TENSORS];
@@ -59,47 +58,31 @@ __global__ __launch_bounds__(256) void sgd_master_kernel(const SgdTable t)
     const bool g16 = p16 && t.grad16;
     const bool has_m = t.momentum != 0.0f;
     const int64_t n = t.n[ti], n4 = n >> 2;
-    // 4 elements per thread and iteration: 16-byte accesses on the fp32 arrays, 8-byte on the bf16 ones
-    // (torch allocations are 256-byte aligned and every array of a tensor starts at its storage offset 0 or a
-    // multiple of 4 elements: checked on the host, which otherwise sends the tensor through the scalar tail path)
+    // 4 elements per thread and iteration: 16-byte accesses on the fp32 arrays, 8-byte on the bf16 ones (every array starts
+    // 16- / 8-byte aligned: checked on the host); the < 4 leftover elements go through the scalar tail below
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n4; v += (int64_t)gridDim.x * 256) {
         rn::f32x4 wv = ((const rn::f32x4 *)w)[v];
         rn::f32x4 mv = {0.f, 0.f, 0.f, 0.f};
         if (has_m && !t.first) mv = ((const rn::f32x4 *)m)[v];
-        float g[4];
-        if (g16) {
-            const rn::u32x2 gv = ((const rn::u32x2 *)t.grad[ti])[v];
-            g[0] = rn::mma<DT>::lo(gv.x); g[1] = rn::mma<DT>::hi(gv.x);
-            g[2] = rn::mma<DT>::lo(gv.y); g[3] = rn::mma<DT>::hi(gv.y);
-        } else {
-            const rn::f32x4 gv = ((const rn::f32x4 *)t.grad[ti])[v];
-            g[0] = gv.x; g[1] = gv.y; g[2] = gv.z; g[3] = gv.w;
-        }
+        const rn::f32x4 gv = rn::load_grad4<DT>(t, ti, v, g16);
+        const float g[4] = {gv.x, gv.y, gv.z, gv.w};
         float ww[4] = {wv.x, wv.y, wv.z, wv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float gj = t.grad_scale ? g[j] * inv_scale : g[j];
-            if (t.clip_coef) gj = gj * coef;
+            const float gj = rn::unscale_clip(g[j], t.grad_scale, inv_scale, t.clip_coef, coef);
             sgd_one(t, gj, ww[j], mm[j]);
         }
         wv.x = ww[0]; wv.y = ww[1]; wv.z = ww[2]; wv.w = ww[3];
         mv.x = mm[0]; mv.y = mm[1]; mv.z = mm[2]; mv.w = mm[3];
         ((rn::f32x4 *)w)[v] = wv;
         if (has_m) ((rn::f32x4 *)m)[v] = mv;
-        if (p16) {
-            rn::u32x2 o;
-            o.x = rn::dt<DT>::pk(ww[0], ww[1]); o.y = rn::dt<DT>::pk(ww[2], ww[3]);
-            ((rn::u32x2 *)p16)[v] = o;
-        }
+        if (p16) rn::store16x4<DT>(p16, v, ww);
     }
     if (blockIdx.x == 0) {                                       // < 4 leftover elements
         const int64_t i = n4 * 4 + threadIdx.x;
         if (threadIdx.x < 4 && i < n) {
             float wi = w[i], mi = (has_m && !t.first) ? m[i] : 0.0f;
-            float g = g16 ? rn::mma<DT>::lo((uint32_t)((const uint16_t *)t.grad[ti])[i]) : ((const float *)t.grad[ti])[i];
-            if (t.grad_scale) g *= inv_scale;
-            if (t.clip_coef) g *= coef;
-            sgd_one(t, g, wi, mi);
+            sgd_one(t, rn::unscale_clip(rn::load_grad1<DT>(t, ti, i, g16), t.grad_scale, inv_scale, t.clip_coef, coef), wi, mi);
             w[i] = wi;
             if (has_m) m[i] = mi;
             if (p16) p16[i] = rn::mma<DT>::dn(wi);
@@ -109,22 +92,21 @@ __global__ __launch_bounds__(256) void sgd_master_kernel(const SgdTable t)
 
 }  // namespace
 
-RN_API int rn_sgd_master_step_clip(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
-                                   const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
-                                   float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
-                                   const float *clip_coef, void *stream)
+RN_API int rn_sgd_master_step(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
+                              const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
+                              float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
+                              const float *clip_coef, void *stream)
 {
     if (dtype16 != RN_BF16 && dtype16 != RN_F16) return RN_EUNSUPPORTED;
     if (!masters || !momenta || !grads || !params16 || !numels || n_tensors < 0) return RN_EINVAL;
+    // (16-bit gradients too must start on 16 bytes here: the contract parallel.BucketedGradAllReduce's views are laid out for)
+    const int rc = rn::check_step_tensors<1>(masters, {momenta}, momentum != 0.0f, grads, params16, numels, n_tensors, grads16, 16);
+    if (rc != RN_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     for (int base = 0; base < n_tensors; base += SGD_MAX_TENSORS) {
         SgdTable t;
         const int cnt = (n_tensors - base) < SGD_MAX_TENSORS ? (n_tensors - base) : SGD_MAX_TENSORS;
         for (int i = 0; i < cnt; ++i) {
-            if (!masters[base + i] || !grads[base + i] || numels[base + i] < 0 || (momentum != 0.0f && !momenta[base + i])) return RN_EINVAL;
-            if (!rn::aligned(masters[base + i], 16) || !rn::aligned(grads[base + i], 16) || (momenta[base + i] && !rn::aligned(momenta[base + i], 16)) ||
-                (params16[base + i] && !rn::aligned(params16[base + i], 8)))
-                return RN_EALIGN;
             t.master[i] = masters[base + i]; t.mom[i] = momenta[base + i]; t.grad[i] = grads[base + i];
             t.p16[i] = params16[base + i]; t.n[i] = numels[base + i];
         }
@@ -132,33 +114,12 @@ RN_API int rn_sgd_master_step_clip(float *const *masters, float *const *momenta,
         t.nesterov = nesterov; t.first = first_step; t.grad16 = grads16;
         t.f16 = dtype16 == RN_F16; t.grad_scale = grad_scale; t.found_inf = found_inf;
         t.clip_coef = clip_coef;
-        int64_t max_n = 1;
-        for (int i = 0; i < cnt; ++i) max_n = t.n[i] > max_n ? t.n[i] : max_n;
-        int64_t bx = (max_n / 4 + 255) / 256;                    // one pass over the largest tensor, capped
-        if (bx > SGD_BLOCKS_X) bx = SGD_BLOCKS_X;
-        if (bx < 1) bx = 1;
-        if (t.f16) hipLaunchKernelGGL(sgd_master_kernel<true>, dim3((unsigned)bx, (unsigned)cnt), dim3(256), 0, st, t);
-        else hipLaunchKernelGGL(sgd_master_kernel<false>, dim3((unsigned)bx, (unsigned)cnt), dim3(256), 0, st, t);
+        const dim3 grid = rn::step_grid(t.n, cnt);
+        if (t.f16) hipLaunchKernelGGL(sgd_master_kernel<true>, grid, dim3(256), 0, st, t);
+        else hipLaunchKernelGGL(sgd_master_kernel<false>, grid, dim3(256), 0, st, t);
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
-}
-
-RN_API int rn_sgd_master_step_ex(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
-                                 const int64_t *numels, int n_tensors, int grads16, int dtype16, float lr, float momentum, float dampening,
-                                 float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
-                                 void *stream)
-{
-    return rn_sgd_master_step_clip(masters, momenta, grads, params16, numels, n_tensors, grads16, dtype16, lr, momentum, dampening, weight_decay,
-                                   nesterov, first_step, grad_scale, found_inf, nullptr, stream);
-}
-
-RN_API int rn_sgd_master_step(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
-                              const int64_t *numels, int n_tensors, int grads16, float lr, float momentum, float dampening,
-                              float weight_decay, int nesterov, int first_step, void *stream)
-{
-    return rn_sgd_master_step_ex(masters, momenta, grads, params16, numels, n_tensors, grads16, RN_BF16, lr, momentum, dampening, weight_decay,
-                                 nesterov, first_step, nullptr, nullptr, stream);
 }
 
 // ---- many small device-to-device copies in one launch ---------------------------------------------------------------------------

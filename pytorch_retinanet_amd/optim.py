@@ -79,6 +79,77 @@ def _is_capturing() -> bool:
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
+def _device_block(blk: Optional[Tensor], n: int, device: torch.device, in_capture: str, elsewhere: str) -> Tensor:
+    """``blk``, or -- the first time -- a zeroed ``float64[n]`` on ``device`` for its owner to keep for good (captured steps hold its
+    address: it is never moved or replaced).  Not created inside a capture (``in_capture``: the owner's message) and not used from a
+    second device (``elsewhere``, formatted with ``have`` / ``want``)."""
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if blk is None:
+        if _is_capturing():
+            raise RuntimeError(in_capture)
+        return torch.empty(n, dtype=torch.float64, device=device).fill_(0)      # (a fill kernel, not a memset: graph.py)
+    if blk.device != device:
+        raise RuntimeError(elsewhere.format(have=blk.device, want=device))
+    return blk
+
+
+def _collect(params: Iterable[Tensor], grads: Optional[Dict[Tensor, Tensor]], refuse, state, **rec) -> Optional[dict]:
+    """One walk over ``params`` for a multi-tensor launch: the gradient of each (``grads[p]`` wins over ``p.grad``), its fp32 tensor
+    (``p.master`` behind a 16-bit working copy, else ``p.data``), the dtype checks, and the gradient brought to that tensor's strides.
+    Returns ``rec`` with ``masters`` / ``gptrs`` / ``p16s`` / ``ns``, ``grads16`` (the gradients of the 16-bit parameters are 16-bit too), ``dt16``,
+    ``dev`` and ``keep`` (the re-laid-out gradients: they must outlive the launch) -- or None when no parameter has a gradient.
+    ``refuse(cpu)``: the user's exception for a CPU tensor (True) or a tensor that is not fp32 (False).  ``state(rec, p, w)``: the
+    user's hook, called after those checks to create its per-parameter state and add its own pointers to ``rec``; ``w`` is None for
+    a parameter without a gradient."""
+    rec.update(masters=[], gptrs=[], p16s=[], ns=[], grads16=None, dt16=None, keep=[], dev=None)
+    for p in params:
+        g = grads.get(p) if grads is not None else None
+        if g is None:
+            g = p.grad
+        if g is None:
+            state(rec, p, None)
+            continue
+        has16 = hasattr(p, "master")
+        w = p.master if has16 else p.data
+        if not (p.is_cuda and g.is_cuda):
+            raise refuse(True)
+        if w.dtype != torch.float32:
+            raise refuse(False)
+        state(rec, p, w)
+        if has16:
+            if rec["dt16"] is None:
+                rec["dt16"] = p.dtype
+            elif rec["dt16"] != p.dtype:
+                raise RuntimeError("the 16-bit working copies of one launch must share a dtype")
+            is16 = g.dtype == p.dtype
+            if not is16 and g.dtype != torch.float32:
+                raise TypeError(f"unsupported gradient dtype {g.dtype} for a {p.dtype} working copy")
+            if rec["grads16"] is None:
+                rec["grads16"] = is16
+            elif rec["grads16"] != is16:
+                raise RuntimeError("gradients of the 16-bit parameters must be all 16-bit or all fp32")
+        elif g.dtype != torch.float32:
+            raise TypeError("fp32 parameters need fp32 gradients")
+        # same memory order for the fp32 tensor, the optimizer's state, the gradient and the 16-bit copy: all carry the parameter's strides
+        if g.stride() != w.stride():
+            g = g.contiguous(memory_format=torch.channels_last) if w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last) \
+                else g.contiguous()
+            rec["keep"].append(g)
+        if rec["dev"] is None:
+            rec["dev"] = w.device
+        rec["masters"].append(w.data_ptr()); rec["gptrs"].append(g.data_ptr()); rec["p16s"].append(p.data.data_ptr() if has16 else 0); rec["ns"].append(w.numel())
+    return rec if rec["ns"] else None
+
+
+def _ptrs(values: List[int]):
+    return (C.c_void_p * len(values))(*values)
+
+
+def _dt16(dtype) -> int:
+    return RN_F16 if dtype == torch.float16 else RN_BF16
+
+
 RN_CLIP_STATE = 8                       # doubles in the clip block (include/retinanet_hip.h)
 RN_CLIP_CHUNK = 16384                   # elements per scratch slot
 _CLIP_COEF_BYTE = 8                     # byte offset of clip_coef in the block
@@ -148,22 +219,18 @@ class GradClip:
             check(lib.rn_grad_clip_set(self._block.data_ptr(), float(value), torch.cuda.current_stream(dev).cuda_stream), "rn_grad_clip_set")
 
     def _ensure(self, device: torch.device, slots: int) -> None:
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._block is None:
-            if _is_capturing():
-                raise RuntimeError("GradClip: take one step before capturing one: its device block cannot be created inside a capture")
-            self._block = torch.empty(RN_CLIP_STATE, dtype=torch.float64, device=device).fill_(0)      # (a fill kernel, not a memset: graph.py)
+        new = self._block is None
+        self._block = _device_block(self._block, RN_CLIP_STATE, device,
+                                    "GradClip: take one step before capturing one: its device block cannot be created inside a capture",
+                                    "GradClip: its state lives on {have}, not {want}; use one object per device")
+        if new:
             self._write_max_norm(self._max_norm)
-        elif self._block.device != device:
-            # (a captured step holds the block's address: it is never replaced while this object lives)
-            raise RuntimeError(f"GradClip: its state lives on {self._block.device}, not {device}; use one object per device")
         if self._scratch is None or self._scratch.numel() < slots:
             if _is_capturing():
                 raise RuntimeError("GradClip: the set of gradients grew since the last eager step: take one step before capturing one")
             if self._scratch is not None:
                 self._retired.append(self._scratch)
-            self._scratch = torch.empty(max(slots, 1), dtype=torch.float64, device=device)
+            self._scratch = torch.empty(max(slots, 1), dtype=torch.float64, device=self._block.device)
 
     def compute(self, gptrs: List[int], p16s: List[int], ns: List[int], dtype16: int, scale: Optional[Tensor], device: torch.device) -> int:
         """One ``rn_grad_norm_clip`` call on the current stream over the gradients at ``gptrs`` (``p16s[i] != 0``: gradient i is
@@ -172,7 +239,7 @@ class GradClip:
         slots = sum((k + RN_CLIP_CHUNK - 1) // RN_CLIP_CHUNK for k in ns)
         self._ensure(device, slots)
         with torch.cuda.device(self._block.device):
-            check(lib.rn_grad_norm_clip((C.c_void_p * n)(*gptrs), (C.c_void_p * n)(*p16s), (C.c_int64 * n)(*ns), n, 1, dtype16,
+            check(lib.rn_grad_norm_clip(_ptrs(gptrs), _ptrs(p16s), (C.c_int64 * n)(*ns), n, 1, dtype16,
                                         scale.data_ptr() if scale is not None else None, self._scratch.data_ptr(), self._scratch.numel(),
                                         self._block.data_ptr(), torch.cuda.current_stream().cuda_stream), "rn_grad_norm_clip")
         return self._block.data_ptr() + _CLIP_COEF_BYTE
@@ -272,15 +339,12 @@ class GradAccumulator:
             check(lib.rn_grad_accum_set(self._block.data_ptr(), int(value), torch.cuda.current_stream(dev).cuda_stream), "rn_grad_accum_set")
 
     def _ensure_block(self, device: torch.device) -> None:
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._block is None:
-            if _is_capturing():
-                raise RuntimeError("GradAccumulator: take one step before capturing one: its device block cannot be created inside a capture")
-            self._block = torch.empty(RN_ACCUM_STATE, dtype=torch.float64, device=device).fill_(0)     # (a fill kernel, not a memset: graph.py)
+        new = self._block is None
+        self._block = _device_block(self._block, RN_ACCUM_STATE, device,
+                                    "GradAccumulator: take one step before capturing one: its device block cannot be created inside a capture",
+                                    "GradAccumulator: its state lives on {have}, not {want}; use one object per device")
+        if new:
             self._write_n(self._n)
-        elif self._block.device != device:
-            raise RuntimeError(f"GradAccumulator: its state lives on {self._block.device}, not {device}; use one object per device")
 
     # -- the window -------------------------------------------------------------------------------------------------
     def next_is_final(self) -> bool:
@@ -295,50 +359,35 @@ class GradAccumulator:
     def accumulate(self, params: Iterable[Tensor]) -> int:
         """One ``rn_grad_accumulate`` call on the current stream over every parameter of ``params`` that has a ``.grad``; returns the
         number of gradients added.  A parameter met for the first time gets its accumulator here (not inside a capture)."""
-        accs, gptrs, is16, ns = [], [], [], []
-        keep: List[Tensor] = []
-        dt16 = None
-        dev = None
-        for p in params:
-            g = p.grad
-            if g is None:
-                continue
-            if not g.is_cuda:
-                raise RuntimeError("GradAccumulator has no CPU fallback: it accumulates CUDA gradients (SimpleTrainer accumulates into "
-                                   ".grad for every other device)")
-            dev = g.device if dev is None else dev
-            w = p.master if hasattr(p, "master") else p.data
-            if w.dtype != torch.float32:
-                raise TypeError("GradAccumulator handles CUDA fp32 parameters and 16-bit parameters converted by use_16bit_conv_weights")
-            a = self._acc.get(p)
-            if a is None:
-                if _is_capturing():
-                    raise RuntimeError("GradAccumulator: take one step before capturing one: the accumulators cannot be created inside a capture")
-                a = self._acc[p] = torch.empty_like(w)              # the master's strides; overwritten by the window's first micro-batch
-                if self._host_pos != 0:
-                    a.fill_(0)                                      # (a parameter that joins in mid-window starts from zero)
-            if g.dtype in (torch.bfloat16, torch.float16):
-                if dt16 is None:
-                    dt16 = g.dtype
-                elif dt16 != g.dtype:
-                    raise RuntimeError("the 16-bit gradients of one accumulation must share a dtype")
-            elif g.dtype != torch.float32:
-                raise TypeError(f"unsupported gradient dtype {g.dtype}")
-            if g.stride() != a.stride():                            # same memory order for the accumulator and the gradient
-                g = g.contiguous(memory_format=torch.channels_last) if a.dim() == 4 and a.is_contiguous(memory_format=torch.channels_last) \
-                    else g.contiguous()
-                keep.append(g)
-            accs.append(a.data_ptr()); gptrs.append(g.data_ptr()); ns.append(a.numel())
-            is16.append(g.data_ptr() if g.dtype != torch.float32 else 0)
-        if not accs:
+        r = _collect(params, None, self._refuse, self._accumulator, accs=[])
+        if r is None:
             return 0
-        self._ensure_block(dev)
-        n = len(accs)
+        self._ensure_block(r["dev"])
+        n = len(r["accs"])
         with torch.cuda.device(self._block.device):
-            check(lib.rn_grad_accumulate((C.c_void_p * n)(*accs), (C.c_void_p * n)(*gptrs), (C.c_void_p * n)(*is16), (C.c_int64 * n)(*ns), n, 1,
-                                         RN_F16 if dt16 == torch.float16 else RN_BF16, self._block.data_ptr(),
-                                         torch.cuda.current_stream().cuda_stream), "rn_grad_accumulate")
+            check(lib.rn_grad_accumulate(_ptrs(r["accs"]), _ptrs(r["gptrs"]), _ptrs(r["p16s"]), (C.c_int64 * n)(*r["ns"]), n, int(bool(r["grads16"])),
+                                         _dt16(r["dt16"]), self._block.data_ptr(), torch.cuda.current_stream().cuda_stream), "rn_grad_accumulate")
         return n
+
+    @staticmethod
+    def _refuse(cpu: bool) -> Exception:
+        if cpu:
+            return RuntimeError("GradAccumulator has no CPU fallback: it accumulates CUDA gradients (SimpleTrainer accumulates into "
+                                ".grad for every other device)")
+        return TypeError("GradAccumulator handles CUDA fp32 parameters and 16-bit parameters converted by use_16bit_conv_weights")
+
+    def _accumulator(self, rec: dict, p: Tensor, w: Optional[Tensor]) -> None:
+        "``_collect``'s hook: the accumulator of ``p``, created the first time it is met (not inside a capture)."
+        if w is None:
+            return
+        a = self._acc.get(p)
+        if a is None:
+            if _is_capturing():
+                raise RuntimeError("GradAccumulator: take one step before capturing one: the accumulators cannot be created inside a capture")
+            a = self._acc[p] = torch.empty_like(w)              # the master's strides; overwritten by the window's first micro-batch
+            if self._host_pos != 0:
+                a.fill_(0)                                      # (a parameter that joins in mid-window starts from zero)
+        rec["accs"].append(a.data_ptr())
 
     def advance(self, final: bool) -> None:
         """One ``rn_grad_accum_advance`` launch on the current stream, after ``accumulate`` (and, for a final step, after the optimizer
@@ -398,22 +447,63 @@ def _clip_coef_ptr(opt, recs: List[dict], scale: Optional[Tensor]) -> Optional[i
     for r in recs:
         gptrs += r["gptrs"]; ns += r["ns"]
         is16 += [p if r["grads16"] else 0 for p in r["p16s"]]      # (a group may hold fp32 gradients for its 16-bit copies: the exchange's views)
-    return clip.compute(gptrs, is16, ns, RN_F16 if torch.float16 in dt16s else RN_BF16, scale, recs[0]["dev"])
+    return clip.compute(gptrs, is16, ns, _dt16(dt16s.pop() if dt16s else None), scale, recs[0]["dev"])
 
 
 def _install_clip(opt, max_grad_norm) -> None:
     opt.grad_clip = GradClip(max_grad_norm) if max_grad_norm is not None else None
 
 
-class MasterSGD(torch.optim.Optimizer):
+class _MasterOptimizer(torch.optim.Optimizer):
+    """What ``MasterSGD`` and ``MasterAdam`` / ``MasterAdamW`` share: ``step()`` around one ``_launch`` per parameter group."""
     # torch.amp.GradScaler.step() hands such an optimizer `grad_scale` / `found_inf` (device scalars) instead of unscaling the gradients
-    # and reading found_inf back on the host: the kernel divides and skips on the device (rn_sgd_master_step_ex), nothing synchronises
+    # and reading found_inf back on the host: the kernel divides and skips on the device, nothing synchronises
     _step_supports_amp_scaling = True
     # fp32 masters behind 16-bit conv weights (RetinaNetModel.configure_optimizers converts the model), and step(grads=...) takes the
     # fp32 bucket views of parallel.BucketedGradAllReduce
     _rn_master_weights = True
     # step() clips by global norm when `grad_clip` holds an optim.GradClip (constructor: max_grad_norm=...)
     _rn_grad_clip = True
+    _handles = "CUDA fp32 parameters and 16-bit parameters converted by use_16bit_conv_weights"
+
+    @torch.no_grad()
+    def step(self, closure=None, grads: Optional[Dict[Tensor, Tensor]] = None):
+        """``grads``: optional ``{param: fp32 gradient}`` overriding ``param.grad`` (the fp32 views of
+        ``parallel.BucketedGradAllReduce`` after the exchange, the accumulators of ``GradAccumulator``)."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._before_collect()
+        note_raw_write()                   # masters, 16-bit copies and BN affine parameters change without a _version bump
+        recs = [r for r in (_collect(group["params"], grads, self._refuse, self._state, gi=gi, group=group)
+                            for gi, group in enumerate(self.param_groups)) if r is not None]
+        scale, found = _amp_scalars(self)                                  # (set by GradScaler.step around this call)
+        coef = _clip_coef_ptr(self, recs, scale)                           # (None without a clip: the unclipped step)
+        for r in recs:
+            with torch.cuda.device(r["dev"]):
+                self._launch(r, scale.data_ptr() if scale is not None else None, found.data_ptr() if found is not None else None, coef)
+        from . import biasact
+        biasact.invalidate_dgrad_weights()           # (the kernel wrote the parameters through raw pointers: no version counter moved)
+        return loss
+
+    def _refuse(self, cpu: bool) -> Exception:
+        return TypeError(f"{type(self).__name__} handles {self._handles}")
+
+    def _before_collect(self) -> None:
+        pass
+
+    def _state(self, rec: dict, p: Tensor, w: Optional[Tensor]) -> None:
+        "``_collect``'s hook: create the state of ``p`` (``w``: its fp32 tensor; None: ``p`` has no gradient) and add its pointers to ``rec``."
+        raise NotImplementedError
+
+    def _launch(self, rec: dict, scale: Optional[int], found: Optional[int], coef: Optional[int]) -> None:
+        "The step of one group's ``rec`` on the current stream (``scale`` / ``found`` / ``coef``: nullable device addresses)."
+        raise NotImplementedError
+
+
+class MasterSGD(_MasterOptimizer):
+    _handles = "CUDA fp32 parameters and bf16 parameters converted by use_bf16_conv_weights"
 
     def __init__(self, params: Iterable, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False, max_grad_norm: Optional[float] = None):
@@ -422,100 +512,38 @@ class MasterSGD(torch.optim.Optimizer):
         _install_clip(self, max_grad_norm)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov))
 
-    @torch.no_grad()
-    def step(self, closure=None, grads: Optional[Dict[Tensor, Tensor]] = None):
-        """``grads``: optional ``{param: fp32 gradient}`` overriding ``param.grad`` (the fp32 views of
-        ``parallel.BucketedGradAllReduce`` after the exchange)."""
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        note_raw_write()                   # masters, bf16 copies and BN affine parameters change without a _version bump
-        recs = [r for r in (self._collect(group, grads) for group in self.param_groups) if r is not None]
-        scale, found = _amp_scalars(self)                                  # (set by GradScaler.step around this call)
-        coef = _clip_coef_ptr(self, recs, scale)                           # (None without a clip: the calls below are the unclipped ones)
-        for r in recs:
-            group, n = r["group"], len(r["masters"])
-            args = ((C.c_void_p * n)(*r["masters"]), (C.c_void_p * n)(*r["moms"]), (C.c_void_p * n)(*r["gptrs"]),
-                    (C.c_void_p * n)(*r["p16s"]), (C.c_int64 * n)(*r["ns"]), n, int(bool(r["grads16"])),
-                    RN_F16 if r["dt16"] == torch.float16 else RN_BF16, float(group["lr"]),
-                    float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]),
-                    int(group["nesterov"]), int(bool(r["first"])), scale.data_ptr() if scale is not None else None,
-                    found.data_ptr() if found is not None else None)
-            with torch.cuda.device(r["dev"]):
-                if coef is None:
-                    check(lib.rn_sgd_master_step_ex(*args, torch.cuda.current_stream().cuda_stream), "rn_sgd_master_step_ex")
-                else:
-                    check(lib.rn_sgd_master_step_clip(*args, coef, torch.cuda.current_stream().cuda_stream), "rn_sgd_master_step_clip")
-        from . import biasact
-        biasact.invalidate_dgrad_weights()           # (the kernel wrote the parameters through raw pointers: no version counter moved)
-        return loss
+    def _state(self, rec: dict, p: Tensor, w: Optional[Tensor]) -> None:
+        if w is None:
+            return
+        group, st = rec["group"], self.state[p]
+        if "momentum_buffer" not in st:
+            # (under a GradScaler the very first step may be SKIPPED by found_inf: the buffer then has to hold zeros, with
+            # which the next step's momentum * buf + (1 - dampening) * g is torch's first-step buf = g -- for dampening == 0
+            # only; a fill kernel, not a memset: graph.py)
+            amp = getattr(self, "found_inf", None) is not None
+            if amp and group["momentum"] != 0 and group["dampening"] != 0:
+                raise ValueError("MasterSGD under loss scaling needs dampening == 0: a first step skipped by found_inf leaves a zero "
+                                 "momentum buffer, and the next step's momentum * 0 + (1 - dampening) * g is not torch.optim.SGD's first-step buf = g")
+            st["momentum_buffer"] = (torch.empty_like(w).fill_(0) if amp else torch.empty_like(w)) if group["momentum"] != 0 else None
+            st["steps"] = 0
+        if rec.setdefault("first", st["steps"] == 0) != (st["steps"] == 0):
+            raise RuntimeError("parameters of one group must have taken the same number of steps")
+        st["steps"] += 1
+        rec.setdefault("moms", []).append(st["momentum_buffer"].data_ptr() if st["momentum_buffer"] is not None else 0)
 
-    def _collect(self, group, grads: Optional[Dict[Tensor, Tensor]]) -> Optional[dict]:
-        "The pointers of one group's step (state created, dtypes and strides checked); None when no parameter has a gradient."
-        masters, moms, gptrs, p16s, ns = [], [], [], [], []
-        grads16 = None
-        dt16 = None
-        first = None
-        keep: List[Tensor] = []
-        for p in group["params"]:
-            g = grads.get(p) if grads is not None else None
-            if g is None:
-                g = p.grad
-            if g is None:
-                continue
-            has16 = hasattr(p, "master")
-            w = p.master if has16 else p.data
-            if w.dtype != torch.float32 or not p.is_cuda:
-                raise TypeError("MasterSGD handles CUDA fp32 parameters and bf16 parameters converted by use_bf16_conv_weights")
-            st = self.state[p]
-            if "momentum_buffer" not in st:
-                # (under a GradScaler the very first step may be SKIPPED by found_inf: the buffer then has to hold zeros, with
-                # which the next step's momentum * buf + (1 - dampening) * g is torch's first-step buf = g -- for dampening == 0
-                # only; a fill kernel, not a memset: graph.py)
-                amp = getattr(self, "found_inf", None) is not None
-                if amp and group["momentum"] != 0 and group["dampening"] != 0:
-                    raise ValueError("MasterSGD under loss scaling needs dampening == 0: a first step skipped by found_inf leaves a zero "
-                                     "momentum buffer, and the next step's momentum * 0 + (1 - dampening) * g is not torch.optim.SGD's first-step buf = g")
-                st["momentum_buffer"] = (torch.empty_like(w).fill_(0) if amp else torch.empty_like(w)) if group["momentum"] != 0 else None
-                st["steps"] = 0
-            if first is None:
-                first = st["steps"] == 0
-            elif first != (st["steps"] == 0):
-                raise RuntimeError("parameters of one group must have taken the same number of steps")
-            st["steps"] += 1
-            if has16:
-                if dt16 is None:
-                    dt16 = p.dtype
-                elif dt16 != p.dtype:
-                    raise RuntimeError("the 16-bit working copies of one group must share a dtype")
-                is16 = g.dtype == p.dtype
-                if not is16 and g.dtype != torch.float32:
-                    raise TypeError(f"unsupported gradient dtype {g.dtype} for a {p.dtype} working copy")
-                if grads16 is None:
-                    grads16 = is16
-                elif grads16 != is16:
-                    raise RuntimeError("gradients of the 16-bit parameters must be all 16-bit or all fp32")
-            elif g.dtype != torch.float32:
-                raise TypeError("fp32 parameters need fp32 gradients")
-            # same memory order for master / momentum / gradient / bf16 copy: all carry the parameter's strides
-            if g.stride() != w.stride():
-                g = g.contiguous(memory_format=torch.channels_last) if w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last) \
-                    else g.contiguous()
-                keep.append(g)
-            masters.append(w.data_ptr()); moms.append(st["momentum_buffer"].data_ptr() if st["momentum_buffer"] is not None else 0)
-            gptrs.append(g.data_ptr()); p16s.append(p.data.data_ptr() if has16 else 0); ns.append(w.numel())
-        if not masters:
-            return None
-        return dict(group=group, masters=masters, moms=moms, gptrs=gptrs, p16s=p16s, ns=ns, grads16=grads16, dt16=dt16, first=first,
-                    keep=keep, dev=group["params"][0].device)
+    def _launch(self, rec: dict, scale: Optional[int], found: Optional[int], coef: Optional[int]) -> None:
+        group, n = rec["group"], len(rec["ns"])
+        check(lib.rn_sgd_master_step(_ptrs(rec["masters"]), _ptrs(rec["moms"]), _ptrs(rec["gptrs"]), _ptrs(rec["p16s"]), (C.c_int64 * n)(*rec["ns"]), n,
+                                     int(bool(rec["grads16"])), _dt16(rec["dt16"]), float(group["lr"]), float(group["momentum"]),
+                                     float(group["dampening"]), float(group["weight_decay"]), int(group["nesterov"]), int(bool(rec["first"])),
+                                     scale, found, coef, torch.cuda.current_stream().cuda_stream), "rn_sgd_master_step")
 
 
 RN_ADAM_HPARAMS = 16                    # doubles per group in the device block (include/retinanet_hip.h)
 _HP_STEP = 5                            # the step counter's slot in it
 
 
-class _MasterAdamBase(torch.optim.Optimizer):
+class _MasterAdamBase(_MasterOptimizer):
     """``torch.optim.Adam`` / ``AdamW`` on fp32 masters with 16-bit conv working copies (``use_16bit_conv_weights``), in one HIP
     prologue plus one launch per 40 tensors and parameter group (``rn_adam_master_step``, ``csrc/adam.hip``): torch's single-tensor
     fp32 arithmetic, in its order.
@@ -527,10 +555,7 @@ class _MasterAdamBase(torch.optim.Optimizer):
     and not at all in a step that ``torch.amp.GradScaler`` skips (found_inf), as in torch's fused Adam.  ``state_dict()`` /
     ``load_state_dict()`` use torch's Adam format (per-parameter ``step``, ``exp_avg``, ``exp_avg_sq``): checkpoints move both ways
     between this class and its torch counterpart (weights: ``master_state_dict`` / ``load_master_state_dict``)."""
-    _step_supports_amp_scaling = True
-    _rn_master_weights = True
     _rn_device_hparams = True            # lr / betas / eps / weight_decay are read on the device: no part of a captured graph's key
-    _rn_grad_clip = True                 # step() clips by global norm when `grad_clip` holds an optim.GradClip
     _decoupled = False
 
     def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
@@ -560,12 +585,12 @@ class _MasterAdamBase(torch.optim.Optimizer):
         return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
 
     def _block(self, i: int, dev: torch.device) -> Tensor:
-        blk = self._blocks.get(i)
-        if blk is None:
-            if _is_capturing():
-                raise RuntimeError(f"{type(self).__name__}: take one step (or call sync_device_hparams()) before capturing a step: "
-                                   "the device blocks and moments cannot be created inside a capture")
-            blk = torch.empty(RN_ADAM_HPARAMS, dtype=torch.float64, device=dev).fill_(0)      # (a fill kernel, not a memset: graph.py)
+        name = type(self).__name__
+        blk = _device_block(self._blocks.get(i), RN_ADAM_HPARAMS, dev,
+                            f"{name}: take one step (or call sync_device_hparams()) before capturing a step: "
+                            "the device blocks and moments cannot be created inside a capture",
+                            f"{name}: the state of parameter group {i} lives on {{have}}, not {{want}}; a group stays on one device")
+        if i not in self._blocks:
             self._blocks[i] = blk
             self._written.pop(i, None)
         return blk
@@ -592,98 +617,34 @@ class _MasterAdamBase(torch.optim.Optimizer):
                 self._write_block(i, group)
 
     # -- the step ------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, closure=None, grads: Optional[Dict[Tensor, Tensor]] = None):
-        """``grads``: optional ``{param: fp32 gradient}`` overriding ``param.grad`` (the fp32 views of
-        ``parallel.BucketedGradAllReduce`` after the exchange), as for ``MasterSGD``."""
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        capturing = _is_capturing()
-        if not capturing:
-            self.sync_device_hparams()
-        note_raw_write()                   # masters, 16-bit copies and BN affine parameters change without a _version bump
-        recs = [r for r in (self._collect(gi, group, grads, capturing) for gi, group in enumerate(self.param_groups)) if r is not None]
-        scale, found = _amp_scalars(self)                                  # (set by GradScaler.step around this call)
-        for r in recs:
-            if r["gi"] not in self._blocks:
-                self._block(r["gi"], r["dev"])                             # (raises under capture)
-        coef = _clip_coef_ptr(self, recs, scale)                           # (None without a clip: the calls below are the unclipped ones)
-        for r in recs:
-            n = len(r["masters"])
-            args = ((C.c_void_p * n)(*r["masters"]), (C.c_void_p * n)(*r["ms"]), (C.c_void_p * n)(*r["vs"]),
-                    (C.c_void_p * n)(*r["gptrs"]), (C.c_void_p * n)(*r["p16s"]), (C.c_int64 * n)(*r["ns"]), n,
-                    int(bool(r["grads16"])), RN_F16 if r["dt16"] == torch.float16 else RN_BF16, int(self._decoupled),
-                    self._blocks[r["gi"]].data_ptr(), scale.data_ptr() if scale is not None else None,
-                    found.data_ptr() if found is not None else None)
-            with torch.cuda.device(r["dev"]):
-                if coef is None:
-                    check(lib.rn_adam_master_step(*args, torch.cuda.current_stream().cuda_stream), "rn_adam_master_step")
-                else:
-                    check(lib.rn_adam_master_step_clip(*args, coef, torch.cuda.current_stream().cuda_stream), "rn_adam_master_step_clip")
-        from . import biasact
-        biasact.invalidate_dgrad_weights()           # (the kernel wrote the parameters through raw pointers: no version counter moved)
-        return loss
+    def _before_collect(self) -> None:
+        self.sync_device_hparams()                   # (does nothing while the stream is capturing)
 
-    def _collect(self, gi: int, group, grads: Optional[Dict[Tensor, Tensor]], capturing: bool) -> Optional[dict]:
-        "The pointers of one group's step (moments created, dtypes and strides checked); None when no parameter has a gradient."
+    def _state(self, rec: dict, p: Tensor, w: Optional[Tensor]) -> None:
         name = type(self).__name__
-        masters, ms, vs, gptrs, p16s, ns = [], [], [], [], [], []
-        grads16 = None
-        dt16 = None
-        keep: List[Tensor] = []
-        had_state = new_state = False
-        for p in group["params"]:
-            g = grads.get(p) if grads is not None else None
-            if g is None:
-                g = p.grad
-            if g is None:
-                if "exp_avg" in self.state.get(p, {}):
-                    raise RuntimeError(f"{name}: a parameter with optimizer state has no gradient in this step: the step counter is "
-                                       "one per group, so every parameter of a group must step together")
-                continue
-            has16 = hasattr(p, "master")
-            w = p.master if has16 else p.data
-            if w.dtype != torch.float32 or not p.is_cuda:
-                raise TypeError(f"{name} handles CUDA fp32 parameters and 16-bit parameters converted by use_16bit_conv_weights")
-            st = self.state[p]
-            if "exp_avg" not in st:
-                if capturing:
-                    raise RuntimeError(f"{name}: take one step before capturing one: the moments cannot be created inside a capture")
-                # same memory order as the master (empty_like keeps the strides); a fill kernel, not a memset (graph.py)
-                st["exp_avg"] = torch.empty_like(w).fill_(0)
-                st["exp_avg_sq"] = torch.empty_like(w).fill_(0)
-                new_state = True
-            else:
-                had_state = True
-            if has16:
-                if dt16 is None:
-                    dt16 = p.dtype
-                elif dt16 != p.dtype:
-                    raise RuntimeError("the 16-bit working copies of one group must share a dtype")
-                is16 = g.dtype == p.dtype
-                if not is16 and g.dtype != torch.float32:
-                    raise TypeError(f"unsupported gradient dtype {g.dtype} for a {p.dtype} working copy")
-                if grads16 is None:
-                    grads16 = is16
-                elif grads16 != is16:
-                    raise RuntimeError("gradients of the 16-bit parameters must be all 16-bit or all fp32")
-            elif g.dtype != torch.float32:
-                raise TypeError("fp32 parameters need fp32 gradients")
-            # same memory order for master / moments / gradient / 16-bit copy: all carry the parameter's strides
-            if g.stride() != w.stride():
-                g = g.contiguous(memory_format=torch.channels_last) if w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last) \
-                    else g.contiguous()
-                keep.append(g)
-            masters.append(w.data_ptr()); ms.append(st["exp_avg"].data_ptr()); vs.append(st["exp_avg_sq"].data_ptr())
-            gptrs.append(g.data_ptr()); p16s.append(p.data.data_ptr() if has16 else 0); ns.append(w.numel())
-        if had_state and new_state:
+        has_state = "exp_avg" in self.state.get(p, {})
+        if w is None:
+            if has_state:
+                raise RuntimeError(f"{name}: a parameter with optimizer state has no gradient in this step: the step counter is "
+                                   "one per group, so every parameter of a group must step together")
+            return
+        st = self.state[p]
+        if not has_state:
+            if _is_capturing():
+                raise RuntimeError(f"{name}: take one step before capturing one: the moments cannot be created inside a capture")
+            # same memory order as the master (empty_like keeps the strides); a fill kernel, not a memset (graph.py)
+            st["exp_avg"] = torch.empty_like(w).fill_(0)
+            st["exp_avg_sq"] = torch.empty_like(w).fill_(0)
+        if rec.setdefault("had_state", has_state) != has_state:
             raise RuntimeError(f"{name}: a parameter joined a group that has already stepped: the step counter is one per group")
-        if not masters:
-            return None
-        return dict(gi=gi, group=group, masters=masters, ms=ms, vs=vs, gptrs=gptrs, p16s=p16s, ns=ns, grads16=grads16, dt16=dt16,
-                    keep=keep, dev=group["params"][0].device)
+        rec.setdefault("ms", []).append(st["exp_avg"].data_ptr()); rec.setdefault("vs", []).append(st["exp_avg_sq"].data_ptr())
+
+    def _launch(self, rec: dict, scale: Optional[int], found: Optional[int], coef: Optional[int]) -> None:
+        n = len(rec["ns"])
+        blk = self._block(rec["gi"], rec["dev"])                             # (raises under capture when it is not there yet)
+        check(lib.rn_adam_master_step(_ptrs(rec["masters"]), _ptrs(rec["ms"]), _ptrs(rec["vs"]), _ptrs(rec["gptrs"]), _ptrs(rec["p16s"]),
+                                      (C.c_int64 * n)(*rec["ns"]), n, int(bool(rec["grads16"])), _dt16(rec["dt16"]), int(self._decoupled),
+                                      blk.data_ptr(), scale, found, coef, torch.cuda.current_stream().cuda_stream), "rn_adam_master_step")
 
     # -- checkpoints in torch's Adam format ------------------------------------------------------------------------
     def group_steps(self) -> List[float]:

@@ -308,7 +308,7 @@ class ExchangeGradScaler(torch.amp.GradScaler):
     ``step_exchanged`` takes found_inf from the EXCHANGED buckets (``BucketedGradAllReduce.found_inf``: identical on every rank, so all
     ranks skip or step together and ``update()`` moves every rank's scale the same way -- one scale per step on every rank without a
     second collective) and steps on the buckets' views.  With ``optim.MasterSGD`` (or ``MasterAdam`` / ``MasterAdamW``) the unscale and the skip happen on the device
-    (``rn_sgd_master_step_ex`` / ``rn_adam_master_step`` read scale and flag): nothing synchronises and the whole sequence captures into the optimizer segment of
+    (``rn_sgd_master_step`` / ``rn_adam_master_step`` read scale and flag): nothing synchronises and the whole sequence captures into the optimizer segment of
     ``graph.CapturedTrainStep``.  Other optimizers: the buckets are unscaled in place and the flag is read on the host, as the stock
     scaler does."""
 

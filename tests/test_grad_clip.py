@@ -195,3 +195,65 @@ def test_new_entry_points_reject_bad_arguments_before_any_gpu_call():
     assert lib.rn_grad_norm_clip(one(p), one(0), n1(40000), 1, 1, RN_BF16, None, p, 2, p, 0) == EINVAL        # 3 chunks, 2 slots
     assert lib.rn_grad_norm_clip(one(p + 8), one(0), n1(100), 1, 1, RN_BF16, None, p, 1, p, 0) == EALIGN      # fp32 gradient: 16 bytes
     assert lib.rn_grad_norm_clip(one(p + 4), one(p), n1(100), 1, 1, RN_BF16, None, p, 1, p, 0) == EALIGN      # 16-bit gradient: 8 bytes
+
+
+def test_step_entry_points_reject_bad_arguments_before_any_gpu_call():
+    """``rn_sgd_master_step`` / ``rn_adam_master_step`` (the only two step entry points; a null ``clip_coef`` is the unclipped step):
+    every tensor is checked before the first launch, so no case below touches a device."""
+    import ctypes as C
+    from pytorch_retinanet_amd._lib import RN_BF16, lib
+    EINVAL, EALIGN, EUNSUP = -1, -2, -4
+    p = 4096
+    arr = lambda vs: (C.c_void_p * len(vs))(*vs)
+    num = lambda vs: (C.c_int64 * len(vs))(*vs)
+
+    def sgd(masters, moms, grads, p16s, ns, n=None, grads16=1, dt=RN_BF16, momentum=0.9):
+        a = [arr(v) if v is not None else None for v in (masters, moms, grads, p16s)]
+        return lib.rn_sgd_master_step(*a, num(ns) if ns is not None else None, len(ns) if n is None else n, grads16, dt, 0.1, momentum, 0.0,
+                                      1e-3, 0, 1, None, None, None, 0)
+
+    def adam(masters, ms, vs, grads, p16s, ns, n=None, grads16=1, dt=RN_BF16, hp=p):
+        a = [arr(v) if v is not None else None for v in (masters, ms, vs, grads, p16s)]
+        return lib.rn_adam_master_step(*a, num(ns) if ns is not None else None, len(ns) if n is None else n, grads16, dt, 1, hp, None, None, None, 0)
+
+    # -- SGD
+    assert sgd([p], [p], [p], [0], [100], dt=7) == EUNSUP                          # a bad dtype16
+    for hole in range(5):                                                          # null tables
+        t = [[p], [p], [p], [0], [100]]
+        t[hole] = None
+        assert sgd(*t, n=1) == EINVAL
+    assert sgd([p], [p], [p], [0], [100], n=-1) == EINVAL
+    assert sgd([0], [p], [p], [0], [100]) == EINVAL                                # a null master
+    assert sgd([p], [p], [0], [0], [100]) == EINVAL                                # a null gradient
+    assert sgd([p], [0], [p], [0], [100]) == EINVAL                                # a null momentum buffer with momentum != 0
+    assert sgd([p], [p], [p], [0], [-1]) == EINVAL                                 # a negative numel
+    assert sgd([p + 8], [p], [p], [0], [100]) == EALIGN                            # master: 16 bytes
+    assert sgd([p], [p + 8], [p], [0], [100]) == EALIGN                            # momentum buffer: 16 bytes
+    assert sgd([p], [p], [p + 8], [0], [100]) == EALIGN                            # fp32 gradient: 16 bytes
+    assert sgd([p], [p], [p + 8], [p], [100]) == EALIGN                            # 16-bit gradient: 16 bytes too (parallel.py's views)
+    assert sgd([p], [p], [p], [p + 4], [100]) == EALIGN                            # the 16-bit copy: 8 bytes
+    assert sgd([p], [p], [p], [0], [100], n=0) == 0                                # nothing to do: no launch
+    # the first 48 tensors (one launch) are valid, the 49th is not: the error comes back and nothing has been launched
+    good = [p] * 48
+    assert sgd(good + [0], good + [p], good + [p], [0] * 49, [0] * 49) == EINVAL
+    assert sgd(good + [p + 8], good + [p], good + [p], [0] * 49, [0] * 49) == EALIGN
+    assert sgd(good + [p], good + [p], good + [p], [0] * 49, [0] * 48 + [-1]) == EINVAL
+    # -- Adam / AdamW
+    assert adam([p], [p], [p], [p], [0], [100], dt=7) == EUNSUP
+    for hole in range(6):
+        t = [[p], [p], [p], [p], [0], [100]]
+        t[hole] = None
+        assert adam(*t, n=1) == EINVAL
+    assert adam([p], [p], [p], [p], [0], [100], hp=0) == EINVAL and adam([p], [p], [p], [p], [0], [100], hp=p + 4) == EALIGN
+    assert adam([p], [p], [p], [p], [0], [100], n=-1) == EINVAL
+    assert adam([0], [p], [p], [p], [0], [100]) == EINVAL                          # a null master
+    assert adam([p], [0], [p], [p], [0], [100]) == EINVAL and adam([p], [p], [0], [p], [0], [100]) == EINVAL       # a null moment
+    assert adam([p], [p], [p], [0], [0], [100]) == EINVAL                          # a null gradient
+    assert adam([p], [p], [p], [p], [0], [-1]) == EINVAL
+    assert adam([p + 8], [p], [p], [p], [0], [100]) == EALIGN                      # master: 16 bytes
+    assert adam([p], [p + 8], [p], [p], [0], [100]) == EALIGN and adam([p], [p], [p + 8], [p], [0], [100]) == EALIGN
+    assert adam([p], [p], [p], [p + 8], [0], [100]) == EALIGN                      # fp32 gradient: 16 bytes
+    assert adam([p], [p], [p], [p + 4], [p], [100]) == EALIGN                      # 16-bit gradient: 8 bytes
+    assert adam([p], [p], [p], [p], [p + 4], [100]) == EALIGN                      # the 16-bit copy: 8 bytes
+    good = [p] * 40
+    assert adam(good + [0], good + [p], good + [p], good + [p], [0] * 41, [0] * 41) == EINVAL

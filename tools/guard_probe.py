@@ -294,7 +294,7 @@ def main() -> None:
             ptrs = lambda ts: (C.c_void_p * n_t)(*[t.data_ptr() if t is not None else 0 for t in ts])
             check(lib.rn_adam_master_step(ptrs(masters), ptrs(ms), ptrs(vs), ptrs(gd), ptrs(p16), (C.c_int64 * n_t)(*sizes), n_t, 1,
                                           RN_F16 if dt == torch.float16 else RN_BF16, 1, hp.data_ptr(), scale.data_ptr(), found.data_ptr(),
-                                          st), "rn_adam_master_step")
+                                          None, st), "rn_adam_master_step")
             for prm, x in zip(ropt.param_groups[0]["params"], gs16):
                 prm.grad = x.float()
             ropt.param_groups[0]["lr"] = lr
@@ -310,7 +310,7 @@ def main() -> None:
         assert float(hp[5]) == 3.0, float(hp[5])
         print("ok adam", str(dt), n_t, f"{worst:.2e}", flush=True)
     elif which == "clip":
-        # rn_grad_norm_clip + rn_sgd_master_step_clip + rn_adam_master_step_clip (csrc/clip.hip, optim.hip, adam.hip): 230 tensors (two
+        # rn_grad_norm_clip + rn_sgd_master_step + rn_adam_master_step with a clip_coef (csrc/clip.hip, optim.hip, adam.hip): 230 tensors (two
         # norm launches of 224 + 6), every gradient ENDING at the last byte its alignment contract allows in its own mapping (16-bit
         # gradients 8-byte aligned: the norm kernel's head path; sizes through the tail paths; one tensor of three chunks), the
         # scratch buffer of exactly the required slots and the clip block at the end of theirs.  The norm against float64, the two
@@ -361,8 +361,8 @@ def main() -> None:
         p16 = [at_end(w.to(dt), 8) if h else None for w, h in zip(w32, with16)]
         moms = [at_end(torch.zeros(n, device=DEV)) for n in sizes]
         gd16 = [at_end(x * 8.0) for x in gs]                                           # (the SGD step wants 16-byte aligned gradients)
-        check(lib.rn_sgd_master_step_clip(ptrs(masters), ptrs(moms), ptrs(gd16), ptrs(p16), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, 0.05, 0.9, 0.0,
-                                          1e-2, 0, 1, scale.data_ptr(), found.data_ptr(), coef_ptr, st), "rn_sgd_master_step_clip")
+        check(lib.rn_sgd_master_step(ptrs(masters), ptrs(moms), ptrs(gd16), ptrs(p16), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, 0.05, 0.9, 0.0,
+                                     1e-2, 0, 1, scale.data_ptr(), found.data_ptr(), coef_ptr, st), "rn_sgd_master_step")
         ref_p = [torch.nn.Parameter(w.clone()) for w in w32]
         ropt = torch.optim.SGD(ref_p, lr=0.05, momentum=0.9, weight_decay=1e-2, foreach=False)
         for prm, x in zip(ref_p, clipped):
@@ -380,8 +380,8 @@ def main() -> None:
         vs = [at_end(torch.zeros(n, device=DEV)) for n in sizes]
         hp = at_end(torch.zeros(16, dtype=torch.float64, device=DEV), 8)
         check(lib.rn_adam_hparams_set(hp.data_ptr(), 1e-2, 0.9, 0.999, 1e-8, 0.1, -1.0, st), "rn_adam_hparams_set")
-        check(lib.rn_adam_master_step_clip(ptrs(masters), ptrs(ms), ptrs(vs), ptrs(gd), ptrs(p16), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, 1,
-                                           hp.data_ptr(), scale.data_ptr(), found.data_ptr(), coef_ptr, st), "rn_adam_master_step_clip")
+        check(lib.rn_adam_master_step(ptrs(masters), ptrs(ms), ptrs(vs), ptrs(gd), ptrs(p16), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, 1,
+                                      hp.data_ptr(), scale.data_ptr(), found.data_ptr(), coef_ptr, st), "rn_adam_master_step")
         ref_p = [torch.nn.Parameter(w.clone()) for w in w32]
         ropt = torch.optim.AdamW(ref_p, lr=1e-2, weight_decay=0.1, foreach=False)
         for prm, x in zip(ref_p, clipped):
