@@ -8,6 +8,19 @@ image sizes and the GT counts are known, so the launch sequence is captured once
 (reference analogue: none -- the reference launches ~40 torch ops per image from a Python loop with 4 host syncs each,
 ``retinanet/losses.py:66-126``).
 
+The step has ONE body, ``CapturedTrainStep._step``, and every kind of step is that body with other arguments:
+  zero the gradients -> ``_forward`` (the net under autocast and ``losses.grad_prescale``; total = the sum of its two losses)
+  -> ``_backward`` ((scaled) total.backward()) -> ``ddp.finish()`` -> ``accumulate`` -> ``apply_gradients`` -> ``advance`` -> the loss dict.
+  * a gradient exchange (``ddp=``) replaces the optimizer's zero_grad by its own and adds the wait for the collectives (``finish``);
+  * a segmented step (below, ``segmented=``) installs ``backbone.StageCuts`` for the forward pass and ``_backward`` then runs three
+    stages, calling ``mark(i)`` after each: the eager step issues the finished buckets' all-reduces there, the capture also ends one
+    graph and begins the next;
+  * an accumulator (``accumulate=``) adds the gradients to its fp32 sums after the backward pass and moves its window after the
+    optimizer; a micro step (``final=False``) is the same body without ``apply_gradients``;
+  * ``apply_gradients(optimizer, scaler, source)`` is the one place that decides how the gradients reach the optimizer: through the
+    scaler or not, from the source (the exchange's buckets or the accumulator: ``step_exchanged`` / ``step(grads=...)``) or from ``.grad``.
+    ``model.SimpleTrainer``'s eager loop ends in the same function.
+
 Rules the capture relies on (all true of this package; checked by ``tests/test_graph_gpu.py``):
   * no host synchronisation and no host->device copy from temporary host memory inside the step: the GT offsets come from
     ``ops.gt_offsets`` (cached per count tuple), canvas masks / anchors / zero pages from their caches -- the eager steps
@@ -23,9 +36,8 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     new p needs no capture.  Gradient clipping (``optimizer.grad_clip``, ``optim.GradClip``) is keyed the same way: ``max_norm`` is
     read from the object's device block, whose first (eager) step creates it.
     Gradient accumulation (``accumulate=optim.GradAccumulator``) is keyed by the installed object too, and the window position is NOT
-    part of the key: it lives in the object's device block.  A signature then holds up to two graphs -- the micro step (zero_grad ->
-    forward -> backward -> accumulate -> advance) and the final step (the same, plus clip + optimizer step on the accumulators + scaler
-    update, then the window reset) -- each warmed by its own ``eager_steps`` eager calls; ``max_graphs`` still counts signatures.
+    part of the key: it lives in the object's device block.  A signature then holds up to two graphs -- the micro step and the final
+    step (``_Signature.steps``) -- each warmed by its own ``eager_steps`` eager calls; ``max_graphs`` still counts signatures.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -96,13 +108,34 @@ def _net_targets(targets):
 
 
 class _Entry:
-    __slots__ = ("graph", "images", "targets", "losses", "calls", "failed", "match_state", "segments", "bucket_ids", "pool", "packed", "micro")
+    "One kind of step of one signature: the calls seen so far and, once captured, the graph(s), their static inputs and the losses they write."
+    __slots__ = ("calls", "failed", "graph", "segments", "bucket_ids", "pool", "images", "targets", "losses", "match_state")
 
     def __init__(self):
-        self.graph, self.images, self.targets, self.losses, self.calls, self.failed, self.match_state = None, None, None, None, 0, False, None
-        self.segments, self.bucket_ids, self.pool = None, None, None
-        self.packed = None        # GT capacity mode: this entry's ops.PackedGT (B x class rows), staged before every call
-        self.micro = None         # gradient accumulation: the signature's second holder (the micro step's graph, buffers and call count)
+        self.calls, self.failed = 0, False
+        self.clear()
+
+    def clear(self) -> None:
+        "Nothing captured (the initial state, and what a failed capture goes back to): drops the graphs and their private memory pool."
+        self.graph = self.segments = self.bucket_ids = self.pool = None
+        self.images = self.targets = self.losses = self.match_state = None
+
+    def hold_inputs(self, images, targets) -> None:
+        """The static inputs every replay reads (copies of this call's; packed GT is static already) and the fused loss kernel's state
+        words: zero-filled here, OUTSIDE the capture, and owned by this entry (``ops.use_match_state``)."""
+        self.images = [im.clone() for im in images]
+        self.targets = targets if isinstance(targets, ops.PackedGT) else \
+            [{k: (v.clone() if isinstance(v, Tensor) else v) for k, v in t.items()} for t in targets]
+        self.match_state = ops.new_match_state(images[0].device)
+
+
+class _Signature:
+    "What one input signature owns: the GT staging buffers of the capacity mode and an ``_Entry`` per kind of step."
+    __slots__ = ("packed", "steps")
+
+    def __init__(self, packed=None):
+        self.packed = packed      # GT capacity mode: ops.PackedGT (B x class rows), staged before every call of either kind
+        self.steps = {}           # final -> _Entry.  Without gradient accumulation every step is final
 
 
 class MemsetNodeInGraph(RuntimeError):
@@ -195,6 +228,24 @@ def retinanet_stage_of(name: str) -> int:
     return 0
 
 
+def apply_gradients(optimizer, scaler, source=None) -> None:
+    """How the gradients of a finished backward pass reach the optimizer -- decided here and nowhere else.  ``source``: who holds them
+    when ``.grad`` is not the place to look -- a gradient exchange (``parallel.BucketedGradAllReduce``, after ``finish()``), an
+    ``optim.GradAccumulator``, or None.  A scaler takes its found_inf from the source (``ExchangeGradScaler.step_exchanged``) and is
+    updated; the master optimizers step on the source's fp32 views (``step(grads=source.grad_views())``); any other optimizer, and
+    every optimizer without a source, reads ``.grad``."""
+    if scaler is not None:
+        if source is not None:
+            scaler.step_exchanged(optimizer, source)
+        else:
+            scaler.step(optimizer)
+        scaler.update()
+    elif source is not None and getattr(optimizer, "_rn_master_weights", False):
+        optimizer.step(grads=source.grad_views())
+    else:
+        optimizer.step()
+
+
 class CapturedTrainStep:
     def __init__(self, net, optimizer, ddp=None, amp_dtype: Optional[torch.dtype] = torch.bfloat16, eager_steps: int = 2,
                  max_graphs: int = 4, enabled: bool = True, segmented: Optional[bool] = None, scaler=None, gt_capacity=None,
@@ -239,33 +290,30 @@ class CapturedTrainStep:
             ddp.deferred = True
         self.amp_dtype = amp_dtype
         self.eager_steps, self.max_graphs, self.enabled = max(int(eager_steps), 1), int(max_graphs), enabled
-        self._entries: "OrderedDict[tuple, _Entry]" = OrderedDict()
+        self._entries: "OrderedDict[tuple, _Signature]" = OrderedDict()
         self.replays = 0          # steps served by a graph replay (diagnostics / tests)
         self.captures = 0
 
     # -- the step itself (identical in eager mode and under capture) -------------------------------------------------
-    def _staged(self, images, targets, mark) -> Dict[str, Tensor]:
-        """The step with the backward pass in stages; ``mark(i)`` runs after stage i's kernels have been enqueued (i = 0, 1, 2: the
-        buckets completed so far may be exchanged; 3: after the optimizer).  ``ddp.finish()`` -- the wait for the exchange -- runs
-        between mark(2) and the optimizer, outside any capture."""
-        from .backbone import StageCuts
-        net, opt, ddp = self.net, self.optimizer, self.ddp
-        trunk = net.backbone.backbone
-        cuts = StageCuts()
-        ddp.zero_grad()
-        trunk.stage_cuts = cuts
+    def _forward(self, images, targets) -> Tuple[Dict[str, Tensor], Tensor]:
+        "The forward pass under autocast -> (the net's loss dict, the sum of the two losses)."
         from .losses import grad_prescale, scaler_prescale
+        # fp16: the loss kernel multiplies the GradScaler's scale into its gradients before it rounds them to fp16 (losses.grad_prescale)
         pre = scaler_prescale(self.scaler, images[0].device) if images[0].is_cuda else None
-        try:
-            with torch.autocast(images[0].device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None, cache_enabled=False), \
-                    grad_prescale(pre):
-                losses = net(list(images), _net_targets(targets))
-                total = losses["classification_loss"] + losses["regression_loss"]
-        finally:
-            trunk.stage_cuts = None
-        # stage 0: head + FPN; gradients of the cut leaves.  fp16: the scaled loss -- every later stage starts from scaled leaf gradients
+        with torch.autocast(images[0].device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None, cache_enabled=False), \
+                grad_prescale(pre):
+            losses = self.net(list(images), _net_targets(targets))
+            total = losses["classification_loss"] + losses["regression_loss"]
+        return losses, total
+
+    def _backward(self, total: Tensor, cuts, mark) -> None:
+        """The backward pass: one autograd call, or -- ``cuts``: the ``backbone.StageCuts`` the forward pass filled -- three stages, with
+        ``mark(i)`` after stage i's kernels have been enqueued (the buckets completed so far may be exchanged)."""
+        # fp16: the scaled loss -- every later stage starts from scaled leaf gradients
         (self.scaler.scale(total) if self.scaler is not None else total).backward()
-        mark(0)
+        if cuts is None:
+            return
+        mark(0)                                                   # stage 0 was head + FPN; gradients of the cut leaves
         pairs = cuts.pairs                                        # [(C3, leaf), (C4, leaf), (C5, leaf)] in forward order
         # C3 / C4 join the data gradients of their consumers in the receiver's GEMM (pwconv._GradJoin); the FPN lateral's gradient was
         # produced in ANOTHER autograd pass (stage 0), so it is handed to the join here: the receiver accumulates into it (addmm_) and
@@ -283,77 +331,42 @@ class CapturedTrainStep:
             pairs[0][0].backward(pairs[0][1].grad)
             pairs[0][1].grad = None
         mark(2)
-        ddp.finish()
-        if self.scaler is not None:
-            self.scaler.step_exchanged(opt, ddp)                  # found_inf from the exchanged buckets: the same on every rank
-            self.scaler.update()
-        elif getattr(opt, "_rn_master_weights", False):
-            opt.step(grads=ddp.grad_views())
-        else:
-            opt.step()
-        mark(3)
-        return {"classification_loss": losses["classification_loss"].detach(), "regression_loss": losses["regression_loss"].detach(),
-                "loss": total.detach()}
 
-    def _step_accumulating(self, images, targets, final: bool) -> Dict[str, Tensor]:
-        """One micro-batch of an accumulation window: the plain step up to the backward pass, then the gradients into the fp32
-        accumulators; ``final``: clip + optimizer step on the accumulators (+ scaler update), and the window reset."""
-        net, opt, acc = self.net, self.optimizer, self.accumulate
-        opt.zero_grad(set_to_none=True)
-        from .losses import grad_prescale, scaler_prescale
-        pre = scaler_prescale(self.scaler, images[0].device) if images[0].is_cuda else None
-        with torch.autocast(images[0].device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None, cache_enabled=False), grad_prescale(pre):
-            losses = net(list(images), _net_targets(targets))
-            total = losses["classification_loss"] + losses["regression_loss"]
-        # the UNDIVIDED loss goes backward (and to the caller): the 1 / n of the window is the accumulate kernel's weight
-        (self.scaler.scale(total) if self.scaler is not None else total).backward()
-        acc.accumulate(p for g in opt.param_groups for p in g["params"])
-        if final:
-            if self.scaler is not None:
-                self.scaler.step_exchanged(opt, acc)                  # found_inf of the whole window, from the accumulator's block
-                self.scaler.update()
-            else:
-                opt.step(grads=acc.grad_views())
-        acc.advance(final)
-        return {"classification_loss": losses["classification_loss"].detach(), "regression_loss": losses["regression_loss"].detach(),
-                "loss": total.detach()}
-
-    def _step(self, images: Sequence[Tensor], targets: Sequence[Dict[str, Tensor]], final: bool = True) -> Dict[str, Tensor]:
-        net, opt, ddp = self.net, self.optimizer, self.ddp
-        if self.accumulate is not None:
-            return self._step_accumulating(images, targets, final)
-        if self.segmented:
-            return self._staged(images, targets, lambda i: ddp.issue_ready() if i < 3 else None)
+    def _step(self, images: Sequence[Tensor], targets: Sequence[Dict[str, Tensor]], final: bool = True, mark=None) -> Dict[str, Tensor]:
+        """One step.  ``final`` (gradient accumulation only; without it every step is final): False = a micro step, which stops
+        short of the optimizer.  ``mark`` (segmented steps only): called with i = 0, 1, 2 after each backward stage and with 3 after
+        the optimizer; the default issues the finished buckets' all-reduces, the segmented capture ends and begins its graphs in it.
+        ``ddp.finish()`` -- the wait for the exchange -- runs between mark(2) and the optimizer, outside any capture."""
+        net, opt, ddp, acc = self.net, self.optimizer, self.ddp, self.accumulate
         if ddp is not None:
             ddp.zero_grad()
         else:
             opt.zero_grad(set_to_none=True)
-        dev_type = images[0].device.type
-        from .losses import grad_prescale, scaler_prescale
-        # fp16: the loss kernel multiplies the GradScaler's scale into its gradients before it rounds them to fp16 (losses.grad_prescale)
-        pre = scaler_prescale(self.scaler, images[0].device) if images[0].is_cuda else None
-        with torch.autocast(dev_type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None, cache_enabled=False), grad_prescale(pre):
-            losses = net(list(images), _net_targets(targets))
-            total = losses["classification_loss"] + losses["regression_loss"]
-        if self.scaler is not None:
-            self.scaler.scale(total).backward()
-            if ddp is not None:
-                ddp.finish()
-                self.scaler.step_exchanged(opt, ddp)
-            else:
-                self.scaler.step(opt)
-            self.scaler.update()
-            return {"classification_loss": losses["classification_loss"].detach(), "regression_loss": losses["regression_loss"].detach(),
-                    "loss": total.detach()}
-        total.backward()
+        cuts = None
+        if self.segmented:
+            from .backbone import StageCuts
+            if mark is None:
+                mark = lambda i: ddp.issue_ready() if i < 3 else None
+            trunk = net.backbone.backbone
+            cuts = trunk.stage_cuts = StageCuts()
+        try:
+            losses, total = self._forward(images, targets)
+        finally:
+            if cuts is not None:
+                trunk.stage_cuts = None
+        self._backward(total, cuts, mark)
         if ddp is not None:
             ddp.finish()
-            if getattr(opt, "_rn_master_weights", False):
-                opt.step(grads=ddp.grad_views())
-            else:
-                opt.step()
-        else:
-            opt.step()
+        if acc is not None:
+            # the UNDIVIDED loss went backward (and goes to the caller): the 1 / n of the window is the accumulate kernel's weight
+            acc.accumulate(p for g in opt.param_groups for p in g["params"])
+        if final:
+            # (under a scaler, found_inf comes from the source: the exchanged buckets -- the same on every rank -- or the whole window)
+            apply_gradients(opt, self.scaler, ddp if ddp is not None else acc)
+        if acc is not None:
+            acc.advance(final)                                    # (final: the window reset)
+        if cuts is not None:
+            mark(3)
         return {"classification_loss": losses["classification_loss"].detach(), "regression_loss": losses["regression_loss"].detach(),
                 "loss": total.detach()}
 
@@ -391,10 +404,7 @@ class CapturedTrainStep:
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."
         dev = images[0].device
-        e.images = [im.clone() for im in images]
-        e.targets = targets if isinstance(targets, ops.PackedGT) else \
-            [{k: (v.clone() if isinstance(v, Tensor) else v) for k, v in t.items()} for t in targets]
-        e.match_state = ops.new_match_state(dev)
+        e.hold_inputs(images, targets)
         e.pool = torch.cuda.graph_pool_handle()
         e.segments, e.bucket_ids = [], []
         ddp = self.ddp
@@ -428,11 +438,11 @@ class CapturedTrainStep:
             ddp.finish = finish_then_begin
             try:
                 begin()
-                e.losses = self._staged(e.images, e.targets, mark)
+                e.losses = self._step(e.images, e.targets, mark=mark)
             except BaseException:
                 # a failure inside an open segment (a MIOpen / check() error in forward or backward) must END that capture before
                 # anything else touches the device from this thread: torch.cuda.graph.__exit__ does this for the one-graph path, the
-                # hand-driven begin / mark pair has to do it itself.  Then the half-built segments and their pool are dropped.
+                # hand-driven begin / mark pair has to do it itself.  Then the half-built segments are reset (the caller clears the entry).
                 if state["open"]:
                     # the autograd engine may have pulled OTHER streams into the capture (an AccumulateGrad node created by an eager
                     # step lives on the stream of that step: the engine makes that stream wait for the capturing one and joins it
@@ -455,7 +465,6 @@ class CapturedTrainStep:
                     except Exception:                # noqa: BLE001
                         pass
                 state["g"] = None
-                e.segments, e.bucket_ids, e.pool, e.losses = None, None, None, None
                 raise
             finally:
                 ddp.finish = orig_finish
@@ -473,13 +482,9 @@ class CapturedTrainStep:
     def _capture(self, e: _Entry, images, targets, final: bool = True) -> None:
         if self.segmented:
             return self._capture_segments(e, images, targets)
-        e.images = [im.clone() for im in images]
-        e.targets = targets if isinstance(targets, ops.PackedGT) else \
-            [{k: (v.clone() if isinstance(v, Tensor) else v) for k, v in t.items()} for t in targets]
+        e.hold_inputs(images, targets)
         torch.cuda.synchronize()
         g = _new_graph()
-        # the fused loss kernel's state words: zero-filled here, OUTSIDE the capture, and owned by this entry (ops.use_match_state)
-        e.match_state = ops.new_match_state(e.images[0].device)
         with ops.use_match_state(e.match_state), torch.cuda.graph(g, capture_error_mode="thread_local"):
             e.losses = self._step(e.images, e.targets, final)
         _repair_memset_nodes(g)
@@ -501,28 +506,23 @@ class CapturedTrainStep:
             return self._step(images, targets, final)
         key = self._signature(images, targets)
         cap = self._capacity_of(targets)
-        e = self._entries.get(key)
-        if e is None:
-            e = self._entries[key] = _Entry()
-            if cap is not None:
-                e.packed = ops.PackedGT.empty(len(images), cap, images[0].device)
+        sig = self._entries.get(key)
+        if sig is None:
+            sig = self._entries[key] = _Signature(ops.PackedGT.empty(len(images), cap, images[0].device) if cap is not None else None)
             while len(self._entries) > self.max_graphs:
-                self._entries.popitem(last=False)            # drops the graph and its private memory pool
+                self._entries.popitem(last=False)            # drops the signature's graphs and their private memory pools
         else:
             self._entries.move_to_end(key)
-        sig = e                                               # (the signature's entry: GT staging buffers)
-        if acc is not None and not final:
-            # the micro step's graph, static buffers and warm-up count: a second holder inside the signature's entry
-            if sig.micro is None:
-                sig.micro = _Entry()
-                sig.micro.packed = sig.packed
-            e = sig.micro
+        # (gradient accumulation: the micro and the final step of a signature each have their graph, static buffers and warm-up count)
+        e = sig.steps.get(final)
+        if e is None:
+            e = sig.steps[final] = _Entry()
         e.calls += 1
-        if e.packed is not None:
-            # GT capacity mode: this batch's GT into the entry's static buffers (one launch, current stream), for eager steps,
-            # the capture and replays alike; the step itself then reads nothing but e.packed
-            ops.gt_stage([t["boxes"] for t in targets], [t["labels"] for t in targets], e.packed)
-            targets = e.packed
+        if sig.packed is not None:
+            # GT capacity mode: this batch's GT into the signature's static buffers (one launch, current stream), for eager steps,
+            # the capture and replays alike; the step itself then reads nothing but sig.packed
+            ops.gt_stage([t["boxes"] for t in targets], [t["labels"] for t in targets], sig.packed)
+            targets = sig.packed
         if e.failed or e.calls <= self.eager_steps:
             return self._step(images, targets, final)
         if e.graph is None and e.segments is None:
@@ -530,8 +530,8 @@ class CapturedTrainStep:
                 self._capture(e, images, targets, final)
             except Exception as exc:                          # noqa: BLE001 -- a step that cannot be captured still has to run
                 _log.warning("train-step capture failed (%s: %s); this input signature runs eagerly", type(exc).__name__, exc)
-                e.failed, e.graph, e.images, e.targets, e.losses, e.segments = True, None, None, None, None, None
-                e.bucket_ids, e.pool, e.match_state = None, None, None
+                e.failed = True
+                e.clear()
                 torch.cuda.synchronize()                      # (the capture's side stream has been joined by _capture_segments' finally)
                 if self.ddp is not None:
                     self.ddp.reset()
@@ -545,7 +545,7 @@ class CapturedTrainStep:
             # device (24 separate copies cost 0.19 ms per step), plain copies for the rest
             dsts, srcs = [], []
             pairs = list(zip(e.images, images))
-            if e.packed is None:
+            if sig.packed is None:
                 pairs += [(dt[k], v) for dt, st in zip(e.targets, targets) for k, v in st.items() if isinstance(v, Tensor)]
             for dst, src in pairs:
                 if src.device == dst.device and src.dtype == dst.dtype and src.shape == dst.shape and src.is_contiguous() and dst.is_contiguous():

@@ -369,51 +369,25 @@ class SimpleTrainer:
                     tgs = [{k: v for k, v in t.items() if isinstance(v, torch.Tensor) and k in ("boxes", "labels")} for t in targets]
                     out = stepper(list(images), tgs, final=final) if device_acc else stepper(list(images), tgs)
                     self.captured_steps = stepper.replays
-                elif n_acc > 1:
-                    # the plain thing: every micro-batch adds (loss / N)'s gradients into .grad; step and zero at the end of the window
+                else:
+                    # the plain thing: every micro-batch adds (loss / N)'s gradients into .grad; zero at the start of a window, step at
+                    # its end (N = 1: every batch is a window)
+                    from .graph import apply_gradients
                     from .losses import grad_prescale, scaler_prescale
                     with self._autocast(), grad_prescale(scaler_prescale(scaler, self.device)):
                         out = model.training_step(batch, i)
                     if i % n_acc == 0:
-                        optimizer.zero_grad(set_to_none=False)
-                    part = out["loss"] / n_acc
+                        ddp.zero_grad() if ddp is not None else optimizer.zero_grad(set_to_none=False)
+                    part = out["loss"] / n_acc if n_acc > 1 else out["loss"]      # (N = 1: a division by 1 would be one more launch)
                     (scaler.scale(part) if scaler is not None else part).backward()
                     if final:
+                        if ddp is not None:
+                            ddp.finish()
                         if torch_clip:
                             if scaler is not None:
                                 scaler.unscale_(optimizer)
                             grad_norm = torch.nn.utils.clip_grad_norm_(model.net.parameters(), clip_val)
-                        if scaler is not None:
-                            scaler.step(optimizer)
-                            scaler.update()
-                        else:
-                            optimizer.step()
-                else:
-                    from .losses import grad_prescale, scaler_prescale
-                    with self._autocast(), grad_prescale(scaler_prescale(scaler, self.device)):
-                        out = model.training_step(batch, i)
-                    ddp.zero_grad() if ddp else optimizer.zero_grad(set_to_none=False)
-                    if scaler is not None:
-                        scaler.scale(out["loss"]).backward()
-                        if ddp:
-                            ddp.finish()
-                            scaler.step_exchanged(optimizer, ddp)
-                        else:
-                            if torch_clip:
-                                scaler.unscale_(optimizer)
-                                grad_norm = torch.nn.utils.clip_grad_norm_(model.net.parameters(), clip_val)
-                            scaler.step(optimizer)
-                        scaler.update()
-                    else:
-                        out["loss"].backward()
-                        if ddp:
-                            ddp.finish()
-                        if torch_clip:
-                            grad_norm = torch.nn.utils.clip_grad_norm_(model.net.parameters(), clip_val)
-                        if ddp and getattr(optimizer, "_rn_master_weights", False):
-                            optimizer.step(grads=ddp.grad_views())       # fp32 bucket views of the bf16 working copies
-                        else:
-                            optimizer.step()
+                        apply_gradients(optimizer, scaler, ddp)       # (a master optimizer: on the fp32 bucket views of the 16-bit working copies)
                 if not final:
                     continue                                  # (schedulers, max_steps and the log count optimizer steps)
                 step += 1
