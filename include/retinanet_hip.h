@@ -817,6 +817,39 @@ int rn_grad_accum_set(void *block, int n, void *stream);
 int rn_grad_accum_advance(void *block, int final, void *stream);
 int rn_grad_accumulate(float *const *accs, const void *const *grads, void *const *params16, const int64_t *numels, int n_tensors,
                        int grads16, int dtype16, void *block, void *stream);
+/* ---- exponential moving average of the fp32 master weights for the master optimizers, capturable (csrc/ema.hip) -----
+ * What torchvision's detection recipes (--model-ema), timm's ModelEma and Lightning's EMA callbacks keep beside the trained weights,
+ * with everything that changes from one update to the next in a DEVICE block, so one captured step serves every update.
+ * The block: RN_EMA_STATE doubles (8-byte aligned, zero-filled by its owner before first use), laid out as
+ *   byte  0  f64 decay      in [0, 1)
+ *   byte  8  f64 warmup     >= 0; 0: no warm-up
+ *   byte 16  i64 updates    updates applied so far (skipped steps not counted)
+ *   byte 24  i64 skipped    steps skipped because found_inf was set
+ *   byte 32  f32 om         (RN_EMA_OM_OFFSET) the factor the NEXT update uses, for t = updates, all in double:
+ *                             d_t = warmup > 0 ? min(decay, (1 + t) / (warmup + t)) : decay;   om = float(1.0 - d_t)
+ *   the rest reserved.
+ * rn_ema_set: one single-wave launch writing decay and warmup, `updates` when it is >= 0 (-1 keeps the current value), and om for
+ * them -- the host's only way in; a captured step follows the values last written.
+ * rn_ema_update: emas / masters / numels are HOST arrays over the tensors of ALL parameter groups, all f32 and 16-byte aligned, emas[i]
+ * in the memory order of masters[i].  found_inf: nullable DEVICE f32 scalar (the GradScaler's): when it is non-null and non-zero nothing
+ * is written.  Per element, in fp32 with three roundings (no fused multiply-add):
+ *   ema = updates == 0 ? w : ema + (w - ema) * om
+ * At updates == 0 the average is overwritten without being read (nothing initialises it).  One workgroup per RN_CLIP_CHUNK elements of
+ * a tensor, one launch per 160 tensors; nothing is read or written beyond numels[i]; the block is only read.  No host synchronisation,
+ * no memset, no atomics: capturable.
+ * rn_ema_advance: one single-wave launch, to be enqueued after rn_ema_update with the same found_inf: a skipped step does skipped += 1,
+ * any other updates += 1 and recomputes om for the next update.
+ * rn_ema_swap: ema[i] <-> master[i] elementwise, in place; where params16 != NULL and params16[i] != NULL (dtype16: RN_BF16 | RN_F16,
+ * 8-byte aligned) the 16-bit rounding of the NEW master value is stored there, as the step kernels store it.  Calling it twice is the
+ * identity on all three arrays.  One launch per 120 tensors. */
+#define RN_EMA_STATE 8
+#define RN_EMA_OM_OFFSET 32
+int rn_ema_set(void *block, double decay, double warmup, int64_t updates, void *stream);
+int rn_ema_update(float *const *emas, const float *const *masters, const int64_t *numels, int n_tensors, const void *block,
+                  const float *found_inf, void *stream);
+int rn_ema_advance(void *block, const float *found_inf, void *stream);
+int rn_ema_swap(float *const *emas, float *const *masters, void *const *params16, const int64_t *numels, int n_tensors, int dtype16,
+                void *stream);
 
 /* ---- T1 transform (normalise + resize + pad + batch) -------------------------------------------
  * Replaces torchvision's GeneralizedRCNNTransform as the reference runs it at

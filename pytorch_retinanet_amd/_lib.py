@@ -124,6 +124,10 @@ SIGNATURES = {
     "rn_grad_accum_set": (C.c_int, [_vp, C.c_int, _vp]),
     "rn_grad_accum_advance": (C.c_int, [_vp, C.c_int, _vp]),
     "rn_grad_accumulate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "rn_ema_set": (C.c_int, [_vp, C.c_double, C.c_double, _i64, _vp]),
+    "rn_ema_update": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "rn_ema_advance": (C.c_int, [_vp, _vp, _vp]),
+    "rn_ema_swap": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "rn_conv3x3_canvas_to_levels": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               _vp, _vp]),
     "rn_conv3x3_levels_to_canvas": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

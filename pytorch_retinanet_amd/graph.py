@@ -38,6 +38,9 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     Gradient accumulation (``accumulate=optim.GradAccumulator``) is keyed by the installed object too, and the window position is NOT
     part of the key: it lives in the object's device block.  A signature then holds up to two graphs -- the micro step and the final
     step (``_Signature.steps``) -- each warmed by its own ``eager_steps`` eager calls; ``max_graphs`` still counts signatures.
+    A weight average (``optimizer.weight_ema``, ``optim.WeightEMA``) is keyed by the installed object as well: its update is part of
+    ``optimizer.step`` and reads its factor and count from the object's device block, so a graph captured without one is never
+    replayed once one is installed, and the reverse; without one the key is the plain one.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -399,7 +402,12 @@ class CapturedTrainStep:
         key = (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype, hflip, clip)
         # gradient accumulation (optim.GradAccumulator): the object, as for the clip -- its window position, 1 / n and found_inf are
         # read from its device block.  Without one the key is exactly the one above.
-        return key if self.accumulate is None else key + (self.accumulate,)
+        if self.accumulate is not None:
+            key = key + (self.accumulate,)
+        # the weight average (optim.WeightEMA on a master optimizer): its update is part of the optimizer step and reads its factor and
+        # count from the object's device block -- the object again; installing or removing one re-captures.  Without one nothing is added.
+        ema = getattr(self.optimizer, "weight_ema", None)
+        return key if ema is None else key + (("weight_ema", ema),)
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."

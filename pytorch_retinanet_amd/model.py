@@ -223,7 +223,8 @@ class SimpleTrainer:
 
     def __init__(self, max_epochs: int = 1, device: Optional[str] = None, precision: str = "bf16",
                  channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True,
-                 gt_capacity=None, gradient_clip_val: float = 0.0, accumulate_grad_batches: int = 1):
+                 gt_capacity=None, gradient_clip_val: float = 0.0, accumulate_grad_batches: int = 1,
+                 weight_ema_decay: float = 0.0, weight_ema_warmup: float = 0.0):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
@@ -249,7 +250,15 @@ class SimpleTrainer:
         the trainer installs an ``optim.GradAccumulator`` (``self.grad_accumulator``): the micro-batch gradients are summed in fp32 on
         the device inside the step and capture stays on (a micro graph and a final graph per batch signature).  Any other optimizer
         or device: eagerly, ``(loss / N).backward()`` into ``.grad``, then step and zero every N; this composes with the torch clip
-        and the stock ``GradScaler`` (unscaled once, at the step).  Single process only: N > 1 under ``torch.distributed`` raises."""
+        and the stock ``GradScaler`` (unscaled once, at the step).  Single process only: N > 1 under ``torch.distributed`` raises.
+
+        ``weight_ema_decay`` / ``weight_ema_warmup`` (0 = off; left at 0, optional ``trainer.weight_ema_decay`` / ``trainer.weight_ema_warmup``
+        in the hparams are honoured): keep an exponential moving average of the weights (torchvision's ``--model-ema``, timm's
+        ``ModelEma``) and validate / test on it.  With a master optimizer on CUDA the trainer installs an ``optim.WeightEMA`` on the
+        optimizer (``self.weight_ema``): the update runs on the device inside ``optimizer.step`` (once per optimizer step, skipped with a
+        step the loss scaler skips, identical on every rank) and capture stays on.  Validation inside ``fit`` and ``test()`` after it
+        run inside ``weight_ema.swapped(...)``; training always resumes on the training weights.  BatchNorm running statistics are not
+        averaged.  Any other optimizer or device raises: there is no CPU fallback."""
         from .graph import gt_capacity_classes
         from .optim import check_accumulate_grad_batches
         self.accumulate_grad_batches = check_accumulate_grad_batches(accumulate_grad_batches)
@@ -258,6 +267,12 @@ class SimpleTrainer:
         if not self.gradient_clip_val >= 0.0:
             raise ValueError(f"gradient_clip_val must be >= 0 (0 = off), got {gradient_clip_val}")
         self.grad_clip = None                             # the optim.GradClip of the last fit() (master optimizers)
+        self.weight_ema_decay, self.weight_ema_warmup = float(weight_ema_decay or 0.0), float(weight_ema_warmup or 0.0)
+        if not 0.0 <= self.weight_ema_decay < 1.0:
+            raise ValueError(f"weight_ema_decay must be in [0, 1) (0 = off), got {weight_ema_decay}")
+        if not 0.0 <= self.weight_ema_warmup < float("inf"):
+            raise ValueError(f"weight_ema_warmup must be a finite number >= 0 (0 = no warm-up), got {weight_ema_warmup}")
+        self.weight_ema = None                            # the optim.WeightEMA of the last fit() (master optimizers on CUDA)
         gt_capacity_classes(gt_capacity)                  # (bad values fail here, not at the first step)
         self.gt_capacity = gt_capacity
         self.max_epochs, self.max_steps, self.log_every, self.capture = max_epochs, max_steps, log_every, capture
@@ -285,6 +300,34 @@ class SimpleTrainer:
         section = conf.get("trainer") if hasattr(conf, "get") else None
         value = (section or {}).get("accumulate_grad_batches")
         return 1 if value is None else check_accumulate_grad_batches(value, "trainer.accumulate_grad_batches")
+
+    def resolve_weight_ema_decay(self, conf) -> float:
+        "The constructor's ``weight_ema_decay`` or, when that is 0, ``trainer.weight_ema_decay`` of the hparams (absent: 0 = off)."
+        if self.weight_ema_decay > 0:
+            return self.weight_ema_decay
+        section = conf.get("trainer") if hasattr(conf, "get") else None
+        value = float((section or {}).get("weight_ema_decay") or 0.0)
+        if not 0.0 <= value < 1.0:
+            raise ValueError(f"trainer.weight_ema_decay must be in [0, 1) (0 = off), got {value}")
+        return value
+
+    def resolve_weight_ema_warmup(self, conf) -> float:
+        "The constructor's ``weight_ema_warmup`` or, when that is 0, ``trainer.weight_ema_warmup`` of the hparams (absent: 0 = no warm-up)."
+        if self.weight_ema_warmup > 0:
+            return self.weight_ema_warmup
+        section = conf.get("trainer") if hasattr(conf, "get") else None
+        value = float((section or {}).get("weight_ema_warmup") or 0.0)
+        if not 0.0 <= value < float("inf"):
+            raise ValueError(f"trainer.weight_ema_warmup must be a finite number >= 0 (0 = no warm-up), got {value}")
+        return value
+
+    def _ema_weights(self, model):
+        """The context validation and testing run in: ``model``'s weights exchanged with the average that the last fit() kept, else
+        nothing.  A model whose parameters are not the averaged ones is refused (``WeightEMA.swap``): it would be evaluated on its raw
+        weights while another model's were swapped."""
+        import contextlib
+        ema = self.weight_ema
+        return ema.swapped(model.net.parameters()) if ema is not None and ema.ready else contextlib.nullcontext()
 
     def _autocast(self):
         return torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype is not None and self.device.type == "cuda")
@@ -342,6 +385,19 @@ class SimpleTrainer:
                 if self.capture:
                     self.log.info("gradient_clip_val=%g with %s: torch.nn.utils.clip_grad_norm_ runs eagerly, the step is not captured "
                                   "(the master optimizers clip inside the captured step)", clip_val, type(optimizer).__name__)
+        # the weight average: on the device inside optimizer.step for the master optimizers, nothing else
+        ema_decay, ema_warmup = self.resolve_weight_ema_decay(model.conf), self.resolve_weight_ema_warmup(model.conf)
+        self.weight_ema = getattr(optimizer, "weight_ema", None) if getattr(optimizer, "_rn_weight_ema", False) else None
+        if ema_decay > 0:
+            if not (getattr(optimizer, "_rn_weight_ema", False) and self.device.type == "cuda"):
+                raise ValueError(f"weight_ema_decay={ema_decay} with {type(optimizer).__name__} on {self.device.type} is not supported: the "
+                                 "average is kept on the GPU inside the step of the master optimizers, and there is no CPU fallback "
+                                 "(optimizer.class_name: pytorch_retinanet_amd.optim.MasterSGD / MasterAdam / MasterAdamW, on CUDA)")
+            from .optim import WeightEMA
+            if self.weight_ema is None:
+                self.weight_ema = optimizer.weight_ema = WeightEMA(ema_decay, ema_warmup)
+            else:
+                self.weight_ema.decay, self.weight_ema.warmup = ema_decay, ema_warmup      # (the trainer's values win)
         grad_norm = None
         stepper = None
         capturable = (self.capture and not torch_clip and (n_acc == 1 or device_acc) and self.device.type == "cuda" and ddp is None
@@ -417,7 +473,7 @@ class SimpleTrainer:
         was_training = model.training
         model.eval()                      # Lightning validates in eval mode: BN uses (and does not update) running statistics
         try:
-            with torch.no_grad():
+            with torch.no_grad(), self._ema_weights(model):            # (the swap is undone when validation raises, too)
                 for i, batch in enumerate(loader):
                     with self._autocast():
                         out = model.validation_step(_to_device(batch, self.device), i)
@@ -433,7 +489,7 @@ class SimpleTrainer:
     def test(self, model: RetinaNetModel):
         model.to(self.device).eval()
         outs = []
-        with torch.no_grad():
+        with torch.no_grad(), self._ema_weights(model):
             for i, batch in enumerate(model.test_dataloader()):
                 with self._autocast():
                     outs.append(model.test_step(_to_device(batch, self.device), i))

@@ -22,7 +22,13 @@ captures like the plain one.
 ``GradAccumulator`` -- Lightning's ``accumulate_grad_batches`` for the three of them (``rn_grad_accumulate``, ``csrc/accum.hip``): the
 gradients of N micro-batches summed into fp32 accumulators (never in 16 bits), the window position, 1 / N and found_inf in a device
 block, the optimizer stepping on the accumulators through ``step(grads=...)``: one micro graph and one final graph per batch signature.
+
+``WeightEMA`` -- an exponential moving average of the fp32 weights for the three of them (``rn_ema_update``, ``csrc/ema.hip``; torchvision's
+``--model-ema``, timm's ``ModelEma``): installed as ``optimizer.weight_ema`` it is updated inside ``step()`` -- skipped with the step under a
+loss scaler, part of a captured step -- with the decay schedule and the update count in a device block; ``swapped()`` exchanges it with the
+training weights for evaluation and checkpoints.
 """
+import contextlib
 import ctypes as C
 from typing import Dict, Iterable, List, Optional
 
@@ -423,6 +429,312 @@ class GradAccumulator:
         return {"windows": windows, "nonfinite": nonfinite, "micro_batches": micro}
 
 
+def _is_dense(t: Tensor) -> bool:
+    "Whether ``t``'s elements are exactly ``numel()`` consecutive elements of memory, in whatever order of dimensions."
+    expected = 1
+    for size, stride in sorted(((n, st) for n, st in zip(t.shape, t.stride()) if n != 1), key=lambda x: x[1]):
+        if stride != expected:
+            return False
+        expected *= size
+    return True
+
+
+RN_EMA_STATE = 8                        # doubles in the EMA block (include/retinanet_hip.h)
+_EMA_OM = 8                             # om's index among the block's 32-bit words (byte 32)
+
+
+class WeightEMA:
+    """An exponential moving average of the fp32 weights of ``MasterSGD`` / ``MasterAdam`` / ``MasterAdamW`` -- ``--model-ema`` of
+    torchvision's detection recipes, timm's ``ModelEma``, Lightning's EMA callbacks -- to be evaluated and checkpointed in place of the
+    raw weights.  Install it as ``optimizer.weight_ema``: every ``step()`` then ends with ``update(all parameters, found_inf)``, one
+    ``rn_ema_update`` call over the masters (``p.master`` behind a 16-bit working copy, ``p.data`` otherwise; ``csrc/ema.hip``) and one
+    ``rn_ema_advance`` launch:
+
+        ema = w                              at the first update (the average is overwritten: nothing initialises it)
+        ema = ema + (w - ema) * om           afterwards, in fp32, three roundings
+        om  = float32(1 - d_t),  d_t = min(decay, (1 + t) / (warmup + t)) if warmup > 0 else decay     (t: updates so far; in double)
+
+    ``om``, the update count, ``decay`` and ``warmup`` live in a device block that the kernels read and advance: a captured step is the
+    same graph at every update, and assigning ``decay`` / ``warmup`` (between replays) is one tiny launch, no re-capture.  A step that a
+    loss scaler skips (``found_inf``) leaves the average and the count untouched and is counted in ``stats()["skipped"]``.  Because the
+    update sits inside ``optimizer.step``, accumulation micro steps do not update, and under data parallelism every rank computes the
+    same average from the same exchanged step.  The averages and the block are created by the first ``update`` -- not inside a capture --
+    and kept for good (captured steps hold their addresses).
+
+    ``swap(params)`` exchanges the training weights and the average in place, all of them at once (``rn_ema_swap``; the 16-bit working copies are refreshed
+    from the new masters), ``swapped(params)`` does so around a ``with`` block: inside it the model IS the averaged model, and
+    ``master_state_dict(model)`` is its checkpoint.  ``update`` raises while swapped.
+
+    Only parameters are averaged.  BatchNorm running statistics and other buffers are NOT: the swapped model uses the live buffers
+    (the reference trains with ``freeze_bn: true``, where they never move)."""
+
+    def __init__(self, decay: float = 0.9998, warmup: float = 0.0):
+        self._decay, self._warmup = self._check(decay, warmup)
+        self._block: Optional[Tensor] = None          # float64[RN_EMA_STATE] on the device of the first parameter (kept for good)
+        self._ema: Dict[Tensor, Tensor] = {}          # parameter -> its fp32 average (the master's / parameter's strides), in the order met
+        self._swapped = False
+        # A load_state_dict() into an object without averages waits here for the first update: {"updates", "ema": tensors by position}.
+        # Invariant: it is only ever set while _ema is empty, the k-th average CREATED by that first update takes ema[k] (k = len(_ema)
+        # at that moment, shape-checked; parameters beyond the list start from their weights), and the update drops it when it is
+        # done -- a later update never sees a stale or half-consumed list.
+        self._loaded: Optional[dict] = None
+
+    @staticmethod
+    def _check(decay, warmup):
+        decay, warmup = float(decay), float(warmup)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"WeightEMA: decay must be in [0, 1), got {decay}")
+        if not 0.0 <= warmup < float("inf"):
+            raise ValueError(f"WeightEMA: warmup must be a finite number >= 0 (0 = no warm-up), got {warmup}")
+        return decay, warmup
+
+    def __repr__(self) -> str:
+        return f"WeightEMA(decay={self._decay}, warmup={self._warmup})"
+
+    @staticmethod
+    def one_minus_decay(t: int, decay: float, warmup: float = 0.0) -> np.float32:
+        """Pure-Python restatement of the factor of update number ``t`` (``csrc/ema.hip``): in double, ``d_t = min(decay, (1 + t) /
+        (warmup + t))`` with a warm-up and ``decay`` without, then ``float32(1 - d_t)``."""
+        t, decay, warmup = float(int(t)), float(decay), float(warmup)
+        d = min(decay, (1.0 + t) / (warmup + t)) if warmup > 0.0 else decay
+        return np.float32(1.0 - d)
+
+    # -- the device block ---------------------------------------------------------------------------------------------
+    @property
+    def decay(self) -> float:
+        return self._decay
+
+    @decay.setter
+    def decay(self, value: float) -> None:
+        "A new decay: written into the device block (no re-capture needed; not inside a capture)."
+        self._rewrite(*self._check(value, self._warmup))
+
+    @property
+    def warmup(self) -> float:
+        return self._warmup
+
+    @warmup.setter
+    def warmup(self, value: float) -> None:
+        "A new warm-up constant: written into the device block (no re-capture needed; not inside a capture)."
+        self._rewrite(*self._check(self._decay, value))
+
+    def _rewrite(self, decay: float, warmup: float) -> None:
+        if self._block is not None:
+            if _is_capturing():
+                raise RuntimeError("WeightEMA: decay / warmup cannot be set inside a capture (the write would replay the values of capture time)")
+            self._write(decay, warmup, -1)
+        self._decay, self._warmup = decay, warmup
+
+    def _write(self, decay: float, warmup: float, updates: int) -> None:
+        dev = self._block.device
+        with torch.cuda.device(dev):
+            check(lib.rn_ema_set(self._block.data_ptr(), float(decay), float(warmup), int(updates), torch.cuda.current_stream(dev).cuda_stream),
+                  "rn_ema_set")
+
+    def _ensure_block(self, device: torch.device) -> None:
+        new = self._block is None
+        self._block = _device_block(self._block, RN_EMA_STATE, device,
+                                    "WeightEMA: take one step before capturing one: its device block cannot be created inside a capture",
+                                    "WeightEMA: its state lives on {have}, not {want}; use one object per device")
+        if new:
+            self._write(self._decay, self._warmup, self._loaded["updates"] if self._loaded is not None else 0)
+
+    # -- the update ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _refuse(cpu: bool) -> Exception:
+        if cpu:
+            return RuntimeError("WeightEMA has no CPU fallback: it averages the CUDA fp32 weights of MasterSGD / MasterAdam / MasterAdamW")
+        return TypeError("WeightEMA handles CUDA fp32 parameters and 16-bit parameters converted by use_16bit_conv_weights")
+
+    def _walk(self, params: Iterable[Tensor], create: bool) -> Optional[dict]:
+        "One walk over ``params``: the fp32 tensor of each, its average (created here when ``create``), its 16-bit copy, the checks."
+        rec = dict(emas=[], masters=[], p16s=[], ns=[], dt16=None, dev=None)
+        for p in params:
+            has16 = hasattr(p, "master")
+            w = p.master if has16 else p.data
+            if not w.is_cuda:
+                raise self._refuse(True)
+            if w.dtype != torch.float32:
+                raise self._refuse(False)
+            if rec["dev"] is None:
+                rec["dev"] = w.device
+            elif rec["dev"] != w.device:
+                raise RuntimeError("WeightEMA: the parameters of one call must live on one device")
+            # the kernels walk numel() consecutive elements from data_ptr(): a strided view would be read and written outside itself
+            if not _is_dense(w) or (has16 and p.data.stride() != w.stride()):
+                raise ValueError(f"WeightEMA: a parameter of shape {tuple(w.shape)} and strides {tuple(w.stride())} is not dense in memory "
+                                 "(or its 16-bit copy is laid out differently): make it contiguous first")
+            a = self._ema.get(p)
+            if a is None:
+                if not create:
+                    raise RuntimeError("WeightEMA: a parameter without an average (update() has never seen it) cannot be swapped")
+                if _is_capturing():
+                    raise RuntimeError("WeightEMA: take one step before capturing one: the averages cannot be created inside a capture")
+                a = torch.empty_like(w)                        # the master's strides
+                saved = self._loaded["ema"][len(self._ema)] if self._loaded is not None and len(self._ema) < len(self._loaded["ema"]) else None
+                if saved is not None and tuple(saved.shape) != tuple(w.shape):
+                    raise RuntimeError(f"WeightEMA: the loaded average at position {len(self._ema)} has shape {tuple(saved.shape)}, "
+                                       f"the parameter {tuple(w.shape)}")
+                a.copy_(w if saved is None else saved)          # (a parameter that joins later starts from its current value)
+                self._ema[p] = a
+            if has16:
+                if rec["dt16"] is None:
+                    rec["dt16"] = p.dtype
+                elif rec["dt16"] != p.dtype:
+                    raise RuntimeError("the 16-bit working copies of one launch must share a dtype")
+            rec["emas"].append(a.data_ptr()); rec["masters"].append(w.data_ptr()); rec["p16s"].append(p.data.data_ptr() if has16 else 0)
+            rec["ns"].append(w.numel())
+        return rec if rec["ns"] else None
+
+    @torch.no_grad()
+    def update(self, params: Iterable[Tensor], found_inf: Optional[Tensor] = None) -> int:
+        """One ``rn_ema_update`` call and one ``rn_ema_advance`` launch on the current stream over ``params``; returns the number of
+        tensors.  ``found_inf``: the loss scaler's device flag (CUDA fp32 scalar) or None; a non-zero flag skips the update on the
+        device.  A parameter met for the first time gets its average here (not inside a capture)."""
+        if self._swapped:
+            raise RuntimeError("WeightEMA: update() while swapped would average the average: swap back first")
+        if found_inf is not None and not (found_inf.is_cuda and found_inf.dtype == torch.float32 and found_inf.numel() == 1):
+            raise TypeError("found_inf must be a CUDA fp32 scalar (torch.amp.GradScaler)")
+        r = self._walk(params, create=True)
+        if r is None:
+            return 0
+        self._ensure_block(r["dev"])
+        self._loaded = None
+        n = len(r["ns"])
+        found = found_inf.data_ptr() if found_inf is not None else None
+        with torch.cuda.device(self._block.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib.rn_ema_update(_ptrs(r["emas"]), _ptrs(r["masters"]), (C.c_int64 * n)(*r["ns"]), n, self._block.data_ptr(), found, stream),
+                  "rn_ema_update")
+            check(lib.rn_ema_advance(self._block.data_ptr(), found, stream), "rn_ema_advance")
+        return n
+
+    # -- the swap -----------------------------------------------------------------------------------------------------
+    @property
+    def is_swapped(self) -> bool:
+        "Whether the parameters currently hold the average (and this object the training weights)."
+        return self._swapped
+
+    @property
+    def ready(self) -> bool:
+        "Whether an update has created the averages (there is something to swap)."
+        return bool(self._ema)
+
+    def parameters(self) -> List[Tensor]:
+        "The averaged parameters, in the order ``update`` met them."
+        return list(self._ema)
+
+    def average_of(self, p: Tensor) -> Tensor:
+        "The fp32 average of parameter ``p`` (the tensor itself, not a copy; while swapped it holds the training weights)."
+        a = self._ema.get(p)
+        if a is None:
+            raise KeyError("WeightEMA: this parameter has no average (update() has never seen it)")
+        return a
+
+    def preallocate(self, p: Tensor, storage: Tensor) -> None:
+        """Keep the average of ``p`` in ``storage`` -- a CUDA fp32 tensor of the master's shape and strides, 16-byte aligned -- instead of
+        allocating one (averages carved from one buffer, say).  Before ``p``'s first update only; the first update overwrites it."""
+        w = p.master if hasattr(p, "master") else p.data
+        if p in self._ema:
+            raise RuntimeError("WeightEMA: this parameter already has its average")
+        if self._loaded is not None:
+            raise RuntimeError("WeightEMA: a loaded state is waiting for the first update, which hands it out by position")
+        if not (storage.is_cuda and storage.dtype == torch.float32 and storage.shape == w.shape and storage.stride() == w.stride()
+                and storage.device == w.device and storage.data_ptr() % 16 == 0):
+            raise ValueError("WeightEMA: the storage of an average is a 16-byte aligned CUDA fp32 tensor of the master's shape, strides and device")
+        self._ema[p] = storage
+
+    @torch.no_grad()
+    def swap(self, params: Optional[Iterable[Tensor]] = None) -> None:
+        """Exchange the fp32 weights of every averaged parameter with their averages, in place, and refresh the 16-bit working copies
+        from the new weights: one ``rn_ema_swap`` call.  A second call undoes the first bit for bit.  ``params`` (default: the averaged
+        parameters) names whose weights the caller expects to change -- a model's parameters, say --: it must be exactly the averaged
+        set, in any order; a subset is refused, since ``is_swapped`` is one flag for all of them."""
+        if _is_capturing():
+            raise RuntimeError("WeightEMA: swap() is not part of a step: it cannot be captured")
+        params = self.parameters() if params is None else list(params)
+        if not self._ema or not params:
+            raise RuntimeError("WeightEMA: nothing to swap (the averages are created by the first update)")
+        r = self._walk(params, create=False)                 # (raises for a parameter without an average)
+        if len({id(p) for p in params}) != len(params) or len(params) != len(self._ema):
+            raise RuntimeError(f"WeightEMA: swap() exchanges all {len(self._ema)} averaged parameters at once, got {len(params)} "
+                               "(a subset would leave is_swapped meaningless)")
+        n = len(r["ns"])
+        with torch.cuda.device(r["dev"]):
+            check(lib.rn_ema_swap(_ptrs(r["emas"]), _ptrs(r["masters"]), _ptrs(r["p16s"]), (C.c_int64 * n)(*r["ns"]), n, _dt16(r["dt16"]),
+                                  torch.cuda.current_stream().cuda_stream), "rn_ema_swap")
+        self._swapped = not self._swapped
+        note_raw_write()                   # masters, 16-bit copies and BN affine parameters changed without a _version bump
+        from . import biasact
+        biasact.invalidate_dgrad_weights()
+
+    @contextlib.contextmanager
+    def swapped(self, params: Optional[Iterable[Tensor]] = None):
+        "``with ema.swapped(params):`` -- the parameters hold the average inside the block and the training weights again after it."
+        params = self.parameters() if params is None else list(params)
+        self.swap(params)
+        try:
+            yield self
+        finally:
+            self.swap(params)
+
+    # -- reading it back ----------------------------------------------------------------------------------------------
+    @property
+    def updates(self) -> int:
+        "Updates applied so far, skipped steps not counted (reads the block: synchronises)."
+        if self._block is None:
+            return int(self._loaded["updates"]) if self._loaded is not None else 0
+        return int(self._block.view(torch.int64)[2])
+
+    def stats(self) -> Dict[str, int]:
+        "Updates applied and steps skipped by found_inf (reads the block: synchronises)."
+        if self._block is None:
+            return {"updates": self.updates, "skipped": 0}
+        updates, skipped = self._block.view(torch.int64)[2:4].tolist()
+        return {"updates": updates, "skipped": skipped}
+
+    @property
+    def next_factor(self) -> Tensor:
+        "``om`` of the next update (device fp32 scalar, a view into the block)."
+        if self._block is None:
+            raise RuntimeError("WeightEMA: no update has been made yet (the device block is created by the first one)")
+        return self._block.view(torch.float32)[_EMA_OM]
+
+    def state_dict(self) -> dict:
+        "The averages by position (the order ``update`` met the parameters), ``decay``, ``warmup`` and ``updates`` (synchronises)."
+        if self._swapped:
+            raise RuntimeError("WeightEMA: state_dict() while swapped would save the training weights as the average: swap back first")
+        if self._loaded is not None and not self._ema:
+            return {"decay": self._decay, "warmup": self._warmup, "updates": self.updates, "ema": [t.clone() for t in self._loaded["ema"]]}
+        return {"decay": self._decay, "warmup": self._warmup, "updates": self.updates, "ema": [a.detach().clone() for a in self._ema.values()]}
+
+    @torch.no_grad()
+    def load_state_dict(self, state: dict) -> None:
+        """Restore ``decay``, ``warmup``, ``updates`` (through ``rn_ema_set``) and the averages.  Into an object that has averages they
+        are copied by position; into a fresh one they wait for the first ``update``, which hands them to the parameters in its order."""
+        if self._swapped:
+            raise RuntimeError("WeightEMA: load_state_dict() while swapped: swap back first")
+        if _is_capturing():
+            raise RuntimeError("WeightEMA: load_state_dict() cannot be captured")
+        decay, warmup = self._check(state["decay"], state["warmup"])
+        updates, saved = int(state["updates"]), list(state["ema"])
+        if updates < 0:
+            raise ValueError(f"WeightEMA: updates must be >= 0, got {updates}")
+        if self._ema:
+            if len(saved) != len(self._ema):
+                raise RuntimeError(f"WeightEMA: the state holds {len(saved)} averages, this object {len(self._ema)}")
+            for a, t in zip(self._ema.values(), saved):
+                if tuple(a.shape) != tuple(t.shape):
+                    raise RuntimeError(f"WeightEMA: a loaded average has shape {tuple(t.shape)}, the parameter {tuple(a.shape)}")
+            for a, t in zip(self._ema.values(), saved):
+                a.copy_(t)
+        else:
+            self._loaded = {"updates": updates, "ema": [t.detach().clone() for t in saved]}
+        self._decay, self._warmup = decay, warmup
+        if self._block is not None:
+            self._write(decay, warmup, updates)
+
+
 def _amp_scalars(opt):
     "``grad_scale`` / ``found_inf`` as torch.amp.GradScaler.step sets them around the call (or None, None)."
     scale, found = getattr(opt, "grad_scale", None), getattr(opt, "found_inf", None)
@@ -464,6 +776,9 @@ class _MasterOptimizer(torch.optim.Optimizer):
     _rn_master_weights = True
     # step() clips by global norm when `grad_clip` holds an optim.GradClip (constructor: max_grad_norm=...)
     _rn_grad_clip = True
+    # step() ends with the update of `weight_ema` when that holds an optim.WeightEMA (skipped with the step on found_inf)
+    _rn_weight_ema = True
+    weight_ema = None
     _handles = "CUDA fp32 parameters and 16-bit parameters converted by use_16bit_conv_weights"
 
     @torch.no_grad()
@@ -483,6 +798,11 @@ class _MasterOptimizer(torch.optim.Optimizer):
         for r in recs:
             with torch.cuda.device(r["dev"]):
                 self._launch(r, scale.data_ptr() if scale is not None else None, found.data_ptr() if found is not None else None, coef)
+        ema = getattr(self, "weight_ema", None)
+        if ema is not None and recs:
+            if not isinstance(ema, WeightEMA):
+                raise TypeError(f"weight_ema must be an optim.WeightEMA, not {type(ema).__name__}")
+            ema.update((p for group in self.param_groups for p in group["params"]), found)
         from . import biasact
         biasact.invalidate_dgrad_weights()           # (the kernel wrote the parameters through raw pointers: no version counter moved)
         return loss
