@@ -1,7 +1,22 @@
-"""Conv epilogues for the head: ``bias_act`` (bias + ReLU + optional position mask, one HIP launch each
-way) and the packed level canvas that lets the shared head towers run ONE convolution per layer over
-all five pyramid levels (reference: ``retinanet/layers.py:143-171``, ``:213-241`` -- four 3x3 conv +
-ReLU pairs per tower, applied level by level).
+"""The 3x3 convolutions this library runs on its own kernels (``csrc/conv.hip``, ``csrc/narrow3x3.hip``, ``csrc/wgrad3x3.hip``),
+host side, and what goes with them.  In file order:
+
+* ``bias_act``: bias + ReLU + optional position mask behind a MIOpen conv, one launch each way.
+* ``Canvas``, ``pack_levels`` / ``unpack_levels``: the five pyramid levels packed into one zero-bordered sheet, so that the shared head
+  towers run ONE convolution per layer (reference: ``retinanet/layers.py:143-171``, ``:213-241`` -- four 3x3 conv + ReLU pairs per
+  tower, applied level by level).
+* ``tower_conv`` / ``tower_conv_pair``: a tower layer (both towers' layers in one launch) on the canvas, bias + ReLU + gap mask in the
+  epilogue; ``TowerLink`` lets a layer's ReLU backward and bias gradient ride in the data-gradient kernel of the layer above.
+* ``dgrad_weights`` and its table: the flipped weights of every 3x3 data gradient of a step in one launch.
+* ``cls_output_conv`` / ``box_output_conv``: the two output convs from the canvas straight to the dense per-level tensors the loss and
+  detection kernels read, gradients gathered back from them (level modes).
+* ``dense_conv_group``: the FPN's three 256 -> 256 output convs as one launch each way.
+* the backbone's 3x3 / stride-1 convs: ``conv3x3_mfma_bwd`` (256 channels, dense kernels), ``conv3x3_dgrad_fwd`` (64 / 128 / 512
+  channels: narrow, band and K-split forward kernels, the data gradient issued as a forward product, the weight gradient on the
+  narrow kernel) and the inference-time ``conv3x3_dense_bias_act``.
+
+Every path has a module-level switch (read here at call time: ``bench.py --set biasact.NAME=value``, tests, ``tools/``) and a MIOpen
+fallback for operands outside its kernel's range.
 
 Why a canvas: MIOpen runs the 3x3/256-channel tower conv of the R50 config at 657 TFLOP/s on P3 but at
 170 / 60 / 18 TFLOP/s on P5 / P6 / P7 (tiny grids), and every level costs its own bias-add, ReLU and
@@ -12,7 +27,6 @@ padding 1 never mixes levels as long as the gaps hold zeros, which the epilogue'
 after every layer.
 """
 import ctypes as C
-import os
 import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -21,12 +35,12 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor
 
+from ._launch import as_cl, cl, int_array as _int_array, ptr_array as _ptr_array, scratch, stream_on, zero_page as _zero_page
 from ._lib import RN_BF16, RN_F16, RN_F32, check, lib
 from .ops import _timed          # event pairs around the MFMA conv launches when ops.enable_timing(True) (bench.py)
 
 _DT = {torch.float32: RN_F32, torch.bfloat16: RN_BF16, torch.float16: RN_F16}
 H16 = (torch.bfloat16, torch.float16)          # the element types of the MFMA conv kernels (v_mfma_*_bf16 / _f16: same rate, same kernels)
-_WS: Dict[tuple, Tensor] = {}
 PAIR_SHEETS = True     # two images per canvas sheet (Canvas.of) when that takes fewer positions
 MFMA_FLOP: Dict[str, float] = {}      # USEFUL flop per call of every timed MFMA launch (bench.py: achieved TFLOP/s of the own conv kernels)
 _REAL_PER_SHEET: Dict[tuple, int] = {}  # (Hp, Wp) of a canvas sheet -> feature positions on it (gaps / borders are not useful work)
@@ -45,20 +59,12 @@ def _mfma_call(tag: str, dev: torch.device, flop: float, status_thunk, what: str
 
 
 def _workspace(dev: torch.device, stream: int, channels: int):
-    need = lib.rn_bn_workspace_bytes(channels)
-    key = (dev.index, stream)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _WS[key] = torch.empty((max(need, lib.rn_bn_workspace_bytes(1024)),), dtype=torch.uint8, device=dev)
+    ws = scratch("bias_act", dev, stream, lib.rn_bn_workspace_bytes(channels), floor=lib.rn_bn_workspace_bytes(1024))
     return ws.data_ptr(), ws.numel()
 
 
-def _cl(t: Tensor) -> bool:
-    return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
-
-
 def fusable(x: Tensor, bias: Optional[Tensor]) -> bool:
-    return (x.is_cuda and x.dtype in _DT and _cl(x) and x.shape[1] % 8 == 0 and x.numel() > 0 and bias is not None
+    return (x.is_cuda and x.dtype in _DT and cl(x) and x.shape[1] % 8 == 0 and x.numel() > 0 and bias is not None
             and bias.dtype == torch.float32)
 
 
@@ -67,9 +73,7 @@ class _BiasAct(torch.autograd.Function):
     def forward(ctx, x, bias, mask, relu):
         N, Cc, H, W = x.shape
         dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = stream_on(dev)
         y = torch.empty_like(x)
         check(lib.rn_bias_act_forward(x.data_ptr(), bias.data_ptr(), mask.data_ptr() if mask is not None else 0, y.data_ptr(),
                                       _DT[x.dtype], N * H * W, Cc, H * W, int(relu), stream), "rn_bias_act_forward")
@@ -82,11 +86,8 @@ class _BiasAct(torch.autograd.Function):
         y, mask = ctx.saved_tensors
         relu, M, Cc, HW, dt = ctx.cfg
         dev = dy.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        if dy.dtype != dt or not _cl(dy):
-            dy = dy.to(dt).contiguous(memory_format=torch.channels_last)
+        stream = stream_on(dev)
+        dy = as_cl(dy, dt)
         need_dx = relu or mask is not None
         dx = torch.empty_like(dy) if need_dx else dy
         dbias = torch.empty((Cc,), dtype=torch.float32, device=dev)
@@ -97,7 +98,6 @@ class _BiasAct(torch.autograd.Function):
         return dx, dbias, None, None
 
 
-_WG_WS: Dict[tuple, Tensor] = {}
 MFMA_WGRAD = True      # weight gradient of the canvas convs on the MFMA kernel (False: MIOpen)
 
 
@@ -111,11 +111,7 @@ def _canvas_wgrad(gs, xs, ws, Wp: int, stream: int):
     N, _, Hp, _ = x0.shape
     M = N * Hp * Wp
     P = len(gs)
-    need = lib.rn_conv3x3_wgrad_workspace_bytes(P, M)
-    key = (dev.index, stream)
-    wsb = _WG_WS.get(key)
-    if wsb is None or wsb.numel() < need:
-        wsb = _WG_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
+    wsb = scratch("wgrad", dev, stream, lib.rn_conv3x3_wgrad_workspace_bytes(P, M))
     dws = [torch.empty((256, 256, 3, 3), dtype=x0.dtype, device=dev, memory_format=torch.channels_last) for _ in range(P)]
     _mfma_call(f"mfma_tower_wgrad_x{P}", dev, P * 2.0 * _real_positions(N, Hp, Wp) * 256 * 2304,
                lambda: lib.rn_conv3x3_canvas_wgrad_batched(_ptr_array(gs), _ptr_array(xs), _ptr_array(dws), P, _DT[x0.dtype], M, Wp, 256, 256,
@@ -134,11 +130,8 @@ class _TowerConv(torch.autograd.Function):
         N, Cin, Hp, Wp = x.shape
         Cout = w.shape[0]
         dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        if not _cl(w):
-            w = w.contiguous(memory_format=torch.channels_last)
+        stream = stream_on(dev)
+        w = as_cl(w)
         y = torch.empty((N, Cout, Hp, Wp), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
         _mfma_call("mfma_tower_fwd_x1", dev, 2.0 * _real_positions(N, Hp, Wp) * Cout * 9 * Cin,
                    lambda: lib.rn_conv3x3_canvas(x.data_ptr(), w.data_ptr(), bias.data_ptr(), mask.data_ptr(), y.data_ptr(), _DT[x.dtype],
@@ -152,11 +145,8 @@ class _TowerConv(torch.autograd.Function):
         N, Cin, Hp, Wp = x.shape
         Cout = w.shape[0]
         dev = dy.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        if dy.dtype != x.dtype or not _cl(dy):
-            dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        stream = stream_on(dev)
+        dy = as_cl(dy, x.dtype)
         M = N * Hp * Wp
         g = torch.empty_like(dy)                                   # gradient at the conv output: ReLU + canvas mask
         dbias = torch.empty((Cout,), dtype=torch.float32, device=dev)
@@ -181,10 +171,6 @@ class _TowerConv(torch.autograd.Function):
         return dx, dw, dbias, None
 
 
-def _ptr_array(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None else 0 for t in ts])
-
-
 TOWER_SUM2 = True        # first tower layer: the shared input's gradient as ONE two-source data-gradient launch (rn_conv3x3_canvas_sum2)
 
 
@@ -205,7 +191,6 @@ class TowerLink:
         self.half = [None, None]
 
 
-_CS_WS: Dict[tuple, Tensor] = {}
 FUSE_TOWER_RELU_BWD = True
 BOX_OUTPUT_WGRAD_MFMA = True   # ... and its weight gradient on the narrow gathering kernel
 BOX_OUTPUT_WGRAD_NARROW = True  # ... or (round 5, preferred) on csrc/wgrad3x3.hip over the 64-channel canvas gradient
@@ -221,11 +206,9 @@ class _TowerConvPair(torch.autograd.Function):
         N, Cin, Hp, Wp = x0.shape
         Cout = w0.shape[0]
         dev = x0.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        w0 = w0 if _cl(w0) else w0.contiguous(memory_format=torch.channels_last)
-        w1 = w1 if _cl(w1) else w1.contiguous(memory_format=torch.channels_last)
+        stream = stream_on(dev)
+        w0 = as_cl(w0)
+        w1 = as_cl(w1)
         ys = [torch.empty((N, Cout, Hp, Wp), dtype=x0.dtype, device=dev, memory_format=torch.channels_last) for _ in range(2)]
         rms = None
         if link is not None and FUSE_TOWER_RELU_BWD and any(ctx.needs_input_grad[:6]):
@@ -247,25 +230,22 @@ class _TowerConvPair(torch.autograd.Function):
         N, Cin, Hp, Wp = x0.shape
         Cout = w0.shape[0]
         dev = x0.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = stream_on(dev)
         M = N * Hp * Wp
         link, prev = ctx.link, ctx.prev
         gs, dbs = [], []
         if (link is not None and link.ptrs is not None
                 and link.ptrs == (dy0.data_ptr(), dy0._version, dy1.data_ptr(), dy1._version)
-                and dy0.dtype == x0.dtype and _cl(dy0) and _cl(dy1)):
+                and dy0.dtype == x0.dtype and cl(dy0) and cl(dy1)):
             gs, dbs = [dy0, dy1], list(link.dbias)            # the layer above already applied this layer's ReLU mask
         else:
             wp, wn = _workspace(dev, stream, Cout)
             for i, (dy, y) in enumerate(((dy0, y0), (dy1, y1))):
                 h = link.half[i] if link is not None else None
-                if h is not None and h[:2] == (dy.data_ptr(), dy._version) and dy.dtype == x0.dtype and _cl(dy):
+                if h is not None and h[:2] == (dy.data_ptr(), dy._version) and dy.dtype == x0.dtype and cl(dy):
                     gs.append(dy); dbs.append(h[2])              # the output conv above already applied this layer's ReLU mask
                     continue
-                if dy.dtype != x0.dtype or not _cl(dy):
-                    dy = dy.to(x0.dtype).contiguous(memory_format=torch.channels_last)
+                dy = as_cl(dy, x0.dtype)
                 g = torch.empty_like(dy)
                 db = torch.empty((Cout,), dtype=torch.float32, device=dev)
                 check(lib.rn_bias_act_backward(dy.data_ptr(), y.data_ptr(), mask.data_ptr(), g.data_ptr(), db.data_ptr(), _DT[x0.dtype],
@@ -287,11 +267,7 @@ class _TowerConvPair(torch.autograd.Function):
                            lambda: lib.rn_conv3x3_canvas_sum2(gs[0].data_ptr(), gs[1].data_ptr(), wcat.data_ptr(), mask.data_ptr(), dxs[0].data_ptr(),
                                                               _DT[x0.dtype], M, Hp * Wp, Wp, Cout, Cin, stream), "rn_conv3x3_canvas_sum2")
             elif prev is not None and prev.relu_masks is not None and Cin == Cout:
-                need = lib.rn_conv3x3_colsum_workspace_bytes(2, M, Cin)
-                key = (dev.index, stream)
-                wsb = _CS_WS.get(key)
-                if wsb is None or wsb.numel() < need:
-                    wsb = _CS_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
+                wsb = scratch("colsum", dev, stream, lib.rn_conv3x3_colsum_workspace_bytes(2, M, Cin))
                 dbp = [torch.empty((Cin,), dtype=torch.float32, device=dev) for _ in range(2)]
                 _mfma_call("mfma_tower_dgrad_x2", dev, 2 * 2.0 * _real_positions(N, Hp, Wp) * Cout * 9 * Cin,
                            lambda: lib.rn_conv3x3_canvas_dgrad_relu_batched(_ptr_array(gs), _ptr_array(wts), _ptr_array(prev.relu_masks), mask.data_ptr(),
@@ -318,11 +294,16 @@ def tower_conv_pair(x0: Tensor, x1: Tensor, w0: Tensor, w1: Tensor, b0: Tensor, 
     return _TowerConvPair.apply(x0, x1, w0.to(x0.dtype), w1.to(x0.dtype), b0, b1, mask, prev, link)
 
 
+def _plain3x3(conv) -> bool:
+    "3x3 / stride 1 / pad 1 / dilation 1 / groups 1: the only geometry the kernels of this file take."
+    return (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+            and conv.groups == 1)
+
+
 def tower_conv_fusable(x: Tensor, conv) -> bool:
     "The MFMA canvas conv covers bf16, 3x3 / stride 1 / pad 1, Cin % 64 == 0 and Cout % 256 == 0 (head towers: 256 -> 256)."
     # (its data gradient runs on the same kernel when Cin % 256 == 0 as well, else on MIOpen)
-    return (x.is_cuda and x.dtype in H16 and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and
-            conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None and
+    return (x.is_cuda and x.dtype in H16 and _plain3x3(conv) and conv.bias is not None and
             conv.in_channels % 64 == 0 and conv.out_channels % 256 == 0)
 
 
@@ -425,18 +406,15 @@ class Canvas:
 def _pack_native(cv: "Canvas", levels: Sequence[Tensor], canvas_t: Tensor, n_images: int, to_canvas: bool) -> bool:
     """``rn_canvas_pack``: all levels <-> the canvas sheets in one launch (False: shapes / dtypes the kernel does not take)."""
     x = canvas_t
-    if not (x.is_cuda and x.dtype in H16 and x.dim() == 4 and _cl(x) and x.shape[1] % 2 == 0
+    if not (x.is_cuda and x.dtype in H16 and x.dim() == 4 and cl(x) and x.shape[1] % 2 == 0
             and len(levels) <= 6 and x.shape[0] * cv.H * cv.W < (1 << 22)):
         return False
     for t in levels:
-        if not (t.is_cuda and t.dtype == x.dtype and t.dim() == 4 and t.shape[1] == x.shape[1] and (_cl(t) or t.shape[1] == 1)
+        if not (t.is_cuda and t.dtype == x.dtype and t.dim() == 4 and t.shape[1] == x.shape[1] and (cl(t) or t.shape[1] == 1)
                 and t.data_ptr() % 16 == 0):
             return False
-    dev = x.device
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
     check(lib.rn_canvas_pack(_ptr_array(levels), _layout(cv, n_images), x.data_ptr(), _DT[x.dtype], x.shape[0], cv.H, cv.W, x.shape[1],
-                             1 if to_canvas else 0, torch.cuda.current_stream().cuda_stream), "rn_canvas_pack")
+                             1 if to_canvas else 0, stream_on(x.device)), "rn_canvas_pack")
     return True
 
 
@@ -465,7 +443,7 @@ def _gather_levels(cv: "Canvas", x: Tensor, n_images: int) -> List[Tensor]:
     "The per-level tensors [n_images, C, h, w] (channels-last) cut out of canvas sheets."
     S = cv.slots
     outs = [torch.empty((n_images, x.shape[1], h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last) for h, w in cv.shapes]
-    if _pack_native(cv, outs, x if _cl(x) else x.contiguous(memory_format=torch.channels_last), n_images, False):
+    if _pack_native(cv, outs, as_cl(x), n_images, False):
         return outs
     if S == 1:
         return [x[:, :, r:r + h, c:c + w].contiguous(memory_format=torch.channels_last) for (r, c), (h, w) in zip(cv.origin, cv.shapes)]
@@ -496,7 +474,7 @@ def _scatter_levels(cv: "Canvas", grads, shape, dt, dev, n_images: int) -> Tenso
     S = cv.slots
     g = torch.empty(shape, dtype=dt, device=dev, memory_format=torch.channels_last)
     if all(gl is not None for gl in grads):
-        lv = [gl if (gl.dtype == dt and _cl(gl)) else gl.to(dt).contiguous(memory_format=torch.channels_last) for gl in grads]
+        lv = [as_cl(gl, dt) for gl in grads]
         if _pack_native(cv, lv, g, n_images, True):
             return g
     g.fill_(0)
@@ -520,16 +498,6 @@ def unpack_levels(canvas: Canvas, x: Tensor, n_images: Optional[int] = None) -> 
 
 # ---------------------------------------------------------------------------------------------------
 # The class-output conv (retinanet/layers.py:163-167) on the canvas, dense per-level logits out
-_ZEROS: Dict[int, Tensor] = {}
-
-
-def _zero_page(dev: torch.device) -> Tensor:
-    z = _ZEROS.get(dev.index)
-    if z is None:
-        z = _ZEROS[dev.index] = torch.empty((256,), dtype=torch.uint8, device=dev).fill_(0)
-    return z
-
-
 class RnCanvasLayout(C.Structure):
     _fields_ = [("map", C.c_void_p), ("slots", C.c_int32), ("n_images", C.c_int32), ("T", C.c_int32), ("hw", C.c_int32 * 6)]
 
@@ -573,7 +541,7 @@ def invalidate_dgrad_weights() -> None:
 
 def _dw_eligible(w: Tensor) -> bool:
     return (DGRAD_WEIGHT_TABLE and w.is_cuda and w.dtype in H16 and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)
-            and _cl(w) and w.shape[0] % 32 == 0 and w.shape[1] % 32 == 0)
+            and cl(w) and w.shape[0] % 32 == 0 and w.shape[1] % 32 == 0)
 
 
 def refresh_dgrad_weights(device=None) -> int:
@@ -591,12 +559,10 @@ def refresh_dgrad_weights(device=None) -> int:
         return 0
     dev = live[0][0].device
     live = [(w, e) for w, e in live if w.device == dev]
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
     n = len(live)
     check(lib.rn_conv3x3_dgrad_weight_many(_ptr_array([w for w, _ in live]), _ptr_array([e.flipped for _, e in live]),
                                            _int_array([int(w.shape[0]) for w, _ in live]), _int_array([int(w.shape[1]) for w, _ in live]), n,
-                                           torch.cuda.current_stream(dev).cuda_stream), "rn_conv3x3_dgrad_weight_many")
+                                           stream_on(dev)), "rn_conv3x3_dgrad_weight_many")
     for w, e in live:
         e.version, e.epoch = w._version, _DW_EPOCH
     return n
@@ -613,7 +579,7 @@ def dgrad_weights(ws: Sequence[Tensor], stream: int) -> List[Tensor]:
     todo = [i for i, t in enumerate(out) if t is None]
     if todo:
         Cout, Cin = int(ws[0].shape[0]), int(ws[0].shape[1])
-        srcs = [ws[i] if _cl(ws[i]) else ws[i].contiguous(memory_format=torch.channels_last) for i in todo]
+        srcs = [as_cl(ws[i]) for i in todo]
         dsts = [torch.empty((Cin, Cout, 3, 3), dtype=ws[i].dtype, device=ws[i].device, memory_format=torch.channels_last) for i in todo]
         check(lib.rn_conv3x3_dgrad_weight_batched(_ptr_array(srcs), _ptr_array(dsts), len(todo), Cout, Cin, stream), "rn_conv3x3_dgrad_weight_batched")
         for i, d in zip(todo, dsts):
@@ -632,7 +598,7 @@ def _dgrad_weight(w: Tensor) -> Tensor:
     e .. e+7 carry channels Cout-8 .. Cout-1 with zero weight on the repeated ones; zeros up to Kpad."""
     Cout, Cin = w.shape[0], w.shape[1]
     Kpad = (Cout + 63) // 64 * 64
-    if w.is_cuda and w.dtype in H16 and _cl(w) and Cout >= 8:
+    if w.is_cuda and w.dtype in H16 and cl(w) and Cout >= 8:
         # one launch (the torch form below is a flip, a fill and two or three strided copies: ~35 us of 5-us kernels per conv)
         out = torch.empty((Cin, Kpad, 3, 3), dtype=w.dtype, device=w.device, memory_format=torch.channels_last)
         check(lib.rn_conv3x3_levels_dgrad_weight(w.data_ptr(), out.data_ptr(), Cout, Cin, Kpad, torch.cuda.current_stream(w.device).cuda_stream),
@@ -648,6 +614,62 @@ def _dgrad_weight(w: Tensor) -> Tensor:
     return out
 
 
+# The two output convs in level mode (``csrc/conv.hip``): the canvas in, dense per-level ``[N, h*w*A, last]`` tensors out, and both
+# gradients gathered back from the dense per-level gradients.  What the class and the box conv share is written once here.
+def _levels_flop(cv: "Canvas", N: int, Cout: int, Cin: int) -> float:
+    "Flop on the positions and channels that exist (the kernels also walk canvas gaps and pad Cout)."
+    return 2.0 * N * sum(h * wd for h, wd in cv.shapes) * Cout * 9 * Cin
+
+
+def _levels_forward(tag: str, x: Tensor, w: Tensor, bias: Optional[Tensor], cv: "Canvas", N: int, last: int) -> List[Tensor]:
+    "``rn_conv3x3_canvas_to_levels``: conv(x) + bias for canvas sheets ``x`` -> per level ``[N, h*w*(Cout // last), last]``."
+    sheets, Cin, Hp, Wp = x.shape
+    Cout = w.shape[0]
+    dev = x.device
+    stream = stream_on(dev)
+    w = as_cl(w)
+    ys = [torch.empty((N, h * wd * (Cout // last), last), dtype=x.dtype, device=dev) for h, wd in cv.shapes]
+    _mfma_call(tag, dev, _levels_flop(cv, N, Cout, Cin),
+               lambda: lib.rn_conv3x3_canvas_to_levels(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else 0,
+                                                       _layout(cv, N), _ptr_array(ys), _DT[x.dtype], sheets, Hp, Wp, Cin, Cout,
+                                                       _zero_page(dev).data_ptr(), stream), "rn_conv3x3_canvas_to_levels")
+    return ys
+
+
+def _levels_grads(dys, x: Tensor, Cout: int, cv: "Canvas", N: int) -> List[Tensor]:
+    "The gradients autograd hands an output conv as dense ``[N, h*w*Cout]`` tensors of the activation dtype (None = zeros)."
+    gs = []
+    for dy, (h, wd) in zip(dys, cv.shapes):
+        if dy is None:
+            dy = torch.empty((N, h * wd * Cout), dtype=x.dtype, device=x.device).fill_(0)
+        gs.append(dy.to(x.dtype).contiguous())
+    return gs
+
+
+def _levels_backward_data(tag: str, relu_link, gs, x: Tensor, w: Tensor, cv: "Canvas", N: int, stream: int) -> Tensor:
+    sheets, Cin, Hp, Wp = x.shape
+    Cout = w.shape[0]
+    dx = torch.empty_like(x)
+    wt = _dgrad_weight(w)
+    _mfma_call(tag, x.device, _levels_flop(cv, N, Cout, Cin),
+               lambda: _levels_dgrad(relu_link, gs, _layout(cv, N), Cout, wt, cv, dx, x, sheets, Hp, Wp, Cin, stream),
+               "rn_conv3x3_levels_to_canvas")
+    return dx
+
+
+def _levels_backward_weight(tag: str, gs, x: Tensor, Cout: int, cv: "Canvas", N: int, stream: int) -> Tensor:
+    "``rn_conv3x3_levels_wgrad``: the gathering position-contraction kernel (its narrow variant when Cout <= 64); Cin == 256."
+    sheets, Cin, Hp, Wp = x.shape
+    dev = x.device
+    wsb = scratch("wgrad", dev, stream, lib.rn_conv3x3_wgrad_workspace_bytes((Cout + 255) // 256, sheets * Hp * Wp))
+    dw = torch.empty((Cout, Cin, 3, 3), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
+    _mfma_call(tag, dev, _levels_flop(cv, N, Cout, Cin),
+               lambda: lib.rn_conv3x3_levels_wgrad(_ptr_array(gs), _layout(cv, N), Cout, x.data_ptr(), dw.data_ptr(), _DT[x.dtype], sheets, Hp, Wp,
+                                                   Cin, _zero_page(dev).data_ptr(), wsb.data_ptr(), wsb.numel(), stream),
+               "rn_conv3x3_levels_wgrad")
+    return dw
+
+
 class _ClsOutputConv(torch.autograd.Function):
     """``class_subnet_output`` on the zero-bordered canvas: the result is written per pyramid level as the dense
     ``[N, h*w*A, K]`` logits the loss / detection kernels stream (exactly Cout = A*K channels: no dead classes, no unpack
@@ -656,22 +678,9 @@ class _ClsOutputConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, canvas, num_classes, n_images, relu_link=None):
         ctx.relu_link = relu_link
-        sheets, Cin, Hp, Wp = x.shape
         N = int(n_images)
-        Cout = w.shape[0]
-        dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        if not _cl(w):
-            w = w.contiguous(memory_format=torch.channels_last)
-        ys = [torch.empty((N, h * wd * (Cout // num_classes), num_classes), dtype=x.dtype, device=dev) for h, wd in canvas.shapes]
-        # flop counted on the positions and channels that exist (the kernel also walks canvas gaps and pads Cout to 256s)
-        real = N * sum(h * wd for h, wd in canvas.shapes)
-        _mfma_call("mfma_cls_output_fwd", dev, 2.0 * real * Cout * 9 * Cin,
-                   lambda: lib.rn_conv3x3_canvas_to_levels(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                           _layout(canvas, N), _ptr_array(ys), _DT[x.dtype], sheets, Hp, Wp, Cin, Cout,
-                                                           _zero_page(dev).data_ptr(), stream), "rn_conv3x3_canvas_to_levels")
+        w = as_cl(w)
+        ys = _levels_forward("mfma_cls_output_fwd", x, w, bias, canvas, N, num_classes)
         ctx.save_for_backward(x, w)
         ctx.canvas, ctx.has_bias, ctx.n_images = canvas, bias is not None, N
         return tuple(ys)
@@ -679,39 +688,15 @@ class _ClsOutputConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dys):
         x, w = ctx.saved_tensors
-        cv = ctx.canvas
-        sheets, Cin, Hp, Wp = x.shape
-        N = ctx.n_images
+        cv, N = ctx.canvas, ctx.n_images
         Cout = w.shape[0]
-        dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        gs = []
-        for dy, (h, wd) in zip(dys, cv.shapes):
-            if dy is None:
-                dy = torch.empty((N, h * wd * Cout), dtype=x.dtype, device=dev).fill_(0)
-            gs.append(dy.to(x.dtype).contiguous())
-        lv = _layout(cv, N)
-        real = N * sum(h * wd for h, wd in cv.shapes)
+        stream = stream_on(x.device)
+        gs = _levels_grads(dys, x, Cout, cv, N)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            wt = _dgrad_weight(w)
-            _mfma_call("mfma_cls_output_dgrad", dev, 2.0 * real * Cout * 9 * Cin,
-                       lambda: _levels_dgrad(ctx.relu_link, gs, lv, Cout, wt, cv, dx, x, sheets, Hp, Wp, Cin, stream),
-                       "rn_conv3x3_levels_to_canvas")
+            dx = _levels_backward_data("mfma_cls_output_dgrad", ctx.relu_link, gs, x, w, cv, N, stream)
         if ctx.needs_input_grad[1]:
-            need = lib.rn_conv3x3_wgrad_workspace_bytes((Cout + 255) // 256, sheets * Hp * Wp)
-            key = (dev.index, stream)
-            wsb = _WG_WS.get(key)
-            if wsb is None or wsb.numel() < need:
-                wsb = _WG_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
-            dw = torch.empty((Cout, Cin, 3, 3), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
-            _mfma_call("mfma_cls_output_wgrad", dev, 2.0 * real * Cout * 9 * Cin,
-                       lambda: lib.rn_conv3x3_levels_wgrad(_ptr_array(gs), lv, Cout, x.data_ptr(), dw.data_ptr(), _DT[x.dtype], sheets, Hp, Wp,
-                                                           Cin, _zero_page(dev).data_ptr(), wsb.data_ptr(), wsb.numel(), stream),
-                       "rn_conv3x3_levels_wgrad")
+            dw = _levels_backward_weight("mfma_cls_output_wgrad", gs, x, Cout, cv, N, stream)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = _colsum_levels(gs, Cout)
         return dx, dw, db, None, None, None, None
@@ -723,11 +708,7 @@ def _colsum_levels(gs: Sequence[Tensor], C_: int) -> Tensor:
     if gs[0].dtype not in H16 or C_ % 2 or len(gs) > 6:
         return sum(g.reshape(-1, C_).sum(0, dtype=torch.float32) for g in gs)
     stream = torch.cuda.current_stream().cuda_stream
-    need = lib.rn_colsum_rows_workspace_bytes(len(gs), C_)
-    key = (dev.index, stream, "rows")
-    wsb = _CS_WS.get(key)
-    if wsb is None or wsb.numel() < need:
-        wsb = _CS_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
+    wsb = scratch("colsum_rows", dev, stream, lib.rn_colsum_rows_workspace_bytes(len(gs), C_))
     out = torch.empty((C_,), dtype=torch.float32, device=dev)
     n = len(gs)
     check(lib.rn_colsum_rows(_ptr_array(gs), (C.c_int64 * n)(*[g.numel() // C_ for g in gs]), n, C_, _DT[gs[0].dtype], out.data_ptr(),
@@ -736,10 +717,11 @@ def _colsum_levels(gs: Sequence[Tensor], C_: int) -> Tensor:
 
 
 class _BoxOutputConv(torch.autograd.Function):
-    """``box_subnet_output`` (256 -> A*4 = 36 channels) on the canvas: MIOpen forward + unpack to the dense per-level
-    ``[N, h*w*A, 4]`` deltas; the DATA gradient gathers the per-level gradients straight from those dense tensors with the
-    MFMA level-mode kernel (``rn_conv3x3_levels_to_canvas``: 9 K-tiles per tile instead of a 36-channel MIOpen igemm, 55 vs
-    165 us); the weight gradient stays with MIOpen on the re-assembled canvas gradient."""
+    """``box_subnet_output`` (256 -> A*4 = 36 channels) on the canvas, like ``_ClsOutputConv`` with 4 as the trailing dimension:
+    forward and data gradient on the level-mode kernels (their narrow, <= 64 column variants; ``rn_conv3x3_levels_to_canvas``: 9
+    K-tiles per tile instead of a 36-channel MIOpen igemm, 55 vs 165 us).  The weight gradient runs on ``csrc/wgrad3x3.hip`` over the
+    gradient scattered into a 64-channel canvas (``BOX_OUTPUT_WGRAD_NARROW``), else on the gathering kernel
+    (``BOX_OUTPUT_WGRAD_MFMA``), else on MIOpen; with ``BOX_OUTPUT_FWD_MFMA`` off the forward is MIOpen's conv + unpack."""
 
     @staticmethod
     def forward(ctx, x, w, bias, canvas, n_images, relu_link=None):
@@ -747,21 +729,8 @@ class _BoxOutputConv(torch.autograd.Function):
         ctx.save_for_backward(x, w)
         ctx.canvas, ctx.n_images, ctx.has_bias = canvas, int(n_images), bias is not None
         N = ctx.n_images
-        sheets, Cin, Hp, Wp = x.shape
-        Cout = w.shape[0]
         if BOX_OUTPUT_FWD_MFMA and (bias is None or bias.dtype == torch.float32):
-            # the narrow (<= 64 columns) variant of the MFMA level-mode kernel writes the dense per-level deltas directly
-            dev = x.device
-            if dev.index != torch.cuda.current_device():
-                torch.cuda.set_device(dev)
-            stream = torch.cuda.current_stream().cuda_stream
-            wc = w if _cl(w) else w.contiguous(memory_format=torch.channels_last)
-            ys = [torch.empty((N, h * wd * (Cout // 4), 4), dtype=x.dtype, device=dev) for h, wd in canvas.shapes]
-            _mfma_call("mfma_box_output_fwd", dev, 2.0 * N * sum(h * wd for h, wd in canvas.shapes) * Cout * 9 * Cin,
-                       lambda: lib.rn_conv3x3_canvas_to_levels(x.data_ptr(), wc.data_ptr(), bias.data_ptr() if bias is not None else 0,
-                                                               _layout(canvas, N), _ptr_array(ys), _DT[x.dtype], sheets, Hp, Wp, Cin, Cout,
-                                                               _zero_page(dev).data_ptr(), stream), "rn_conv3x3_canvas_to_levels")
-            return tuple(ys)
+            return tuple(_levels_forward("mfma_box_output_fwd", x, w, bias, canvas, N, 4))
         y = F.conv2d(x, w, bias.to(x.dtype) if bias is not None else None, stride=1, padding=1)
         outs = _gather_levels(canvas, y, N)
         return tuple(t.permute(0, 2, 3, 1).reshape(N, -1, 4) for t in outs)        # layers.py:189-191, zero-copy
@@ -773,21 +742,16 @@ class _BoxOutputConv(torch.autograd.Function):
         sheets, Cin, Hp, Wp = x.shape
         Cout = w.shape[0]
         dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        gs = []
-        for dy, (h, wd) in zip(dys, cv.shapes):
-            if dy is None:
-                dy = torch.empty((N, h * wd * Cout), dtype=x.dtype, device=dev).fill_(0)
-            gs.append(dy.to(x.dtype).contiguous())
+        stream = stream_on(dev)
+        gs = _levels_grads(dys, x, Cout, cv, N)
+
+        def on_canvas():
+            "The per-level gradients scattered into canvas sheets [sheets, Cout, Hp, Wp]."
+            return _scatter_levels(cv, [gl.view(N, h, wd, Cout).permute(0, 3, 1, 2) for gl, (h, wd) in zip(gs, cv.shapes)],
+                                   (sheets, Cout, Hp, Wp), x.dtype, dev, N)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            wt = _dgrad_weight(w)
-            _mfma_call("mfma_box_output_dgrad", dev, 2.0 * N * sum(h * wd for h, wd in cv.shapes) * Cout * 9 * Cin,
-                       lambda: _levels_dgrad(ctx.relu_link, gs, _layout(cv, N), Cout, wt, cv, dx, x, sheets, Hp, Wp, Cin, stream),
-                       "rn_conv3x3_levels_to_canvas")
+            dx = _levels_backward_data("mfma_box_output_dgrad", ctx.relu_link, gs, x, w, cv, N, stream)
         if (ctx.needs_input_grad[1] and BOX_OUTPUT_WGRAD_NARROW and Cout <= 64 and Cin % 64 == 0 and x.dtype in H16
                 and wgrad_narrow_ok(torch.empty((64, Cin, 3, 3), dtype=x.dtype, device="meta"), (1, 1), x)):
             # Round 5: the canvas IS a zero-bordered channels-last tensor and the gradient is zero on its gaps, so the weight gradient of
@@ -795,28 +759,14 @@ class _BoxOutputConv(torch.autograd.Function):
             # taps of a 64 x 64 block of dW per team of waves: x is read once per 64 output channels instead of once per tap) on the
             # per-level gradients scattered into a 64-channel canvas (Cout = 36 padded with zero channels).  110 us against 198 for the
             # narrow gathering variant of the position-contraction kernel (which stages the 256-channel x nine times).
-            g36 = _scatter_levels(cv, [gl.view(N, h, wd, Cout).permute(0, 3, 1, 2) for gl, (h, wd) in zip(gs, cv.shapes)],
-                                  (sheets, Cout, Hp, Wp), x.dtype, dev, N)
-            g64 = F.pad(g36, (0, 0, 0, 0, 0, 64 - Cout)).contiguous(memory_format=torch.channels_last)
+            g64 = F.pad(on_canvas(), (0, 0, 0, 0, 0, 64 - Cout)).contiguous(memory_format=torch.channels_last)
             dw64 = conv3x3_wgrad_narrow(g64, x, torch.empty((64, Cin, 3, 3), dtype=x.dtype, device="meta"), tag="mfma_box_output_wgrad",
-                                        flop=2.0 * N * sum(h * wd for h, wd in cv.shapes) * Cout * 9 * Cin)
+                                        flop=_levels_flop(cv, N, Cout, Cin))
             dw = dw64[:Cout].contiguous(memory_format=torch.channels_last)
         elif ctx.needs_input_grad[1] and BOX_OUTPUT_WGRAD_MFMA and Cin == 256:
-            # the narrow (<= 64 rows) variant of the gathering MFMA weight-gradient kernel
-            need = lib.rn_conv3x3_wgrad_workspace_bytes(1, sheets * Hp * Wp)
-            key = (dev.index, stream)
-            wsb = _WG_WS.get(key)
-            if wsb is None or wsb.numel() < need:
-                wsb = _WG_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
-            dw = torch.empty((Cout, Cin, 3, 3), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
-            _mfma_call("mfma_box_output_wgrad", dev, 2.0 * N * sum(h * wd for h, wd in cv.shapes) * Cout * 9 * Cin,
-                       lambda: lib.rn_conv3x3_levels_wgrad(_ptr_array(gs), _layout(cv, N), Cout, x.data_ptr(), dw.data_ptr(), _DT[x.dtype], sheets, Hp, Wp,
-                                                           Cin, _zero_page(dev).data_ptr(), wsb.data_ptr(), wsb.numel(), stream),
-                       "rn_conv3x3_levels_wgrad")
+            dw = _levels_backward_weight("mfma_box_output_wgrad", gs, x, Cout, cv, N, stream)
         elif ctx.needs_input_grad[1]:
-            g = _scatter_levels(cv, [gl.view(N, h, wd, Cout).permute(0, 3, 1, 2) for gl, (h, wd) in zip(gs, cv.shapes)],
-                                (sheets, Cout, Hp, Wp), x.dtype, dev, N)
-            dw = torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])[1]
+            dw = torch.ops.aten.convolution_backward(on_canvas(), x, w, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])[1]
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = _colsum_levels(gs, Cout)
         return dx, dw, db, None, None, None
@@ -835,11 +785,7 @@ def _levels_dgrad(relu_link, gs, lv, Cout, wt, cv, dx, x, sheets, Hp, Wp, Cin, s
     if link is None or link.relu_masks is None or not FUSE_TOWER_RELU_BWD:
         return lib.rn_conv3x3_levels_to_canvas(_ptr_array(gs), lv, Cout, wt.data_ptr(), cv.mask.data_ptr(), dx.data_ptr(), _DT[x.dtype], sheets,
                                                Hp, Wp, wt.shape[1], Cin, _zero_page(dev).data_ptr(), stream)
-    need = lib.rn_conv3x3_colsum_workspace_bytes(1, sheets * Hp * Wp, Cin)
-    key = (dev.index, stream, "lv")
-    wsb = _CS_WS.get(key)
-    if wsb is None or wsb.numel() < need:
-        wsb = _CS_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
+    wsb = scratch("colsum_lv", dev, stream, lib.rn_conv3x3_colsum_workspace_bytes(1, sheets * Hp * Wp, Cin))
     db = torch.empty((Cin,), dtype=torch.float32, device=dev)
     rc = lib.rn_conv3x3_levels_to_canvas_relu(_ptr_array(gs), lv, Cout, wt.data_ptr(), link.relu_masks[i].data_ptr(), cv.mask.data_ptr(),
                                               dx.data_ptr(), db.data_ptr(), _DT[x.dtype], sheets, Hp, Wp, wt.shape[1], Cin,
@@ -856,8 +802,7 @@ def box_output_conv(x: Tensor, conv, canvas: "Canvas", n_images: int, relu_link=
 
 def cls_output_conv_fusable(x: Tensor, conv, canvas: "Canvas") -> bool:
     "bf16 canvas with a zero border, 3x3 / stride 1 / pad 1, Cin == 256, an even number of output channels (>= 8), <= 6 levels."
-    return (x.is_cuda and x.dtype in H16 and _cl(x) and canvas.pad == 1 and conv.kernel_size == (3, 3)
-            and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
+    return (x.is_cuda and x.dtype in H16 and cl(x) and canvas.pad == 1 and _plain3x3(conv)
             and conv.in_channels == 256 and conv.out_channels % 2 == 0 and 8 <= conv.out_channels <= 1024
             and len(canvas.shapes) <= 6 and canvas.slots <= 8 and x.shape[0] * canvas.H * canvas.W < (1 << 22)
             and (conv.bias is None or conv.bias.dtype == torch.float32))
@@ -873,7 +818,6 @@ def cls_output_conv(x: Tensor, conv, canvas: "Canvas", num_classes: int, n_image
 # ---------------------------------------------------------------------------------------------------
 # The FPN's 3x3 output convs (retinanet/layers.py:34-38, applied at :62-64) on the dense MFMA kernels
 DENSE_GROUP = True     # False: every level through its nn.Conv2d (MIOpen)
-_DENSE_WS: Dict[tuple, Tensor] = {}
 
 
 def dense_group_fusable(xs: Sequence[Tensor], convs) -> bool:
@@ -882,75 +826,74 @@ def dense_group_fusable(xs: Sequence[Tensor], convs) -> bool:
         return False
     N = xs[0].shape[0]
     for x, conv in zip(xs, convs):
-        if not (x.is_cuda and x.dtype in H16 and _cl(x) and x.shape[0] == N and x.shape[1] == 256 and
-                N * x.shape[2] * x.shape[3] < (1 << 22) and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and
-                conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None and
+        if not (x.is_cuda and x.dtype in H16 and cl(x) and x.shape[0] == N and x.shape[1] == 256 and
+                N * x.shape[2] * x.shape[3] < (1 << 22) and _plain3x3(conv) and conv.bias is not None and
                 conv.in_channels == 256 and conv.out_channels == 256 and conv.bias.dtype == torch.float32):
             return False
     return True
 
 
-def _int_array(v):
-    return (C.c_int * len(v))(*[int(i) for i in v])
+def _dense_batched(xs, ws, bs, tag: str, flop: float) -> List[Tensor]:
+    """``[conv3x3(x_p, w_p) (+ b_p)]`` for P <= 4 channels-last ``[N, 256, h_p, w_p]`` inputs in ONE launch of the MFMA implicit GEMM
+    (``rn_conv3x3_dense_batched``: the problems' row tiles share the grid, taps that leave the image read zeros).  With flipped
+    weights and ``bs`` None it is the data gradient."""
+    dev = xs[0].device
+    stream = stream_on(dev)
+    ys = [torch.empty_like(x) for x in xs]
+    _mfma_call(tag, dev, flop,
+               lambda: lib.rn_conv3x3_dense_batched(_ptr_array(xs), _ptr_array(ws), _ptr_array(bs) if bs is not None else None, _ptr_array(ys),
+                                                    len(xs), _DT[xs[0].dtype], xs[0].shape[0], _int_array([x.shape[2] for x in xs]),
+                                                    _int_array([x.shape[3] for x in xs]), 256, 256, _zero_page(dev).data_ptr(), stream),
+               "rn_conv3x3_dense_batched")
+    return ys
+
+
+def _dense_wgrad(gs, xs, tag: str, flop: float) -> List[Tensor]:
+    "The P weight gradients [256, 256, 3, 3] of ``_dense_batched`` in one launch of the position-contraction kernel."
+    dev = xs[0].device
+    stream = stream_on(dev)
+    P = len(xs)
+    wsb = scratch("dense_wgrad", dev, stream, lib.rn_conv3x3_dense_wgrad_workspace_bytes(P))
+    dws = [torch.empty((256, 256, 3, 3), dtype=xs[0].dtype, device=dev, memory_format=torch.channels_last) for _ in range(P)]
+    _mfma_call(tag, dev, flop,
+               lambda: lib.rn_conv3x3_dense_wgrad_batched(_ptr_array(gs), _ptr_array(xs), _ptr_array(dws), P, _DT[xs[0].dtype], xs[0].shape[0],
+                                                          _int_array([x.shape[2] for x in xs]), _int_array([x.shape[3] for x in xs]), 256, 256,
+                                                          _zero_page(dev).data_ptr(), wsb.data_ptr(), wsb.numel(), stream),
+               "rn_conv3x3_dense_wgrad_batched")
+    return dws
+
+
+def _dense_flop(xs) -> float:
+    return sum(2.0 * x.shape[0] * x.shape[2] * x.shape[3] * 256 * 2304 for x in xs)
 
 
 class _DenseConvGroup(torch.autograd.Function):
     """``[conv_p(x_p) for p]`` -- P <= 4 convolutions 3x3 / pad 1, 256 -> 256, each with its own weights and its own
-    ``[N, 256, h_p, w_p]`` channels-last bf16 input -- as ONE launch of the MFMA implicit GEMM each way
-    (``rn_conv3x3_dense_batched``: the levels' row tiles share the grid, taps that leave the image read zeros), one launch of
-    the position-contraction weight-gradient kernel (``rn_conv3x3_dense_wgrad_batched``) and the bias fused into the
-    forward epilogue.  Arguments: x_0 .. x_{P-1}, w_0 .. (bf16, channels-last), b_0 .. (f32)."""
+    ``[N, 256, h_p, w_p]`` channels-last bf16 input -- as one launch each way (``_dense_batched``), one launch for the weight
+    gradients (``_dense_wgrad``) and the bias fused into the forward epilogue.  Arguments: x_0 .. x_{P-1}, w_0 .. (bf16,
+    channels-last), b_0 .. (f32)."""
 
     @staticmethod
     def forward(ctx, *args):
         P = len(args) // 3
-        xs, ws, bs = args[:P], [w if _cl(w) else w.contiguous(memory_format=torch.channels_last) for w in args[P:2 * P]], args[2 * P:]
-        dev = xs[0].device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        N = xs[0].shape[0]
-        hs, wds = [x.shape[2] for x in xs], [x.shape[3] for x in xs]
-        ys = [torch.empty_like(x) for x in xs]
-        flop = sum(2.0 * N * h * w * 256 * 2304 for h, w in zip(hs, wds))
-        _mfma_call(f"mfma_fpn_output_fwd_x{P}", dev, flop,
-                   lambda: lib.rn_conv3x3_dense_batched(_ptr_array(xs), _ptr_array(ws), _ptr_array(bs), _ptr_array(ys), P, _DT[xs[0].dtype], N,
-                                                        _int_array(hs), _int_array(wds), 256, 256, _zero_page(dev).data_ptr(), stream),
-                   "rn_conv3x3_dense_batched")
+        xs, ws, bs = args[:P], [as_cl(w) for w in args[P:2 * P]], args[2 * P:]
+        ys = _dense_batched(xs, ws, bs, f"mfma_fpn_output_fwd_x{P}", _dense_flop(xs))
         ctx.save_for_backward(*xs, *ws)
-        ctx.geom = (P, N, hs, wds, flop)
         return tuple(ys)
 
     @staticmethod
     def backward(ctx, *dys):
-        P, N, hs, wds, flop = ctx.geom
+        P = len(dys)
         xs, ws = ctx.saved_tensors[:P], ctx.saved_tensors[P:]
-        dev = xs[0].device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        gs = [dy if (dy.dtype == xs[0].dtype and _cl(dy)) else dy.to(xs[0].dtype).contiguous(memory_format=torch.channels_last) for dy in dys]
+        N, flop = xs[0].shape[0], _dense_flop(xs)
+        gs = [as_cl(dy, xs[0].dtype) for dy in dys]
         dxs = [None] * P
         if any(ctx.needs_input_grad[:P]):
-            wts = dgrad_weights(list(ws), stream)
-            dxs = [torch.empty_like(x) for x in xs]
-            _mfma_call(f"mfma_fpn_output_dgrad_x{P}", dev, flop,
-                       lambda: lib.rn_conv3x3_dense_batched(_ptr_array(gs), _ptr_array(wts), None, _ptr_array(dxs), P, _DT[xs[0].dtype], N,
-                                                            _int_array(hs), _int_array(wds), 256, 256, _zero_page(dev).data_ptr(), stream),
-                       "rn_conv3x3_dense_batched")
+            wts = dgrad_weights(list(ws), stream_on(xs[0].device))
+            dxs = _dense_batched(gs, wts, None, f"mfma_fpn_output_dgrad_x{P}", flop)
         dws = [None] * P
         if any(ctx.needs_input_grad[P:2 * P]):
-            need = lib.rn_conv3x3_dense_wgrad_workspace_bytes(P)
-            key = (dev.index, stream)
-            wsb = _DENSE_WS.get(key)
-            if wsb is None or wsb.numel() < need:
-                wsb = _DENSE_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
-            dws = [torch.empty((256, 256, 3, 3), dtype=xs[0].dtype, device=dev, memory_format=torch.channels_last) for _ in range(P)]
-            _mfma_call(f"mfma_fpn_output_wgrad_x{P}", dev, flop,
-                       lambda: lib.rn_conv3x3_dense_wgrad_batched(_ptr_array(gs), _ptr_array(xs), _ptr_array(dws), P, _DT[xs[0].dtype], N, _int_array(hs),
-                                                                  _int_array(wds), 256, 256, _zero_page(dev).data_ptr(), wsb.data_ptr(),
-                                                                  wsb.numel(), stream),
-                       "rn_conv3x3_dense_wgrad_batched")
+            dws = _dense_wgrad(gs, xs, f"mfma_fpn_output_wgrad_x{P}", flop)
         dbs = [(_colsum_levels([g.permute(0, 2, 3, 1).reshape(N, -1)], 256) if ctx.needs_input_grad[2 * P + p] else None) for p, g in enumerate(gs)]
         return (*dxs, *dws, *dbs)
 
@@ -969,64 +912,32 @@ CONV3X3_FWD = True      # ... and the forward too (in the step CK's kernel takes
 
 
 def conv3x3_bwd_fusable(conv, x: Tensor) -> bool:
-    return (CONV3X3_BWD and x.is_cuda and x.dtype in H16 and conv.weight.dtype == x.dtype and _cl(x) and
-            conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and
-            conv.groups == 1 and conv.bias is None and conv.in_channels == 256 and conv.out_channels == 256 and
+    return (CONV3X3_BWD and x.is_cuda and x.dtype in H16 and conv.weight.dtype == x.dtype and cl(x) and
+            _plain3x3(conv) and conv.bias is None and conv.in_channels == 256 and conv.out_channels == 256 and
             torch.is_grad_enabled() and x.shape[0] * x.shape[2] * x.shape[3] < (1 << 22))
 
 
 class _Conv3x3MfmaBwd(torch.autograd.Function):
-    "``F.conv2d(x, w, None, 1, 1)`` (256 -> 256, bf16 channels-last) with both gradients on ``rn_conv3x3_dense_*`` (P = 1)."
+    "``F.conv2d(x, w, None, 1, 1)`` (256 -> 256, bf16 channels-last) with both gradients on the dense kernels (``_dense_batched``, P = 1)."
 
     @staticmethod
     def forward(ctx, x, w):
         ctx.save_for_backward(x, w)
         if not CONV3X3_FWD:
             return F.conv2d(x, w, None, 1, 1)
-        N, _, h, wd = x.shape
-        dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        wc = w if _cl(w) else w.contiguous(memory_format=torch.channels_last)
-        y = torch.empty_like(x)
-        _mfma_call("mfma_conv2_fwd", dev, 2.0 * N * h * wd * 256 * 2304,
-                   lambda: lib.rn_conv3x3_dense_batched(_ptr_array([x]), _ptr_array([wc]), None, _ptr_array([y]), 1, _DT[x.dtype], N,
-                                                        _int_array([h]), _int_array([wd]), 256, 256, _zero_page(dev).data_ptr(), stream),
-                   "rn_conv3x3_dense_batched")
-        return y
+        return _dense_batched([x], [as_cl(w)], None, "mfma_conv2_fwd", _dense_flop([x]))[0]
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        N, _, h, wd = x.shape
-        dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        g = dy if (dy.dtype == x.dtype and _cl(dy)) else dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
-        wc = w if _cl(w) else w.contiguous(memory_format=torch.channels_last)
-        flop = 2.0 * N * h * wd * 256 * 2304
+        g = as_cl(dy, x.dtype)
+        flop = _dense_flop([x])
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            wt = dgrad_weights([w], stream)[0]
-            dx = torch.empty_like(x)
-            _mfma_call("mfma_conv2_dgrad", dev, flop,
-                       lambda: lib.rn_conv3x3_dense_batched(_ptr_array([g]), _ptr_array([wt]), None, _ptr_array([dx]), 1, _DT[x.dtype], N,
-                                                            _int_array([h]), _int_array([wd]), 256, 256, _zero_page(dev).data_ptr(), stream),
-                       "rn_conv3x3_dense_batched")
+            wt = dgrad_weights([w], stream_on(x.device))[0]
+            dx = _dense_batched([g], [wt], None, "mfma_conv2_dgrad", flop)[0]
         if ctx.needs_input_grad[1]:
-            need = lib.rn_conv3x3_dense_wgrad_workspace_bytes(1)
-            key = (dev.index, stream)
-            wsb = _DENSE_WS.get(key)
-            if wsb is None or wsb.numel() < need:
-                wsb = _DENSE_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
-            dw = torch.empty((256, 256, 3, 3), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
-            _mfma_call("mfma_conv2_wgrad", dev, flop,
-                       lambda: lib.rn_conv3x3_dense_wgrad_batched(_ptr_array([g]), _ptr_array([x]), _ptr_array([dw]), 1, _DT[x.dtype], N, _int_array([h]),
-                                                                  _int_array([wd]), 256, 256, _zero_page(dev).data_ptr(), wsb.data_ptr(),
-                                                                  wsb.numel(), stream),
-                       "rn_conv3x3_dense_wgrad_batched")
+            dw = _dense_wgrad([g], [x], "mfma_conv2_wgrad", flop)[0]
         return dx, dw
 
 
@@ -1048,7 +959,7 @@ NARROW_FWD = True
 
 
 def narrow_fwd_ok(x: Tensor, w: Tensor) -> bool:
-    return (NARROW_FWD and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and _cl(x) and
+    return (NARROW_FWD and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and cl(x) and
             tuple(w.shape) == (64, 64, 3, 3) and x.shape[1] == 64 and x.numel() // 64 < (1 << 31))
 
 
@@ -1056,10 +967,8 @@ def conv3x3_narrow_forward(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, 
     """``F.conv2d(x, w, None, 1, 1)`` for bf16 channels-last x [N, 64, H, W] and w [64, 64, 3, 3] on ``rn_conv3x3_narrow_forward``;
     with ``bias`` (f32 [64]): ``act(conv + bias)``, act = ReLU when ``relu`` (the folded-BatchNorm inference path)."""
     dev = x.device
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    wc = w if _cl(w) else w.contiguous(memory_format=torch.channels_last)
+    stream = stream_on(dev)
+    wc = as_cl(w)
     N, C, H, W = x.shape
     y = torch.empty_like(x, memory_format=torch.channels_last)
     _mfma_call("mfma_conv2_narrow_fwd", dev, 2.0 * N * H * W * C * C * 9,
@@ -1073,18 +982,21 @@ def conv3x3_narrow_forward(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, 
 DENSE_EVAL = True
 
 
-def dense_eval_ok(x: Tensor, w: Tensor) -> bool:
-    return (DENSE_EVAL and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and _cl(x) and _cl(w) and
+def _dense_operands_ok(x: Tensor, w: Tensor) -> bool:
+    "What the dense mode of the head's MFMA kernel takes: 16-bit channels-last x and w, Cin % 64 == 0, Cout % 256 == 0, < 2^22 positions."
+    return (x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and cl(x) and cl(w) and
             tuple(w.shape[2:]) == (3, 3) and w.shape[1] == x.shape[1] and w.shape[1] % 64 == 0 and w.shape[0] % 256 == 0 and
             x.shape[0] * x.shape[2] * x.shape[3] < (1 << 22))
+
+
+def dense_eval_ok(x: Tensor, w: Tensor) -> bool:
+    return DENSE_EVAL and _dense_operands_ok(x, w)
 
 
 def conv3x3_dense_bias_act(x: Tensor, w: Tensor, bias: Optional[Tensor], relu: bool) -> Tensor:
     "``act(F.conv2d(x, w, bias, 1, 1))`` (bf16 channels-last, Cin % 64 == 0, Cout % 256 == 0; bias f32) on ``rn_conv3x3_dense_batched_act``."
     dev = x.device
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = stream_on(dev)
     N, Cin, h, wd = x.shape
     Cout = int(w.shape[0])
     y = torch.empty((N, Cout, h, wd), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
@@ -1097,13 +1009,10 @@ def conv3x3_dense_bias_act(x: Tensor, w: Tensor, bias: Optional[Tensor], relu: b
 
 
 DENSE_SPLITK = True     # few-row-tile convolutions (conv2 of layer4: forward and, with flipped weights, data gradient) on the dense MFMA kernel, K split
-_SPLITK_WS: Dict[tuple, Tensor] = {}
 
 
 def dense_splitk_bytes(x: Tensor, w: Tensor) -> int:
-    if not (DENSE_SPLITK and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and _cl(x) and _cl(w) and
-            tuple(w.shape[2:]) == (3, 3) and w.shape[1] == x.shape[1] and w.shape[1] % 64 == 0 and w.shape[0] % 256 == 0 and
-            x.shape[0] * x.shape[2] * x.shape[3] < (1 << 22)):
+    if not (DENSE_SPLITK and _dense_operands_ok(x, w)):
         return 0
     return int(lib.rn_conv3x3_dense_splitk_workspace_bytes(x.shape[0], x.shape[2], x.shape[3], int(w.shape[0])))
 
@@ -1111,15 +1020,10 @@ def dense_splitk_bytes(x: Tensor, w: Tensor) -> int:
 def conv3x3_dense_splitk(x: Tensor, w: Tensor, need: int, tag: str = "mfma_conv2_splitk") -> Tensor:
     "``F.conv2d(x, w, None, 1, 1)`` on ``rn_conv3x3_dense_splitk`` (``need`` = ``dense_splitk_bytes(x, w)`` > 0); no autograd."
     dev = x.device
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = stream_on(dev)
     N, Cin, h, wd = x.shape
     Cout = int(w.shape[0])
-    key = (dev.index, stream)
-    ws = _SPLITK_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _SPLITK_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
+    ws = scratch("splitk", dev, stream, need)
     y = torch.empty((N, Cout, h, wd), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
     _mfma_call(tag, dev, 2.0 * N * h * wd * Cout * 9 * Cin,
                lambda: lib.rn_conv3x3_dense_splitk(x.data_ptr(), w.data_ptr(), y.data_ptr(), _DT[x.dtype], N, h, wd, Cin, Cout, _zero_page(dev).data_ptr(),
@@ -1132,7 +1036,7 @@ DENSE_BAND_MAX_COUT = 128
 
 
 def dense_band_ok(x: Tensor, w: Tensor) -> bool:
-    return (DENSE_BAND and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and _cl(x) and _cl(w) and
+    return (DENSE_BAND and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and cl(x) and cl(w) and
             tuple(w.shape[2:]) == (3, 3) and w.shape[1] == x.shape[1] and w.shape[1] % 64 == 0 and w.shape[0] % 128 == 0 and
             w.shape[0] <= DENSE_BAND_MAX_COUT and x.shape[0] * x.shape[2] * x.shape[3] * max(int(w.shape[0]), int(w.shape[1])) < (1 << 31))
 
@@ -1140,9 +1044,7 @@ def dense_band_ok(x: Tensor, w: Tensor) -> bool:
 def conv3x3_dense_band(x: Tensor, w: Tensor, tag: str = "mfma_conv2_band") -> Tensor:
     "``F.conv2d(x, w, None, 1, 1)`` on ``rn_conv3x3_dense_band``; no autograd."
     dev = x.device
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = stream_on(dev)
     N, Cin, h, wd = x.shape
     Cout = int(w.shape[0])
     y = torch.empty((N, Cout, h, wd), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
@@ -1159,9 +1061,7 @@ def conv3x3_dense_band_stats(x: Tensor, w: Tensor, tag: str = "mfma_conv2_band")
     """``conv3x3_dense_band`` + (sum y, sum y^2) per channel of the stored output, no second pass over it -> (y, partial f32
     [tiles, 2, Cout], tiles) for ``rn_bn_stats_finalize``."""
     dev = x.device
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = stream_on(dev)
     N, Cin, h, wd = x.shape
     Cout = int(w.shape[0])
     tiles = int(lib.rn_conv3x3_dense_band_tiles(N, h, wd))
@@ -1181,34 +1081,31 @@ def conv3x3_same(x: Tensor, w: Tensor) -> Tensor:
         return conv3x3_dense_band(x, w)
     need = dense_splitk_bytes(x, w)
     if need > 0:
-        return conv3x3_dense_splitk(x, w if _cl(w) else w.contiguous(memory_format=torch.channels_last), need)
+        return conv3x3_dense_splitk(x, as_cl(w), need)
     return F.conv2d(x, w, None, 1, 1)
 
 
 def dgrad_as_fwd_ok(w: Tensor, stride, x: Tensor) -> bool:
-    return (DGRAD_AS_FWD and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and _cl(x) and w.dim() == 4 and
+    return (DGRAD_AS_FWD and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and cl(x) and w.dim() == 4 and
             tuple(w.shape[2:]) == (3, 3) and tuple(stride) == (1, 1) and w.shape[0] % 32 == 0 and w.shape[1] % 32 == 0)
 
 
 def conv3x3_dgrad_as_fwd(g: Tensor, w: Tensor) -> Tensor:
     "Data gradient of ``F.conv2d(x, w, None, 1, 1)`` (w [Cout, Cin, 3, 3] bf16) for the output gradient ``g``: a forward convolution."
     dev = g.device
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = stream_on(dev)
     wt = dgrad_weights([w], stream)[0]
-    gc = g if (g.dtype == w.dtype and _cl(g)) else g.to(w.dtype).contiguous(memory_format=torch.channels_last)
+    gc = as_cl(g, w.dtype)
     return conv3x3_same(gc, wt)
 
 
 # Their weight gradient: one team of waves holds all nine taps of a 64 x 64 block of dW (csrc/wgrad3x3.hip) instead of one
 # workgroup per tap re-reading both operands (MIOpen: 123 us + a zero fill + a cast per layer1 block).
 NARROW_WGRAD = True
-_NARROW_WS: Dict[tuple, Tensor] = {}
 
 
 def wgrad_narrow_ok(w: Tensor, stride, x: Tensor) -> bool:
-    return (NARROW_WGRAD and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and _cl(x) and w.dim() == 4 and
+    return (NARROW_WGRAD and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and cl(x) and w.dim() == 4 and
             tuple(w.shape[2:]) == (3, 3) and tuple(stride) == (1, 1) and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0 and
             w.shape[0] * w.shape[1] <= 512 * 512)
 
@@ -1216,17 +1113,11 @@ def wgrad_narrow_ok(w: Tensor, stride, x: Tensor) -> bool:
 def conv3x3_wgrad_narrow(g: Tensor, x: Tensor, w: Tensor, tag: str = "mfma_conv2_narrow_wgrad", flop: Optional[float] = None) -> Tensor:
     "Weight gradient of ``F.conv2d(x, w, None, 1, 1)`` (bf16 channels-last, Cout / Cin multiples of 64) -> like ``w``, channels-last."
     dev = x.device
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = stream_on(dev)
     N, Cin, H, W = x.shape
     Cout = int(w.shape[0])
-    gc = g if (g.dtype == x.dtype and _cl(g)) else g.to(x.dtype).contiguous(memory_format=torch.channels_last)
-    need = lib.rn_conv3x3_wgrad_narrow_workspace_bytes(Cout, Cin)
-    key = (dev.index, stream)
-    ws = _NARROW_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _NARROW_WS[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
+    gc = as_cl(g, x.dtype)
+    ws = scratch("narrow_wgrad", dev, stream, lib.rn_conv3x3_wgrad_narrow_workspace_bytes(Cout, Cin))
     dw = torch.empty((Cout, Cin, 3, 3), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
     _mfma_call(tag, dev, flop if flop is not None else 2.0 * N * H * W * Cout * Cin * 9,
                lambda: lib.rn_conv3x3_wgrad_narrow(gc.data_ptr(), x.data_ptr(), dw.data_ptr(), _DT[x.dtype], N, H, W, Cout, Cin,
@@ -1252,7 +1143,7 @@ class _Conv3x3DgradAsFwd(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        g = dy if (dy.dtype == x.dtype and _cl(dy)) else dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        g = as_cl(dy, x.dtype)
         dx = conv3x3_dgrad_as_fwd(g, w) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
@@ -1261,8 +1152,7 @@ class _Conv3x3DgradAsFwd(torch.autograd.Function):
 
 
 def conv3x3_dgrad_fwd_fusable(conv, x: Tensor) -> bool:
-    return (dgrad_as_fwd_ok(conv.weight, conv.stride, x) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and
-            conv.bias is None and torch.is_grad_enabled())
+    return dgrad_as_fwd_ok(conv.weight, conv.stride, x) and _plain3x3(conv) and conv.bias is None and torch.is_grad_enabled()
 
 
 def conv3x3_dgrad_fwd(conv, x: Tensor) -> Tensor:

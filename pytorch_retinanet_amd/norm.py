@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
+from ._launch import as_cl, cl, stream_on
 from ._lib import RN_BF16, RN_F16, RN_F32, check, lib
 
 _DT = {torch.float32: RN_F32, torch.bfloat16: RN_BF16, torch.float16: RN_F16}
@@ -48,19 +49,13 @@ def _workspace(dev: torch.device, stream: int, C_: int):
     return ws.data_ptr(), ws.numel()
 
 
-def _cl(t: Tensor) -> bool:
-    return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
-
-
 class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps, relu, link=None):
         N, Cc, H, W = x.shape
         M = N * H * W
         dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = stream_on(dev)
         y = torch.empty_like(x)                                   # keeps the channels_last strides
         stats = torch.empty((4 * Cc,), dtype=torch.float32, device=dev)   # save_mean | save_invstd | coef a | coef b
         sp = stats.data_ptr()
@@ -85,11 +80,8 @@ class _BNAct(torch.autograd.Function):
         x, bits, weight, stats = ctx.saved_tensors
         training, relu, has_res, M, Cc = ctx.cfg
         dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
-        stream = torch.cuda.current_stream().cuda_stream
-        if dy.dtype != x.dtype or not _cl(dy):
-            dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        stream = stream_on(dev)
+        dy = as_cl(dy, x.dtype)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if has_res else None
         grads = torch.empty((5 * Cc,), dtype=torch.float32, device=dev)     # dgamma | dbeta | coef a | k0 | k1
@@ -109,11 +101,11 @@ class _BNAct(torch.autograd.Function):
 
 class FusedBatchNorm2d(nn.BatchNorm2d):
     def _fusable(self, x: Tensor, residual: Optional[Tensor]) -> bool:
-        if not (x.is_cuda and x.dtype in _DT and x.shape[1] % 8 == 0 and _cl(x) and x.numel()):
+        if not (x.is_cuda and x.dtype in _DT and x.shape[1] % 8 == 0 and cl(x) and x.numel()):
             return False
         if not (self.affine and self.track_running_stats and self.momentum is not None and self.weight.dtype == torch.float32):
             return False
-        if residual is not None and not (residual.shape == x.shape and residual.dtype == x.dtype and _cl(residual)):
+        if residual is not None and not (residual.shape == x.shape and residual.dtype == x.dtype and cl(residual)):
             return False
         return True
 

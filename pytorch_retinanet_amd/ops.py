@@ -13,6 +13,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._launch import zero_page
 from ._lib import RN_BF16, RN_F16, RN_F32, RnDetectParams, RnLevel, RnLossParams, check, lib
 
 RN_MATCH_NUM_FG_ZEROED, RN_MATCH_FLAGGED_ONLY = 1, 2          # include/retinanet_hip.h
@@ -178,7 +179,6 @@ def gt_pack(boxes: Sequence[Tensor], labels: Sequence[Tensor], dev: torch.device
     gt_boxes = torch.empty((total, 4), dtype=torch.float32, device=dev)
     gt_labels = torch.empty((total,), dtype=torch.int64, device=dev)
     num_fg = torch.empty((B,), dtype=torch.int32, device=dev)
-    from .biasact import _zero_page
     srcs, dsts, nb, o = [], [], [], 0
     for b, l, c in zip(bs, ls, counts):
         if c:
@@ -186,7 +186,7 @@ def gt_pack(boxes: Sequence[Tensor], labels: Sequence[Tensor], dev: torch.device
             dsts += [gt_boxes.data_ptr() + 16 * o, gt_labels.data_ptr() + 8 * o]
             nb += [16 * c, 8 * c]
             o += c
-    srcs.append(_zero_page(dev).data_ptr()); dsts.append(num_fg.data_ptr()); nb.append(4 * B)
+    srcs.append(zero_page(dev).data_ptr()); dsts.append(num_fg.data_ptr()); nb.append(4 * B)
     n = len(srcs)
     with torch.cuda.device(dev), _timed("gt_pack", dev):
         check(lib.rn_copy_many((C.c_void_p * n)(*srcs), (C.c_void_p * n)(*dsts), (C.c_int64 * n)(*nb), n, _stream(dev)), "rn_copy_many")

@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
+from ._launch import stream_on
 from ._lib import RN_BF16, RN_F16, RN_F32, check, lib
 
 _DT = {torch.float32: RN_F32, torch.bfloat16: RN_BF16, torch.float16: RN_F16}
@@ -16,12 +17,11 @@ class _MaxPool3x3s2(torch.autograd.Function):
     def forward(ctx, x):
         N, C, H, W = x.shape
         dev = x.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
+        stream = stream_on(dev)
         y = torch.empty((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
         arg = torch.empty(y.shape, dtype=torch.uint8, device=dev, memory_format=torch.channels_last) if x.requires_grad else None
         check(lib.rn_maxpool3x3s2_forward(x.data_ptr(), y.data_ptr(), arg.data_ptr() if arg is not None else 0, _DT[x.dtype],
-                                          N, H, W, C, torch.cuda.current_stream().cuda_stream), "rn_maxpool3x3s2_forward")
+                                          N, H, W, C, stream), "rn_maxpool3x3s2_forward")
         ctx.save_for_backward(arg)
         ctx.meta = (x.shape, x.dtype)
         return y
@@ -31,13 +31,11 @@ class _MaxPool3x3s2(torch.autograd.Function):
         (arg,) = ctx.saved_tensors
         (N, C, H, W), dt = ctx.meta
         dev = dy.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
+        stream = stream_on(dev)
         if dy.dtype != dt or not dy.is_contiguous(memory_format=torch.channels_last):
             dy = dy.to(dt).contiguous(memory_format=torch.channels_last)
         dx = torch.empty((N, C, H, W), dtype=dt, device=dev, memory_format=torch.channels_last)
-        check(lib.rn_maxpool3x3s2_backward(arg.data_ptr(), dy.data_ptr(), dx.data_ptr(), _DT[dt], N, H, W, C,
-                                           torch.cuda.current_stream().cuda_stream), "rn_maxpool3x3s2_backward")
+        check(lib.rn_maxpool3x3s2_backward(arg.data_ptr(), dy.data_ptr(), dx.data_ptr(), _DT[dt], N, H, W, C, stream), "rn_maxpool3x3s2_backward")
         return dx
 
 
@@ -59,26 +57,23 @@ class _AddUpsample2x(torch.autograd.Function):
     def forward(ctx, lat, top):
         N, C, H, W = lat.shape
         dev = lat.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
+        stream = stream_on(dev)
         out = torch.empty_like(lat)
-        check(lib.rn_fpn_add_upsample2x(lat.data_ptr(), top.data_ptr(), out.data_ptr(), _DT[lat.dtype], N, H, W, C,
-                                        torch.cuda.current_stream().cuda_stream), "rn_fpn_add_upsample2x")
+        check(lib.rn_fpn_add_upsample2x(lat.data_ptr(), top.data_ptr(), out.data_ptr(), _DT[lat.dtype], N, H, W, C, stream), "rn_fpn_add_upsample2x")
         return out
 
     @staticmethod
     def backward(ctx, g):
         N, C, H, W = g.shape
         dev = g.device
-        if dev.index != torch.cuda.current_device():
-            torch.cuda.set_device(dev)
+        stream = stream_on(dev)
         if not g.is_contiguous(memory_format=torch.channels_last):
             g = g.contiguous(memory_format=torch.channels_last)
         dtop = None
         if ctx.needs_input_grad[1]:
             dtop = torch.empty((N, C, H // 2, W // 2), dtype=g.dtype, device=dev, memory_format=torch.channels_last)
-            check(lib.rn_fpn_upsample2x_backward(g.data_ptr(), dtop.data_ptr(), _DT[g.dtype], N, H // 2, W // 2, C,
-                                                 torch.cuda.current_stream().cuda_stream), "rn_fpn_upsample2x_backward")
+            check(lib.rn_fpn_upsample2x_backward(g.data_ptr(), dtop.data_ptr(), _DT[g.dtype], N, H // 2, W // 2, C, stream),
+                  "rn_fpn_upsample2x_backward")
         return (g if ctx.needs_input_grad[0] else None), dtop
 
 

@@ -29,6 +29,7 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from . import norm
+from ._launch import cl, stream_on
 from ._lib import (RN_BF16, RN_F16, RN_PW_EPI_BIAS, RN_PW_EPI_RELU_BWD, RN_PW_EPI_RESID, RN_PW_EPI_STATS, RN_PW_PRO_AFFINE_RELU, RN_PW_PRO_BN_BWD,
                    RnPwConv, RnPwEpilogue, RnPwPrologue, check, lib)
 from .ops import _timed
@@ -50,10 +51,6 @@ _DT16 = {torch.bfloat16: RN_BF16, torch.float16: RN_F16}
 PW_FLOP: Dict[str, float] = {}        # useful flop per call of the timed pw launches (bench.py)
 
 
-def _cl(t: Tensor) -> bool:
-    return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
-
-
 def _desc(x: Tensor, n_out: int, taps: int, stride: int) -> Tuple[RnPwConv, Tuple[int, int, int, int]]:
     "Geometry of a conv over channels-last ``x`` [Nimg, Cin, H, W] -> ([Nimg, n_out, Ho, Wo])."
     Nimg, Cin, H, W = x.shape
@@ -61,12 +58,6 @@ def _desc(x: Tensor, n_out: int, taps: int, stride: int) -> Tuple[RnPwConv, Tupl
     k = 3 if taps == 9 else 1
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     return RnPwConv(Nimg * Ho * Wo, Cin, n_out, taps, stride, pad, Ho, Wo, H, W, _DT16[x.dtype]), (Nimg, n_out, Ho, Wo)
-
-
-def _stream(dev: torch.device) -> int:
-    if dev.index != torch.cuda.current_device():
-        torch.cuda.set_device(dev)
-    return torch.cuda.current_stream().cuda_stream
 
 
 def affine_relu(coef: Tensor) -> RnPwPrologue:
@@ -91,7 +82,7 @@ def pw_forward(x: Tensor, w: Tensor, stride: int = 1, pro: Optional[RnPwPrologue
     taps = int(w.shape[2] * w.shape[3])
     d, oshape = _desc(x, int(w.shape[0]), taps, stride)
     y = torch.empty(oshape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    st = _stream(x.device)
+    st = stream_on(x.device)
     PW_FLOP[tag] = 2.0 * d.M * d.N * taps * d.Cin
     with _timed(tag, x.device):
         check(lib.rn_pw_conv_forward(C.byref(d), x.data_ptr(), w.data_ptr(), y.data_ptr(), C.byref(pro) if pro is not None else None,
@@ -114,14 +105,14 @@ EVAL_1X1_FUSED = True
 
 
 def eval_conv1x1_ok(conv, x: Tensor, w: Tensor, residual: Optional[Tensor]) -> bool:
-    if not (EVAL_1X1_FUSED and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and _cl(x) and _cl(w)):
+    if not (EVAL_1X1_FUSED and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and cl(x) and cl(w)):
         return False
     if conv.kernel_size != (1, 1) or conv.padding != (0, 0) or conv.dilation != (1, 1) or conv.groups != 1 or conv.stride not in ((1, 1), (2, 2)):
         return False
     Cout, Cin = int(w.shape[0]), int(w.shape[1])
     if Cin % 64 or Cout % 64 or x.shape[0] * x.shape[2] * x.shape[3] >= (1 << 31):
         return False
-    return residual is None or (residual.dtype in H16 and _cl(residual))
+    return residual is None or (residual.dtype in H16 and cl(residual))
 
 
 def eval_conv1x1(conv, x: Tensor, w: Tensor, bias: Tensor, relu: bool, residual: Optional[Tensor]) -> Tensor:
@@ -156,7 +147,7 @@ def pw_wgrad(g: Tensor, x: Tensor, w_like: Tensor, stride: int = 1, gpro: Option
     assert tuple(g.shape) == oshape, (tuple(g.shape), oshape)
     dw = torch.empty_like(w_like)
     dev = x.device
-    st = _stream(dev)
+    st = stream_on(dev)
     need = lib.rn_pw_wgrad_workspace_bytes(C.byref(d))
     if defer is not None and DEFER_WGRAD_REDUCE and len(defer) < 8:
         ws = torch.empty((need,), dtype=torch.uint8, device=dev)
@@ -187,7 +178,7 @@ def pw_wgrad_flush(defer: list) -> None:
     assert all(e[3].dtype == defer[0][3].dtype for e in defer)
     check(lib.rn_pw_wgrad_reduce_many_dt((C.c_void_p * n)(*[e[0].data_ptr() for e in defer]), (C.c_int * n)(*[e[1] for e in defer]),
                                          (C.c_int64 * n)(*[e[2] for e in defer]), (C.c_void_p * n)(*[e[3].data_ptr() for e in defer]), n,
-                                         _DT16[defer[0][3].dtype], _stream(defer[0][3].device)), "rn_pw_wgrad_reduce_many_dt")
+                                         _DT16[defer[0][3].dtype], stream_on(defer[0][3].device)), "rn_pw_wgrad_reduce_many_dt")
     defer.clear()
 
 
@@ -203,7 +194,7 @@ def bn_finalize(partial: Tensor, nb: int, M: int, bn) -> Tensor:
     sp = stats.data_ptr()
     rm, rv, nbt = _bn_buffers(bn)
     check(lib.rn_bn_stats_finalize(partial.data_ptr(), nb, M, Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), rm, rv, nbt, bn.momentum, bn.eps,
-                                   sp, sp + 4 * Cc, sp + 8 * Cc, _stream(partial.device)), "rn_bn_stats_finalize")
+                                   sp, sp + 4 * Cc, sp + 8 * Cc, stream_on(partial.device)), "rn_bn_stats_finalize")
     norm.note_raw_write()
     return stats
 
@@ -213,7 +204,7 @@ def bn_stats(x: Tensor, bn) -> Tensor:
     Nimg, Cc, H, W = x.shape
     M = Nimg * H * W
     dev = x.device
-    st = _stream(dev)
+    st = stream_on(dev)
     stats = torch.empty((4 * Cc,), dtype=torch.float32, device=dev)
     sp = stats.data_ptr()
     wp, wn = norm._workspace(dev, st, Cc)
@@ -234,11 +225,11 @@ def bn_apply(x: Tensor, stats: Tensor, relu: bool, residual: Optional[Tensor] = 
     if res_stats is not None:
         assert relu and residual is not None
         check(lib.rn_bn_apply_res_affine(x.data_ptr(), residual.data_ptr(), res_stats.data_ptr() + 8 * Cc, y.data_ptr(), _DT16[x.dtype], M, Cc,
-                                         stats.data_ptr() + 8 * Cc, bits.data_ptr() if bits is not None else 0, _stream(x.device)),
+                                         stats.data_ptr() + 8 * Cc, bits.data_ptr() if bits is not None else 0, stream_on(x.device)),
               "rn_bn_apply_res_affine")
         return y, bits
     check(lib.rn_bn_apply(x.data_ptr(), residual.data_ptr() if residual is not None else 0, y.data_ptr(), _DT16[x.dtype], M, Cc,
-                          stats.data_ptr() + 8 * Cc, int(relu), bits.data_ptr() if bits is not None else 0, _stream(x.device)), "rn_bn_apply")
+                          stats.data_ptr() + 8 * Cc, int(relu), bits.data_ptr() if bits is not None else 0, stream_on(x.device)), "rn_bn_apply")
     return y, bits
 
 
@@ -275,7 +266,7 @@ class _BottleneckFn(torch.autograd.Function):
             z2 = biasact.conv3x3_same(a1, w2)                                # 64 channels: csrc/narrow3x3.hip
         else:
             z2 = F.conv2d(a1, w2, None, blk.conv2.stride, blk.conv2.padding)
-        if not _cl(z2):
+        if not cl(z2):
             z2 = z2.contiguous(memory_format=torch.channels_last)
         if st2 is None:
             st2 = bn_stats(z2, blk.bn2)
@@ -291,7 +282,7 @@ class _BottleneckFn(torch.autograd.Function):
             PW_FLOP["pw_conv3_fwd"] = 2.0 * M1 * Cm * C4o
             with _timed("pw_conv3_fwd", dev):
                 check(lib.rn_pw_conv3_forward(M1, Cm, C4o, _DT16[x.dtype], z2.data_ptr(), st2.data_ptr() + 8 * Cm, w3.data_ptr(), z3.data_ptr(),
-                                              p3.data_ptr(), _stream(dev)), "rn_pw_conv3_forward")
+                                              p3.data_ptr(), stream_on(dev)), "rn_pw_conv3_forward")
         else:
             e3, p3, nb3 = stats_epilogue(M1, w3.shape[0], dev)
             z3 = pw_forward(z2, w3, pro=affine_relu(st2[2 * Cm:]), epi=e3, tag="pw_conv3_fwd")
@@ -321,7 +312,7 @@ class _BottleneckFn(torch.autograd.Function):
             PW_FLOP["pw_block_out_conv1"] = 2.0 * M1 * C4 * CN
             with _timed("pw_block_out_conv1", dev):
                 check(lib.rn_pw_block_out_conv1(M1, C4, CN, _DT16[x.dtype], z3.data_ptr(), res.data_ptr(), ra, rb, p3o + 8 * C4, p3o + 12 * C4,
-                                                w1n.data_ptr(), out.data_ptr(), bits.data_ptr(), z1n.data_ptr(), partn.data_ptr(), _stream(dev)),
+                                                w1n.data_ptr(), out.data_ptr(), bits.data_ptr(), z1n.data_ptr(), partn.data_ptr(), stream_on(dev)),
                       "rn_pw_block_out_conv1")
             blk.__dict__["_chain_tmp"] = (z1n, partn, nbn, w1n.data_ptr(), w1n._version, z3, bits, st3)
         elif wd is not None:
@@ -338,8 +329,8 @@ class _BottleneckFn(torch.autograd.Function):
         x, w1, g1, w2, g2, w3, g3, wd, gd, z1, a1, z2, z3, zd, bits, st1, st2, st3, std, pz3, pbits, pst3 = ctx.saved_tensors
         blk = ctx.blk
         dev = x.device
-        st = _stream(dev)
-        if g_out.dtype != x.dtype or not _cl(g_out):
+        st = stream_on(dev)
+        if g_out.dtype != x.dtype or not cl(g_out):
             g_out = g_out.to(x.dtype).contiguous(memory_format=torch.channels_last)
         C4, Cm = w3.shape[0], w2.shape[0]
         M1 = z3.shape[0] * z3.shape[2] * z3.shape[3]
@@ -406,13 +397,13 @@ class _BottleneckFn(torch.autograd.Function):
             # stride 1: the data gradient as a forward convolution with the flipped weights (CK's forward kernel, no zero fill)
             da1 = biasact.conv3x3_dgrad_as_fwd(dz2, w2)
             dw2 = biasact.conv3x3_weight_gradient(dz2, a1, w2)
-        elif STRIDED_WGRAD_PW and tuple(blk.conv2.stride) == (2, 2) and tuple(blk.conv2.padding) == (1, 1) and _cl(w2):
+        elif STRIDED_WGRAD_PW and tuple(blk.conv2.stride) == (2, 2) and tuple(blk.conv2.padding) == (1, 1) and cl(w2):
             da1 = torch.ops.aten.convolution_backward(dz2, a1, w2, None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
             dw2 = pw_wgrad(dz2, a1, w2, stride=2, tag="pw_conv2_s2_wgrad")
         else:
             da1, dw2 = torch.ops.aten.convolution_backward(dz2, a1, w2, None, list(blk.conv2.stride), list(blk.conv2.padding), [1, 1], False,
                                                            [0, 0], 1, [True, True, False])[:2]
-        if not _cl(da1):
+        if not cl(da1):
             da1 = da1.contiguous(memory_format=torch.channels_last)
         # bn1 backward (ReLU mask recomputed from z1 and the forward coefficients)
         gr1 = torch.empty((5 * Cm,), dtype=torch.float32, device=dev)
@@ -469,7 +460,7 @@ def _conv1_dgrad(dz1: Tensor, w1t: Tensor, x: Tensor, resid: Tensor, rbits: Opti
         with _timed("pw_conv1_dgrad_sums", dev):
             check(lib.rn_pw_dgrad_resid_sums(M0, Cm, Cin, _DT16[x.dtype], dz1.data_ptr(), w1t.data_ptr(), resid.data_ptr(),
                                              rbits.data_ptr() if rbits is not None else 0, rs, x.shape[2], x.shape[3], pz3.data_ptr(),
-                                             pbits.data_ptr(), pm, pm + 4 * Cin, dx.data_ptr(), parts.data_ptr(), _stream(dev)),
+                                             pbits.data_ptr(), pm, pm + 4 * Cin, dx.data_ptr(), parts.data_ptr(), stream_on(dev)),
                   "rn_pw_dgrad_resid_sums")
         # the entry keeps dx itself: a gradient somebody else still references is never accumulated into in place by the autograd engine
         # (torch/csrc/autograd/input_buffer.cpp: only uniquely owned buffers are), so a second consumer of the producer's output shows up
@@ -485,7 +476,7 @@ def _conv1_dgrad(dz1: Tensor, w1t: Tensor, x: Tensor, resid: Tensor, rbits: Opti
 
 def bottleneck_fusable(blk, x: Tensor, in_forward: bool = False) -> bool:
     "``in_forward``: asked from inside an autograd Function's forward (grad mode is off there) about the block that will run next"
-    if not (FUSED_BOTTLENECK and x.is_cuda and x.dtype in H16 and _cl(x) and (in_forward or torch.is_grad_enabled())):
+    if not (FUSED_BOTTLENECK and x.is_cuda and x.dtype in H16 and cl(x) and (in_forward or torch.is_grad_enabled())):
         return False
     bns = [blk.bn1, blk.bn2, blk.bn3] + ([blk.downsample[1]] if blk.downsample is not None else [])
     convs = [blk.conv1, blk.conv2, blk.conv3] + ([blk.downsample[0]] if blk.downsample is not None else [])
@@ -500,7 +491,7 @@ def bottleneck_fusable(blk, x: Tensor, in_forward: bool = False) -> bool:
         return False
     if blk.conv1.stride != (1, 1) or blk.conv3.stride != (1, 1) or blk.conv2.stride[0] != blk.conv2.stride[1] or blk.conv2.stride[0] not in (1, 2):
         return False
-    if not _cl(blk.conv2.weight):
+    if not cl(blk.conv2.weight):
         return False
     if x.shape[0] * x.shape[2] * x.shape[3] >= (1 << 31) // max(blk.conv3.out_channels, 1) * 8:
         return False
@@ -631,7 +622,7 @@ class _Conv1x1(torch.autograd.Function):
         Nimg, Cin, H, W = x.shape
         Cout = w.shape[0]
         M = Nimg * H * W
-        if g.dtype != x.dtype or not _cl(g):
+        if g.dtype != x.dtype or not cl(g):
             g = g.to(x.dtype).contiguous(memory_format=torch.channels_last)
         dx = dw = db = None
         g2 = g.permute(0, 2, 3, 1).reshape(M, Cout)
@@ -640,7 +631,7 @@ class _Conv1x1(torch.autograd.Function):
             acc = None
             if join is not None and ctx.receiver:
                 acc, join.full = join.full, None
-                if acc is not None and not (acc.dtype == x.dtype and acc.shape == x.shape and _cl(acc)):
+                if acc is not None and not (acc.dtype == x.dtype and acc.shape == x.shape and cl(acc)):
                     acc = acc.to(x.dtype).contiguous(memory_format=torch.channels_last)
             if _dgrad_by_mm(M, Cin, Cout):
                 if acc is not None:
@@ -686,7 +677,7 @@ class _Conv1x1S2(torch.autograd.Function):
         x, w = ctx.saved_tensors
         Nimg, Cin, H, W = x.shape
         Cout = w.shape[0]
-        if g.dtype != x.dtype or not _cl(g):
+        if g.dtype != x.dtype or not cl(g):
             g = g.to(x.dtype).contiguous(memory_format=torch.channels_last)
         Ho, Wo = g.shape[2], g.shape[3]
         dx = dw = None
@@ -700,7 +691,7 @@ class _Conv1x1S2(torch.autograd.Function):
                 dx = torch.empty_like(x).fill_(0)
                 dx[:, :, ::2, ::2] = comp
         if ctx.needs_input_grad[1]:
-            if DOWN_WGRAD_PW and x.shape[1] % 64 == 0 and Cout % 64 == 0 and _cl(x):
+            if DOWN_WGRAD_PW and x.shape[1] % 64 == 0 and Cout % 64 == 0 and cl(x):
                 dw = pw_wgrad(g, x, w, stride=2, tag="pw_down_wgrad")       # csrc/pw.hip: rows of x picked at stride 2 in the operand load
             else:
                 dw = torch.ops.aten.convolution_backward(g, x, w, None, [2, 2], [0, 0], [1, 1], False, [0, 0], 1, [False, True, False])[1]
@@ -720,20 +711,20 @@ class _Conv3x3S2(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        if g.dtype != x.dtype or not _cl(g):
+        if g.dtype != x.dtype or not cl(g):
             g = g.to(x.dtype).contiguous(memory_format=torch.channels_last)
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = torch.ops.aten.convolution_backward(g, x, w, None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
         if ctx.needs_input_grad[1]:
-            dw = pw_wgrad(g, x, w if _cl(w) else w.contiguous(memory_format=torch.channels_last), stride=2, tag="pw_conv2_s2_wgrad")
+            dw = pw_wgrad(g, x, w if cl(w) else w.contiguous(memory_format=torch.channels_last), stride=2, tag="pw_conv2_s2_wgrad")
         return dx, dw
 
 
 def conv3x3_s2_ok(conv, x: Tensor, bias_ok: bool = False) -> bool:
     "``_Conv3x3S2`` applies (``bias_ok``: the caller adds the bias itself)."
     w = conv.weight
-    return (STRIDED_WGRAD_PW and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and _cl(x) and conv.kernel_size == (3, 3) and conv.stride == (2, 2)
+    return (STRIDED_WGRAD_PW and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and cl(x) and conv.kernel_size == (3, 3) and conv.stride == (2, 2)
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and (bias_ok or conv.bias is None) and conv.in_channels % 64 == 0
             and conv.out_channels % 64 == 0 and torch.is_grad_enabled() and x.shape[0] * x.shape[2] * x.shape[3] < (1 << 24))
 
@@ -742,7 +733,7 @@ def conv1x1(conv, x: Tensor) -> Tensor:
     """``conv(x)`` for a 1x1 / stride-1 ``nn.Conv2d`` on bf16 channels-last activations with every product on the fastest of
     MIOpen / hipBLASLt / csrc/pw.hip (``_Conv1x1``); anything else is ``conv(x)``."""
     w = conv.weight
-    if (MM_1X1 and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and _cl(x) and conv.kernel_size == (1, 1)
+    if (MM_1X1 and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and cl(x) and conv.kernel_size == (1, 1)
             and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1 and conv.in_channels % 64 == 0
             and conv.out_channels % 64 == 0 and torch.is_grad_enabled() and x.shape[0] * x.shape[2] * x.shape[3] < (1 << 24)):
         join, receiver = _join_of(x)
@@ -750,7 +741,7 @@ def conv1x1(conv, x: Tensor) -> Tensor:
         if receiver:
             join.recv_node = y.grad_fn
         return y
-    if (MM_1X1 and JOIN_GRADS and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and _cl(x) and conv.kernel_size == (1, 1)
+    if (MM_1X1 and JOIN_GRADS and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and cl(x) and conv.kernel_size == (1, 1)
             and conv.stride == (2, 2) and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None and conv.in_channels % 64 == 0
             and conv.out_channels % 64 == 0 and torch.is_grad_enabled() and x.requires_grad and getattr(x, "_rn_join", None) is not None
             and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.shape[0] * x.shape[2] * x.shape[3] < (1 << 24)):
@@ -774,7 +765,7 @@ _STEM_WS: Dict[tuple, Tensor] = {}
 
 
 def stem_fusable(conv, bn, x: Tensor) -> bool:
-    return (FUSED_STEM and x.is_cuda and x.dtype in H16 and _cl(x) and torch.is_grad_enabled() and x.shape[1] == 3 and
+    return (FUSED_STEM and x.is_cuda and x.dtype in H16 and cl(x) and torch.is_grad_enabled() and x.shape[1] == 3 and
             conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3) and conv.dilation == (1, 1) and
             conv.groups == 1 and conv.bias is None and conv.out_channels == 64 and conv.weight.dtype in H16 and
             bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None and bn.weight.dtype == torch.float32 and
@@ -790,12 +781,12 @@ class _StemFn(torch.autograd.Function):
     def forward(ctx, bn, pool, x, w, gamma, beta):
         B, _, H, W = x.shape
         dev = x.device
-        st = _stream(dev)
+        st = stream_on(dev)
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         # xp: the zero-bordered NHWC4 copy of the image; the weight gradient reads it again, so it belongs to this call
         ws = (torch.empty((lib.rn_stem_padded_bytes(B, H, W),), dtype=torch.uint8, device=dev),
               torch.empty((64 * 7 * 32,), dtype=x.dtype, device=dev))
-        wc = w if _cl(w) else w.contiguous(memory_format=torch.channels_last)
+        wc = w if cl(w) else w.contiguous(memory_format=torch.channels_last)
         z = torch.empty((B, 64, Ho, Wo), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
         nb = lib.rn_stem_partial_rows(B, H, W)
         partial = torch.empty((nb * 2 * 64,), dtype=torch.float32, device=dev)
@@ -822,10 +813,10 @@ class _StemFn(torch.autograd.Function):
     def backward(ctx, da):
         x, w, gamma, z, stats, xp, arg = ctx.saved_tensors
         dev = z.device
-        st = _stream(dev)
+        st = stream_on(dev)
         Cc = 64
         M = z.shape[0] * z.shape[2] * z.shape[3]
-        if not (da.dtype == z.dtype and _cl(da)):
+        if not (da.dtype == z.dtype and cl(da)):
             da = da.to(z.dtype).contiguous(memory_format=torch.channels_last)
         gr = torch.empty((5 * Cc,), dtype=torch.float32, device=dev)
         sp = stats.data_ptr()
@@ -884,7 +875,7 @@ STEM_EVAL = True
 
 
 def stem_eval_ok(conv, pool, x: Tensor, w: Tensor) -> bool:
-    return (STEM_EVAL and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and _cl(x) and x.shape[1] == 3 and
+    return (STEM_EVAL and x.is_cuda and x.dtype in H16 and w.dtype == x.dtype and x.dim() == 4 and cl(x) and x.shape[1] == 3 and
             conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1 and
             conv.out_channels == 64 and pool is not None and pool.kernel_size == 3 and pool.stride == 2 and pool.padding == 1 and
             pool.dilation == 1 and not pool.ceil_mode and not pool.return_indices and
@@ -895,11 +886,11 @@ def stem_eval(x: Tensor, w: Tensor, bias: Tensor) -> Tensor:
     "``maxpool3x3s2(relu(conv7x7s2(x, w) + bias))`` on csrc/stem.hip + the pooling kernel (w: the folded bf16 weight, bias f32 [64])."
     B, _, H, W = x.shape
     dev = x.device
-    st = _stream(dev)
+    st = stream_on(dev)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     xp = torch.empty((lib.rn_stem_padded_bytes(B, H, W),), dtype=torch.uint8, device=dev)
     wk = torch.empty((64 * 7 * 32,), dtype=x.dtype, device=dev)
-    wc = w if _cl(w) else w.contiguous(memory_format=torch.channels_last)
+    wc = w if cl(w) else w.contiguous(memory_format=torch.channels_last)
     z = torch.empty((B, 64, Ho, Wo), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
     partial = torch.empty((lib.rn_stem_partial_rows(B, H, W) * 2 * 64,), dtype=torch.float32, device=dev)      # (the kernel's statistics: unused here)
     PW_FLOP["stem_fwd"] = 2.0 * B * Ho * Wo * 64 * 147
