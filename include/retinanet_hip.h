@@ -500,6 +500,13 @@ int rn_gt_flip_scale_many(const void *const *boxes, const int64_t *counts, int B
                           const uint8_t *flags, float *out_boxes, int64_t rows, void *stream);
 int rn_gt_flip_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const float *ratios,
                             const uint8_t *flags, int B, int64_t rows, int64_t max_per_image, void *stream);
+/* The same two kernels for a resize decided on the device (augment.RandomShortSide): ratios_dev is DEVICE float[2B] = (rh, rw), written by
+ * rn_short_side_draw in the same stream, and flags_or_null may be NULL (nothing flips).  Bit-identical to the host-ratio forms given the
+ * same values; every other rule is theirs. */
+int rn_gt_flip_scale_many_dev(const void *const *boxes, const int64_t *counts, int B, const float *widths, const float *ratios_dev,
+                              const uint8_t *flags_or_null, float *out_boxes, int64_t rows, void *stream);
+int rn_gt_flip_scale_packed_dev(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const float *ratios_dev,
+                                const uint8_t *flags_or_null, int B, int64_t rows, int64_t max_per_image, void *stream);
 /* n widening copies dsts[i] (f32) <- srcs[i] (src_dtype: RN_BF16 or RN_F16), counts[i] elements each, one launch per 64: the
  * gather of 16-bit parameter gradients into the fp32 buckets of the gradient exchange (no reference analogue: Lightning's DDP
  * exchanges fp32 gradients of fp32 parameters).  HOST arrays. */
@@ -867,6 +874,13 @@ int rn_transform_batch(const void *const *images, const int32_t *in_hw, const in
 int rn_transform_batch_flip(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
                             const float mean[3], const float std[3], int Hp, int Wp,
                             void *out, int out_dtype, int channels_last, const uint8_t *flags, void *stream);
+/* The same launch with the output sizes read from the device: out_hw_dev is DEVICE i32[B][2] = (h, w) after the resize (rn_short_side_draw
+ * writes it in the same stream), flags_or_null the flip's DEVICE flags or NULL.  Hp / Wp stay host values: a size above the canvas is
+ * clamped to it in the kernel (nothing is written outside out), a size <= 0 leaves the image all padding.  Per output pixel the code
+ * is rn_transform_batch's: bit-identical to rn_transform_batch / rn_transform_batch_flip called with the same sizes on the host. */
+int rn_transform_batch_dev(const void *const *images, const int32_t *in_hw, int B, const float mean[3], const float std[3],
+                           int Hp, int Wp, void *out, int out_dtype, int channels_last, const int32_t *out_hw_dev,
+                           const uint8_t *flags_or_null, void *stream);
 
 /* ---- train-time augmentation: the horizontal-flip decision, drawn on the device ------------------------------------
  * rn_hflip_state: a DEVICE block (8-byte aligned) owned by augment.RandomHorizontalFlip, written by the host outside any capture.
@@ -876,6 +890,19 @@ int rn_transform_batch_flip(const void *const *images, const int32_t *in_hw, con
  * so p = 0 never flips and p = 1 always does.  Captured into a hipGraph, every replay draws anew. */
 typedef struct rn_hflip_state { uint64_t seed; int64_t counter; float p; int32_t reserved; } rn_hflip_state;
 int rn_hflip_draw(rn_hflip_state *state, int B, uint8_t *flags, void *stream);
+
+/* ---- train-time augmentation: the short side of multi-scale training, drawn on the device ---------------------------
+ * rn_short_side_state: a DEVICE block (8-byte aligned) owned by augment.RandomShortSide, written by the host outside any capture:
+ * n candidate short sides (1 <= n <= RN_SHORT_SIDE_MAX; the kernel clamps n to that range).
+ * rn_short_side_draw: for every image b < B, with u the hash of rn_hflip_draw on (seed ^ 0x5CA1E5CA1E5CA1E5, counter, b),
+ *   short = sizes[min(int(u * n), n - 1)];  scale = short / min(h, w);  if (max(h, w) * scale > max_size) scale = max_size / max(h, w);
+ *   out_hw[b] = (floor(h * scale), floor(w * scale))                    (double, this order: torchvision's GeneralizedRCNNTransform)
+ *   ratios[2b], ratios[2b + 1] = float(nh) / float(h), float(nw) / float(w)                              (fp32, correctly rounded)
+ * then counter += 1.  in_hw: HOST i32[B][2] = (h, w), carried in the kernel arguments, one single-wave launch per 64 images (only the
+ * last one advances the counter); out_hw: DEVICE i32[B][2]; ratios: DEVICE f32[2B].  Captured into a hipGraph, every replay draws anew. */
+#define RN_SHORT_SIDE_MAX 16
+typedef struct rn_short_side_state { uint64_t seed; int64_t counter; int32_t n; int32_t reserved; int32_t sizes[RN_SHORT_SIDE_MAX]; } rn_short_side_state;
+int rn_short_side_draw(rn_short_side_state *state, const int32_t *in_hw, int max_size, int B, int32_t *out_hw, float *ratios, void *stream);
 
 /* ---- K6 nms (op boundary) ---------------------------------------------------
  * Replaces torchvision.ops.nms as called at retinanet/models.py:210, batched over

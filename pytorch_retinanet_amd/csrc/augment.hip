@@ -1,4 +1,4 @@
-// Train-time augmentation decisions drawn on the device (augment.RandomHorizontalFlip).
+// Train-time augmentation decisions drawn on the device (augment.RandomHorizontalFlip, augment.RandomShortSide).
 //
 // The reference's only training augmentation is a random horizontal flip with p = 0.5 (hparams.yaml transforms,
 // albumentations.HorizontalFlip; RandomHorizontalFlip(prob=0.5) for COCO), decided per image on the host.  Here the decision is
@@ -18,6 +18,24 @@
 // and the comparison is in fp32, so p = 0 never flips and p = 1 always does.  augment.RandomHorizontalFlip.draw restates this in
 // Python.  The kernel is one wave: every lane reads the block (one uniform load), lane 0 writes counter + 1 with an ordinary
 // global store after that read, which its value depends on.
+//
+// Multi-scale training (torchvision's min_size tuple: one short side per image and step) is drawn the same way, so that ONE captured
+// graph serves every scale over a fixed canvas:
+//
+//   rn_short_side_draw   out_hw[b], ratios[b] for b < B from u(seed ^ salt, counter, b), then counter += 1
+//
+// with the block rn_short_side_state (seed, counter, n, sizes[16]):
+//
+//   idx   = min(int(u * n), n - 1)                      (u has 24 bits and n <= 16: u * n is exact in fp32)
+//   short = sizes[idx]
+//   scale = short / min(h, w);  if (max(h, w) * scale > max_size) scale = max_size / max(h, w)          (double, this order)
+//   nh    = floor(h * scale),  nw = floor(w * scale)                                                    (double)
+//   rh    = float(nh) / float(h),  rw = float(nw) / float(w)                                            (fp32, correctly rounded)
+//
+// i.e. transform.GeneralizedRCNNTransform._scale_for, the two floors of its resize and transform._ratios; this file is built without
+// FMA contraction and with IEEE division.  The salt keeps a flip and a jitter that share a seed from tying small sizes to flipped
+// images.  The input sizes are host values carried in the kernel arguments (64 images per launch; lane i serves image i); a batch
+// of more than 64 images takes several launches that read the SAME counter, and only the last one advances it.
 #include "rn_common.hpp"
 
 namespace {
@@ -42,6 +60,38 @@ __global__ __launch_bounds__(HF_BLOCK) void hflip_draw_kernel(rn_hflip_state *st
     if (threadIdx.x == 0) st->counter = counter + 1;
 }
 
+constexpr int SS_MAX_IMAGES = 64;   // per launch (kernel-argument table): one lane per image
+constexpr uint64_t SS_SALT = 0x5CA1E5CA1E5CA1E5ull;
+static_assert(SS_MAX_IMAGES == HF_BLOCK, "one lane per image of a launch");
+
+struct ShortSideTable { int32_t ih[SS_MAX_IMAGES], iw[SS_MAX_IMAGES]; };
+
+__global__ __launch_bounds__(HF_BLOCK) void short_side_draw_kernel(rn_short_side_state *st, const ShortSideTable t, const int cnt, const int base,
+                                                                  const int max_size, const int advance, int32_t *__restrict__ out_hw,
+                                                                  float *__restrict__ ratios)
+{
+    const uint64_t seed = st->seed ^ SS_SALT;
+    const int64_t counter = st->counter;
+    int n = st->n;
+    n = n < 1 ? 1 : (n > RN_SHORT_SIDE_MAX ? RN_SHORT_SIDE_MAX : n);          // (device data: the index below stays inside sizes[])
+    const int i = (int)threadIdx.x;
+    if (i < cnt) {
+        const int b = base + i;
+        int idx = (int)(hflip_u(seed, counter, b) * (float)n);
+        idx = idx < n - 1 ? idx : n - 1;
+        const int h = t.ih[i], w = t.iw[i];
+        const double lo = (double)(h < w ? h : w), hi = (double)(h < w ? w : h);
+        double scale = (double)st->sizes[idx] / lo;
+        if (hi * scale > (double)max_size) scale = (double)max_size / hi;
+        const int nh = (int)floor((double)h * scale), nw = (int)floor((double)w * scale);
+        out_hw[2 * b] = nh;
+        out_hw[2 * b + 1] = nw;
+        ratios[2 * b] = (float)nh / (float)h;
+        ratios[2 * b + 1] = (float)nw / (float)w;
+    }
+    if (advance && threadIdx.x == 0) st->counter = counter + 1;
+}
+
 }  // namespace
 
 RN_API int rn_hflip_draw(rn_hflip_state *state, int B, uint8_t *flags, void *stream)
@@ -50,5 +100,27 @@ RN_API int rn_hflip_draw(rn_hflip_state *state, int B, uint8_t *flags, void *str
     if (!rn::aligned(state, 8)) return RN_EALIGN;
     hipLaunchKernelGGL(hflip_draw_kernel, dim3(1), dim3(HF_BLOCK), 0, (hipStream_t)stream, state, B, flags);
     RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
+RN_API int rn_short_side_draw(rn_short_side_state *state, const int32_t *in_hw, int max_size, int B, int32_t *out_hw, float *ratios,
+                              void *stream)
+{
+    if (!state || !in_hw || !out_hw || !ratios || B <= 0 || max_size <= 0) return RN_EINVAL;
+    if (!rn::aligned(state, 8) || !rn::aligned(out_hw, 4) || !rn::aligned(ratios, 4)) return RN_EALIGN;
+    for (int b = 0; b < B; ++b)
+        if (in_hw[2 * b] <= 0 || in_hw[2 * b + 1] <= 0) return RN_EINVAL;
+    for (int base = 0; base < B; base += SS_MAX_IMAGES) {
+        const int cnt = (B - base) < SS_MAX_IMAGES ? (B - base) : SS_MAX_IMAGES;
+        ShortSideTable t;
+        for (int i = 0; i < SS_MAX_IMAGES; ++i) {
+            t.ih[i] = i < cnt ? in_hw[2 * (base + i)] : 1;
+            t.iw[i] = i < cnt ? in_hw[2 * (base + i) + 1] : 1;
+        }
+        // (launches of one stream run in order: the earlier ones read the counter that the last one advances)
+        hipLaunchKernelGGL(short_side_draw_kernel, dim3(1), dim3(HF_BLOCK), 0, (hipStream_t)stream, state, t, cnt, base, max_size,
+                           base + cnt == B ? 1 : 0, out_hw, ratios);
+        RN_LAUNCH_CHECK();
+    }
     return RN_OK;
 }

@@ -15,6 +15,10 @@
 //                       and counts by value, like rn_gt_stage) and packs them into a fresh buffer; the _packed form is
 //                       rn_gt_scale_packed plus widths and flags.  The flags are device data written by rn_hflip_draw inside the
 //                       same captured step, so the decision never reaches the host.
+//   rn_gt_flip_scale_many_dev / rn_gt_flip_scale_packed_dev
+//                       the same two kernels with the ratios read from DEVICE memory (f32[2B] = (rh, rw), written by rn_short_side_draw
+//                       inside the same captured step: augment.RandomShortSide) and the flags optional (null: nothing flips).  The
+//                       arithmetic on a row is flip_scale either way: bit-identical to the host-ratio forms given the same values.
 // All kernels index their argument tables by blockIdx only (a per-lane index into the argument segment becomes a vector load of
 // the table; CHANGELOG, the compiler's treatment of hand-written loops, item 2).
 #include "rn_common.hpp"
@@ -82,27 +86,31 @@ struct FlipManyTable {
     float w[GT_MAX], rh[GT_MAX], rw[GT_MAX];
 };
 
+// DEV: rh / rw of image base + i from ``ratios`` (device) instead of the table, and ``flags`` may be null
+template <bool DEV>
 __global__ __launch_bounds__(GT_BLOCK) void gt_flip_scale_many_kernel(const FlipManyTable t, const uint8_t *__restrict__ flags,
-                                                                     rn::f32x4 *__restrict__ out, int base)
+                                                                     const float *__restrict__ ratios, rn::f32x4 *__restrict__ out, int base)
 {
     const int i = blockIdx.y;
     const rn::f32x4 *__restrict__ sb = t.boxes[i];
     const int32_t n = t.count[i], o = t.off[i];
-    const float w = t.w[i], rh = t.rh[i], rw = t.rw[i];
-    const bool flip = flags[base + i] != 0;
+    const float w = t.w[i], rh = DEV ? ratios[2 * (base + i)] : t.rh[i], rw = DEV ? ratios[2 * (base + i) + 1] : t.rw[i];
+    const bool flip = DEV ? (flags != nullptr && flags[base + i] != 0) : flags[base + i] != 0;
     for (int32_t r = (int32_t)blockIdx.x * GT_BLOCK + (int32_t)threadIdx.x; r < n; r += (int32_t)gridDim.x * GT_BLOCK)
         out[o + r] = flip_scale(sb[r], flip, w, rh, rw);
 }
 
 struct FlipScaleTable { float w[GT_MAX]; float rh[GT_MAX]; float rw[GT_MAX]; };
 
+template <bool DEV>
 __global__ __launch_bounds__(GT_BLOCK) void gt_flip_scale_kernel(const FlipScaleTable t, const uint8_t *__restrict__ flags,
-                                                                const rn::f32x4 *__restrict__ in, rn::f32x4 *__restrict__ out,
-                                                                const int32_t *__restrict__ gt_off, int base, int32_t rows)
+                                                                const float *__restrict__ ratios, const rn::f32x4 *__restrict__ in,
+                                                                rn::f32x4 *__restrict__ out, const int32_t *__restrict__ gt_off, int base,
+                                                                int32_t rows)
 {
     const int i = blockIdx.y;
-    const float w = t.w[i], rh = t.rh[i], rw = t.rw[i];
-    const bool flip = flags[base + i] != 0;
+    const float w = t.w[i], rh = DEV ? ratios[2 * (base + i)] : t.rh[i], rw = DEV ? ratios[2 * (base + i) + 1] : t.rw[i];
+    const bool flip = DEV ? (flags != nullptr && flags[base + i] != 0) : flags[base + i] != 0;
     int32_t lo = gt_off[base + i], hi = gt_off[base + i + 1];
     lo = lo < 0 ? 0 : (lo > rows ? rows : lo);
     hi = hi < lo ? lo : (hi > rows ? rows : hi);
@@ -185,12 +193,15 @@ RN_API int rn_gt_scale_packed(const float *gt_boxes, float *out_boxes, const int
     return RN_OK;
 }
 
-RN_API int rn_gt_flip_scale_many(const void *const *boxes, const int64_t *counts, int B, const float *widths, const float *ratios,
-                                 const uint8_t *flags, float *out_boxes, int64_t rows, void *stream)
+namespace {
+
+// ratios: HOST float[2B], or null with ratios_dev (DEVICE float[2B]) in their place; flags may be null only with ratios_dev
+int flip_scale_many(const void *const *boxes, const int64_t *counts, int B, const float *widths, const float *ratios, const float *ratios_dev,
+                    const uint8_t *flags, float *out_boxes, int64_t rows, void *stream)
 {
-    if (!boxes || !counts || !widths || !ratios || !flags || B <= 0 || rows < 0) return RN_EINVAL;
+    if (!boxes || !counts || !widths || (!ratios == !ratios_dev) || (!flags && !ratios_dev) || B <= 0 || rows < 0) return RN_EINVAL;
     if (rows > 0 && !out_boxes) return RN_EINVAL;
-    if (out_boxes && !rn::aligned(out_boxes, 16)) return RN_EALIGN;
+    if ((out_boxes && !rn::aligned(out_boxes, 16)) || (ratios_dev && !rn::aligned(ratios_dev, 4))) return RN_EALIGN;
     int64_t total = 0;
     for (int b = 0; b < B; ++b) {
         const int64_t c = counts[b];
@@ -217,25 +228,31 @@ RN_API int rn_gt_flip_scale_many(const void *const *boxes, const int64_t *counts
             t.count[i] = (int32_t)c;
             t.off[i] = (int32_t)off;
             t.w[i] = on ? widths[base + i] : 0.0f;
-            t.rh[i] = on ? ratios[2 * (base + i)] : 1.0f;
-            t.rw[i] = on ? ratios[2 * (base + i) + 1] : 1.0f;
+            t.rh[i] = on && ratios ? ratios[2 * (base + i)] : 1.0f;
+            t.rw[i] = on && ratios ? ratios[2 * (base + i) + 1] : 1.0f;
             off += c;
             if (c > most) most = c;
         }
-        hipLaunchKernelGGL(gt_flip_scale_many_kernel, dim3((unsigned)grid_x(most), (unsigned)cnt), dim3(GT_BLOCK), 0, st, t, flags,
-                           (rn::f32x4 *)out_boxes, base);
+        const dim3 grid((unsigned)grid_x(most), (unsigned)cnt);
+        if (ratios_dev)
+            hipLaunchKernelGGL(gt_flip_scale_many_kernel<true>, grid, dim3(GT_BLOCK), 0, st, t, flags, ratios_dev, (rn::f32x4 *)out_boxes, base);
+        else
+            hipLaunchKernelGGL(gt_flip_scale_many_kernel<false>, grid, dim3(GT_BLOCK), 0, st, t, flags, ratios_dev, (rn::f32x4 *)out_boxes, base);
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
 }
 
-RN_API int rn_gt_flip_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const float *ratios,
-                                   const uint8_t *flags, int B, int64_t rows, int64_t max_per_image, void *stream)
+int flip_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const float *ratios,
+                      const float *ratios_dev, const uint8_t *flags, int B, int64_t rows, int64_t max_per_image, void *stream)
 {
-    if (!gt_off || !widths || !ratios || !flags || B <= 0 || rows < 0 || rows > INT32_MAX || max_per_image < 0) return RN_EINVAL;
+    if (!gt_off || !widths || (!ratios == !ratios_dev) || (!flags && !ratios_dev) || B <= 0 || rows < 0 || rows > INT32_MAX || max_per_image < 0)
+        return RN_EINVAL;
     if (rows > 0 && (!gt_boxes || !out_boxes)) return RN_EINVAL;
     if (rows > 0 && gt_boxes == out_boxes) return RN_EINVAL;
-    if (!rn::aligned(gt_off, 4) || (gt_boxes && !rn::aligned(gt_boxes, 16)) || (out_boxes && !rn::aligned(out_boxes, 16))) return RN_EALIGN;
+    if (!rn::aligned(gt_off, 4) || (gt_boxes && !rn::aligned(gt_boxes, 16)) || (out_boxes && !rn::aligned(out_boxes, 16)) ||
+        (ratios_dev && !rn::aligned(ratios_dev, 4)))
+        return RN_EALIGN;
     if (rows == 0) return RN_OK;
     hipStream_t st = (hipStream_t)stream;
     for (int base = 0; base < B; base += GT_MAX) {
@@ -243,12 +260,48 @@ RN_API int rn_gt_flip_scale_packed(const float *gt_boxes, float *out_boxes, cons
         FlipScaleTable t;
         for (int i = 0; i < GT_MAX; ++i) {
             t.w[i] = i < cnt ? widths[base + i] : 0.0f;
-            t.rh[i] = i < cnt ? ratios[2 * (base + i)] : 1.0f;
-            t.rw[i] = i < cnt ? ratios[2 * (base + i) + 1] : 1.0f;
+            t.rh[i] = i < cnt && ratios ? ratios[2 * (base + i)] : 1.0f;
+            t.rw[i] = i < cnt && ratios ? ratios[2 * (base + i) + 1] : 1.0f;
         }
-        hipLaunchKernelGGL(gt_flip_scale_kernel, dim3((unsigned)grid_x(max_per_image), (unsigned)cnt), dim3(GT_BLOCK), 0, st, t, flags,
-                           (const rn::f32x4 *)gt_boxes, (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
+        const dim3 grid((unsigned)grid_x(max_per_image), (unsigned)cnt);
+        if (ratios_dev)
+            hipLaunchKernelGGL(gt_flip_scale_kernel<true>, grid, dim3(GT_BLOCK), 0, st, t, flags, ratios_dev, (const rn::f32x4 *)gt_boxes,
+                               (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
+        else
+            hipLaunchKernelGGL(gt_flip_scale_kernel<false>, grid, dim3(GT_BLOCK), 0, st, t, flags, ratios_dev, (const rn::f32x4 *)gt_boxes,
+                               (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
+}
+
+}  // namespace
+
+RN_API int rn_gt_flip_scale_many(const void *const *boxes, const int64_t *counts, int B, const float *widths, const float *ratios,
+                                 const uint8_t *flags, float *out_boxes, int64_t rows, void *stream)
+{
+    if (!ratios || !flags) return RN_EINVAL;
+    return flip_scale_many(boxes, counts, B, widths, ratios, nullptr, flags, out_boxes, rows, stream);
+}
+
+RN_API int rn_gt_flip_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const float *ratios,
+                                   const uint8_t *flags, int B, int64_t rows, int64_t max_per_image, void *stream)
+{
+    if (!ratios || !flags) return RN_EINVAL;
+    return flip_scale_packed(gt_boxes, out_boxes, gt_off, widths, ratios, nullptr, flags, B, rows, max_per_image, stream);
+}
+
+RN_API int rn_gt_flip_scale_many_dev(const void *const *boxes, const int64_t *counts, int B, const float *widths, const float *ratios_dev,
+                                     const uint8_t *flags_or_null, float *out_boxes, int64_t rows, void *stream)
+{
+    if (!ratios_dev) return RN_EINVAL;
+    return flip_scale_many(boxes, counts, B, widths, nullptr, ratios_dev, flags_or_null, out_boxes, rows, stream);
+}
+
+RN_API int rn_gt_flip_scale_packed_dev(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths,
+                                       const float *ratios_dev, const uint8_t *flags_or_null, int B, int64_t rows, int64_t max_per_image,
+                                       void *stream)
+{
+    if (!ratios_dev) return RN_EINVAL;
+    return flip_scale_packed(gt_boxes, out_boxes, gt_off, widths, nullptr, ratios_dev, flags_or_null, B, rows, max_per_image, stream);
 }

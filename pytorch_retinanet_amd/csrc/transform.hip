@@ -20,6 +20,11 @@
 // rn_transform_batch_flip is the same launch with a per-image flag (device, uint8[B], rn_hflip_draw writes it inside a captured
 // step): a flagged image's taps are computed as above and then read from the mirrored source columns iw-1-xa / iw-1-xb, i.e.
 // exactly what rn_transform_batch computes on img.flip(-1) (the reference flips the raw image before the model's transform).
+//
+// rn_transform_batch_dev is the same launch again with the output sizes read from DEVICE memory (i32[B][2], rn_short_side_draw writes
+// them inside a captured step: augment.RandomShortSide) instead of the kernel-argument table; the canvas Hp x Wp stays a host value
+// and a size read from the device is clamped to it, so nothing it holds can make a thread write outside the batch.  Everything after
+// the two loads is the code above: bit-identical to rn_transform_batch / _flip called with the same sizes on the host.
 #include "rn_common.hpp"
 
 namespace {
@@ -34,6 +39,7 @@ struct TransformArgs {
     int32_t B, Hp, Wp;
     void *out;                         // first image of this launch
     const uint8_t *flags;              // FLIP: this launch's first image's flag (device)
+    const int32_t *out_hw;             // DEV: this launch's first image's (oh, ow) (device); oh / ow above are unused
 };
 
 __device__ __forceinline__ void tap_axis(const int dst, const int in, const int out, int &i0, int &i1, float &l0, float &l1)
@@ -69,14 +75,21 @@ template <> struct store4<RN_F16> {
     }
 };
 
-template <int DT, bool NHWC, bool FLIP>
+template <int DT, bool NHWC, bool FLIP, bool DEV>
 __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArgs a)
 {
     const int b = blockIdx.z;
     const int y = blockIdx.y;
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * TB_PX;
     if (x0 >= a.Wp) return;
-    const int ih = a.ih[b], iw = a.iw[b], oh = a.oh[b], ow = a.ow[b];
+    const int ih = a.ih[b], iw = a.iw[b];
+    int oh, ow;
+    if (DEV) {                                                  // device data: clamped to the canvas (<= 0: the image is all padding)
+        oh = a.out_hw[2 * b]; ow = a.out_hw[2 * b + 1];
+        oh = oh < a.Hp ? oh : a.Hp; ow = ow < a.Wp ? ow : a.Wp;
+    } else {
+        oh = a.oh[b]; ow = a.ow[b];
+    }
     const bool flip = FLIP && a.flags[b] != 0;           // source column c of the flipped image is column iw-1-c of img
     float v[3][TB_PX];
 #pragma unroll
@@ -131,17 +144,20 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
     }
 }
 
-int transform_batch(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B, const float mean[3],
-                    const float std[3], int Hp, int Wp, void *out, int out_dtype, int channels_last, const uint8_t *flags, void *stream)
+// out_hw: HOST sizes, or null with out_hw_dev (DEVICE i32[B][2]) in their place
+int transform_batch(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, const int32_t *out_hw_dev, int B,
+                    const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype, int channels_last,
+                    const uint8_t *flags, void *stream)
 {
-    if (!images || !in_hw || !out_hw || !mean || !std || !out || B <= 0 || Hp <= 0 || Wp <= 0) return RN_EINVAL;
+    if (!images || !in_hw || (!out_hw == !out_hw_dev) || !mean || !std || !out || B <= 0 || Hp <= 0 || Wp <= 0) return RN_EINVAL;
+    if (out_hw_dev && !rn::aligned(out_hw_dev, 4)) return RN_EALIGN;
     if (out_dtype != RN_F32 && out_dtype != RN_BF16 && out_dtype != RN_F16) return RN_EINVAL;
     if (Wp % TB_PX) return RN_EUNSUPPORTED;
     if (Hp > 65535) return RN_EUNSUPPORTED;                     // gridDim.y
     if (!rn::aligned(out, 16)) return RN_EALIGN;
     for (int b = 0; b < B; ++b) {
-        if (!images[b] || in_hw[2 * b] <= 0 || in_hw[2 * b + 1] <= 0 || out_hw[2 * b] <= 0 || out_hw[2 * b + 1] <= 0) return RN_EINVAL;
-        if (out_hw[2 * b] > Hp || out_hw[2 * b + 1] > Wp) return RN_EINVAL;
+        if (!images[b] || in_hw[2 * b] <= 0 || in_hw[2 * b + 1] <= 0) return RN_EINVAL;
+        if (out_hw && (out_hw[2 * b] <= 0 || out_hw[2 * b + 1] <= 0 || out_hw[2 * b] > Hp || out_hw[2 * b + 1] > Wp)) return RN_EINVAL;
         if (!rn::aligned(images[b], 4)) return RN_EALIGN;
         if (std[0] == 0.0f || std[1] == 0.0f || std[2] == 0.0f) return RN_EINVAL;
     }
@@ -153,20 +169,22 @@ int transform_batch(const void *const *images, const int32_t *in_hw, const int32
         for (int i = 0; i < a.B; ++i) {
             a.img[i] = (const float *)images[b0 + i];
             a.ih[i] = in_hw[2 * (b0 + i)]; a.iw[i] = in_hw[2 * (b0 + i) + 1];
-            a.oh[i] = out_hw[2 * (b0 + i)]; a.ow[i] = out_hw[2 * (b0 + i) + 1];
+            a.oh[i] = out_hw ? out_hw[2 * (b0 + i)] : 0; a.ow[i] = out_hw ? out_hw[2 * (b0 + i) + 1] : 0;
         }
         for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std[c]; }
         a.Hp = Hp; a.Wp = Wp;
         a.out = (unsigned char *)out + (size_t)b0 * 3 * Hp * Wp * esz;
         a.flags = flags ? flags + b0 : nullptr;
+        a.out_hw = out_hw_dev ? out_hw_dev + 2 * b0 : nullptr;
         const dim3 blk(256), grid((unsigned)((Wp / TB_PX + 255) / 256), (unsigned)Hp, (unsigned)a.B);
+#define RN_TB_LAUNCH_L(DT, FLIP, DEV)                                                                                 \
+        if (channels_last) hipLaunchKernelGGL((transform_batch_kernel<DT, true, FLIP, DEV>), grid, blk, 0, st, a);    \
+        else hipLaunchKernelGGL((transform_batch_kernel<DT, false, FLIP, DEV>), grid, blk, 0, st, a)
 #define RN_TB_LAUNCH(DT)                                                                                              \
-        if (flags) {                                                                                                  \
-            if (channels_last) hipLaunchKernelGGL((transform_batch_kernel<DT, true, true>), grid, blk, 0, st, a);     \
-            else hipLaunchKernelGGL((transform_batch_kernel<DT, false, true>), grid, blk, 0, st, a);                  \
+        if (out_hw_dev) {                                                                                             \
+            if (flags) { RN_TB_LAUNCH_L(DT, true, true); } else { RN_TB_LAUNCH_L(DT, false, true); }                  \
         } else {                                                                                                      \
-            if (channels_last) hipLaunchKernelGGL((transform_batch_kernel<DT, true, false>), grid, blk, 0, st, a);    \
-            else hipLaunchKernelGGL((transform_batch_kernel<DT, false, false>), grid, blk, 0, st, a);                 \
+            if (flags) { RN_TB_LAUNCH_L(DT, true, false); } else { RN_TB_LAUNCH_L(DT, false, false); }                \
         }
         switch (out_dtype) {
             case RN_F32: RN_TB_LAUNCH(RN_F32); break;
@@ -174,6 +192,7 @@ int transform_batch(const void *const *images, const int32_t *in_hw, const int32
             default: RN_TB_LAUNCH(RN_F16); break;
         }
 #undef RN_TB_LAUNCH
+#undef RN_TB_LAUNCH_L
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
@@ -185,13 +204,22 @@ RN_API int rn_transform_batch(const void *const *images, const int32_t *in_hw, c
                               const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype,
                               int channels_last, void *stream)
 {
-    return transform_batch(images, in_hw, out_hw, B, mean, std, Hp, Wp, out, out_dtype, channels_last, nullptr, stream);
+    if (!out_hw) return RN_EINVAL;
+    return transform_batch(images, in_hw, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, nullptr, stream);
 }
 
 RN_API int rn_transform_batch_flip(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
                                    const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype,
                                    int channels_last, const uint8_t *flags, void *stream)
 {
-    if (!flags) return RN_EINVAL;
-    return transform_batch(images, in_hw, out_hw, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags, stream);
+    if (!flags || !out_hw) return RN_EINVAL;
+    return transform_batch(images, in_hw, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags, stream);
+}
+
+RN_API int rn_transform_batch_dev(const void *const *images, const int32_t *in_hw, int B, const float mean[3], const float std[3],
+                                  int Hp, int Wp, void *out, int out_dtype, int channels_last, const int32_t *out_hw_dev,
+                                  const uint8_t *flags_or_null, void *stream)
+{
+    if (!out_hw_dev) return RN_EINVAL;
+    return transform_batch(images, in_hw, nullptr, out_hw_dev, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags_or_null, stream);
 }

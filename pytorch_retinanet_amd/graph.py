@@ -41,6 +41,9 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     A weight average (``optimizer.weight_ema``, ``optim.WeightEMA``) is keyed by the installed object as well: its update is part of
     ``optimizer.step`` and reads its factor and count from the object's device block, so a graph captured without one is never
     replayed once one is installed, and the reverse; without one the key is the plain one.
+    Multi-scale training (``net.transform.scale_jitter``, ``augment.RandomShortSide``) is keyed by the installed object too: the short
+    sides are drawn inside the step from the object's device block and the padded canvas depends on the image shapes alone, so one
+    graph replays while the scales vary (the host-side draw from a ``min_size`` tuple makes nearly every batch a new signature).
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -407,7 +410,12 @@ class CapturedTrainStep:
         # the weight average (optim.WeightEMA on a master optimizer): its update is part of the optimizer step and reads its factor and
         # count from the object's device block -- the object again; installing or removing one re-captures.  Without one nothing is added.
         ema = getattr(self.optimizer, "weight_ema", None)
-        return key if ema is None else key + (("weight_ema", ema),)
+        if ema is not None:
+            key = key + (("weight_ema", ema),)
+        # the short side drawn on the device (transform.scale_jitter): the draw is part of the step and reads seed / counter / sizes from
+        # the object's device block, and the canvas follows from the image shapes -- the object again.  Without one nothing is added.
+        jitter = getattr(getattr(self.net, "transform", None), "scale_jitter", None)
+        return key if jitter is None else key + (("scale_jitter", jitter),)
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."

@@ -224,7 +224,8 @@ class SimpleTrainer:
     def __init__(self, max_epochs: int = 1, device: Optional[str] = None, precision: str = "bf16",
                  channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True,
                  gt_capacity=None, gradient_clip_val: float = 0.0, accumulate_grad_batches: int = 1,
-                 weight_ema_decay: float = 0.0, weight_ema_warmup: float = 0.0):
+                 weight_ema_decay: float = 0.0, weight_ema_warmup: float = 0.0, device_scale_jitter: bool = False,
+                 scale_jitter_seed: int = 0):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
@@ -258,7 +259,15 @@ class SimpleTrainer:
         optimizer (``self.weight_ema``): the update runs on the device inside ``optimizer.step`` (once per optimizer step, skipped with a
         step the loss scaler skips, identical on every rank) and capture stays on.  Validation inside ``fit`` and ``test()`` after it
         run inside ``weight_ema.swapped(...)``; training always resumes on the training weights.  BatchNorm running statistics are not
-        averaged.  Any other optimizer or device raises: there is no CPU fallback."""
+        averaged.  Any other optimizer or device raises: there is no CPU fallback.
+
+        ``device_scale_jitter`` / ``scale_jitter_seed`` (off by default; left False, an optional ``trainer.device_scale_jitter`` in the
+        hparams is honoured): multi-scale training inside the captured step.  When the model's ``min_size`` has more than one entry,
+        ``fit`` installs ``augment.RandomShortSide(min_size, scale_jitter_seed)`` as ``net.transform.scale_jitter`` before the first step
+        (``self.scale_jitter``; under ``torch.distributed`` rank r draws from seed + r): the short side of every image is drawn on the
+        device over a canvas sized for the largest entry, so one graph replays while the scales vary.  Without it a ``min_size`` tuple
+        is drawn on the host, which changes the canvas -- and with it the graph signature -- at nearly every step.  A single-entry
+        ``min_size`` installs nothing and logs one line.  The cost: the whole canvas is processed whatever was drawn."""
         from .graph import gt_capacity_classes
         from .optim import check_accumulate_grad_batches
         self.accumulate_grad_batches = check_accumulate_grad_batches(accumulate_grad_batches)
@@ -273,6 +282,8 @@ class SimpleTrainer:
         if not 0.0 <= self.weight_ema_warmup < float("inf"):
             raise ValueError(f"weight_ema_warmup must be a finite number >= 0 (0 = no warm-up), got {weight_ema_warmup}")
         self.weight_ema = None                            # the optim.WeightEMA of the last fit() (master optimizers on CUDA)
+        self.device_scale_jitter, self.scale_jitter_seed = bool(device_scale_jitter), int(scale_jitter_seed)
+        self.scale_jitter = None                          # the augment.RandomShortSide of the last fit()
         gt_capacity_classes(gt_capacity)                  # (bad values fail here, not at the first step)
         self.gt_capacity = gt_capacity
         self.max_epochs, self.max_steps, self.log_every, self.capture = max_epochs, max_steps, log_every, capture
@@ -321,6 +332,27 @@ class SimpleTrainer:
             raise ValueError(f"trainer.weight_ema_warmup must be a finite number >= 0 (0 = no warm-up), got {value}")
         return value
 
+    def resolve_device_scale_jitter(self, conf) -> bool:
+        "The constructor's ``device_scale_jitter`` or, when that is False, ``trainer.device_scale_jitter`` of the hparams (absent: off)."
+        if self.device_scale_jitter:
+            return True
+        section = conf.get("trainer") if hasattr(conf, "get") else None
+        return bool((section or {}).get("device_scale_jitter") or False)
+
+    def _install_scale_jitter(self, model, rank: Optional[int]) -> None:
+        "``fit``'s part of ``device_scale_jitter``: a ``RandomShortSide`` over the transform's ``min_size`` tuple, or one log line."
+        transform = model.net.transform
+        self.scale_jitter = getattr(transform, "scale_jitter", None)
+        if self.resolve_device_scale_jitter(model.conf):
+            sizes = tuple(getattr(transform, "min_size", ()))
+            if len(sizes) > 1:
+                from .augment import RandomShortSide
+                self.scale_jitter = transform.scale_jitter = RandomShortSide(sizes, seed=self.scale_jitter_seed)
+            else:
+                self.log.info("device_scale_jitter: min_size %s has a single entry, there is nothing to draw: no RandomShortSide installed", sizes)
+        if self.scale_jitter is not None and rank is not None:
+            self.scale_jitter.set_rank(rank)              # seed = base seed + rank: each rank draws its own scales
+
     def _ema_weights(self, model):
         """The context validation and testing run in: ``model``'s weights exchanged with the average that the last fit() kept, else
         nothing.  A model whose parameters are not the averaged ones is refused (``WeightEMA.swap``): it would be evaluated on its raw
@@ -351,6 +383,7 @@ class SimpleTrainer:
         hflip = getattr(model.net.transform, "hflip", None)
         if hflip is not None and ddp is not None:
             hflip.set_rank(dist.get_rank())               # seed = base seed + rank: each rank flips its own choice of images
+        self._install_scale_jitter(model, dist.get_rank() if ddp is not None else None)
         # precision "16" = fp16 autocast WITH dynamic loss scaling, like the reference's native-AMP run (Lightning precision=16):
         # fp16 gradients of a focal loss normalised by num_fg underflow without it
         # (under a gradient exchange: parallel.ExchangeGradScaler -- found_inf from the exchanged buckets, one decision for all ranks)

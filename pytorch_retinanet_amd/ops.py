@@ -594,6 +594,37 @@ def transform_batch(images: Sequence[Tensor], out_sizes: Sequence[Tuple[int, int
     return out
 
 
+def transform_batch_dev(images: Sequence[Tensor], out_hw: Tensor, mean: Sequence[float], std: Sequence[float], Hp: int, Wp: int,
+                        out_dtype: torch.dtype = torch.float32, channels_last: bool = False, flags: Optional[Tensor] = None) -> Tensor:
+    """``transform_batch`` with the output sizes on the device (``rn_transform_batch_dev``): ``out_hw`` int32 [B, 2] on the images'
+    device, as ``short_side_draw`` writes it; ``Hp`` / ``Wp`` stay host values (a size above the canvas is clamped in the kernel).
+    Bit-identical to ``transform_batch`` called with the same sizes on the host, with or without ``flags``."""
+    dev = _need_dev(*images, out_hw)
+    B = len(images)
+    if B == 0:
+        raise ValueError("need at least one image")
+    if out_hw.dtype != torch.int32 or tuple(out_hw.shape) != (B, 2) or not out_hw.is_contiguous():
+        raise ValueError(f"out_hw must be a contiguous int32 [{B}, 2] tensor, got {tuple(out_hw.shape)} {out_hw.dtype}")
+    if flags is not None:
+        _check_flags(flags, B, dev)
+    imgs = []
+    for im in images:
+        if im.dim() != 3 or im.shape[0] != 3 or im.dtype != torch.float32:
+            raise ValueError(f"transform_batch_dev expects f32 [3, h, w] images, got {tuple(im.shape)} {im.dtype}")
+        imgs.append(im if im.is_contiguous() else im.contiguous())
+    if out_dtype not in _DT:
+        raise ValueError(f"unsupported output dtype {out_dtype}")
+    out = torch.empty((B, 3, Hp, Wp), dtype=out_dtype, device=dev,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    ptrs = (C.c_void_p * B)(*[im.data_ptr() for im in imgs])
+    in_hw = (C.c_int32 * (2 * B))(*[int(v) for im in imgs for v in im.shape[1:]])
+    with torch.cuda.device(dev), _timed("transform_batch", dev):
+        check(lib.rn_transform_batch_dev(ptrs, in_hw, B, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(Hp), int(Wp), _ptr(out),
+                                         _DT[out_dtype], int(bool(channels_last)), _ptr(out_hw), _ptr(flags), _stream(dev)),
+              "rn_transform_batch_dev")
+    return out
+
+
 # ---- train-time horizontal flip (augment.RandomHorizontalFlip) ----------------------------------------------------------------
 _HFLIP_FIELDS = {"seed": (0, "<Q"), "counter": (8, "<q"), "p": (16, "<f")}     # include/retinanet_hip.h: rn_hflip_state
 HFLIP_STATE_BYTES = 24
@@ -682,6 +713,113 @@ def gt_flip_scale_packed(gt: PackedGT, widths: Sequence[float], ratios: Sequence
         check(lib.rn_gt_flip_scale_packed(_ptr(gt.gt_boxes), _ptr(out), _ptr(gt.gt_off), (C.c_float * gt.B)(*[float(w) for w in widths]),
                                           (C.c_float * len(flat))(*flat), _ptr(flags), gt.B, gt.rows, gt.cap_per_image, _stream(dev)),
               "rn_gt_flip_scale_packed")
+    return gt.with_boxes(out)
+
+
+# ---- multi-scale training: the short side drawn on the device (augment.RandomShortSide) ---------------------------------------
+SHORT_SIDE_MAX = 16                      # include/retinanet_hip.h: RN_SHORT_SIDE_MAX
+SHORT_SIDE_STATE_BYTES = 24 + 4 * SHORT_SIDE_MAX     # rn_short_side_state: seed u64, counter i64, n i32, reserved i32, sizes i32[16]
+
+
+def _check_short_side_block(block: Tensor) -> torch.device:
+    dev = _need_dev(block)
+    if block.dtype != torch.uint8 or block.numel() != SHORT_SIDE_STATE_BYTES or block.data_ptr() % 8:
+        raise ValueError("block must be an rn_short_side_state made by short_side_state()")
+    return dev
+
+
+def short_side_state(dev: torch.device, seed: int, counter: int, sizes: Sequence[int]) -> Tensor:
+    "A new ``rn_short_side_state`` block (uint8 [88]) on ``dev``: one host->device copy, outside any capture."
+    block = torch.empty((SHORT_SIDE_STATE_BYTES,), dtype=torch.uint8, device=dev)
+    short_side_state_write(block, seed=seed, counter=counter, sizes=sizes)
+    return block
+
+
+def short_side_state_write(block: Tensor, seed: Optional[int] = None, counter: Optional[int] = None,
+                           sizes: Optional[Sequence[int]] = None) -> None:
+    """Overwrite the given fields of an ``rn_short_side_state`` block (the others keep their device values; ``sizes`` writes n, the
+    reserved word and all 16 entries): host->device copies on the current stream, ordered with the draws around them.  Not inside
+    a capture: the values would be baked into the graph."""
+    _check_short_side_block(block)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("short_side_state_write inside a stream capture")
+    parts = []
+    if seed is not None:
+        parts.append((0, struct.pack("<Q", int(seed) & (2 ** 64 - 1))))
+    if counter is not None:
+        parts.append((8, struct.pack("<q", int(counter))))
+    if sizes is not None:
+        sizes = [int(v) for v in sizes]
+        if not 1 <= len(sizes) <= SHORT_SIDE_MAX or min(sizes) <= 0:
+            raise ValueError(f"need 1..{SHORT_SIDE_MAX} positive short sides, got {sizes}")
+        parts.append((16, struct.pack(f"<ii{SHORT_SIDE_MAX}i", len(sizes), 0, *(sizes + [sizes[-1]] * (SHORT_SIDE_MAX - len(sizes))))))
+    for off, raw in parts:
+        block[off:off + len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+
+
+def short_side_state_read(block: Tensor) -> Tuple[int, int, Tuple[int, ...]]:
+    "(seed, counter, sizes) of an ``rn_short_side_state`` block: one device->host copy (synchronises)."
+    _check_short_side_block(block)
+    raw = bytes(block.cpu().numpy().tobytes())
+    seed, counter, n, _ = struct.unpack_from("<Qqii", raw, 0)
+    return seed, counter, tuple(struct.unpack_from(f"<{SHORT_SIDE_MAX}i", raw, 24)[:max(0, min(n, SHORT_SIDE_MAX))])
+
+
+def short_side_draw(block: Tensor, in_hw: Sequence[Tuple[int, int]], max_size: int) -> Tuple[Tensor, Tensor]:
+    """``rn_short_side_draw``: for the images of sizes ``in_hw`` ((h, w) host ints) the resized sizes int32 [B, 2] and the box ratios
+    f32 [2B] = (rh, rw) per image, drawn from the block's seed / counter / sizes, then the block's counter advances by one -- one
+    launch per 64 images on the current stream, no host synchronisation (capturable: each replay draws anew)."""
+    dev = _check_short_side_block(block)
+    B = len(in_hw)
+    if B == 0:
+        raise ValueError("need at least one image size")
+    out_hw = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    ratios = torch.empty((2 * B,), dtype=torch.float32, device=dev)
+    hw = (C.c_int32 * (2 * B))(*[int(v) for s in in_hw for v in s])
+    with torch.cuda.device(dev), _timed("short_side_draw", dev):
+        check(lib.rn_short_side_draw(_ptr(block), hw, int(max_size), B, _ptr(out_hw), _ptr(ratios), _stream(dev)), "rn_short_side_draw")
+    return out_hw, ratios
+
+
+def _check_ratios_dev(ratios: Tensor, B: int, dev: torch.device) -> None:
+    if ratios.dtype != torch.float32 or ratios.device != dev or ratios.numel() != 2 * B or not ratios.is_contiguous():
+        raise ValueError(f"ratios must be a contiguous f32 tensor of {2 * B} entries on {dev}, got {tuple(ratios.shape)} {ratios.dtype} "
+                         f"on {ratios.device}")
+
+
+def gt_flip_scale_many_dev(boxes: Sequence[Tensor], widths: Sequence[float], ratios: Tensor, flags: Optional[Tensor] = None) -> Tensor:
+    """``gt_flip_scale_many`` with the ratios on the device (``ratios`` f32 [2B] = (rh, rw) per image, as ``short_side_draw`` writes
+    them) and the flags optional (None: nothing flips) -- ``rn_gt_flip_scale_many_dev``, bit-identical given the same values."""
+    dev = _need_dev(ratios, flags)
+    B = len(boxes)
+    if B == 0 or len(widths) != B:
+        raise ValueError(f"{B} box tensors, {len(widths)} widths")
+    _check_ratios_dev(ratios, B, dev)
+    if flags is not None:
+        _check_flags(flags, B, dev)
+    bs = [_aligned(b.reshape(-1, 4).to(device=dev, dtype=torch.float32), 16) for b in boxes]
+    counts = [int(b.shape[0]) for b in bs]
+    out = torch.empty((sum(counts), 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("gt_flip_scale_many", dev):
+        check(lib.rn_gt_flip_scale_many_dev((C.c_void_p * B)(*[_ptr(t).value for t in bs]), (C.c_int64 * B)(*counts), B,
+                                            (C.c_float * B)(*[float(w) for w in widths]), _ptr(ratios), _ptr(flags),
+                                            _ptr(out), int(out.shape[0]), _stream(dev)), "rn_gt_flip_scale_many_dev")
+    return out
+
+
+def gt_flip_scale_packed_dev(gt: PackedGT, widths: Sequence[float], ratios: Tensor, flags: Optional[Tensor] = None) -> PackedGT:
+    "``gt_flip_scale_packed`` with the ratios on the device and the flags optional (``rn_gt_flip_scale_packed_dev``), out of place."
+    dev = _need_dev(gt.gt_boxes, gt.gt_off, ratios, flags)
+    if len(widths) != gt.B:
+        raise ValueError(f"{len(widths)} widths for packed GT of {gt.B} images")
+    _check_ratios_dev(ratios, gt.B, dev)
+    if flags is not None:
+        _check_flags(flags, gt.B, dev)
+    out = torch.empty_like(gt.gt_boxes)
+    with torch.cuda.device(dev), _timed("gt_flip_scale_packed", dev):
+        check(lib.rn_gt_flip_scale_packed_dev(_ptr(gt.gt_boxes), _ptr(out), _ptr(gt.gt_off), (C.c_float * gt.B)(*[float(w) for w in widths]),
+                                              _ptr(ratios), _ptr(flags), gt.B, gt.rows, gt.cap_per_image, _stream(dev)),
+              "rn_gt_flip_scale_packed_dev")
     return gt.with_boxes(out)
 
 

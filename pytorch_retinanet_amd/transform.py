@@ -23,6 +23,18 @@ On the fused path the decisions are drawn on the device (``rn_hflip_draw``), the
 gather (``rn_transform_batch_flip``) and the boxes' flip + resize one launch (``rn_gt_flip_scale_many`` / ``_packed``), so
 a captured train step draws new flips at every replay.  The PyTorch path does the same with ``img.flip(-1)`` and the box
 formula, selected by the flags with ``torch.where``.  ``hflip`` is a plain attribute: the state-dict keys do not change.
+
+Multi-scale training on the device (``scale_jitter``: an ``augment.RandomShortSide``, None by default): in training mode and when
+targets are given, each image's short side is drawn by the installed object instead of by ``_target_short_side`` (which is then not
+consulted; eval mode is exactly as without one).  The padded canvas is computed on the host from the object's upper bound of every
+image's size (its largest short side), rounded up to ``size_divisible``: it depends on the image shapes alone, so a captured
+train step keeps ONE graph while the scales vary.  On the fused path the sizes are drawn on the device (``rn_short_side_draw``),
+stay there as ``scale_jitter.sizes_drawn`` (int32 [B, 2]) and are read by the transform kernel (``rn_transform_batch_dev``) and
+the box kernels (``rn_gt_flip_scale_many_dev`` / ``_packed_dev``); the flip composes.  ``ImageList.image_sizes`` then holds the
+upper-bound sizes, not the drawn ones -- the training pass does not read them beyond their number (anchors, matching and the
+loss are laid out on the padded canvas).  The PyTorch path draws the same sizes from the Python restatement, resizes each image
+with ``resize`` and pads the batch to the same canvas.  The known cost: the whole canvas is processed whatever was drawn, so small
+draws save no compute.  ``scale_jitter`` is a plain attribute too.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -101,6 +113,7 @@ class GeneralizedRCNNTransform(nn.Module):
         self.size_divisible = size_divisible
         self._stats = {}
         self.hflip = None             # augment.RandomHorizontalFlip: the train-time flip (module docstring)
+        self.scale_jitter = None      # augment.RandomShortSide: the short side drawn on the device (module docstring)
 
     # -- pieces ------------------------------------------------------------------------
     def normalize(self, image: Tensor) -> Tensor:
@@ -124,9 +137,10 @@ class GeneralizedRCNNTransform(nn.Module):
             scale = float(self.max_size) / hi
         return scale
 
-    def resize(self, image: Tensor, target: Optional[Dict[str, Tensor]]):
+    def resize(self, image: Tensor, target: Optional[Dict[str, Tensor]], short: Optional[float] = None):
+        "``short``: the short side to resize to (a ``scale_jitter``'s draw) instead of ``_target_short_side()``."
         h, w = int(image.shape[-2]), int(image.shape[-1])
-        scale = self._scale_for(h, w, self._target_short_side())
+        scale = self._scale_for(h, w, self._target_short_side() if short is None else float(short))
         nh, nw = int(math.floor(h * scale)), int(math.floor(w * scale))
         if (nh, nw) != (h, w):
             image = F.interpolate(image[None], scale_factor=scale, mode="bilinear",
@@ -136,11 +150,14 @@ class GeneralizedRCNNTransform(nn.Module):
             target["boxes"] = resize_boxes(target["boxes"], (h, w), image.shape[-2:])
         return image, target
 
-    def batch_images(self, images: List[Tensor]) -> Tensor:
+    def _canvas(self, sizes: Sequence[Tuple[int, int]]) -> Tuple[int, int]:
         d = float(self.size_divisible)
+        return int(math.ceil(max(s[0] for s in sizes) / d) * d), int(math.ceil(max(s[1] for s in sizes) / d) * d)
+
+    def batch_images(self, images: List[Tensor], canvas: Optional[Tuple[int, int]] = None) -> Tensor:
+        "``canvas``: the padded (H, W) to use instead of the images' own maximum rounded up (a ``scale_jitter``'s fixed canvas)."
         c = max(im.shape[0] for im in images)
-        hh = int(math.ceil(max(im.shape[1] for im in images) / d) * d)
-        ww = int(math.ceil(max(im.shape[2] for im in images) / d) * d)
+        hh, ww = canvas if canvas is not None else self._canvas([im.shape[1:] for im in images])
         out = images[0].new_zeros((len(images), c, hh, ww))
         for im, dst in zip(images, out):
             dst[: im.shape[0], : im.shape[1], : im.shape[2]].copy_(im)
@@ -158,9 +175,34 @@ class GeneralizedRCNNTransform(nn.Module):
             return None
         return self.hflip.next_flags(len(images), images[0].device)
 
+    def _jitter(self, targets):
+        "The installed ``scale_jitter`` when it acts on this call (training mode, targets given), else None."
+        return self.scale_jitter if self.scale_jitter is not None and self.training and targets is not None else None
+
+    def _forward_fused_jitter(self, jitter, images: List[Tensor], targets, out_dtype: torch.dtype, channels_last: bool, flags):
+        "The fused path with the sizes drawn on the device: nothing about the draw reaches the host, the canvas is the bound's."
+        from . import ops
+        in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
+        widths = [float(w) for _, w in in_hw]
+        bounds = [jitter.bound(h, w, self.max_size) for h, w in in_hw]
+        out_hw, ratios = jitter.next_sizes(in_hw, self.max_size, images[0].device)
+        if _is_packed(targets):
+            targets = ops.gt_flip_scale_packed_dev(targets, widths, ratios, flags)
+        else:
+            counts = [int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets]
+            rows = ops.gt_flip_scale_many_dev([t["boxes"] for t in targets], widths, ratios, flags).split(counts)
+            for t, r in zip(targets, rows):
+                t["boxes"] = r
+        hp, wp = self._canvas(bounds)
+        batch = ops.transform_batch_dev(images, out_hw, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags)
+        return ImageList(batch, bounds), targets
+
     def _forward_fused(self, images: List[Tensor], targets, out_dtype: torch.dtype, channels_last: bool):
         from . import ops                       # the HIP library is only needed once a CUDA image shows up
         flags = self._flips(images, targets)
+        jitter = self._jitter(targets)
+        if jitter is not None:
+            return self._forward_fused_jitter(jitter, images, targets, out_dtype, channels_last, flags)
         sizes, ratios, widths = [], [], []
         packed = _is_packed(targets)
         for i, im in enumerate(images):
@@ -181,9 +223,7 @@ class GeneralizedRCNNTransform(nn.Module):
             rows = ops.gt_flip_scale_many([t["boxes"] for t in targets], widths, ratios, flags).split(counts)
             for t, r in zip(targets, rows):
                 t["boxes"] = r
-        d = float(self.size_divisible)
-        hp = int(math.ceil(max(s[0] for s in sizes) / d) * d)
-        wp = int(math.ceil(max(s[1] for s in sizes) / d) * d)
+        hp, wp = self._canvas(sizes)
         batch = ops.transform_batch(images, sizes, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags)
         return ImageList(batch, sizes), targets
 
@@ -206,6 +246,14 @@ class GeneralizedRCNNTransform(nn.Module):
         if self._fusable(images):
             return self._forward_fused(images, targets, out_dtype or torch.float32, channels_last)
         flags = self._flips(images, targets)
+        jitter = self._jitter(targets)
+        shorts = bounds = None
+        if jitter is not None:
+            # the same draw from the Python restatement (CUDA images that are not fusable: the counter is read back, one synchronisation)
+            in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
+            shorts = jitter.draw_short(jitter.counter, len(images))
+            jitter.next_sizes(in_hw, self.max_size, images[0].device)
+            bounds = [jitter.bound(h, w, self.max_size) for h, w in in_hw]
         ratios, widths = [], []
         for i, im in enumerate(images):
             if im.dim() != 3:
@@ -215,7 +263,7 @@ class GeneralizedRCNNTransform(nn.Module):
             widths.append(float(hw[1]))
             if flags is not None:
                 im, tgt = _flip_where(flags[i], im, tgt)
-            im, tgt = self.resize(self.normalize(im), tgt)
+            im, tgt = self.resize(self.normalize(im), tgt, None if shorts is None else shorts[i])
             images[i] = im
             if packed:
                 ratios.append(_ratios(hw, im.shape[-2:]))
@@ -224,6 +272,8 @@ class GeneralizedRCNNTransform(nn.Module):
         if packed:
             from . import ops
             targets = _resize_packed(targets, ratios) if flags is None else ops.gt_flip_scale_packed(targets, widths, ratios, flags)
+        if bounds is not None:
+            return ImageList(self.batch_images(images, self._canvas(bounds)), bounds), targets
         sizes = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
         return ImageList(self.batch_images(images), sizes), targets
 
