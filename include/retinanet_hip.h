@@ -507,6 +507,12 @@ int rn_gt_flip_scale_many_dev(const void *const *boxes, const int64_t *counts, i
                               const uint8_t *flags_or_null, float *out_boxes, int64_t rows, void *stream);
 int rn_gt_flip_scale_packed_dev(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const float *ratios_dev,
                                 const uint8_t *flags_or_null, int B, int64_t rows, int64_t max_per_image, void *stream);
+/* rn_gt_flip_scale_packed_dev with the original widths on the device as well: in_hw_dev is DEVICE i32[B][2] = (h, w) before the resize, as
+ * rn_image_stage writes it (graph.CapturedTrainStep, image capacity mode); W_b = float(w).  Bit-identical to the _dev form given the
+ * same values; every other rule is its. */
+int rn_gt_flip_scale_packed_var(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const int32_t *in_hw_dev,
+                                const float *ratios_dev, const uint8_t *flags_or_null, int B, int64_t rows, int64_t max_per_image,
+                                void *stream);
 /* n widening copies dsts[i] (f32) <- srcs[i] (src_dtype: RN_BF16 or RN_F16), counts[i] elements each, one launch per 64: the
  * gather of 16-bit parameter gradients into the fp32 buckets of the gradient exchange (no reference analogue: Lightning's DDP
  * exchanges fp32 gradients of fp32 parameters).  HOST arrays. */
@@ -865,7 +871,8 @@ int rn_ema_swap(float *const *emas, float *const *masters, void *const *params16
  * into one batch [B][3][Hp][Wp].  images: HOST array of B device pointers, each f32 [3][h][w]
  * contiguous; in_hw / out_hw: HOST i32[B][2] = (h, w) before / after the resize (the caller computes
  * the sizes exactly as torchvision does, floor(size * scale) in double); mean / std: HOST f32[3].
- * out: dtype out_dtype, NCHW or (channels_last != 0) NHWC memory order; Wp % 4 == 0. */
+ * out: dtype out_dtype, NCHW or (channels_last != 0) NHWC memory order; Wp % 4 == 0.  A std of 0 is RN_EINVAL in every form below
+ * (rn_transform_batch, _flip, _dev and _var alike). */
 int rn_transform_batch(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
                        const float mean[3], const float std[3], int Hp, int Wp,
                        void *out, int out_dtype, int channels_last, void *stream);
@@ -880,6 +887,22 @@ int rn_transform_batch_flip(const void *const *images, const int32_t *in_hw, con
  * is rn_transform_batch's: bit-identical to rn_transform_batch / rn_transform_batch_flip called with the same sizes on the host. */
 int rn_transform_batch_dev(const void *const *images, const int32_t *in_hw, int B, const float mean[3], const float std[3],
                            int Hp, int Wp, void *out, int out_dtype, int channels_last, const int32_t *out_hw_dev,
+                           const uint8_t *flags_or_null, void *stream);
+
+/* ---- images of varying sizes in fixed-size buffers (graph.CapturedTrainStep, image capacity mode) ----------------------------------
+ * rn_image_stage: the B images f32 [3][h_b][w_b] (dense, 4-byte aligned; images: HOST array of device pointers, in_hw: HOST i32[B][2],
+ * both passed by value) into a fixed arena of B slots of ``slot`` floats each (16-byte aligned): image b dense at the start of slot b
+ * with its own strides, and in_hw_dev (DEVICE i32[B][2]) = its (h, w).  One launch per 64 images, 16-byte copies where the source
+ * allows.  Floats [3 h_b w_b, slot) of a slot are left untouched.  RN_EINVAL (nothing launched): a null pointer, a size <= 0,
+ * 3 h w > slot, B <= 0; RN_EALIGN: a misaligned pointer.
+ * rn_transform_batch_var: rn_transform_batch_dev reading the staged images: image b from arena + b * slot, its (ih, iw) from in_hw_dev
+ * and its (oh, ow) from out_hw_dev (rn_resize_plan_dev writes it in the same stream).  No address or size of an image is a kernel
+ * argument: a captured graph serves every batch that fits the arena.  Device data cannot move a thread outside the operands: oh / ow
+ * are clamped to the canvas, and an image with ih < 1, iw < 1 or 3 ih iw > slot is all padding.  Per output pixel the code is
+ * rn_transform_batch's: bit-identical to rn_transform_batch / _flip called with the same sizes and the same Hp, Wp on the host. */
+int rn_image_stage(const void *const *images, const int32_t *in_hw, int B, float *arena, int64_t slot, int32_t *in_hw_dev, void *stream);
+int rn_transform_batch_var(const float *arena, int64_t slot, const int32_t *in_hw_dev, const int32_t *out_hw_dev, int B,
+                           const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype, int channels_last,
                            const uint8_t *flags_or_null, void *stream);
 
 /* ---- train-time augmentation: the horizontal-flip decision, drawn on the device ------------------------------------
@@ -903,6 +926,12 @@ int rn_hflip_draw(rn_hflip_state *state, int B, uint8_t *flags, void *stream);
 #define RN_SHORT_SIDE_MAX 16
 typedef struct rn_short_side_state { uint64_t seed; int64_t counter; int32_t n; int32_t reserved; int32_t sizes[RN_SHORT_SIDE_MAX]; } rn_short_side_state;
 int rn_short_side_draw(rn_short_side_state *state, const int32_t *in_hw, int max_size, int B, int32_t *out_hw, float *ratios, void *stream);
+/* rn_resize_plan_dev: the same plan with the input sizes read from the device (in_hw_dev: DEVICE i32[B][2], rn_image_stage writes it).
+ * With a state block: rn_short_side_draw's draw exactly -- same hash, salt and counter advance.  With state_or_null == NULL nothing is
+ * drawn and every image gets the short side fixed_short (> 0).  One single-wave launch for any B.  A size < 1 in in_hw_dev gives
+ * out_hw = (0, 0) and ratios = (0, 0). */
+int rn_resize_plan_dev(rn_short_side_state *state_or_null, const int32_t *in_hw_dev, int fixed_short, int max_size, int B, int32_t *out_hw,
+                       float *ratios, void *stream);
 
 /* ---- K6 nms (op boundary) ---------------------------------------------------
  * Replaces torchvision.ops.nms as called at retinanet/models.py:210, batched over

@@ -174,6 +174,7 @@ SIGNATURES = {
     "rn_gt_flip_scale_packed": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _vp, C.c_int, _i64, _i64, _vp]),
     "rn_gt_flip_scale_many_dev": (C.c_int, [_vp, C.POINTER(_i64), C.c_int, C.POINTER(_f32), _vp, _vp, _vp, _i64, _vp]),
     "rn_gt_flip_scale_packed_dev": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _vp, C.c_int, _i64, _i64, _vp]),
+    "rn_gt_flip_scale_packed_var": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _i64, _i64, _vp]),
     "rn_cast_many_to_f32": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "rn_transpose_many": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "rn_conv3x3_levels_dgrad_weight": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
@@ -195,8 +196,12 @@ SIGNATURES = {
                                           C.c_int, C.c_int, _vp, _vp]),
     "rn_transform_batch_dev": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_f32), C.POINTER(_f32), C.c_int, C.c_int, _vp,
                                          C.c_int, C.c_int, _vp, _vp, _vp]),
+    "rn_image_stage": (C.c_int, [_vp, C.POINTER(_i32), C.c_int, _vp, _i64, _vp, _vp]),
+    "rn_transform_batch_var": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, C.POINTER(_f32), C.POINTER(_f32), C.c_int, C.c_int, _vp,
+                                         C.c_int, C.c_int, _vp, _vp]),
     "rn_hflip_draw": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "rn_short_side_draw": (C.c_int, [_vp, C.POINTER(_i32), C.c_int, C.c_int, _vp, _vp, _vp]),
+    "rn_resize_plan_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "rn_nms_workspace_bytes": (_sz, [_i64, C.c_int]),
     "rn_nms_segments": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _f32, _vp, _vp, _vp, _sz, _vp]),
     "rn_detect_workspace_bytes": (_sz, [C.c_int, _i64, C.c_int, _i64]),

@@ -245,6 +245,25 @@ class RandomShortSide:
         self.sizes_drawn, self.ratios_drawn = sizes, ratios
         return sizes, ratios
 
+    def next_sizes_dev(self, in_hw: Tensor, max_size: float) -> Tuple[Tensor, Tensor]:
+        """``next_sizes`` for images whose sizes only the device holds (``in_hw`` int32 [B, 2] on a CUDA device, as ``ops.image_stage``
+        writes it: the image capacity mode of ``graph.CapturedTrainStep``): one ``rn_resize_plan_dev`` launch for any B (capturable).
+        The same stream of draws: at counter n it gives what ``draw(n, sizes, max_size)`` gives for the sizes ``in_hw`` holds, and
+        the counter advances by one."""
+        from . import ops
+        if int(max_size) != max_size:
+            raise ValueError(f"the device draw takes an integer max_size, got {max_size}")
+        device = in_hw.device
+        if device.type != "cuda":
+            raise RuntimeError("RandomShortSide.next_sizes_dev: the sizes must be on the GPU (there is no CPU fallback)")
+        if self._block is None:
+            self._block = ops.short_side_state(device, self._seed, self._counter, self._sizes)
+        elif self._block.device != device:
+            raise RuntimeError(f"RandomShortSide: its state lives on {self._block.device}, not {device}; use one object per device")
+        sizes, ratios = ops.resize_plan_dev(self._block, in_hw, None, int(max_size))
+        self.sizes_drawn, self.ratios_drawn = sizes, ratios
+        return sizes, ratios
+
     # -- settings and state ---------------------------------------------------------------------------------------------
     @property
     def sizes(self) -> Tuple[int, ...]:

@@ -36,6 +36,14 @@
 // FMA contraction and with IEEE division.  The salt keeps a flip and a jitter that share a seed from tying small sizes to flipped
 // images.  The input sizes are host values carried in the kernel arguments (64 images per launch; lane i serves image i); a batch
 // of more than 64 images takes several launches that read the SAME counter, and only the last one advances it.
+//
+//   rn_resize_plan_dev   the same plan with h, w read from DEVICE memory (in_hw i32[B][2], written by rn_image_stage: the image
+//                        capacity mode of graph.CapturedTrainStep), so a captured step serves images of any size
+//
+// With a state block the draw is rn_short_side_draw's: same hash, salt and counter advance (augment.RandomShortSide.draw restates
+// both).  With a null block the short side is a value passed by the host (a transform without multi-scale training) and nothing
+// is drawn.  No table in the kernel arguments: one wave walks the images 64 at a time, so one launch serves any B.  A size < 1
+// (device data) gives out_hw = (0, 0) and ratios (0, 0): the transform kernel treats such an image as all padding.
 #include "rn_common.hpp"
 
 namespace {
@@ -64,6 +72,21 @@ constexpr int SS_MAX_IMAGES = 64;   // per launch (kernel-argument table): one l
 constexpr uint64_t SS_SALT = 0x5CA1E5CA1E5CA1E5ull;
 static_assert(SS_MAX_IMAGES == HF_BLOCK, "one lane per image of a launch");
 
+// The plan of ONE image, shared by the two kernels below so that they cannot drift apart: _scale_for, the two floors of resize and
+// _ratios for an h x w image (both >= 1) and the short side ``shrt``, written to entry b of out_hw / ratios.
+__device__ __forceinline__ void resize_plan(const int h, const int w, const int shrt, const int max_size, const int b,
+                                            int32_t *__restrict__ out_hw, float *__restrict__ ratios)
+{
+    const double lo = (double)(h < w ? h : w), hi = (double)(h < w ? w : h);
+    double scale = (double)shrt / lo;
+    if (hi * scale > (double)max_size) scale = (double)max_size / hi;
+    const int nh = (int)floor((double)h * scale), nw = (int)floor((double)w * scale);
+    out_hw[2 * b] = nh;
+    out_hw[2 * b + 1] = nw;
+    ratios[2 * b] = (float)nh / (float)h;
+    ratios[2 * b + 1] = (float)nw / (float)w;
+}
+
 struct ShortSideTable { int32_t ih[SS_MAX_IMAGES], iw[SS_MAX_IMAGES]; };
 
 __global__ __launch_bounds__(HF_BLOCK) void short_side_draw_kernel(rn_short_side_state *st, const ShortSideTable t, const int cnt, const int base,
@@ -79,17 +102,43 @@ __global__ __launch_bounds__(HF_BLOCK) void short_side_draw_kernel(rn_short_side
         const int b = base + i;
         int idx = (int)(hflip_u(seed, counter, b) * (float)n);
         idx = idx < n - 1 ? idx : n - 1;
-        const int h = t.ih[i], w = t.iw[i];
-        const double lo = (double)(h < w ? h : w), hi = (double)(h < w ? w : h);
-        double scale = (double)st->sizes[idx] / lo;
-        if (hi * scale > (double)max_size) scale = (double)max_size / hi;
-        const int nh = (int)floor((double)h * scale), nw = (int)floor((double)w * scale);
-        out_hw[2 * b] = nh;
-        out_hw[2 * b + 1] = nw;
-        ratios[2 * b] = (float)nh / (float)h;
-        ratios[2 * b + 1] = (float)nw / (float)w;
+        resize_plan(t.ih[i], t.iw[i], st->sizes[idx], max_size, b, out_hw, ratios);
     }
     if (advance && threadIdx.x == 0) st->counter = counter + 1;
+}
+
+// DRAW: short side from the state block (and the counter advanced), else ``fixed_short``; st is null without DRAW
+template <bool DRAW>
+__global__ __launch_bounds__(HF_BLOCK) void resize_plan_dev_kernel(rn_short_side_state *st, const int32_t *__restrict__ in_hw, const int fixed_short,
+                                                                  const int max_size, const int B, int32_t *__restrict__ out_hw,
+                                                                  float *__restrict__ ratios)
+{
+    uint64_t seed = 0;
+    int64_t counter = 0;
+    int n = 1;
+    if (DRAW) {
+        seed = st->seed ^ SS_SALT;
+        counter = st->counter;
+        n = st->n;
+        n = n < 1 ? 1 : (n > RN_SHORT_SIDE_MAX ? RN_SHORT_SIDE_MAX : n);      // (device data: the index below stays inside sizes[])
+    }
+    for (int b = (int)threadIdx.x; b < B; b += HF_BLOCK) {
+        int shrt = fixed_short;
+        if (DRAW) {
+            int idx = (int)(hflip_u(seed, counter, b) * (float)n);
+            idx = idx < n - 1 ? idx : n - 1;
+            shrt = st->sizes[idx];
+        }
+        const int h = in_hw[2 * b], w = in_hw[2 * b + 1];
+        if (h >= 1 && w >= 1) {
+            resize_plan(h, w, shrt, max_size, b, out_hw, ratios);
+        } else {                                                               // (device data: an empty entry, nothing is divided)
+            out_hw[2 * b] = out_hw[2 * b + 1] = 0;
+            ratios[2 * b] = ratios[2 * b + 1] = 0.0f;
+        }
+    }
+    // (one wave: every lane read the counter above, in program order before this store)
+    if (DRAW && threadIdx.x == 0) st->counter = counter + 1;
 }
 
 }  // namespace
@@ -122,5 +171,22 @@ RN_API int rn_short_side_draw(rn_short_side_state *state, const int32_t *in_hw, 
                            base + cnt == B ? 1 : 0, out_hw, ratios);
         RN_LAUNCH_CHECK();
     }
+    return RN_OK;
+}
+
+RN_API int rn_resize_plan_dev(rn_short_side_state *state_or_null, const int32_t *in_hw_dev, int fixed_short, int max_size, int B,
+                              int32_t *out_hw, float *ratios, void *stream)
+{
+    if (!in_hw_dev || !out_hw || !ratios || B <= 0 || max_size <= 0) return RN_EINVAL;
+    if (!state_or_null && fixed_short <= 0) return RN_EINVAL;
+    if ((state_or_null && !rn::aligned(state_or_null, 8)) || !rn::aligned(in_hw_dev, 4) || !rn::aligned(out_hw, 4) || !rn::aligned(ratios, 4))
+        return RN_EALIGN;
+    if (state_or_null)
+        hipLaunchKernelGGL(resize_plan_dev_kernel<true>, dim3(1), dim3(HF_BLOCK), 0, (hipStream_t)stream, state_or_null, in_hw_dev, 0, max_size,
+                           B, out_hw, ratios);
+    else
+        hipLaunchKernelGGL(resize_plan_dev_kernel<false>, dim3(1), dim3(HF_BLOCK), 0, (hipStream_t)stream, state_or_null, in_hw_dev, fixed_short,
+                           max_size, B, out_hw, ratios);
+    RN_LAUNCH_CHECK();
     return RN_OK;
 }

@@ -19,6 +19,10 @@
 //                       the same two kernels with the ratios read from DEVICE memory (f32[2B] = (rh, rw), written by rn_short_side_draw
 //                       inside the same captured step: augment.RandomShortSide) and the flags optional (null: nothing flips).  The
 //                       arithmetic on a row is flip_scale either way: bit-identical to the host-ratio forms given the same values.
+//   rn_gt_flip_scale_packed_var
+//                       the _packed_dev kernel with the original widths read from DEVICE memory too (i32[B][2] = (h, w), written by
+//                       rn_image_stage: graph.CapturedTrainStep's image capacity mode) instead of the host ``widths`` array; the
+//                       width becomes a float exactly as the host's float(w) does, so the rows are bit-identical again.
 // All kernels index their argument tables by blockIdx only (a per-lane index into the argument segment becomes a vector load of
 // the table; CHANGELOG, the compiler's treatment of hand-written loops, item 2).
 #include "rn_common.hpp"
@@ -102,14 +106,16 @@ __global__ __launch_bounds__(GT_BLOCK) void gt_flip_scale_many_kernel(const Flip
 
 struct FlipScaleTable { float w[GT_MAX]; float rh[GT_MAX]; float rw[GT_MAX]; };
 
-template <bool DEV>
+// VAR (implies DEV): the width of image base + i from ``in_hw`` (device, (h, w) pairs) instead of the table
+template <bool DEV, bool VAR>
 __global__ __launch_bounds__(GT_BLOCK) void gt_flip_scale_kernel(const FlipScaleTable t, const uint8_t *__restrict__ flags,
-                                                                const float *__restrict__ ratios, const rn::f32x4 *__restrict__ in,
-                                                                rn::f32x4 *__restrict__ out, const int32_t *__restrict__ gt_off, int base,
-                                                                int32_t rows)
+                                                                const float *__restrict__ ratios, const int32_t *__restrict__ in_hw,
+                                                                const rn::f32x4 *__restrict__ in, rn::f32x4 *__restrict__ out,
+                                                                const int32_t *__restrict__ gt_off, int base, int32_t rows)
 {
     const int i = blockIdx.y;
-    const float w = t.w[i], rh = DEV ? ratios[2 * (base + i)] : t.rh[i], rw = DEV ? ratios[2 * (base + i) + 1] : t.rw[i];
+    const float w = VAR ? (float)in_hw[2 * (base + i) + 1] : t.w[i];
+    const float rh = DEV ? ratios[2 * (base + i)] : t.rh[i], rw = DEV ? ratios[2 * (base + i) + 1] : t.rw[i];
     const bool flip = DEV ? (flags != nullptr && flags[base + i] != 0) : flags[base + i] != 0;
     int32_t lo = gt_off[base + i], hi = gt_off[base + i + 1];
     lo = lo < 0 ? 0 : (lo > rows ? rows : lo);
@@ -243,15 +249,17 @@ int flip_scale_many(const void *const *boxes, const int64_t *counts, int B, cons
     return RN_OK;
 }
 
-int flip_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const float *ratios,
-                      const float *ratios_dev, const uint8_t *flags, int B, int64_t rows, int64_t max_per_image, void *stream)
+// widths: HOST float[B], or null with in_hw_dev (DEVICE i32[B][2]) in their place -- only together with ratios_dev
+int flip_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const float *widths, const int32_t *in_hw_dev,
+                      const float *ratios, const float *ratios_dev, const uint8_t *flags, int B, int64_t rows, int64_t max_per_image,
+                      void *stream)
 {
-    if (!gt_off || !widths || (!ratios == !ratios_dev) || (!flags && !ratios_dev) || B <= 0 || rows < 0 || rows > INT32_MAX || max_per_image < 0)
+    if (!gt_off || (!widths == !in_hw_dev) || (in_hw_dev && !ratios_dev) || (!ratios == !ratios_dev) || (!flags && !ratios_dev) || B <= 0 || rows < 0 || rows > INT32_MAX || max_per_image < 0)
         return RN_EINVAL;
     if (rows > 0 && (!gt_boxes || !out_boxes)) return RN_EINVAL;
     if (rows > 0 && gt_boxes == out_boxes) return RN_EINVAL;
     if (!rn::aligned(gt_off, 4) || (gt_boxes && !rn::aligned(gt_boxes, 16)) || (out_boxes && !rn::aligned(out_boxes, 16)) ||
-        (ratios_dev && !rn::aligned(ratios_dev, 4)))
+        (ratios_dev && !rn::aligned(ratios_dev, 4)) || (in_hw_dev && !rn::aligned(in_hw_dev, 4)))
         return RN_EALIGN;
     if (rows == 0) return RN_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -259,17 +267,20 @@ int flip_scale_packed(const float *gt_boxes, float *out_boxes, const int32_t *gt
         const int cnt = (B - base) < GT_MAX ? (B - base) : GT_MAX;
         FlipScaleTable t;
         for (int i = 0; i < GT_MAX; ++i) {
-            t.w[i] = i < cnt ? widths[base + i] : 0.0f;
+            t.w[i] = i < cnt && widths ? widths[base + i] : 0.0f;
             t.rh[i] = i < cnt && ratios ? ratios[2 * (base + i)] : 1.0f;
             t.rw[i] = i < cnt && ratios ? ratios[2 * (base + i) + 1] : 1.0f;
         }
         const dim3 grid((unsigned)grid_x(max_per_image), (unsigned)cnt);
-        if (ratios_dev)
-            hipLaunchKernelGGL(gt_flip_scale_kernel<true>, grid, dim3(GT_BLOCK), 0, st, t, flags, ratios_dev, (const rn::f32x4 *)gt_boxes,
-                               (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
+        if (in_hw_dev)
+            hipLaunchKernelGGL((gt_flip_scale_kernel<true, true>), grid, dim3(GT_BLOCK), 0, st, t, flags, ratios_dev, in_hw_dev,
+                               (const rn::f32x4 *)gt_boxes, (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
+        else if (ratios_dev)
+            hipLaunchKernelGGL((gt_flip_scale_kernel<true, false>), grid, dim3(GT_BLOCK), 0, st, t, flags, ratios_dev, in_hw_dev,
+                               (const rn::f32x4 *)gt_boxes, (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
         else
-            hipLaunchKernelGGL(gt_flip_scale_kernel<false>, grid, dim3(GT_BLOCK), 0, st, t, flags, ratios_dev, (const rn::f32x4 *)gt_boxes,
-                               (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
+            hipLaunchKernelGGL((gt_flip_scale_kernel<false, false>), grid, dim3(GT_BLOCK), 0, st, t, flags, ratios_dev, in_hw_dev,
+                               (const rn::f32x4 *)gt_boxes, (rn::f32x4 *)out_boxes, gt_off, base, (int32_t)rows);
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
@@ -288,7 +299,7 @@ RN_API int rn_gt_flip_scale_packed(const float *gt_boxes, float *out_boxes, cons
                                    const uint8_t *flags, int B, int64_t rows, int64_t max_per_image, void *stream)
 {
     if (!ratios || !flags) return RN_EINVAL;
-    return flip_scale_packed(gt_boxes, out_boxes, gt_off, widths, ratios, nullptr, flags, B, rows, max_per_image, stream);
+    return flip_scale_packed(gt_boxes, out_boxes, gt_off, widths, nullptr, ratios, nullptr, flags, B, rows, max_per_image, stream);
 }
 
 RN_API int rn_gt_flip_scale_many_dev(const void *const *boxes, const int64_t *counts, int B, const float *widths, const float *ratios_dev,
@@ -303,5 +314,13 @@ RN_API int rn_gt_flip_scale_packed_dev(const float *gt_boxes, float *out_boxes, 
                                        void *stream)
 {
     if (!ratios_dev) return RN_EINVAL;
-    return flip_scale_packed(gt_boxes, out_boxes, gt_off, widths, nullptr, ratios_dev, flags_or_null, B, rows, max_per_image, stream);
+    return flip_scale_packed(gt_boxes, out_boxes, gt_off, widths, nullptr, nullptr, ratios_dev, flags_or_null, B, rows, max_per_image, stream);
+}
+
+RN_API int rn_gt_flip_scale_packed_var(const float *gt_boxes, float *out_boxes, const int32_t *gt_off, const int32_t *in_hw_dev,
+                                       const float *ratios_dev, const uint8_t *flags_or_null, int B, int64_t rows, int64_t max_per_image,
+                                       void *stream)
+{
+    if (!in_hw_dev || !ratios_dev) return RN_EINVAL;
+    return flip_scale_packed(gt_boxes, out_boxes, gt_off, nullptr, in_hw_dev, nullptr, ratios_dev, flags_or_null, B, rows, max_per_image, stream);
 }

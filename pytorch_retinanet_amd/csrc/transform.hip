@@ -25,6 +25,17 @@
 // them inside a captured step: augment.RandomShortSide) instead of the kernel-argument table; the canvas Hp x Wp stays a host value
 // and a size read from the device is clamped to it, so nothing it holds can make a thread write outside the batch.  Everything after
 // the two loads is the code above: bit-identical to rn_transform_batch / _flip called with the same sizes on the host.
+//
+// rn_transform_batch_var is the _dev launch with the INPUT side on the device as well (graph.CapturedTrainStep's image capacity mode):
+// image b lies dense at the start of slot b of a fixed arena (rn_image_stage, below, copies it there before every step) and its
+// (ih, iw) are read from device memory next to the (oh, ow) of the resize plan (rn_resize_plan_dev), so neither an image's address nor
+// any of its sizes is a kernel argument and one captured graph serves images of every size that fits a slot.  What the device holds
+// cannot move a thread outside its operands: oh / ow are clamped to the canvas, and an image with ih < 1, iw < 1 or 3 * ih * iw > slot
+// is all padding (every tap lies inside [0, 3 * ih * iw) otherwise).  After the loads it is the code above once more.
+//
+// rn_image_stage copies B dense f32 [3][h_b][w_b] images into their arena slots and writes in_hw on the device: ONE launch per 64
+// images with the pointers and sizes passed BY VALUE in the kernel arguments (like rn_gt_stage), 16-byte vector copies when the
+// source is 16-byte aligned (a slot always is) and 4-byte copies otherwise and for the tail.
 #include "rn_common.hpp"
 
 namespace {
@@ -40,6 +51,9 @@ struct TransformArgs {
     void *out;                         // first image of this launch
     const uint8_t *flags;              // FLIP: this launch's first image's flag (device)
     const int32_t *out_hw;             // DEV: this launch's first image's (oh, ow) (device); oh / ow above are unused
+    const float *arena;                // VAR: this launch's first image's slot (device); img / ih / iw above are unused
+    const int32_t *in_hw;              // VAR: this launch's first image's (ih, iw) (device)
+    int64_t slot;                      // VAR: floats per slot
 };
 
 __device__ __forceinline__ void tap_axis(const int dst, const int in, const int out, int &i0, int &i1, float &l0, float &l1)
@@ -75,14 +89,15 @@ template <> struct store4<RN_F16> {
     }
 };
 
-template <int DT, bool NHWC, bool FLIP, bool DEV>
+// VAR implies DEV
+template <int DT, bool NHWC, bool FLIP, bool DEV, bool VAR>
 __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArgs a)
 {
     const int b = blockIdx.z;
     const int y = blockIdx.y;
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * TB_PX;
     if (x0 >= a.Wp) return;
-    const int ih = a.ih[b], iw = a.iw[b];
+    const int ih = VAR ? a.in_hw[2 * b] : a.ih[b], iw = VAR ? a.in_hw[2 * b + 1] : a.iw[b];
     int oh, ow;
     if (DEV) {                                                  // device data: clamped to the canvas (<= 0: the image is all padding)
         oh = a.out_hw[2 * b]; ow = a.out_hw[2 * b + 1];
@@ -90,6 +105,7 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
     } else {
         oh = a.oh[b]; ow = a.ow[b];
     }
+    if (VAR && (ih < 1 || iw < 1 || (int64_t)ih * iw > a.slot / 3)) oh = ow = 0;      // device data that no slot can hold (3 * ih * iw > slot): all padding
     const bool flip = FLIP && a.flags[b] != 0;           // source column c of the flipped image is column iw-1-c of img
     float v[3][TB_PX];
 #pragma unroll
@@ -98,7 +114,7 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
         for (int p = 0; p < TB_PX; ++p) v[c][p] = 0.0f;
 
     if (y < oh && x0 < ow) {
-        const float *__restrict__ src = a.img[b];
+        const float *__restrict__ src = VAR ? a.arena + (int64_t)b * a.slot : a.img[b];
         const int64_t plane = (int64_t)ih * iw;
         int y0, y1; float ly0, ly1;
         tap_axis(y, ih, oh, y0, y1, ly0, ly1);
@@ -144,47 +160,59 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
     }
 }
 
-// out_hw: HOST sizes, or null with out_hw_dev (DEVICE i32[B][2]) in their place
-int transform_batch(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, const int32_t *out_hw_dev, int B,
-                    const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype, int channels_last,
-                    const uint8_t *flags, void *stream)
+// out_hw: HOST sizes, or null with out_hw_dev (DEVICE i32[B][2]) in their place; images / in_hw: HOST arrays, or both null with
+// arena / slot / in_hw_dev (the staged images on the DEVICE) in their place -- only together with out_hw_dev
+int transform_batch(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev,
+                    const int32_t *out_hw, const int32_t *out_hw_dev, int B, const float mean[3], const float std[3], int Hp, int Wp,
+                    void *out, int out_dtype, int channels_last, const uint8_t *flags, void *stream)
 {
-    if (!images || !in_hw || (!out_hw == !out_hw_dev) || !mean || !std || !out || B <= 0 || Hp <= 0 || Wp <= 0) return RN_EINVAL;
+    const bool var = arena != nullptr;
+    if ((!out_hw == !out_hw_dev) || !mean || !std || !out || B <= 0 || Hp <= 0 || Wp <= 0) return RN_EINVAL;
+    if (var ? (images || in_hw || !in_hw_dev || !out_hw_dev || slot < 3) : (!images || !in_hw || in_hw_dev))
+        return RN_EINVAL;
     if (out_hw_dev && !rn::aligned(out_hw_dev, 4)) return RN_EALIGN;
+    if (var && (!rn::aligned(arena, 16) || !rn::aligned(in_hw_dev, 4))) return RN_EALIGN;
     if (out_dtype != RN_F32 && out_dtype != RN_BF16 && out_dtype != RN_F16) return RN_EINVAL;
     if (Wp % TB_PX) return RN_EUNSUPPORTED;
     if (Hp > 65535) return RN_EUNSUPPORTED;                     // gridDim.y
     if (!rn::aligned(out, 16)) return RN_EALIGN;
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < B && !var; ++b) {
         if (!images[b] || in_hw[2 * b] <= 0 || in_hw[2 * b + 1] <= 0) return RN_EINVAL;
         if (out_hw && (out_hw[2 * b] <= 0 || out_hw[2 * b + 1] <= 0 || out_hw[2 * b] > Hp || out_hw[2 * b + 1] > Wp)) return RN_EINVAL;
         if (!rn::aligned(images[b], 4)) return RN_EALIGN;
         if (std[0] == 0.0f || std[1] == 0.0f || std[2] == 0.0f) return RN_EINVAL;
     }
+    // (every form refuses a zero std: the list forms in the loop above, where the check has always been, the staged form here)
+    if (var && (std[0] == 0.0f || std[1] == 0.0f || std[2] == 0.0f)) return RN_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const size_t esz = out_dtype == RN_F32 ? 4 : 2;
     for (int b0 = 0; b0 < B; b0 += TB_MAX_IMAGES) {
         TransformArgs a;
         a.B = (B - b0) < TB_MAX_IMAGES ? (B - b0) : TB_MAX_IMAGES;
         for (int i = 0; i < a.B; ++i) {
-            a.img[i] = (const float *)images[b0 + i];
-            a.ih[i] = in_hw[2 * (b0 + i)]; a.iw[i] = in_hw[2 * (b0 + i) + 1];
+            a.img[i] = var ? nullptr : (const float *)images[b0 + i];
+            a.ih[i] = var ? 0 : in_hw[2 * (b0 + i)]; a.iw[i] = var ? 0 : in_hw[2 * (b0 + i) + 1];
             a.oh[i] = out_hw ? out_hw[2 * (b0 + i)] : 0; a.ow[i] = out_hw ? out_hw[2 * (b0 + i) + 1] : 0;
         }
+        a.arena = var ? arena + (int64_t)b0 * slot : nullptr;
+        a.in_hw = var ? in_hw_dev + 2 * b0 : nullptr;
+        a.slot = slot;
         for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std[c]; }
         a.Hp = Hp; a.Wp = Wp;
         a.out = (unsigned char *)out + (size_t)b0 * 3 * Hp * Wp * esz;
         a.flags = flags ? flags + b0 : nullptr;
         a.out_hw = out_hw_dev ? out_hw_dev + 2 * b0 : nullptr;
         const dim3 blk(256), grid((unsigned)((Wp / TB_PX + 255) / 256), (unsigned)Hp, (unsigned)a.B);
-#define RN_TB_LAUNCH_L(DT, FLIP, DEV)                                                                                 \
-        if (channels_last) hipLaunchKernelGGL((transform_batch_kernel<DT, true, FLIP, DEV>), grid, blk, 0, st, a);    \
-        else hipLaunchKernelGGL((transform_batch_kernel<DT, false, FLIP, DEV>), grid, blk, 0, st, a)
-#define RN_TB_LAUNCH(DT)                                                                                              \
-        if (out_hw_dev) {                                                                                             \
-            if (flags) { RN_TB_LAUNCH_L(DT, true, true); } else { RN_TB_LAUNCH_L(DT, false, true); }                  \
-        } else {                                                                                                      \
-            if (flags) { RN_TB_LAUNCH_L(DT, true, false); } else { RN_TB_LAUNCH_L(DT, false, false); }                \
+#define RN_TB_LAUNCH_L(DT, FLIP, DEV, VAR)                                                                                \
+        if (channels_last) hipLaunchKernelGGL((transform_batch_kernel<DT, true, FLIP, DEV, VAR>), grid, blk, 0, st, a);   \
+        else hipLaunchKernelGGL((transform_batch_kernel<DT, false, FLIP, DEV, VAR>), grid, blk, 0, st, a)
+#define RN_TB_LAUNCH(DT)                                                                                                  \
+        if (var) {                                                                                                        \
+            if (flags) { RN_TB_LAUNCH_L(DT, true, true, true); } else { RN_TB_LAUNCH_L(DT, false, true, true); }          \
+        } else if (out_hw_dev) {                                                                                          \
+            if (flags) { RN_TB_LAUNCH_L(DT, true, true, false); } else { RN_TB_LAUNCH_L(DT, false, true, false); }        \
+        } else {                                                                                                          \
+            if (flags) { RN_TB_LAUNCH_L(DT, true, false, false); } else { RN_TB_LAUNCH_L(DT, false, false, false); }      \
         }
         switch (out_dtype) {
             case RN_F32: RN_TB_LAUNCH(RN_F32); break;
@@ -198,14 +226,75 @@ int transform_batch(const void *const *images, const int32_t *in_hw, const int32
     return RN_OK;
 }
 
+// ---- the images of a batch into the slots of a fixed arena (the image capacity mode) -----------------------------------------------
+constexpr int IS_MAX = 64;          // images per launch (kernel-argument table)
+constexpr int IS_BLOCK = 256;
+constexpr int IS_GRID_X = 256;      // blocks per image at most (a grid-stride loop covers the rest)
+
+struct ImageStageTable {
+    const float *src[IS_MAX];
+    int64_t n[IS_MAX];                 // 3 * h * w floats (<= slot: checked on the host)
+    int32_t h[IS_MAX], w[IS_MAX];
+};
+
+// (the table is indexed by blockIdx only: a per-lane index into the argument segment becomes a vector load of the table)
+__global__ __launch_bounds__(IS_BLOCK) void image_stage_kernel(const ImageStageTable t, float *__restrict__ arena, const int64_t slot,
+                                                              int32_t *__restrict__ in_hw, const int base)
+{
+    const int i = blockIdx.y;
+    const float *__restrict__ s = t.src[i];
+    float *__restrict__ d = arena + (int64_t)(base + i) * slot;
+    const int64_t n = t.n[i];
+    const int64_t tid = (int64_t)blockIdx.x * IS_BLOCK + threadIdx.x, step = (int64_t)gridDim.x * IS_BLOCK;
+    // 16-byte copies where both sides allow (exactly n floats of the source are read and of the slot written), 4-byte ones for the rest
+    const int64_t n4 = ((((uintptr_t)s) | ((uintptr_t)d)) & 15) == 0 ? n >> 2 : 0;
+    for (int64_t v = tid; v < n4; v += step) ((rn::f32x4 *)d)[v] = ((const rn::f32x4 *)s)[v];
+    for (int64_t e = n4 * 4 + tid; e < n; e += step) d[e] = s[e];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        in_hw[2 * (base + i)] = t.h[i];
+        in_hw[2 * (base + i) + 1] = t.w[i];
+    }
+}
+
 }  // namespace
+
+RN_API int rn_image_stage(const void *const *images, const int32_t *in_hw, int B, float *arena, int64_t slot, int32_t *in_hw_dev, void *stream)
+{
+    if (!images || !in_hw || !arena || !in_hw_dev || B <= 0 || slot <= 0) return RN_EINVAL;
+    if (!rn::aligned(arena, 16) || !rn::aligned(in_hw_dev, 4)) return RN_EALIGN;
+    // every argument is checked before anything is launched: a rejected call leaves the arena as it was
+    for (int b = 0; b < B; ++b) {
+        const int64_t h = in_hw[2 * b], w = in_hw[2 * b + 1];
+        if (!images[b] || h <= 0 || w <= 0 || h * w > slot / 3) return RN_EINVAL;      // (3 * h * w > slot, without the overflow)
+        if (!rn::aligned(images[b], 4)) return RN_EALIGN;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int base = 0; base < B; base += IS_MAX) {
+        const int cnt = (B - base) < IS_MAX ? (B - base) : IS_MAX;
+        ImageStageTable t;
+        int64_t most = 0;
+        for (int i = 0; i < IS_MAX; ++i) {
+            const bool on = i < cnt;
+            t.src[i] = on ? (const float *)images[base + i] : nullptr;
+            t.h[i] = on ? in_hw[2 * (base + i)] : 0;
+            t.w[i] = on ? in_hw[2 * (base + i) + 1] : 0;
+            t.n[i] = (int64_t)3 * t.h[i] * t.w[i];
+            if (t.n[i] > most) most = t.n[i];
+        }
+        int64_t bx = (most / 4 + IS_BLOCK - 1) / IS_BLOCK;
+        bx = bx < 1 ? 1 : (bx > IS_GRID_X ? IS_GRID_X : bx);
+        hipLaunchKernelGGL(image_stage_kernel, dim3((unsigned)bx, (unsigned)cnt), dim3(IS_BLOCK), 0, st, t, arena, slot, in_hw_dev, base);
+        RN_LAUNCH_CHECK();
+    }
+    return RN_OK;
+}
 
 RN_API int rn_transform_batch(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
                               const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype,
                               int channels_last, void *stream)
 {
     if (!out_hw) return RN_EINVAL;
-    return transform_batch(images, in_hw, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, nullptr, stream);
+    return transform_batch(images, in_hw, nullptr, 0, nullptr, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, nullptr, stream);
 }
 
 RN_API int rn_transform_batch_flip(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
@@ -213,7 +302,7 @@ RN_API int rn_transform_batch_flip(const void *const *images, const int32_t *in_
                                    int channels_last, const uint8_t *flags, void *stream)
 {
     if (!flags || !out_hw) return RN_EINVAL;
-    return transform_batch(images, in_hw, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags, stream);
+    return transform_batch(images, in_hw, nullptr, 0, nullptr, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags, stream);
 }
 
 RN_API int rn_transform_batch_dev(const void *const *images, const int32_t *in_hw, int B, const float mean[3], const float std[3],
@@ -221,5 +310,14 @@ RN_API int rn_transform_batch_dev(const void *const *images, const int32_t *in_h
                                   const uint8_t *flags_or_null, void *stream)
 {
     if (!out_hw_dev) return RN_EINVAL;
-    return transform_batch(images, in_hw, nullptr, out_hw_dev, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags_or_null, stream);
+    return transform_batch(images, in_hw, nullptr, 0, nullptr, nullptr, out_hw_dev, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags_or_null, stream);
+}
+
+RN_API int rn_transform_batch_var(const float *arena, int64_t slot, const int32_t *in_hw_dev, const int32_t *out_hw_dev, int B,
+                                  const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype, int channels_last,
+                                  const uint8_t *flags_or_null, void *stream)
+{
+    if (!arena || !in_hw_dev || !out_hw_dev) return RN_EINVAL;
+    return transform_batch(nullptr, nullptr, arena, slot, in_hw_dev, nullptr, out_hw_dev, B, mean, std, Hp, Wp, out, out_dtype, channels_last,
+                           flags_or_null, stream);
 }

@@ -57,8 +57,21 @@ every call, eager ones included, first stages its GT into the entry's fixed-size
 offsets written on the device); the step then runs on that ``ops.PackedGT``.  The GT kernels read each image's range from the
 device offsets and take the host-side counts only as launch hints, for which the capacity is an upper bound
 (``losses.RetinaNetLosses.forward_levels``).  A batch above the last class keeps the exact-shape key.
+
+Image capacity mode (``image_capacity="auto"`` or a list of padded canvases; needs the GT capacity mode): real detection data has
+images of hundreds of different sizes, and the transform bakes every image's address, input size and resized size into kernel
+arguments, so again nearly every batch is a new signature.  With the mode on, a batch is keyed by its canvas class -- the first
+listed canvas (Hp, Wp) that contains the batch's own padded canvas (``image_canvas_class``; host arithmetic on the image shapes) --
+and its pixel class -- the smallest power of two >= its largest h x w, at least 2**16 (``image_pixel_class``) -- and every call,
+eager ones included, first stages its images into the entry's fixed arena (``ops.image_stage``: B slots of 3 x pixel class fp32, the
+sizes written on the device); the step then runs on that ``ops.StagedImages``.  The resize plan, the box rescale and the transform
+kernel read every input size from device memory (``rn_resize_plan_dev``, ``rn_gt_flip_scale_packed_var``, ``rn_transform_batch_var``)
+and write the class canvas.  The cost: the conv stack processes the class canvas whatever the batch's own canvas was; a finer class
+list trades captures for compute.  A batch that fits no class -- or whose GT fits no capacity class -- keeps the exact-shape key
+and path.  fp32 CHW CUDA images only (uint8 / HWC input is not implemented); training only.
 """
 import ctypes as C
+import math
 import os
 import logging
 from collections import OrderedDict
@@ -104,8 +117,65 @@ def gt_capacity_class(counts: Sequence[int], classes: Sequence[int]) -> Optional
     return None
 
 
+_UNSET = object()                           # "not computed by the caller" (None is a value: no class)
+IMAGE_PIXEL_CLASS_FLOOR = 2 ** 16           # the smallest pixel class (an arena slot is 3 x the class fp32)
+
+
+def _ceil_to(v, d: int) -> int:
+    return int(math.ceil(float(v) / d) * d)           # (transform.GeneralizedRCNNTransform._canvas rounds the same way)
+
+
+def image_capacity_classes(value, transform=None) -> Optional[Tuple[Tuple[int, int], ...]]:
+    """``CapturedTrainStep(image_capacity=...)`` -> the canvas classes: None (off), "auto" or a non-empty sequence of distinct (Hp, Wp)
+    pairs of positive ints, each a multiple of the transform's ``size_divisible``; ValueError for anything else.  "auto" is derived
+    from ``transform``: with m = max(min_size) and M = max_size, both rounded up to ``size_divisible``, [(m, M), (M, m), (M, M)] with
+    duplicates removed -- landscape, portrait, mixed.  Without a transform (``SimpleTrainer``'s constructor) "auto" stays "auto" and a
+    list is checked for everything but divisibility."""
+    if value is None:
+        return None
+    msg = f"image_capacity: expected None, 'auto' or distinct (Hp, Wp) pairs of positive ints, got {value!r}"
+    if isinstance(value, str):
+        if value != "auto":
+            raise ValueError(msg)
+        if transform is None:
+            return "auto"
+        d = int(transform.size_divisible)
+        m, M = _ceil_to(max(transform.min_size), d), _ceil_to(transform.max_size, d)
+        return tuple(dict.fromkeys([(m, M), (M, m), (M, M)]))
+    try:
+        classes = tuple(tuple(c) for c in value)
+    except TypeError:
+        raise ValueError(msg) from None
+    if not classes or any(len(c) != 2 or any(isinstance(v, bool) or not isinstance(v, int) or v <= 0 for v in c) for c in classes) \
+            or len(set(classes)) != len(classes):
+        raise ValueError(msg)
+    if transform is not None:
+        d = int(transform.size_divisible)
+        if any(v % d for c in classes for v in c):
+            raise ValueError(f"image_capacity: every canvas side must be a multiple of the transform's size_divisible ({d}), got {value!r}")
+    return tuple((int(h), int(w)) for h, w in classes)
+
+
+def image_canvas_class(canvas: Sequence[int], classes: Sequence[Tuple[int, int]]) -> Optional[Tuple[int, int]]:
+    "The first listed class that contains the padded canvas (H, W), or None when none does."
+    for hp, wp in classes:
+        if canvas[0] <= hp and canvas[1] <= wp:
+            return (int(hp), int(wp))
+    return None
+
+
+def image_pixel_class(in_hw: Sequence[Tuple[int, int]]) -> int:
+    "The smallest power of two >= the largest h x w of the batch, at least ``IMAGE_PIXEL_CLASS_FLOOR``."
+    most = max((int(h) * int(w) for h, w in in_hw), default=0)
+    return max(IMAGE_PIXEL_CLASS_FLOOR, 1 << max(most - 1, 0).bit_length())
+
+
 def _gt_counts(targets) -> List[int]:
     return [int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets]
+
+
+def _device_of(images) -> torch.device:
+    return images.device if isinstance(images, ops.StagedImages) else images[0].device
 
 
 def _net_targets(targets):
@@ -127,20 +197,21 @@ class _Entry:
         self.images = self.targets = self.losses = self.match_state = None
 
     def hold_inputs(self, images, targets) -> None:
-        """The static inputs every replay reads (copies of this call's; packed GT is static already) and the fused loss kernel's state
-        words: zero-filled here, OUTSIDE the capture, and owned by this entry (``ops.use_match_state``)."""
-        self.images = [im.clone() for im in images]
+        """The static inputs every replay reads (copies of this call's; packed GT and staged images are static already) and the fused
+        loss kernel's state words: zero-filled here, OUTSIDE the capture, and owned by this entry (``ops.use_match_state``)."""
+        self.images = images if isinstance(images, ops.StagedImages) else [im.clone() for im in images]
         self.targets = targets if isinstance(targets, ops.PackedGT) else \
             [{k: (v.clone() if isinstance(v, Tensor) else v) for k, v in t.items()} for t in targets]
-        self.match_state = ops.new_match_state(images[0].device)
+        self.match_state = ops.new_match_state(_device_of(images))
 
 
 class _Signature:
-    "What one input signature owns: the GT staging buffers of the capacity mode and an ``_Entry`` per kind of step."
-    __slots__ = ("packed", "steps")
+    "What one input signature owns: the GT staging buffers and the image arena of the capacity modes and an ``_Entry`` per kind of step."
+    __slots__ = ("packed", "staged", "steps")
 
-    def __init__(self, packed=None):
+    def __init__(self, packed=None, staged=None):
         self.packed = packed      # GT capacity mode: ops.PackedGT (B x class rows), staged before every call of either kind
+        self.staged = staged      # image capacity mode: ops.StagedImages (B slots of 3 x pixel class), staged the same way
         self.steps = {}           # final -> _Entry.  Without gradient accumulation every step is final
 
 
@@ -255,7 +326,7 @@ def apply_gradients(optimizer, scaler, source=None) -> None:
 class CapturedTrainStep:
     def __init__(self, net, optimizer, ddp=None, amp_dtype: Optional[torch.dtype] = torch.bfloat16, eager_steps: int = 2,
                  max_graphs: int = 4, enabled: bool = True, segmented: Optional[bool] = None, scaler=None, gt_capacity=None,
-                 accumulate=None):
+                 accumulate=None, image_capacity=None):
         """``segmented`` (default: on whenever gradients are exchanged): the step with a gradient exchange as FOUR linear hipGraphs --
         forward + head / FPN backward | layer4, layer3 backward | layer2 .. stem backward | optimizer -- with the finished buckets'
         all-reduces issued EAGERLY on the process group's communication stream between the replays and the wait for them in
@@ -267,8 +338,17 @@ class CapturedTrainStep:
         or increasing positive ints -- the GT capacity mode of the module docstring.
         ``accumulate``: None (default) or an ``optim.GradAccumulator`` -- gradient accumulation.  A call is then a micro step (forward,
         backward, accumulate) or a final step (the same, then clip + optimizer step on the accumulators): ``stepper(images, targets,
-        final=...)``, the default being the accumulator's own count (every ``accumulate.n``-th call is final).  Single process only."""
+        final=...)``, the default being the accumulator's own count (every ``accumulate.n``-th call is final).  Single process only.
+        ``image_capacity``: None (default: the exact image shapes are part of the signature), "auto" (three canvases derived from the
+        net's transform) or a list of padded canvases (Hp, Wp) -- the image capacity mode of the module docstring.  Needs
+        ``gt_capacity``: real data varies in both, and the staged path rescales packed GT only."""
         self.gt_capacity = gt_capacity_classes(gt_capacity)
+        self.image_capacity = image_capacity_classes(image_capacity, getattr(net, "transform", None))
+        if self.image_capacity is not None:
+            if self.gt_capacity is None:
+                raise ValueError("image_capacity needs gt_capacity as well (\"auto\" or a class list): the staged path rescales packed GT only")
+            if self.image_capacity == "auto":
+                raise ValueError("image_capacity='auto' needs a net with a transform to derive the canvases from")
         if accumulate is not None:
             from .optim import GradAccumulator
             if not isinstance(accumulate, GradAccumulator):
@@ -305,10 +385,11 @@ class CapturedTrainStep:
         "The forward pass under autocast -> (the net's loss dict, the sum of the two losses)."
         from .losses import grad_prescale, scaler_prescale
         # fp16: the loss kernel multiplies the GradScaler's scale into its gradients before it rounds them to fp16 (losses.grad_prescale)
-        pre = scaler_prescale(self.scaler, images[0].device) if images[0].is_cuda else None
-        with torch.autocast(images[0].device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None, cache_enabled=False), \
+        dev = _device_of(images)
+        pre = scaler_prescale(self.scaler, dev) if dev.type == "cuda" else None
+        with torch.autocast(dev.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None, cache_enabled=False), \
                 grad_prescale(pre):
-            losses = self.net(list(images), _net_targets(targets))
+            losses = self.net(images if isinstance(images, ops.StagedImages) else list(images), _net_targets(targets))
             total = losses["classification_loss"] + losses["regression_loss"]
         return losses, total
 
@@ -380,7 +461,24 @@ class CapturedTrainStep:
         "The batch's capacity class, or None (mode off, or a count above the last class: exact-shape keying)."
         return None if self.gt_capacity is None else gt_capacity_class(_gt_counts(targets), self.gt_capacity)
 
-    def _signature(self, images, targets) -> tuple:
+    def _image_class_of(self, images, targets, cap=_UNSET) -> Optional[Tuple[Tuple[int, int], int, List[Tuple[int, int]]]]:
+        """The batch's (canvas class, pixel class, per-image resized bounds), or None: mode off, GT above its last class (the staged
+        path takes packed GT; ``cap``: the batch's GT class when the caller has it), images the fused transform does not take, a short
+        side drawn on the host, or a canvas no class contains -- exact-shape keying then.  Host arithmetic on the image shapes; nothing
+        synchronises.  ``__call__`` computes it ONCE per step and hands it to ``_signature`` and, as ``StagedImages.bounds``, to the
+        transform."""
+        if self.image_capacity is None or (self._capacity_of(targets) if cap is _UNSET else cap) is None:
+            return None
+        tr = self.net.transform
+        if not tr._fusable(list(images)) or (getattr(tr, "scale_jitter", None) is None and tr.staged_short_side() is None):
+            return None
+        in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
+        bounds = tr.staged_bounds(in_hw)
+        canvas = image_canvas_class(tr._canvas(bounds), self.image_capacity)
+        return None if canvas is None else (canvas, image_pixel_class(in_hw), bounds)
+
+    def _signature(self, images, targets, cap=_UNSET, icls=_UNSET) -> tuple:
+        "``cap`` / ``icls``: the batch's GT class and image class when the caller has computed them (``__call__``); else computed here."
         if getattr(self.optimizer, "_rn_device_hparams", False):
             # (optim.MasterAdam / MasterAdamW: the kernels read lr / betas / eps / weight_decay from device blocks that
             # sync_device_hparams() refreshes before every replay -- a per-step LR schedule keeps one graph)
@@ -388,8 +486,14 @@ class CapturedTrainStep:
         else:
             groups = tuple((g.get("lr"), g.get("momentum"), g.get("weight_decay"), g.get("dampening"), g.get("nesterov"))
                            for g in self.optimizer.param_groups)
-        ims = tuple((tuple(im.shape), im.dtype, im.device) for im in images)
-        cap = self._capacity_of(targets)
+        if cap is _UNSET:
+            cap = self._capacity_of(targets)
+        if icls is _UNSET:
+            icls = self._image_class_of(images, targets, cap)
+        if icls is not None:
+            ims = ("img_cap", len(images), icls[0], icls[1], images[0].dtype, images[0].device)      # (the entry's arena: B slots)
+        else:
+            ims = tuple((tuple(im.shape), im.dtype, im.device) for im in images)
         if cap is not None:
             tgs = ("gt_cap", cap)          # (the entry's packed buffers are B x cap rows; B is in the image shapes)
         else:
@@ -419,7 +523,7 @@ class CapturedTrainStep:
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."
-        dev = images[0].device
+        dev = _device_of(images)
         e.hold_inputs(images, targets)
         e.pool = torch.cuda.graph_pool_handle()
         e.segments, e.bucket_ids = [], []
@@ -520,11 +624,14 @@ class CapturedTrainStep:
         final = bool(final)
         if not self.enabled or not images or not images[0].is_cuda:
             return self._step(images, targets, final)
-        key = self._signature(images, targets)
         cap = self._capacity_of(targets)
+        icls = self._image_class_of(images, targets, cap)          # (once per step: the key, the arena and the transform's bounds)
+        key = self._signature(images, targets, cap, icls)
+        dev = images[0].device
         sig = self._entries.get(key)
         if sig is None:
-            sig = self._entries[key] = _Signature(ops.PackedGT.empty(len(images), cap, images[0].device) if cap is not None else None)
+            sig = self._entries[key] = _Signature(ops.PackedGT.empty(len(images), cap, dev) if cap is not None else None,
+                                                  ops.new_image_arena(len(images), icls[1], dev, icls[0]) if icls is not None else None)
             while len(self._entries) > self.max_graphs:
                 self._entries.popitem(last=False)            # drops the signature's graphs and their private memory pools
         else:
@@ -539,6 +646,11 @@ class CapturedTrainStep:
             # the capture and replays alike; the step itself then reads nothing but sig.packed
             ops.gt_stage([t["boxes"] for t in targets], [t["labels"] for t in targets], sig.packed)
             targets = sig.packed
+        if sig.staged is not None:
+            # image capacity mode: this batch's images into the signature's arena and their sizes next to them (one launch per 64
+            # images, current stream), for eager steps, the capture and replays alike; the step reads nothing but sig.staged
+            ops.image_stage(images, sig.staged, bounds=icls[2])
+            images = sig.staged
         if e.failed or e.calls <= self.eager_steps:
             return self._step(images, targets, final)
         if e.graph is None and e.segments is None:
@@ -551,7 +663,7 @@ class CapturedTrainStep:
                 torch.cuda.synchronize()                      # (the capture's side stream has been joined by _capture_segments' finally)
                 if self.ddp is not None:
                     self.ddp.reset()
-                stuck = _device_usable(images[0].device)
+                stuck = _device_usable(dev)
                 if stuck is not None:
                     raise CaptureUnwindError(f"the failed capture ({type(exc).__name__}: {exc}) left the device in stream-capture mode "
                                              f"({type(stuck).__name__}: {stuck}); this process cannot run further GPU work") from exc
@@ -560,7 +672,7 @@ class CapturedTrainStep:
             # the step's inputs into the graph's static buffers: one multi-tensor launch per dtype for what already lives on the
             # device (24 separate copies cost 0.19 ms per step), plain copies for the rest
             dsts, srcs = [], []
-            pairs = list(zip(e.images, images))
+            pairs = list(zip(e.images, images)) if sig.staged is None else []
             if sig.packed is None:
                 pairs += [(dt[k], v) for dt, st in zip(e.targets, targets) for k, v in st.items() if isinstance(v, Tensor)]
             for dst, src in pairs:

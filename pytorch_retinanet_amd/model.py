@@ -219,13 +219,15 @@ class SimpleTrainer:
     ``fit`` (train + optional validation, scheduler stepping per the hparams contract) and ``test``.
     Under ``torch.distributed`` every rank runs this loop on its own shard of the dataset (``DistributedSampler``),
     gradients are averaged by ``BucketedGradAllReduce`` and the validation loss is averaged over ranks before it
-    reaches a monitoring scheduler.  Validation runs in ``eval()`` mode like Lightning's (BN buffers untouched)."""
+    reaches a monitoring scheduler.  Validation runs in ``eval()`` mode like Lightning's (BN buffers untouched).
+    After ``fit``: ``captured_steps`` = the steps served by a graph replay, ``captured_graphs`` = the graphs captured for them (one per
+    input signature that reached a replay; with the capacity modes: one per class met)."""
 
     def __init__(self, max_epochs: int = 1, device: Optional[str] = None, precision: str = "bf16",
                  channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True,
                  gt_capacity=None, gradient_clip_val: float = 0.0, accumulate_grad_batches: int = 1,
                  weight_ema_decay: float = 0.0, weight_ema_warmup: float = 0.0, device_scale_jitter: bool = False,
-                 scale_jitter_seed: int = 0):
+                 scale_jitter_seed: int = 0, image_capacity=None):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
@@ -267,8 +269,13 @@ class SimpleTrainer:
         (``self.scale_jitter``; under ``torch.distributed`` rank r draws from seed + r): the short side of every image is drawn on the
         device over a canvas sized for the largest entry, so one graph replays while the scales vary.  Without it a ``min_size`` tuple
         is drawn on the host, which changes the canvas -- and with it the graph signature -- at nearly every step.  A single-entry
-        ``min_size`` installs nothing and logs one line.  The cost: the whole canvas is processed whatever was drawn."""
-        from .graph import gt_capacity_classes
+        ``min_size`` installs nothing and logs one line.  The cost: the whole canvas is processed whatever was drawn.
+
+        ``image_capacity`` (None = off; left None, an optional ``trainer.image_capacity`` in the hparams is honoured): passed to the
+        ``CapturedTrainStep`` -- "auto" or a list of padded canvases (Hp, Wp) keys batches by canvas class and pixel class instead of
+        by their images' exact shapes, so data whose images differ in size still replays.  Needs ``gt_capacity``.  The cost: the conv
+        stack processes the class canvas whatever the batch's own canvas was."""
+        from .graph import gt_capacity_classes, image_capacity_classes
         from .optim import check_accumulate_grad_batches
         self.accumulate_grad_batches = check_accumulate_grad_batches(accumulate_grad_batches)
         self.grad_accumulator = None                      # the optim.GradAccumulator of the last fit() (master optimizers on CUDA)
@@ -286,8 +293,13 @@ class SimpleTrainer:
         self.scale_jitter = None                          # the augment.RandomShortSide of the last fit()
         gt_capacity_classes(gt_capacity)                  # (bad values fail here, not at the first step)
         self.gt_capacity = gt_capacity
+        image_capacity_classes(image_capacity)            # (the same: divisibility by the net's size_divisible is checked in fit())
+        if image_capacity is not None and gt_capacity is None:
+            raise ValueError("image_capacity needs gt_capacity as well (\"auto\" or a class list)")
+        self.image_capacity = image_capacity
         self.max_epochs, self.max_steps, self.log_every, self.capture = max_epochs, max_steps, log_every, capture
         self.captured_steps = 0
+        self.captured_graphs = 0                          # captures of the last fit() (one per input signature that reached a replay)
         self.device = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
         self.amp_dtype = {"bf16": torch.bfloat16, "16": torch.float16, "32": None}[str(precision)]
         self.channels_last = channels_last
@@ -338,6 +350,16 @@ class SimpleTrainer:
             return True
         section = conf.get("trainer") if hasattr(conf, "get") else None
         return bool((section or {}).get("device_scale_jitter") or False)
+
+    def resolve_image_capacity(self, conf):
+        "The constructor's ``image_capacity`` or, when that is None, ``trainer.image_capacity`` of the hparams (absent: off)."
+        if self.image_capacity is not None:
+            return self.image_capacity
+        section = conf.get("trainer") if hasattr(conf, "get") else None
+        value = (section or {}).get("image_capacity")
+        if value is None or isinstance(value, str):
+            return value
+        return [tuple(int(v) if int(v) == v else v for v in c) for c in value]      # (a YAML list of [Hp, Wp] lists)
 
     def _install_scale_jitter(self, model, rank: Optional[int]) -> None:
         "``fit``'s part of ``device_scale_jitter``: a ``RandomShortSide`` over the transform's ``min_size`` tuple, or one log line."
@@ -441,7 +463,8 @@ class SimpleTrainer:
             from .graph import CapturedTrainStep
             # (device accumulation without capture: the same step object runs eagerly, so the gradients are still summed in fp32)
             stepper = CapturedTrainStep(model.net, optimizer, None, amp_dtype=self.amp_dtype, scaler=scaler, gt_capacity=self.gt_capacity,
-                                        accumulate=self.grad_accumulator, enabled=bool(capturable))
+                                        accumulate=self.grad_accumulator, enabled=bool(capturable),
+                                        image_capacity=self.resolve_image_capacity(model.conf))
         step = 0
         for epoch in range(self.max_epochs):
             model.train()
@@ -457,7 +480,7 @@ class SimpleTrainer:
                     images, targets, _ = batch
                     tgs = [{k: v for k, v in t.items() if isinstance(v, torch.Tensor) and k in ("boxes", "labels")} for t in targets]
                     out = stepper(list(images), tgs, final=final) if device_acc else stepper(list(images), tgs)
-                    self.captured_steps = stepper.replays
+                    self.captured_steps, self.captured_graphs = stepper.replays, stepper.captures
                 else:
                     # the plain thing: every micro-batch adds (loss / N)'s gradients into .grad; zero at the start of a window, step at
                     # its end (N = 1: every batch is a window)

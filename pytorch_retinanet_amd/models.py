@@ -121,10 +121,18 @@ class Retinanet(nn.Module):
         """Losses of the batch (models.py:274-288).  The reference requires `targets`
         (its Lightning wrapper's ``forward`` therefore raises); here
         ``targets=None`` means inference and returns ``predict(images)``.  ``targets`` may also be packed GT
-        (``ops.PackedGT``, staged by ``ops.gt_stage``: the GT capacity mode of ``graph.CapturedTrainStep``)."""
+        (``ops.PackedGT``, staged by ``ops.gt_stage``: the GT capacity mode of ``graph.CapturedTrainStep``), and ``images`` staged
+        images (``ops.StagedImages``, staged by ``ops.image_stage``: its image capacity mode; training mode only) -- they go to
+        the transform as they are, with the canvas they carry."""
         if targets is None:
             return self.predict(images)
-        images, targets = self.transform(images, targets, **self._batch_layout())
+        from .transform import _is_staged
+        if _is_staged(images):
+            if not self.training:
+                raise ValueError("staged images (ops.StagedImages) are a training input")
+            images, targets = self.transform(images, targets, canvas=images.canvas, **self._batch_layout())
+        else:
+            images, targets = self.transform(images, targets, **self._batch_layout())
         batch = images.tensors
         if self.backbone.backbone.conv1.weight.is_contiguous(memory_format=torch.channels_last):
             batch = batch.contiguous(memory_format=torch.channels_last)        # no-op after the fused transform

@@ -823,6 +823,133 @@ def gt_flip_scale_packed_dev(gt: PackedGT, widths: Sequence[float], ratios: Tens
     return gt.with_boxes(out)
 
 
+# ---- images of varying sizes in a fixed arena (graph.CapturedTrainStep, image capacity mode) ----------------------------------
+class StagedImages:
+    """The images of a batch in a fixed-size device arena (``graph.CapturedTrainStep``'s image capacity mode): ``arena`` f32 [B, slot]
+    -- image b dense at the start of row b, ``[3][h_b][w_b]`` with its own strides -- and ``in_hw`` i32 [B, 2] = its (h, w), as
+    ``image_stage`` writes them.  The kernels read every input size from ``in_hw``; the host keeps the bounds: ``slot`` (floats per
+    image, 3 x the pixel class) and ``canvas`` (the padded (Hp, Wp) of the batch's canvas class, set by whoever owns the arena).
+    ``hw`` is the host's list of the (h, w) staged last and ``bounds`` the per-image sizes after the resize that whoever staged them
+    worked out from it (None: the transform works them out): for canvas and bound arithmetic only, no kernel argument is derived
+    from either.  Floats [3 h_b w_b, slot) of a row hold whatever they held before: no kernel reads them."""
+    __slots__ = ("arena", "in_hw", "B", "slot", "hw", "bounds", "canvas")
+
+    def __init__(self, arena: Tensor, in_hw: Tensor, canvas: Optional[Tuple[int, int]] = None):
+        if arena.dim() != 2 or arena.dtype != torch.float32 or not arena.is_contiguous():
+            raise ValueError(f"arena must be a contiguous f32 [B, slot] tensor, got {tuple(arena.shape)} {arena.dtype}")
+        if in_hw.dtype != torch.int32 or tuple(in_hw.shape) != (arena.shape[0], 2) or not in_hw.is_contiguous() or in_hw.device != arena.device:
+            raise ValueError(f"in_hw must be a contiguous int32 [{arena.shape[0]}, 2] tensor on {arena.device}")
+        self.arena, self.in_hw = arena, in_hw
+        self.B, self.slot = int(arena.shape[0]), int(arena.shape[1])
+        self.hw: List[Tuple[int, int]] = []
+        self.bounds: Optional[List[Tuple[int, int]]] = None
+        self.canvas = None if canvas is None else (int(canvas[0]), int(canvas[1]))
+
+    @property
+    def device(self) -> torch.device:
+        return self.arena.device
+
+    def __len__(self) -> int:
+        return self.B
+
+    @classmethod
+    def empty(cls, B: int, pixel_class: int, dev: torch.device, canvas: Optional[Tuple[int, int]] = None) -> "StagedImages":
+        "An arena for B images of at most ``pixel_class`` pixels each (uninitialised: ``image_stage`` fills it)."
+        return cls(torch.empty((int(B), 3 * int(pixel_class)), dtype=torch.float32, device=dev),
+                   torch.empty((int(B), 2), dtype=torch.int32, device=dev), canvas)
+
+
+def new_image_arena(B: int, pixel_class: int, dev: torch.device, canvas: Optional[Tuple[int, int]] = None) -> StagedImages:
+    "``StagedImages.empty``: the arena a signature of the image capacity mode owns (B slots of 3 x ``pixel_class`` fp32)."
+    return StagedImages.empty(B, pixel_class, dev, canvas)
+
+
+def image_stage(images: Sequence[Tensor], out: StagedImages, bounds: Optional[Sequence[Tuple[int, int]]] = None) -> StagedImages:
+    """The images (CUDA f32 ``[3, h_b, w_b]`` on ``out``'s device) into ``out``'s arena, ``in_hw`` = their sizes: one launch per 64
+    images (``rn_image_stage``) on the current stream; no host copy, no synchronisation.  Strided images are made dense first.
+    ValueError for another dtype or layout (uint8 / HWC input is not implemented), a zero size or an image above the slot.
+    ``bounds``: the per-image sizes after the resize, when the caller has them (kept as ``out.bounds`` for the transform)."""
+    dev = _need_dev(out.arena, *images)
+    B = len(images)
+    if B != out.B:
+        raise ValueError(f"{B} images for an arena of {out.B} slots")
+    imgs, hw = [], []
+    for im in images:
+        if im.dim() != 3 or im.shape[0] != 3 or im.dtype != torch.float32:
+            raise ValueError(f"image_stage expects f32 [3, h, w] images, got {tuple(im.shape)} {im.dtype}")
+        h, w = int(im.shape[1]), int(im.shape[2])
+        if h <= 0 or w <= 0 or 3 * h * w > out.slot:
+            raise ValueError(f"a {h} x {w} image does not fit an arena slot of {out.slot} floats")
+        imgs.append(im if im.is_contiguous() else im.contiguous())
+        hw.append((h, w))
+    with torch.cuda.device(dev), _timed("image_stage", dev):
+        check(lib.rn_image_stage((C.c_void_p * B)(*[im.data_ptr() for im in imgs]), (C.c_int32 * (2 * B))(*[v for s in hw for v in s]), B,
+                                 _ptr(out.arena), out.slot, _ptr(out.in_hw), _stream(dev)), "rn_image_stage")
+    if bounds is not None and len(bounds) != B:
+        raise ValueError(f"{len(bounds)} bounds for {B} images")
+    out.hw, out.bounds = hw, (None if bounds is None else [(int(h), int(w)) for h, w in bounds])
+    return out
+
+
+def resize_plan_dev(block: Optional[Tensor], in_hw: Tensor, short: Optional[int], max_size: int) -> Tuple[Tensor, Tensor]:
+    """``rn_resize_plan_dev``: ``short_side_draw`` with the input sizes on the device (``in_hw`` int32 [B, 2], as ``image_stage`` writes
+    it) -> (resized sizes int32 [B, 2], box ratios f32 [2B]).  With ``block`` (an ``rn_short_side_state``) the short sides are drawn
+    as ``short_side_draw`` draws them and the block's counter advances by one; with ``block=None`` every image gets ``short``.
+    One launch for any B on the current stream, no host synchronisation (capturable)."""
+    dev = _need_dev(in_hw) if block is None else _check_short_side_block(block)
+    if in_hw.dtype != torch.int32 or in_hw.dim() != 2 or in_hw.shape[1] != 2 or not in_hw.is_contiguous() or in_hw.device != dev:
+        raise ValueError(f"in_hw must be a contiguous int32 [B, 2] tensor on {dev}, got {tuple(in_hw.shape)} {in_hw.dtype} on {in_hw.device}")
+    B = int(in_hw.shape[0])
+    if B == 0:
+        raise ValueError("need at least one image size")
+    if block is None and (short is None or int(short) != short or int(short) <= 0):
+        raise ValueError(f"without a state block the short side must be a positive integer, got {short!r}")
+    out_hw = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    ratios = torch.empty((2 * B,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("resize_plan_dev", dev):
+        check(lib.rn_resize_plan_dev(_ptr(block), _ptr(in_hw), 0 if block is not None else int(short), int(max_size), B, _ptr(out_hw),
+                                     _ptr(ratios), _stream(dev)), "rn_resize_plan_dev")
+    return out_hw, ratios
+
+
+def transform_batch_var(staged: StagedImages, out_hw: Tensor, mean: Sequence[float], std: Sequence[float], Hp: int, Wp: int,
+                        out_dtype: torch.dtype = torch.float32, channels_last: bool = False, flags: Optional[Tensor] = None) -> Tensor:
+    """``transform_batch_dev`` on staged images (``rn_transform_batch_var``): image b from the arena's slot b, its size from
+    ``staged.in_hw`` and its output size from ``out_hw`` (int32 [B, 2], ``resize_plan_dev``), all read on the device; a size no slot
+    can hold leaves the image all padding.  Bit-identical to ``transform_batch`` called with the same sizes and canvas on the host."""
+    dev = _need_dev(staged.arena, staged.in_hw, out_hw)
+    B = staged.B
+    if out_hw.dtype != torch.int32 or tuple(out_hw.shape) != (B, 2) or not out_hw.is_contiguous():
+        raise ValueError(f"out_hw must be a contiguous int32 [{B}, 2] tensor, got {tuple(out_hw.shape)} {out_hw.dtype}")
+    if flags is not None:
+        _check_flags(flags, B, dev)
+    if out_dtype not in _DT:
+        raise ValueError(f"unsupported output dtype {out_dtype}")
+    out = torch.empty((B, 3, Hp, Wp), dtype=out_dtype, device=dev,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    with torch.cuda.device(dev), _timed("transform_batch", dev):
+        check(lib.rn_transform_batch_var(_ptr(staged.arena), staged.slot, _ptr(staged.in_hw), _ptr(out_hw), B, (C.c_float * 3)(*mean),
+                                         (C.c_float * 3)(*std), int(Hp), int(Wp), _ptr(out), _DT[out_dtype], int(bool(channels_last)),
+                                         _ptr(flags), _stream(dev)), "rn_transform_batch_var")
+    return out
+
+
+def gt_flip_scale_packed_var(gt: PackedGT, in_hw: Tensor, ratios: Tensor, flags: Optional[Tensor] = None) -> PackedGT:
+    """``gt_flip_scale_packed_dev`` with the original widths on the device too (``in_hw`` int32 [B, 2], ``StagedImages.in_hw``) --
+    ``rn_gt_flip_scale_packed_var``, out of place, bit-identical given the same values."""
+    dev = _need_dev(gt.gt_boxes, gt.gt_off, in_hw, ratios, flags)
+    if in_hw.dtype != torch.int32 or tuple(in_hw.shape) != (gt.B, 2) or not in_hw.is_contiguous():
+        raise ValueError(f"in_hw must be a contiguous int32 [{gt.B}, 2] tensor, got {tuple(in_hw.shape)} {in_hw.dtype}")
+    _check_ratios_dev(ratios, gt.B, dev)
+    if flags is not None:
+        _check_flags(flags, gt.B, dev)
+    out = torch.empty_like(gt.gt_boxes)
+    with torch.cuda.device(dev), _timed("gt_flip_scale_packed", dev):
+        check(lib.rn_gt_flip_scale_packed_var(_ptr(gt.gt_boxes), _ptr(out), _ptr(gt.gt_off), _ptr(in_hw), _ptr(ratios), _ptr(flags), gt.B,
+                                              gt.rows, gt.cap_per_image, _stream(dev)), "rn_gt_flip_scale_packed_var")
+    return gt.with_boxes(out)
+
+
 def decode_clip(deltas: Tensor, anchors: Tensor, image_hw: Optional[Tensor],
                 reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0)) -> Tensor:
     """K4.  deltas [B,A,4] or [A,4]; image_hw i32 [B,2] (device) or None.  -> f32 boxes, same leading shape."""

@@ -35,6 +35,13 @@ upper-bound sizes, not the drawn ones -- the training pass does not read them be
 loss are laid out on the padded canvas).  The PyTorch path draws the same sizes from the Python restatement, resizes each image
 with ``resize`` and pads the batch to the same canvas.  The known cost: the whole canvas is processed whatever was drawn, so small
 draws save no compute.  ``scale_jitter`` is a plain attribute too.
+
+Staged images (``forward(ops.StagedImages, packed GT, canvas=(Hp, Wp))``: the image capacity mode of ``graph.CapturedTrainStep``):
+the batch lies in a fixed device arena with its sizes next to it (``ops.image_stage``), and nothing this call launches takes an
+image's address or size as an argument -- the resize plan (``rn_resize_plan_dev``: the fixed short side, or the ``scale_jitter``'s
+draw), the boxes (``rn_gt_flip_scale_packed_var``) and the transform kernel (``rn_transform_batch_var``) read them on the device, over
+the canvas the caller fixed.  Training mode, packed GT and the fused path only.  The result is bit-identical to the list path's on
+the same canvas; the cost is the jitter's: the conv stack processes the whole class canvas whatever the batch's own canvas was.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -76,6 +83,13 @@ def _is_packed(targets) -> bool:
         return False
     from .ops import PackedGT
     return isinstance(targets, PackedGT)
+
+
+def _is_staged(images) -> bool:
+    if isinstance(images, (list, tuple)):
+        return False
+    from .ops import StagedImages
+    return isinstance(images, StagedImages)
 
 
 def resize_boxes(boxes: Tensor, original_size: Sequence[int], new_size: Sequence[int]) -> Tensor:
@@ -227,12 +241,70 @@ class GeneralizedRCNNTransform(nn.Module):
         batch = ops.transform_batch(images, sizes, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags)
         return ImageList(batch, sizes), targets
 
+    def staged_short_side(self) -> Optional[int]:
+        """The short side the staged path passes to the device when no ``scale_jitter`` is installed, or None when that path cannot
+        serve this transform in training: a ``min_size`` tuple drawn on the host changes from step to step (install an
+        ``augment.RandomShortSide``), and the device plan takes integers."""
+        if len(self.min_size) != 1 or int(self.min_size[0]) != self.min_size[0] or int(self.max_size) != self.max_size:
+            return None
+        return int(self.min_size[0])
+
+    def staged_bounds(self, in_hw: Sequence[Tuple[int, int]]) -> List[Tuple[int, int]]:
+        """Host arithmetic on the raw sizes alone: per image the size after the resize -- with a ``scale_jitter`` installed the upper
+        bound of every size it can draw (``jitter.bound``).  The natural canvas of a staged batch is ``_canvas`` over these."""
+        jitter = self.scale_jitter
+        if jitter is not None:
+            return [jitter.bound(int(h), int(w), self.max_size) for h, w in in_hw]
+        short = self.staged_short_side()               # (the value the device plan gets: bound and plan cannot drift apart)
+        if short is None:
+            raise ValueError(f"staged images need one integer min_size and an integer max_size (got {self.min_size}, {self.max_size}), "
+                             "or an augment.RandomShortSide as scale_jitter")
+        short = float(short)
+        out = []
+        for h, w in in_hw:
+            scale = self._scale_for(int(h), int(w), short)
+            out.append((int(math.floor(h * scale)), int(math.floor(w * scale))))
+        return out
+
+    def _forward_staged(self, staged, targets, canvas, out_dtype: torch.dtype, channels_last: bool):
+        "Staged images over a fixed canvas: every input size is read on the device (module docstring)."
+        from . import ops
+        if not self.training or not _is_packed(targets):
+            raise ValueError("staged images (ops.StagedImages) are a training input and come with packed GT (ops.PackedGT)")
+        if targets.B != staged.B or len(staged.hw) != staged.B:
+            raise ValueError(f"packed GT of {targets.B} images for {len(staged.hw)} staged images in an arena of {staged.B}")
+        if canvas is None:
+            raise ValueError("staged images need canvas=(Hp, Wp)")
+        if not (len(self.image_mean) == 3 and len(self.image_std) == 3 and self.size_divisible % 4 == 0):
+            raise ValueError("staged images take the fused transform only: 3 channels, size_divisible a multiple of 4")
+        hp, wp = int(canvas[0]), int(canvas[1])
+        bounds = staged.bounds if staged.bounds is not None else self.staged_bounds(staged.hw)      # (the stager's, when it has them)
+        need = self._canvas(bounds)
+        if need[0] > hp or need[1] > wp:
+            raise ValueError(f"canvas {hp} x {wp} does not contain the batch's own canvas {need[0]} x {need[1]}")
+        flags = self.hflip.next_flags(staged.B, staged.device) if self.hflip is not None else None
+        jitter = self.scale_jitter
+        if jitter is not None:
+            out_hw, ratios = jitter.next_sizes_dev(staged.in_hw, self.max_size)
+        else:
+            # (staged_short_side() is not None here: staged_bounds / the stager checked it)
+            out_hw, ratios = ops.resize_plan_dev(None, staged.in_hw, self.staged_short_side(), int(self.max_size))
+        # (launched whatever the ratios are: the host cannot know them; a ratio of 1 leaves a row bit for bit as it was)
+        targets = ops.gt_flip_scale_packed_var(targets, staged.in_hw, ratios, flags)
+        batch = ops.transform_batch_var(staged, out_hw, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags)
+        return ImageList(batch, bounds), targets
+
     # -- whole transform -----------------------------------------------------------------
     def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None,
-                out_dtype: Optional[torch.dtype] = None, channels_last: bool = False):
+                out_dtype: Optional[torch.dtype] = None, channels_last: bool = False, canvas: Optional[Tuple[int, int]] = None):
         """``out_dtype`` / ``channels_last``: layout hints for the fused CUDA path (defaults: fp32, NCHW --
         what torchvision's transform returns); ignored by the PyTorch fallback.  ``targets`` may be packed GT (``ops.PackedGT``):
-        its boxes are rescaled per image on the device (``rn_gt_scale_packed``) and a PackedGT comes back."""
+        its boxes are rescaled per image on the device (``rn_gt_scale_packed``) and a PackedGT comes back.  ``images`` may be staged
+        images (``ops.StagedImages``) with ``canvas`` = the padded (Hp, Wp) to produce: the module docstring's last paragraph."""
+        if _is_staged(images):
+            return self._forward_staged(images, targets, canvas, out_dtype or torch.float32, channels_last)
+        if canvas is not None:
+            raise ValueError("canvas= goes with staged images (ops.StagedImages) only")
         images = list(images)
         packed = _is_packed(targets)
         if packed:
