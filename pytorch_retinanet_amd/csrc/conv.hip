@@ -1040,6 +1040,7 @@ struct WgradArgs {
     // every workgroup fetching its own copy (the gathered class-output gradient + activations are 388 MB, the 36 copies 6.1 GB);
     // the (xcd_units - 32) units per split that do not fit XCD s's 32 CUs run on XCD 7.  Host: S <= 7, (xcd_units - 32) * S <= 32.
     int xcd_units;
+    int row_tiles;                              // tap-row kernel: tiles of 128 output channels (its xcd_units: 3 * row_tiles, see there)
 };
 
 // GATHER = false: G and X are canvases (the head towers).  GATHER = true: the gradient operand is gathered, position by
@@ -1287,6 +1288,253 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_wgrad_kernel(const Wgrad
                 out[row * 256 + col] = acc[mi][ni][r];
             }
         }
+}
+
+// TAP-ROW form of the gathering weight gradient (the class-output conv, row_elems > 64).  The three horizontal taps of kernel row
+// kh contract the SAME gradient tile against activation tiles that are the same canvas rows shifted by -1 / 0 / +1 position, so
+// one workgroup per (position split, kernel row, tile of 128 output channels) accumulates all three: per K-tile of 64 positions
+// it stages ONE gathered G tile (64 x 128 channels, 16 KiB) and ONE X band of 66 positions m - 1 .. m + 64, shifted by
+// (kh - 1) * Wp (33 KiB), where the tap-per-workgroup kernel above stages 32 + 32 KiB for a third of the MFMAs.  Tap kw reads its
+// X fragments from the band at row offset kw; the swizzle is keyed on the BAND row ((row & 3) << 2 on the 16-byte chunk index,
+// as above), so a transposing read's 4 rows still carry 4 different keys at any shift.
+// 8 waves of 128(n) x 32(c) x 3 taps: 12 accumulator tiles = 192 registers, which leaves room for ONE k-step's fragments
+// (4 G + 3 X fragments, 28 registers) at two waves per SIMD: a K-tile is four (load, MFMA) phase pairs of 12 MFMAs instead of two
+// of 16, same ping-pong, same counted waits (G three stages, two K-tiles ahead, 2 pieces per wave; X two stages, one ahead,
+// 5 pieces per wave -- the fifth is the band's last two rows, 8 lanes of every wave, so that all waves count alike).
+// 810 channels are 7 tiles (896 rows, the tap-per-workgroup form pads to 1 024).  Partials: [tile][split][tap][128][256] f32.
+constexpr int TR_ROWS = 128;                                      // output channels per workgroup
+constexpr int TR_TILE_A = WG_POS * TR_ROWS * 2, TR_TILE_B = (WG_POS + 2) * 512;
+constexpr int TR_LDS_BYTES = 3 * TR_TILE_A + 2 * TR_TILE_B;       // 114 KiB
+template <int DT>
+__global__ __launch_bounds__(CONV_THREADS) void conv3x3_wgrad_taprow_kernel(const WgradArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];                 // [G0 G1 G2 | X0 X1]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int pp = wave >> 2;                                     // ping-pong group: waves 0-3 / 4-7
+    const int U = 3 * a.row_tiles;
+    int split = blockIdx.x, unit = (int)blockIdx.y * a.row_tiles + (int)blockIdx.z;
+    if (a.xcd_units > 0) {
+        // 1-D grid of 256 placed by XCD (XCD = blockIdx.x % 8): XCD c runs all U units of split c on its first U CUs; the other
+        // 32 - U take half of split 8 + (c >> 1) (the even XCD of a pair the first (U + 1) / 2 units, whole kernel rows first)
+        const int L = blockIdx.x, xcd = L & 7, w = L >> 3;
+        if (w < U) { split = xcd; unit = w; }
+        else { const int h = (U + 1) / 2; split = 8 + (xcd >> 1); unit = (xcd & 1) * h + (w - U); if (w - U >= h) return; }
+        if (split >= a.S || unit >= U) return;
+    }
+    const int kh = unit / a.row_tiles, tile = unit - kh * a.row_tiles;
+    const int KT = a.tiles_per_split, Wp = a.Wp;
+    const int M = (int)a.M;                                       // (host: M < 2^22 -- positions and X byte offsets are 32-bit here)
+    const unsigned char *__restrict__ X = (const unsigned char *)a.Xs[0];
+    const int m_begin = split * KT * WG_POS;
+    const int boff = (kh - 1) * Wp - 1;                          // band row r of a K-tile at t0 is canvas position t0 + boff + r
+    unsigned char *const Abase = lds, *const Bbase = lds + 3 * TR_TILE_A;
+
+    f32x16 acc[3][4];                                             // [tap of the kernel row][32 output channels]
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[s][i][r] = 0.0f;
+
+    // transposed-read addresses, as in conv3x3_wgrad_kernel: G rows are 256 bytes (16 chunks), band rows 512 (32 chunks)
+    const int grp = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    uint32_t a_off[4], b_off[3];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        const int ch = mi * 4 + 2 * (grp & 1) + (p >> 1);
+        a_off[mi] = (uint32_t)((8 * (grp >> 1) + q) * 256 + ((ch ^ (q << 2)) << 4) + (p & 1) * 8);
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int ch = wave * 4 + 2 * (grp & 1) + (p >> 1), row = 8 * (grp >> 1) + q + s;
+        b_off[s] = (uint32_t)(row * 512 + ((ch ^ wg_swz_row(row)) << 4) + (p & 1) * 8);
+    }
+    const uint32_t lds_base = (uint32_t)(uintptr_t)lds;
+
+    // X band staging: pieces 0..3 are rows 16 i + (tid >> 5), all 512 threads; piece 4 is rows 64 / 65, lanes 0..7 of every wave
+    // (row 64 + (wave >> 2), chunks 8 (wave & 3) + lane).  Rows 16 apart share their swizzle key: one offset serves pieces 0..3.
+    const int b_row = tid >> 5, b_cp = tid & 31;
+    const int b4_row = WG_POS + (wave >> 2), b4_cp = (wave & 3) * 8 + (lane & 7);
+    const uint32_t voff = (uint32_t)(b_row * 512 + ((b_cp ^ wg_swz_row(b_row)) << 4));
+    const uint32_t voff4 = (uint32_t)(b4_row * 512 + ((b4_cp ^ wg_swz_row(b4_row)) << 4));
+    auto piece_b = [&](const int kt, const int i) {
+        const int t0 = m_begin + kt * WG_POS + boff;                                          // canvas position of band row 0
+        unsigned char *const sb = Bbase + (kt & 1) * TR_TILE_B;
+        unsigned char *const dst = i < 4 ? sb + i * (CONV_THREADS * 16) + wave * (RN_WAVE * 16) : sb + WG_POS * 512 + wave * 128;
+        if (i == 4 && lane >= 8) return;
+        if (t0 >= 0 && t0 + WG_POS + 2 <= M) {                                                // wave-uniform
+            const uint32_t o = (uint32_t)(t0 * 512 + (i < 4 ? i * 16 * 512 : 0)) + (i < 4 ? voff : voff4);
+            __builtin_amdgcn_global_load_lds((const void *)(X + o), (lds_void_ptr)dst, 16, 0, 0);
+        } else {
+            // a band that leaves the canvas: those rows are clamped into it.  What they hold is never used: a tap outside the canvas
+            // belongs to a position of the first / last canvas line or past the end, where the gathered gradient row is zero.
+            const uint32_t v = i < 4 ? voff + (uint32_t)(i * 16 * 512) : voff4;
+            int ms = t0 + (int)(v >> 9);
+            ms = ms < 0 ? 0 : (ms >= M ? M - 1 : ms);
+            __builtin_amdgcn_global_load_lds((const void *)(X + ((uint32_t)ms * 512u + (v & 511u))), (lds_void_ptr)dst, 16, 0, 0);
+        }
+    };
+    // G staging: piece i = 0, 1 of a wave is rows 4 (8 i + wave) + (lane >> 4), chunk lane & 15 -- 8 distinct rows per wave and K-tile.
+    // Lane j < 8 looks up row 4 (8 (j >> 2) + wave) + (j & 3) and the wave shares the pointers by v_readlane.  A lane's piece always
+    // holds the same 8 output channels (the rows of a piece start at a multiple of 4, so lane >> 4 is its swizzle key).
+    LevelRegs lregs = level_regs(a.lv);
+    const int g_e = tile * TR_ROWS + (((lane & 15) ^ ((lane >> 4) << 2)) << 3);              // first output channel of this lane's pieces
+    // the piece that straddles the row end reads the row's last 8 channels instead (never past the row); the reduction
+    // kernel writes its dW rows to the channels they really are
+    const int g_es = g_e + 8 > a.lv.row_elems ? a.lv.row_elems - 8 : g_e;
+    const bool g_ok = g_e < a.lv.row_elems;
+    const uint16_t *grow[2] = {nullptr, nullptr};                 // this lane's source of pieces 0 / 1 (the zero page for gaps and past the row end)
+    int w_n = 0;
+    int32_t w_entry = -1;
+    bool w_valid = false;
+    auto rows_pos = [&](const int kt) {                            // -> w_n, w_valid; returns the (clamped) sheet position
+        const int j = lane & 7;
+        const int m = m_begin + kt * WG_POS + 4 * (8 * (j >> 2) + wave) + (j & 3);
+        w_valid = m < M;
+        int pos;
+        sheet_coords(w_valid ? m : M - 1, (int)a.HWp, w_n, pos);
+        return pos;
+    };
+    w_entry = a.lv.map[rows_pos(0)];                               // (prologue: nothing in flight yet)
+    auto gather_rows = [&](const int kt) {
+        const uint16_t *mine = level_row(a.lv, lregs, w_n, w_valid ? w_entry : -1);
+        map_fetch(w_entry, a.lv.map + rows_pos(kt + 1 < KT ? kt + 1 : kt));
+        const int sel = lane >> 4;
+        const uint16_t *lo0 = pair_ptr<0, 1>(mine, sel & 1), *hi0 = pair_ptr<2, 3>(mine, sel & 1);
+        const uint16_t *lo1 = pair_ptr<4, 5>(mine, sel & 1), *hi1 = pair_ptr<6, 7>(mine, sel & 1);
+        const uint16_t *r0 = sel & 2 ? hi0 : lo0, *r1 = sel & 2 ? hi1 : lo1;
+        grow[0] = (r0 && g_ok) ? r0 + g_es : a.zeros;
+        grow[1] = (r1 && g_ok) ? r1 + g_es : a.zeros;
+    };
+    auto piece_a = [&](const int stage, const int i) {
+        unsigned char *const dst = Abase + stage * TR_TILE_A + (i * 8 + wave) * (RN_WAVE * 16);
+        __builtin_amdgcn_global_load_lds((const void *)grow[i], (lds_void_ptr)dst, 16, 0, 0);
+    };
+    gather_rows(0);
+    piece_a(0, 0); piece_a(0, 1);
+#pragma unroll
+    for (int i = 0; i < 5; ++i) piece_b(0, i);
+    if (KT > 1) {
+        asm volatile("s_waitcnt vmcnt(7)" ::: "memory");           // the fetch for K-tile 1 is older than tile 0's 7 pieces
+        map_landed(w_entry);
+        gather_rows(1);
+        piece_a(1, 0); piece_a(1, 1);
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        map_landed(w_entry);
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+    if (pp == 1) __builtin_amdgcn_s_barrier();                    // ping-pong, as in the forward kernel
+
+    unsigned long long fa[4][2], fb[3][2];                        // [fragment][k half]
+#define RN_TR_READ(dst, addr, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
+    // k-step kk covers positions 16 kk .. 16 kk + 15 of the tile: G byte offset 16 kk * 256 (+ 4 * 256 for the second k half),
+    // band byte offset 16 kk * 512 (+ 4 * 512)
+#define RN_LOAD_FRAGS(AOFF0, AOFF1, BOFF0, BOFF1)                                                            \
+    RN_TR_READ(fb[0][0], bbase + b_off[0], BOFF0); RN_TR_READ(fb[0][1], bbase + b_off[0], BOFF1);            \
+    RN_TR_READ(fa[0][0], abase + a_off[0], AOFF0); RN_TR_READ(fa[0][1], abase + a_off[0], AOFF1);            \
+    RN_TR_READ(fa[1][0], abase + a_off[1], AOFF0); RN_TR_READ(fa[1][1], abase + a_off[1], AOFF1);            \
+    RN_TR_READ(fa[2][0], abase + a_off[2], AOFF0); RN_TR_READ(fa[2][1], abase + a_off[2], AOFF1);            \
+    RN_TR_READ(fa[3][0], abase + a_off[3], AOFF0); RN_TR_READ(fa[3][1], abase + a_off[3], AOFF1);            \
+    RN_TR_READ(fb[1][0], bbase + b_off[1], BOFF0); RN_TR_READ(fb[1][1], bbase + b_off[1], BOFF1);            \
+    RN_TR_READ(fb[2][0], bbase + b_off[2], BOFF0); RN_TR_READ(fb[2][1], bbase + b_off[2], BOFF1);
+    struct U2 { unsigned long long lo, hi; };
+#define RN_FRAG(v) __builtin_bit_cast(typename rn::mma<DT>::frag, U2{v[0], v[1]})
+#define RN_MFMA_PHASE()                                                            \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);          \
+    __builtin_amdgcn_s_setprio(1);                                                 \
+    _Pragma("unroll") for (int s = 0; s < 3; ++s)                                  \
+        _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                           \
+            acc[s][mi] = rn::mma<DT>::m32(RN_FRAG(fa[mi]), RN_FRAG(fb[s]), acc[s][mi]);            \
+    __builtin_amdgcn_s_setprio(0);                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                             \
+    __builtin_amdgcn_s_barrier();
+
+    int scur = 0, sa = 2;                                           // G stages (mod 3) of K-tiles kt and kt + 2
+    for (int kt = 0; kt < KT; ++kt) {
+        const uint32_t abase = lds_base + (uint32_t)(scur * TR_TILE_A), bbase = lds_base + (uint32_t)(3 * TR_TILE_A + (kt & 1) * TR_TILE_B);
+        scur = scur == 2 ? 0 : scur + 1;
+        RN_LOAD_FRAGS(0, 1024, 0, 2048)
+        __builtin_amdgcn_sched_barrier(0);
+        if (kt + 1 < KT) { piece_b(kt + 1, 0); piece_b(kt + 1, 1); piece_b(kt + 1, 2); }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        RN_MFMA_PHASE()
+        RN_LOAD_FRAGS(4096, 5120, 8192, 10240)
+        __builtin_amdgcn_sched_barrier(0);
+        if (kt + 1 < KT) { piece_b(kt + 1, 3); piece_b(kt + 1, 4); }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        RN_MFMA_PHASE()
+        RN_LOAD_FRAGS(8192, 9216, 16384, 18432)
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        RN_MFMA_PHASE()
+        RN_LOAD_FRAGS(12288, 13312, 24576, 26624)
+        __builtin_amdgcn_sched_barrier(0);
+        if (kt + 2 < KT) {
+            gather_rows(kt + 2);
+            piece_a(sa, 0); piece_a(sa, 1);
+            sa = sa == 2 ? 0 : sa + 1;
+            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            map_landed(w_entry);
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        RN_MFMA_PHASE()
+    }
+#undef RN_TR_READ
+#undef RN_LOAD_FRAGS
+#undef RN_FRAG
+#undef RN_MFMA_PHASE
+    if (pp == 0) __builtin_amdgcn_s_barrier();
+
+    // partial tiles [kw][n][c] f32 of this (tile, split, kernel row)
+    float *__restrict__ out = a.partial + (((int64_t)tile * a.S + split) * 9 + kh * 3) * (TR_ROWS * 256);
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            const int col = wave * 32 + (lane & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                out[(s * TR_ROWS + row) * 256 + col] = acc[s][mi][r];
+            }
+        }
+}
+
+// dW[n][t][c] (16-bit) = sum over the splits of the tap-row kernel's partial[tile][s][t][n - 128 tile][c]; the straddling
+// piece's rows of the LAST tile are shifted as in wgrad_reduce_kernel below (shift_from is tile-local)
+template <int DT>
+__global__ __launch_bounds__(256) void wgrad_reduce_taprow_kernel(const float *__restrict__ partial, const int S, uint16_t *dw, const int row_elems,
+                                                                  const int shift_from, const int shift)
+{
+    const int tile = blockIdx.y;
+    const bool last = tile == (int)gridDim.y - 1;
+    const int rows = row_elems - tile * TR_ROWS < TR_ROWS ? row_elems - tile * TR_ROWS : TR_ROWS;
+    const int i4 = (int)blockIdx.x * 256 + threadIdx.x;                   // over 9 * 128 * 256 / 4 float4 groups of [t][n][c]
+    if (i4 >= 9 * TR_ROWS * 256 / 4) return;
+    const int e = i4 * 4;
+    const int t = e / (TR_ROWS * 256), n = (e % (TR_ROWS * 256)) / 256, c = e % 256;
+    int n_out = n;
+    if (shift > 0 && last && n >= shift_from) {
+        if (n < shift_from + shift || n >= shift_from + 8) return;
+        n_out = n - shift;
+    } else if (n >= rows) return;
+    rn::f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int sp = 0; sp < S; ++sp) {                                       // fixed order: deterministic
+        const rn::f32x4 v = ((const rn::f32x4 *)(partial + ((int64_t)tile * S + sp) * 9 * (TR_ROWS * 256)))[i4];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    rn::u32x2 o;
+    o.x = rn::dt<DT>::pk(s.x, s.y); o.y = rn::dt<DT>::pk(s.z, s.w);
+    *(rn::u32x2 *)(dw + ((int64_t)(tile * TR_ROWS + n_out) * 9 + t) * 256 + c) = o;
 }
 
 // dW[p][n][t][c] (bf16) = sum over the splits of partial[p][s][t][n][c]
@@ -1871,13 +2119,60 @@ static int wgrad_splits(const int P, const int64_t M, int *tiles_per_split)
     return (int)((ktiles + tps - 1) / tps);
 }
 
+#ifndef WGRAD_TAPROW
+#define WGRAD_TAPROW 1               // rn_conv3x3_levels_wgrad, row_elems > 64: conv3x3_wgrad_taprow_kernel (0: one workgroup per tap, conv3x3_wgrad_kernel)
+#endif
+
+// Position splits of the tap-row kernel: one workgroup per (split, kernel row, tile of 128 output channels)
+static int taprow_splits(const int T, const int64_t M, int *tiles_per_split)
+{
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    int S = cus / (3 * T);
+    if (S < 1) S = 1;
+    if (S > 64) S = 64;
+    const int64_t ktiles = (M + WG_POS - 1) / WG_POS;
+    const int tps = (int)((ktiles + S - 1) / S);
+    if (tiles_per_split) *tiles_per_split = tps;
+    return (int)((ktiles + tps - 1) / tps);
+}
+
 // f32 partials of the splits the launch will really use (it used to size for the 64-split maximum: 151 MB per problem)
 RN_API size_t rn_conv3x3_wgrad_workspace_bytes(int P, int64_t M)
 {
     if (P <= 0 || P > CONV_MAX_PROBLEMS || M <= 0) return 0;
     // (the NARROW box-output launch runs P = 1 after a P - 1 launch in the same workspace: the P-problem figure covers both)
     const int S = wgrad_splits(P, M, nullptr), S1 = wgrad_splits(1, M, nullptr);
-    return ((size_t)P * S + (size_t)S1) * 9 * 65536 * sizeof(float);
+    size_t need = ((size_t)P * S + (size_t)S1) * 9 * 65536 * sizeof(float);
+    // the tap-row launch of a gathered gradient with P tiles of 256 channels runs 2 P - 1 or 2 P tiles of 128 (or one) with
+    // its own split count: cover whichever is larger
+    for (int T = 2 * P - 1 > 1 ? 2 * P - 1 : 1; T <= 2 * P; ++T) {
+        const size_t tr = (size_t)T * taprow_splits(T, M, nullptr) * 9 * TR_ROWS * 256 * sizeof(float);
+        need = tr > need ? tr : need;
+    }
+    return need;
+}
+
+// The tap-row launch + its reduction (GATHER only: a.lv, a.Xs[0], a.Wp, a.HWp, a.zeros filled by the caller)
+template <int DT>
+static int taprow_launch_dt(WgradArgs &a, uint16_t *dw, int row_elems, int64_t M, void *workspace, hipStream_t st, int shift_from, int shift)
+{
+    static rn::DynLdsOptIn opt_in = {};
+    { const int rc = opt_in.ensure((const void *)conv3x3_wgrad_taprow_kernel<DT>, TR_LDS_BYTES); if (rc != RN_OK) return rc; }
+    const int T = (row_elems + TR_ROWS - 1) / TR_ROWS, U = 3 * T;
+    const int S = taprow_splits(T, M, &a.tiles_per_split);
+    a.S = S; a.M = M; a.partial = (float *)workspace; a.row_tiles = T;
+    // XCD placement (see the kernel): split c < 8 whole on XCD c, splits 8 .. 11 in halves on the CUs that leaves free
+    a.xcd_units = (WGRAD_XCD_MAP && U <= 32 && (S <= 8 || (S <= 12 && (U + 1) / 2 <= 32 - U))) ? U : 0;
+    if (a.xcd_units > 0)
+        hipLaunchKernelGGL(conv3x3_wgrad_taprow_kernel<DT>, dim3(256, 1, 1), dim3(CONV_THREADS), TR_LDS_BYTES, st, a);
+    else
+        hipLaunchKernelGGL(conv3x3_wgrad_taprow_kernel<DT>, dim3((unsigned)S, 3, (unsigned)T), dim3(CONV_THREADS), TR_LDS_BYTES, st, a);
+    RN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(wgrad_reduce_taprow_kernel<DT>, dim3(9 * TR_ROWS * 256 / 4 / 256, (unsigned)T), dim3(256), 0, st, (const float *)workspace, S, dw,
+                       row_elems, shift_from, shift);
+    RN_LAUNCH_CHECK();
+    return RN_OK;
 }
 
 template <int DT, bool GATHER, bool NARROW>
@@ -1969,6 +2264,12 @@ RN_API int rn_conv3x3_levels_wgrad(const void *const *gs, const rn_canvas_layout
         const int rows1[CONV_MAX_PROBLEMS] = {rows[P - 1], 0, 0, 0};
         a.ch_base = (P - 1) * 256;
         return wgrad_launch<true, true>(a, dw1, rows1, 1, M, (float *)workspace + used, (hipStream_t)stream, tail ? e_last : 0, tail ? 8 - tail : 0);
+    }
+    if (WGRAD_TAPROW && row_elems > 64) {
+        // one workgroup per (split, kernel row, 128 output channels): a third of the G staging and of the X staging per MFMA
+        const int last0 = (row_elems - 1) / TR_ROWS * TR_ROWS, sf = tail ? row_elems - tail - last0 : 0, sh = tail ? 8 - tail : 0;
+        return a.f16 ? taprow_launch_dt<RN_F16>(a, (uint16_t *)dw, row_elems, M, workspace, (hipStream_t)stream, sf, sh)
+                     : taprow_launch_dt<RN_BF16>(a, (uint16_t *)dw, row_elems, M, workspace, (hipStream_t)stream, sf, sh);
     }
     return wgrad_launch<true>(a, dws, rows, P, M, workspace, (hipStream_t)stream, tail ? e_last : 0, tail ? 8 - tail : 0);
 }
