@@ -972,6 +972,27 @@ int rn_detect_levels(const void *const *cls_levels, const void *const *box_level
                      float *out_boxes, float *out_scores, int64_t *out_labels, int32_t *out_count,
                      int32_t *out_status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the end of predict on the device (graph.CapturedPredict, csrc/finish.hip) ---------------------------------------------
+ * rn_detect_finish_var: transform.postprocess for the batch -- the padded outputs of rn_detect / rn_detect_levels (out_boxes
+ * f32[B][max_det][4], out_scores f32[B][max_det], out_labels i64[B][max_det], out_count i32[B], out_status i32[B]) mapped from the
+ * resized images (out_hw_dev: DEVICE i32[B][2], rn_resize_plan_dev writes it) back to the original ones (in_hw_dev: DEVICE
+ * i32[B][2], rn_image_stage writes it) -- gathered into ONE result block of rn_detect_result_bytes(B, max_det) bytes (16-byte
+ * aligned), whose sections each start on a 16-byte boundary:
+ *   offset 0                          counts i32[B]                    (out_count as it is)
+ *   4 B                               status i32[B]                    (out_status as it is)
+ *   o_boxes  = up16(8 B)              boxes  f32[B][max_det][4]
+ *   o_scores = o_boxes + 16 B max_det scores f32[B][max_det]
+ *   o_labels = up16(o_scores + 4 B max_det)   labels i64[B][max_det]
+ *   total    = up16(o_labels + 8 B max_det)                            (up16: rounded up to a multiple of 16)
+ * Row r < count[b] (clamped to [0, max_det]): rh = float(orig_h) / float(res_h), rw = float(orig_w) / float(res_w) -- fp32 divisions
+ * of the fp32-rounded integers -- and box = (x1 * rw, y1 * rh, x2 * rw, y2 * rh), one fp32 multiply each (transform.resize_boxes);
+ * score and label copied.  Rows r >= count[b] and all padding are written as zero: the block is a pure function of the inputs.
+ * One launch for any B, no image size in the arguments, no synchronisation (capturable).  RN_EWORKSPACE: result_bytes too small. */
+size_t rn_detect_result_bytes(int B, int max_det);
+int rn_detect_finish_var(const float *out_boxes, const float *out_scores, const int64_t *out_labels, const int32_t *out_count,
+                         const int32_t *out_status, const int32_t *in_hw_dev, const int32_t *out_hw_dev, int B, int max_det,
+                         void *result, size_t result_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

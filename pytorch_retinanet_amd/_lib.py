@@ -209,6 +209,8 @@ SIGNATURES = {
                             _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rn_detect_levels": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp,
                                    C.POINTER(RnDetectParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rn_detect_result_bytes": (_sz, [C.c_int, C.c_int]),
+    "rn_detect_finish_var": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _sz, _vp]),
 }
 
 

@@ -68,12 +68,23 @@ sizes written on the device); the step then runs on that ``ops.StagedImages``.  
 kernel read every input size from device memory (``rn_resize_plan_dev``, ``rn_gt_flip_scale_packed_var``, ``rn_transform_batch_var``)
 and write the class canvas.  The cost: the conv stack processes the class canvas whatever the batch's own canvas was; a finer class
 list trades captures for compute.  A batch that fits no class -- or whose GT fits no capacity class -- keeps the exact-shape key
-and path.  fp32 CHW CUDA images only (uint8 / HWC input is not implemented); training only.
+and path.  fp32 CHW CUDA images only (uint8 / HWC input is not implemented).
+
+Inference (``CapturedPredict``, at the end of this file): ``net.predict(images)`` as one graph replay per batch, for batches whose image sizes
+vary.  A batch is keyed by B, its canvas class and pixel class (the same ``image_capacity_classes`` / ``image_canvas_class`` / ``image_pixel_class``,
+over the sizes after the resize to the fixed eval short side), the autocast dtype and the memory format; every call stages its images into the
+key's arena and runs ``Retinanet.predict_staged`` -- the eval-mode staged transform, the conv stack under ``no_grad``, the anchors of the canvas,
+``rn_detect_levels`` on the device sizes and ``rn_detect_finish_var``, which maps the boxes back to the original sizes and gathers everything the
+host reads into one block -- eagerly for the first ``eager_calls`` calls of a key and as a captured linear graph afterwards, followed by ONE
+device-to-host copy and one wait.  A captured pass bakes in the folded BatchNorm weights (``backbone._folded``), so the predictor stamps the
+weights (``norm.RAW_WRITES`` plus every parameter's and buffer's ``(data_ptr, _version)``) and drops every graph when the stamp moves; an image with
+more candidates than the fixed ``max_candidates`` reruns its batch eagerly with the worst case; a batch no class holds goes to plain ``net.predict``.
 """
 import ctypes as C
 import math
 import os
 import logging
+import time
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -82,7 +93,7 @@ from torch import Tensor
 
 from . import ops
 from ._lib import check, lib
-from .norm import note_raw_write
+from .norm import RAW_WRITES, note_raw_write
 
 _log = logging.getLogger(__name__)
 
@@ -697,3 +708,222 @@ class CapturedTrainStep:
         note_raw_write()                                      # parameters and BN statistics changed behind torch's back
         self.replays += 1
         return e.losses
+
+
+# ---- inference ------------------------------------------------------------------------------------------------------------------
+class _PredictEntry:
+    "One key of ``CapturedPredict``: the image arena every call of that key stages into and, once captured, the graph and the block it writes."
+    __slots__ = ("calls", "failed", "graph", "staged", "block", "host", "keep")
+
+    def __init__(self, staged, host):
+        self.calls, self.failed = 0, False
+        self.graph = self.block = self.keep = None
+        self.staged = staged          # ops.StagedImages: B slots of 3 x pixel class, canvas = the class canvas
+        self.host = host              # pinned uint8 [rn_detect_result_bytes]: where the one device-to-host copy of a call lands
+        # keep: once captured, every tensor the graph reads or writes that an out-of-graph CACHE owns (_cached_tensors) -- the graph
+        # holds their addresses, the caches may drop them (the anchor cache clears itself beyond 16 shapes, a scratch buffer is
+        # replaced when a call needs a larger one), and memory handed back to the allocator is reused by whoever asks next
+
+
+def _cached_tensors(net) -> List[Tensor]:
+    """Every tensor owned by a cache that evicts or replaces its entries and whose address a captured pass of ``net`` may hold: the
+    anchors of ``AnchorGenerator._cache`` (cleared beyond 16 feature-map shapes: every ``predict`` on a canvas of its own adds one),
+    the per-(name, device, stream) scratch buffers of ``_launch.scratch`` and the BatchNorm workspaces of ``norm._WS`` (each replaced
+    when a call needs more).  A reference taken here keeps the memory the graph points at from being handed out again.  The zero page
+    (``_launch.zero_page``) and the level canvases (``biasact.Canvas._cache``) are never evicted; the folded weights of
+    ``backbone._folded`` are replaced only when the weights change, which drops the graph first (``_weights_stamp``)."""
+    from . import _launch, norm
+    gen = getattr(net, "anchor_generator", None)
+    return list(getattr(gen, "_cache", {}).values()) + list(_launch._SCRATCH.values()) + list(norm._WS.values())
+
+
+class CapturedPredict:
+    """``net.predict(images)`` as ONE graph replay per batch, for batches whose image sizes vary (the module docstring's last section).
+
+    ``predictor(images)`` -- a list of fp32 CHW CUDA images -- returns what ``net.predict(images)`` returns: a list of
+    ``{"boxes", "scores", "labels"}`` in original image coordinates; CPU tensors by default, ``to="device"`` gives views of the entry's
+    device block instead (read them before the next call with the same key overwrites it).  ``net`` must be in eval mode (a net in
+    training mode is served by plain ``net.predict``).  ``image_capacity``: "auto" or a list of padded canvases (Hp, Wp), as for
+    ``CapturedTrainStep``; ``amp_dtype``: the autocast dtype of the pass (None: whatever autocast state the caller is in);
+    ``eager_calls`` (>= 1): calls of a new key that run ``predict_staged`` eagerly before the capture (they fill the anchor, zero-page
+    and folded-weight caches and let MIOpen choose its algorithms); ``max_graphs``: keys kept, least recently used first out;
+    ``max_candidates``: the detect chain's fixed per-image candidate capacity (None: ``ops.detect_levels``' default).
+
+    ``stats``: ``captures`` (graphs captured), ``replays`` (calls served by one), ``eager`` (calls that ran ``predict_staged`` eagerly:
+    warm-up, failed captures, overflow reruns), ``fallbacks`` (calls whose result came from outside the replayed path: plain
+    ``net.predict`` for a batch no class holds, or the eager rerun after a candidate overflow), ``overflows`` (the latter alone) and
+    ``invalidations`` (times every graph was dropped because the weights had changed).  ``host_seconds``: the time spent inside
+    ``__call__`` so far EXCEPT the waits for the device -- the per-call host cost (class and key arithmetic, the stamp walk, staging,
+    the replay, the copy's enqueue, building the result), ``host_calls`` the calls it covers (fallbacks to ``net.predict`` excluded)."""
+
+    def __init__(self, net, image_capacity="auto", amp_dtype: Optional[torch.dtype] = None, eager_calls: int = 1, max_graphs: int = 8,
+                 max_candidates: Optional[int] = None):
+        if image_capacity is None:
+            raise ValueError("image_capacity: CapturedPredict needs 'auto' or a list of (Hp, Wp) canvases (None would never replay)")
+        self.image_capacity = image_capacity_classes(image_capacity, getattr(net, "transform", None))
+        if self.image_capacity == "auto":
+            raise ValueError("image_capacity='auto' needs a net with a transform to derive the canvases from")
+        if amp_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError(f"amp_dtype: expected None, torch.bfloat16 or torch.float16, got {amp_dtype!r}")
+        if isinstance(eager_calls, bool) or int(eager_calls) != eager_calls or int(eager_calls) < 1:
+            raise ValueError(f"eager_calls must be an int >= 1 (the first call of a key fills the caches a capture must not), got {eager_calls!r}")
+        if isinstance(max_graphs, bool) or int(max_graphs) != max_graphs or int(max_graphs) < 1:
+            raise ValueError(f"max_graphs must be an int >= 1, got {max_graphs!r}")
+        if max_candidates is not None and (isinstance(max_candidates, bool) or not isinstance(max_candidates, int) or max_candidates < 1):
+            raise ValueError(f"max_candidates must be None or an int >= 1, got {max_candidates!r}")
+        self.net, self.amp_dtype, self.max_candidates = net, amp_dtype, max_candidates
+        self.eager_calls, self.max_graphs = int(eager_calls), int(max_graphs)
+        self._entries: "OrderedDict[tuple, _PredictEntry]" = OrderedDict()
+        self._stamp = None            # the weights the entries' graphs were captured under (_weights_stamp)
+        self.stats = {"captures": 0, "replays": 0, "eager": 0, "fallbacks": 0, "overflows": 0, "invalidations": 0}
+        self.host_seconds, self.host_calls, self._waited = 0.0, 0, 0.0
+
+    # -- keys ---------------------------------------------------------------------------------------------------------------------
+    def _autocast_dtype(self) -> Optional[torch.dtype]:
+        "The autocast dtype of this call: ``amp_dtype``, else the caller's own autocast state (None: fp32)."
+        if self.amp_dtype is not None:
+            return self.amp_dtype
+        return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
+
+    def _autocast(self, dtype):
+        return torch.autocast("cuda", dtype=dtype, enabled=dtype is not None, cache_enabled=False)
+
+    def _class_of(self, images) -> Optional[Tuple[Tuple[int, int], int, List[Tuple[int, int]]]]:
+        """The batch's (canvas class, pixel class, per-image resized sizes), or None -- the batch goes to plain ``net.predict``: no
+        images, images the fused transform does not take, a net or transform in training mode, a short side the device plan cannot
+        take, or a canvas no class contains.  Host arithmetic on the image shapes; nothing synchronises."""
+        net = self.net
+        tr = net.transform
+        if not isinstance(images, (list, tuple)) or not images or net.training or tr.training:
+            return None
+        if not all(isinstance(im, Tensor) for im in images) or not tr._fusable(list(images)) or tr.staged_eval_short_side() is None:
+            return None
+        if any(im.device != images[0].device for im in images):
+            return None
+        in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
+        if any(h <= 0 or w <= 0 for h, w in in_hw):
+            return None
+        bounds = tr.staged_eval_bounds(in_hw)
+        canvas = image_canvas_class(tr._canvas(bounds), self.image_capacity)
+        return None if canvas is None else (canvas, image_pixel_class(in_hw), bounds)
+
+    def _walk(self) -> Tuple[tuple, tuple]:
+        """ONE walk over the net's modules per call -> (every module's ``training`` flag, the weights stamp).  The stamp is what a
+        captured inference graph bakes in beyond its inputs: the folded BatchNorm weights of ``backbone._folded`` and every other tensor
+        derived from the weights outside the graph.  ``norm.RAW_WRITES`` (the library's own raw-pointer writes: optimizer steps, EMA
+        swaps, train-step replays) plus (data_ptr, _version) of every parameter and buffer (load_state_dict, in-place torch ops, .to())."""
+        mode, stamp = [], [RAW_WRITES[0]]
+        for m in self.net.modules():
+            mode.append(m.training)
+            for t in m._parameters.values():
+                if t is not None:
+                    stamp.append((t.data_ptr(), t._version))
+            for t in m._buffers.values():
+                if t is not None:
+                    stamp.append((t.data_ptr(), t._version))
+        return tuple(mode), tuple(stamp)
+
+    def _key(self, images, icls, dtype, mode: Optional[tuple] = None) -> tuple:
+        "``mode``: the modules' training flags when the caller has them from ``_walk`` (``__call__``); else walked here."
+        net = self.net
+        tr = net.transform
+        cl = net.backbone.backbone.conv1.weight.is_contiguous(memory_format=torch.channels_last)
+        if mode is None:
+            mode = self._walk()[0]
+        # (what the pass takes BY VALUE: the eval short side, max_size, mean and std are kernel arguments of the plan and the transform,
+        # the thresholds and max_det of the detect chain)
+        return ("predict", len(images), icls[0], icls[1], dtype, cl, images[0].device, mode, tr.staged_eval_short_side(), int(tr.max_size),
+                tuple(tr.image_mean), tuple(tr.image_std), net.score_thres, net.nms_thres, net.detections_per_img)
+
+    def _weights_stamp(self) -> tuple:
+        return self._walk()[1]
+
+    # -- the call -----------------------------------------------------------------------------------------------------------------
+    def _body(self, staged, dtype, max_candidates) -> Tensor:
+        "The pass itself, identical in eager mode and under capture: linear, on the current stream, nothing read back."
+        with self._autocast(dtype):
+            return self.net.predict_staged(staged, staged.canvas, max_candidates)
+
+    def _read(self, e: _PredictEntry, block: Tensor, B: int) -> Tensor:
+        "The one device-to-host copy of a call, into the entry's pinned buffer, and the one wait -> a host copy of the block."
+        e.host.copy_(block, non_blocking=True)
+        t0 = time.perf_counter()
+        torch.cuda.current_stream(block.device).synchronize()
+        self._waited += time.perf_counter() - t0
+        return e.host.clone()
+
+    def _fallback(self, images, dtype):
+        self.stats["fallbacks"] += 1
+        with self._autocast(dtype):
+            return self.net.predict(images)
+
+    def __call__(self, images: Sequence[Tensor], to: str = "cpu") -> List[Dict[str, Tensor]]:
+        if to not in ("cpu", "device"):
+            raise ValueError(f"to: expected 'cpu' or 'device', got {to!r}")
+        dtype = self._autocast_dtype()
+        icls = self._class_of(images)
+        if icls is None:
+            out = self._fallback(images, dtype)
+            return out if to == "device" else [{k: v.cpu() for k, v in d.items()} for d in out]
+        t0, w0 = time.perf_counter(), self._waited
+        try:
+            return self._serve(list(images), icls, dtype, to)
+        finally:
+            self.host_seconds += (time.perf_counter() - t0) - (self._waited - w0)
+            self.host_calls += 1
+
+    def _serve(self, images: List[Tensor], icls, dtype, to: str) -> List[Dict[str, Tensor]]:
+        B, dev, max_det = len(images), images[0].device, int(self.net.detections_per_img)
+        mode, stamp = self._walk()
+        if self._stamp is not None and stamp != self._stamp and self._entries:
+            self._entries.clear()                             # every graph, arena and private pool: they were built on other weights
+            self.stats["invalidations"] += 1
+        self._stamp = stamp
+        key = self._key(images, icls, dtype, mode)
+        e = self._entries.get(key)
+        if e is None:
+            total = ops.detect_result_layout(B, max_det)["total"]
+            e = self._entries[key] = _PredictEntry(ops.new_image_arena(B, icls[1], dev, icls[0]),
+                                                   torch.empty((total,), dtype=torch.uint8).pin_memory())
+            while len(self._entries) > self.max_graphs:
+                self._entries.popitem(last=False)
+        else:
+            self._entries.move_to_end(key)
+        e.calls += 1
+        # this batch's images into the entry's arena and their sizes next to them: eager calls, the capture and replays alike
+        ops.image_stage(images, e.staged, bounds=icls[2])
+        if e.graph is None and not e.failed and e.calls > self.eager_calls:
+            try:
+                torch.cuda.synchronize()
+                g = _new_graph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    e.block = self._body(e.staged, dtype, self.max_candidates)
+                _repair_memset_nodes(g)
+                e.graph, e.keep = g, _cached_tensors(self.net)
+                self.stats["captures"] += 1
+            except Exception as exc:                          # noqa: BLE001 -- a pass that cannot be captured still has to run
+                _log.warning("predict capture failed (%s: %s); this key runs eagerly", type(exc).__name__, exc)
+                e.failed, e.graph, e.block, e.keep = True, None, None, None
+                torch.cuda.synchronize()
+        if e.graph is not None:
+            e.graph.replay()
+            block = e.block
+            self.stats["replays"] += 1
+        else:
+            block = self._body(e.staged, dtype, self.max_candidates)
+            self.stats["eager"] += 1
+        host = self._read(e, block, B)
+        if bool(ops.detect_result_views(host, B, max_det)["status"].any()):
+            # the fixed candidate capacity was too small for an image of this batch: once more, eagerly, on the same staged batch with
+            # the worst case -- what ops.detect_levels' own retry does
+            block = self._body(e.staged, dtype, "all")
+            self.stats["eager"] += 1
+            self.stats["overflows"] += 1
+            self.stats["fallbacks"] += 1
+            host = self._read(e, block, B)
+        if to == "device":
+            counts = ops.detect_result_views(host, B, max_det)["counts"].tolist()
+            v = ops.detect_result_views(block, B, max_det)
+            return [{"boxes": v["boxes"][b, :n], "scores": v["scores"][b, :n], "labels": v["labels"][b, :n]}
+                    for b, n in enumerate(min(max(int(c), 0), max_det) for c in counts)]
+        return ops.detect_result_dicts(host, B, max_det)

@@ -71,6 +71,7 @@ class RetinaNetModel(_Base):
         self.save_hyperparameters(conf)
         self.trn_ds = self.val_ds = self.test_ds = None
         self.test_evaluator = None
+        self.predictor = None         # a callable images -> detections used by test_step instead of net.predict (graph.CapturedPredict)
 
     def forward(self, xb, *args, **kwargs):
         # reference model.py:33-35 calls self.net(xb) with no targets (a TypeError there, Q19);
@@ -172,7 +173,7 @@ class RetinaNetModel(_Base):
     def test_step(self, batch, batch_idx, *args, **kwargs):
         images, targets, _ = batch
         targets = [{k: v for k, v in t.items()} for t in targets]
-        outputs = self.net.predict(images)
+        outputs = self.net.predict(images) if self.predictor is None else self.predictor(images)
         res = {t["image_id"].item(): o for t, o in zip(targets, outputs)}
         if self.test_evaluator is not None:
             self.test_evaluator.update(res)
@@ -227,7 +228,7 @@ class SimpleTrainer:
                  channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True,
                  gt_capacity=None, gradient_clip_val: float = 0.0, accumulate_grad_batches: int = 1,
                  weight_ema_decay: float = 0.0, weight_ema_warmup: float = 0.0, device_scale_jitter: bool = False,
-                 scale_jitter_seed: int = 0, image_capacity=None):
+                 scale_jitter_seed: int = 0, image_capacity=None, predict_image_capacity=None):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
@@ -274,7 +275,13 @@ class SimpleTrainer:
         ``image_capacity`` (None = off; left None, an optional ``trainer.image_capacity`` in the hparams is honoured): passed to the
         ``CapturedTrainStep`` -- "auto" or a list of padded canvases (Hp, Wp) keys batches by canvas class and pixel class instead of
         by their images' exact shapes, so data whose images differ in size still replays.  Needs ``gt_capacity``.  The cost: the conv
-        stack processes the class canvas whatever the batch's own canvas was."""
+        stack processes the class canvas whatever the batch's own canvas was.
+
+        ``predict_image_capacity`` (None = off; left None, an optional ``trainer.predict_image_capacity`` in the hparams is honoured):
+        "auto" or a list of padded canvases (Hp, Wp) -- ``test()`` installs a ``graph.CapturedPredict`` over them as the model's
+        ``predictor`` (``self.predictor``; removed again when ``test()`` returns), so every test batch is one graph replay keyed by its
+        canvas class whatever its images' sizes are.  It runs inside the weight average's swap, and its graphs are dropped whenever the
+        weights change.  CUDA only; the cost is the class canvas again."""
         from .graph import gt_capacity_classes, image_capacity_classes
         from .optim import check_accumulate_grad_batches
         self.accumulate_grad_batches = check_accumulate_grad_batches(accumulate_grad_batches)
@@ -297,6 +304,9 @@ class SimpleTrainer:
         if image_capacity is not None and gt_capacity is None:
             raise ValueError("image_capacity needs gt_capacity as well (\"auto\" or a class list)")
         self.image_capacity = image_capacity
+        image_capacity_classes(predict_image_capacity)    # (the same)
+        self.predict_image_capacity = predict_image_capacity
+        self.predictor = None                             # the graph.CapturedPredict of the last test()
         self.max_epochs, self.max_steps, self.log_every, self.capture = max_epochs, max_steps, log_every, capture
         self.captured_steps = 0
         self.captured_graphs = 0                          # captures of the last fit() (one per input signature that reached a replay)
@@ -357,6 +367,16 @@ class SimpleTrainer:
             return self.image_capacity
         section = conf.get("trainer") if hasattr(conf, "get") else None
         value = (section or {}).get("image_capacity")
+        if value is None or isinstance(value, str):
+            return value
+        return [tuple(int(v) if int(v) == v else v for v in c) for c in value]      # (a YAML list of [Hp, Wp] lists)
+
+    def resolve_predict_image_capacity(self, conf):
+        "The constructor's ``predict_image_capacity`` or, when that is None, ``trainer.predict_image_capacity`` of the hparams (absent: off)."
+        if self.predict_image_capacity is not None:
+            return self.predict_image_capacity
+        section = conf.get("trainer") if hasattr(conf, "get") else None
+        value = (section or {}).get("predict_image_capacity")
         if value is None or isinstance(value, str):
             return value
         return [tuple(int(v) if int(v) == v else v for v in c) for c in value]      # (a YAML list of [Hp, Wp] lists)
@@ -545,8 +565,19 @@ class SimpleTrainer:
     def test(self, model: RetinaNetModel):
         model.to(self.device).eval()
         outs = []
-        with torch.no_grad(), self._ema_weights(model):
-            for i, batch in enumerate(model.test_dataloader()):
-                with self._autocast():
-                    outs.append(model.test_step(_to_device(batch, self.device), i))
+        capacity = self.resolve_predict_image_capacity(getattr(model, "conf", None))
+        installed = False
+        if capacity is not None and self.device.type == "cuda" and getattr(model, "predictor", None) is None:
+            from .graph import CapturedPredict
+            # (inside the swap below: the predictor stamps the weights it captured under, so the swap and its undoing drop its graphs)
+            self.predictor = model.predictor = CapturedPredict(model.net, capacity, amp_dtype=self.amp_dtype)
+            installed = True
+        try:
+            with torch.no_grad(), self._ema_weights(model):
+                for i, batch in enumerate(model.test_dataloader()):
+                    with self._autocast():
+                        outs.append(model.test_step(_to_device(batch, self.device), i))
+        finally:
+            if installed:
+                model.predictor = None
         return model.test_epoch_end(outs), outs

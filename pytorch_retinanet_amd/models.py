@@ -122,7 +122,8 @@ class Retinanet(nn.Module):
         (its Lightning wrapper's ``forward`` therefore raises); here
         ``targets=None`` means inference and returns ``predict(images)``.  ``targets`` may also be packed GT
         (``ops.PackedGT``, staged by ``ops.gt_stage``: the GT capacity mode of ``graph.CapturedTrainStep``), and ``images`` staged
-        images (``ops.StagedImages``, staged by ``ops.image_stage``: its image capacity mode; training mode only) -- they go to
+        images (``ops.StagedImages``, staged by ``ops.image_stage``: its image capacity mode; training mode only -- inference on staged images is
+        ``predict_staged``) -- they go to
         the transform as they are, with the canvas they carry."""
         if targets is None:
             return self.predict(images)
@@ -194,3 +195,28 @@ class Retinanet(nn.Module):
             detections = self.process_detections_levels(self.retinanet_head.forward_levels(feature_maps), anchors,
                                                         images.image_sizes)
             return self.transform.postprocess(detections, images.image_sizes, original_image_sizes)
+
+    def predict_staged(self, staged, canvas: Optional[Tuple[int, int]] = None, max_candidates=None) -> Tensor:
+        """``predict`` on staged images (``ops.StagedImages``, staged by ``ops.image_stage``) over the padded canvas ``canvas`` (default:
+        the one the arena carries) -> the DEVICE result block of ``ops.detect_finish_var`` (``ops.detect_result_dicts`` turns it
+        into ``predict``'s list of dicts).  The same chain -- transform, conv stack under ``no_grad``, anchors on the canvas, detect,
+        rescale to the original sizes -- but nothing it launches takes an image's address or size as an argument and nothing is read
+        back: the sizes stay on the device from ``rn_image_stage`` to ``rn_detect_finish_var``.  No synchronisation, so
+        ``graph.CapturedPredict`` captures it.  ``max_candidates``: the detect chain's per-image capacity (``ops.detect_levels``: an
+        int, None for its default, "all" for the worst case); an image that needed more has ``status != 0`` in the block, and the
+        caller runs the batch again with "all".  Eval mode only: ``net.eval()`` first -- this does not flip the flag as ``predict`` does."""
+        if self.training or self.transform.training:
+            raise ValueError("predict_staged runs in eval mode: call net.eval() first")
+        canvas = staged.canvas if canvas is None else canvas
+        with torch.no_grad():
+            images, _ = self.transform(staged, None, canvas=canvas, **self._batch_layout())
+            batch = images.tensors
+            if self.backbone.backbone.conv1.weight.is_contiguous(memory_format=torch.channels_last):
+                batch = batch.contiguous(memory_format=torch.channels_last)        # no-op after the fused transform
+            feature_maps = self.fpn(self.backbone(batch))
+            anchors = self.anchor_generator(images, feature_maps)
+            outputs = self.retinanet_head.forward_levels(feature_maps)
+            padded = ops.detect_levels(outputs["cls_levels"], outputs["bbox_levels"], anchors, None, self.score_thres, MIN_BOX_SIZE,
+                                       self.nms_thres, self.detections_per_img, reg_w=BBOX_REG_WEIGHTS, max_candidates=max_candidates,
+                                       image_hw_dev=images.image_sizes_dev, padded=True)
+            return ops.detect_finish_var(*padded, staged.in_hw, images.image_sizes_dev)

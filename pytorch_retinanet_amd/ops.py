@@ -1009,9 +1009,14 @@ def detect(cls: Tensor, deltas: Tensor, anchors, image_sizes: Sequence[Tuple[int
 def detect_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], anchors, image_sizes: Sequence[Tuple[int, int]],
                   score_thr: float, min_box: float, nms_thr: float, max_det: int,
                   reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0), max_candidates: Optional[int] = None,
-                  enqueue_only: Optional[list] = None) -> List[dict]:
+                  enqueue_only: Optional[list] = None, image_hw_dev: Optional[Tensor] = None, padded: bool = False):
     """``detect`` on per-level head outputs (cls_levels[l] [B,A_l,K], box_levels[l] [B,A_l,4]) without
-    concatenating them; identical results to ``detect(torch.cat(cls_levels, 1), torch.cat(box_levels, 1), ...)``."""
+    concatenating them; identical results to ``detect(torch.cat(cls_levels, 1), torch.cat(box_levels, 1), ...)``.
+    ``image_hw_dev`` (int32 [B, 2] on the outputs' device, e.g. ``resize_plan_dev``'s sizes): the image sizes the boxes are clipped to,
+    used instead of an upload of ``image_sizes`` (which may then be None).  ``padded``: enqueue the chain ONCE and return the padded
+    device outputs ``(out_boxes [B, max_det, 4], out_scores, out_labels, meta i32 [2, B] = counts | status)`` without reading
+    anything back -- no synchronisation and no retry: ``status[b] != 0`` tells the caller that ``max_candidates`` (an int, None for the
+    default, or "all" for the worst case A * K) was too small for image b."""
     L = len(cls_levels)
     if L == 0 or L > _lib.RN_MAX_LEVELS or len(box_levels) != L:
         raise ValueError("need 1..8 levels of (cls, box) outputs")
@@ -1030,9 +1035,21 @@ def detect_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], an
         first = anchors[0]
         anchors = first if all(a is first or a.data_ptr() == first.data_ptr() for a in anchors) else torch.stack(list(anchors))
     anchors, bstride = _anchor_args(anchors.to(dev), B, A)
-    hw = image_hw_tensor(image_sizes, dev)
+    if image_hw_dev is not None:
+        if image_hw_dev.dtype != torch.int32 or tuple(image_hw_dev.shape) != (B, 2) or not image_hw_dev.is_contiguous() \
+                or image_hw_dev.device != dev:
+            raise ValueError(f"image_hw_dev must be a contiguous int32 [{B}, 2] tensor on {dev}, got {tuple(image_hw_dev.shape)} "
+                             f"{image_hw_dev.dtype} on {image_hw_dev.device}")
+        hw = image_hw_dev
+    else:
+        hw = image_hw_tensor(image_sizes, dev)
     params = RnDetectParams(score_thr, min_box, nms_thr, int(max_det), (C.c_float * 4)(*reg_w))
-    cap = int(max_candidates) if max_candidates else min(A * K, 1 << 18)
+    if isinstance(max_candidates, str):
+        if max_candidates != "all":
+            raise ValueError(f"max_candidates: expected an int, None or 'all', got {max_candidates!r}")
+        cap = A * K
+    else:
+        cap = int(max_candidates) if max_candidates else min(A * K, 1 << 18)
     out_boxes = torch.empty((B, max_det, 4), dtype=torch.float32, device=dev)
     out_scores = torch.empty((B, max_det), dtype=torch.float32, device=dev)
     out_labels = torch.empty((B, max_det), dtype=torch.int64, device=dev)
@@ -1053,6 +1070,8 @@ def detect_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], an
             return []
         with torch.cuda.device(dev), _timed("detect", dev):
             enqueue()
+        if padded:                            # (graph.CapturedPredict: the outputs stay on the device, rn_detect_finish_var reads them)
+            return out_boxes, out_scores, out_labels, meta
         meta_h = meta.cpu()                                              # the one sync
         if not bool(meta_h[1].any()) or cap >= A * K:
             break
@@ -1060,3 +1079,100 @@ def detect_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], an
     counts = meta_h[0].tolist()
     return [{"boxes": out_boxes[b, :n], "scores": out_scores[b, :n], "labels": out_labels[b, :n]}
             for b, n in enumerate(counts)]
+
+
+# ---- the end of predict on the device (graph.CapturedPredict) ------------------------------------------------------------------
+def _up16(v: int) -> int:
+    return (int(v) + 15) & ~15
+
+
+def detect_result_layout(B: int, max_det: int) -> dict:
+    """Byte offsets of ``rn_detect_finish_var``'s result block (``include/retinanet_hip.h``): counts i32[B] at 0, status i32[B],
+    then -- each on a 16-byte boundary -- boxes f32[B][max_det][4], scores f32[B][max_det], labels i64[B][max_det]; ``total`` =
+    ``rn_detect_result_bytes(B, max_det)``."""
+    B, max_det = int(B), int(max_det)
+    if B <= 0 or max_det <= 0:
+        raise ValueError(f"need B >= 1 and max_det >= 1, got {B}, {max_det}")
+    rows = B * max_det
+    boxes = _up16(8 * B)
+    scores = boxes + 16 * rows
+    labels = _up16(scores + 4 * rows)
+    return {"counts": 0, "status": 4 * B, "boxes": boxes, "scores": scores, "labels": labels, "total": _up16(labels + 8 * rows)}
+
+
+def detect_result_views(block: Tensor, B: int, max_det: int) -> dict:
+    """Typed views of a result block (a uint8 tensor of ``detect_result_layout(B, max_det)["total"]`` bytes, on any device):
+    counts / status int32 [B], boxes f32 [B, max_det, 4], scores f32 [B, max_det], labels int64 [B, max_det]."""
+    lay = detect_result_layout(B, max_det)
+    if block.dtype != torch.uint8 or block.dim() != 1 or block.numel() != lay["total"] or not block.is_contiguous():
+        raise ValueError(f"a result block for B={B}, max_det={max_det} is a contiguous uint8 tensor of {lay['total']} bytes, "
+                         f"got {tuple(block.shape)} {block.dtype}")
+    rows = int(B) * int(max_det)
+    part = lambda name, nbytes, dt: block[lay[name]:lay[name] + nbytes].view(dt)
+    return {"counts": part("counts", 4 * B, torch.int32), "status": part("status", 4 * B, torch.int32),
+            "boxes": part("boxes", 16 * rows, torch.float32).view(B, max_det, 4),
+            "scores": part("scores", 4 * rows, torch.float32).view(B, max_det),
+            "labels": part("labels", 8 * rows, torch.int64).view(B, max_det)}
+
+
+def detect_result_dicts(block: Tensor, B: int, max_det: int) -> List[dict]:
+    "A result block (host or device) as ``Retinanet.predict``'s list of dicts: views of the block, one host read of the counts."
+    v = detect_result_views(block, B, max_det)
+    counts = [min(max(int(n), 0), int(max_det)) for n in v["counts"].tolist()]
+    return [{"boxes": v["boxes"][b, :n], "scores": v["scores"][b, :n], "labels": v["labels"][b, :n]} for b, n in enumerate(counts)]
+
+
+def detect_finish_reference(out_boxes, out_scores, out_labels, out_count, out_status, in_hw, out_hw):
+    """``rn_detect_finish_var`` restated in numpy (the tests' yardstick): the same block, byte for byte, as a uint8 array.  The two
+    roundings are the kernel's: fp32 ratio = fp32(original) / fp32(resized), then one fp32 multiply per coordinate."""
+    import numpy as np
+    boxes = np.ascontiguousarray(out_boxes, dtype=np.float32)
+    B, max_det = int(boxes.shape[0]), int(boxes.shape[1])
+    lay = detect_result_layout(B, max_det)
+    count = np.asarray(out_count, dtype=np.int32).reshape(B)
+    in_hw, out_hw = np.asarray(in_hw, dtype=np.int32).reshape(B, 2), np.asarray(out_hw, dtype=np.int32).reshape(B, 2)
+    rb = np.zeros((B, max_det, 4), np.float32)
+    rs = np.zeros((B, max_det), np.float32)
+    rl = np.zeros((B, max_det), np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = in_hw.astype(np.float32) / out_hw.astype(np.float32)              # [B, 2] = (rh, rw)
+        for b in range(B):
+            n = min(max(int(count[b]), 0), max_det)
+            rh, rw = ratio[b]
+            rb[b, :n] = boxes[b, :n] * np.array([rw, rh, rw, rh], np.float32)
+            rs[b, :n] = np.asarray(out_scores, dtype=np.float32)[b, :n]
+            rl[b, :n] = np.asarray(out_labels, dtype=np.int64)[b, :n]
+    block = np.zeros(lay["total"], np.uint8)
+    for name, arr in (("counts", count), ("status", np.asarray(out_status, dtype=np.int32).reshape(B)), ("boxes", rb), ("scores", rs),
+                      ("labels", rl)):
+        raw = np.frombuffer(np.ascontiguousarray(arr).tobytes(), np.uint8)
+        block[lay[name]:lay[name] + raw.size] = raw
+    return block
+
+
+def detect_finish_var(out_boxes: Tensor, out_scores: Tensor, out_labels: Tensor, meta: Tensor, in_hw: Tensor, out_hw: Tensor,
+                      out: Optional[Tensor] = None) -> Tensor:
+    """``rn_detect_finish_var``: ``transform.postprocess`` on the device.  The padded outputs of ``detect_levels(padded=True)`` (``meta``
+    int32 [2, B] = counts | status), the original sizes ``in_hw`` (int32 [B, 2], ``StagedImages.in_hw``) and the resized ones
+    ``out_hw`` (``resize_plan_dev``) -> ONE result block (uint8 [``detect_result_layout``'s total]; ``out``: written in place when
+    given) holding counts, status and the rescaled boxes / scores / labels with every row past an image's count zeroed.  One launch
+    for any B on the current stream, no synchronisation (capturable)."""
+    dev = _need_dev(out_boxes, out_scores, out_labels, meta, in_hw, out_hw, out)
+    if out_boxes.dim() != 3 or out_boxes.shape[2] != 4 or out_boxes.dtype != torch.float32 or not out_boxes.is_contiguous():
+        raise ValueError(f"out_boxes must be a contiguous f32 [B, max_det, 4] tensor, got {tuple(out_boxes.shape)} {out_boxes.dtype}")
+    B, max_det = int(out_boxes.shape[0]), int(out_boxes.shape[1])
+    if B == 0 or max_det == 0:
+        raise ValueError("need at least one image and one row per image")
+    for name, t, dt, shape in (("out_scores", out_scores, torch.float32, (B, max_det)), ("out_labels", out_labels, torch.int64, (B, max_det)),
+                               ("meta", meta, torch.int32, (2, B)), ("in_hw", in_hw, torch.int32, (B, 2)), ("out_hw", out_hw, torch.int32, (B, 2))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor, got {tuple(t.shape)} {t.dtype}")
+    total = detect_result_layout(B, max_det)["total"]
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() != total or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor of {total} bytes, got {tuple(out.shape)} {out.dtype}")
+    with torch.cuda.device(dev), _timed("detect_finish", dev):
+        check(lib.rn_detect_finish_var(_ptr(out_boxes), _ptr(out_scores), _ptr(out_labels), _ptr(meta[0]), _ptr(meta[1]), _ptr(in_hw),
+                                       _ptr(out_hw), B, max_det, _ptr(out), total, _stream(dev)), "rn_detect_finish_var")
+    return out

@@ -40,8 +40,10 @@ Staged images (``forward(ops.StagedImages, packed GT, canvas=(Hp, Wp))``: the im
 the batch lies in a fixed device arena with its sizes next to it (``ops.image_stage``), and nothing this call launches takes an
 image's address or size as an argument -- the resize plan (``rn_resize_plan_dev``: the fixed short side, or the ``scale_jitter``'s
 draw), the boxes (``rn_gt_flip_scale_packed_var``) and the transform kernel (``rn_transform_batch_var``) read them on the device, over
-the canvas the caller fixed.  Training mode, packed GT and the fused path only.  The result is bit-identical to the list path's on
-the same canvas; the cost is the jitter's: the conv stack processes the whole class canvas whatever the batch's own canvas was.
+the canvas the caller fixed.  In training mode with packed GT, or in eval mode without targets (``Retinanet.predict_staged``: the plan
+with the fixed eval short side ``min_size[-1]``, no flip, no jitter; the sizes it wrote stay on the device as ``ImageList.image_sizes_dev``);
+the fused path only.  The result is bit-identical to the list path's on the same canvas; the cost is the jitter's: the conv stack
+processes the whole class canvas whatever the batch's own canvas was.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -259,29 +261,69 @@ class GeneralizedRCNNTransform(nn.Module):
         if short is None:
             raise ValueError(f"staged images need one integer min_size and an integer max_size (got {self.min_size}, {self.max_size}), "
                              "or an augment.RandomShortSide as scale_jitter")
-        short = float(short)
+        return self._sizes_for(in_hw, float(short))
+
+    def _sizes_for(self, in_hw: Sequence[Tuple[int, int]], short: float) -> List[Tuple[int, int]]:
         out = []
         for h, w in in_hw:
             scale = self._scale_for(int(h), int(w), short)
             out.append((int(math.floor(h * scale)), int(math.floor(w * scale))))
         return out
 
-    def _forward_staged(self, staged, targets, canvas, out_dtype: torch.dtype, channels_last: bool):
-        "Staged images over a fixed canvas: every input size is read on the device (module docstring)."
-        from . import ops
-        if not self.training or not _is_packed(targets):
-            raise ValueError("staged images (ops.StagedImages) are a training input and come with packed GT (ops.PackedGT)")
-        if targets.B != staged.B or len(staged.hw) != staged.B:
-            raise ValueError(f"packed GT of {targets.B} images for {len(staged.hw)} staged images in an arena of {staged.B}")
+    def staged_eval_short_side(self) -> Optional[int]:
+        """The short side the staged path passes to the device in eval mode -- ``min_size[-1]``, what ``_target_short_side`` returns
+        there -- or None when it or ``max_size`` is no integer (the device plan takes integers)."""
+        if int(self.min_size[-1]) != self.min_size[-1] or int(self.max_size) != self.max_size:
+            return None
+        return int(self.min_size[-1])
+
+    def staged_eval_bounds(self, in_hw: Sequence[Tuple[int, int]]) -> List[Tuple[int, int]]:
+        "``staged_bounds`` for eval mode: the sizes after the resize to the fixed eval short side (a ``scale_jitter`` does not act there)."
+        short = self.staged_eval_short_side()
+        if short is None:
+            raise ValueError(f"staged images in eval mode need an integer min_size[-1] and an integer max_size (got {self.min_size}, {self.max_size})")
+        return self._sizes_for(in_hw, float(short))
+
+    def _check_staged_canvas(self, canvas, staged, bounds_of) -> Tuple[Tuple[int, int], List[Tuple[int, int]]]:
+        "-> ((Hp, Wp), the per-image bounds: the stager's when it has them, else ``bounds_of(staged.hw)``); ValueError when they do not fit."
         if canvas is None:
             raise ValueError("staged images need canvas=(Hp, Wp)")
         if not (len(self.image_mean) == 3 and len(self.image_std) == 3 and self.size_divisible % 4 == 0):
             raise ValueError("staged images take the fused transform only: 3 channels, size_divisible a multiple of 4")
         hp, wp = int(canvas[0]), int(canvas[1])
-        bounds = staged.bounds if staged.bounds is not None else self.staged_bounds(staged.hw)      # (the stager's, when it has them)
+        bounds = staged.bounds if staged.bounds is not None else bounds_of(staged.hw)
         need = self._canvas(bounds)
         if need[0] > hp or need[1] > wp:
             raise ValueError(f"canvas {hp} x {wp} does not contain the batch's own canvas {need[0]} x {need[1]}")
+        return (hp, wp), bounds
+
+    def _forward_staged_eval(self, staged, canvas, out_dtype: torch.dtype, channels_last: bool):
+        """Staged images in eval mode (``Retinanet.predict_staged``): the resize plan with the fixed eval short side, no flip, no
+        jitter, no targets.  The sizes the plan wrote stay on the device as ``ImageList.image_sizes_dev`` (int32 [B, 2]): the detect
+        chain clips to them and ``rn_detect_finish_var`` maps the boxes back with them; ``image_sizes`` holds the host's restatement."""
+        from . import ops
+        if len(staged.hw) != staged.B:
+            raise ValueError(f"{len(staged.hw)} staged images in an arena of {staged.B}")
+        (hp, wp), bounds = self._check_staged_canvas(canvas, staged, self.staged_eval_bounds)
+        short = self.staged_eval_short_side()
+        if short is None:
+            raise ValueError(f"staged images in eval mode need an integer min_size[-1] and an integer max_size (got {self.min_size}, {self.max_size})")
+        out_hw, _ = ops.resize_plan_dev(None, staged.in_hw, short, int(self.max_size))
+        batch = ops.transform_batch_var(staged, out_hw, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last)
+        images = ImageList(batch, bounds)
+        images.image_sizes_dev = out_hw
+        return images, None
+
+    def _forward_staged(self, staged, targets, canvas, out_dtype: torch.dtype, channels_last: bool):
+        "Staged images over a fixed canvas: every input size is read on the device (module docstring)."
+        from . import ops
+        if not self.training and targets is None:
+            return self._forward_staged_eval(staged, canvas, out_dtype, channels_last)
+        if not self.training or not _is_packed(targets):
+            raise ValueError("staged images (ops.StagedImages) are a training input and come with packed GT (ops.PackedGT)")
+        if targets.B != staged.B or len(staged.hw) != staged.B:
+            raise ValueError(f"packed GT of {targets.B} images for {len(staged.hw)} staged images in an arena of {staged.B}")
+        (hp, wp), bounds = self._check_staged_canvas(canvas, staged, self.staged_bounds)
         flags = self.hflip.next_flags(staged.B, staged.device) if self.hflip is not None else None
         jitter = self.scale_jitter
         if jitter is not None:
