@@ -933,6 +933,41 @@ int rn_short_side_draw(rn_short_side_state *state, const int32_t *in_hw, int max
 int rn_resize_plan_dev(rn_short_side_state *state_or_null, const int32_t *in_hw_dev, int fixed_short, int max_size, int B, int32_t *out_hw,
                        float *ratios, void *stream);
 
+/* ---- train-time augmentation: colour jitter (augment.ColorJitter), drawn and applied on the device ---------------------
+ * The pin is torchvision 0.8's tensor ColorJitter (transforms.functional_tensor) on fp32 RGB in [0, 1]; all arithmetic is fp32, left to
+ * right, one rounding per operation (no FMA), clamp = to [0, 1], gray(r, g, b) = 0.2989 r + 0.587 g + 0.114 b.  Operation ids:
+ *   0 brightness f: x = clamp(x * f)                     1 contrast f: x = clamp(f * x + (1 - f) * m), m = the image's mean gray
+ *   2 saturation f: x = clamp(f * x + (1 - f) * gray)    3 hue f: RGB -> HSV, h = (h + f) - floor(h + f), HSV -> RGB
+ * rn_color_jitter_state: a DEVICE block (8-byte aligned) owned by augment.ColorJitter, written by the host outside any capture.
+ * rn_color_coef: what one image gets, 32 bytes: its four factors (indexed by operation id), the contrast mean, and ``order`` = four
+ * nibbles, nibble k = the id of the k-th operation applied, 0xF = nothing (a disabled operation; every slot of an image the p draw
+ * left alone).
+ * rn_color_jitter_draw: one single-wave launch for any B, with u_k = the hash of rn_hflip_draw on (seed ^ salt_k, counter, b):
+ *   applied = u_apply < p;  order = the min(int(u_order * 24), 23)-th permutation of (0, 1, 2, 3) in lexicographic order, ids outside
+ *   enabled_mask replaced by 0xF;  f[k] = lo[k] + u_k * (hi[k] - lo[k])   (fp32, this order);  mean = 0;  then counter += 1.
+ *   salts: apply 0xC0104A11C0104A11, order 0x04DE404DE404DE45, factors 0xB416B416B416B417, 0xC0274A57C0274A57, 0x5A7C5A7C5A7C5A7D,
+ *   0x40E040E040E040E1.
+ * rn_color_mean: for every image whose order holds a contrast, coef[b].mean = float(sum of double(gray(pre(pixel))) / double(h w)),
+ * pre = the image's operations before the contrast (the code the transform kernel runs); other images keep their mean field.  No
+ * atomics: a fixed number of blocks per image, each a fixed-order sum in double into its own workspace slot, and a second launch adding
+ * the slots in index order.  Input: images / in_hw (HOST arrays as for rn_transform_batch; 64 images per launch) with arena and
+ * in_hw_dev NULL, or both NULL with the staged images arena / slot / in_hw_dev (rn_image_stage) -- there an image no slot can hold
+ * (ih < 1, iw < 1, 3 ih iw > slot) contributes nothing and gets mean 0.  workspace: rn_color_mean_workspace_bytes(B), 8-byte aligned.
+ * rn_transform_batch_color: the transform launch with the operations of coef[b].order applied to every source pixel it reads, before
+ * the normalisation (the jitter acts on the raw image; it commutes with the flip).  One entry point for every form: images / in_hw
+ * or arena / slot / in_hw_dev as for rn_color_mean (the staged form only with out_hw_dev), exactly one of out_hw (HOST) and out_hw_dev
+ * (DEVICE), flags_or_null.  An order of all 0xF gives rn_transform_batch's bits. */
+typedef struct rn_color_jitter_state { uint64_t seed; int64_t counter; float p; float lo[4]; float hi[4]; int32_t enabled_mask; } rn_color_jitter_state;
+typedef struct rn_color_coef { float f[4]; float mean; int32_t order; int32_t pad[2]; } rn_color_coef;
+int rn_color_jitter_draw(rn_color_jitter_state *state, int B, rn_color_coef *coef, void *stream);
+size_t rn_color_mean_workspace_bytes(int B);
+int rn_color_mean(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev, int B,
+                  rn_color_coef *coef, void *workspace, size_t workspace_bytes, void *stream);
+int rn_transform_batch_color(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev,
+                             const int32_t *out_hw, const int32_t *out_hw_dev, int B, const float mean[3], const float std[3], int Hp,
+                             int Wp, void *out, int out_dtype, int channels_last, const uint8_t *flags_or_null, const rn_color_coef *coef,
+                             void *stream);
+
 /* ---- K6 nms (op boundary) ---------------------------------------------------
  * Replaces torchvision.ops.nms as called at retinanet/models.py:210, batched over
  * S independent segments: seg_off i32[S+1]; boxes f32[N][4], scores f32[N].

@@ -202,7 +202,12 @@ SIGNATURES = {
     "rn_hflip_draw": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "rn_short_side_draw": (C.c_int, [_vp, C.POINTER(_i32), C.c_int, C.c_int, _vp, _vp, _vp]),
     "rn_resize_plan_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
-    "rn_nms_workspace_bytes": (_sz, [_i64, C.c_int]),
+    "rn_color_jitter_draw": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "rn_color_mean_workspace_bytes": (_sz, [C.c_int]),
+    "rn_color_mean": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_int, _vp, _vp, _sz, _vp]),
+    "rn_transform_batch_color": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_int, C.POINTER(_f32), C.POINTER(_f32), C.c_int, C.c_int,
+                                           _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "rn_nms_workspace_bytes":(_sz, [_i64, C.c_int]),
     "rn_nms_segments": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _f32, _vp, _vp, _vp, _sz, _vp]),
     "rn_detect_workspace_bytes": (_sz, [C.c_int, _i64, C.c_int, _i64]),
     "rn_detect": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i64, C.c_int, _vp, _i64, _vp, C.POINTER(RnDetectParams),

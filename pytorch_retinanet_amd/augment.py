@@ -18,6 +18,14 @@ nearly every batch is a new graph signature and the step stays on the eager path
 the largest candidate, and the sizes themselves are drawn on the device inside the step (``rn_short_side_draw``), read by the
 transform kernel (``rn_transform_batch_dev``) and the box kernels (``rn_gt_flip_scale_many_dev`` / ``_packed_dev``) from device
 memory.  The price is deliberate: the conv stack processes the whole canvas whatever was drawn, so a small draw saves no compute.
+
+``ColorJitter`` is the photometric half (``GeneralizedRCNNTransform.color_jitter``): torchvision's ``ColorJitter`` -- brightness,
+contrast, saturation and hue in a random order, each with a factor drawn from its range -- on fp32 RGB images in [0, 1].  The pin is
+torchvision 0.8's TENSOR algorithm (``transforms.functional_tensor``; ``apply_color_ops`` below restates it in torch).  albumentations'
+``ColorJitter`` takes the same arguments but works on uint8 through OpenCV, so its results differ slightly; an hparams entry naming
+either maps onto this class.  Per image one launch draws ``rn_color_coef`` (four factors and the order: ``rn_color_jitter_draw``), one
+pair of launches computes the contrast's mean gray when a contrast is enabled (``rn_color_mean``), and the operations run inside the
+transform kernel on every source pixel it reads (``rn_transform_batch_color``) -- all inside the captured step, each replay a new draw.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -26,7 +34,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-__all__ = ["RandomHorizontalFlip", "RandomShortSide", "hflip_u"]
+__all__ = ["RandomHorizontalFlip", "RandomShortSide", "ColorJitter", "hflip_u", "apply_color_ops"]
 
 _M64 = 2 ** 64 - 1
 
@@ -313,6 +321,300 @@ class RandomShortSide:
         self.reseed(int(state["seed"]), int(state["counter"]))
 
 
+# ---- colour jitter -----------------------------------------------------------------------------------------------------
+COLOR_OPS = ("brightness", "contrast", "saturation", "hue")         # operation ids 0..3 (include/retinanet_hip.h: rn_color_coef)
+COLOR_SKIP = 0xF
+COLOR_SALT_APPLY, COLOR_SALT_ORDER = 0xC0104A11C0104A11, 0x04DE404DE404DE45
+COLOR_SALT_FACTOR = (0xB416B416B416B417, 0xC0274A57C0274A57, 0x5A7C5A7C5A7C5A7D, 0x40E040E040E040E1)
+_COLOR_IDENTITY = (1.0, 1.0, 1.0, 0.0)
+_PERMS = None
+
+
+def color_order(idx: int, enabled_mask: int = 0xF) -> int:
+    "The idx-th permutation of (0, 1, 2, 3) in lexicographic order as four nibbles (nibble k = the k-th operation; disabled -> 0xF)."
+    global _PERMS
+    if _PERMS is None:
+        import itertools
+        _PERMS = list(itertools.permutations(range(4)))
+    return sum(((op if (enabled_mask >> op) & 1 else COLOR_SKIP) << (4 * k)) for k, op in enumerate(_PERMS[idx]))
+
+
+def order_ops(order: int) -> List[int]:
+    "The operation ids an ``order`` applies, in application order (the 0xF nibbles dropped)."
+    return [(order >> (4 * k)) & 0xF for k in range(4) if (order >> (4 * k)) & 0xF != COLOR_SKIP]
+
+
+def _gray(r: Tensor, g: Tensor, b: Tensor) -> Tensor:
+    c = r.new_tensor([0.2989, 0.587, 0.114])
+    return c[0] * r + c[1] * g + c[2] * b
+
+
+def _blend(x: Tensor, other, f: Tensor) -> Tensor:
+    return (f * x + (1.0 - f) * other).clamp(0.0, 1.0)
+
+
+def _hue(img: Tensor, f: Tensor) -> Tensor:
+    r, g, b = img.unbind(0)
+    one, six = img.new_tensor(1.0), img.new_tensor(6.0)
+    maxc, minc = img.max(0).values, img.min(0).values
+    eq = maxc == minc
+    cr = maxc - minc
+    s = cr / torch.where(eq, one, maxc)
+    d = torch.where(eq, one, cr)
+    rc, gc, bc = (maxc - r) / d, (maxc - g) / d, (maxc - b) / d
+    h0 = torch.where(maxc == r, bc - gc, torch.where(maxc == g, 2.0 + rc - bc, 4.0 + gc - rc))
+    h = torch.fmod(h0 / six + 1.0, one)
+    v = maxc
+    h = h + f
+    h = h - torch.floor(h)
+    h6 = h * 6.0
+    fl = torch.floor(h6)
+    ff = h6 - fl
+    i = torch.remainder(fl.to(torch.int32), 6)
+    p = (v * (1.0 - s)).clamp(0.0, 1.0)
+    q = (v * (1.0 - s * ff)).clamp(0.0, 1.0)
+    t = (v * (1.0 - s * (1.0 - ff))).clamp(0.0, 1.0)
+
+    def pick(c0, c1, c2, c3, c4, c5):
+        return torch.where(i == 0, c0, torch.where(i == 1, c1, torch.where(i == 2, c2, torch.where(i == 3, c3, torch.where(i == 4, c4, c5)))))
+    return torch.stack((pick(v, q, p, p, t, v), pick(t, v, v, q, p, p), pick(p, p, t, v, v, q)))
+
+
+def color_mean_of(image: Tensor) -> float:
+    "The contrast's mean: the gray values (fp32) of an fp32 ``[3, h, w]`` image summed in double, over h w, rounded to fp32."
+    gray = _gray(*image.unbind(0))
+    return float(np.float32(float(gray.to(torch.float64).sum()) / float(gray.numel())))
+
+
+def apply_color_ops(image: Tensor, factors: Sequence[float], order: int, mean: Optional[float] = None) -> Tensor:
+    """torchvision 0.8's tensor ColorJitter arithmetic on one fp32 RGB ``[3, h, w]`` image in [0, 1] (what the transform kernel runs per
+    pixel, ``csrc/rn_color.hpp``): the operations of ``order`` with ``factors`` (indexed by operation id), every step one fp32 rounding.
+    ``mean``: the contrast's mean gray when the caller has it, else computed here (``color_mean_of`` on the image as it is then)."""
+    if image.dim() != 3 or image.shape[0] != 3 or image.dtype != torch.float32:
+        raise ValueError(f"the colour jitter takes fp32 RGB [3, h, w] images in [0, 1], got {tuple(image.shape)} {image.dtype}")
+    x = image
+    for op in order_ops(order):
+        f = x.new_tensor(float(factors[op]))
+        if op == 0:
+            x = (x * f).clamp(0.0, 1.0)
+        elif op == 1:
+            x = _blend(x, x.new_tensor(color_mean_of(x) if mean is None else float(mean)), f)
+        elif op == 2:
+            x = _blend(x, _gray(*x.unbind(0))[None], f)
+        else:
+            x = _hue(x, f)
+    return x
+
+
+class ColorJitter:
+    """torchvision's ``ColorJitter`` for fp32 RGB training images in [0, 1], drawn and applied on the device.  ``brightness`` /
+    ``contrast`` / ``saturation``: a number v for factors in [max(0, 1 - v), 1 + v] or a pair (lo, hi); ``hue``: v for [-v, v] with
+    0 <= v <= 0.5 or a pair inside [-0.5, 0.5]; 0 or None disables an operation.  With probability ``p`` an image is jittered: its
+    enabled operations run in an order drawn from the 24 permutations, each with a factor drawn uniformly from its range.  Install it
+    as ``net.transform.color_jitter``; it acts only in training mode and only when targets are given, on the raw image (before the
+    normalisation, the resize and the flip).  Not an ``nn.Module``: it adds no key to the model's state dict.  ``seed``: the stream of
+    draws (``SimpleTrainer`` adds the rank under ``torch.distributed``)."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, p: float = 1.0, seed: int = 0):
+        self.base_seed = int(seed) & _M64
+        self._ranges = [self._check_range(n, v) for n, v in zip(COLOR_OPS, (brightness, contrast, saturation, hue))]
+        self._p, self._seed, self._counter = RandomHorizontalFlip._check_p(p), self.base_seed, 0
+        self._block: Optional[Tensor] = None          # rn_color_jitter_state on the device of the first CUDA batch (kept for good)
+        self._built_mask = self.enabled_mask          # what the launches of a captured step were chosen for (fixed once a block exists)
+        self.coef: Optional[Tensor] = None            # the last device batch's rn_color_coef rows (f32 [B, 8])
+        self.drawn: Optional[List[Tuple[Tuple[float, ...], int]]] = None     # the last host-drawn batch's (factors, order)
+
+    @staticmethod
+    def _check_range(name: str, value) -> Optional[Tuple[float, float]]:
+        "-> (lo, hi) as fp32 values, or None for a disabled operation (torchvision's ``_check_input``)."
+        hue = name == "hue"
+        if value is None:
+            return None
+        if isinstance(value, (list, tuple)):
+            if len(value) != 2:
+                raise ValueError(f"{name} must be a number or a pair (lo, hi), got {value!r}")
+            lo, hi = float(value[0]), float(value[1])
+        else:
+            v = float(value)
+            if v < 0:
+                raise ValueError(f"{name} must not be negative, got {value!r}")
+            lo, hi = (-v, v) if hue else (max(0.0, 1.0 - v), 1.0 + v)
+        bound = (-0.5, 0.5) if hue else (0.0, float("inf"))
+        if not bound[0] <= lo <= hi <= bound[1]:
+            raise ValueError(f"{name} range ({lo}, {hi}) must be ordered and inside [{bound[0]}, {bound[1]}]")
+        lo, hi = float(np.float32(lo)), float(np.float32(hi))
+        centre = 0.0 if hue else 1.0
+        return None if lo == hi == centre else (lo, hi)
+
+    def __repr__(self) -> str:
+        body = ", ".join(f"{n}={r}" for n, r in zip(COLOR_OPS, self._ranges))
+        return f"ColorJitter({body}, p={self._p}, seed={self._seed})"
+
+    # -- the draws ------------------------------------------------------------------------------------------------------
+    @property
+    def enabled_mask(self) -> int:
+        return sum(1 << k for k, r in enumerate(self._ranges) if r is not None)
+
+    def _lo_hi(self) -> Tuple[List[float], List[float]]:
+        "The block's lo / hi: a disabled operation holds its identity factor twice."
+        lo = [r[0] if r is not None else _COLOR_IDENTITY[k] for k, r in enumerate(self._ranges)]
+        hi = [r[1] if r is not None else _COLOR_IDENTITY[k] for k, r in enumerate(self._ranges)]
+        return lo, hi
+
+    @staticmethod
+    def draw_coefs(seed: int, counter: int, B: int, p: float, lo: Sequence[float], hi: Sequence[float],
+                   enabled_mask: int) -> List[Tuple[Tuple[float, ...], int]]:
+        """Pure-Python restatement of ``rn_color_jitter_draw``, bit for bit: per image (factors, order) -- the four factors as fp32
+        values, ``order`` the four nibbles (0xFFFF when the p draw leaves the image alone)."""
+        seed, counter, f32 = int(seed) & _M64, int(counter), np.float32
+        p32 = f32(p)
+        out = []
+        for b in range(int(B)):
+            applied = f32(hflip_u(seed ^ COLOR_SALT_APPLY, counter, b)) < p32
+            idx = min(int(f32(hflip_u(seed ^ COLOR_SALT_ORDER, counter, b)) * f32(24.0)), 23)
+            order = color_order(idx, enabled_mask) if applied else 0xFFFF
+            fac = tuple(float(f32(lo[k]) + f32(hflip_u(seed ^ COLOR_SALT_FACTOR[k], counter, b)) * (f32(hi[k]) - f32(lo[k]))) for k in range(4))
+            out.append((fac, order))
+        return out
+
+    def draw(self, counter: int, B: int) -> List[Tuple[Tuple[float, ...], int]]:
+        "The (factors, order) this object draws for a batch of B images at ``counter`` (no state change)."
+        lo, hi = self._lo_hi()
+        return self.draw_coefs(self._seed, counter, B, self._p, lo, hi, self.enabled_mask)
+
+    def next_draw(self, B: int) -> List[Tuple[Tuple[float, ...], int]]:
+        """The next batch's (factors, order) on the HOST, and the counter advanced by one: what CPU tensors and images the fused
+        transform does not take use (``apply_color_ops``).  With a device block the counter is read back and written (a
+        synchronisation); not inside a capture."""
+        n = self.counter
+        self.drawn = self.draw(n, B)
+        self._counter = n + 1
+        if self._block is not None:
+            from . import ops
+            ops.color_jitter_state_write(self._block, counter=n + 1)
+        return self.drawn
+
+    def next_coef(self, images) -> Tensor:
+        """The next batch's ``rn_color_coef`` rows (f32 [B, 8]) on the images' device, and the counter advanced by one: one
+        ``rn_color_jitter_draw`` launch and, when a contrast is enabled, ``rn_color_mean`` over the images (capturable; the block is
+        created at the first call, which must not be inside a capture).  ``images``: CUDA f32 ``[3, h, w]`` tensors or
+        ``ops.StagedImages``."""
+        from . import ops
+        staged = isinstance(images, ops.StagedImages)
+        device, B = (images.device, images.B) if staged else (images[0].device, len(images))
+        if device.type != "cuda":
+            raise RuntimeError("ColorJitter.next_coef draws on the GPU; CPU batches use next_draw()")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._block is None:
+            lo, hi = self._lo_hi()
+            self._built_mask = self.enabled_mask
+            self._block = ops.color_jitter_state(device, self._seed, self._counter, self._p, lo, hi, self._built_mask)
+        elif self._block.device != device:
+            # (a captured step holds the block's address: it is never replaced while this object lives)
+            raise RuntimeError(f"ColorJitter: its state lives on {self._block.device}, not {device}; use one object per device")
+        coef = ops.color_jitter_draw(self._block, B)
+        if self._built_mask & 2:                       # (a contrast that was never enabled launches nothing)
+            ops.color_mean(images, coef)
+        self.coef = coef
+        return coef
+
+    # -- settings and state ---------------------------------------------------------------------------------------------
+    def _range(self, k: int) -> Optional[Tuple[float, float]]:
+        return self._ranges[k]
+
+    def _set_range(self, k: int, value) -> None:
+        """A new range: written into the device block (no re-capture needed; not inside a capture).  Enabling an operation the object
+        was built without changes which kernels a step launches, so it is refused once the block exists."""
+        r = self._check_range(COLOR_OPS[k], value)
+        if self._block is not None and r is not None and not (self._built_mask >> k) & 1:
+            raise ValueError(f"ColorJitter: {COLOR_OPS[k]} was disabled when this object's device state was created; enabling it changes "
+                             "which kernels a (captured) step launches -- install a new ColorJitter instead")
+        self._ranges[k] = r
+        if self._block is not None:
+            from . import ops
+            lo, hi = self._lo_hi()
+            ops.color_jitter_state_write(self._block, lo=lo, hi=hi, enabled_mask=self.enabled_mask)
+
+    brightness = property(lambda self: self._range(0), lambda self, v: self._set_range(0, v))
+    contrast = property(lambda self: self._range(1), lambda self, v: self._set_range(1, v))
+    saturation = property(lambda self: self._range(2), lambda self, v: self._set_range(2, v))
+    hue = property(lambda self: self._range(3), lambda self, v: self._set_range(3, v))
+
+    @property
+    def p(self) -> float:
+        return self._p
+
+    @p.setter
+    def p(self, value: float) -> None:
+        "A new probability: written into the device block (no re-capture needed; not inside a capture)."
+        self._p = RandomHorizontalFlip._check_p(value)
+        if self._block is not None:
+            from . import ops
+            ops.color_jitter_state_write(self._block, p=self._p)
+
+    @property
+    def seed(self) -> int:
+        return self._seed
+
+    def reseed(self, seed: int, counter: int = 0) -> None:
+        "Start a new stream of draws (seed, counter); not inside a capture."
+        self._seed, self._counter = int(seed) & _M64, int(counter)
+        if self._block is not None:
+            from . import ops
+            ops.color_jitter_state_write(self._block, seed=self._seed, counter=self._counter)
+
+    def set_rank(self, rank: int) -> None:
+        "One stream per data-parallel rank: seed = ``base_seed`` (the constructor's) + rank, the counter kept."
+        self.reseed((self.base_seed + int(rank)) & _M64, self.counter)
+
+    @property
+    def counter(self) -> int:
+        "Batches drawn so far (with the device block: one read-back, i.e. a synchronisation)."
+        if self._block is not None:
+            from . import ops
+            return int(ops.color_jitter_state_read(self._block)[1])
+        return self._counter
+
+    def state_dict(self) -> Dict[str, object]:
+        state = {"seed": self._seed, "counter": self.counter, "p": self._p}
+        state.update({n: (None if r is None else list(r)) for n, r in zip(COLOR_OPS, self._ranges)})
+        return state
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        for k, n in enumerate(COLOR_OPS):
+            self._set_range(k, state[n])
+        self.p = state["p"]
+        self.reseed(int(state["seed"]), int(state["counter"]))
+
+
+_COLOR_JITTER_NAMES = ("albumentations.ColorJitter", "torchvision.transforms.ColorJitter", "ColorJitter")
+
+
+def color_jitter_from_transforms(entries, seed: int = 0, log=None) -> Optional[ColorJitter]:
+    """The colour jitter an hparams ``transforms`` list asks for, or None.  ``albumentations.ColorJitter`` (brightness, contrast,
+    saturation and hue default to 0.2, ``p`` to 0.5; ``always_apply: true`` means p = 1) and ``torchvision.transforms.ColorJitter`` /
+    a bare ``ColorJitter`` (each default 0, p = 1) map onto ``ColorJitter``, whose arithmetic is torchvision's tensor algorithm:
+    albumentations works on uint8 through OpenCV and differs slightly.  Other entries are ``from_transforms``' business."""
+    import logging
+    log = log or logging.getLogger(__name__)
+    found = None
+    for e in entries or []:
+        name = str(e.get("class_name", "")) if isinstance(e, dict) else str(e)
+        params = dict(e.get("params") or {}) if isinstance(e, dict) else {}
+        if name not in _COLOR_JITTER_NAMES:
+            continue
+        if found is not None:
+            log.warning("transforms: a second colour jitter (%s) is skipped", name)
+            continue
+        alb = name.startswith("albumentations.")
+        default = 0.2 if alb else 0
+        p = 1.0 if params.get("always_apply") else float(params.get("p", 0.5 if alb else 1.0))
+        kw = {n: params.get(n, default) for n in COLOR_OPS}
+        found = ColorJitter(p=p, seed=seed, **{n: (tuple(v) if isinstance(v, (list, tuple)) else v) for n, v in kw.items()})
+    return found
+
+
 def from_transforms(entries, seed: int = 0, log=None) -> Optional[RandomHorizontalFlip]:
     """The flip an hparams ``transforms`` list asks for (reference ``hparams.yaml:55-58``), or None.  ``albumentations.HorizontalFlip``
     (``p``, default 0.5; ``always_apply: true`` means p = 1) and ``RandomHorizontalFlip`` (``prob``, default 0.5; any module path) map
@@ -328,9 +630,11 @@ def from_transforms(entries, seed: int = 0, log=None) -> Optional[RandomHorizont
             p = 1.0 if params.get("always_apply") else float(params.get("p", 0.5))
         elif short == "RandomHorizontalFlip":
             p = float(params.get("prob", params.get("p", 0.5)))
+        elif name in _COLOR_JITTER_NAMES:              # color_jitter_from_transforms maps these
+            continue
         else:
-            log.warning("transforms: %s is not supported (albumentations is not available; only the horizontal flip is implemented, "
-                        "on the GPU): skipped", name)
+            log.warning("transforms: %s is not supported (albumentations is not available; only the horizontal flip and ColorJitter are "
+                        "implemented, on the GPU): skipped", name)
             continue
         if found is not None:
             log.warning("transforms: a second horizontal flip (%s) is skipped", name)

@@ -44,6 +44,27 @@
 // both).  With a null block the short side is a value passed by the host (a transform without multi-scale training) and nothing
 // is drawn.  No table in the kernel arguments: one wave walks the images 64 at a time, so one launch serves any B.  A size < 1
 // (device data) gives out_hw = (0, 0) and ratios (0, 0): the transform kernel treats such an image as all padding.
+//
+// Colour jitter (augment.ColorJitter: torchvision's ColorJitter on fp32 RGB in [0, 1]) is drawn the same way once more:
+//
+//   rn_color_jitter_draw   coef[b] = {four factors, mean = 0, order} for b < B, then counter += 1
+//
+// with the block rn_color_jitter_state (seed, counter, p, lo[4], hi[4], enabled_mask) and six salts, one per uniform:
+//
+//   applied = u_apply < p                                                               (fp32 compare)
+//   order   = the min(int(u_order * 24), 23)-th permutation of (brightness, contrast, saturation, hue) in lexicographic order, as
+//             four nibbles; a disabled operation's nibble is 0xF, and so is every nibble of an image that is not applied
+//   f[k]    = lo[k] + u_k * (hi[k] - lo[k])                                             (fp32, this order; drawn whatever ``applied``)
+//
+// The operations themselves run inside the transform kernel (transform.hip, rn_color.hpp).  The one thing that is not per-pixel is
+// the contrast's mean gray, taken over the image as it is when the contrast's turn comes:
+//
+//   rn_color_mean   coef[b].mean = float(sum_pixels double(gray(pre(pixel))) / double(h w)) for the images whose order holds a contrast
+//
+// pre = the operations before the contrast, by the helper the transform kernel calls.  No atomics: 32 blocks per image, thread t of
+// block k adds the pixels k * 256 + t + j * 8192 in order of j, the block adds its 256 sums as a fixed tree, and a second single-wave
+// launch adds an image's 32 partials in index order -- two calls give the same bits.
+#include "rn_color.hpp"
 #include "rn_common.hpp"
 
 namespace {
@@ -141,7 +162,174 @@ __global__ __launch_bounds__(HF_BLOCK) void resize_plan_dev_kernel(rn_short_side
     if (DRAW && threadIdx.x == 0) st->counter = counter + 1;
 }
 
+// ---- colour jitter: the draw and the contrast mean (augment.ColorJitter) -------------------------------------------------------------
+constexpr uint64_t CJ_SALT_APPLY = 0xC0104A11C0104A11ull, CJ_SALT_ORDER = 0x04DE404DE404DE45ull;
+constexpr uint64_t CJ_SALT_F0 = 0xB416B416B416B417ull, CJ_SALT_F1 = 0xC0274A57C0274A57ull, CJ_SALT_F2 = 0x5A7C5A7C5A7C5A7Dull,
+                   CJ_SALT_F3 = 0x40E040E040E040E1ull;
+
+// the idx-th permutation of (0, 1, 2, 3) in lexicographic order as four nibbles (nibble k = the k-th element), ids outside ``mask`` -> 0xF
+__device__ __forceinline__ int color_order(int idx, const int mask)
+{
+    int avail = 0x3210, order = 0;      // the ids not yet placed, ascending
+    const int div[4] = {6, 2, 1, 1};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = idx / div[k];     // which of the remaining ids comes next (0 at k = 3: idx is 0 by then)
+        idx -= d * div[k];
+        const int id = (avail >> (4 * d)) & 0xF;
+        avail = (avail & ((1 << (4 * d)) - 1)) | ((avail >> (4 * d + 4)) << (4 * d));
+        order |= (((mask >> id) & 1) ? id : rn::COLOR_SKIP) << (4 * k);
+    }
+    return order;
+}
+
+__global__ __launch_bounds__(HF_BLOCK) void color_jitter_draw_kernel(rn_color_jitter_state *st, const int B, rn_color_coef *__restrict__ coef)
+{
+    const uint64_t seed = st->seed;
+    const int64_t counter = st->counter;
+    const float p = st->p;
+    const int mask = st->enabled_mask & 0xF;
+    float lo[4], hi[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { lo[k] = st->lo[k]; hi[k] = st->hi[k]; }
+    const uint64_t salt[4] = {CJ_SALT_F0, CJ_SALT_F1, CJ_SALT_F2, CJ_SALT_F3};
+    for (int b = (int)threadIdx.x; b < B; b += HF_BLOCK) {
+        rn_color_coef c;
+        const bool applied = hflip_u(seed ^ CJ_SALT_APPLY, counter, b) < p;
+        int idx = (int)(hflip_u(seed ^ CJ_SALT_ORDER, counter, b) * 24.0f);
+        idx = idx < 23 ? idx : 23;
+        c.order = applied ? color_order(idx, mask) : 0xFFFF;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c.f[k] = lo[k] + hflip_u(seed ^ salt[k], counter, b) * (hi[k] - lo[k]);
+        c.mean = 0.0f;
+        c.pad[0] = c.pad[1] = 0;
+        coef[b] = c;
+    }
+    // (one wave: every lane read the counter above, in program order before this store)
+    if (threadIdx.x == 0) st->counter = counter + 1;
+}
+
+constexpr int CM_MAX_IMAGES = 64;   // per launch (kernel-argument table)
+constexpr int CM_BLOCKS = 32;       // blocks per image: fixed, so the order of every sum is
+constexpr int CM_BLOCK = 256;
+
+struct ColorMeanArgs {
+    const float *img[CM_MAX_IMAGES];   // [3][h][w] f32, contiguous
+    int32_t ih[CM_MAX_IMAGES], iw[CM_MAX_IMAGES];
+    const float *arena;                // VAR: this launch's first image's slot (device); img / ih / iw above are unused
+    const int32_t *in_hw;              // VAR: this launch's first image's (ih, iw) (device)
+    int64_t slot;                      // VAR: floats per slot
+    rn_color_coef *coef;               // this launch's first image
+    double *partial;                   // this launch's first image: [image][CM_BLOCKS]
+};
+
+// (ih, iw) of image b of the launch; false: an image no slot can hold (device data) -- the guards of transform_batch_kernel<VAR>
+template <bool VAR>
+__device__ __forceinline__ bool color_mean_size(const ColorMeanArgs &a, const int b, int &ih, int &iw)
+{
+    ih = VAR ? a.in_hw[2 * b] : a.ih[b];
+    iw = VAR ? a.in_hw[2 * b + 1] : a.iw[b];
+    return !(VAR && (ih < 1 || iw < 1 || (int64_t)ih * iw > a.slot / 3));
+}
+
+// partial[b][blockIdx.x] = the sum in double, in a fixed order, of gray(pre(pixel)) over the pixels blockIdx.x * 256 + t + j * 8192
+template <bool VAR>
+__global__ __launch_bounds__(CM_BLOCK) void color_mean_partial_kernel(const ColorMeanArgs a)
+{
+    __shared__ double sums[CM_BLOCK];
+    const int b = blockIdx.y;
+    const rn_color_coef c = a.coef[b];
+    if (!rn::color_has_contrast(c.order)) return;
+    int ih, iw;
+    const bool fits = color_mean_size<VAR>(a, b, ih, iw);
+    double acc = 0.0;
+    if (fits) {
+        const float *__restrict__ src = VAR ? a.arena + (int64_t)b * a.slot : a.img[b];
+        const int64_t plane = (int64_t)ih * iw;
+        for (int64_t i = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x; i < plane; i += (int64_t)CM_BLOCKS * CM_BLOCK) {
+            float r = src[i], g = src[plane + i], bl = src[2 * plane + i];
+            rn::color_apply<true>(r, g, bl, c);
+            acc += (double)rn::color_gray(r, g, bl);
+        }
+    }
+    sums[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = CM_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sums[threadIdx.x] += sums[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.partial[(int64_t)b * CM_BLOCKS + blockIdx.x] = sums[0];
+}
+
+// lane i: image i of the launch -- its partials added in index order, mean = float(sum / double(h w)); 0 for an image no slot holds
+template <bool VAR>
+__global__ __launch_bounds__(HF_BLOCK) void color_mean_finish_kernel(const ColorMeanArgs a, const int cnt)
+{
+    const int b = (int)threadIdx.x;
+    if (b >= cnt) return;
+    if (!rn::color_has_contrast(a.coef[b].order)) return;
+    int ih, iw;
+    if (!color_mean_size<VAR>(a, b, ih, iw)) { a.coef[b].mean = 0.0f; return; }
+    double sum = 0.0;
+    for (int k = 0; k < CM_BLOCKS; ++k) sum += a.partial[(int64_t)b * CM_BLOCKS + k];
+    a.coef[b].mean = (float)(sum / (double)((int64_t)ih * iw));
+}
+
 }  // namespace
+
+RN_API int rn_color_jitter_draw(rn_color_jitter_state *state, int B, rn_color_coef *coef, void *stream)
+{
+    if (!state || !coef || B <= 0) return RN_EINVAL;
+    if (!rn::aligned(state, 8) || !rn::aligned(coef, 4)) return RN_EALIGN;
+    hipLaunchKernelGGL(color_jitter_draw_kernel, dim3(1), dim3(HF_BLOCK), 0, (hipStream_t)stream, state, B, coef);
+    RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
+RN_API size_t rn_color_mean_workspace_bytes(int B)
+{
+    return B > 0 ? (size_t)B * CM_BLOCKS * sizeof(double) : 0;
+}
+
+RN_API int rn_color_mean(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev, int B,
+                         rn_color_coef *coef, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const bool var = arena != nullptr;
+    if (!coef || !workspace || B <= 0) return RN_EINVAL;
+    if (var ? (images || in_hw || !in_hw_dev || slot < 3) : (!images || !in_hw || in_hw_dev)) return RN_EINVAL;
+    if (workspace_bytes < rn_color_mean_workspace_bytes(B)) return RN_EINVAL;
+    if (!rn::aligned(coef, 4) || !rn::aligned(workspace, 8)) return RN_EALIGN;
+    if (var && (!rn::aligned(arena, 16) || !rn::aligned(in_hw_dev, 4))) return RN_EALIGN;
+    for (int b = 0; b < B && !var; ++b) {
+        if (!images[b] || in_hw[2 * b] <= 0 || in_hw[2 * b + 1] <= 0) return RN_EINVAL;
+        if (!rn::aligned(images[b], 4)) return RN_EALIGN;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int b0 = 0; b0 < B; b0 += CM_MAX_IMAGES) {
+        const int cnt = (B - b0) < CM_MAX_IMAGES ? (B - b0) : CM_MAX_IMAGES;
+        ColorMeanArgs a;
+        for (int i = 0; i < CM_MAX_IMAGES; ++i) {
+            const bool on = !var && i < cnt;
+            a.img[i] = on ? (const float *)images[b0 + i] : nullptr;
+            a.ih[i] = on ? in_hw[2 * (b0 + i)] : 0;
+            a.iw[i] = on ? in_hw[2 * (b0 + i) + 1] : 0;
+        }
+        a.arena = var ? arena + (int64_t)b0 * slot : nullptr;
+        a.in_hw = var ? in_hw_dev + 2 * b0 : nullptr;
+        a.slot = slot;
+        a.coef = coef + b0;                                      // (this launch's first image: the kernels index from 0)
+        a.partial = (double *)workspace + (int64_t)b0 * CM_BLOCKS;
+        if (var) {
+            hipLaunchKernelGGL(color_mean_partial_kernel<true>, dim3(CM_BLOCKS, (unsigned)cnt), dim3(CM_BLOCK), 0, st, a);
+            hipLaunchKernelGGL(color_mean_finish_kernel<true>, dim3(1), dim3(HF_BLOCK), 0, st, a, cnt);
+        } else {
+            hipLaunchKernelGGL(color_mean_partial_kernel<false>, dim3(CM_BLOCKS, (unsigned)cnt), dim3(CM_BLOCK), 0, st, a);
+            hipLaunchKernelGGL(color_mean_finish_kernel<false>, dim3(1), dim3(HF_BLOCK), 0, st, a, cnt);
+        }
+        RN_LAUNCH_CHECK();
+    }
+    return RN_OK;
+}
 
 RN_API int rn_hflip_draw(rn_hflip_state *state, int B, uint8_t *flags, void *stream)
 {

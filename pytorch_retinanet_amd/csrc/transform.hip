@@ -36,6 +36,14 @@
 // rn_image_stage copies B dense f32 [3][h_b][w_b] images into their arena slots and writes in_hw on the device: ONE launch per 64
 // images with the pointers and sizes passed BY VALUE in the kernel arguments (like rn_gt_stage), 16-byte vector copies when the
 // source is 16-byte aligned (a slot always is) and 4-byte copies otherwise and for the tail.
+//
+// rn_transform_batch_color is any of the launches above with the train-time colour jitter (augment.ColorJitter) applied to the raw
+// pixels: template flag COLOR, and per image a rn_color_coef on the device (rn_color_jitter_draw writes the factors and the order
+// inside a captured step, rn_color_mean the contrast mean).  With COLOR every tap loads its three channels, runs the operations of
+// coef[b].order on the triple (rn_color.hpp; b = blockIdx.z, so the branches are wave-uniform) and is then normalised and blended as
+// above.  The jitter is per pixel apart from the mean, so it commutes with the flip; an order of all 0xF gives the plain launch's bits.
+// The COLOR = false instantiations are the code they were.
+#include "rn_color.hpp"
 #include "rn_common.hpp"
 
 namespace {
@@ -54,6 +62,7 @@ struct TransformArgs {
     const float *arena;                // VAR: this launch's first image's slot (device); img / ih / iw above are unused
     const int32_t *in_hw;              // VAR: this launch's first image's (ih, iw) (device)
     int64_t slot;                      // VAR: floats per slot
+    const rn_color_coef *coef;         // COLOR: this launch's first image's coefficients (device)
 };
 
 __device__ __forceinline__ void tap_axis(const int dst, const int in, const int out, int &i0, int &i1, float &l0, float &l1)
@@ -89,8 +98,17 @@ template <> struct store4<RN_F16> {
     }
 };
 
+// COLOR: the three channels of the source pixel at ``at`` after the colour operations of c, normalised
+__device__ __forceinline__ void color_tap(const float *__restrict__ src, const int64_t plane, const int64_t at, const rn_color_coef &c,
+                                          const float (&mean)[3], const float (&std)[3], float (&o)[3])
+{
+    float r = src[at], g = src[plane + at], b = src[2 * plane + at];
+    rn::color_apply<false>(r, g, b, c);
+    o[0] = (r - mean[0]) / std[0]; o[1] = (g - mean[1]) / std[1]; o[2] = (b - mean[2]) / std[2];
+}
+
 // VAR implies DEV
-template <int DT, bool NHWC, bool FLIP, bool DEV, bool VAR>
+template <int DT, bool NHWC, bool FLIP, bool DEV, bool VAR, bool COLOR>
 __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArgs a)
 {
     const int b = blockIdx.z;
@@ -118,7 +136,32 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
         const int64_t plane = (int64_t)ih * iw;
         int y0, y1; float ly0, ly1;
         tap_axis(y, ih, oh, y0, y1, ly0, ly1);
-        if (ih == oh && iw == ow) {                             // identity: one tap
+        if (COLOR) {
+            const rn_color_coef cc = a.coef[b];
+            const bool ident = ih == oh && iw == ow;             // one tap, as below
+#pragma unroll
+            for (int p = 0; p < TB_PX; ++p) {
+                const int x = x0 + p;
+                if (x < ow) {
+                    int xa, xb; float lx0, lx1;
+                    tap_axis(x, iw, ow, xa, xb, lx0, lx1);
+                    if (flip) { xa = iw - 1 - xa; xb = iw - 1 - xb; }
+                    float p00[3];
+                    color_tap(src, plane, (int64_t)y0 * iw + xa, cc, a.mean, a.std, p00);
+                    if (ident) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) v[c][p] = p00[c];
+                    } else {
+                        float p01[3], p10[3], p11[3];
+                        color_tap(src, plane, (int64_t)y0 * iw + xb, cc, a.mean, a.std, p01);
+                        color_tap(src, plane, (int64_t)y1 * iw + xa, cc, a.mean, a.std, p10);
+                        color_tap(src, plane, (int64_t)y1 * iw + xb, cc, a.mean, a.std, p11);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) v[c][p] = ly0 * (lx0 * p00[c] + lx1 * p01[c]) + ly1 * (lx0 * p10[c] + lx1 * p11[c]);
+                    }
+                }
+            }
+        } else if (ih == oh && iw == ow) {                      // identity: one tap
 #pragma unroll
             for (int p = 0; p < TB_PX; ++p) {
                 const int x = x0 + p;
@@ -164,9 +207,10 @@ __global__ __launch_bounds__(256) void transform_batch_kernel(const TransformArg
 // arena / slot / in_hw_dev (the staged images on the DEVICE) in their place -- only together with out_hw_dev
 int transform_batch(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev,
                     const int32_t *out_hw, const int32_t *out_hw_dev, int B, const float mean[3], const float std[3], int Hp, int Wp,
-                    void *out, int out_dtype, int channels_last, const uint8_t *flags, void *stream)
+                    void *out, int out_dtype, int channels_last, const uint8_t *flags, const rn_color_coef *coef, void *stream)
 {
     const bool var = arena != nullptr;
+    if (coef && !rn::aligned(coef, 4)) return RN_EALIGN;
     if ((!out_hw == !out_hw_dev) || !mean || !std || !out || B <= 0 || Hp <= 0 || Wp <= 0) return RN_EINVAL;
     if (var ? (images || in_hw || !in_hw_dev || !out_hw_dev || slot < 3) : (!images || !in_hw || in_hw_dev))
         return RN_EINVAL;
@@ -202,10 +246,13 @@ int transform_batch(const void *const *images, const int32_t *in_hw, const float
         a.out = (unsigned char *)out + (size_t)b0 * 3 * Hp * Wp * esz;
         a.flags = flags ? flags + b0 : nullptr;
         a.out_hw = out_hw_dev ? out_hw_dev + 2 * b0 : nullptr;
+        a.coef = coef ? coef + b0 : nullptr;
         const dim3 blk(256), grid((unsigned)((Wp / TB_PX + 255) / 256), (unsigned)Hp, (unsigned)a.B);
+#define RN_TB_LAUNCH_C(DT, NHWC, FLIP, DEV, VAR)                                                                          \
+        if (coef) hipLaunchKernelGGL((transform_batch_kernel<DT, NHWC, FLIP, DEV, VAR, true>), grid, blk, 0, st, a);      \
+        else hipLaunchKernelGGL((transform_batch_kernel<DT, NHWC, FLIP, DEV, VAR, false>), grid, blk, 0, st, a)
 #define RN_TB_LAUNCH_L(DT, FLIP, DEV, VAR)                                                                                \
-        if (channels_last) hipLaunchKernelGGL((transform_batch_kernel<DT, true, FLIP, DEV, VAR>), grid, blk, 0, st, a);   \
-        else hipLaunchKernelGGL((transform_batch_kernel<DT, false, FLIP, DEV, VAR>), grid, blk, 0, st, a)
+        if (channels_last) { RN_TB_LAUNCH_C(DT, true, FLIP, DEV, VAR); } else { RN_TB_LAUNCH_C(DT, false, FLIP, DEV, VAR); }
 #define RN_TB_LAUNCH(DT)                                                                                                  \
         if (var) {                                                                                                        \
             if (flags) { RN_TB_LAUNCH_L(DT, true, true, true); } else { RN_TB_LAUNCH_L(DT, false, true, true); }          \
@@ -221,6 +268,7 @@ int transform_batch(const void *const *images, const int32_t *in_hw, const float
         }
 #undef RN_TB_LAUNCH
 #undef RN_TB_LAUNCH_L
+#undef RN_TB_LAUNCH_C
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
@@ -294,7 +342,7 @@ RN_API int rn_transform_batch(const void *const *images, const int32_t *in_hw, c
                               int channels_last, void *stream)
 {
     if (!out_hw) return RN_EINVAL;
-    return transform_batch(images, in_hw, nullptr, 0, nullptr, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, nullptr, stream);
+    return transform_batch(images, in_hw, nullptr, 0, nullptr, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, nullptr, nullptr, stream);
 }
 
 RN_API int rn_transform_batch_flip(const void *const *images, const int32_t *in_hw, const int32_t *out_hw, int B,
@@ -302,7 +350,7 @@ RN_API int rn_transform_batch_flip(const void *const *images, const int32_t *in_
                                    int channels_last, const uint8_t *flags, void *stream)
 {
     if (!flags || !out_hw) return RN_EINVAL;
-    return transform_batch(images, in_hw, nullptr, 0, nullptr, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags, stream);
+    return transform_batch(images, in_hw, nullptr, 0, nullptr, out_hw, nullptr, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags, nullptr, stream);
 }
 
 RN_API int rn_transform_batch_dev(const void *const *images, const int32_t *in_hw, int B, const float mean[3], const float std[3],
@@ -310,7 +358,7 @@ RN_API int rn_transform_batch_dev(const void *const *images, const int32_t *in_h
                                   const uint8_t *flags_or_null, void *stream)
 {
     if (!out_hw_dev) return RN_EINVAL;
-    return transform_batch(images, in_hw, nullptr, 0, nullptr, nullptr, out_hw_dev, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags_or_null, stream);
+    return transform_batch(images, in_hw, nullptr, 0, nullptr, nullptr, out_hw_dev, B, mean, std, Hp, Wp, out, out_dtype, channels_last, flags_or_null, nullptr, stream);
 }
 
 RN_API int rn_transform_batch_var(const float *arena, int64_t slot, const int32_t *in_hw_dev, const int32_t *out_hw_dev, int B,
@@ -319,5 +367,15 @@ RN_API int rn_transform_batch_var(const float *arena, int64_t slot, const int32_
 {
     if (!arena || !in_hw_dev || !out_hw_dev) return RN_EINVAL;
     return transform_batch(nullptr, nullptr, arena, slot, in_hw_dev, nullptr, out_hw_dev, B, mean, std, Hp, Wp, out, out_dtype, channels_last,
-                           flags_or_null, stream);
+                           flags_or_null, nullptr, stream);
+}
+
+RN_API int rn_transform_batch_color(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev,
+                                    const int32_t *out_hw, const int32_t *out_hw_dev, int B, const float mean[3], const float std[3], int Hp,
+                                    int Wp, void *out, int out_dtype, int channels_last, const uint8_t *flags_or_null,
+                                    const rn_color_coef *coef, void *stream)
+{
+    if (!coef) return RN_EINVAL;
+    return transform_batch(images, in_hw, arena, slot, in_hw_dev, out_hw, out_hw_dev, B, mean, std, Hp, Wp, out, out_dtype, channels_last,
+                           flags_or_null, coef, stream);
 }

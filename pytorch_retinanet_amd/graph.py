@@ -44,6 +44,8 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     Multi-scale training (``net.transform.scale_jitter``, ``augment.RandomShortSide``) is keyed by the installed object too: the short
     sides are drawn inside the step from the object's device block and the padded canvas depends on the image shapes alone, so one
     graph replays while the scales vary (the host-side draw from a ``min_size`` tuple makes nearly every batch a new signature).
+    The colour jitter (``net.transform.color_jitter``, ``augment.ColorJitter``) is keyed by the installed object as well: factors and
+    order are drawn inside the step from its device block, so its ranges and p may change between replays.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -530,7 +532,12 @@ class CapturedTrainStep:
         # the short side drawn on the device (transform.scale_jitter): the draw is part of the step and reads seed / counter / sizes from
         # the object's device block, and the canvas follows from the image shapes -- the object again.  Without one nothing is added.
         jitter = getattr(getattr(self.net, "transform", None), "scale_jitter", None)
-        return key if jitter is None else key + (("scale_jitter", jitter),)
+        if jitter is not None:
+            key = key + (("scale_jitter", jitter),)
+        # the colour jitter (transform.color_jitter): drawn inside the step from the object's device block and applied by the transform
+        # kernel -- the object once more: new ranges or a new p replay the same graph.  Without one nothing is added.
+        color = getattr(getattr(self.net, "transform", None), "color_jitter", None)
+        return key if color is None else key + (("color_jitter", color),)
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."

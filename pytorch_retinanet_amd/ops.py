@@ -560,14 +560,18 @@ def image_hw_tensor(sizes: Sequence[Tuple[int, int]], device: torch.device) -> T
 
 def transform_batch(images: Sequence[Tensor], out_sizes: Sequence[Tuple[int, int]], mean: Sequence[float],
                     std: Sequence[float], Hp: int, Wp: int, out_dtype: torch.dtype = torch.float32,
-                    channels_last: bool = False, flags: Optional[Tensor] = None) -> Tensor:
+                    channels_last: bool = False, flags: Optional[Tensor] = None, coef: Optional[Tensor] = None) -> Tensor:
     """T1: (x - mean) / std -> bilinear resize of image b to out_sizes[b] -> zero-padded batch
     ``[B, 3, Hp, Wp]`` (``out_dtype``; channels_last memory format on request) in one launch.
     images: CUDA f32 ``[3, h, w]`` tensors; Wp % 4 == 0.  ``flags`` (uint8 [>= B] on the images' device, ``hflip_draw``): image b is
-    horizontally flipped first where flags[b] != 0 (``rn_transform_batch_flip``: bit-identical to the transform of ``img.flip(-1)``)."""
+    horizontally flipped first where flags[b] != 0 (``rn_transform_batch_flip``: bit-identical to the transform of ``img.flip(-1)``).
+    ``coef`` (f32 [B, 8] = ``rn_color_coef`` per image, ``color_jitter_draw`` / ``color_mean``): the colour jitter applied to the raw
+    pixels (``rn_transform_batch_color``)."""
     dev = _need_dev(*images)
     if flags is not None:
         _check_flags(flags, len(images), dev)
+    if coef is not None:
+        _check_coef(coef, len(images), dev)
     B = len(images)
     if B == 0 or len(out_sizes) != B:
         raise ValueError("need one output size per image")
@@ -584,7 +588,11 @@ def transform_batch(images: Sequence[Tensor], out_sizes: Sequence[Tuple[int, int
     in_hw = (C.c_int32 * (2 * B))(*[int(v) for im in imgs for v in im.shape[1:]])
     out_hw = (C.c_int32 * (2 * B))(*[int(v) for s in out_sizes for v in s])
     with torch.cuda.device(dev), _timed("transform_batch", dev):
-        if flags is None:
+        if coef is not None:
+            check(lib.rn_transform_batch_color(ptrs, in_hw, None, 0, None, out_hw, None, B, (C.c_float * 3)(*mean), (C.c_float * 3)(*std),
+                                               int(Hp), int(Wp), _ptr(out), _DT[out_dtype], int(bool(channels_last)), _ptr(flags),
+                                               _ptr(coef), _stream(dev)), "rn_transform_batch_color")
+        elif flags is None:
             check(lib.rn_transform_batch(ptrs, in_hw, out_hw, B, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(Hp), int(Wp),
                                          _ptr(out), _DT[out_dtype], int(bool(channels_last)), _stream(dev)), "rn_transform_batch")
         else:
@@ -595,11 +603,14 @@ def transform_batch(images: Sequence[Tensor], out_sizes: Sequence[Tuple[int, int
 
 
 def transform_batch_dev(images: Sequence[Tensor], out_hw: Tensor, mean: Sequence[float], std: Sequence[float], Hp: int, Wp: int,
-                        out_dtype: torch.dtype = torch.float32, channels_last: bool = False, flags: Optional[Tensor] = None) -> Tensor:
+                        out_dtype: torch.dtype = torch.float32, channels_last: bool = False, flags: Optional[Tensor] = None,
+                        coef: Optional[Tensor] = None) -> Tensor:
     """``transform_batch`` with the output sizes on the device (``rn_transform_batch_dev``): ``out_hw`` int32 [B, 2] on the images'
     device, as ``short_side_draw`` writes it; ``Hp`` / ``Wp`` stay host values (a size above the canvas is clamped in the kernel).
-    Bit-identical to ``transform_batch`` called with the same sizes on the host, with or without ``flags``."""
+    Bit-identical to ``transform_batch`` called with the same sizes on the host, with or without ``flags`` / ``coef``."""
     dev = _need_dev(*images, out_hw)
+    if coef is not None:
+        _check_coef(coef, len(images), dev)
     B = len(images)
     if B == 0:
         raise ValueError("need at least one image")
@@ -619,6 +630,11 @@ def transform_batch_dev(images: Sequence[Tensor], out_hw: Tensor, mean: Sequence
     ptrs = (C.c_void_p * B)(*[im.data_ptr() for im in imgs])
     in_hw = (C.c_int32 * (2 * B))(*[int(v) for im in imgs for v in im.shape[1:]])
     with torch.cuda.device(dev), _timed("transform_batch", dev):
+        if coef is not None:
+            check(lib.rn_transform_batch_color(ptrs, in_hw, None, 0, None, None, _ptr(out_hw), B, (C.c_float * 3)(*mean),
+                                               (C.c_float * 3)(*std), int(Hp), int(Wp), _ptr(out), _DT[out_dtype], int(bool(channels_last)),
+                                               _ptr(flags), _ptr(coef), _stream(dev)), "rn_transform_batch_color")
+            return out
         check(lib.rn_transform_batch_dev(ptrs, in_hw, B, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(Hp), int(Wp), _ptr(out),
                                          _DT[out_dtype], int(bool(channels_last)), _ptr(out_hw), _ptr(flags), _stream(dev)),
               "rn_transform_batch_dev")
@@ -677,6 +693,110 @@ def hflip_draw(block: Tensor, B: int) -> Tensor:
     with torch.cuda.device(dev), _timed("hflip_draw", dev):
         check(lib.rn_hflip_draw(_ptr(block), B, _ptr(flags), _stream(dev)), "rn_hflip_draw")
     return flags
+
+
+# ---- train-time colour jitter (augment.ColorJitter) ----------------------------------------------------------------------------
+# include/retinanet_hip.h: rn_color_jitter_state = seed u64, counter i64, p f32, lo f32[4], hi f32[4], enabled_mask i32
+COLOR_JITTER_STATE_BYTES = 56
+COLOR_COEF_FLOATS = 8                  # rn_color_coef: f f32[4], mean f32, order i32, pad i32[2]
+COLOR_OPS = ("brightness", "contrast", "saturation", "hue")        # the operation ids 0..3
+COLOR_IDENTITY = (1.0, 1.0, 1.0, 0.0)  # the factor that leaves the pixel alone (what a disabled operation's range holds)
+
+
+def _check_color_block(block: Tensor) -> torch.device:
+    dev = _need_dev(block)
+    if block.dtype != torch.uint8 or block.numel() != COLOR_JITTER_STATE_BYTES or block.data_ptr() % 8:
+        raise ValueError("block must be an rn_color_jitter_state made by color_jitter_state()")
+    return dev
+
+
+def _check_coef(coef: Tensor, B: int, dev: torch.device) -> None:
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (B, COLOR_COEF_FLOATS) or not coef.is_contiguous() or coef.device != dev:
+        raise ValueError(f"coef must be a contiguous f32 [{B}, {COLOR_COEF_FLOATS}] tensor (rn_color_coef per image) on {dev}, got "
+                         f"{tuple(coef.shape)} {coef.dtype} on {coef.device}")
+
+
+def color_jitter_state(dev: torch.device, seed: int, counter: int, p: float, lo: Sequence[float], hi: Sequence[float],
+                       enabled_mask: int) -> Tensor:
+    "A new ``rn_color_jitter_state`` block (uint8 [56]) on ``dev``: one host->device copy, outside any capture."
+    block = torch.empty((COLOR_JITTER_STATE_BYTES,), dtype=torch.uint8, device=dev)
+    color_jitter_state_write(block, seed=seed, counter=counter, p=p, lo=lo, hi=hi, enabled_mask=enabled_mask)
+    return block
+
+
+def color_jitter_state_write(block: Tensor, seed: Optional[int] = None, counter: Optional[int] = None, p: Optional[float] = None,
+                             lo: Optional[Sequence[float]] = None, hi: Optional[Sequence[float]] = None,
+                             enabled_mask: Optional[int] = None) -> None:
+    """Overwrite the given fields of an ``rn_color_jitter_state`` block (the others keep their device values): host->device copies on
+    the current stream, ordered with the draws around them.  Not inside a capture: the values would be baked into the graph."""
+    _check_color_block(block)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("color_jitter_state_write inside a stream capture")
+    parts = []
+    if seed is not None:
+        parts.append((0, struct.pack("<Q", int(seed) & (2 ** 64 - 1))))
+    if counter is not None:
+        parts.append((8, struct.pack("<q", int(counter))))
+    if p is not None:
+        parts.append((16, struct.pack("<f", float(p))))
+    if lo is not None:
+        parts.append((20, struct.pack("<4f", *[float(v) for v in lo])))
+    if hi is not None:
+        parts.append((36, struct.pack("<4f", *[float(v) for v in hi])))
+    if enabled_mask is not None:
+        parts.append((52, struct.pack("<i", int(enabled_mask) & 0xF)))
+    for off, raw in parts:
+        block[off:off + len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+
+
+def color_jitter_state_read(block: Tensor) -> Tuple[int, int, float, Tuple[float, ...], Tuple[float, ...], int]:
+    "(seed, counter, p, lo, hi, enabled_mask) of an ``rn_color_jitter_state`` block: one device->host copy (synchronises)."
+    _check_color_block(block)
+    v = struct.unpack("<Qqf4f4fi", bytes(block.cpu().numpy().tobytes()))
+    return v[0], v[1], v[2], tuple(v[3:7]), tuple(v[7:11]), v[11]
+
+
+def color_jitter_draw(block: Tensor, B: int) -> Tensor:
+    """``rn_color_jitter_draw``: coef f32 [B, 8] (``rn_color_coef`` per image: four factors, mean = 0, the order as int32 bits in column
+    5) drawn from the block, then the block's counter advances by one -- one launch on the current stream for any B, no host
+    synchronisation (capturable: each replay draws anew)."""
+    dev = _check_color_block(block)
+    B = int(B)
+    if B <= 0:
+        raise ValueError(f"B must be positive, got {B}")
+    coef = torch.empty((B, COLOR_COEF_FLOATS), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("color_jitter_draw", dev):
+        check(lib.rn_color_jitter_draw(_ptr(block), B, _ptr(coef), _stream(dev)), "rn_color_jitter_draw")
+    return coef
+
+
+def color_mean(images, coef: Tensor, workspace: Optional[Tensor] = None) -> Tensor:
+    """``rn_color_mean``: writes ``coef[b, 4]`` = the mean gray of image b as it is when its contrast's turn comes, for the images whose
+    order holds a contrast (in place; returns ``coef``).  ``images``: CUDA f32 ``[3, h, w]`` tensors, or ``StagedImages``.  No atomics,
+    a fixed order of every sum: two calls give the same bits.  ``workspace``: uint8, >= ``rn_color_mean_workspace_bytes(B)``."""
+    staged = isinstance(images, StagedImages)
+    dev = _need_dev(coef, *((images.arena, images.in_hw) if staged else images))
+    B = images.B if staged else len(images)
+    _check_coef(coef, B, dev)
+    need = int(lib.rn_color_mean_workspace_bytes(B))
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    _need_dev(workspace)
+    with torch.cuda.device(dev), _timed("color_mean", dev):
+        if staged:
+            check(lib.rn_color_mean(None, None, _ptr(images.arena), images.slot, _ptr(images.in_hw), B, _ptr(coef), _ptr(workspace),
+                                    int(workspace.numel() * workspace.element_size()), _stream(dev)), "rn_color_mean")
+        else:
+            imgs = []
+            for im in images:
+                if im.dim() != 3 or im.shape[0] != 3 or im.dtype != torch.float32:
+                    raise ValueError(f"color_mean expects f32 [3, h, w] images, got {tuple(im.shape)} {im.dtype}")
+                imgs.append(im if im.is_contiguous() else im.contiguous())
+            ptrs = (C.c_void_p * B)(*[im.data_ptr() for im in imgs])
+            in_hw = (C.c_int32 * (2 * B))(*[int(v) for im in imgs for v in im.shape[1:]])
+            check(lib.rn_color_mean(ptrs, in_hw, None, 0, None, B, _ptr(coef), _ptr(workspace),
+                                    int(workspace.numel() * workspace.element_size()), _stream(dev)), "rn_color_mean")
+    return coef
 
 
 def gt_flip_scale_many(boxes: Sequence[Tensor], widths: Sequence[float], ratios: Sequence[Tuple[float, float]], flags: Tensor) -> Tensor:
@@ -913,7 +1033,8 @@ def resize_plan_dev(block: Optional[Tensor], in_hw: Tensor, short: Optional[int]
 
 
 def transform_batch_var(staged: StagedImages, out_hw: Tensor, mean: Sequence[float], std: Sequence[float], Hp: int, Wp: int,
-                        out_dtype: torch.dtype = torch.float32, channels_last: bool = False, flags: Optional[Tensor] = None) -> Tensor:
+                        out_dtype: torch.dtype = torch.float32, channels_last: bool = False, flags: Optional[Tensor] = None,
+                        coef: Optional[Tensor] = None) -> Tensor:
     """``transform_batch_dev`` on staged images (``rn_transform_batch_var``): image b from the arena's slot b, its size from
     ``staged.in_hw`` and its output size from ``out_hw`` (int32 [B, 2], ``resize_plan_dev``), all read on the device; a size no slot
     can hold leaves the image all padding.  Bit-identical to ``transform_batch`` called with the same sizes and canvas on the host."""
@@ -923,11 +1044,18 @@ def transform_batch_var(staged: StagedImages, out_hw: Tensor, mean: Sequence[flo
         raise ValueError(f"out_hw must be a contiguous int32 [{B}, 2] tensor, got {tuple(out_hw.shape)} {out_hw.dtype}")
     if flags is not None:
         _check_flags(flags, B, dev)
+    if coef is not None:
+        _check_coef(coef, B, dev)
     if out_dtype not in _DT:
         raise ValueError(f"unsupported output dtype {out_dtype}")
     out = torch.empty((B, 3, Hp, Wp), dtype=out_dtype, device=dev,
                       memory_format=torch.channels_last if channels_last else torch.contiguous_format)
     with torch.cuda.device(dev), _timed("transform_batch", dev):
+        if coef is not None:
+            check(lib.rn_transform_batch_color(None, None, _ptr(staged.arena), staged.slot, _ptr(staged.in_hw), None, _ptr(out_hw), B,
+                                               (C.c_float * 3)(*mean), (C.c_float * 3)(*std), int(Hp), int(Wp), _ptr(out), _DT[out_dtype],
+                                               int(bool(channels_last)), _ptr(flags), _ptr(coef), _stream(dev)), "rn_transform_batch_color")
+            return out
         check(lib.rn_transform_batch_var(_ptr(staged.arena), staged.slot, _ptr(staged.in_hw), _ptr(out_hw), B, (C.c_float * 3)(*mean),
                                          (C.c_float * 3)(*std), int(Hp), int(Wp), _ptr(out), _DT[out_dtype], int(bool(channels_last)),
                                          _ptr(flags), _stream(dev)), "rn_transform_batch_var")

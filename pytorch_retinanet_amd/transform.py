@@ -36,6 +36,14 @@ loss are laid out on the padded canvas).  The PyTorch path draws the same sizes 
 with ``resize`` and pads the batch to the same canvas.  The known cost: the whole canvas is processed whatever was drawn, so small
 draws save no compute.  ``scale_jitter`` is a plain attribute too.
 
+Train-time colour jitter (``color_jitter``: an ``augment.ColorJitter``, None by default): in training mode and when targets are given,
+each image is jittered with probability p -- torchvision's tensor ``ColorJitter`` on the raw fp32 RGB image in [0, 1], before the
+normalisation, the resize and the flip (it is per pixel apart from the contrast's mean, so it commutes with the flip).  On the fused
+paths the factors and the order are drawn on the device (``rn_color_jitter_draw``), the contrast's mean gray is one pair of launches
+over the source images when a contrast is enabled (``rn_color_mean``), and the operations run inside the transform kernel on every
+source pixel it reads (``rn_transform_batch_color``); the rows stay on the device as ``color_jitter.coef``.  The PyTorch path draws the
+same stream from the Python restatement and applies ``augment.apply_color_ops``.  ``color_jitter`` is a plain attribute too.
+
 Staged images (``forward(ops.StagedImages, packed GT, canvas=(Hp, Wp))``: the image capacity mode of ``graph.CapturedTrainStep``):
 the batch lies in a fixed device arena with its sizes next to it (``ops.image_stage``), and nothing this call launches takes an
 image's address or size as an argument -- the resize plan (``rn_resize_plan_dev``: the fixed short side, or the ``scale_jitter``'s
@@ -130,6 +138,7 @@ class GeneralizedRCNNTransform(nn.Module):
         self._stats = {}
         self.hflip = None             # augment.RandomHorizontalFlip: the train-time flip (module docstring)
         self.scale_jitter = None      # augment.RandomShortSide: the short side drawn on the device (module docstring)
+        self.color_jitter = None      # augment.ColorJitter: the colour jitter drawn and applied on the device (module docstring)
 
     # -- pieces ------------------------------------------------------------------------
     def normalize(self, image: Tensor) -> Tensor:
@@ -195,7 +204,15 @@ class GeneralizedRCNNTransform(nn.Module):
         "The installed ``scale_jitter`` when it acts on this call (training mode, targets given), else None."
         return self.scale_jitter if self.scale_jitter is not None and self.training and targets is not None else None
 
-    def _forward_fused_jitter(self, jitter, images: List[Tensor], targets, out_dtype: torch.dtype, channels_last: bool, flags):
+    def _color(self, images, targets) -> Optional[Tensor]:
+        """This batch's ``rn_color_coef`` rows (f32 [B, 8] on the images' device; the jitter's counter advances), or None when no
+        ``color_jitter`` acts on this call.  ``images``: fusable CUDA images or ``ops.StagedImages``."""
+        cj = getattr(self, "color_jitter", None)
+        if cj is None or not self.training or targets is None:
+            return None
+        return cj.next_coef(images)
+
+    def _forward_fused_jitter(self, jitter, images: List[Tensor], targets, out_dtype: torch.dtype, channels_last: bool, flags, coef=None):
         "The fused path with the sizes drawn on the device: nothing about the draw reaches the host, the canvas is the bound's."
         from . import ops
         in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
@@ -210,15 +227,17 @@ class GeneralizedRCNNTransform(nn.Module):
             for t, r in zip(targets, rows):
                 t["boxes"] = r
         hp, wp = self._canvas(bounds)
-        batch = ops.transform_batch_dev(images, out_hw, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags)
+        batch = ops.transform_batch_dev(images, out_hw, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags,
+                                        coef=coef)
         return ImageList(batch, bounds), targets
 
     def _forward_fused(self, images: List[Tensor], targets, out_dtype: torch.dtype, channels_last: bool):
         from . import ops                       # the HIP library is only needed once a CUDA image shows up
         flags = self._flips(images, targets)
+        coef = self._color(images, targets)
         jitter = self._jitter(targets)
         if jitter is not None:
-            return self._forward_fused_jitter(jitter, images, targets, out_dtype, channels_last, flags)
+            return self._forward_fused_jitter(jitter, images, targets, out_dtype, channels_last, flags, coef)
         sizes, ratios, widths = [], [], []
         packed = _is_packed(targets)
         for i, im in enumerate(images):
@@ -240,7 +259,7 @@ class GeneralizedRCNNTransform(nn.Module):
             for t, r in zip(targets, rows):
                 t["boxes"] = r
         hp, wp = self._canvas(sizes)
-        batch = ops.transform_batch(images, sizes, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags)
+        batch = ops.transform_batch(images, sizes, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags, coef=coef)
         return ImageList(batch, sizes), targets
 
     def staged_short_side(self) -> Optional[int]:
@@ -325,6 +344,7 @@ class GeneralizedRCNNTransform(nn.Module):
             raise ValueError(f"packed GT of {targets.B} images for {len(staged.hw)} staged images in an arena of {staged.B}")
         (hp, wp), bounds = self._check_staged_canvas(canvas, staged, self.staged_bounds)
         flags = self.hflip.next_flags(staged.B, staged.device) if self.hflip is not None else None
+        coef = self._color(staged, targets)
         jitter = self.scale_jitter
         if jitter is not None:
             out_hw, ratios = jitter.next_sizes_dev(staged.in_hw, self.max_size)
@@ -333,7 +353,8 @@ class GeneralizedRCNNTransform(nn.Module):
             out_hw, ratios = ops.resize_plan_dev(None, staged.in_hw, self.staged_short_side(), int(self.max_size))
         # (launched whatever the ratios are: the host cannot know them; a ratio of 1 leaves a row bit for bit as it was)
         targets = ops.gt_flip_scale_packed_var(targets, staged.in_hw, ratios, flags)
-        batch = ops.transform_batch_var(staged, out_hw, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags)
+        batch = ops.transform_batch_var(staged, out_hw, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags,
+                                        coef=coef)
         return ImageList(batch, bounds), targets
 
     # -- whole transform -----------------------------------------------------------------
@@ -360,6 +381,11 @@ class GeneralizedRCNNTransform(nn.Module):
         if self._fusable(images):
             return self._forward_fused(images, targets, out_dtype or torch.float32, channels_last)
         flags = self._flips(images, targets)
+        cj = getattr(self, "color_jitter", None)
+        if cj is not None and self.training and targets is not None:
+            # the same draw from the Python restatement, applied with torch ops (augment.apply_color_ops) to the raw image
+            from .augment import apply_color_ops
+            images = [apply_color_ops(im, fac, order) for im, (fac, order) in zip(images, cj.next_draw(len(images)))]
         jitter = self._jitter(targets)
         shorts = bounds = None
         if jitter is not None:
