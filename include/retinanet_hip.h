@@ -968,6 +968,44 @@ int rn_transform_batch_color(const void *const *images, const int32_t *in_hw, co
                              int Wp, void *out, int out_dtype, int channels_last, const uint8_t *flags_or_null, const rn_color_coef *coef,
                              void *stream);
 
+/* ---- train-time augmentation: bbox-safe random crop (augment.BBoxSafeRandomCrop), a second staging pass ------------------
+ * albumentations' BBoxSafeRandomCrop with erosion_rate = 0 in intent -- each margin drawn uniformly between the image edge and the
+ * union of the boxes -- on integer pixels: no box inside the image is ever cut, none is dropped (the GT counts and gt_off stay), and
+ * the result is NOT bit-compatible with albumentations' float rounding.  It works on staged images and packed GT only (rn_image_stage,
+ * rn_gt_stage): the draw writes a rectangle per image next to the cropped sizes, the copy moves each window densely into a second arena,
+ * and everything downstream (rn_resize_plan_dev, rn_color_mean, rn_transform_batch_var / _color, rn_gt_flip_scale_packed_var) runs
+ * unchanged on (arena_out, crop_hw) -- bit-identical to running on the sliced tensor img[:, y0:y0+ch, x0:x0+cw].
+ * rn_bbox_crop_state: a DEVICE block (8-byte aligned) owned by augment.BBoxSafeRandomCrop, written by the host outside any capture.
+ * rn_bbox_crop_draw: one wave per image, no atomics, then a single-wave launch doing counter += 1; any B.  For image b with
+ * (h, w) = in_hw_dev[b] and the rows [gt_off[b], gt_off[b + 1]) (clamped to [0, rows]) of gt_boxes f32[rows][4] = (x1, y1, x2, y2):
+ *   1. u_k = the hash of rn_hflip_draw on (seed ^ salt_k, counter, b); salts: apply 0xC409C409C409C40B, left 0x1EF71EF71EF71EF7,
+ *      top 0x70B070B070B070B1, right 0x4167416741674169, bottom 0xB077B077B077B079.
+ *   2. Identity -- rect = (0, 0, h, w), crop_hw = (h, w), the rows copied bit for bit -- when the image has no rows, u_apply >= p,
+ *      h < 1 or w < 1, or any of min x1, min y1, max x2, max y2 over the rows is not finite (a NaN among the values of an extreme
+ *      makes it NaN).  For h < 1 or w < 1: rect = (0, 0, 0, 0) and crop_hw = (0, 0).
+ *   3. The union in pixels (int() saturates):  ux1 = clamp(int(floorf(min x1)), 0, w - 1),  uy1 likewise with h - 1;
+ *      ux2 = clamp(int(ceilf(max x2)), ux1 + 1, w),  uy2 likewise with uy1 + 1 and h.
+ *   4. The rectangle, fp32 multiplies and truncation:  x0 = min(int(u_left * float(ux1 + 1)), ux1),  y0 likewise from u_top and uy1;
+ *      xe = ux2 + min(int(u_right * float(w - ux2 + 1)), w - ux2),  ye likewise from u_bottom, uy2 and h;  cw = xe - x0,  ch = ye - y0.
+ *   5. The orientation is kept, so a batch stays inside its own canvas class: if h <= w and ch > cw,
+ *      x0 = max(0, min(x0 - (ch - cw) / 2, w - ch)) and cw = ch; if h > w and cw > ch, the same on y.  The rectangle stays inside the
+ *      image and keeps containing the union.
+ *   6. out_boxes[r] = (x1 - float(x0), y1 - float(y0), x2 - float(x0), y2 - float(y0)), one fp32 subtraction each.
+ * rect: DEVICE i32[B][4] = (y0, x0, ch, cw); crop_hw: DEVICE i32[B][2] = (ch, cw); out_boxes: f32[rows][4], out of place (16-byte
+ * aligned like gt_boxes); rows outside [gt_off[0], gt_off[B]) are not written.  Captured into a hipGraph, every replay draws anew.
+ * rn_image_crop_stage: image b's window [3][ch][cw] at (y0, x0) = rect[b] of the image [3][h][w] at arena + b * slot goes densely to
+ * the start of arena_out + b * slot_out.  A fixed grid per image; no size is a launch argument.  Device data cannot move a thread
+ * outside the operands: the rectangle is clamped to in_hw_dev again, and an image with h < 1, w < 1, 3 h w > slot, ch < 1, cw < 1 or
+ * 3 ch cw > slot_out is skipped (its destination slot is left as it was).  Floats past 3 ch cw of a destination slot are left alone.
+ * 16-byte stores where the destination slot is 16-byte aligned; the source rows are read with 4-byte loads (they start at x0).
+ * RN_EINVAL: a null pointer, arena == arena_out, B <= 0 or > 65535, a slot < 3 or >= 2^31 floats. */
+typedef struct rn_bbox_crop_state { uint64_t seed; int64_t counter; float p; int32_t reserved; } rn_bbox_crop_state;
+int rn_bbox_crop_draw(rn_bbox_crop_state *state, const float *gt_boxes, const int32_t *gt_off, const int32_t *in_hw_dev, int B,
+                      int32_t *rect /* DEVICE i32[B][4] = (y0, x0, ch, cw) */, int32_t *crop_hw /* DEVICE i32[B][2] = (ch, cw) */,
+                      float *out_boxes /* [rows][4], out of place */, int64_t rows, void *stream);
+int rn_image_crop_stage(const float *arena, int64_t slot, const int32_t *in_hw_dev, const int32_t *rect, int B,
+                        float *arena_out, int64_t slot_out, void *stream);
+
 /* ---- K6 nms (op boundary) ---------------------------------------------------
  * Replaces torchvision.ops.nms as called at retinanet/models.py:210, batched over
  * S independent segments: seg_off i32[S+1]; boxes f32[N][4], scores f32[N].

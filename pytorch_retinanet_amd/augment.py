@@ -26,6 +26,13 @@ torchvision 0.8's TENSOR algorithm (``transforms.functional_tensor``; ``apply_co
 either maps onto this class.  Per image one launch draws ``rn_color_coef`` (four factors and the order: ``rn_color_jitter_draw``), one
 pair of launches computes the contrast's mean gray when a contrast is enabled (``rn_color_mean``), and the operations run inside the
 transform kernel on every source pixel it reads (``rn_transform_batch_color``) -- all inside the captured step, each replay a new draw.
+
+``BBoxSafeRandomCrop`` is the geometric augmentation detection users add next (``GeneralizedRCNNTransform.crop``): albumentations'
+``BBoxSafeRandomCrop`` with ``erosion_rate = 0`` in intent, on integer pixels -- not bit-compatible with albumentations' float rounding.
+It drops no box, so the GT counts and offsets of a captured step do not change.  On staged images with packed GT it is a second
+staging pass: ``rn_bbox_crop_draw`` draws a rectangle per image around the union of its boxes and shifts the boxes,
+``rn_image_crop_stage`` copies each window densely into a second arena, and everything downstream runs unchanged on that arena --
+bit-identical to running on the sliced tensors.  Other inputs draw the same rectangles on the host (one synchronisation on CUDA).
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -34,7 +41,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-__all__ = ["RandomHorizontalFlip", "RandomShortSide", "ColorJitter", "hflip_u", "apply_color_ops"]
+__all__ = ["RandomHorizontalFlip", "RandomShortSide", "ColorJitter", "BBoxSafeRandomCrop", "hflip_u", "apply_color_ops"]
 
 _M64 = 2 ** 64 - 1
 
@@ -588,6 +595,202 @@ class ColorJitter:
         self.reseed(int(state["seed"]), int(state["counter"]))
 
 
+# ---- bbox-safe random crop ------------------------------------------------------------------------------------------------
+CROP_SALT_APPLY = 0xC409C409C409C40B                                 # include/retinanet_hip.h: rn_bbox_crop_draw, step 1
+CROP_SALT_LEFT, CROP_SALT_TOP, CROP_SALT_RIGHT, CROP_SALT_BOTTOM = 0x1EF71EF71EF71EF7, 0x70B070B070B070B1, 0x4167416741674169, 0xB077B077B077B079
+_I32_MIN, _I32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def _sat_int(f) -> int:
+    "int(f) for a finite fp32 value, saturating at the int32 range (the kernel's conversion)."
+    f = float(f)
+    return _I32_MIN if f <= -2147483648.0 else (_I32_MAX if f >= 2147483648.0 else int(f))
+
+
+def _clamp(v: int, lo: int, hi: int) -> int:
+    return lo if v < lo else (hi if v > hi else v)
+
+
+def _crop_axis(u_lo: float, u_hi: float, u1: int, u2: int, n: int) -> Tuple[int, int]:
+    "(start, end) of the crop on one axis of length n around the union [u1, u2): fp32 multiplies, truncation (step 4)."
+    f32 = np.float32
+    a, c = int(f32(u_lo) * f32(u1 + 1)), int(f32(u_hi) * f32(n - u2 + 1))
+    return min(a, u1), u2 + min(c, n - u2)
+
+
+class BBoxSafeRandomCrop:
+    """With probability ``p`` crop each training image to a random window that contains all of its boxes, and shift the boxes with it:
+    albumentations' ``BBoxSafeRandomCrop`` with ``erosion_rate = 0`` in intent -- each margin is drawn uniformly between the image edge
+    and the union of the boxes -- on integer pixels.  No box that lies inside the image is ever cut and none is dropped, so the GT
+    counts do not change.  It is NOT bit-compatible with albumentations' float rounding; ``draw_rects`` is the definition (the numbered
+    rule of ``rn_bbox_crop_draw`` in ``include/retinanet_hip.h``).  The crop keeps the orientation (a landscape image stays landscape:
+    the short axis of the window is widened if need be), so a batch stays inside its canvas class.  An image without boxes, with a
+    non-finite box or of size 0 is left alone.
+
+    Install it as ``net.transform.crop``; it acts only in training mode and only when targets are given, before the flip, the colour
+    jitter and the resize.  On staged images with packed GT (``graph.CapturedTrainStep(image_capacity=..., gt_capacity=...)``) the
+    rectangles are drawn on the device from the boxes (``rn_bbox_crop_draw``) and each window is copied into a second arena
+    (``rn_image_crop_stage``), inside the captured step, each replay a new draw; ``CapturedTrainStep`` needs ``image_capacity`` for it.
+    Every other input (CPU tensors, CUDA lists) takes the same stream of rectangles from ``draw_rects`` on the HOST: the boxes and the
+    counter are read back, which on CUDA is one synchronisation per step.  Not an ``nn.Module``: it adds no key to the model's state
+    dict.  ``seed``: the stream of draws (``SimpleTrainer`` adds the rank under ``torch.distributed``)."""
+
+    def __init__(self, p: float = 1.0, seed: int = 0):
+        self.base_seed = int(seed) & _M64
+        self._p, self._seed, self._counter = RandomHorizontalFlip._check_p(p), self.base_seed, 0
+        self._block: Optional[Tensor] = None          # rn_bbox_crop_state on the device of the first CUDA batch (kept for good)
+        self.rect: Optional[Tensor] = None            # the last device batch's rectangles (int32 [B, 4] = (y0, x0, ch, cw))
+        self.rects: Optional[List[Tuple[int, int, int, int]]] = None      # the last host-drawn batch's rectangles
+
+    def __repr__(self) -> str:
+        return f"BBoxSafeRandomCrop(p={self._p}, seed={self._seed})"
+
+    # -- the draws ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def draw_rects(seed: int, counter: int, in_hw: Sequence[Tuple[int, int]], boxes_per_image, p: float) -> List[Tuple[int, int, int, int]]:
+        """Pure-Python restatement of ``rn_bbox_crop_draw``, exactly: per image the rectangle (y0, x0, ch, cw).  ``boxes_per_image[b]``:
+        image b's boxes, anything ``numpy.asarray`` turns into fp32 [T, 4] = (x1, y1, x2, y2) (a CPU tensor, an array, a list; None or
+        empty for no boxes)."""
+        seed, counter, f32 = int(seed) & _M64, int(counter), np.float32
+        p32 = f32(p)
+        out = []
+        for b, (h, w) in enumerate(in_hw):
+            h, w = int(h), int(w)
+            if h < 1 or w < 1:
+                out.append((0, 0, 0, 0))
+                continue
+            bx = boxes_per_image[b]
+            bx = np.zeros((0, 4), f32) if bx is None else np.asarray(bx, dtype=f32).reshape(-1, 4)
+            identity = (0, 0, h, w)
+            if bx.shape[0] == 0 or not f32(hflip_u(seed ^ CROP_SALT_APPLY, counter, b)) < p32:
+                out.append(identity)
+                continue
+            # (numpy's min / max propagate a NaN, as the kernel's flag does)
+            ext = (bx[:, 0].min(), bx[:, 1].min(), bx[:, 2].max(), bx[:, 3].max())
+            if not all(np.isfinite(v) for v in ext):
+                out.append(identity)
+                continue
+            ux1, uy1 = _clamp(_sat_int(np.floor(ext[0])), 0, w - 1), _clamp(_sat_int(np.floor(ext[1])), 0, h - 1)
+            ux2, uy2 = _clamp(_sat_int(np.ceil(ext[2])), ux1 + 1, w), _clamp(_sat_int(np.ceil(ext[3])), uy1 + 1, h)
+            x0, xe = _crop_axis(hflip_u(seed ^ CROP_SALT_LEFT, counter, b), hflip_u(seed ^ CROP_SALT_RIGHT, counter, b), ux1, ux2, w)
+            y0, ye = _crop_axis(hflip_u(seed ^ CROP_SALT_TOP, counter, b), hflip_u(seed ^ CROP_SALT_BOTTOM, counter, b), uy1, uy2, h)
+            cw, ch = xe - x0, ye - y0
+            if h <= w and ch > cw:
+                x0, cw = max(0, min(x0 - (ch - cw) // 2, w - ch)), ch
+            elif h > w and cw > ch:
+                y0, ch = max(0, min(y0 - (cw - ch) // 2, h - cw)), cw
+            out.append((y0, x0, ch, cw))
+        return out
+
+    def draw(self, counter: int, in_hw: Sequence[Tuple[int, int]], boxes_per_image) -> List[Tuple[int, int, int, int]]:
+        "The rectangles this object draws at ``counter`` for images of sizes ``in_hw`` with these boxes (no state change)."
+        return self.draw_rects(self._seed, counter, in_hw, boxes_per_image, self._p)
+
+    @staticmethod
+    def bound(h: int, w: int, short: int, max_size: int) -> Tuple[int, int]:
+        """An upper bound of the size after the resize of every crop of an h x w image: the crop keeps the orientation, so its short
+        side becomes at most ``short`` -- the largest short side that can be drawn -- and its long side at most ``max_size``."""
+        return (int(short), int(max_size)) if int(h) <= int(w) else (int(max_size), int(short))
+
+    def next_rects(self, in_hw: Sequence[Tuple[int, int]], boxes_per_image) -> List[Tuple[int, int, int, int]]:
+        """The next batch's rectangles on the HOST, and the counter advanced by one: what CPU tensors and CUDA lists use.  The boxes
+        are read on the host (CUDA tensors are copied back: a synchronisation) and, with a device block, so is the counter; not
+        inside a capture."""
+        n = self.counter
+        boxes = [None if b is None else (b.detach().cpu().numpy() if isinstance(b, Tensor) else b) for b in boxes_per_image]
+        self.rects = self.draw(n, in_hw, boxes)
+        self._counter = n + 1
+        if self._block is not None:
+            from . import ops
+            ops.bbox_crop_state_write(self._block, counter=n + 1)
+        return self.rects
+
+    def device_block(self, device: torch.device) -> Tensor:
+        """The ``rn_bbox_crop_state`` block on ``device`` that ``ops.bbox_crop_staged`` draws from, created at the first call (which
+        must not be inside a capture) and kept for good: a captured step holds its address."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("BBoxSafeRandomCrop: the device draw runs on the GPU; CPU batches use next_rects()")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._block is None:
+            from . import ops
+            self._block = ops.bbox_crop_state(device, self._seed, self._counter, self._p)
+        elif self._block.device != device:
+            raise RuntimeError(f"BBoxSafeRandomCrop: its state lives on {self._block.device}, not {device}; use one object per device")
+        return self._block
+
+    # -- settings and state ---------------------------------------------------------------------------------------------
+    @property
+    def p(self) -> float:
+        return self._p
+
+    @p.setter
+    def p(self, value: float) -> None:
+        "A new probability: written into the device block (no re-capture needed; not inside a capture)."
+        self._p = RandomHorizontalFlip._check_p(value)
+        if self._block is not None:
+            from . import ops
+            ops.bbox_crop_state_write(self._block, p=self._p)
+
+    @property
+    def seed(self) -> int:
+        return self._seed
+
+    def reseed(self, seed: int, counter: int = 0) -> None:
+        "Start a new stream of draws (seed, counter); not inside a capture."
+        self._seed, self._counter = int(seed) & _M64, int(counter)
+        if self._block is not None:
+            from . import ops
+            ops.bbox_crop_state_write(self._block, seed=self._seed, counter=self._counter)
+
+    def set_rank(self, rank: int) -> None:
+        "One stream per data-parallel rank: seed = ``base_seed`` (the constructor's) + rank, the counter kept."
+        self.reseed((self.base_seed + int(rank)) & _M64, self.counter)
+
+    @property
+    def counter(self) -> int:
+        "Batches drawn so far (with the device block: one read-back, i.e. a synchronisation)."
+        if self._block is not None:
+            from . import ops
+            return int(ops.bbox_crop_state_read(self._block)[1])
+        return self._counter
+
+    def state_dict(self) -> Dict[str, object]:
+        return {"seed": self._seed, "counter": self.counter, "p": self._p}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.p = state["p"]
+        self.reseed(int(state["seed"]), int(state["counter"]))
+
+
+_BBOX_CROP_NAMES = ("albumentations.BBoxSafeRandomCrop", "BBoxSafeRandomCrop")
+
+
+def bbox_crop_from_transforms(entries, seed: int = 0, log=None) -> Optional[BBoxSafeRandomCrop]:
+    """The bbox-safe random crop an hparams ``transforms`` list asks for, or None.  ``albumentations.BBoxSafeRandomCrop`` (``p``
+    defaults to 1.0, albumentations' own default; ``always_apply: true`` means p = 1) maps onto ``BBoxSafeRandomCrop``, which works on
+    integer pixels and is not bit-compatible with albumentations.  A non-zero ``erosion_rate`` is warned about and treated as 0.
+    ``RandomSizedBBoxSafeCrop`` and every other crop are not this one: ``from_transforms`` skips them with its warning."""
+    import logging
+    log = log or logging.getLogger(__name__)
+    found = None
+    for e in entries or []:
+        name = str(e.get("class_name", "")) if isinstance(e, dict) else str(e)
+        params = dict(e.get("params") or {}) if isinstance(e, dict) else {}
+        if name not in _BBOX_CROP_NAMES:
+            continue
+        if found is not None:
+            log.warning("transforms: a second bbox-safe crop (%s) is skipped", name)
+            continue
+        if float(params.get("erosion_rate", 0.0) or 0.0) != 0.0:
+            log.warning("transforms: %s erosion_rate=%s is not implemented and is treated as 0 (the crop never cuts into the union of "
+                        "the boxes)", name, params.get("erosion_rate"))
+        p = 1.0 if params.get("always_apply") else float(params.get("p", 1.0))
+        found = BBoxSafeRandomCrop(p=p, seed=seed)
+    return found
+
+
 _COLOR_JITTER_NAMES = ("albumentations.ColorJitter", "torchvision.transforms.ColorJitter", "ColorJitter")
 
 
@@ -630,11 +833,11 @@ def from_transforms(entries, seed: int = 0, log=None) -> Optional[RandomHorizont
             p = 1.0 if params.get("always_apply") else float(params.get("p", 0.5))
         elif short == "RandomHorizontalFlip":
             p = float(params.get("prob", params.get("p", 0.5)))
-        elif name in _COLOR_JITTER_NAMES:              # color_jitter_from_transforms maps these
+        elif name in _COLOR_JITTER_NAMES or name in _BBOX_CROP_NAMES:      # color_jitter_ / bbox_crop_from_transforms map these
             continue
         else:
-            log.warning("transforms: %s is not supported (albumentations is not available; only the horizontal flip and ColorJitter are "
-                        "implemented, on the GPU): skipped", name)
+            log.warning("transforms: %s is not supported (albumentations is not available; only the horizontal flip, ColorJitter and "
+                        "BBoxSafeRandomCrop are implemented, on the GPU): skipped", name)
             continue
         if found is not None:
             log.warning("transforms: a second horizontal flip (%s) is skipped", name)

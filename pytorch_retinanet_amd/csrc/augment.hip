@@ -64,6 +64,19 @@
 // pre = the operations before the contrast, by the helper the transform kernel calls.  No atomics: 32 blocks per image, thread t of
 // block k adds the pixels k * 256 + t + j * 8192 in order of j, the block adds its 256 sums as a fixed tree, and a second single-wave
 // launch adds an image's 32 partials in index order -- two calls give the same bits.
+//
+// The bbox-safe random crop (augment.BBoxSafeRandomCrop: albumentations' BBoxSafeRandomCrop with erosion_rate = 0 in intent, on integer
+// pixels) is a second staging pass over staged images and packed GT (the image capacity mode), so nothing downstream changes:
+//
+//   rn_bbox_crop_draw     rect[b] = (y0, x0, ch, cw), crop_hw[b] = (ch, cw), out_boxes = the boxes shifted by (x0, y0); then counter += 1
+//   rn_image_crop_stage   image b's window [3][ch][cw] of arena slot b, dense, to the start of slot b of a second arena
+//
+// The draw is one wave per image: the lanes walk the image's rows, the union of the boxes is a wave reduction (no atomics), every lane
+// then computes the same rectangle (the numbered rule in include/retinanet_hip.h; augment.BBoxSafeRandomCrop.draw_rects restates it) and
+// the lanes write the shifted rows.  Every wave reads the counter, so it is advanced by a single-wave launch of its own behind the
+// draw.  The copy is a bandwidth kernel with a fixed grid (CS_BLOCKS blocks per image): a thread gathers four consecutive floats of the
+// dense destination -- the source rows start at x0 and are only 4-byte aligned, so they are read as four 4-byte loads, which the lanes
+// of a wave still coalesce -- and writes them as one 16-byte store when the destination slot is 16-byte aligned.
 #include "rn_color.hpp"
 #include "rn_common.hpp"
 
@@ -275,7 +288,201 @@ __global__ __launch_bounds__(HF_BLOCK) void color_mean_finish_kernel(const Color
     a.coef[b].mean = (float)(sum / (double)((int64_t)ih * iw));
 }
 
+// ---- bbox-safe random crop: the draw and the copy (augment.BBoxSafeRandomCrop) ---------------------------------------------------------
+constexpr uint64_t BC_SALT_APPLY = 0xC409C409C409C40Bull, BC_SALT_LEFT = 0x1EF71EF71EF71EF7ull, BC_SALT_TOP = 0x70B070B070B070B1ull,
+                   BC_SALT_RIGHT = 0x4167416741674169ull, BC_SALT_BOTTOM = 0xB077B077B077B079ull;
+
+// int(f) for a finite f, saturating (a box far outside the image must not leave the conversion undefined)
+__device__ __forceinline__ int sat_int(const float f)
+{
+    return f <= -2147483648.0f ? INT32_MIN : (f >= 2147483648.0f ? INT32_MAX : (int)f);
+}
+
+__device__ __forceinline__ int clamp_int(const int v, const int lo, const int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the start and the end of the crop on one axis of length n: the margins before the union [u1, u2) and behind it, each drawn uniformly
+__device__ __forceinline__ void crop_axis(const float u_lo, const float u_hi, const int u1, const int u2, const int n, int &start, int &end)
+{
+    const int a = (int)(u_lo * (float)(u1 + 1)), c = (int)(u_hi * (float)(n - u2 + 1));
+    start = a < u1 ? a : u1;
+    end = u2 + (c < n - u2 ? c : n - u2);
+}
+
+// one wave per image (blockIdx.x); the state block is only read here
+__global__ __launch_bounds__(HF_BLOCK) void bbox_crop_draw_kernel(const rn_bbox_crop_state *__restrict__ st, const rn::f32x4 *__restrict__ in,
+                                                                 const int32_t *__restrict__ gt_off, const int32_t *__restrict__ in_hw,
+                                                                 int32_t *__restrict__ rect, int32_t *__restrict__ crop_hw,
+                                                                 rn::f32x4 *__restrict__ out, const int32_t rows)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const uint64_t seed = st->seed;
+    const int64_t counter = st->counter;
+    const float p = st->p;
+    const int h = in_hw[2 * b], w = in_hw[2 * b + 1];
+    int32_t lo = gt_off[b], hi = gt_off[b + 1];
+    lo = lo < 0 ? 0 : (lo > rows ? rows : lo);                                  // (device data: the rows stay inside the buffers)
+    hi = hi < lo ? lo : (hi > rows ? rows : hi);
+    // the union of the boxes: min x1, min y1, max x2, max y2; a NaN anywhere among them makes its extreme NaN
+    float mx1 = INFINITY, my1 = INFINITY, mx2 = -INFINITY, my2 = -INFINITY;
+    int nan = 0;
+    for (int32_t r = lo + lane; r < hi; r += HF_BLOCK) {
+        const rn::f32x4 v = in[r];
+        nan |= (v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w);
+        mx1 = fminf(mx1, v.x);
+        my1 = fminf(my1, v.y);
+        mx2 = fmaxf(mx2, v.z);
+        my2 = fmaxf(my2, v.w);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mx1 = fminf(mx1, __shfl_xor(mx1, o, RN_WAVE));
+        my1 = fminf(my1, __shfl_xor(my1, o, RN_WAVE));
+        mx2 = fmaxf(mx2, __shfl_xor(mx2, o, RN_WAVE));
+        my2 = fmaxf(my2, __shfl_xor(my2, o, RN_WAVE));
+        nan |= __shfl_xor(nan, o, RN_WAVE);
+    }
+    const bool empty = h < 1 || w < 1;
+    const bool finite = !nan && isfinite(mx1) && isfinite(my1) && isfinite(mx2) && isfinite(my2);
+    const bool crop = hi > lo && hflip_u(seed ^ BC_SALT_APPLY, counter, b) < p && !empty && finite;
+    int y0 = 0, x0 = 0, ch = empty ? 0 : h, cw = empty ? 0 : w;
+    if (crop) {
+        const int ux1 = clamp_int(sat_int(floorf(mx1)), 0, w - 1), uy1 = clamp_int(sat_int(floorf(my1)), 0, h - 1);
+        const int ux2 = clamp_int(sat_int(ceilf(mx2)), ux1 + 1, w), uy2 = clamp_int(sat_int(ceilf(my2)), uy1 + 1, h);
+        int xe, ye;
+        crop_axis(hflip_u(seed ^ BC_SALT_LEFT, counter, b), hflip_u(seed ^ BC_SALT_RIGHT, counter, b), ux1, ux2, w, x0, xe);
+        crop_axis(hflip_u(seed ^ BC_SALT_TOP, counter, b), hflip_u(seed ^ BC_SALT_BOTTOM, counter, b), uy1, uy2, h, y0, ye);
+        cw = xe - x0;
+        ch = ye - y0;
+        // the orientation is kept: the short axis of the crop is widened around its middle, inside the image
+        if (h <= w && ch > cw) {
+            const int s = x0 - (ch - cw) / 2, m = w - ch;
+            x0 = s < m ? s : m;
+            x0 = x0 > 0 ? x0 : 0;
+            cw = ch;
+        } else if (h > w && cw > ch) {
+            const int s = y0 - (cw - ch) / 2, m = h - cw;
+            y0 = s < m ? s : m;
+            y0 = y0 > 0 ? y0 : 0;
+            ch = cw;
+        }
+    }
+    if (lane == 0) {
+        rect[4 * b] = y0;
+        rect[4 * b + 1] = x0;
+        rect[4 * b + 2] = ch;
+        rect[4 * b + 3] = cw;
+        crop_hw[2 * b] = ch;
+        crop_hw[2 * b + 1] = cw;
+    }
+    const float fx = (float)x0, fy = (float)y0;
+    for (int32_t r = lo + lane; r < hi; r += HF_BLOCK) {
+        rn::f32x4 v = in[r];
+        if (crop) {                                                             // (else copied bit for bit)
+            v.x -= fx;
+            v.y -= fy;
+            v.z -= fx;
+            v.w -= fy;
+        }
+        out[r] = v;
+    }
+}
+
+// (one wave: every lane reads the counter, in program order before lane 0's store; stream order puts it behind every wave of the draw)
+__global__ __launch_bounds__(HF_BLOCK) void bbox_crop_advance_kernel(rn_bbox_crop_state *st)
+{
+    const int64_t counter = st->counter;
+    if (threadIdx.x == 0) st->counter = counter + 1;
+}
+
+constexpr int CS_BLOCKS = 256;      // blocks per image: fixed, so neither the grid nor an argument depends on a size
+constexpr int CS_BLOCK = 256;
+
+// source index of destination element e of a [3][ch][cw] window at (y0, x0) of a [3][h][w] image (all < 2^31: the host checked the slots)
+struct CropGeom { uint32_t y0, x0, ch, cw, w, plane_s, plane_d; };
+
+__device__ __forceinline__ void crop_split(const CropGeom &g, const uint32_t e, uint32_t &c, uint32_t &y, uint32_t &x)
+{
+    c = e / g.plane_d;
+    const uint32_t r = e - c * g.plane_d;
+    y = r / g.cw;
+    x = r - y * g.cw;
+}
+
+__global__ __launch_bounds__(CS_BLOCK) void image_crop_stage_kernel(const float *__restrict__ arena, const int64_t slot,
+                                                                   const int32_t *__restrict__ in_hw, const int32_t *__restrict__ rect,
+                                                                   float *__restrict__ arena_out, const int64_t slot_out)
+{
+    const int b = blockIdx.y;
+    const int h = in_hw[2 * b], w = in_hw[2 * b + 1];
+    if (h < 1 || w < 1 || (int64_t)h * w > slot / 3) return;                    // (device data: an image no slot can hold)
+    // the rectangle re-clamped to the image: whatever rect holds, no thread leaves the source slot
+    const int y0 = clamp_int(rect[4 * b], 0, h - 1), x0 = clamp_int(rect[4 * b + 1], 0, w - 1);
+    int ch = rect[4 * b + 2], cw = rect[4 * b + 3];
+    ch = ch < h - y0 ? ch : h - y0;
+    cw = cw < w - x0 ? cw : w - x0;
+    if (ch < 1 || cw < 1 || (int64_t)ch * cw > slot_out / 3) return;            // (nor the destination slot)
+    const float *__restrict__ s = arena + (int64_t)b * slot;
+    float *__restrict__ d = arena_out + (int64_t)b * slot_out;
+    CropGeom g;
+    g.y0 = (uint32_t)y0; g.x0 = (uint32_t)x0; g.ch = (uint32_t)ch; g.cw = (uint32_t)cw; g.w = (uint32_t)w;
+    g.plane_s = (uint32_t)h * (uint32_t)w;
+    g.plane_d = (uint32_t)ch * (uint32_t)cw;
+    const uint32_t n = 3u * g.plane_d;                                          // <= slot_out < 2^31
+    const uint32_t tid = blockIdx.x * CS_BLOCK + threadIdx.x, step = CS_BLOCKS * CS_BLOCK;
+    // four consecutive destination floats per thread as ONE 16-byte store where the slot's address allows; the source is read float by
+    // float (its rows start at x0: 4-byte aligned only), the lanes of a wave reading neighbouring addresses
+    const uint32_t n4 = (((uintptr_t)d) & 15) == 0 ? n >> 2 : 0;
+    for (uint32_t v = tid; v < n4; v += step) {
+        uint32_t c, y, x;
+        crop_split(g, 4u * v, c, y, x);
+        float f[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            f[j] = s[c * g.plane_s + (g.y0 + y) * g.w + g.x0 + x];
+            if (++x == g.cw) {
+                x = 0;
+                if (++y == g.ch) { y = 0; ++c; }
+            }
+        }
+        rn::f32x4 o;
+        o.x = f[0]; o.y = f[1]; o.z = f[2]; o.w = f[3];
+        ((rn::f32x4 *)d)[v] = o;
+    }
+    for (uint32_t e = 4u * n4 + tid; e < n; e += step) {
+        uint32_t c, y, x;
+        crop_split(g, e, c, y, x);
+        d[e] = s[c * g.plane_s + (g.y0 + y) * g.w + g.x0 + x];
+    }
+}
+
 }  // namespace
+
+RN_API int rn_bbox_crop_draw(rn_bbox_crop_state *state, const float *gt_boxes, const int32_t *gt_off, const int32_t *in_hw_dev, int B,
+                             int32_t *rect, int32_t *crop_hw, float *out_boxes, int64_t rows, void *stream)
+{
+    if (!state || !gt_off || !in_hw_dev || !rect || !crop_hw || B <= 0 || rows < 0 || rows > INT32_MAX) return RN_EINVAL;
+    if (rows > 0 && (!gt_boxes || !out_boxes || gt_boxes == out_boxes)) return RN_EINVAL;
+    if (!rn::aligned(state, 8) || !rn::aligned(gt_off, 4) || !rn::aligned(in_hw_dev, 4) || !rn::aligned(rect, 4) || !rn::aligned(crop_hw, 4) ||
+        !rn::aligned(gt_boxes, 16) || !rn::aligned(out_boxes, 16))
+        return RN_EALIGN;
+    hipLaunchKernelGGL(bbox_crop_draw_kernel, dim3((unsigned)B), dim3(HF_BLOCK), 0, (hipStream_t)stream, state, (const rn::f32x4 *)gt_boxes,
+                       gt_off, in_hw_dev, rect, crop_hw, (rn::f32x4 *)out_boxes, (int32_t)rows);
+    hipLaunchKernelGGL(bbox_crop_advance_kernel, dim3(1), dim3(HF_BLOCK), 0, (hipStream_t)stream, state);
+    RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
+RN_API int rn_image_crop_stage(const float *arena, int64_t slot, const int32_t *in_hw_dev, const int32_t *rect, int B, float *arena_out,
+                               int64_t slot_out, void *stream)
+{
+    if (!arena || !in_hw_dev || !rect || !arena_out || arena == arena_out || B <= 0 || B > 65535) return RN_EINVAL;
+    if (slot < 3 || slot_out < 3 || slot > INT32_MAX || slot_out > INT32_MAX) return RN_EINVAL;      // (the kernel indexes a slot with 32 bits)
+    if (!rn::aligned(arena, 4) || !rn::aligned(arena_out, 4) || !rn::aligned(in_hw_dev, 4) || !rn::aligned(rect, 4)) return RN_EALIGN;
+    hipLaunchKernelGGL(image_crop_stage_kernel, dim3(CS_BLOCKS, (unsigned)B), dim3(CS_BLOCK), 0, (hipStream_t)stream, arena, slot, in_hw_dev,
+                       rect, arena_out, slot_out);
+    RN_LAUNCH_CHECK();
+    return RN_OK;
+}
 
 RN_API int rn_color_jitter_draw(rn_color_jitter_state *state, int B, rn_color_coef *coef, void *stream)
 {

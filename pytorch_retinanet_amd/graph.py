@@ -46,6 +46,10 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     graph replays while the scales vary (the host-side draw from a ``min_size`` tuple makes nearly every batch a new signature).
     The colour jitter (``net.transform.color_jitter``, ``augment.ColorJitter``) is keyed by the installed object as well: factors and
     order are drawn inside the step from its device block, so its ranges and p may change between replays.
+    The bbox-safe random crop (``net.transform.crop``, ``augment.BBoxSafeRandomCrop``) is keyed by the installed object too, and needs
+    the image capacity mode (a ``ValueError`` says so): the rectangles are drawn inside the step from the staged GT and the windows
+    copied into a second arena, so one graph replays while the crops vary and p may change between replays.  A batch no class holds
+    runs eagerly with the crop drawn on the host.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -537,7 +541,12 @@ class CapturedTrainStep:
         # the colour jitter (transform.color_jitter): drawn inside the step from the object's device block and applied by the transform
         # kernel -- the object once more: new ranges or a new p replay the same graph.  Without one nothing is added.
         color = getattr(getattr(self.net, "transform", None), "color_jitter", None)
-        return key if color is None else key + (("color_jitter", color),)
+        if color is not None:
+            key = key + (("color_jitter", color),)
+        # the bbox-safe random crop (transform.crop): the rectangles are drawn inside the step from the object's device block and the
+        # staged GT, and the canvas class follows from the image shapes (``crop.bound``) -- the object again.  Without one nothing is added.
+        crop = getattr(getattr(self.net, "transform", None), "crop", None)
+        return key if crop is None else key + (("crop", crop),)
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."
@@ -644,6 +653,14 @@ class CapturedTrainStep:
             return self._step(images, targets, final)
         cap = self._capacity_of(targets)
         icls = self._image_class_of(images, targets, cap)          # (once per step: the key, the arena and the transform's bounds)
+        if getattr(getattr(self.net, "transform", None), "crop", None) is not None:
+            if self.image_capacity is None:
+                raise ValueError("a bbox-safe random crop (net.transform.crop) changes every image's size from step to step: "
+                                 "CapturedTrainStep needs image_capacity= (and gt_capacity=) for it -- the staged path draws the crop on "
+                                 "the device; without them call the net directly (the crop is then drawn on the host)")
+            if icls is None:
+                # a batch no class holds: the crop is drawn on the host there (a synchronisation), which no capture can contain
+                return self._step(images, targets, final)
         key = self._signature(images, targets, cap, icls)
         dev = images[0].device
         sig = self._entries.get(key)

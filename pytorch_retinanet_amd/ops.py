@@ -1078,6 +1078,68 @@ def gt_flip_scale_packed_var(gt: PackedGT, in_hw: Tensor, ratios: Tensor, flags:
     return gt.with_boxes(out)
 
 
+# ---- train-time bbox-safe random crop (augment.BBoxSafeRandomCrop): a second staging pass ------------------------------------
+# include/retinanet_hip.h: rn_bbox_crop_state = seed u64, counter i64, p f32, reserved i32 -- the layout of rn_hflip_state, so the
+# block is made, written and read by hflip_state / hflip_state_write / hflip_state_read
+BBOX_CROP_STATE_BYTES = HFLIP_STATE_BYTES
+bbox_crop_state, bbox_crop_state_write, bbox_crop_state_read = hflip_state, hflip_state_write, hflip_state_read
+
+
+def bbox_crop_draw(block: Tensor, in_hw: Tensor, gt: PackedGT) -> Tuple[Tensor, Tensor, Tensor]:
+    """``rn_bbox_crop_draw``: per image the crop rectangle drawn from the block's seed / counter / p around the union of its boxes ->
+    (rect int32 [B, 4] = (y0, x0, ch, cw), crop_hw int32 [B, 2] = (ch, cw), the boxes shifted by (x0, y0) in a fresh f32 [rows, 4]
+    buffer; rows outside the images' ranges unwritten), then the block's counter advances by one.  ``in_hw``: int32 [B, 2] on the
+    device (``StagedImages.in_hw``).  One wave per image plus the counter's single-wave launch, on the current stream, no host
+    synchronisation (capturable: each replay draws anew)."""
+    dev = _need_dev(block, in_hw, gt.gt_boxes, gt.gt_off)
+    if block.dtype != torch.uint8 or block.numel() != BBOX_CROP_STATE_BYTES or block.data_ptr() % 8:
+        raise ValueError("block must be an rn_bbox_crop_state made by bbox_crop_state()")
+    if in_hw.dtype != torch.int32 or tuple(in_hw.shape) != (gt.B, 2) or not in_hw.is_contiguous():
+        raise ValueError(f"in_hw must be a contiguous int32 [{gt.B}, 2] tensor, got {tuple(in_hw.shape)} {in_hw.dtype}")
+    if gt.gt_boxes.dtype != torch.float32 or not gt.gt_boxes.is_contiguous() or gt.gt_boxes.data_ptr() % 16:
+        raise ValueError("packed GT boxes must be a contiguous, 16-byte aligned f32 [rows, 4] tensor")
+    rect = torch.empty((gt.B, 4), dtype=torch.int32, device=dev)
+    crop_hw = torch.empty((gt.B, 2), dtype=torch.int32, device=dev)
+    out = torch.empty_like(gt.gt_boxes)
+    with torch.cuda.device(dev), _timed("bbox_crop_draw", dev):
+        check(lib.rn_bbox_crop_draw(_ptr(block), _ptr(gt.gt_boxes), _ptr(gt.gt_off), _ptr(in_hw), gt.B, _ptr(rect), _ptr(crop_hw), _ptr(out),
+                                    gt.rows, _stream(dev)), "rn_bbox_crop_draw")
+    return rect, crop_hw, out
+
+
+def image_crop_stage(staged: StagedImages, rect: Tensor, crop_hw: Tensor, out: Optional[StagedImages] = None) -> StagedImages:
+    """``rn_image_crop_stage``: image b's window ``rect[b]`` = (y0, x0, ch, cw) of ``staged``, dense at the start of slot b of a second
+    arena whose sizes are ``crop_hw`` (int32 [B, 2]; the tensor is kept, not copied) -- a ``StagedImages`` like any other, bit-identical
+    to staging ``img[:, y0:y0+ch, x0:x0+cw]``.  ``out``: an arena to write into (its ``in_hw`` is ignored), else one with ``staged``'s
+    slot is allocated here.  The host-side ``hw``, ``bounds`` and ``canvas`` are carried over: the host does not know the rectangles.
+    One launch on the current stream, a fixed grid, no host synchronisation (capturable)."""
+    dev = _need_dev(staged.arena, staged.in_hw, rect, crop_hw)
+    B = staged.B
+    for name, t, cols in (("rect", rect, 4), ("crop_hw", crop_hw, 2)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, cols) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 [{B}, {cols}] tensor, got {tuple(t.shape)} {t.dtype}")
+    arena = torch.empty_like(staged.arena) if out is None else out.arena
+    if arena.device != dev or arena.shape[0] != B or arena.data_ptr() == staged.arena.data_ptr():
+        raise ValueError(f"the output arena must be another arena of {B} slots on {dev}")
+    res = StagedImages(arena, crop_hw, staged.canvas)
+    with torch.cuda.device(dev), _timed("image_crop_stage", dev):
+        check(lib.rn_image_crop_stage(_ptr(staged.arena), staged.slot, _ptr(staged.in_hw), _ptr(rect), B, _ptr(arena), res.slot,
+                                      _stream(dev)), "rn_image_crop_stage")
+    res.hw, res.bounds = list(staged.hw), (None if staged.bounds is None else list(staged.bounds))
+    return res
+
+
+def bbox_crop_staged(crop, staged: StagedImages, packed: PackedGT) -> Tuple[StagedImages, PackedGT]:
+    """The bbox-safe random crop of a staged batch (``crop``: an ``augment.BBoxSafeRandomCrop``): ``bbox_crop_draw`` from the object's
+    device block, then ``image_crop_stage`` into an arena allocated here, like the other intermediates of a step -> (the cropped
+    ``StagedImages``, ``packed.with_boxes(the shifted boxes)``).  The rectangles stay on the device as ``crop.rect``."""
+    if packed.B != staged.B:
+        raise ValueError(f"packed GT of {packed.B} images for an arena of {staged.B}")
+    rect, crop_hw, boxes = bbox_crop_draw(crop.device_block(staged.device), staged.in_hw, packed)
+    crop.rect = rect
+    return image_crop_stage(staged, rect, crop_hw), packed.with_boxes(boxes)
+
+
 def decode_clip(deltas: Tensor, anchors: Tensor, image_hw: Optional[Tensor],
                 reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0)) -> Tensor:
     """K4.  deltas [B,A,4] or [A,4]; image_hw i32 [B,2] (device) or None.  -> f32 boxes, same leading shape."""

@@ -52,6 +52,15 @@ the canvas the caller fixed.  In training mode with packed GT, or in eval mode w
 with the fixed eval short side ``min_size[-1]``, no flip, no jitter; the sizes it wrote stay on the device as ``ImageList.image_sizes_dev``);
 the fused path only.  The result is bit-identical to the list path's on the same canvas; the cost is the jitter's: the conv stack
 processes the whole class canvas whatever the batch's own canvas was.
+
+Train-time bbox-safe random crop (``crop``: an ``augment.BBoxSafeRandomCrop``, None by default): in training mode and when targets are
+given, each image is cropped with probability p to a random window that contains all of its boxes, and the boxes are shifted with it --
+FIRST, before the flip, the colour jitter and the resize, which then see the cropped image.  On staged images with packed GT it is a
+second staging pass on the device (``ops.bbox_crop_staged``: ``rn_bbox_crop_draw`` + ``rn_image_crop_stage`` into a second arena, the
+cropped sizes next to it), so everything after it runs unchanged and is bit-identical to the same call on the sliced images; the canvas
+follows from ``crop.bound`` (the crop keeps the orientation), so ``staged_bounds`` depends on the image shapes alone.  Every other input
+draws the same rectangles on the HOST from the Python restatement -- the boxes and the counter are read back, one synchronisation on
+CUDA -- slices the images and shifts the boxes with torch, and goes on as without a crop.  ``crop`` is a plain attribute too.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -139,6 +148,7 @@ class GeneralizedRCNNTransform(nn.Module):
         self.hflip = None             # augment.RandomHorizontalFlip: the train-time flip (module docstring)
         self.scale_jitter = None      # augment.RandomShortSide: the short side drawn on the device (module docstring)
         self.color_jitter = None      # augment.ColorJitter: the colour jitter drawn and applied on the device (module docstring)
+        self.crop = None              # augment.BBoxSafeRandomCrop: the bbox-safe random crop, before everything else (module docstring)
 
     # -- pieces ------------------------------------------------------------------------
     def normalize(self, image: Tensor) -> Tensor:
@@ -274,12 +284,17 @@ class GeneralizedRCNNTransform(nn.Module):
         """Host arithmetic on the raw sizes alone: per image the size after the resize -- with a ``scale_jitter`` installed the upper
         bound of every size it can draw (``jitter.bound``).  The natural canvas of a staged batch is ``_canvas`` over these."""
         jitter = self.scale_jitter
-        if jitter is not None:
-            return [jitter.bound(int(h), int(w), self.max_size) for h, w in in_hw]
-        short = self.staged_short_side()               # (the value the device plan gets: bound and plan cannot drift apart)
-        if short is None:
+        short = None if jitter is not None else self.staged_short_side()      # (the value the device plan gets: bound and plan cannot drift apart)
+        if jitter is None and short is None:
             raise ValueError(f"staged images need one integer min_size and an integer max_size (got {self.min_size}, {self.max_size}), "
                              "or an augment.RandomShortSide as scale_jitter")
+        crop = getattr(self, "crop", None)
+        if crop is not None:
+            # the window is drawn on the device: the bound is that of every window of the image's orientation (``crop.bound``)
+            most = max((jitter.canvas_short,) + tuple(jitter.sizes)) if jitter is not None else short
+            return [crop.bound(int(h), int(w), most, int(self.max_size)) for h, w in in_hw]
+        if jitter is not None:
+            return [jitter.bound(int(h), int(w), self.max_size) for h, w in in_hw]
         return self._sizes_for(in_hw, float(short))
 
     def _sizes_for(self, in_hw: Sequence[Tuple[int, int]], short: float) -> List[Tuple[int, int]]:
@@ -343,6 +358,10 @@ class GeneralizedRCNNTransform(nn.Module):
         if targets.B != staged.B or len(staged.hw) != staged.B:
             raise ValueError(f"packed GT of {targets.B} images for {len(staged.hw)} staged images in an arena of {staged.B}")
         (hp, wp), bounds = self._check_staged_canvas(canvas, staged, self.staged_bounds)
+        crop = getattr(self, "crop", None)
+        if crop is not None:
+            # a second staging pass: from here on ``staged`` is the arena of the windows and its sizes are the cropped ones
+            staged, targets = ops.bbox_crop_staged(crop, staged, targets)
         flags = self.hflip.next_flags(staged.B, staged.device) if self.hflip is not None else None
         coef = self._color(staged, targets)
         jitter = self.scale_jitter
@@ -356,6 +375,33 @@ class GeneralizedRCNNTransform(nn.Module):
         batch = ops.transform_batch_var(staged, out_hw, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags,
                                         coef=coef)
         return ImageList(batch, bounds), targets
+
+    def _crop_on_host(self, images: List[Tensor], targets):
+        """The installed ``crop`` for images that are not staged: the rectangles from the Python restatement (``crop.next_rects`` reads
+        the boxes and the counter on the host: one synchronisation on CUDA), the images sliced (views) and the boxes shifted with
+        torch -- one fp32 subtraction each, as the kernel does -- for target dicts and packed GT alike."""
+        in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
+        packed = _is_packed(targets)
+        if packed:
+            off = [int(v) for v in targets.gt_off.tolist()]
+            rows = targets.gt_boxes.detach().cpu()
+            boxes = [rows[lo:hi] for lo, hi in zip(off[:-1], off[1:])]
+        else:
+            boxes = [t["boxes"].reshape(-1, 4) for t in targets]
+        rects = self.crop.next_rects(in_hw, boxes)
+        images = [im[:, y0:y0 + ch, x0:x0 + cw] for im, (y0, x0, ch, cw) in zip(images, rects)]
+        shifted = []
+        for b, (bx, (y0, x0, _, _)) in enumerate(zip(boxes, rects)):
+            moved = (y0, x0) != (0, 0) and bx.shape[0] > 0
+            shifted.append(bx - bx.new_tensor([x0, y0, x0, y0], dtype=torch.float32) if moved else bx)
+        if packed:
+            out = rows.clone()
+            for lo, hi, bx in zip(off[:-1], off[1:], shifted):
+                out[lo:hi] = bx
+            return images, targets.with_boxes(out.to(targets.gt_boxes.device))
+        for t, bx in zip(targets, shifted):
+            t["boxes"] = bx
+        return images, targets
 
     # -- whole transform -----------------------------------------------------------------
     def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None,
@@ -378,6 +424,8 @@ class GeneralizedRCNNTransform(nn.Module):
         for im in images:
             if im.dim() != 3:
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(im.shape)}")
+        if getattr(self, "crop", None) is not None and self.training and targets is not None:
+            images, targets = self._crop_on_host(images, targets)
         if self._fusable(images):
             return self._forward_fused(images, targets, out_dtype or torch.float32, channels_last)
         flags = self._flips(images, targets)
