@@ -43,6 +43,9 @@
 #ifndef BAND_NARROW_FWD
 #define BAND_NARROW_FWD 1            // the <= 64-column TO_LEVELS launches on conv3x3_band_narrow_kernel (0: the tile kernel's NARROW variant)
 #endif
+#ifndef TOWER_BAND
+#define TOWER_BAND 1                 // the CANVAS launches with Cout = 256 (head towers, forward and data gradient) on the tile kernel's BAND walk (0: its tile walk)
+#endif
 
 namespace {
 
@@ -51,6 +54,7 @@ typedef __attribute__((address_space(3))) void *lds_void_ptr;
 
 constexpr int CONV_BM = 256, CONV_BN = 256, CONV_BK = 64, CONV_THREADS = 512;
 constexpr int CONV_LDS_BYTES = 5 * CONV_BM * CONV_BK * 2;        // 160 KiB
+constexpr int BAND_BYTES = (CONV_BM + 8) * 128;                   // a band: 264 rows of 64 channels (258 are read; pieces are whole 8-row groups)
 #define SWZ(row) (((row) >> 1) & 7)
 
 constexpr int CONV_MAX_PROBLEMS = 4;
@@ -200,12 +204,20 @@ struct ConvProblem { const uint16_t *X, *W; const float *bias; uint16_t *Y; };
 
 struct Walk { int tap, chunk; };      // position of the K walk
 
+// BAND (CANVAS only, full width; TOWER_BAND): the K walk stages the activation operand once per (channel chunk, kernel ROW) as a
+// band of 258 canvas positions that the row's three taps read at band rows +0 / +1 / +2 -- 12 bands of 33 KiB per tile instead of 36
+// tiles of 32 KiB, 17 LDS-DMA pieces per wave and kernel row instead of 24.  Staging depth: two band buffers + two weight buffers
+// (133 120 bytes; a third weight buffer would make 165 888 and does not fit the CU's 163 840) -- see the walk.  Same products in the
+// same order as the tile walk, same 8-wave / accumulator layout and epilogues.  Compiler's resource usage, bf16 and fp16 alike:
+// 256 VGPRs, 0 AGPRs, 79 SGPRs, no scratch, no spill, 160 KiB of dynamic LDS (the epilogue's), 2 waves per SIMD.  Measured (two
+// [8,153,170,256] -> 256 towers per launch, inside the replayed train step): 391 -> 327 us per launch.
 // NARROW (TO_LEVELS only): a column tile of at most 64 output channels -- the last, ragged tile of the 810-channel
 // class-output conv (42 columns).  All 8 waves split the ROWS (32 each) and compute 32 x 64: a quarter of the MFMAs and a
 // quarter of the weight staging of a full tile whose other 192 columns would be zeros.
-template <int DT, int MODE, bool NARROW = false>
+template <int DT, int MODE, bool NARROW = false, bool BAND = false>
 __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const ConvArgs args)
 {
+    static_assert(!BAND || (MODE == MODE_CANVAS && !NARROW), "the band walk serves the full-width CANVAS mode");
     constexpr int MI = NARROW ? 1 : 4;                            // 32-row accumulator tiles per wave
     int prob = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
     if (args.xcd_ny > 0) {
@@ -244,7 +256,9 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
     // 9 -> 3 per chunk.  Correct, and -3 % with the 32 x 32 x 16 instruction; +9 % slower than this loop with 16 x 16 x 32 (its
     // full vmcnt(0) drain at every band's last tap costs more when the matrix instruction leaves the partner wave half the
     // issue slots).  Ablations on it: no weight DMA -11 %, no band DMA -14 %, neither -28 % -- the tile is bound by the
-    // fragment-read / MFMA / barrier cadence and the DMA ISSUE slots, not by staging bandwidth.  Removed; see git history.)
+    // fragment-read / MFMA / barrier cadence and the DMA ISSUE slots, not by staging bandwidth.  Removed; see git history.
+    // The BAND walk below is that idea WITHOUT the drain: the next band's pieces are spread over the first two taps of the current
+    // one and every wait is counted, so a wait only ever covers pieces the next phase reads.  CANVAS, Cout = 256: 391 -> 327 us.)
     unsigned char *const Abase = lds, *const Bbase = lds + 3 * TILE;
     // K walk.  CANVAS / TO_LEVELS: chunk outer, tap inner (a tile's input lines stay in L2 across its taps).
     // FROM_LEVELS: tap outer, chunk inner -- the gathered row pointers of a tap are computed once per 13 K-tiles.
@@ -323,6 +337,23 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
         voff_b[i] = (uint32_t)(row * 9 * args.Cin + ((cp ^ SWZ(row)) << 3)) * 2u;
     }
     const bool a_edge = m0 - (Wp + 1) < 0 || m0 + CONV_BM + Wp + 1 > M;             // wave-uniform
+    // BAND: the three horizontal taps of kernel row r read ONE band per (channel chunk, r) -- the 258 canvas positions from
+    // m0 + (r - 1) Wp - 1, band row j = position + j, in rows of 128 bytes with the tile's swizzle keyed on the BAND row -- and tap
+    // column s reads its fragments at band row = tile row + s (rows 16 apart still share a key: the mi offsets stay immediates).
+    // Pieces 0..3 of a band are the tile's (row = q >> 3: voff_a serves them); the fifth is band rows 256 .. 263, row 256 + wave in
+    // lanes 0..7 of EVERY wave, so that all waves count the same number of pieces.
+    // (k-step 1 reads chunk + 4 of the same row: its address is k-step 0's with byte bit 6 flipped -- one register per tap column.)
+    uint32_t a_off_band[3] = {0u, 0u, 0u}, voff_a4 = 0u, keep_bits = 0xffffu;
+    const bool band_edge = m0 - Wp - 1 < 0 || m0 + Wp - 1 + (CONV_BM + 8) > M;       // wave-uniform: one of the tile's bands leaves the canvas
+    if (BAND) {
+#pragma unroll
+        for (int sft = 0; sft < 3; ++sft) {
+            const int chunk = lane >> 4, row = wm * 128 + (lane & 15) + sft;
+            a_off_band[sft] = row * 128 + ((chunk ^ SWZ(row)) << 4);
+        }
+        const int row = CONV_BM + wave, cp = lane & 7;
+        voff_a4 = (uint32_t)(row * (args.x_split > 0 ? args.x_ld : args.Cin) + ((cp ^ SWZ(row)) << 3)) * 2u;
+    }
     uint32_t tap_ok[4] = {0u, 0u, 0u, 0u};                         // DENSE: bit t = tap t of staged row i lies inside the row's image
     if (MODE == MODE_DENSE) {
 #pragma unroll
@@ -383,6 +414,9 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
         unsigned char *const sb = Bbase + stage * TILE;
         if (!b_ragged) {
             const unsigned char *base = (const unsigned char *)a.W + (((int64_t)n0 * 9 + t) * args.Cin + c0) * 2;
+            if (BAND)      // (weight rows 64 apart share their key too: one per-lane offset, the piece's 64 rows on the SALU side)
+                __builtin_amdgcn_global_load_lds((const void *)(base + (int64_t)i * (64 * 9 * 2) * args.Cin + voff_b[0]), (lds_void_ptr)lds_piece(sb, i), 16, 0, 0);
+            else
             __builtin_amdgcn_global_load_lds((const void *)(base + voff_b[i]), (lds_void_ptr)lds_piece(sb, i), 16, 0, 0);
         } else {
             const int q = i * CONV_THREADS + tid, row = q >> 3, cp = q & 7;
@@ -391,9 +425,37 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
             __builtin_amdgcn_global_load_lds((const void *)g, (lds_void_ptr)lds_piece(sb, i), 16, 0, 0);
         }
     };
+    // BAND: piece i = 0..4 of the band of (channel chunk w.chunk, kernel row w.tap / 3) into band buffer buf.  A band that leaves the
+    // canvas (first / last tiles) has its rows clamped into it, position by position as the tile walk clamps its taps: the same rows
+    // feed the same products.
+    auto piece_band = [&](const Walk w, const int buf, const int i) {
+        if (i == 4 && lane >= 8) return;
+        const uint16_t *X = a.X;
+        int ld = args.Cin, cs = w.chunk * CONV_BK;
+        if (args.x_split > 0) {                                        // (wave-uniform)
+            ld = args.x_ld;
+            if (w.chunk >= args.x_split) { X = args.X2s[prob]; cs -= args.x_split * CONV_BK; }
+        }
+        const int p0 = (int)m0 + (w.tap / 3 - 1) * Wp - 1;               // canvas position of band row 0 (host: M * ld * 2 < 2^32 on this walk)
+        unsigned char *const sb = lds + buf * BAND_BYTES;
+        unsigned char *const dst = i < 4 ? lds_piece(sb, i) : sb + (CONV_BM + wave) * 128;
+        // (pieces 0..3 are rows 64 apart, which share their key: piece 0's per-lane offset from a base moved by SALU)
+        const int row0 = i < 4 ? tid >> 3 : CONV_BM + wave;
+        const uint32_t vo = i < 4 ? voff_a[0] : voff_a4;
+        if (!band_edge) {
+            const unsigned char *base = (const unsigned char *)X + (((int64_t)p0 + (i < 4 ? i * 64 : 0)) * ld + cs) * 2;
+            __builtin_amdgcn_global_load_lds((const void *)(base + vo), (lds_void_ptr)dst, 16, 0, 0);
+        } else {
+            // per-lane positions and byte offsets stay 32-bit: the row's swizzled chunk is its fast-path offset less the row's start
+            int m = p0 + row0 + (i < 4 ? i * 64 : 0);
+            m = m < 0 ? 0 : (m >= (int)M ? (int)M - 1 : m);
+            const uint32_t o = (uint32_t)m * (uint32_t)(ld * 2) + (vo - (uint32_t)row0 * (uint32_t)(ld * 2));
+            __builtin_amdgcn_global_load_lds((const void *)((const unsigned char *)X + cs * 2 + o), (lds_void_ptr)dst, 16, 0, 0);
+        }
+    };
     typename rn::mma<DT>::frag fa[MT], fb[NT];
 #define RN_DS_READ(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
-#define RN_LOAD_FRAGS_AT(AA, KS)                                                   \
+#define RN_LOAD_FRAGS_AT(AA, KS)                                                \
     { const uint32_t ba = bbase + b_off[KS], aa = (AA);                            \
       RN_DS_READ(fb[0], ba, 0); RN_DS_READ(fb[1], ba, 2048); RN_DS_READ(fb[2], ba, 4096); RN_DS_READ(fb[3], ba, 6144); \
       RN_DS_READ(fa[0], aa, 0); RN_DS_READ(fa[1], aa, 2048);                        \
@@ -415,6 +477,14 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
     Walk wa = {0, 0}, wb = {0, 0};                                  // K-tile whose A / B pieces are issued next
     if (MODE == MODE_DENSE) { wa.tap = wb.tap = kt0 % 9; wa.chunk = wb.chunk = kt0 / 9; }
     int sa = 0;                                                     // its A stage (mod 3)
+    if (BAND) {                                                     // band 0 and the weights of tap 0; wa walks the BANDS (tap = 3 r)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) piece_band(wa, 0, i);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) piece_b(wb, 0, i);
+        wa.tap = 3; advance(wb);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
     if (MODE == MODE_FROM_LEVELS) gather_tap(0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) piece_a(wa, 0, i);
@@ -432,6 +502,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
     sa = 2;
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     if (MODE == MODE_FROM_LEVELS) map_landed(g_entry);
+    }
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();                    // group 1 runs one barrier interval behind group 0
 
@@ -445,7 +516,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
     uint32_t keep[16];                                              // (one register each: packed into bytes the compiler waits for every load in turn)
 #pragma unroll
     for (int i = 0; i < 16; ++i) keep[i] = 1;
-    auto epilogue_prefetch = [&]() {
+    auto epilogue_prefetch = [&](uint32_t (&kp)[16]) {
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
             const int col = wn * 64 + ni * 16 + (lane & 15);
@@ -459,10 +530,71 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
                 const int row = i * 16 + (tid >> 5);
                 int64_t pos = pos0 + row;
                 if (one_wrap) pos = pos >= HWp ? pos - HWp : pos; else pos = (int64_t)((uint32_t)pos % (uint32_t)HWp);
-                keep[i] = args.mask[pos];                             // (pos < HWp whatever the row: no branch, the 16 loads fly together; rows past M are not stored)
+                kp[i] = args.mask[pos];                             // (pos < HWp whatever the row: no branch, the 16 loads fly together; rows past M are not stored)
             }
         }
     };
+    if (BAND) {
+        // BAND walk: the tile walk's K-tiles in the tile walk's order (chunk outer, kernel row, tap column: the same products summed
+        // in the same order), the same two (load, MFMA) phase pairs per tap and the same ping-pong -- but the activation operand of the
+        // three taps of a kernel row is ONE band, staged once: per tile 12 bands of 33 KiB instead of 36 tiles of 32 KiB, 17 LDS-DMA
+        // pieces per wave and kernel row instead of 24.
+        // Staging depth: TWO band buffers (band b + 1 lands under band b's three taps) and TWO 32 KiB weight buffers (one tap ahead),
+        // 2 x 33 792 + 2 x 32 768 = 133 120 bytes.  Three rotating weight buffers -- what would let a tap's weights be requested two
+        // taps ahead -- make 165 888 bytes with two bands and do not fit the CU's 163 840; one band buffer would leave the first tap
+        // of every kernel row waiting for its whole fill.  The weight buffers stay where the tile walk has them (behind 96 KiB), and
+        // the epilogue reuses all of it as before.
+        // Issue order (pieces per wave): tap (b, s), first load phase: the 4 weight pieces of the next tap; second load phase:
+        // s = 0: band b + 1 pieces 0..2, s = 1: pieces 3, 4, s = 2: none.  The counted wait at the end of the second load phase
+        // leaves only the band pieces just issued in flight (3 / 2 / 0): the next tap's weights are older, and after s = 2 the whole
+        // next band has landed, one barrier before any wave of either group reads it.  A band buffer is refilled from the second load
+        // phase of the tap after its last reader, a weight buffer from the first: the tile walk's distances.
+        const int NB = 3 * cpt;
+        for (int b = 0; b < NB; ++b) {
+            const uint32_t aband = lds_base + (uint32_t)((b & 1) * BAND_BYTES);
+            const bool more = b + 1 < NB;
+            uint32_t kp[16];                                        // (per band: the 16 keep bytes live only from their request to their packing, both in tap 0)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) kp[i] = 1;
+#pragma unroll
+            for (int sft = 0; sft < 3; ++sft) {
+                const int kt = 3 * b + sft;
+                const uint32_t bbase = lds_base + (uint32_t)(3 * TILE + (kt & 1) * TILE);
+                RN_LOAD_FRAGS_AT(aband + a_off_band[sft], 0)
+                __builtin_amdgcn_sched_barrier(0);
+                if (more || sft < 2) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) piece_b(wb, (kt + 1) & 1, i);
+                    advance(wb);
+                }
+                if (sft == 0 && b == 0) epilogue_prefetch(kp);
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_barrier();
+                RN_MFMA_PHASE()
+                RN_LOAD_FRAGS_AT(aband + (a_off_band[sft] ^ 64u), 1)
+                __builtin_amdgcn_sched_barrier(0);
+                if (more && sft == 0) {
+                    piece_band(wa, (b + 1) & 1, 0); piece_band(wa, (b + 1) & 1, 1); piece_band(wa, (b + 1) & 1, 2);
+                    asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+                    if (b == 0) {                                   // the keep bytes requested in tap 0 have landed: 16 registers -> 16 bits for the walk
+                        keep_bits = 0u;
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) keep_bits |= kp[i] ? 1u << i : 0u;
+                    }
+                } else if (more && sft == 1) {
+                    piece_band(wa, (b + 1) & 1, 3); piece_band(wa, (b + 1) & 1, 4);
+                    wa.tap += 3;
+                    if (wa.tap == 9) { wa.tap = 0; ++wa.chunk; }
+                    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                } else {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_barrier();
+                RN_MFMA_PHASE()
+            }
+        }
+    } else {
     int scur = 0;                                                   // A stage of K-tile kt (mod 3)
     for (int kt = 0; kt < KT; ++kt) {
         const uint32_t abase = lds_base + (uint32_t)(scur * TILE), bbase = lds_base + (uint32_t)(3 * TILE + (kt & 1) * TILE);
@@ -475,7 +607,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
             for (int i = 0; i < 4; ++i) piece_b(wb, (kt + 1) & 1, i);
             advance(wb);
         }
-        if (kt == 0) epilogue_prefetch();
+        if (kt == 0) epilogue_prefetch(keep);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         RN_MFMA_PHASE()
@@ -496,6 +628,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         RN_MFMA_PHASE()
+    }
     }
 
 #undef RN_DS_READ
@@ -606,7 +739,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
             const int64_t m = m0 + row;
             if (m < M) {
                 uint4 v = *(const uint4 *)(Ys + row * CONV_BN + piece * 8);
-                if (!keep[i]) v = make_uint4(0, 0, 0, 0);
+                if (BAND ? !((keep_bits >> i) & 1u) : !keep[i]) v = make_uint4(0, 0, 0, 0);
                 if (relu_mask) {
                     // (the byte's four word masks come out of a 256-entry LDS table: expanded with shifts and selects they were ~24 of the
                     //  ~60 VALU instructions per piece of a loop that takes 4.9 us per tile, tools/probes)
@@ -662,8 +795,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_canvas_kernel(const Conv
 // buffers of the band's three weight tiles (24 KiB); one band ahead by LDS-DMA, counted vmcnt, two barriers per band; 8 waves of
 // 32 rows x 64 columns, 48 MFMAs (16x16x32) per wave and band.  Same products in another order than the tile kernel (kernel
 // row outer): results agree to f32 summation order.
-// (a band is CONV_BM + 2 = 258 positions)
-constexpr int BAND_BYTES = (CONV_BM + 8) * 128;                   // 264 rows of 64 channels: pieces are whole 8-row groups
+// (a band is CONV_BM + 2 = 258 positions; BAND_BYTES is defined with the tile kernel, whose BAND walk stages the same bands)
 constexpr int BANDW_BYTES = 3 * 64 * 128;                         // the band's three taps: 64 weight rows x 64 channels each
 constexpr int BAND_LDS = 2 * BAND_BYTES + 2 * BANDW_BYTES;        // 116 736 bytes
 
@@ -1760,20 +1892,20 @@ __global__ __launch_bounds__(256) void colsum_reduce_kernel(const float *__restr
 #ifndef CONV_XCD_MAP
 #define CONV_XCD_MAP 1
 #endif
-template <int DT, int MODE, bool NARROW>
+template <int DT, int MODE, bool NARROW, bool BAND = false>
 static int conv_launch_dt(const ConvArgs &a, const dim3 grid, hipStream_t st)
 {
     if (MODE != MODE_DENSE && (a.M >= ((int64_t)1 << 31) || a.HWp >= ((int64_t)1 << 31))) return RN_EUNSUPPORTED;      // 32-bit position arithmetic in the kernel
     // 160 KiB of dynamic LDS needs the opt-in once per device (the attribute lives with the device's code object)
     static rn::DynLdsOptIn opt_in = {};
-    { const int rc = opt_in.ensure((const void *)conv3x3_canvas_kernel<DT, MODE, NARROW>, CONV_LDS_BYTES); if (rc != RN_OK) return rc; }
+    { const int rc = opt_in.ensure((const void *)conv3x3_canvas_kernel<DT, MODE, NARROW, BAND>, CONV_LDS_BYTES); if (rc != RN_OK) return rc; }
     if (CONV_XCD_MAP && grid.x >= 16) {
         ConvArgs b = a;
         b.xcd_ny = (int)grid.y; b.xcd_q = (int)(grid.x / 8); b.xcd_r = (int)(grid.x % 8);
-        hipLaunchKernelGGL((conv3x3_canvas_kernel<DT, MODE, NARROW>), dim3(8u * (unsigned)(b.xcd_q + (b.xcd_r > 0)) * grid.y, 1, grid.z), dim3(CONV_THREADS),
+        hipLaunchKernelGGL((conv3x3_canvas_kernel<DT, MODE, NARROW, BAND>), dim3(8u * (unsigned)(b.xcd_q + (b.xcd_r > 0)) * grid.y, 1, grid.z), dim3(CONV_THREADS),
                            CONV_LDS_BYTES, st, b);
     } else
-    hipLaunchKernelGGL((conv3x3_canvas_kernel<DT, MODE, NARROW>), grid, dim3(CONV_THREADS), CONV_LDS_BYTES, st, a);
+    hipLaunchKernelGGL((conv3x3_canvas_kernel<DT, MODE, NARROW, BAND>), grid, dim3(CONV_THREADS), CONV_LDS_BYTES, st, a);
     RN_LAUNCH_CHECK();
     return RN_OK;
 }
@@ -1781,6 +1913,16 @@ template <int MODE, bool NARROW = false>
 static int conv_launch_mode(const ConvArgs &a, const dim3 grid, hipStream_t st)
 {
     return a.f16 ? conv_launch_dt<RN_F16, MODE, NARROW>(a, grid, st) : conv_launch_dt<RN_BF16, MODE, NARROW>(a, grid, st);
+}
+// The CANVAS launches (head towers: forward, data gradient, two-source data gradient).  TOWER_BAND: one 256-column tile per row tile runs
+// the kernel's BAND walk; other widths, and an activation tensor whose byte offsets (M rows of ld elements) would leave 32 bits, keep the
+// tile walk.
+static int conv_launch_canvas(const ConvArgs &a, const dim3 grid, hipStream_t st)
+{
+    const int ld = a.x_split > 0 ? a.x_ld : a.Cin;
+    if (TOWER_BAND && a.Cout == CONV_BN && a.Cin % CONV_BK == 0 && a.M > 0 && (a.M + CONV_BM + 8) * (int64_t)ld * 2 < ((int64_t)1 << 32))
+        return a.f16 ? conv_launch_dt<RN_F16, MODE_CANVAS, false, true>(a, grid, st) : conv_launch_dt<RN_BF16, MODE_CANVAS, false, true>(a, grid, st);
+    return conv_launch_mode<MODE_CANVAS>(a, grid, st);
 }
 static inline bool conv_dtype_ok(const int dtype) { return dtype == RN_BF16 || dtype == RN_F16; }
 
@@ -1832,7 +1974,7 @@ RN_API int rn_conv3x3_canvas_batched_ex(const void *const *xs, const void *const
     }
     a.mask = mask; a.M = M; a.HWp = HWp; a.Cin = Cin; a.Cout = Cout; a.Wp = Wp; a.relu = relu ? 1 : 0; a.zeros = nullptr;
     const dim3 grid((unsigned)((M + CONV_BM - 1) / CONV_BM), (unsigned)(Cout / CONV_BN), (unsigned)P);
-    return conv_launch_mode<MODE_CANVAS>(a, grid, (hipStream_t)stream);
+    return conv_launch_canvas(a, grid, (hipStream_t)stream);
 }
 
 RN_API int rn_conv3x3_canvas_sum2(const void *x, const void *x2, const void *w, const uint8_t *mask, void *y, int dtype, int64_t M,
@@ -1849,7 +1991,7 @@ RN_API int rn_conv3x3_canvas_sum2(const void *x, const void *x2, const void *w, 
     a.x_split = C / CONV_BK; a.x_ld = C;
     a.mask = mask; a.M = M; a.HWp = HWp; a.Cin = 2 * C; a.Cout = Cout; a.Wp = Wp; a.relu = 0; a.zeros = nullptr;
     const dim3 grid((unsigned)((M + CONV_BM - 1) / CONV_BM), (unsigned)(Cout / CONV_BN), 1);
-    return conv_launch_mode<MODE_CANVAS>(a, grid, (hipStream_t)stream);
+    return conv_launch_canvas(a, grid, (hipStream_t)stream);
 }
 
 RN_API int rn_conv3x3_canvas(const void *x, const void *w, const float *bias, const uint8_t *mask, void *y, int dtype,
@@ -1995,7 +2137,7 @@ RN_API int rn_conv3x3_canvas_dgrad_relu_batched(const void *const *gs, const voi
     }
     a.mask = mask; a.M = M; a.HWp = HWp; a.Cin = Cin; a.Cout = Cout; a.Wp = Wp; a.relu = 0; a.zeros = nullptr;
     const dim3 grid((unsigned)tiles, (unsigned)(Cout / CONV_BN), (unsigned)P);
-    const int rc = conv_launch_mode<MODE_CANVAS>(a, grid, (hipStream_t)stream);
+    const int rc = conv_launch_canvas(a, grid, (hipStream_t)stream);
     if (rc != RN_OK) return rc;
     hipLaunchKernelGGL(colsum_reduce_kernel, dim3((unsigned)((Cout + 7) / 8), (unsigned)P), dim3(256), 0, (hipStream_t)stream,
                        (const float *)workspace, (int)tiles, Cout, outs[0], outs[1], outs[2], outs[3]);
