@@ -1006,6 +1006,57 @@ int rn_bbox_crop_draw(rn_bbox_crop_state *state, const float *gt_boxes, const in
 int rn_image_crop_stage(const float *arena, int64_t slot, const int32_t *in_hw_dev, const int32_t *rect, int B,
                         float *arena_out, int64_t slot_out, void *stream);
 
+/* ---- train-time augmentation: shift / scale / rotate (augment.ShiftScaleRotate), a second staging pass ---------------------
+ * albumentations' ShiftScaleRotate (bilinear, reflect-101 border) in intent, NOT bit for bit: OpenCV's warpAffine uses fixed-point
+ * weights and albumentations' box code depends on its version.  The numbered rule below and augment.ShiftScaleRotate's restatement
+ * (draw_coefs, warp_boxes, warp_image) are the definition.  It works on staged images and packed GT only: the draw writes a pair of
+ * matrices per image and the packed GT of the rows that survive, the warp gathers each image into a second arena with the same
+ * (h, w) and slot layout, and everything downstream runs unchanged on (arena_out, in_hw_dev, the new packed GT).
+ * rn_affine_state: a DEVICE block (8-byte aligned) owned by augment.ShiftScaleRotate, written by the host outside any capture;
+ * lo / hi: the ranges of (angle in degrees, scale, dx, dy), dx and dy as fractions of the width and the height.
+ * rn_affine_coef: per image the forward matrix m = (m00, m01, m02, m10, m11, m12), its inverse inv in the same order, applied
+ * (0: the image and its rows are left alone) and kept, the number of rows the image has in the output.
+ * rn_affine_draw: three launches, no atomics -- one wave per image (coef), one wave per image (the offsets and the rows), one wave
+ * (counter += 1); any B <= 65535.  For image b with (h, w) = in_hw_dev[b] and its rows [gt_off[b], gt_off[b + 1]), the offsets
+ * clamped to [0, rows]:
+ *   1. u_k = the hash of rn_hflip_draw on (seed ^ salt_k, counter, b); salts: apply 0xA551A551A551A551, angle 0xA4613A4613A46135,
+ *      scale 0x5CA7E5CA7E5CA7E5, dx 0xD0C5D0C5D0C5D0C5, dy 0xD1E7D1E7D1E7D1E7.  applied = u_apply < p;  angle = lo + u * (hi - lo), and
+ *      scale, dx, dy likewise from their ranges: fp32, this order.
+ *   2. In double from the fp32 draws, each entry rounded to fp32 once:  t = angle * pi / 180,  a = scale * cos t,  b = scale * sin t,
+ *      cx = (w - 1) / 2,  cy = (h - 1) / 2,  tx = ((1 - a) cx - b cy) + dx w,  ty = (b cx + (1 - a) cy) + dy h,  det = a a + b b;
+ *      m = (a, b, tx, -b, a, ty);  inv = (a / det, -b / det, -(i00 tx + i01 ty), b / det, a / det, -(i10 tx + i11 ty)) with the
+ *      unrounded i00 .. i11.  The image is LEFT ALONE -- applied = 0, m = inv = the identity, its rows copied bit for bit, its pixels
+ *      copied bit for bit -- when not applied, h < 1 or w < 1, any fp32 entry of m or inv is not finite, or det < 1e-12.
+ *   3. Boxes, fp32 without FMA, with min(p, q) = q < p ? q : p and max(p, q) = q > p ? q : p folded from the left: the corners
+ *      (x1, y1), (x2, y1), (x2, y2), (x1, y2) go through X = (m00 x + m01 y) + m02, Y = (m10 x + m11 y) + m12; (X1, Y1, X2, Y2) = the
+ *      min / max of the four; the new box is each value v clamped as v < 0 ? 0 : (v > float(w) ? float(w) : v) (float(h) for Y1, Y2).
+ *      Au = (X2 - X1) (Y2 - Y1) unclamped and Ac the same product clamped.  A row is KEPT iff all eight corner values are finite,
+ *      the clamped width > 0, the clamped height > 0 and Ac >= min_visibility * Au.  If the image has rows and none would be kept
+ *      the image is left alone as in step 2 (a deviation: no image loses all of its GT).  An image without rows is warped.
+ *   4. Kept rows go to out_boxes f32[rows][4] / out_labels i64[rows] in image order, stable within an image; out_gt_off i32[B + 1] is
+ *      the prefix of the kept counts, every entry at most rows, and no row at or past index rows is written whatever gt_off claims.
+ *      Rows past out_gt_off[B] are not written.  The same inputs give the same bits on every call.  The last launch: counter += 1.
+ * rn_image_warp_stage: image b, [3][h][w] at arena + b * slot, goes to arena_out + b * slot_out with the same (h, w).  With
+ * applied = 0 the 3 h w floats are copied bit for bit (a wave-uniform branch).  Else, for a destination pixel (x, y):
+ *   5. sx = (i00 x + i01 y) + i02, sy likewise (fp32, no FMA), each made s >= -2^30 ? s : -2^30 and then s <= 2^30 ? s : 2^30;
+ *      x0 = floorf(sx), fx = sx - x0, x1 = x0 + 1, the same for y; an index i of an axis of length n becomes 0 if n == 1, else with
+ *      period = 2 (n - 1) and t = i mod period (non-negative) it is t < n ? t : period - t (reflect-101, no loop);
+ *      v = (p00 (1 - fx) + p01 fx) (1 - fy) + (p10 (1 - fx) + p11 fx) fy, every operation rounded once, for each of the 3 channels.
+ * A fixed grid per image and 32 x 32 destination tiles; no size is a launch argument.  One thread computes the indices and weights of
+ * its pixels once for the three channels.  16-byte stores where w % 4 == 0 and the destination slot is 16-byte aligned.  Device
+ * data cannot move a thread outside the operands: every index is reflected into the image, and an image with h < 1, w < 1,
+ * 3 h w > slot or 3 h w > slot_out is skipped (its destination slot is left as it was).  Floats past 3 h w of a slot are left alone.
+ * RN_EINVAL: a null pointer (the row buffers may be null when rows == 0), an output aliasing its input, arena == arena_out, B <= 0 or
+ * > 65535, rows < 0 or >= 2^31, a slot < 3 or >= 2^31 floats.  RN_EALIGN: state not 8-byte, boxes not 16-byte, labels not 8-byte, the
+ * rest not 4-byte aligned. */
+typedef struct rn_affine_state { uint64_t seed; int64_t counter; float p; float min_visibility; float lo[4]; float hi[4]; } rn_affine_state;
+typedef struct rn_affine_coef { float m[6]; float inv[6]; int32_t applied; int32_t kept; int32_t reserved[2]; } rn_affine_coef;
+int rn_affine_draw(rn_affine_state *state, const float *gt_boxes, const int64_t *gt_labels, const int32_t *gt_off, const int32_t *in_hw_dev,
+                   int B, rn_affine_coef *coef /* DEVICE [B] */, float *out_boxes /* [rows][4] */, int64_t *out_labels /* [rows] */,
+                   int32_t *out_gt_off /* [B + 1] */, int64_t rows, void *stream);
+int rn_image_warp_stage(const float *arena, int64_t slot, const int32_t *in_hw_dev, const rn_affine_coef *coef, int B, float *arena_out,
+                        int64_t slot_out, void *stream);
+
 /* ---- K6 nms (op boundary) ---------------------------------------------------
  * Replaces torchvision.ops.nms as called at retinanet/models.py:210, batched over
  * S independent segments: seg_off i32[S+1]; boxes f32[N][4], scores f32[N].

@@ -33,6 +33,12 @@ It drops no box, so the GT counts and offsets of a captured step do not change. 
 staging pass: ``rn_bbox_crop_draw`` draws a rectangle per image around the union of its boxes and shifts the boxes,
 ``rn_image_crop_stage`` copies each window densely into a second arena, and everything downstream runs unchanged on that arena --
 bit-identical to running on the sliced tensors.  Other inputs draw the same rectangles on the host (one synchronisation on CUDA).
+
+``ShiftScaleRotate`` is the second transform of the reference's published recipe (``demo.ipynb``: ``HorizontalFlip``,
+``ShiftScaleRotate``, ``RandomBrightnessContrast``): albumentations' ``ShiftScaleRotate`` with bilinear interpolation and the reflect-101
+border in intent, not bit for bit.  It is a second staging pass as well -- ``rn_affine_draw`` draws a matrix per image and packs the GT
+rows that survive it (rows can disappear: the offsets change), ``rn_image_warp_stage`` gathers each image into a second arena -- and
+its Python restatement (``draw_coefs``, ``warp_boxes``, ``warp_image``) serves every other input on the host.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -41,7 +47,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-__all__ = ["RandomHorizontalFlip", "RandomShortSide", "ColorJitter", "BBoxSafeRandomCrop", "hflip_u", "apply_color_ops"]
+__all__ = ["RandomHorizontalFlip", "RandomShortSide", "ColorJitter", "BBoxSafeRandomCrop", "ShiftScaleRotate", "hflip_u", "apply_color_ops"]
 
 _M64 = 2 ** 64 - 1
 
@@ -791,6 +797,333 @@ def bbox_crop_from_transforms(entries, seed: int = 0, log=None) -> Optional[BBox
     return found
 
 
+# ---- shift / scale / rotate -----------------------------------------------------------------------------------------------
+AFFINE_SALT_APPLY = 0xA551A551A551A551                               # include/retinanet_hip.h: rn_affine_draw, step 1
+AFFINE_SALT_ANGLE, AFFINE_SALT_SCALE, AFFINE_SALT_DX, AFFINE_SALT_DY = 0xA4613A4613A46135, 0x5CA7E5CA7E5CA7E5, 0xD0C5D0C5D0C5D0C5, 0xD1E7D1E7D1E7D1E7
+AFFINE_MIN_DET = 1e-12                                               # step 2: below it the image is left alone
+_IDENTITY6 = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def _limit(v, name: str, bias: float = 0.0) -> Tuple[float, float]:
+    "albumentations' to_tuple: a scalar v is the range (-v, v), a pair is taken as given; ``bias`` is added to both ends; fp32 values."
+    if isinstance(v, (list, tuple)):
+        if len(v) != 2:
+            raise ValueError(f"{name} must be a number or a pair, got {v!r}")
+        lo, hi = float(v[0]), float(v[1])
+    else:
+        lo, hi = -float(v), float(v)
+    lo, hi = float(np.float32(min(lo, hi) + bias)), float(np.float32(max(lo, hi) + bias))
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError(f"{name} must be finite, got {v!r}")
+    return lo, hi
+
+
+class AffineCoefs:
+    """What ``rn_affine_draw`` writes per image, on the host: ``m`` and ``inv`` fp32 numpy [B, 6] (the forward matrix
+    (m00, m01, m02, m10, m11, m12) and its inverse), ``applied`` a list of bools."""
+    __slots__ = ("m", "inv", "applied")
+
+    def __init__(self, m, inv, applied):
+        self.m, self.inv = np.asarray(m, dtype=np.float32).reshape(-1, 6), np.asarray(inv, dtype=np.float32).reshape(-1, 6)
+        self.applied = [bool(a) for a in applied]
+
+    @classmethod
+    def from_device(cls, coef: Tensor) -> "AffineCoefs":
+        "From an ``rn_affine_coef`` tensor (``ops.affine_draw``, ``ShiftScaleRotate.coef``): one device->host copy."
+        raw = coef.detach().cpu().contiguous().numpy()
+        return cls(raw[:, 0:6].copy().view(np.float32), raw[:, 6:12].copy().view(np.float32), raw[:, 12] != 0)
+
+
+def _boxes_f32(bx) -> np.ndarray:
+    if bx is None:
+        return np.zeros((0, 4), np.float32)
+    if isinstance(bx, Tensor):
+        bx = bx.detach().cpu().numpy()
+    return np.asarray(bx, dtype=np.float32).reshape(-1, 4)
+
+
+def _warp_rows(m, h: int, w: int, min_visibility, bx: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    "Step 3 of ``rn_affine_draw`` on fp32 rows [T, 4] -> (the clamped boxes [T, 4], keep bool [T]); numpy fp32, one rounding per operation."
+    f32 = np.float32
+    m = [f32(v) for v in m]
+    xs, ys = (bx[:, 0], bx[:, 2], bx[:, 2], bx[:, 0]), (bx[:, 1], bx[:, 1], bx[:, 3], bx[:, 3])
+    with np.errstate(all="ignore"):
+        X = [(m[0] * x + m[1] * y) + m[2] for x, y in zip(xs, ys)]
+        Y = [(m[3] * x + m[4] * y) + m[5] for x, y in zip(xs, ys)]
+        finite = np.ones(bx.shape[0], bool)
+        for v in X + Y:
+            finite &= np.isfinite(v)
+
+        def fold(vals, better):                                        # min(p, q) = q < p ? q : p (max: >), folded from the left
+            acc = vals[0]
+            for q in vals[1:]:
+                acc = np.where(better(q, acc), q, acc)
+            return acc
+
+        X1, X2, Y1, Y2 = fold(X, np.less), fold(X, np.greater), fold(Y, np.less), fold(Y, np.greater)
+        clamp = lambda v, top: np.where(v < f32(0), f32(0), np.where(v > f32(top), f32(top), v)).astype(f32)
+        out = np.stack([clamp(X1, w), clamp(Y1, h), clamp(X2, w), clamp(Y2, h)], 1).astype(f32)
+        au = (X2 - X1) * (Y2 - Y1)
+        cw, ch = out[:, 2] - out[:, 0], out[:, 3] - out[:, 1]
+        keep = finite & (cw > 0) & (ch > 0) & (cw * ch >= f32(min_visibility) * au)
+    return out, keep
+
+
+class ShiftScaleRotate:
+    """With probability ``p`` move each training image by a random shift, scale and rotation about its centre (bilinear
+    interpolation, reflect-101 border) and take its boxes along: albumentations' ``ShiftScaleRotate`` in intent, with its argument
+    meanings and defaults -- a scalar limit v is the range (-v, v), a pair is taken as given; the angle is in degrees, the scale is drawn
+    from ``1 + scale_limit`` (which must stay > 0: ``ValueError``) and the two shifts, fractions of the width and the height, both from
+    ``shift_limit``.  A box becomes the bounding box of its four moved corners, clipped to the image; it is dropped when nothing of it
+    is left or when less than ``min_visibility`` of its area is.  It is NOT bit-compatible with albumentations (OpenCV's ``warpAffine``
+    uses fixed-point weights, albumentations' box code depends on its version): ``draw_coefs``, ``warp_boxes`` and ``warp_image``
+    restate the numbered rule of ``rn_affine_draw`` / ``rn_image_warp_stage`` in ``include/retinanet_hip.h``, and that rule is the
+    definition.  One deviation is stated there: an image whose boxes would ALL be dropped is left alone, so no image loses all of
+    its GT.  Other interpolations and border modes are not implemented.
+
+    Install it as ``net.transform.shift_scale_rotate``; it acts only in training mode and only when targets are given, after the crop
+    and before the flip, the colour jitter and the resize.  On staged images with packed GT
+    (``graph.CapturedTrainStep(image_capacity=..., gt_capacity=...)``) the matrices are drawn on the device (``rn_affine_draw``, which
+    also packs the surviving rows), and each image is warped into a second arena (``rn_image_warp_stage``), inside the captured step,
+    each replay a new draw.  Every other input (CPU tensors, CUDA lists) takes the same stream of draws from the restatement on the
+    HOST: the boxes and the counter are read back, which on CUDA is one synchronisation per step; double-precision ``sin`` / ``cos``
+    may differ between host and device in the last bit, so the two paths agree to an fp32 step of a matrix entry, not always bit
+    for bit.  Not an ``nn.Module``: it adds no key to the model's state dict.  ``seed``: the stream of draws (``SimpleTrainer`` adds
+    the rank under ``torch.distributed``)."""
+
+    def __init__(self, shift_limit=0.0625, scale_limit=0.1, rotate_limit=45, p: float = 0.5, min_visibility: float = 0.0, seed: int = 0):
+        self.base_seed = int(seed) & _M64
+        self._p, self._seed, self._counter = RandomHorizontalFlip._check_p(p), self.base_seed, 0
+        self._set_ranges(shift_limit, scale_limit, rotate_limit, min_visibility)
+        self._block: Optional[Tensor] = None          # rn_affine_state on the device of the first CUDA batch (kept for good)
+        self.coef: Optional[Tensor] = None            # the last device batch's rn_affine_coef (int32 [B, 16]; AffineCoefs.from_device)
+        self.coefs: Optional[AffineCoefs] = None      # the last host-drawn batch's coefficients
+
+    def _set_ranges(self, shift_limit, scale_limit, rotate_limit, min_visibility) -> None:
+        shift, scale, angle = _limit(shift_limit, "shift_limit"), _limit(scale_limit, "scale_limit", 1.0), _limit(rotate_limit, "rotate_limit")
+        if not scale[0] > 0.0:
+            raise ValueError(f"1 + scale_limit must stay > 0, got the scale range {scale}")
+        mv = float(min_visibility)
+        if not 0.0 <= mv <= 1.0:
+            raise ValueError(f"min_visibility must be in [0, 1], got {min_visibility}")
+        self.shift_limit, self.scale_range, self.rotate_limit, self.min_visibility = shift, scale, angle, float(np.float32(mv))
+
+    @property
+    def ranges(self) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
+        "(lo, hi) of (angle, scale, dx, dy): what the device block holds."
+        r = (self.rotate_limit, self.scale_range, self.shift_limit, self.shift_limit)
+        return tuple(v[0] for v in r), tuple(v[1] for v in r)
+
+    def __repr__(self) -> str:
+        return (f"ShiftScaleRotate(shift_limit={self.shift_limit}, scale_limit={tuple(float(np.float32(v - 1.0)) for v in self.scale_range)}, "
+                f"rotate_limit={self.rotate_limit}, p={self._p}, min_visibility={self.min_visibility}, seed={self._seed})")
+
+    # -- the restatement ------------------------------------------------------------------------------------------------
+    @staticmethod
+    def draw_coefs(seed: int, counter: int, in_hw: Sequence[Tuple[int, int]], boxes_per_image, p: float, lo: Sequence[float],
+                   hi: Sequence[float], min_visibility: float = 0.0) -> AffineCoefs:
+        """Restatement of ``rn_affine_draw``'s steps 1 and 2 (and the all-dropped rule of step 3): the draws in fp32, the matrices in
+        float64 numpy rounded to fp32 once.  ``lo`` / ``hi``: the ranges of (angle, scale, dx, dy).  ``boxes_per_image[b]``: image b's
+        boxes, anything ``numpy.asarray`` turns into fp32 [T, 4] (None or empty for no boxes)."""
+        seed, counter, f32, f64 = int(seed) & _M64, int(counter), np.float32, np.float64
+        p32 = f32(p)
+        ms, invs, flags = [], [], []
+        for b, (h, w) in enumerate(in_hw):
+            h, w = int(h), int(w)
+            applied = f32(hflip_u(seed ^ AFFINE_SALT_APPLY, counter, b)) < p32
+            angle, scale, dx, dy = (f32(lo[k]) + f32(hflip_u(seed ^ salt, counter, b)) * (f32(hi[k]) - f32(lo[k]))
+                                    for k, salt in enumerate((AFFINE_SALT_ANGLE, AFFINE_SALT_SCALE, AFFINE_SALT_DX, AFFINE_SALT_DY)))
+            with np.errstate(all="ignore"):
+                t = f64(angle) * f64(np.pi) / f64(180.0)
+                ca, sb = f64(scale) * np.cos(t), f64(scale) * np.sin(t)
+                cx, cy = (f64(w) - 1.0) / 2.0, (f64(h) - 1.0) / 2.0
+                tx, ty = ((1.0 - ca) * cx - sb * cy) + f64(dx) * f64(w), (sb * cx + (1.0 - ca) * cy) + f64(dy) * f64(h)
+                det = ca * ca + sb * sb
+                i00, i01, i10, i11 = ca / det, -sb / det, sb / det, ca / det
+                m = np.array([ca, sb, tx, -sb, ca, ty], f64).astype(f32)
+                inv = np.array([i00, i01, -(i00 * tx + i01 * ty), i10, i11, -(i10 * tx + i11 * ty)], f64).astype(f32)
+            ok = bool(applied) and h >= 1 and w >= 1 and bool(det >= AFFINE_MIN_DET) and bool(np.isfinite(m).all() and np.isfinite(inv).all())
+            if ok:
+                bx = _boxes_f32(boxes_per_image[b] if boxes_per_image is not None else None)
+                if bx.shape[0] > 0 and not _warp_rows(m, h, w, min_visibility, bx)[1].any():
+                    ok = False                                         # (no image loses all of its GT)
+            if not ok:
+                m, inv = np.array(_IDENTITY6, f32), np.array(_IDENTITY6, f32)
+            ms.append(m), invs.append(inv), flags.append(ok)
+        return AffineCoefs(np.stack(ms) if ms else np.zeros((0, 6), f32), np.stack(invs) if invs else np.zeros((0, 6), f32), flags)
+
+    @staticmethod
+    def warp_boxes(coefs: AffineCoefs, in_hw: Sequence[Tuple[int, int]], boxes_per_image, labels_per_image=None,
+                   min_visibility: float = 0.0):
+        """Restatement of steps 3 and 4 for given coefficients: per image (boxes fp32 tensor [T', 4], labels tensor [T'] or None) --
+        the kept rows in order, moved and clipped; an image with ``applied`` false keeps its rows bit for bit."""
+        out = []
+        for b, (h, w) in enumerate(in_hw):
+            bx = _boxes_f32(boxes_per_image[b])
+            lb = None if labels_per_image is None else labels_per_image[b]
+            if coefs.applied[b] and bx.shape[0] > 0:
+                moved, keep = _warp_rows(coefs.m[b], int(h), int(w), min_visibility, bx)
+                bx = moved[keep]
+                if lb is not None:
+                    lb = lb[torch.from_numpy(keep).to(lb.device)] if isinstance(lb, Tensor) else np.asarray(lb)[keep]
+            out.append((torch.from_numpy(np.ascontiguousarray(bx)), lb))
+        return out
+
+    @staticmethod
+    def warp_image(img: Tensor, inv: Sequence[float], applied: bool = True) -> Tensor:
+        """Restatement of step 5 on a [3, h, w] fp32 tensor (CPU or CUDA) out of torch elementwise operations in the kernel's order, one
+        rounding each: the image gathered through ``inv`` = (i00, i01, i02, i10, i11, i12), bilinear, reflect-101.  ``applied`` false:
+        the image itself."""
+        if not applied:
+            return img
+        h, w = int(img.shape[-2]), int(img.shape[-1])
+        i = [torch.tensor(float(np.float32(v)), dtype=torch.float32, device=img.device) for v in inv]
+        ys = torch.arange(h, dtype=torch.float32, device=img.device).reshape(h, 1)
+        xs = torch.arange(w, dtype=torch.float32, device=img.device).reshape(1, w)
+        big = torch.tensor(2.0 ** 30, dtype=torch.float32, device=img.device)
+
+        def sat(s):
+            s = torch.where(s >= -big, s, -big)
+            return torch.where(s <= big, s, big)
+
+        def reflect(idx, n):
+            if n == 1:
+                return torch.zeros_like(idx)
+            period = 2 * (n - 1)
+            t = torch.remainder(idx, period)
+            return torch.where(t < n, t, period - t)
+
+        sx, sy = sat((i[0] * xs + i[1] * ys) + i[2]), sat((i[3] * xs + i[4] * ys) + i[5])
+        flx, fly = torch.floor(sx), torch.floor(sy)
+        fx, fy = sx - flx, sy - fly
+        x0, y0 = flx.to(torch.int64), fly.to(torch.int64)
+        xa, xb, ya, yb = reflect(x0, w), reflect(x0 + 1, w), reflect(y0, h), reflect(y0 + 1, h)
+        flat = img.reshape(img.shape[0], h * w)
+        p00, p01, p10, p11 = (flat[:, (yy * w + xx).reshape(-1)].reshape(img.shape) for yy, xx in ((ya, xa), (ya, xb), (yb, xa), (yb, xb)))
+        gx, gy = 1.0 - fx, 1.0 - fy
+        return (p00 * gx + p01 * fx) * gy + (p10 * gx + p11 * fx) * fy
+
+    def draw(self, counter: int, in_hw: Sequence[Tuple[int, int]], boxes_per_image) -> AffineCoefs:
+        "The coefficients this object draws at ``counter`` for images of sizes ``in_hw`` with these boxes (no state change)."
+        lo, hi = self.ranges
+        return self.draw_coefs(self._seed, counter, in_hw, boxes_per_image, self._p, lo, hi, self.min_visibility)
+
+    def next_coefs(self, in_hw: Sequence[Tuple[int, int]], boxes_per_image) -> AffineCoefs:
+        """The next batch's coefficients on the HOST, and the counter advanced by one: what CPU tensors and CUDA lists use.  The boxes
+        are read on the host (CUDA tensors are copied back: a synchronisation) and, with a device block, so is the counter; not
+        inside a capture."""
+        n = self.counter
+        self.coefs = self.draw(n, in_hw, [_boxes_f32(b) for b in boxes_per_image])
+        self._counter = n + 1
+        if self._block is not None:
+            from . import ops
+            ops.affine_state_write(self._block, counter=n + 1)
+        return self.coefs
+
+    def device_block(self, device: torch.device) -> Tensor:
+        """The ``rn_affine_state`` block on ``device`` that ``ops.shift_scale_rotate_staged`` draws from, created at the first call
+        (which must not be inside a capture) and kept for good: a captured step holds its address."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ShiftScaleRotate: the device draw runs on the GPU; CPU batches use next_coefs()")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._block is None:
+            from . import ops
+            lo, hi = self.ranges
+            self._block = ops.affine_state(device, self._seed, self._counter, self._p, self.min_visibility, lo, hi)
+        elif self._block.device != device:
+            raise RuntimeError(f"ShiftScaleRotate: its state lives on {self._block.device}, not {device}; use one object per device")
+        return self._block
+
+    # -- settings and state ---------------------------------------------------------------------------------------------
+    @property
+    def p(self) -> float:
+        return self._p
+
+    @p.setter
+    def p(self, value: float) -> None:
+        "A new probability: written into the device block (no re-capture needed; not inside a capture)."
+        self._p = RandomHorizontalFlip._check_p(value)
+        if self._block is not None:
+            from . import ops
+            ops.affine_state_write(self._block, p=self._p)
+
+    def set_limits(self, shift_limit=None, scale_limit=None, rotate_limit=None, min_visibility=None) -> None:
+        "New ranges (the ones not given stay): written into the device block (no re-capture needed; not inside a capture)."
+        scale_now = tuple(float(np.float32(v - 1.0)) for v in self.scale_range)
+        self._set_ranges(self.shift_limit if shift_limit is None else shift_limit, scale_now if scale_limit is None else scale_limit,
+                         self.rotate_limit if rotate_limit is None else rotate_limit,
+                         self.min_visibility if min_visibility is None else min_visibility)
+        if self._block is not None:
+            from . import ops
+            lo, hi = self.ranges
+            ops.affine_state_write(self._block, min_visibility=self.min_visibility, lo=lo, hi=hi)
+
+    @property
+    def seed(self) -> int:
+        return self._seed
+
+    def reseed(self, seed: int, counter: int = 0) -> None:
+        "Start a new stream of draws (seed, counter); not inside a capture."
+        self._seed, self._counter = int(seed) & _M64, int(counter)
+        if self._block is not None:
+            from . import ops
+            ops.affine_state_write(self._block, seed=self._seed, counter=self._counter)
+
+    def set_rank(self, rank: int) -> None:
+        "One stream per data-parallel rank: seed = ``base_seed`` (the constructor's) + rank, the counter kept."
+        self.reseed((self.base_seed + int(rank)) & _M64, self.counter)
+
+    @property
+    def counter(self) -> int:
+        "Batches drawn so far (with the device block: one read-back, i.e. a synchronisation)."
+        if self._block is not None:
+            from . import ops
+            return int(ops.affine_state_read(self._block)[1])
+        return self._counter
+
+    def state_dict(self) -> Dict[str, object]:
+        return {"seed": self._seed, "counter": self.counter, "p": self._p}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.p = state["p"]
+        self.reseed(int(state["seed"]), int(state["counter"]))
+
+
+_SHIFT_SCALE_ROTATE_NAMES = ("albumentations.ShiftScaleRotate", "ShiftScaleRotate")
+# (parameter, the values that mean albumentations' default): cv2.INTER_LINEAR = 1, cv2.BORDER_REFLECT_101 = 4
+_SSR_FIXED = (("interpolation", (None, 1, "cv2.INTER_LINEAR")), ("border_mode", (None, 4, "cv2.BORDER_REFLECT_101")), ("value", (None,)), ("shift_limit_x", (None,)), ("shift_limit_y", (None,)))
+
+
+def shift_scale_rotate_from_transforms(entries, seed: int = 0, log=None) -> Optional[ShiftScaleRotate]:
+    """The shift / scale / rotate an hparams ``transforms`` list asks for, or None.  ``albumentations.ShiftScaleRotate`` and a bare
+    ``ShiftScaleRotate`` (``shift_limit`` 0.0625, ``scale_limit`` 0.1, ``rotate_limit`` 45, ``p`` 0.5: albumentations' defaults;
+    ``always_apply: true`` means p = 1) map onto ``ShiftScaleRotate``, which is bilinear with the reflect-101 border and not
+    bit-compatible with albumentations.  A non-default ``interpolation``, ``border_mode``, ``value``, ``shift_limit_x`` or
+    ``shift_limit_y`` is warned about and ignored; a second entry is skipped with a warning."""
+    import logging
+    log = log or logging.getLogger(__name__)
+    found = None
+    for e in entries or []:
+        name = str(e.get("class_name", "")) if isinstance(e, dict) else str(e)
+        params = dict(e.get("params") or {}) if isinstance(e, dict) else {}
+        if name not in _SHIFT_SCALE_ROTATE_NAMES:
+            continue
+        if found is not None:
+            log.warning("transforms: a second shift / scale / rotate (%s) is skipped", name)
+            continue
+        for key, defaults in _SSR_FIXED:
+            if params.get(key) not in defaults:
+                log.warning("transforms: %s %s=%s is not implemented and is ignored (bilinear interpolation, the reflect-101 border and "
+                            "one shift_limit for both axes are)", name, key, params.get(key))
+        as_limit = lambda v: tuple(v) if isinstance(v, (list, tuple)) else v
+        p = 1.0 if params.get("always_apply") else float(params.get("p", 0.5))
+        found = ShiftScaleRotate(shift_limit=as_limit(params.get("shift_limit", 0.0625)), scale_limit=as_limit(params.get("scale_limit", 0.1)),
+                                 rotate_limit=as_limit(params.get("rotate_limit", 45)), p=p, seed=seed)
+    return found
+
+
 _COLOR_JITTER_NAMES = ("albumentations.ColorJitter", "torchvision.transforms.ColorJitter", "ColorJitter")
 
 
@@ -833,11 +1166,11 @@ def from_transforms(entries, seed: int = 0, log=None) -> Optional[RandomHorizont
             p = 1.0 if params.get("always_apply") else float(params.get("p", 0.5))
         elif short == "RandomHorizontalFlip":
             p = float(params.get("prob", params.get("p", 0.5)))
-        elif name in _COLOR_JITTER_NAMES or name in _BBOX_CROP_NAMES:      # color_jitter_ / bbox_crop_from_transforms map these
-            continue
+        elif name in _COLOR_JITTER_NAMES or name in _BBOX_CROP_NAMES or name in _SHIFT_SCALE_ROTATE_NAMES:
+            continue                                   # color_jitter_ / bbox_crop_ / shift_scale_rotate_from_transforms map these
         else:
-            log.warning("transforms: %s is not supported (albumentations is not available; only the horizontal flip, ColorJitter and "
-                        "BBoxSafeRandomCrop are implemented, on the GPU): skipped", name)
+            log.warning("transforms: %s is not supported (albumentations is not available; only the horizontal flip, ColorJitter, "
+                        "BBoxSafeRandomCrop and ShiftScaleRotate are implemented, on the GPU): skipped", name)
             continue
         if found is not None:
             log.warning("transforms: a second horizontal flip (%s) is skipped", name)

@@ -79,19 +79,11 @@
 // of a wave still coalesce -- and writes them as one 16-byte store when the destination slot is 16-byte aligned.
 #include "rn_color.hpp"
 #include "rn_common.hpp"
+#include "rn_draw.hpp"              // hflip_u: the hash stated above, shared with affine.hip
 
 namespace {
 
 constexpr int HF_BLOCK = 64;        // one wave: the counter update needs no barrier across waves
-
-__device__ __forceinline__ float hflip_u(const uint64_t seed, const int64_t counter, const int b)
-{
-    uint64_t z = seed ^ ((uint64_t)counter * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(b + 1) * 0xD1B54A32D192ED03ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(uint32_t)(z >> 40) * 0x1p-24f;
-}
 
 __global__ __launch_bounds__(HF_BLOCK) void hflip_draw_kernel(rn_hflip_state *st, const int B, uint8_t *__restrict__ flags)
 {

@@ -50,6 +50,11 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     the image capacity mode (a ``ValueError`` says so): the rectangles are drawn inside the step from the staged GT and the windows
     copied into a second arena, so one graph replays while the crops vary and p may change between replays.  A batch no class holds
     runs eagerly with the crop drawn on the host.
+    Shift / scale / rotate (``net.transform.shift_scale_rotate``, ``augment.ShiftScaleRotate``) is keyed by the installed object too,
+    and needs both capacity modes (a ``ValueError`` says so): the matrices are drawn inside the step, the rows that survive are
+    packed on the device -- the GT counts change from replay to replay, which only packed GT can hold -- and the images are warped
+    into another arena, so one graph replays while the draws vary; p and the ranges may change between replays.  A batch no class
+    holds runs eagerly with the draw on the host.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -546,7 +551,12 @@ class CapturedTrainStep:
         # the bbox-safe random crop (transform.crop): the rectangles are drawn inside the step from the object's device block and the
         # staged GT, and the canvas class follows from the image shapes (``crop.bound``) -- the object again.  Without one nothing is added.
         crop = getattr(getattr(self.net, "transform", None), "crop", None)
-        return key if crop is None else key + (("crop", crop),)
+        if crop is not None:
+            key = key + (("crop", crop),)
+        # shift / scale / rotate (transform.shift_scale_rotate): matrices, surviving rows and warped images all come from the object's
+        # device block inside the step -- the object again.  Without one nothing is added.
+        ssr = getattr(getattr(self.net, "transform", None), "shift_scale_rotate", None)
+        return key if ssr is None else key + (("shift_scale_rotate", ssr),)
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."
@@ -651,6 +661,11 @@ class CapturedTrainStep:
         final = bool(final)
         if not self.enabled or not images or not images[0].is_cuda:
             return self._step(images, targets, final)
+        ssr = getattr(getattr(self.net, "transform", None), "shift_scale_rotate", None)
+        if ssr is not None and (self.image_capacity is None or self.gt_capacity is None):
+            raise ValueError("a shift / scale / rotate (net.transform.shift_scale_rotate) warps every image and drops boxes from step to "
+                             "step: CapturedTrainStep needs gt_capacity= and image_capacity= for it -- the staged path draws and applies "
+                             "it on the device; without them call the net directly (it is then drawn on the host)")
         cap = self._capacity_of(targets)
         icls = self._image_class_of(images, targets, cap)          # (once per step: the key, the arena and the transform's bounds)
         if getattr(getattr(self.net, "transform", None), "crop", None) is not None:
@@ -660,6 +675,10 @@ class CapturedTrainStep:
                                  "the device; without them call the net directly (the crop is then drawn on the host)")
             if icls is None:
                 # a batch no class holds: the crop is drawn on the host there (a synchronisation), which no capture can contain
+                return self._step(images, targets, final)
+        if ssr is not None:
+            if icls is None or cap is None:
+                # a batch no class holds: drawn on the host there (a synchronisation), which no capture can contain
                 return self._step(images, targets, final)
         key = self._signature(images, targets, cap, icls)
         dev = images[0].device

@@ -88,7 +88,7 @@ class RetinaNetModel(_Base):
             self.val_ds = SyntheticDetectionDataset(**{**kw, "seed": kw.get("seed", 0) + 1})
             self.test_ds = SyntheticDetectionDataset(**{**kw, "seed": kw.get("seed", 0) + 2})
         elif d.kind == "csv":             # README.md:103-125: trn_paths / val_paths (optional) / test_paths are csv files
-            from .augment import bbox_crop_from_transforms, color_jitter_from_transforms, from_transforms
+            from .augment import bbox_crop_from_transforms, color_jitter_from_transforms, from_transforms, shift_scale_rotate_from_transforms
             from .datasets import CSVDetectionDataset
             # the training set's transforms (reference model.py:51-52, hparams.yaml:55-58): the horizontal flip runs on the GPU,
             # inside the model's transform (augment.RandomHorizontalFlip); validation / test never flip (eval mode, no targets)
@@ -97,6 +97,8 @@ class RetinaNetModel(_Base):
             self.net.transform.color_jitter = color_jitter_from_transforms(self.conf.get("transforms"))
             # an albumentations.BBoxSafeRandomCrop entry becomes the transform's bbox-safe random crop (augment.BBoxSafeRandomCrop)
             self.net.transform.crop = bbox_crop_from_transforms(self.conf.get("transforms"))
+            # an albumentations.ShiftScaleRotate entry becomes the transform's shift / scale / rotate (augment.ShiftScaleRotate)
+            self.net.transform.shift_scale_rotate = shift_scale_rotate_from_transforms(self.conf.get("transforms"))
             self.trn_ds = CSVDetectionDataset(d.trn_paths)
             self.val_ds = CSVDetectionDataset(d.val_paths) if d.get("val_paths") else None
             self.test_ds = CSVDetectionDataset(d.test_paths) if d.get("test_paths") else None
@@ -435,6 +437,9 @@ class SimpleTrainer:
         crop = getattr(model.net.transform, "crop", None)
         if crop is not None and ddp is not None:
             crop.set_rank(dist.get_rank())                # seed = base seed + rank: each rank draws its own windows
+        ssr = getattr(model.net.transform, "shift_scale_rotate", None)
+        if ssr is not None and ddp is not None:
+            ssr.set_rank(dist.get_rank())                 # seed = base seed + rank: each rank draws its own matrices
         self._install_scale_jitter(model, dist.get_rank() if ddp is not None else None)
         # precision "16" = fp16 autocast WITH dynamic loss scaling, like the reference's native-AMP run (Lightning precision=16):
         # fp16 gradients of a focal loss normalised by num_fg underflow without it

@@ -214,6 +214,10 @@ class PackedGT:
     def with_boxes(self, gt_boxes: Tensor) -> "PackedGT":
         return PackedGT(gt_boxes, self.gt_labels, self.gt_off, self.num_fg, self.cap_per_image)
 
+    def with_rows(self, gt_boxes: Tensor, gt_labels: Tensor, gt_off: Tensor) -> "PackedGT":
+        "New boxes, labels and offsets (an augmentation that drops rows) sharing ``num_fg``: no more rows per image than before."
+        return PackedGT(gt_boxes, gt_labels, gt_off, self.num_fg, self.cap_per_image)
+
 
 def gt_stage(boxes: Sequence[Tensor], labels: Sequence[Tensor], out: PackedGT) -> PackedGT:
     """The per-image GT (``boxes[b]`` [T_b, 4], ``labels[b]`` [T_b]) into ``out``'s buffers, ``gt_off`` = prefix of the counts,
@@ -1138,6 +1142,120 @@ def bbox_crop_staged(crop, staged: StagedImages, packed: PackedGT) -> Tuple[Stag
     rect, crop_hw, boxes = bbox_crop_draw(crop.device_block(staged.device), staged.in_hw, packed)
     crop.rect = rect
     return image_crop_stage(staged, rect, crop_hw), packed.with_boxes(boxes)
+
+
+# ---- train-time shift / scale / rotate (augment.ShiftScaleRotate): a second staging pass --------------------------------------
+# include/retinanet_hip.h: rn_affine_state = seed u64, counter i64, p f32, min_visibility f32, lo f32[4], hi f32[4] with the ranges
+# of (angle, scale, dx, dy); rn_affine_coef = m f32[6], inv f32[6], applied i32, kept i32, reserved i32[2]
+AFFINE_STATE_BYTES = 56
+AFFINE_COEF_WORDS = 16
+
+
+def _check_affine_block(block: Tensor) -> torch.device:
+    dev = _need_dev(block)
+    if block.dtype != torch.uint8 or block.numel() != AFFINE_STATE_BYTES or block.data_ptr() % 8:
+        raise ValueError("block must be an rn_affine_state made by affine_state()")
+    return dev
+
+
+def affine_state(dev: torch.device, seed: int, counter: int, p: float, min_visibility: float, lo: Sequence[float],
+                 hi: Sequence[float]) -> Tensor:
+    "A new ``rn_affine_state`` block (uint8 [56]) on ``dev``: one host->device copy, outside any capture."
+    block = torch.empty((AFFINE_STATE_BYTES,), dtype=torch.uint8, device=dev)
+    affine_state_write(block, seed=seed, counter=counter, p=p, min_visibility=min_visibility, lo=lo, hi=hi)
+    return block
+
+
+def affine_state_write(block: Tensor, seed: Optional[int] = None, counter: Optional[int] = None, p: Optional[float] = None,
+                       min_visibility: Optional[float] = None, lo: Optional[Sequence[float]] = None,
+                       hi: Optional[Sequence[float]] = None) -> None:
+    """Overwrite the given fields of an ``rn_affine_state`` block (the others keep their device values): host->device copies on the
+    current stream, ordered with the draws around them.  Not inside a capture: the values would be baked into the graph."""
+    _check_affine_block(block)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("affine_state_write inside a stream capture")
+    parts = []
+    if seed is not None:
+        parts.append((0, struct.pack("<Q", int(seed) & (2 ** 64 - 1))))
+    if counter is not None:
+        parts.append((8, struct.pack("<q", int(counter))))
+    if p is not None:
+        parts.append((16, struct.pack("<f", float(p))))
+    if min_visibility is not None:
+        parts.append((20, struct.pack("<f", float(min_visibility))))
+    if lo is not None:
+        parts.append((24, struct.pack("<4f", *[float(v) for v in lo])))
+    if hi is not None:
+        parts.append((40, struct.pack("<4f", *[float(v) for v in hi])))
+    for off, raw in parts:
+        block[off:off + len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+
+
+def affine_state_read(block: Tensor) -> Tuple[int, int, float, float, Tuple[float, ...], Tuple[float, ...]]:
+    "(seed, counter, p, min_visibility, lo, hi) of an ``rn_affine_state`` block: one device->host copy (synchronises)."
+    _check_affine_block(block)
+    v = struct.unpack("<Qqff4f4f", bytes(block.cpu().numpy().tobytes()))
+    return v[0], v[1], v[2], v[3], tuple(v[4:8]), tuple(v[8:12])
+
+
+def affine_coef_views(coef: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    "(m f32 [B, 6], inv f32 [B, 6], applied i32 [B], kept i32 [B]): views of an ``rn_affine_coef`` tensor (int32 [B, 16])."
+    return coef[:, 0:6].view(torch.float32), coef[:, 6:12].view(torch.float32), coef[:, 12], coef[:, 13]
+
+
+def affine_draw(block: Tensor, in_hw: Tensor, gt: PackedGT) -> Tuple[Tensor, PackedGT]:
+    """``rn_affine_draw``: per image the matrices drawn from the block, and the rows of ``gt`` that survive them, packed ->
+    (coef int32 [B, 16] = ``rn_affine_coef`` per image, read it through ``affine_coef_views``; a ``PackedGT`` of fresh boxes, labels
+    and offsets that shares ``gt.num_fg``; rows past its ``gt_off[B]`` are unwritten), then the block's counter advances by one.
+    ``in_hw``: int32 [B, 2] on the device (``StagedImages.in_hw``).  Three launches on the current stream, no atomics, no host
+    synchronisation (capturable: each replay draws anew)."""
+    dev = _need_dev(block, in_hw, gt.gt_boxes, gt.gt_labels, gt.gt_off)
+    _check_affine_block(block)
+    if in_hw.dtype != torch.int32 or tuple(in_hw.shape) != (gt.B, 2) or not in_hw.is_contiguous():
+        raise ValueError(f"in_hw must be a contiguous int32 [{gt.B}, 2] tensor, got {tuple(in_hw.shape)} {in_hw.dtype}")
+    if gt.gt_boxes.dtype != torch.float32 or not gt.gt_boxes.is_contiguous() or gt.gt_boxes.data_ptr() % 16:
+        raise ValueError("packed GT boxes must be a contiguous, 16-byte aligned f32 [rows, 4] tensor")
+    if gt.gt_labels.dtype != torch.int64 or not gt.gt_labels.is_contiguous() or gt.gt_labels.numel() != gt.rows:
+        raise ValueError(f"packed GT labels must be a contiguous int64 [{gt.rows}] tensor")
+    coef = torch.empty((gt.B, AFFINE_COEF_WORDS), dtype=torch.int32, device=dev)
+    out = gt.with_rows(torch.empty_like(gt.gt_boxes), torch.empty_like(gt.gt_labels), torch.empty_like(gt.gt_off))
+    with torch.cuda.device(dev), _timed("affine_draw", dev):
+        check(lib.rn_affine_draw(_ptr(block), _ptr(gt.gt_boxes), _ptr(gt.gt_labels), _ptr(gt.gt_off), _ptr(in_hw), gt.B, _ptr(coef),
+                                 _ptr(out.gt_boxes), _ptr(out.gt_labels), _ptr(out.gt_off), gt.rows, _stream(dev)), "rn_affine_draw")
+    return coef, out
+
+
+def image_warp_stage(staged: StagedImages, coef: Tensor, out: Optional[StagedImages] = None) -> StagedImages:
+    """``rn_image_warp_stage``: image b of ``staged`` gathered through ``coef[b]``'s inverse matrix (bilinear, reflect-101) into slot b
+    of a second arena with the same sizes -- ``staged.in_hw`` itself is kept, not copied; an image whose ``applied`` is 0 is copied
+    bit for bit.  ``out``: an arena to write into (its ``in_hw`` is ignored), else one with ``staged``'s slot is allocated here.  The
+    host-side ``hw``, ``bounds`` and ``canvas`` are carried over.  One launch on the current stream, a fixed grid, no host
+    synchronisation (capturable)."""
+    dev = _need_dev(staged.arena, staged.in_hw, coef)
+    B = staged.B
+    if coef.dtype != torch.int32 or tuple(coef.shape) != (B, AFFINE_COEF_WORDS) or not coef.is_contiguous():
+        raise ValueError(f"coef must be a contiguous int32 [{B}, {AFFINE_COEF_WORDS}] tensor (rn_affine_coef per image), got "
+                         f"{tuple(coef.shape)} {coef.dtype}")
+    arena = torch.empty_like(staged.arena) if out is None else out.arena
+    if arena.device != dev or arena.shape[0] != B or arena.data_ptr() == staged.arena.data_ptr():
+        raise ValueError(f"the output arena must be another arena of {B} slots on {dev}")
+    res = StagedImages(arena, staged.in_hw, staged.canvas)
+    with torch.cuda.device(dev), _timed("image_warp_stage", dev):
+        check(lib.rn_image_warp_stage(_ptr(staged.arena), staged.slot, _ptr(staged.in_hw), _ptr(coef), B, _ptr(arena), res.slot,
+                                      _stream(dev)), "rn_image_warp_stage")
+    res.hw, res.bounds = list(staged.hw), (None if staged.bounds is None else list(staged.bounds))
+    return res
+
+
+def shift_scale_rotate_staged(ssr, staged: StagedImages, packed: PackedGT) -> Tuple[StagedImages, PackedGT]:
+    """The shift / scale / rotate of a staged batch (``ssr``: an ``augment.ShiftScaleRotate``): ``affine_draw`` from the object's device
+    block, then ``image_warp_stage`` into an arena allocated here, like the other intermediates of a step -> (the warped
+    ``StagedImages``, the ``PackedGT`` of the rows that survive).  The coefficients stay on the device as ``ssr.coef``."""
+    if packed.B != staged.B:
+        raise ValueError(f"packed GT of {packed.B} images for an arena of {staged.B}")
+    coef, gt = affine_draw(ssr.device_block(staged.device), staged.in_hw, packed)
+    ssr.coef = coef
+    return image_warp_stage(staged, coef), gt
 
 
 def decode_clip(deltas: Tensor, anchors: Tensor, image_hw: Optional[Tensor],

@@ -61,6 +61,15 @@ cropped sizes next to it), so everything after it runs unchanged and is bit-iden
 follows from ``crop.bound`` (the crop keeps the orientation), so ``staged_bounds`` depends on the image shapes alone.  Every other input
 draws the same rectangles on the HOST from the Python restatement -- the boxes and the counter are read back, one synchronisation on
 CUDA -- slices the images and shifts the boxes with torch, and goes on as without a crop.  ``crop`` is a plain attribute too.
+
+Train-time shift / scale / rotate (``shift_scale_rotate``: an ``augment.ShiftScaleRotate``, None by default): in training mode and when
+targets are given, each image is moved with probability p by a random shift, scale and rotation about its centre (bilinear, reflect-101
+border), its boxes become the clipped bounding boxes of their moved corners, and boxes of which nothing (or less than
+``min_visibility``) is left are dropped -- AFTER the crop and before the flip, the colour jitter and the resize.  Sizes do not change, so
+``staged_bounds`` is untouched.  On staged images with packed GT it is one more staging pass on the device
+(``ops.shift_scale_rotate_staged``: ``rn_affine_draw`` + ``rn_image_warp_stage`` into another arena, the surviving rows packed into new
+buffers with new offsets), bit-identical to the same call on images and targets pre-warped by the restatement with the device's
+coefficients.  Every other input draws from the Python restatement on the HOST (one synchronisation on CUDA) and warps with torch ops.
 """
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -149,6 +158,7 @@ class GeneralizedRCNNTransform(nn.Module):
         self.scale_jitter = None      # augment.RandomShortSide: the short side drawn on the device (module docstring)
         self.color_jitter = None      # augment.ColorJitter: the colour jitter drawn and applied on the device (module docstring)
         self.crop = None              # augment.BBoxSafeRandomCrop: the bbox-safe random crop, before everything else (module docstring)
+        self.shift_scale_rotate = None    # augment.ShiftScaleRotate: shift / scale / rotate, after the crop (module docstring)
 
     # -- pieces ------------------------------------------------------------------------
     def normalize(self, image: Tensor) -> Tensor:
@@ -362,6 +372,10 @@ class GeneralizedRCNNTransform(nn.Module):
         if crop is not None:
             # a second staging pass: from here on ``staged`` is the arena of the windows and its sizes are the cropped ones
             staged, targets = ops.bbox_crop_staged(crop, staged, targets)
+        ssr = getattr(self, "shift_scale_rotate", None)
+        if ssr is not None:
+            # one more staging pass: the warped images at the same sizes, and the packed GT of the rows that survive
+            staged, targets = ops.shift_scale_rotate_staged(ssr, staged, targets)
         flags = self.hflip.next_flags(staged.B, staged.device) if self.hflip is not None else None
         coef = self._color(staged, targets)
         jitter = self.scale_jitter
@@ -403,6 +417,40 @@ class GeneralizedRCNNTransform(nn.Module):
             t["boxes"] = bx
         return images, targets
 
+    def _shift_scale_rotate_on_host(self, images: List[Tensor], targets):
+        """The installed ``shift_scale_rotate`` for images that are not staged: the coefficients from the Python restatement
+        (``next_coefs`` reads the boxes and the counter on the host: one synchronisation on CUDA), the images warped with torch ops
+        (``warp_image``) and the rows moved, clipped and dropped by ``warp_boxes`` -- for target dicts and packed GT alike."""
+        ssr = self.shift_scale_rotate
+        in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
+        packed = _is_packed(targets)
+        if packed:
+            off = [int(v) for v in targets.gt_off.tolist()]
+            rows, row_labels = targets.gt_boxes.detach().cpu(), targets.gt_labels.detach().cpu()
+            boxes = [rows[lo:hi] for lo, hi in zip(off[:-1], off[1:])]
+            labels = [row_labels[lo:hi] for lo, hi in zip(off[:-1], off[1:])]
+        else:
+            boxes = [t["boxes"].reshape(-1, 4) for t in targets]
+            labels = [t["labels"].reshape(-1) if "labels" in t else None for t in targets]
+        coefs = ssr.next_coefs(in_hw, boxes)
+        images = [ssr.warp_image(im, coefs.inv[b], coefs.applied[b]) for b, im in enumerate(images)]
+        moved = ssr.warp_boxes(coefs, in_hw, boxes, labels, ssr.min_visibility)
+        if packed:
+            out_b, out_l, at = rows.clone(), row_labels.clone(), 0
+            new_off = [0]
+            for bx, lb in moved:
+                n = int(bx.shape[0])
+                out_b[at:at + n], out_l[at:at + n] = bx, lb
+                at += n
+                new_off.append(at)
+            dev = targets.gt_boxes.device
+            return images, targets.with_rows(out_b.to(dev), out_l.to(dev), torch.tensor(new_off, dtype=torch.int32).to(dev))
+        for t, bx0, (bx, lb) in zip(targets, boxes, moved):
+            t["boxes"] = bx.to(bx0.device)
+            if lb is not None:
+                t["labels"] = lb
+        return images, targets
+
     # -- whole transform -----------------------------------------------------------------
     def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None,
                 out_dtype: Optional[torch.dtype] = None, channels_last: bool = False, canvas: Optional[Tuple[int, int]] = None):
@@ -426,6 +474,8 @@ class GeneralizedRCNNTransform(nn.Module):
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(im.shape)}")
         if getattr(self, "crop", None) is not None and self.training and targets is not None:
             images, targets = self._crop_on_host(images, targets)
+        if getattr(self, "shift_scale_rotate", None) is not None and self.training and targets is not None:
+            images, targets = self._shift_scale_rotate_on_host(images, targets)
         if self._fusable(images):
             return self._forward_fused(images, targets, out_dtype or torch.float32, channels_last)
         flags = self._flips(images, targets)

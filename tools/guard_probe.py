@@ -5,8 +5,8 @@ mapping and the GPU raises a memory access fault (the process aborts) instead of
 ``stem_fwd_kernel`` -- a wave of the last workgroup that owns no tile loaded at a tile index past the last image.
 
 usage: guard_probe.py stem B H W | w3 N H W C | n3 N H W | dense | pw | pool | bottleneck | step KIND MIN MAX | detect DT B H W K [MEAN] |
-       loss DT B H W K T | gt | adam [bf16|f16] | clip [bf16|f16] | accum [bf16|f16]        (driven by tests/test_guard_gpu.py;
-       gt: by tests/test_gt_capacity_gpu.py; adam: by tests/test_master_adam_gpu.py; clip: by tests/test_grad_clip_gpu.py;
+       loss DT B H W K T | gt | affine | adam [bf16|f16] | clip [bf16|f16] | accum [bf16|f16]        (driven by tests/test_guard_gpu.py;
+       gt: by tests/test_gt_capacity_gpu.py; affine: by tests/test_shift_scale_rotate_gpu.py; adam: by tests/test_master_adam_gpu.py; clip: by tests/test_grad_clip_gpu.py;
        accum: by tests/test_grad_accum_gpu.py)
 Prints one "ok ..." line per case; a fault kills the process (non-zero exit status, no "ok" line for the case)."""
 import ctypes as C
@@ -261,6 +261,75 @@ def main() -> None:
         sc = torch.tensor([[rw, rh, rw, rh] for (rh, rw), c in zip(ratios, counts) for _ in range(c)], device=DEV)
         assert torch.equal(dst[:n], out.gt_boxes[:n] * sc)
         print("ok gt", B, cap, n, flush=True)
+    elif which == "affine":
+        # rn_affine_draw + rn_image_warp_stage (csrc/affine.hip) on hostile device data: the state block, the packed GT, the offsets,
+        # the sizes, the coefficients, both arenas and every output end EXACTLY at the end of their mappings.  Image 1 claims h = 0,
+        # image 3 a size no slot holds; gt_off starts below 0 and ends past rows.  Everything else must come out as the restatement says.
+        from pytorch_retinanet_amd import ops
+        from pytorch_retinanet_amd.augment import AffineCoefs, ShiftScaleRotate
+
+        def exact_end(n: int, dtype, fill=0x7f):
+            nbytes = max(n, 1) * dtype.itemsize
+            tot = (nbytes + GRAN - 1) // GRAN * GRAN
+            base = torch.empty((tot,), dtype=torch.uint8, device=DEV)
+            base.fill_(fill)
+            _KEEP.append(base)
+            return base[tot - n * dtype.itemsize:].view(dtype)
+        sizes = [(37, 53), (20, 24), (64, 40), (9, 11), (1, 9)]
+        B, slot, R = len(sizes), 3 * 64 * 40, 12
+        g = torch.Generator(device=DEV).manual_seed(8)
+        ims = [torch.rand((3, h, w), device=DEV, generator=g) for h, w in sizes]
+        arena = exact_end(B * slot, torch.float32).view(B, slot)
+        arena.fill_(-7.25)
+        for b, im in enumerate(ims):
+            arena[b, : im.numel()] = im.reshape(-1)
+        hostile = [(37, 53), (0, 24), (64, 40), (30000, 30000), (1, 9)]
+        in_hw = exact_end(2 * B, torch.int32).view(B, 2)
+        in_hw.copy_(torch.tensor(hostile, dtype=torch.int32))
+        boxes = torch.tensor([[3.5, 4.0, 20.0, 30.0], [49.0, 1.0, 52.5, 4.0], [10.0, 2.0, 40.25, 12.0], [2.0, 3.0, 9.0, 12.0],
+                              [5.0, 6.0, 20.0, 50.0], [36.0, 0.5, 39.5, 3.0], [22.0, 30.0, 38.5, 61.0], [1.0, 1.0, 5.0, 6.0], [2.0, 0.0, 7.0, 1.0]])
+        n = boxes.shape[0]
+        gt_boxes = exact_end(4 * R, torch.float32).view(R, 4)
+        gt_boxes.fill_(-7.25)
+        gt_boxes[:n] = boxes.to(DEV)
+        gt_labels = exact_end(R, torch.int64)
+        gt_labels.copy_(torch.arange(1, R + 1, device=DEV))
+        off = [-5, 3, 4, 7, 8, R + 9]                                  # clamped: 0, 3, 4, 7, 8, R -- image 4 owns rows 8 .. R - 1
+        gt_off = exact_end(B + 1, torch.int32)
+        gt_off.copy_(torch.tensor(off, dtype=torch.int32))
+        clamped = [min(max(v, 0), R) for v in off]
+        block = exact_end(ops.AFFINE_STATE_BYTES, torch.uint8)
+        ops.affine_state_write(block, seed=2, counter=0, p=1.0, min_visibility=0.0, lo=(-45.0, 0.9, -0.0625, -0.0625), hi=(45.0, 1.1, 0.0625, 0.0625))
+        coef = exact_end(B * ops.AFFINE_COEF_WORDS, torch.int32).view(B, ops.AFFINE_COEF_WORDS)
+        out_boxes, out_labels, out_off = exact_end(4 * R, torch.float32).view(R, 4), exact_end(R, torch.int64), exact_end(B + 1, torch.int32)
+        out_boxes.fill_(-7.25)
+        check(lib.rn_affine_draw(block.data_ptr(), gt_boxes.data_ptr(), gt_labels.data_ptr(), gt_off.data_ptr(), in_hw.data_ptr(), B,
+                                 coef.data_ptr(), out_boxes.data_ptr(), out_labels.data_ptr(), out_off.data_ptr(), R, st), "rn_affine_draw")
+        dst = exact_end(B * slot, torch.float32).view(B, slot)
+        dst.fill_(-7.25)
+        check(lib.rn_image_warp_stage(arena.data_ptr(), slot, in_hw.data_ptr(), coef.data_ptr(), B, dst.data_ptr(), slot, st), "rn_image_warp_stage")
+        torch.cuda.synchronize()
+        c = AffineCoefs.from_device(coef)
+        rows_in = gt_boxes.cpu()
+        per = [rows_in[lo:hi] for lo, hi in zip(clamped[:-1], clamped[1:])]
+        host = ShiftScaleRotate.draw_coefs(2, 0, hostile, per, 1.0, (-45.0, 0.9, -0.0625, -0.0625), (45.0, 1.1, 0.0625, 0.0625))
+        assert c.applied == host.applied and not c.applied[1] and c.applied[0] and c.applied[2], c.applied      # (h < 1: left alone)
+        lab = [gt_labels.cpu()[lo:hi] for lo, hi in zip(clamped[:-1], clamped[1:])]
+        want = ShiftScaleRotate.warp_boxes(c, hostile, per, lab)
+        counts = [int(w[0].shape[0]) for w in want]
+        assert out_off.tolist() == [min(sum(counts[:i]), R) for i in range(B + 1)], (out_off.tolist(), counts)
+        total = out_off.tolist()[-1]
+        assert torch.equal(out_boxes.cpu()[:total].view(torch.int32), torch.cat([w[0] for w in want])[:total].view(torch.int32))
+        assert torch.equal(out_labels.cpu()[:total], torch.cat([w[1] for w in want])[:total])
+        assert bool((out_boxes[total:] == -7.25).all()) and ops.affine_state_read(block)[1] == 1
+        for b, im in enumerate(ims):
+            if b in (1, 3):                                                        # skipped: the slot is as it was
+                assert bool((dst[b] == -7.25).all()), b
+                continue
+            ref = ShiftScaleRotate.warp_image(im, c.inv[b], c.applied[b]).reshape(-1)
+            assert torch.equal(dst[b, : ref.numel()].view(torch.int32), ref.view(torch.int32)), b
+            assert bool((dst[b, ref.numel():] == -7.25).all()), b
+        print("ok affine", B, counts, total, flush=True)
     elif which == "adam":
         # rn_adam_master_step (csrc/adam.hip): 45 tensors (two launches of 40 + 5), every master / moment / gradient / 16-bit copy,
         # the hparams block and the GradScaler scalars at the end of their own mappings; sizes through the scalar tail path.
