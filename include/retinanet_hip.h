@@ -1057,6 +1057,54 @@ int rn_affine_draw(rn_affine_state *state, const float *gt_boxes, const int64_t 
 int rn_image_warp_stage(const float *arena, int64_t slot, const int32_t *in_hw_dev, const rn_affine_coef *coef, int B, float *arena_out,
                         int64_t slot_out, void *stream);
 
+/* ---- COCO bbox AP on the device (coco_eval.DeviceBBoxEval, csrc/eval.hip) ---------------------------------------------------
+ * coco_eval.BBoxEval (COCOeval, iouType "bbox", restated) is the definition; the two entry points restate its two interpreted loops
+ * and give its bits: every floating-point step below is ONE double operation, in this order, on values that started as fp32, and
+ * csrc/eval.hip is built without FMA contraction and without fast-math.  No atomics, no workspace that outlives a call; the same
+ * inputs give the same bits on every call.  All arrays are DEVICE arrays; boxes and scores must be finite.
+ * rn_eval_match -- BBoxEval._evaluate_img for every (image, category) pair of the test set, one wave per pair.
+ *   dt_boxes f32[D][4] xyxy, grouped by pair and, inside a pair, sorted by descending score (stable): a detection's rank is its
+ *   position in its pair.  gt_xywh f64[G][4] (x, y, w, h as gt_from_dataset makes them), gt_area f64[G], gt_crowd u8[G], grouped by
+ *   pair in their original order.  pairs i32[P][4] = (dt begin, dt end, gt begin, gt end), clamped into the arrays on the device;
+ *   either range of a pair may be empty.  iou_thrs f64[T] and area_rng f64[A][2] are BBoxEval.iou_thrs / .area_rng uploaded as they
+ *   are.  For a pair, an area range a = (lo, hi) and a threshold t:
+ *   1. Ground truth g is IGNORED iff gt_crowd[g] or not (lo <= gt_area[g] <= hi).  gt_ignored u8[G]: bit a.
+ *   2. Only the pair's first max_det detections take part; the masks of the others are 0.  A detection is (x, y, w, h) =
+ *      (x1, y1, x2 - x1, y2 - y1) with the subtractions in fp32, everything after in double: x + w, y + h, area = w h;
+ *      iw = max(min(dx2, gx2) - max(dx1, gx1), 0), ih likewise, inter = iw ih, ga = gw gh (NOT gt_area),
+ *      union = the detection's area against a crowd row, else (area + ga) - inter;  iou = union > 0 ? inter / union : 0.
+ *   3. Detections in rank order.  The candidates of a detection are the rows with not (iou < min(t, 1 - 1e-10)) that are not yet
+ *      matched at (a, t) -- a crowd row stays available after a match, a non-crowd ignored row does not.  If a cared-for candidate
+ *      exists the match is the cared-for candidate of the largest IoU, the LATER row at equal IoU; only otherwise the ignored
+ *      candidate chosen the same way.
+ *   4. dt_matched u64[D] / dt_ignored u64[D], bit a T + t: matched iff step 3 found a row; ignored iff that row is ignored, or
+ *      nothing was found and the detection's own area < lo or > hi.
+ *   Any ground-truth count per pair works: the lanes take the rows in strips of 64, and the match state of the rows past the first
+ *   strip lives in gt_state u64[G] (scratch; needs no initialisation, holds nothing of use afterwards).
+ *   RN_EINVAL: T < 1 or > 32, A < 1 or > 8, A T > 64 (the masks are 64 bits, gt_ignored is 8), max_det < 1, D, G or P negative or
+ *   >= 2^31, a null pointer to a non-empty array.  RN_EALIGN: boxes not 16-byte, 64-bit arrays not 8-byte, pairs not 4-byte aligned.
+ * rn_eval_accumulate -- the precision / recall arrays of BBoxEval.evaluate, one wave per (t, k, a, m) row.
+ *   matched / ignored u64[N] and rank i32[N]: per category k the entries [cat_off[k], cat_off[k + 1]) (cat_off i64[K + 1], clamped) are
+ *   that category's detections of all evaluated images with rank < the largest maxDets, sorted by descending score, stable over the
+ *   base order "image id ascending, then rank" (the sort is the caller's).  npig i64[K][A]: the ground truth of category k in the
+ *   evaluated images that range a does not ignore.  rec_thrs f64[R], max_dets i32[M].  For a row, over its entries with
+ *   rank < max_dets[m], in list order:
+ *   5. tp / fp = the running counts (integers) of matched & ~ignored / ~matched & ~ignored at bit a T + t;  rc = tp / npig and
+ *      pr = tp / ((fp + tp) + eps), eps = 2^-52 = np.spacing(1), each one double division;  pr becomes its running maximum from the
+ *      right;  precision[t][r][k][a][m] = pr at the first entry with rc >= rec_thrs[r], else 0;  recall[t][k][a][m] = the last rc, 0
+ *      for an empty list.
+ *   6. A row with npig[k][a] <= 0 (no cared-for ground truth, or no pair at all) is -1 throughout.
+ *   The list is walked in chunks of 64 entries with a carry -- forward for the counts, backward for the envelope and the recall
+ *   crossings -- so its length is only bounded by N < 2^31.  precision f64[T][R][K][A][M], recall f64[T][K][A][M]: every element is written.
+ *   RN_EINVAL: the limits on T and A above, M < 1, R < 1 or > 1024, K < 0, T K A M >= 2^31, N negative or >= 2^31, a null pointer
+ *   (the list arrays may be null when N == 0; K == 0 writes nothing).  RN_EALIGN: 64-bit arrays not 8-byte, 32-bit arrays not 4-byte. */
+int rn_eval_match(const float *dt_boxes, int64_t D, const double *gt_xywh, const double *gt_area, const uint8_t *gt_crowd, int64_t G,
+                  const int32_t *pairs, int64_t P, const double *iou_thrs, int T, const double *area_rng, int A, int max_det,
+                  uint64_t *dt_matched, uint64_t *dt_ignored, uint8_t *gt_ignored, uint64_t *gt_state, void *stream);
+int rn_eval_accumulate(const uint64_t *matched, const uint64_t *ignored, const int32_t *rank, int64_t N, const int64_t *cat_off,
+                       const int64_t *npig, const double *rec_thrs, int R, const int32_t *max_dets, int M, int T, int K, int A,
+                       double *precision, double *recall, void *stream);
+
 /* ---- K6 nms (op boundary) ---------------------------------------------------
  * Replaces torchvision.ops.nms as called at retinanet/models.py:210, batched over
  * S independent segments: seg_off i32[S+1]; boxes f32[N][4], scores f32[N].

@@ -211,6 +211,8 @@ SIGNATURES = {
     "rn_image_crop_stage": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _vp, _i64, _vp]),
     "rn_affine_draw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     "rn_image_warp_stage": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _vp, _i64, _vp]),
+    "rn_eval_match": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "rn_eval_accumulate": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "rn_nms_workspace_bytes":(_sz, [_i64, C.c_int]),
     "rn_nms_segments": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _f32, _vp, _vp, _vp, _sz, _vp]),
     "rn_detect_workspace_bytes": (_sz, [C.c_int, _i64, C.c_int, _i64]),

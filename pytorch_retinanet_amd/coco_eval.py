@@ -10,6 +10,10 @@ detections to ground truth at IoU thresholds .50:.05:.95 (crowd / out-of-area gr
 the 12-number ``stats`` vector whose element 0 (AP@[.5:.95]) the reference logs as ``AP``.
 Parity status: known-answer tests only (``tests/test_coco_eval.py``); there is no pycocotools here to
 pin the numbers against.
+
+``DeviceBBoxEval`` / ``CocoEvaluator(..., device=<cuda>)`` run the same protocol on the GPU (``rn_eval_match`` /
+``rn_eval_accumulate``, csrc/eval.hip) with ``BBoxEval`` as the definition: the same ``eval`` arrays, bit for bit
+(``tests/test_device_eval_gpu.py``).  Off unless asked for.
 """
 from collections import defaultdict
 from typing import Dict, Iterable, List, Mapping, Optional, Sequence
@@ -18,7 +22,8 @@ import numpy as np
 import torch
 from torch import Tensor
 
-__all__ = ["convert_to_xywh", "prepare_for_coco_detection", "BBoxEval", "CocoEvaluator", "gt_from_dataset"]
+__all__ = ["convert_to_xywh", "prepare_for_coco_detection", "BBoxEval", "DeviceBBoxEval", "CocoEvaluator", "gt_from_dataset", "group_pairs",
+           "category_lists"]
 
 
 def convert_to_xywh(boxes: Tensor) -> Tensor:
@@ -202,27 +207,193 @@ def gt_from_dataset(dataset) -> List[dict]:
     return rows
 
 
+class PairGroups:
+    """What ``group_pairs`` returns.  ``gt_order`` / ``dt_order``: indices into the caller's rows, grouped by pair (the rows of images
+    outside ``imgs`` are gone); ``pairs`` int32 [P, 4] = (dt begin, dt end, gt begin, gt end) into those orders; ``pair_key`` int64 [P]
+    = category index * len(imgs) + image index, ascending; ``dt_key`` / ``gt_key``: the key of every grouped row; ``dt_rank``: a
+    detection's place in its pair; ``n_img``: len(imgs)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def group_pairs(gt_img: Tensor, gt_cat: Tensor, dt_img: Tensor, dt_cat: Tensor, dt_score: Tensor, imgs: Tensor, cats: Tensor) -> PairGroups:
+    """The dict-of-lists grouping of ``BBoxEval.evaluate`` as tensor operations on the tensors' device (any device: the CPU tests run
+    it).  ``imgs`` / ``cats``: the sorted, distinct image ids to evaluate (at least one) and category ids (every category of
+    ``gt_cat`` and ``dt_cat`` is among them).  Rows are grouped by (category, image) -- category-major, so a category's pairs are
+    neighbours and in ascending image order -- ground truth in its original order, detections by descending score with equal
+    scores in their original order (two stable sorts), which is ``sorted(d, key=-score)`` of the host path."""
+    n_img = int(imgs.numel())
+
+    def keyed(img, cat):
+        ii = torch.searchsorted(imgs, img)
+        ok = (ii < n_img) & (imgs[ii.clamp(max=n_img - 1)] == img)
+        return torch.searchsorted(cats, cat) * n_img + ii, ok
+
+    gkey, gok = keyed(gt_img, gt_cat)
+    gidx = torch.nonzero(gok).squeeze(1)
+    gt_key, o = torch.sort(gkey[gidx], stable=True)
+    gt_order = gidx[o]
+    dkey, dok = keyed(dt_img, dt_cat)
+    didx = torch.nonzero(dok).squeeze(1)
+    o1 = torch.sort(dt_score[didx], descending=True, stable=True).indices
+    dt_key, o2 = torch.sort(dkey[didx][o1], stable=True)
+    dt_order = didx[o1][o2]
+    pair_key = torch.unique_consecutive(torch.sort(torch.cat([gt_key, dt_key])).values)
+    d0, d1 = torch.searchsorted(dt_key, pair_key), torch.searchsorted(dt_key, pair_key, right=True)
+    g0, g1 = torch.searchsorted(gt_key, pair_key), torch.searchsorted(gt_key, pair_key, right=True)
+    pairs = torch.stack([d0, d1, g0, g1], dim=1).to(torch.int32).contiguous()
+    dt_rank = torch.arange(dt_key.numel(), device=dt_key.device) - d0[torch.searchsorted(pair_key, dt_key)]
+    return PairGroups(gt_order=gt_order, dt_order=dt_order, pairs=pairs, pair_key=pair_key, gt_key=gt_key, dt_key=dt_key,
+                      dt_rank=dt_rank, n_img=n_img)
+
+
+def category_lists(groups: PairGroups, dt_score_grouped: Tensor, num_cats: int, max_det: int):
+    """Per category the detections with rank < ``max_det`` of all pairs, by descending score, stable over the base order "image id
+    ascending, then rank" (which is the grouped order itself) -> (indices into the grouped detections, cat_off int64 [K + 1]).
+    This is ``np.argsort(-scores, kind="mergesort")`` of ``BBoxEval.evaluate`` for the largest maxDets; a smaller maxDets is the
+    sub-list with rank < maxDets, because a stable sort of a sub-list is the sub-list of the stable sort."""
+    sel = torch.nonzero(groups.dt_rank < max_det).squeeze(1)
+    o1 = torch.sort(dt_score_grouped[sel], descending=True, stable=True).indices
+    cat = torch.div(groups.dt_key[sel][o1], groups.n_img, rounding_mode="floor")
+    cat, o2 = torch.sort(cat, stable=True)
+    cat_off = torch.searchsorted(cat, torch.arange(num_cats + 1, device=cat.device))
+    return sel[o1][o2], cat_off
+
+
+class DeviceBBoxEval(BBoxEval):
+    """``BBoxEval`` with the matching and the precision / recall rows as HIP kernels (``rn_eval_match`` / ``rn_eval_accumulate``,
+    csrc/eval.hip): the same decisions and the same ``eval["precision"]`` / ``eval["recall"]`` bits, because the kernels do
+    ``BBoxEval``'s double operations one by one (no FMA contraction).  ``gt``: annotation rows as for ``BBoxEval``, uploaded once.
+    Detections come as tensors (``set_detections``), not as rows: xyxy fp32 boxes, scores, labels, image ids.  ``evaluate`` groups
+    them into (image, category) pairs with torch ops on the device (stable sorts, ``unique_consecutive``), runs the two kernels and
+    copies ``precision`` and ``recall`` back in ONE transfer; ``summarize`` / ``_summ`` / ``stats`` are ``BBoxEval``'s.  ``img_ids``
+    restricts the evaluated images as it does there; the categories are the sorted union over ground truth and detections.  Boxes
+    and scores must be finite.  There is no CPU path: a CPU ``device`` is refused."""
+
+    def __init__(self, gt: Iterable[dict], device, img_ids: Optional[Sequence[int]] = None):
+        super().__init__(gt, (), img_ids)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"DeviceBBoxEval runs only as HIP kernels on an MI355X; got device {self.device} (there is no CPU fallback: use BBoxEval).")
+        dev = self.device
+        area = [float(x["area"]) if "area" in x else float(x["bbox"][2] * x["bbox"][3]) for x in self.gt]
+        self._gt_img = torch.tensor([int(x["image_id"]) for x in self.gt], dtype=torch.int64).to(dev)
+        self._gt_cat = torch.tensor([int(x["category_id"]) for x in self.gt], dtype=torch.int64).to(dev)
+        self._gt_xywh = torch.tensor([[float(v) for v in x["bbox"]] for x in self.gt], dtype=torch.float64).reshape(-1, 4).to(dev)
+        self._gt_area = torch.tensor(area, dtype=torch.float64).to(dev)
+        self._gt_crowd = torch.tensor([1 if x.get("iscrowd", 0) else 0 for x in self.gt], dtype=torch.uint8).to(dev)
+        self._thrs = torch.tensor(np.asarray(self.iou_thrs, dtype=np.float64)).to(dev)
+        self._rng = torch.tensor(np.asarray(self.area_rng, dtype=np.float64).reshape(-1, 2)).to(dev)
+        self._rec = torch.tensor(np.asarray(self.rec_thrs, dtype=np.float64)).to(dev)
+        self._max_dets = torch.tensor(list(self.max_dets), dtype=torch.int32).to(dev)
+        self.set_detections(torch.zeros((0, 4)), torch.zeros((0,)), torch.zeros((0,), dtype=torch.int64), torch.zeros((0,), dtype=torch.int64))
+
+    def set_detections(self, boxes: Tensor, scores: Tensor, labels: Tensor, image_ids: Tensor) -> None:
+        "xyxy boxes [D, 4], scores [D], labels [D], image ids [D] (CPU tensors are uploaded); they replace what was set before."
+        n = int(boxes.shape[0])
+        if boxes.dim() != 2 or boxes.shape[1] != 4 or scores.shape != (n,) or labels.shape != (n,) or image_ids.shape != (n,):
+            raise ValueError(f"need boxes [D, 4] and scores, labels, image_ids [D], got {tuple(boxes.shape)}, {tuple(scores.shape)}, "
+                             f"{tuple(labels.shape)}, {tuple(image_ids.shape)}")
+        dev = self.device
+        self._dt = (boxes.to(dev, torch.float32).contiguous(), scores.to(dev, torch.float32).contiguous(),
+                    labels.to(dev, torch.int64).contiguous(), image_ids.to(dev, torch.int64).contiguous())
+
+    def evaluate(self) -> "DeviceBBoxEval":
+        from . import ops
+        dev = self.device
+        boxes, scores, labels, dimg = self._dt
+        T, R, A, M = len(self.iou_thrs), len(self.rec_thrs), len(self.area_rng), len(self.max_dets)
+        if self.img_ids is not None:
+            imgs = torch.tensor(sorted({int(i) for i in self.img_ids}), dtype=torch.int64).to(dev)
+        else:
+            imgs = torch.unique(torch.cat([self._gt_img, dimg]))
+        cats = torch.unique(torch.cat([self._gt_cat, labels]))
+        K = int(cats.numel())
+        if K == 0 or imgs.numel() == 0:
+            self.eval = {"precision": -np.ones((T, R, K, A, M)), "recall": -np.ones((T, K, A, M))}
+            return self
+        g = group_pairs(self._gt_img, self._gt_cat, dimg, labels, scores, imgs, cats)
+        matched, ignored, gt_ignored = ops.eval_match(boxes[g.dt_order], self._gt_xywh[g.gt_order], self._gt_area[g.gt_order],
+                                                      self._gt_crowd[g.gt_order], g.pairs, self._thrs, self._rng, self.max_dets[-1])
+        order, cat_off = category_lists(g, scores[g.dt_order], K, self.max_dets[-1])
+        # the cared-for ground truth per (category, area range): the rows are category-major, so a prefix sum at the category seams
+        cared = ((gt_ignored.to(torch.int64)[:, None] >> torch.arange(A, device=dev)[None, :]) & 1) == 0
+        seams = torch.searchsorted(torch.div(g.gt_key, g.n_img, rounding_mode="floor"), torch.arange(K + 1, device=dev))
+        run = torch.cat([torch.zeros((1, A), dtype=torch.int64, device=dev), torch.cumsum(cared.to(torch.int64), dim=0)])
+        npig = (run[seams[1:]] - run[seams[:-1]]).contiguous()
+        precision, recall = ops.eval_accumulate(matched[order], ignored[order], g.dt_rank[order].to(torch.int32), cat_off, npig, self._rec,
+                                                self._max_dets, T)
+        flat = torch.cat([precision.reshape(-1), recall.reshape(-1)]).cpu().numpy()          # the one transfer back
+        self.eval = {"precision": flat[:precision.numel()].reshape(tuple(precision.shape)).copy(),
+                     "recall": flat[precision.numel():].reshape(tuple(recall.shape)).copy()}
+        return self
+
+    accumulate = evaluate
+
+
 class CocoEvaluator:
     """Same call sequence as the reference's (coco_eval.py:14-58): ``update({image_id: detection dict})``
     per batch, ``synchronize_between_processes()``, ``accumulate()``, ``summarize()``; the result is read from
-    ``coco_eval["bbox"].stats[0]`` (model.py:150-157).  ``gt``: annotation rows (``gt_from_dataset``)."""
+    ``coco_eval["bbox"].stats[0]`` (model.py:150-157).  ``gt``: annotation rows (``gt_from_dataset``).
 
-    def __init__(self, gt: Iterable[dict], iou_types: Sequence[str] = ("bbox",)):
+    ``device``: None or a CPU device is the host path (``BBoxEval``, interpreted).  A CUDA device is the device path:
+    ``coco_eval["bbox"]`` is a ``DeviceBBoxEval``, ``update`` keeps each batch's boxes, scores, labels and image ids as tensors on that
+    device -- no ``.tolist()``, no synchronisation; CPU tensors (what ``graph.CapturedPredict`` returns) are uploaded -- and
+    ``accumulate`` runs the two kernels.  The statistics are the host path's, bit for bit.  Under an initialised process group of more
+    than one rank ``synchronize_between_processes`` turns the kept tensors into rows, gathers them as the host path does and
+    evaluates on the host (``coco_eval["bbox"]`` becomes a ``BBoxEval``): the test loader is never sharded here, so that path exists
+    for callers who shard it themselves."""
+
+    def __init__(self, gt: Iterable[dict], iou_types: Sequence[str] = ("bbox",), device=None):
         assert isinstance(iou_types, (list, tuple))
         if any(t != "bbox" for t in iou_types):
             raise ValueError(f"only iou_type 'bbox' is supported (RetinaNet has no masks / keypoints), got {iou_types}")
         self.iou_types = list(iou_types)
-        self.coco_eval = {"bbox": BBoxEval(gt)}
+        self.device = None if device is None or torch.device(device).type != "cuda" else torch.device(device)
         self.img_ids: List[int] = []
         self.results: List[dict] = []
+        if self.device is None:
+            self.coco_eval = {"bbox": BBoxEval(gt)}
+        else:
+            self.coco_eval = {"bbox": DeviceBBoxEval(gt, self.device)}
+            self.kept: List[tuple] = []            # per update: (boxes [n, 4], scores [n], labels [n], image ids [n]) on the device
 
     def update(self, predictions: Mapping[int, Mapping[str, Tensor]]) -> None:
         self.img_ids.extend(int(i) for i in np.unique(list(predictions.keys())))
-        self.results.extend(prepare_for_coco_detection(predictions))
+        if self.device is None:
+            self.results.extend(prepare_for_coco_detection(predictions))
+            return
+        preds = [(int(i), p) for i, p in predictions.items() if len(p) != 0]
+        if not preds:
+            return
+        dev = self.device
+        # the image ids are built from the shapes alone (host knowledge): nothing is read back from the device
+        ids = torch.repeat_interleave(torch.tensor([i for i, _ in preds], dtype=torch.int64),
+                                      torch.tensor([int(p["scores"].shape[0]) for _, p in preds], dtype=torch.int64))
+        self.kept.append((torch.cat([p["boxes"].reshape(-1, 4) for _, p in preds]).to(dev, torch.float32),
+                          torch.cat([p["scores"].reshape(-1) for _, p in preds]).to(dev, torch.float32),
+                          torch.cat([p["labels"].reshape(-1) for _, p in preds]).to(dev, torch.int64), ids.to(dev)))
+
+    def _kept_tensors(self):
+        if not self.kept:
+            z = torch.zeros((0,), dtype=torch.int64, device=self.device)
+            return torch.zeros((0, 4), device=self.device), torch.zeros((0,), device=self.device), z, z
+        return tuple(torch.cat([k[j] for k in self.kept]) for j in range(4))
+
+    def _kept_rows(self) -> List[dict]:
+        "The kept tensors as the host path's rows (``prepare_for_coco_detection``'s format and arithmetic); synchronises."
+        boxes, scores, labels, ids = self._kept_tensors()
+        xywh = convert_to_xywh(boxes).tolist()
+        return [{"image_id": i, "category_id": l, "bbox": b, "score": s} for i, l, b, s in zip(ids.tolist(), labels.tolist(), xywh, scores.tolist())]
 
     def synchronize_between_processes(self) -> None:
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            if self.device is not None:            # more than one rank: rows, gathered and evaluated on the host
+                self.results = self._kept_rows()
+                self.coco_eval = {"bbox": BBoxEval(self.coco_eval["bbox"].gt)}
+                self.device = None
             gathered: List = [None] * dist.get_world_size()
             dist.all_gather_object(gathered, (self.img_ids, self.results))
             self.img_ids = [i for ids, _ in gathered for i in ids]
@@ -230,6 +401,11 @@ class CocoEvaluator:
 
     def accumulate(self) -> None:
         ev = self.coco_eval["bbox"]
+        if self.device is not None:
+            ev.set_detections(*self._kept_tensors())
+            ev.img_ids = sorted(set(self.img_ids))
+            ev.evaluate()
+            return
         ev.dt, ev.img_ids = self.results, sorted(set(self.img_ids))
         ev.evaluate()
 

@@ -72,6 +72,7 @@ class RetinaNetModel(_Base):
         self.trn_ds = self.val_ds = self.test_ds = None
         self.test_evaluator = None
         self.predictor = None         # a callable images -> detections used by test_step instead of net.predict (graph.CapturedPredict)
+        self.device_eval = False      # test_dataloader: score on the GPU (coco_eval.DeviceBBoxEval) when the net is on CUDA; SimpleTrainer sets it
 
     def forward(self, xb, *args, **kwargs):
         # reference model.py:33-35 calls self.net(xb) with no targets (a TypeError there, Q19);
@@ -134,7 +135,10 @@ class RetinaNetModel(_Base):
     def test_dataloader(self, *args, **kwargs):
         from .coco_eval import CocoEvaluator, gt_from_dataset
         loader = self._loader(self.test_ds, self.conf.dataloader.test_bs)
-        self.test_evaluator = CocoEvaluator(gt_from_dataset(loader.dataset), ["bbox"])       # reference model.py:105-110
+        # device_eval: the metric's matching and precision / recall rows as HIP kernels, the detections kept on the device
+        device = next(self.net.parameters()).device if self.device_eval else None
+        device = device if device is not None and device.type == "cuda" else None
+        self.test_evaluator = CocoEvaluator(gt_from_dataset(loader.dataset), ["bbox"], device=device)       # reference model.py:105-110
         return loader
 
     # -- optimisation ----------------------------------------------------------------------------
@@ -234,7 +238,7 @@ class SimpleTrainer:
                  channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True,
                  gt_capacity=None, gradient_clip_val: float = 0.0, accumulate_grad_batches: int = 1,
                  weight_ema_decay: float = 0.0, weight_ema_warmup: float = 0.0, device_scale_jitter: bool = False,
-                 scale_jitter_seed: int = 0, image_capacity=None, predict_image_capacity=None):
+                 scale_jitter_seed: int = 0, image_capacity=None, predict_image_capacity=None, device_eval: bool = False):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
@@ -287,7 +291,13 @@ class SimpleTrainer:
         "auto" or a list of padded canvases (Hp, Wp) -- ``test()`` installs a ``graph.CapturedPredict`` over them as the model's
         ``predictor`` (``self.predictor``; removed again when ``test()`` returns), so every test batch is one graph replay keyed by its
         canvas class whatever its images' sizes are.  It runs inside the weight average's swap, and its graphs are dropped whenever the
-        weights change.  CUDA only; the cost is the class canvas again."""
+        weights change.  CUDA only; the cost is the class canvas again.
+
+        ``device_eval`` (off by default; left False, an optional ``trainer.device_eval`` in the hparams is honoured): ``test()`` scores the
+        detections on the GPU -- the model's ``test_evaluator`` becomes a ``CocoEvaluator(device=...)`` whose ``coco_eval["bbox"]`` is a
+        ``coco_eval.DeviceBBoxEval``: the detections stay on the device as tensors, the greedy matching and the precision / recall rows run
+        as two HIP kernels (``rn_eval_match`` / ``rn_eval_accumulate``), and the 12 statistics are the host evaluator's bit for bit.  CUDA
+        only: on another device the host evaluator is used as before."""
         from .graph import gt_capacity_classes, image_capacity_classes
         from .optim import check_accumulate_grad_batches
         self.accumulate_grad_batches = check_accumulate_grad_batches(accumulate_grad_batches)
@@ -313,6 +323,7 @@ class SimpleTrainer:
         image_capacity_classes(predict_image_capacity)    # (the same)
         self.predict_image_capacity = predict_image_capacity
         self.predictor = None                             # the graph.CapturedPredict of the last test()
+        self.device_eval = bool(device_eval)
         self.max_epochs, self.max_steps, self.log_every, self.capture = max_epochs, max_steps, log_every, capture
         self.captured_steps = 0
         self.captured_graphs = 0                          # captures of the last fit() (one per input signature that reached a replay)
@@ -386,6 +397,13 @@ class SimpleTrainer:
         if value is None or isinstance(value, str):
             return value
         return [tuple(int(v) if int(v) == v else v for v in c) for c in value]      # (a YAML list of [Hp, Wp] lists)
+
+    def resolve_device_eval(self, conf) -> bool:
+        "The constructor's ``device_eval`` or, when that is False, ``trainer.device_eval`` of the hparams (absent: off)."
+        if self.device_eval:
+            return True
+        section = conf.get("trainer") if hasattr(conf, "get") else None
+        return bool((section or {}).get("device_eval") or False)
 
     def _install_scale_jitter(self, model, rank: Optional[int]) -> None:
         "``fit``'s part of ``device_scale_jitter``: a ``RandomShortSide`` over the transform's ``min_size`` tuple, or one log line."
@@ -582,6 +600,8 @@ class SimpleTrainer:
         outs = []
         capacity = self.resolve_predict_image_capacity(getattr(model, "conf", None))
         installed = False
+        if self.resolve_device_eval(getattr(model, "conf", None)):
+            model.device_eval = True                      # (test_dataloader below builds the evaluator on the model's device)
         if capacity is not None and self.device.type == "cuda" and getattr(model, "predictor", None) is None:
             from .graph import CapturedPredict
             # (inside the swap below: the predictor stamps the weights it captured under, so the swap and its undoing drop its graphs)

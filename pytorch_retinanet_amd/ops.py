@@ -1484,3 +1484,77 @@ def detect_finish_var(out_boxes: Tensor, out_scores: Tensor, out_labels: Tensor,
         check(lib.rn_detect_finish_var(_ptr(out_boxes), _ptr(out_scores), _ptr(out_labels), _ptr(meta[0]), _ptr(meta[1]), _ptr(in_hw),
                                        _ptr(out_hw), B, max_det, _ptr(out), total, _stream(dev)), "rn_detect_finish_var")
     return out
+
+
+# --------------------------------------------------------------------------- #
+# COCO bbox AP on the device (coco_eval.DeviceBBoxEval, csrc/eval.hip)
+def _eval_arg(name: str, t: Tensor, dtype: torch.dtype, shape: Tuple[int, ...]) -> None:
+    if not isinstance(t, Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, Tensor) else type(t).__name__
+        raise ValueError(f"{name} must be a contiguous {dtype} {list(shape)} tensor, got {got}")
+
+
+def _eval_dims(iou_thrs: Tensor, area_rng: Tensor) -> Tuple[int, int]:
+    T, A = int(iou_thrs.numel()), int(area_rng.shape[0]) if area_rng.dim() == 2 else -1
+    _eval_arg("iou_thrs", iou_thrs, torch.float64, (T,))
+    _eval_arg("area_rng", area_rng, torch.float64, (A, 2))
+    if not (1 <= T <= 32 and 1 <= A <= 8 and A * T <= 64):
+        raise ValueError(f"need 1 <= T <= 32 thresholds and 1 <= A <= 8 area ranges with A * T <= 64 (the masks are 64 bits), got T={T}, A={A}")
+    return T, A
+
+
+def eval_match(dt_boxes: Tensor, gt_xywh: Tensor, gt_area: Tensor, gt_crowd: Tensor, pairs: Tensor, iou_thrs: Tensor, area_rng: Tensor,
+               max_det: int = 100) -> Tuple[Tensor, Tensor, Tensor]:
+    """``rn_eval_match``: ``BBoxEval._evaluate_img`` for every (image, category) pair at once.  ``dt_boxes`` f32 [D, 4] xyxy, grouped by
+    pair and sorted by descending score inside a pair; ``gt_xywh`` f64 [G, 4], ``gt_area`` f64 [G], ``gt_crowd`` uint8 [G], grouped by
+    pair; ``pairs`` int32 [P, 4] = (dt begin, dt end, gt begin, gt end); ``iou_thrs`` f64 [T], ``area_rng`` f64 [A, 2] ->
+    (matched int64 [D], ignored int64 [D]: bit ``a * T + t``; gt_ignored uint8 [G]: bit ``a``).  One launch on the current stream,
+    no atomics, no host synchronisation."""
+    D, G, P = int(dt_boxes.shape[0]), int(gt_area.shape[0]), int(pairs.shape[0])
+    _eval_arg("dt_boxes", dt_boxes, torch.float32, (D, 4))
+    _eval_arg("gt_xywh", gt_xywh, torch.float64, (G, 4))
+    _eval_arg("gt_area", gt_area, torch.float64, (G,))
+    _eval_arg("gt_crowd", gt_crowd, torch.uint8, (G,))
+    _eval_arg("pairs", pairs, torch.int32, (P, 4))
+    T, A = _eval_dims(iou_thrs, area_rng)
+    if int(max_det) < 1:
+        raise ValueError(f"max_det must be >= 1, got {max_det}")
+    dev = _need_dev(dt_boxes, gt_xywh, gt_area, gt_crowd, pairs, iou_thrs, area_rng)
+    dt_boxes = _aligned(dt_boxes, 16)
+    matched = torch.empty((D,), dtype=torch.int64, device=dev)
+    ignored = torch.empty((D,), dtype=torch.int64, device=dev)
+    gt_ignored = torch.empty((G,), dtype=torch.uint8, device=dev)
+    gt_state = torch.empty((G,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev), _timed("eval_match", dev):
+        check(lib.rn_eval_match(_ptr(dt_boxes), D, _ptr(gt_xywh), _ptr(gt_area), _ptr(gt_crowd), G, _ptr(pairs), P, _ptr(iou_thrs), T,
+                                _ptr(area_rng), A, int(max_det), _ptr(matched), _ptr(ignored), _ptr(gt_ignored), _ptr(gt_state),
+                                _stream(dev)), "rn_eval_match")
+    return matched, ignored, gt_ignored
+
+
+def eval_accumulate(matched: Tensor, ignored: Tensor, rank: Tensor, cat_off: Tensor, npig: Tensor, rec_thrs: Tensor, max_dets: Tensor,
+                    T: int) -> Tuple[Tensor, Tensor]:
+    """``rn_eval_accumulate``: the precision / recall arrays of ``BBoxEval.evaluate``.  ``matched`` / ``ignored`` int64 [N] and ``rank``
+    int32 [N]: per category its detections sorted by descending score (stable over "image id ascending, then rank"), category k at
+    ``[cat_off[k], cat_off[k + 1])`` (``cat_off`` int64 [K + 1]); ``npig`` int64 [K, A]; ``rec_thrs`` f64 [R]; ``max_dets`` int32 [M];
+    ``T``: the number of thresholds in the masks -> (precision f64 [T, R, K, A, M], recall f64 [T, K, A, M]).  One launch on the
+    current stream, no atomics, no host synchronisation."""
+    N, K, R, M = int(matched.numel()), int(cat_off.numel()) - 1, int(rec_thrs.numel()), int(max_dets.numel())
+    A = int(npig.shape[1]) if npig.dim() == 2 else -1
+    _eval_arg("matched", matched, torch.int64, (N,))
+    _eval_arg("ignored", ignored, torch.int64, (N,))
+    _eval_arg("rank", rank, torch.int32, (N,))
+    _eval_arg("cat_off", cat_off, torch.int64, (K + 1,))
+    _eval_arg("npig", npig, torch.int64, (K, A))
+    _eval_arg("rec_thrs", rec_thrs, torch.float64, (R,))
+    _eval_arg("max_dets", max_dets, torch.int32, (M,))
+    T = int(T)
+    if K < 0 or not (1 <= T <= 32 and 1 <= A <= 8 and A * T <= 64) or M < 1 or not 1 <= R <= 1024:
+        raise ValueError(f"need K >= 0, 1 <= T <= 32, 1 <= A <= 8, A * T <= 64, M >= 1 and 1 <= R <= 1024, got K={K}, T={T}, A={A}, M={M}, R={R}")
+    dev = _need_dev(matched, ignored, rank, cat_off, npig, rec_thrs, max_dets)
+    precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+    recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), _timed("eval_accumulate", dev):
+        check(lib.rn_eval_accumulate(_ptr(matched), _ptr(ignored), _ptr(rank), N, _ptr(cat_off), _ptr(npig), _ptr(rec_thrs), R, _ptr(max_dets), M,
+                                     T, K, A, _ptr(precision), _ptr(recall), _stream(dev)), "rn_eval_accumulate")
+    return precision, recall
