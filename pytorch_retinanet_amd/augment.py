@@ -40,12 +40,16 @@ border in intent, not bit for bit.  It is a second staging pass as well -- ``rn_
 rows that survive it (rows can disappear: the offsets change), ``rn_image_warp_stage`` gathers each image into a second arena -- and
 its Python restatement (``draw_coefs``, ``warp_boxes``, ``warp_image``) serves every other input on the host.
 """
+import logging
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
+
+from . import draw_state
+from .draw_state import COLOR_IDENTITY, COLOR_OPS, SHORT_SIDE_MAX
 
 __all__ = ["RandomHorizontalFlip", "RandomShortSide", "ColorJitter", "BBoxSafeRandomCrop", "ShiftScaleRotate", "hflip_u", "apply_color_ops"]
 
@@ -61,23 +65,125 @@ def hflip_u(seed: int, counter: int, b: int) -> float:
     return (z >> 40) * 2.0 ** -24
 
 
-class RandomHorizontalFlip:
+def _ops():
+    "The kernel launchers, imported at first use: the restatements and the host draws of this module need no device."
+    from . import ops
+    return ops
+
+
+def _check_p(p) -> float:
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"flip probability must be in [0, 1], got {p}")
+    return float(np.float32(p))
+
+
+class _DrawStream:
+    """What the augmentations below share: a stream of draws (seed, counter) and, from the first CUDA batch on, the device block that a
+    draw kernel reads and whose counter it advances (``_layout``: its ``draw_state`` table; ``_fields()``: its fields besides seed and
+    counter, from this object's settings).  A captured step holds the block's address, so it is created once, outside any capture,
+    and never replaced; a replay advances the device counter, not ``_counter``, so ``counter`` reads it back; and a setting is
+    written as its own fields only (``_write``): the block is never rebuilt from host values."""
+    _layout: draw_state.Layout
+
+    def __init__(self, seed: int):
+        self.base_seed = int(seed) & _M64
+        self._seed, self._counter = self.base_seed, 0
+        self._block: Optional[Tensor] = None          # the state block on the device of the first CUDA batch (kept for good)
+
+    def _fields(self) -> Dict[str, object]:
+        raise NotImplementedError
+
+    def _device_block(self, device: torch.device) -> Tensor:
+        "The block on the CUDA ``device``, created at the first call (which must not be inside a capture)."
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._block is None:
+            self._block = draw_state.new(self._layout, device, seed=self._seed, counter=self._counter, **self._fields())
+        elif self._block.device != device:
+            # (a captured step holds the block's address: it is never replaced while this object lives)
+            raise RuntimeError(f"{type(self).__name__}: its state lives on {self._block.device}, not {device}; use one object per device")
+        return self._block
+
+    def _write(self, **fields) -> None:
+        "Settings into the device block, if there is one (no re-capture needed; not inside a capture)."
+        if self._block is not None:
+            draw_state.write(self._layout, self._block, **fields)
+
+    def _host_draw(self, draw: Callable):
+        "``draw(n)`` at the next counter value n, and the counter advanced by one -- on the device too, with a block (a synchronisation)."
+        n = self.counter
+        out = draw(n)
+        self._counter = n + 1
+        self._write(counter=n + 1)
+        return out
+
+    @property
+    def seed(self) -> int:
+        return self._seed
+
+    def reseed(self, seed: int, counter: int = 0) -> None:
+        "Start a new stream of draws (seed, counter); not inside a capture."
+        self._seed, self._counter = int(seed) & _M64, int(counter)
+        self._write(seed=self._seed, counter=self._counter)
+
+    def set_rank(self, rank: int) -> None:
+        """One stream per data-parallel rank: seed = ``base_seed`` (the constructor's) + rank, the counter kept.  Without it every rank
+        would make the same draws at the same batch positions."""
+        self.reseed((self.base_seed + int(rank)) & _M64, self.counter)
+
+    @property
+    def counter(self) -> int:
+        "Batches drawn so far (with the device block: one read-back, i.e. a synchronisation)."
+        if self._block is not None:
+            return int(draw_state.read(self._layout, self._block)[1])
+        return self._counter
+
+    def state_dict(self) -> Dict[str, object]:
+        return {"seed": self._seed, "counter": self.counter}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.reseed(int(state["seed"]), int(state["counter"]))
+
+
+class _ProbStream(_DrawStream):
+    "A stream whose draws apply with probability ``p``, a field of its block."
+
+    def __init__(self, p: float, seed: int):
+        super().__init__(seed)
+        self._p = _check_p(p)
+
+    def _fields(self) -> Dict[str, object]:
+        return {"p": self._p}
+
+    @property
+    def p(self) -> float:
+        return self._p
+
+    @p.setter
+    def p(self, value: float) -> None:
+        "A new probability: written into the device block (no re-capture needed; not inside a capture)."
+        self._p = _check_p(value)
+        self._write(p=self._p)
+
+    def state_dict(self) -> Dict[str, object]:
+        return {**super().state_dict(), "p": self._p}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.p = state["p"]
+        super().load_state_dict(state)
+
+
+class RandomHorizontalFlip(_ProbStream):
     """Flip each training image (and its boxes: x1' = W - x2, x2' = W - x1) with probability ``p``.  Install it as
     ``net.transform.hflip``; it acts only in training mode and only when targets are given.  Not an ``nn.Module``: it adds no key
     to the model's state dict.  ``seed``: the stream of decisions (``SimpleTrainer`` adds the rank under ``torch.distributed``)."""
+    _layout = draw_state.HFLIP
 
     def __init__(self, p: float = 0.5, seed: int = 0):
-        self.base_seed = int(seed) & _M64
-        self._p, self._seed, self._counter = self._check_p(p), self.base_seed, 0
-        self._block: Optional[Tensor] = None          # rn_hflip_state on the device of the first CUDA batch (kept for good)
+        super().__init__(p, seed)
         self.flags: Optional[Tensor] = None           # the last batch's decisions (uint8 [B]; device or CPU)
-
-    @staticmethod
-    def _check_p(p) -> float:
-        p = float(p)
-        if not 0.0 <= p <= 1.0:
-            raise ValueError(f"flip probability must be in [0, 1], got {p}")
-        return float(np.float32(p))
 
     def __repr__(self) -> str:
         return f"RandomHorizontalFlip(p={self._p}, seed={self._seed})"
@@ -100,71 +206,14 @@ class RandomHorizontalFlip:
         if device.type != "cuda":
             if self._block is not None:
                 raise RuntimeError("RandomHorizontalFlip: its state lives on the GPU; draw CPU batches from a fresh object")
-            flags = torch.tensor(self.draw(self._counter, B), dtype=torch.uint8)
-            self._counter += 1
+            flags = torch.tensor(self._host_draw(lambda n: self.draw(n, B)), dtype=torch.uint8)
         else:
-            from . import ops
-            if device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-            if self._block is None:
-                self._block = ops.hflip_state(device, self._seed, self._counter, self._p)
-            elif self._block.device != device:
-                # (a captured step holds the block's address: it is never replaced while this object lives)
-                raise RuntimeError(f"RandomHorizontalFlip: its state lives on {self._block.device}, not {device}; use one object per device")
-            flags = ops.hflip_draw(self._block, B)
+            flags = _ops().hflip_draw(self._device_block(device), B)
         self.flags = flags
         return flags
 
-    # -- settings and state ---------------------------------------------------------------------------------------------
-    @property
-    def p(self) -> float:
-        return self._p
-
-    @p.setter
-    def p(self, value: float) -> None:
-        "A new probability: written into the device block (no re-capture needed; not inside a capture)."
-        self._p = self._check_p(value)
-        if self._block is not None:
-            from . import ops
-            ops.hflip_state_write(self._block, p=self._p)
-
-    @property
-    def seed(self) -> int:
-        return self._seed
-
-    def reseed(self, seed: int, counter: int = 0) -> None:
-        "Start a new stream of decisions (seed, counter); not inside a capture."
-        self._seed, self._counter = int(seed) & _M64, int(counter)
-        if self._block is not None:
-            from . import ops
-            ops.hflip_state_write(self._block, seed=self._seed, counter=self._counter)
-
-    def set_rank(self, rank: int) -> None:
-        """One stream per data-parallel rank: seed = ``base_seed`` (the constructor's) + rank, the counter kept.  Without it every rank
-        would flip the same batch positions."""
-        self.reseed((self.base_seed + int(rank)) & _M64, self.counter)
-
-    @property
-    def counter(self) -> int:
-        "Batches drawn so far (with the device block: one read-back, i.e. a synchronisation)."
-        if self._block is not None:
-            from . import ops
-            return int(ops.hflip_state_read(self._block)[1])
-        return self._counter
-
-    def state_dict(self) -> Dict[str, object]:
-        return {"seed": self._seed, "counter": self.counter, "p": self._p}
-
-    def load_state_dict(self, state: Dict[str, object]) -> None:
-        self._p = self._check_p(state["p"])
-        self.reseed(int(state["seed"]), int(state["counter"]))
-        if self._block is not None:
-            from . import ops
-            ops.hflip_state_write(self._block, p=self._p)
-
 
 SHORT_SIDE_SALT = 0x5CA1E5CA1E5CA1E5      # xor-ed into the seed: a flip and a jitter that share a seed must not tie small sizes to flipped images
-SHORT_SIDE_MAX = 16                       # candidate short sides a device block holds (include/retinanet_hip.h: RN_SHORT_SIDE_MAX)
 
 
 def short_side_hw(h: int, w: int, short: float, max_size: float) -> Tuple[int, int]:
@@ -177,20 +226,19 @@ def short_side_hw(h: int, w: int, short: float, max_size: float) -> Tuple[int, i
     return int(math.floor(h * scale)), int(math.floor(w * scale))
 
 
-class RandomShortSide:
+class RandomShortSide(_DrawStream):
     """Resize each training image to a short side drawn from ``sizes`` (torchvision's ``min_size`` tuple), one draw per image and step,
     made on the device.  Install it as ``net.transform.scale_jitter``; it acts only in training mode and only when targets are given,
     and while it is installed the transform's own host-side draw from ``min_size`` is not consulted in training.  Not an
     ``nn.Module``: it adds no key to the model's state dict.  At most 16 sizes.  The padded canvas is sized for the largest entry
     the object was built with (``canvas_short``), whatever is drawn: one captured graph serves every scale, and small draws save
     no compute.  ``seed``: the stream of draws (``SimpleTrainer`` adds the rank under ``torch.distributed``)."""
+    _layout = draw_state.SHORT_SIDE
 
     def __init__(self, sizes: Sequence[int], seed: int = 0):
-        self.base_seed = int(seed) & _M64
+        super().__init__(seed)
         self._sizes = self._check_sizes(sizes)
         self.canvas_short = max(self._sizes)          # the canvas bound: fixed for good (a captured step holds the canvas)
-        self._seed, self._counter = self.base_seed, 0
-        self._block: Optional[Tensor] = None          # rn_short_side_state on the device of the first CUDA batch (kept for good)
         self.sizes_drawn: Optional[Tensor] = None     # the last batch's sizes after the resize (int32 [B, 2]; device or CPU)
         self.ratios_drawn: Optional[Tensor] = None    # the last batch's box ratios (f32 [2B] = (rh, rw) per image; device or CPU)
 
@@ -202,6 +250,9 @@ class RandomShortSide:
         if any(isinstance(v, bool) or int(v) != v or int(v) <= 0 for v in sizes):
             raise ValueError(f"short sides must be positive integers, got {sizes}")
         return tuple(int(v) for v in sizes)
+
+    def _fields(self) -> Dict[str, object]:
+        return {"sizes": self._sizes}
 
     def __repr__(self) -> str:
         return f"RandomShortSide(sizes={self._sizes}, seed={self._seed})"
@@ -247,22 +298,13 @@ class RandomShortSide:
         if device.type != "cuda":
             if self._block is not None:
                 raise RuntimeError("RandomShortSide: its state lives on the GPU; draw CPU batches from a fresh object")
-            hw = self.draw(self._counter, in_hw_list, max_size)
+            hw = self._host_draw(lambda n: self.draw(n, in_hw_list, max_size))
             sizes = torch.tensor(hw, dtype=torch.int32).reshape(-1, 2)
             ratios = torch.tensor(self.ratios(in_hw_list, hw), dtype=torch.float32).reshape(-1)
-            self._counter += 1
         else:
-            from . import ops
             if int(max_size) != max_size:
                 raise ValueError(f"the device draw takes an integer max_size, got {max_size}")
-            if device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-            if self._block is None:
-                self._block = ops.short_side_state(device, self._seed, self._counter, self._sizes)
-            elif self._block.device != device:
-                # (a captured step holds the block's address: it is never replaced while this object lives)
-                raise RuntimeError(f"RandomShortSide: its state lives on {self._block.device}, not {device}; use one object per device")
-            sizes, ratios = ops.short_side_draw(self._block, in_hw_list, int(max_size))
+            sizes, ratios = _ops().short_side_draw(self._device_block(device), in_hw_list, int(max_size))
         self.sizes_drawn, self.ratios_drawn = sizes, ratios
         return sizes, ratios
 
@@ -271,17 +313,11 @@ class RandomShortSide:
         writes it: the image capacity mode of ``graph.CapturedTrainStep``): one ``rn_resize_plan_dev`` launch for any B (capturable).
         The same stream of draws: at counter n it gives what ``draw(n, sizes, max_size)`` gives for the sizes ``in_hw`` holds, and
         the counter advances by one."""
-        from . import ops
         if int(max_size) != max_size:
             raise ValueError(f"the device draw takes an integer max_size, got {max_size}")
-        device = in_hw.device
-        if device.type != "cuda":
+        if in_hw.device.type != "cuda":
             raise RuntimeError("RandomShortSide.next_sizes_dev: the sizes must be on the GPU (there is no CPU fallback)")
-        if self._block is None:
-            self._block = ops.short_side_state(device, self._seed, self._counter, self._sizes)
-        elif self._block.device != device:
-            raise RuntimeError(f"RandomShortSide: its state lives on {self._block.device}, not {device}; use one object per device")
-        sizes, ratios = ops.resize_plan_dev(self._block, in_hw, None, int(max_size))
+        sizes, ratios = _ops().resize_plan_dev(self._device_block(in_hw.device), in_hw, None, int(max_size))
         self.sizes_drawn, self.ratios_drawn = sizes, ratios
         return sizes, ratios
 
@@ -299,47 +335,20 @@ class RandomShortSide:
             raise ValueError(f"short side {max(value)} exceeds {self.canvas_short}, the largest this object was built with: the padded "
                              "canvas would change; install a new RandomShortSide instead")
         self._sizes = value
-        if self._block is not None:
-            from . import ops
-            ops.short_side_state_write(self._block, sizes=self._sizes)
-
-    @property
-    def seed(self) -> int:
-        return self._seed
-
-    def reseed(self, seed: int, counter: int = 0) -> None:
-        "Start a new stream of draws (seed, counter); not inside a capture."
-        self._seed, self._counter = int(seed) & _M64, int(counter)
-        if self._block is not None:
-            from . import ops
-            ops.short_side_state_write(self._block, seed=self._seed, counter=self._counter)
-
-    def set_rank(self, rank: int) -> None:
-        "One stream per data-parallel rank: seed = ``base_seed`` (the constructor's) + rank, the counter kept."
-        self.reseed((self.base_seed + int(rank)) & _M64, self.counter)
-
-    @property
-    def counter(self) -> int:
-        "Batches drawn so far (with the device block: one read-back, i.e. a synchronisation)."
-        if self._block is not None:
-            from . import ops
-            return int(ops.short_side_state_read(self._block)[1])
-        return self._counter
+        self._write(sizes=self._sizes)
 
     def state_dict(self) -> Dict[str, object]:
-        return {"seed": self._seed, "counter": self.counter, "sizes": list(self._sizes)}
+        return {**super().state_dict(), "sizes": list(self._sizes)}
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
         self.sizes = state["sizes"]
-        self.reseed(int(state["seed"]), int(state["counter"]))
+        super().load_state_dict(state)
 
 
 # ---- colour jitter -----------------------------------------------------------------------------------------------------
-COLOR_OPS = ("brightness", "contrast", "saturation", "hue")         # operation ids 0..3 (include/retinanet_hip.h: rn_color_coef)
 COLOR_SKIP = 0xF
 COLOR_SALT_APPLY, COLOR_SALT_ORDER = 0xC0104A11C0104A11, 0x04DE404DE404DE45
 COLOR_SALT_FACTOR = (0xB416B416B416B417, 0xC0274A57C0274A57, 0x5A7C5A7C5A7C5A7D, 0x40E040E040E040E1)
-_COLOR_IDENTITY = (1.0, 1.0, 1.0, 0.0)
 _PERMS = None
 
 
@@ -419,7 +428,7 @@ def apply_color_ops(image: Tensor, factors: Sequence[float], order: int, mean: O
     return x
 
 
-class ColorJitter:
+class ColorJitter(_ProbStream):
     """torchvision's ``ColorJitter`` for fp32 RGB training images in [0, 1], drawn and applied on the device.  ``brightness`` /
     ``contrast`` / ``saturation``: a number v for factors in [max(0, 1 - v), 1 + v] or a pair (lo, hi); ``hue``: v for [-v, v] with
     0 <= v <= 0.5 or a pair inside [-0.5, 0.5]; 0 or None disables an operation.  With probability ``p`` an image is jittered: its
@@ -427,12 +436,11 @@ class ColorJitter:
     as ``net.transform.color_jitter``; it acts only in training mode and only when targets are given, on the raw image (before the
     normalisation, the resize and the flip).  Not an ``nn.Module``: it adds no key to the model's state dict.  ``seed``: the stream of
     draws (``SimpleTrainer`` adds the rank under ``torch.distributed``)."""
+    _layout = draw_state.COLOR_JITTER
 
     def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, p: float = 1.0, seed: int = 0):
-        self.base_seed = int(seed) & _M64
         self._ranges = [self._check_range(n, v) for n, v in zip(COLOR_OPS, (brightness, contrast, saturation, hue))]
-        self._p, self._seed, self._counter = RandomHorizontalFlip._check_p(p), self.base_seed, 0
-        self._block: Optional[Tensor] = None          # rn_color_jitter_state on the device of the first CUDA batch (kept for good)
+        super().__init__(p, seed)
         self._built_mask = self.enabled_mask          # what the launches of a captured step were chosen for (fixed once a block exists)
         self.coef: Optional[Tensor] = None            # the last device batch's rn_color_coef rows (f32 [B, 8])
         self.drawn: Optional[List[Tuple[Tuple[float, ...], int]]] = None     # the last host-drawn batch's (factors, order)
@@ -470,9 +478,13 @@ class ColorJitter:
 
     def _lo_hi(self) -> Tuple[List[float], List[float]]:
         "The block's lo / hi: a disabled operation holds its identity factor twice."
-        lo = [r[0] if r is not None else _COLOR_IDENTITY[k] for k, r in enumerate(self._ranges)]
-        hi = [r[1] if r is not None else _COLOR_IDENTITY[k] for k, r in enumerate(self._ranges)]
+        lo = [r[0] if r is not None else COLOR_IDENTITY[k] for k, r in enumerate(self._ranges)]
+        hi = [r[1] if r is not None else COLOR_IDENTITY[k] for k, r in enumerate(self._ranges)]
         return lo, hi
+
+    def _fields(self) -> Dict[str, object]:
+        lo, hi = self._lo_hi()
+        return {"p": self._p, "lo": lo, "hi": hi, "enabled_mask": self.enabled_mask}
 
     @staticmethod
     def draw_coefs(seed: int, counter: int, B: int, p: float, lo: Sequence[float], hi: Sequence[float],
@@ -499,12 +511,7 @@ class ColorJitter:
         """The next batch's (factors, order) on the HOST, and the counter advanced by one: what CPU tensors and images the fused
         transform does not take use (``apply_color_ops``).  With a device block the counter is read back and written (a
         synchronisation); not inside a capture."""
-        n = self.counter
-        self.drawn = self.draw(n, B)
-        self._counter = n + 1
-        if self._block is not None:
-            from . import ops
-            ops.color_jitter_state_write(self._block, counter=n + 1)
+        self.drawn = self._host_draw(lambda n: self.draw(n, B))
         return self.drawn
 
     def next_coef(self, images) -> Tensor:
@@ -512,21 +519,14 @@ class ColorJitter:
         ``rn_color_jitter_draw`` launch and, when a contrast is enabled, ``rn_color_mean`` over the images (capturable; the block is
         created at the first call, which must not be inside a capture).  ``images``: CUDA f32 ``[3, h, w]`` tensors or
         ``ops.StagedImages``."""
-        from . import ops
+        ops = _ops()
         staged = isinstance(images, ops.StagedImages)
         device, B = (images.device, images.B) if staged else (images[0].device, len(images))
         if device.type != "cuda":
             raise RuntimeError("ColorJitter.next_coef draws on the GPU; CPU batches use next_draw()")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
         if self._block is None:
-            lo, hi = self._lo_hi()
             self._built_mask = self.enabled_mask
-            self._block = ops.color_jitter_state(device, self._seed, self._counter, self._p, lo, hi, self._built_mask)
-        elif self._block.device != device:
-            # (a captured step holds the block's address: it is never replaced while this object lives)
-            raise RuntimeError(f"ColorJitter: its state lives on {self._block.device}, not {device}; use one object per device")
-        coef = ops.color_jitter_draw(self._block, B)
+        coef = ops.color_jitter_draw(self._device_block(device), B)
         if self._built_mask & 2:                       # (a contrast that was never enabled launches nothing)
             ops.color_mean(images, coef)
         self.coef = coef
@@ -544,61 +544,23 @@ class ColorJitter:
             raise ValueError(f"ColorJitter: {COLOR_OPS[k]} was disabled when this object's device state was created; enabling it changes "
                              "which kernels a (captured) step launches -- install a new ColorJitter instead")
         self._ranges[k] = r
-        if self._block is not None:
-            from . import ops
-            lo, hi = self._lo_hi()
-            ops.color_jitter_state_write(self._block, lo=lo, hi=hi, enabled_mask=self.enabled_mask)
+        lo, hi = self._lo_hi()
+        self._write(lo=lo, hi=hi, enabled_mask=self.enabled_mask)
 
     brightness = property(lambda self: self._range(0), lambda self, v: self._set_range(0, v))
     contrast = property(lambda self: self._range(1), lambda self, v: self._set_range(1, v))
     saturation = property(lambda self: self._range(2), lambda self, v: self._set_range(2, v))
     hue = property(lambda self: self._range(3), lambda self, v: self._set_range(3, v))
 
-    @property
-    def p(self) -> float:
-        return self._p
-
-    @p.setter
-    def p(self, value: float) -> None:
-        "A new probability: written into the device block (no re-capture needed; not inside a capture)."
-        self._p = RandomHorizontalFlip._check_p(value)
-        if self._block is not None:
-            from . import ops
-            ops.color_jitter_state_write(self._block, p=self._p)
-
-    @property
-    def seed(self) -> int:
-        return self._seed
-
-    def reseed(self, seed: int, counter: int = 0) -> None:
-        "Start a new stream of draws (seed, counter); not inside a capture."
-        self._seed, self._counter = int(seed) & _M64, int(counter)
-        if self._block is not None:
-            from . import ops
-            ops.color_jitter_state_write(self._block, seed=self._seed, counter=self._counter)
-
-    def set_rank(self, rank: int) -> None:
-        "One stream per data-parallel rank: seed = ``base_seed`` (the constructor's) + rank, the counter kept."
-        self.reseed((self.base_seed + int(rank)) & _M64, self.counter)
-
-    @property
-    def counter(self) -> int:
-        "Batches drawn so far (with the device block: one read-back, i.e. a synchronisation)."
-        if self._block is not None:
-            from . import ops
-            return int(ops.color_jitter_state_read(self._block)[1])
-        return self._counter
-
     def state_dict(self) -> Dict[str, object]:
-        state = {"seed": self._seed, "counter": self.counter, "p": self._p}
+        state = super().state_dict()
         state.update({n: (None if r is None else list(r)) for n, r in zip(COLOR_OPS, self._ranges)})
         return state
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
         for k, n in enumerate(COLOR_OPS):
             self._set_range(k, state[n])
-        self.p = state["p"]
-        self.reseed(int(state["seed"]), int(state["counter"]))
+        super().load_state_dict(state)
 
 
 # ---- bbox-safe random crop ------------------------------------------------------------------------------------------------
@@ -624,7 +586,7 @@ def _crop_axis(u_lo: float, u_hi: float, u1: int, u2: int, n: int) -> Tuple[int,
     return min(a, u1), u2 + min(c, n - u2)
 
 
-class BBoxSafeRandomCrop:
+class BBoxSafeRandomCrop(_ProbStream):
     """With probability ``p`` crop each training image to a random window that contains all of its boxes, and shift the boxes with it:
     albumentations' ``BBoxSafeRandomCrop`` with ``erosion_rate = 0`` in intent -- each margin is drawn uniformly between the image edge
     and the union of the boxes -- on integer pixels.  No box that lies inside the image is ever cut and none is dropped, so the GT
@@ -640,11 +602,10 @@ class BBoxSafeRandomCrop:
     Every other input (CPU tensors, CUDA lists) takes the same stream of rectangles from ``draw_rects`` on the HOST: the boxes and the
     counter are read back, which on CUDA is one synchronisation per step.  Not an ``nn.Module``: it adds no key to the model's state
     dict.  ``seed``: the stream of draws (``SimpleTrainer`` adds the rank under ``torch.distributed``)."""
+    _layout = draw_state.BBOX_CROP
 
     def __init__(self, p: float = 1.0, seed: int = 0):
-        self.base_seed = int(seed) & _M64
-        self._p, self._seed, self._counter = RandomHorizontalFlip._check_p(p), self.base_seed, 0
-        self._block: Optional[Tensor] = None          # rn_bbox_crop_state on the device of the first CUDA batch (kept for good)
+        super().__init__(p, seed)
         self.rect: Optional[Tensor] = None            # the last device batch's rectangles (int32 [B, 4] = (y0, x0, ch, cw))
         self.rects: Optional[List[Tuple[int, int, int, int]]] = None      # the last host-drawn batch's rectangles
 
@@ -702,72 +663,40 @@ class BBoxSafeRandomCrop:
         """The next batch's rectangles on the HOST, and the counter advanced by one: what CPU tensors and CUDA lists use.  The boxes
         are read on the host (CUDA tensors are copied back: a synchronisation) and, with a device block, so is the counter; not
         inside a capture."""
-        n = self.counter
         boxes = [None if b is None else (b.detach().cpu().numpy() if isinstance(b, Tensor) else b) for b in boxes_per_image]
-        self.rects = self.draw(n, in_hw, boxes)
-        self._counter = n + 1
-        if self._block is not None:
-            from . import ops
-            ops.bbox_crop_state_write(self._block, counter=n + 1)
+        self.rects = self._host_draw(lambda n: self.draw(n, in_hw, boxes))
         return self.rects
 
     def device_block(self, device: torch.device) -> Tensor:
         """The ``rn_bbox_crop_state`` block on ``device`` that ``ops.bbox_crop_staged`` draws from, created at the first call (which
         must not be inside a capture) and kept for good: a captured step holds its address."""
-        device = torch.device(device)
-        if device.type != "cuda":
+        if torch.device(device).type != "cuda":
             raise RuntimeError("BBoxSafeRandomCrop: the device draw runs on the GPU; CPU batches use next_rects()")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._block is None:
-            from . import ops
-            self._block = ops.bbox_crop_state(device, self._seed, self._counter, self._p)
-        elif self._block.device != device:
-            raise RuntimeError(f"BBoxSafeRandomCrop: its state lives on {self._block.device}, not {device}; use one object per device")
-        return self._block
+        return self._device_block(device)
 
-    # -- settings and state ---------------------------------------------------------------------------------------------
-    @property
-    def p(self) -> float:
-        return self._p
 
-    @p.setter
-    def p(self, value: float) -> None:
-        "A new probability: written into the device block (no re-capture needed; not inside a capture)."
-        self._p = RandomHorizontalFlip._check_p(value)
-        if self._block is not None:
-            from . import ops
-            ops.bbox_crop_state_write(self._block, p=self._p)
+def _entries(entries) -> Iterator[Tuple[str, dict]]:
+    "(class name, params) of every entry of an hparams ``transforms`` list: a dict with ``class_name`` / ``params``, or a bare name."
+    for e in entries or []:
+        yield (str(e.get("class_name", "")), dict(e.get("params") or {})) if isinstance(e, dict) else (str(e), {})
 
-    @property
-    def seed(self) -> int:
-        return self._seed
 
-    def reseed(self, seed: int, counter: int = 0) -> None:
-        "Start a new stream of draws (seed, counter); not inside a capture."
-        self._seed, self._counter = int(seed) & _M64, int(counter)
-        if self._block is not None:
-            from . import ops
-            ops.bbox_crop_state_write(self._block, seed=self._seed, counter=self._counter)
+def _named(entries, names: Sequence[str], what: str, log) -> Iterator[Tuple[str, dict]]:
+    "The first entry whose class name is one of ``names``; every further one is skipped with a warning."
+    seen = False
+    for name, params in _entries(entries):
+        if name not in names:
+            continue
+        if seen:
+            log.warning("transforms: a second %s (%s) is skipped", what, name)
+            continue
+        seen = True
+        yield name, params
 
-    def set_rank(self, rank: int) -> None:
-        "One stream per data-parallel rank: seed = ``base_seed`` (the constructor's) + rank, the counter kept."
-        self.reseed((self.base_seed + int(rank)) & _M64, self.counter)
 
-    @property
-    def counter(self) -> int:
-        "Batches drawn so far (with the device block: one read-back, i.e. a synchronisation)."
-        if self._block is not None:
-            from . import ops
-            return int(ops.bbox_crop_state_read(self._block)[1])
-        return self._counter
-
-    def state_dict(self) -> Dict[str, object]:
-        return {"seed": self._seed, "counter": self.counter, "p": self._p}
-
-    def load_state_dict(self, state: Dict[str, object]) -> None:
-        self.p = state["p"]
-        self.reseed(int(state["seed"]), int(state["counter"]))
+def _entry_p(params: dict, default: float) -> float:
+    "An entry's probability: ``always_apply: true`` means 1."
+    return 1.0 if params.get("always_apply") else float(params.get("p", default))
 
 
 _BBOX_CROP_NAMES = ("albumentations.BBoxSafeRandomCrop", "BBoxSafeRandomCrop")
@@ -778,22 +707,13 @@ def bbox_crop_from_transforms(entries, seed: int = 0, log=None) -> Optional[BBox
     defaults to 1.0, albumentations' own default; ``always_apply: true`` means p = 1) maps onto ``BBoxSafeRandomCrop``, which works on
     integer pixels and is not bit-compatible with albumentations.  A non-zero ``erosion_rate`` is warned about and treated as 0.
     ``RandomSizedBBoxSafeCrop`` and every other crop are not this one: ``from_transforms`` skips them with its warning."""
-    import logging
     log = log or logging.getLogger(__name__)
     found = None
-    for e in entries or []:
-        name = str(e.get("class_name", "")) if isinstance(e, dict) else str(e)
-        params = dict(e.get("params") or {}) if isinstance(e, dict) else {}
-        if name not in _BBOX_CROP_NAMES:
-            continue
-        if found is not None:
-            log.warning("transforms: a second bbox-safe crop (%s) is skipped", name)
-            continue
+    for name, params in _named(entries, _BBOX_CROP_NAMES, "bbox-safe crop", log):
         if float(params.get("erosion_rate", 0.0) or 0.0) != 0.0:
             log.warning("transforms: %s erosion_rate=%s is not implemented and is treated as 0 (the crop never cuts into the union of "
                         "the boxes)", name, params.get("erosion_rate"))
-        p = 1.0 if params.get("always_apply") else float(params.get("p", 1.0))
-        found = BBoxSafeRandomCrop(p=p, seed=seed)
+        found = BBoxSafeRandomCrop(p=_entry_p(params, 1.0), seed=seed)
     return found
 
 
@@ -869,7 +789,7 @@ def _warp_rows(m, h: int, w: int, min_visibility, bx: np.ndarray) -> Tuple[np.nd
     return out, keep
 
 
-class ShiftScaleRotate:
+class ShiftScaleRotate(_ProbStream):
     """With probability ``p`` move each training image by a random shift, scale and rotation about its centre (bilinear
     interpolation, reflect-101 border) and take its boxes along: albumentations' ``ShiftScaleRotate`` in intent, with its argument
     meanings and defaults -- a scalar limit v is the range (-v, v), a pair is taken as given; the angle is in degrees, the scale is drawn
@@ -890,12 +810,11 @@ class ShiftScaleRotate:
     may differ between host and device in the last bit, so the two paths agree to an fp32 step of a matrix entry, not always bit
     for bit.  Not an ``nn.Module``: it adds no key to the model's state dict.  ``seed``: the stream of draws (``SimpleTrainer`` adds
     the rank under ``torch.distributed``)."""
+    _layout = draw_state.AFFINE
 
     def __init__(self, shift_limit=0.0625, scale_limit=0.1, rotate_limit=45, p: float = 0.5, min_visibility: float = 0.0, seed: int = 0):
-        self.base_seed = int(seed) & _M64
-        self._p, self._seed, self._counter = RandomHorizontalFlip._check_p(p), self.base_seed, 0
+        super().__init__(p, seed)
         self._set_ranges(shift_limit, scale_limit, rotate_limit, min_visibility)
-        self._block: Optional[Tensor] = None          # rn_affine_state on the device of the first CUDA batch (kept for good)
         self.coef: Optional[Tensor] = None            # the last device batch's rn_affine_coef (int32 [B, 16]; AffineCoefs.from_device)
         self.coefs: Optional[AffineCoefs] = None      # the last host-drawn batch's coefficients
 
@@ -913,6 +832,10 @@ class ShiftScaleRotate:
         "(lo, hi) of (angle, scale, dx, dy): what the device block holds."
         r = (self.rotate_limit, self.scale_range, self.shift_limit, self.shift_limit)
         return tuple(v[0] for v in r), tuple(v[1] for v in r)
+
+    def _fields(self) -> Dict[str, object]:
+        lo, hi = self.ranges
+        return {"p": self._p, "min_visibility": self.min_visibility, "lo": lo, "hi": hi}
 
     def __repr__(self) -> str:
         return (f"ShiftScaleRotate(shift_limit={self.shift_limit}, scale_limit={tuple(float(np.float32(v - 1.0)) for v in self.scale_range)}, "
@@ -1012,42 +935,16 @@ class ShiftScaleRotate:
         """The next batch's coefficients on the HOST, and the counter advanced by one: what CPU tensors and CUDA lists use.  The boxes
         are read on the host (CUDA tensors are copied back: a synchronisation) and, with a device block, so is the counter; not
         inside a capture."""
-        n = self.counter
-        self.coefs = self.draw(n, in_hw, [_boxes_f32(b) for b in boxes_per_image])
-        self._counter = n + 1
-        if self._block is not None:
-            from . import ops
-            ops.affine_state_write(self._block, counter=n + 1)
+        boxes = [_boxes_f32(b) for b in boxes_per_image]
+        self.coefs = self._host_draw(lambda n: self.draw(n, in_hw, boxes))
         return self.coefs
 
     def device_block(self, device: torch.device) -> Tensor:
         """The ``rn_affine_state`` block on ``device`` that ``ops.shift_scale_rotate_staged`` draws from, created at the first call
         (which must not be inside a capture) and kept for good: a captured step holds its address."""
-        device = torch.device(device)
-        if device.type != "cuda":
+        if torch.device(device).type != "cuda":
             raise RuntimeError("ShiftScaleRotate: the device draw runs on the GPU; CPU batches use next_coefs()")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._block is None:
-            from . import ops
-            lo, hi = self.ranges
-            self._block = ops.affine_state(device, self._seed, self._counter, self._p, self.min_visibility, lo, hi)
-        elif self._block.device != device:
-            raise RuntimeError(f"ShiftScaleRotate: its state lives on {self._block.device}, not {device}; use one object per device")
-        return self._block
-
-    # -- settings and state ---------------------------------------------------------------------------------------------
-    @property
-    def p(self) -> float:
-        return self._p
-
-    @p.setter
-    def p(self, value: float) -> None:
-        "A new probability: written into the device block (no re-capture needed; not inside a capture)."
-        self._p = RandomHorizontalFlip._check_p(value)
-        if self._block is not None:
-            from . import ops
-            ops.affine_state_write(self._block, p=self._p)
+        return self._device_block(device)
 
     def set_limits(self, shift_limit=None, scale_limit=None, rotate_limit=None, min_visibility=None) -> None:
         "New ranges (the ones not given stay): written into the device block (no re-capture needed; not inside a capture)."
@@ -1055,40 +952,8 @@ class ShiftScaleRotate:
         self._set_ranges(self.shift_limit if shift_limit is None else shift_limit, scale_now if scale_limit is None else scale_limit,
                          self.rotate_limit if rotate_limit is None else rotate_limit,
                          self.min_visibility if min_visibility is None else min_visibility)
-        if self._block is not None:
-            from . import ops
-            lo, hi = self.ranges
-            ops.affine_state_write(self._block, min_visibility=self.min_visibility, lo=lo, hi=hi)
-
-    @property
-    def seed(self) -> int:
-        return self._seed
-
-    def reseed(self, seed: int, counter: int = 0) -> None:
-        "Start a new stream of draws (seed, counter); not inside a capture."
-        self._seed, self._counter = int(seed) & _M64, int(counter)
-        if self._block is not None:
-            from . import ops
-            ops.affine_state_write(self._block, seed=self._seed, counter=self._counter)
-
-    def set_rank(self, rank: int) -> None:
-        "One stream per data-parallel rank: seed = ``base_seed`` (the constructor's) + rank, the counter kept."
-        self.reseed((self.base_seed + int(rank)) & _M64, self.counter)
-
-    @property
-    def counter(self) -> int:
-        "Batches drawn so far (with the device block: one read-back, i.e. a synchronisation)."
-        if self._block is not None:
-            from . import ops
-            return int(ops.affine_state_read(self._block)[1])
-        return self._counter
-
-    def state_dict(self) -> Dict[str, object]:
-        return {"seed": self._seed, "counter": self.counter, "p": self._p}
-
-    def load_state_dict(self, state: Dict[str, object]) -> None:
-        self.p = state["p"]
-        self.reseed(int(state["seed"]), int(state["counter"]))
+        lo, hi = self.ranges
+        self._write(min_visibility=self.min_visibility, lo=lo, hi=hi)
 
 
 _SHIFT_SCALE_ROTATE_NAMES = ("albumentations.ShiftScaleRotate", "ShiftScaleRotate")
@@ -1102,25 +967,16 @@ def shift_scale_rotate_from_transforms(entries, seed: int = 0, log=None) -> Opti
     ``always_apply: true`` means p = 1) map onto ``ShiftScaleRotate``, which is bilinear with the reflect-101 border and not
     bit-compatible with albumentations.  A non-default ``interpolation``, ``border_mode``, ``value``, ``shift_limit_x`` or
     ``shift_limit_y`` is warned about and ignored; a second entry is skipped with a warning."""
-    import logging
     log = log or logging.getLogger(__name__)
     found = None
-    for e in entries or []:
-        name = str(e.get("class_name", "")) if isinstance(e, dict) else str(e)
-        params = dict(e.get("params") or {}) if isinstance(e, dict) else {}
-        if name not in _SHIFT_SCALE_ROTATE_NAMES:
-            continue
-        if found is not None:
-            log.warning("transforms: a second shift / scale / rotate (%s) is skipped", name)
-            continue
+    for name, params in _named(entries, _SHIFT_SCALE_ROTATE_NAMES, "shift / scale / rotate", log):
         for key, defaults in _SSR_FIXED:
             if params.get(key) not in defaults:
                 log.warning("transforms: %s %s=%s is not implemented and is ignored (bilinear interpolation, the reflect-101 border and "
                             "one shift_limit for both axes are)", name, key, params.get(key))
         as_limit = lambda v: tuple(v) if isinstance(v, (list, tuple)) else v
-        p = 1.0 if params.get("always_apply") else float(params.get("p", 0.5))
         found = ShiftScaleRotate(shift_limit=as_limit(params.get("shift_limit", 0.0625)), scale_limit=as_limit(params.get("scale_limit", 0.1)),
-                                 rotate_limit=as_limit(params.get("rotate_limit", 45)), p=p, seed=seed)
+                                 rotate_limit=as_limit(params.get("rotate_limit", 45)), p=_entry_p(params, 0.5), seed=seed)
     return found
 
 
@@ -1132,22 +988,13 @@ def color_jitter_from_transforms(entries, seed: int = 0, log=None) -> Optional[C
     saturation and hue default to 0.2, ``p`` to 0.5; ``always_apply: true`` means p = 1) and ``torchvision.transforms.ColorJitter`` /
     a bare ``ColorJitter`` (each default 0, p = 1) map onto ``ColorJitter``, whose arithmetic is torchvision's tensor algorithm:
     albumentations works on uint8 through OpenCV and differs slightly.  Other entries are ``from_transforms``' business."""
-    import logging
     log = log or logging.getLogger(__name__)
     found = None
-    for e in entries or []:
-        name = str(e.get("class_name", "")) if isinstance(e, dict) else str(e)
-        params = dict(e.get("params") or {}) if isinstance(e, dict) else {}
-        if name not in _COLOR_JITTER_NAMES:
-            continue
-        if found is not None:
-            log.warning("transforms: a second colour jitter (%s) is skipped", name)
-            continue
+    for name, params in _named(entries, _COLOR_JITTER_NAMES, "colour jitter", log):
         alb = name.startswith("albumentations.")
         default = 0.2 if alb else 0
-        p = 1.0 if params.get("always_apply") else float(params.get("p", 0.5 if alb else 1.0))
         kw = {n: params.get(n, default) for n in COLOR_OPS}
-        found = ColorJitter(p=p, seed=seed, **{n: (tuple(v) if isinstance(v, (list, tuple)) else v) for n, v in kw.items()})
+        found = ColorJitter(p=_entry_p(params, 0.5 if alb else 1.0), seed=seed, **{n: (tuple(v) if isinstance(v, (list, tuple)) else v) for n, v in kw.items()})
     return found
 
 
@@ -1155,15 +1002,12 @@ def from_transforms(entries, seed: int = 0, log=None) -> Optional[RandomHorizont
     """The flip an hparams ``transforms`` list asks for (reference ``hparams.yaml:55-58``), or None.  ``albumentations.HorizontalFlip``
     (``p``, default 0.5; ``always_apply: true`` means p = 1) and ``RandomHorizontalFlip`` (``prob``, default 0.5; any module path) map
     onto ``RandomHorizontalFlip``.  albumentations itself is not used: every other entry is skipped with one warning naming it."""
-    import logging
     log = log or logging.getLogger(__name__)
     found = None
-    for e in entries or []:
-        name = str(e.get("class_name", "")) if isinstance(e, dict) else str(e)
-        params = dict(e.get("params") or {}) if isinstance(e, dict) else {}
+    for name, params in _entries(entries):
         short = name.rsplit(".", 1)[-1]
         if name in ("albumentations.HorizontalFlip", "HorizontalFlip"):
-            p = 1.0 if params.get("always_apply") else float(params.get("p", 0.5))
+            p = _entry_p(params, 0.5)
         elif short == "RandomHorizontalFlip":
             p = float(params.get("prob", params.get("p", 0.5)))
         elif name in _COLOR_JITTER_NAMES or name in _BBOX_CROP_NAMES or name in _SHIFT_SCALE_ROTATE_NAMES:

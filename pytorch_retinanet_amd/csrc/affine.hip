@@ -23,6 +23,8 @@
 // aligned a thread's pixels are four neighbours of one row and leave as one 16-byte store per channel (a wave writes 128-byte row
 // segments); else they are one column position in four rows and a wave writes 128-byte row segments with 4-byte stores.  An image
 // that is left alone (applied = 0) takes a flat copy: the branch depends on blockIdx.y alone, so it is uniform across the block.
+#include <stddef.h>
+
 #include "rn_common.hpp"
 #include "rn_draw.hpp"
 
@@ -67,6 +69,11 @@ __device__ __forceinline__ void row_range(const int32_t *__restrict__ gt_off, co
     lo = lo < 0 ? 0 : (lo > rows ? rows : lo);                                  // (device data: the rows stay inside the buffers)
     hi = hi < lo ? lo : (hi > rows ? rows : hi);
 }
+
+// (the Python side packs the block by these offsets -- draw_state.py's layout table: a struct edit that it does not follow fails here)
+static_assert(sizeof(rn_affine_state) == 56 && offsetof(rn_affine_state, seed) == 0 && offsetof(rn_affine_state, counter) == 8 &&
+                  offsetof(rn_affine_state, p) == 16 && offsetof(rn_affine_state, min_visibility) == 20 && offsetof(rn_affine_state, lo) == 24 &&
+                  offsetof(rn_affine_state, hi) == 40, "draw_state.AFFINE");
 
 // one wave per image (blockIdx.x); the state block is only read here
 __global__ __launch_bounds__(AF_WAVE) void affine_coef_kernel(const rn_affine_state *__restrict__ st, const rn::f32x4 *__restrict__ in,
@@ -180,13 +187,6 @@ __global__ __launch_bounds__(AF_WAVE) void affine_rows_kernel(const rn_affine_st
         }
         at += __popcll(mask);
     }
-}
-
-// (one wave: every lane reads the counter, in program order before lane 0's store; stream order puts it behind every wave of the draw)
-__global__ __launch_bounds__(AF_WAVE) void affine_advance_kernel(rn_affine_state *st)
-{
-    const int64_t counter = st->counter;
-    if (threadIdx.x == 0) st->counter = counter + 1;
 }
 
 // ---- the warp ------------------------------------------------------------------------------------------------------------------
@@ -322,7 +322,7 @@ RN_API int rn_affine_draw(rn_affine_state *state, const float *gt_boxes, const i
                        in_hw_dev, coef, (int32_t)rows);
     hipLaunchKernelGGL(affine_rows_kernel, dim3((unsigned)B), dim3(AF_WAVE), 0, (hipStream_t)stream, state, (const rn::f32x4 *)gt_boxes, gt_labels,
                        gt_off, in_hw_dev, coef, B, (rn::f32x4 *)out_boxes, out_labels, out_gt_off, (int32_t)rows);
-    hipLaunchKernelGGL(affine_advance_kernel, dim3(1), dim3(AF_WAVE), 0, (hipStream_t)stream, state);
+    hipLaunchKernelGGL(draw_advance_kernel, dim3(1), dim3(DRAW_ADVANCE_BLOCK), 0, (hipStream_t)stream, &state->counter);
     RN_LAUNCH_CHECK();
     return RN_OK;
 }

@@ -74,16 +74,23 @@
 // The draw is one wave per image: the lanes walk the image's rows, the union of the boxes is a wave reduction (no atomics), every lane
 // then computes the same rectangle (the numbered rule in include/retinanet_hip.h; augment.BBoxSafeRandomCrop.draw_rects restates it) and
 // the lanes write the shifted rows.  Every wave reads the counter, so it is advanced by a single-wave launch of its own behind the
-// draw.  The copy is a bandwidth kernel with a fixed grid (CS_BLOCKS blocks per image): a thread gathers four consecutive floats of the
+// draw (draw_advance_kernel, rn_draw.hpp).  The copy is a bandwidth kernel with a fixed grid (CS_BLOCKS blocks per image): a thread gathers four consecutive floats of the
 // dense destination -- the source rows start at x0 and are only 4-byte aligned, so they are read as four 4-byte loads, which the lanes
 // of a wave still coalesce -- and writes them as one 16-byte store when the destination slot is 16-byte aligned.
 #include "rn_color.hpp"
 #include "rn_common.hpp"
-#include "rn_draw.hpp"              // hflip_u: the hash stated above, shared with affine.hip
+#include <stddef.h>
+
+#include "rn_draw.hpp"              // hflip_u: the hash stated above, and draw_advance_kernel, shared with affine.hip
 
 namespace {
 
 constexpr int HF_BLOCK = 64;        // one wave: the counter update needs no barrier across waves
+
+// (every static_assert on a state struct below: the Python side packs the block by these offsets -- draw_state.py's layout table --
+// so a struct edit that the table does not follow fails the build)
+static_assert(sizeof(rn_hflip_state) == 24 && offsetof(rn_hflip_state, seed) == 0 && offsetof(rn_hflip_state, counter) == 8 &&
+                  offsetof(rn_hflip_state, p) == 16, "draw_state.HFLIP");
 
 __global__ __launch_bounds__(HF_BLOCK) void hflip_draw_kernel(rn_hflip_state *st, const int B, uint8_t *__restrict__ flags)
 {
@@ -114,6 +121,11 @@ __device__ __forceinline__ void resize_plan(const int h, const int w, const int 
 }
 
 struct ShortSideTable { int32_t ih[SS_MAX_IMAGES], iw[SS_MAX_IMAGES]; };
+
+// (the layout's ``sizes`` field is n, the reserved word and the 16 entries: bytes 16..88)
+static_assert(sizeof(rn_short_side_state) == 24 + 4 * RN_SHORT_SIDE_MAX && RN_SHORT_SIDE_MAX == 16 && offsetof(rn_short_side_state, seed) == 0 &&
+                  offsetof(rn_short_side_state, counter) == 8 && offsetof(rn_short_side_state, n) == 16 &&
+                  offsetof(rn_short_side_state, reserved) == 20 && offsetof(rn_short_side_state, sizes) == 24, "draw_state.SHORT_SIDE");
 
 __global__ __launch_bounds__(HF_BLOCK) void short_side_draw_kernel(rn_short_side_state *st, const ShortSideTable t, const int cnt, const int base,
                                                                   const int max_size, const int advance, int32_t *__restrict__ out_hw,
@@ -187,6 +199,10 @@ __device__ __forceinline__ int color_order(int idx, const int mask)
     }
     return order;
 }
+
+static_assert(sizeof(rn_color_jitter_state) == 56 && offsetof(rn_color_jitter_state, seed) == 0 && offsetof(rn_color_jitter_state, counter) == 8 &&
+                  offsetof(rn_color_jitter_state, p) == 16 && offsetof(rn_color_jitter_state, lo) == 20 && offsetof(rn_color_jitter_state, hi) == 36 &&
+                  offsetof(rn_color_jitter_state, enabled_mask) == 52, "draw_state.COLOR_JITTER");
 
 __global__ __launch_bounds__(HF_BLOCK) void color_jitter_draw_kernel(rn_color_jitter_state *st, const int B, rn_color_coef *__restrict__ coef)
 {
@@ -300,6 +316,9 @@ __device__ __forceinline__ void crop_axis(const float u_lo, const float u_hi, co
     end = u2 + (c < n - u2 ? c : n - u2);
 }
 
+static_assert(sizeof(rn_bbox_crop_state) == 24 && offsetof(rn_bbox_crop_state, seed) == 0 && offsetof(rn_bbox_crop_state, counter) == 8 &&
+                  offsetof(rn_bbox_crop_state, p) == 16, "draw_state.BBOX_CROP");
+
 // one wave per image (blockIdx.x); the state block is only read here
 __global__ __launch_bounds__(HF_BLOCK) void bbox_crop_draw_kernel(const rn_bbox_crop_state *__restrict__ st, const rn::f32x4 *__restrict__ in,
                                                                  const int32_t *__restrict__ gt_off, const int32_t *__restrict__ in_hw,
@@ -379,13 +398,6 @@ __global__ __launch_bounds__(HF_BLOCK) void bbox_crop_draw_kernel(const rn_bbox_
     }
 }
 
-// (one wave: every lane reads the counter, in program order before lane 0's store; stream order puts it behind every wave of the draw)
-__global__ __launch_bounds__(HF_BLOCK) void bbox_crop_advance_kernel(rn_bbox_crop_state *st)
-{
-    const int64_t counter = st->counter;
-    if (threadIdx.x == 0) st->counter = counter + 1;
-}
-
 constexpr int CS_BLOCKS = 256;      // blocks per image: fixed, so neither the grid nor an argument depends on a size
 constexpr int CS_BLOCK = 256;
 
@@ -459,7 +471,7 @@ RN_API int rn_bbox_crop_draw(rn_bbox_crop_state *state, const float *gt_boxes, c
         return RN_EALIGN;
     hipLaunchKernelGGL(bbox_crop_draw_kernel, dim3((unsigned)B), dim3(HF_BLOCK), 0, (hipStream_t)stream, state, (const rn::f32x4 *)gt_boxes,
                        gt_off, in_hw_dev, rect, crop_hw, (rn::f32x4 *)out_boxes, (int32_t)rows);
-    hipLaunchKernelGGL(bbox_crop_advance_kernel, dim3(1), dim3(HF_BLOCK), 0, (hipStream_t)stream, state);
+    hipLaunchKernelGGL(draw_advance_kernel, dim3(1), dim3(DRAW_ADVANCE_BLOCK), 0, (hipStream_t)stream, &state->counter);
     RN_LAUNCH_CHECK();
     return RN_OK;
 }

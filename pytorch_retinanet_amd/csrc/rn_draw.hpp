@@ -13,3 +13,14 @@ static __device__ __forceinline__ float hflip_u(const uint64_t seed, const int64
     z ^= z >> 31;
     return (float)(uint32_t)(z >> 40) * 0x1p-24f;
 }
+
+// counter += 1 as a launch of its own, <<<1, DRAW_ADVANCE_BLOCK>>>, for a draw whose every wave reads the counter: launched LAST, so
+// stream order puts it behind every wave of the draw.  (One wave: every lane reads the counter, in program order before lane 0's
+// store.)  ``counter``: the address of a state block's counter field.
+constexpr int DRAW_ADVANCE_BLOCK = 64;
+
+static __global__ __launch_bounds__(DRAW_ADVANCE_BLOCK) void draw_advance_kernel(int64_t *counter)
+{
+    const int64_t c = *counter;
+    if (threadIdx.x == 0) *counter = c + 1;
+}

@@ -6,14 +6,14 @@ the HIP library, never synchronises with the host, and REFUSES CPU tensors --
 there is no CPU implementation of this path in the product.
 """
 import ctypes as C
-import struct
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, draw_state
 from ._launch import zero_page
+from .draw_state import AFFINE, BBOX_CROP, COLOR_IDENTITY, COLOR_JITTER, COLOR_OPS, HFLIP, SHORT_SIDE, SHORT_SIDE_MAX  # noqa: F401
 from ._lib import RN_BF16, RN_F16, RN_F32, RnDetectParams, RnLevel, RnLossParams, check, lib
 
 RN_MATCH_NUM_FG_ZEROED, RN_MATCH_FLAGGED_ONLY = 1, 2          # include/retinanet_hip.h
@@ -646,8 +646,10 @@ def transform_batch_dev(images: Sequence[Tensor], out_hw: Tensor, mean: Sequence
 
 
 # ---- train-time horizontal flip (augment.RandomHorizontalFlip) ----------------------------------------------------------------
-_HFLIP_FIELDS = {"seed": (0, "<Q"), "counter": (8, "<q"), "p": (16, "<f")}     # include/retinanet_hip.h: rn_hflip_state
-HFLIP_STATE_BYTES = 24
+# The state blocks of the draws below are made, written and read by ``draw_state`` (new / write / read with its layouts); the draw
+# launchers validate theirs through ``draw_state.check``.
+HFLIP_STATE_BYTES, SHORT_SIDE_STATE_BYTES, COLOR_JITTER_STATE_BYTES = HFLIP.nbytes, SHORT_SIDE.nbytes, COLOR_JITTER.nbytes
+BBOX_CROP_STATE_BYTES, AFFINE_STATE_BYTES = BBOX_CROP.nbytes, AFFINE.nbytes
 
 
 def _check_flags(flags: Tensor, B: int, dev: torch.device) -> None:
@@ -656,40 +658,11 @@ def _check_flags(flags: Tensor, B: int, dev: torch.device) -> None:
                          f"on {flags.device}")
 
 
-def hflip_state(dev: torch.device, seed: int, counter: int, p: float) -> Tensor:
-    "A new ``rn_hflip_state`` block (uint8 [24]) on ``dev`` holding seed / counter / p: one host->device copy, outside any capture."
-    block = torch.empty((HFLIP_STATE_BYTES,), dtype=torch.uint8, device=dev)
-    block[20:].zero_()
-    hflip_state_write(block, seed=seed, counter=counter, p=p)
-    return block
-
-
-def hflip_state_write(block: Tensor, seed: Optional[int] = None, counter: Optional[int] = None, p: Optional[float] = None) -> None:
-    """Overwrite the given fields of an ``rn_hflip_state`` block (the others keep their device values): host->device copies on the
-    current stream, so they are ordered with the draws around them.  Not inside a capture: the values would be baked into the graph."""
-    _need_dev(block)
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("hflip_state_write inside a stream capture")
-    for name, v in (("seed", seed), ("counter", counter), ("p", p)):
-        if v is None:
-            continue
-        off, fmt = _HFLIP_FIELDS[name]
-        raw = struct.pack(fmt, (int(v) & (2 ** 64 - 1)) if name == "seed" else (int(v) if name == "counter" else float(v)))
-        block[off:off + len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
-
-
-def hflip_state_read(block: Tensor) -> Tuple[int, int, float]:
-    "(seed, counter, p) of an ``rn_hflip_state`` block: one device->host copy (synchronises)."
-    raw = bytes(block.cpu().numpy().tobytes())
-    return tuple(struct.unpack_from(fmt, raw, off)[0] for off, fmt in _HFLIP_FIELDS.values())
-
-
 def hflip_draw(block: Tensor, B: int) -> Tensor:
     """``rn_hflip_draw``: flags uint8 [B] (1 = flip image b) drawn from the block's seed / counter / p, then the block's counter advances
     by one -- one launch on the current stream, no host synchronisation (capturable: each replay draws anew)."""
     dev = _need_dev(block)
-    if block.dtype != torch.uint8 or block.numel() != HFLIP_STATE_BYTES or block.data_ptr() % 8:
-        raise ValueError("block must be an rn_hflip_state made by hflip_state()")
+    draw_state.check(HFLIP, block)
     B = int(B)
     if B <= 0:
         raise ValueError(f"B must be positive, got {B}")
@@ -700,18 +673,7 @@ def hflip_draw(block: Tensor, B: int) -> Tensor:
 
 
 # ---- train-time colour jitter (augment.ColorJitter) ----------------------------------------------------------------------------
-# include/retinanet_hip.h: rn_color_jitter_state = seed u64, counter i64, p f32, lo f32[4], hi f32[4], enabled_mask i32
-COLOR_JITTER_STATE_BYTES = 56
 COLOR_COEF_FLOATS = 8                  # rn_color_coef: f f32[4], mean f32, order i32, pad i32[2]
-COLOR_OPS = ("brightness", "contrast", "saturation", "hue")        # the operation ids 0..3
-COLOR_IDENTITY = (1.0, 1.0, 1.0, 0.0)  # the factor that leaves the pixel alone (what a disabled operation's range holds)
-
-
-def _check_color_block(block: Tensor) -> torch.device:
-    dev = _need_dev(block)
-    if block.dtype != torch.uint8 or block.numel() != COLOR_JITTER_STATE_BYTES or block.data_ptr() % 8:
-        raise ValueError("block must be an rn_color_jitter_state made by color_jitter_state()")
-    return dev
 
 
 def _check_coef(coef: Tensor, B: int, dev: torch.device) -> None:
@@ -720,51 +682,12 @@ def _check_coef(coef: Tensor, B: int, dev: torch.device) -> None:
                          f"{tuple(coef.shape)} {coef.dtype} on {coef.device}")
 
 
-def color_jitter_state(dev: torch.device, seed: int, counter: int, p: float, lo: Sequence[float], hi: Sequence[float],
-                       enabled_mask: int) -> Tensor:
-    "A new ``rn_color_jitter_state`` block (uint8 [56]) on ``dev``: one host->device copy, outside any capture."
-    block = torch.empty((COLOR_JITTER_STATE_BYTES,), dtype=torch.uint8, device=dev)
-    color_jitter_state_write(block, seed=seed, counter=counter, p=p, lo=lo, hi=hi, enabled_mask=enabled_mask)
-    return block
-
-
-def color_jitter_state_write(block: Tensor, seed: Optional[int] = None, counter: Optional[int] = None, p: Optional[float] = None,
-                             lo: Optional[Sequence[float]] = None, hi: Optional[Sequence[float]] = None,
-                             enabled_mask: Optional[int] = None) -> None:
-    """Overwrite the given fields of an ``rn_color_jitter_state`` block (the others keep their device values): host->device copies on
-    the current stream, ordered with the draws around them.  Not inside a capture: the values would be baked into the graph."""
-    _check_color_block(block)
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("color_jitter_state_write inside a stream capture")
-    parts = []
-    if seed is not None:
-        parts.append((0, struct.pack("<Q", int(seed) & (2 ** 64 - 1))))
-    if counter is not None:
-        parts.append((8, struct.pack("<q", int(counter))))
-    if p is not None:
-        parts.append((16, struct.pack("<f", float(p))))
-    if lo is not None:
-        parts.append((20, struct.pack("<4f", *[float(v) for v in lo])))
-    if hi is not None:
-        parts.append((36, struct.pack("<4f", *[float(v) for v in hi])))
-    if enabled_mask is not None:
-        parts.append((52, struct.pack("<i", int(enabled_mask) & 0xF)))
-    for off, raw in parts:
-        block[off:off + len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
-
-
-def color_jitter_state_read(block: Tensor) -> Tuple[int, int, float, Tuple[float, ...], Tuple[float, ...], int]:
-    "(seed, counter, p, lo, hi, enabled_mask) of an ``rn_color_jitter_state`` block: one device->host copy (synchronises)."
-    _check_color_block(block)
-    v = struct.unpack("<Qqf4f4fi", bytes(block.cpu().numpy().tobytes()))
-    return v[0], v[1], v[2], tuple(v[3:7]), tuple(v[7:11]), v[11]
-
-
 def color_jitter_draw(block: Tensor, B: int) -> Tensor:
     """``rn_color_jitter_draw``: coef f32 [B, 8] (``rn_color_coef`` per image: four factors, mean = 0, the order as int32 bits in column
     5) drawn from the block, then the block's counter advances by one -- one launch on the current stream for any B, no host
     synchronisation (capturable: each replay draws anew)."""
-    dev = _check_color_block(block)
+    dev = _need_dev(block)
+    draw_state.check(COLOR_JITTER, block)
     B = int(B)
     if B <= 0:
         raise ValueError(f"B must be positive, got {B}")
@@ -841,59 +764,12 @@ def gt_flip_scale_packed(gt: PackedGT, widths: Sequence[float], ratios: Sequence
 
 
 # ---- multi-scale training: the short side drawn on the device (augment.RandomShortSide) ---------------------------------------
-SHORT_SIDE_MAX = 16                      # include/retinanet_hip.h: RN_SHORT_SIDE_MAX
-SHORT_SIDE_STATE_BYTES = 24 + 4 * SHORT_SIDE_MAX     # rn_short_side_state: seed u64, counter i64, n i32, reserved i32, sizes i32[16]
-
-
-def _check_short_side_block(block: Tensor) -> torch.device:
-    dev = _need_dev(block)
-    if block.dtype != torch.uint8 or block.numel() != SHORT_SIDE_STATE_BYTES or block.data_ptr() % 8:
-        raise ValueError("block must be an rn_short_side_state made by short_side_state()")
-    return dev
-
-
-def short_side_state(dev: torch.device, seed: int, counter: int, sizes: Sequence[int]) -> Tensor:
-    "A new ``rn_short_side_state`` block (uint8 [88]) on ``dev``: one host->device copy, outside any capture."
-    block = torch.empty((SHORT_SIDE_STATE_BYTES,), dtype=torch.uint8, device=dev)
-    short_side_state_write(block, seed=seed, counter=counter, sizes=sizes)
-    return block
-
-
-def short_side_state_write(block: Tensor, seed: Optional[int] = None, counter: Optional[int] = None,
-                           sizes: Optional[Sequence[int]] = None) -> None:
-    """Overwrite the given fields of an ``rn_short_side_state`` block (the others keep their device values; ``sizes`` writes n, the
-    reserved word and all 16 entries): host->device copies on the current stream, ordered with the draws around them.  Not inside
-    a capture: the values would be baked into the graph."""
-    _check_short_side_block(block)
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("short_side_state_write inside a stream capture")
-    parts = []
-    if seed is not None:
-        parts.append((0, struct.pack("<Q", int(seed) & (2 ** 64 - 1))))
-    if counter is not None:
-        parts.append((8, struct.pack("<q", int(counter))))
-    if sizes is not None:
-        sizes = [int(v) for v in sizes]
-        if not 1 <= len(sizes) <= SHORT_SIDE_MAX or min(sizes) <= 0:
-            raise ValueError(f"need 1..{SHORT_SIDE_MAX} positive short sides, got {sizes}")
-        parts.append((16, struct.pack(f"<ii{SHORT_SIDE_MAX}i", len(sizes), 0, *(sizes + [sizes[-1]] * (SHORT_SIDE_MAX - len(sizes))))))
-    for off, raw in parts:
-        block[off:off + len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
-
-
-def short_side_state_read(block: Tensor) -> Tuple[int, int, Tuple[int, ...]]:
-    "(seed, counter, sizes) of an ``rn_short_side_state`` block: one device->host copy (synchronises)."
-    _check_short_side_block(block)
-    raw = bytes(block.cpu().numpy().tobytes())
-    seed, counter, n, _ = struct.unpack_from("<Qqii", raw, 0)
-    return seed, counter, tuple(struct.unpack_from(f"<{SHORT_SIDE_MAX}i", raw, 24)[:max(0, min(n, SHORT_SIDE_MAX))])
-
-
 def short_side_draw(block: Tensor, in_hw: Sequence[Tuple[int, int]], max_size: int) -> Tuple[Tensor, Tensor]:
     """``rn_short_side_draw``: for the images of sizes ``in_hw`` ((h, w) host ints) the resized sizes int32 [B, 2] and the box ratios
     f32 [2B] = (rh, rw) per image, drawn from the block's seed / counter / sizes, then the block's counter advances by one -- one
     launch per 64 images on the current stream, no host synchronisation (capturable: each replay draws anew)."""
-    dev = _check_short_side_block(block)
+    dev = _need_dev(block)
+    draw_state.check(SHORT_SIDE, block)
     B = len(in_hw)
     if B == 0:
         raise ValueError("need at least one image size")
@@ -1020,7 +896,9 @@ def resize_plan_dev(block: Optional[Tensor], in_hw: Tensor, short: Optional[int]
     it) -> (resized sizes int32 [B, 2], box ratios f32 [2B]).  With ``block`` (an ``rn_short_side_state``) the short sides are drawn
     as ``short_side_draw`` draws them and the block's counter advances by one; with ``block=None`` every image gets ``short``.
     One launch for any B on the current stream, no host synchronisation (capturable)."""
-    dev = _need_dev(in_hw) if block is None else _check_short_side_block(block)
+    dev = _need_dev(in_hw if block is None else block)
+    if block is not None:
+        draw_state.check(SHORT_SIDE, block)
     if in_hw.dtype != torch.int32 or in_hw.dim() != 2 or in_hw.shape[1] != 2 or not in_hw.is_contiguous() or in_hw.device != dev:
         raise ValueError(f"in_hw must be a contiguous int32 [B, 2] tensor on {dev}, got {tuple(in_hw.shape)} {in_hw.dtype} on {in_hw.device}")
     B = int(in_hw.shape[0])
@@ -1083,12 +961,6 @@ def gt_flip_scale_packed_var(gt: PackedGT, in_hw: Tensor, ratios: Tensor, flags:
 
 
 # ---- train-time bbox-safe random crop (augment.BBoxSafeRandomCrop): a second staging pass ------------------------------------
-# include/retinanet_hip.h: rn_bbox_crop_state = seed u64, counter i64, p f32, reserved i32 -- the layout of rn_hflip_state, so the
-# block is made, written and read by hflip_state / hflip_state_write / hflip_state_read
-BBOX_CROP_STATE_BYTES = HFLIP_STATE_BYTES
-bbox_crop_state, bbox_crop_state_write, bbox_crop_state_read = hflip_state, hflip_state_write, hflip_state_read
-
-
 def bbox_crop_draw(block: Tensor, in_hw: Tensor, gt: PackedGT) -> Tuple[Tensor, Tensor, Tensor]:
     """``rn_bbox_crop_draw``: per image the crop rectangle drawn from the block's seed / counter / p around the union of its boxes ->
     (rect int32 [B, 4] = (y0, x0, ch, cw), crop_hw int32 [B, 2] = (ch, cw), the boxes shifted by (x0, y0) in a fresh f32 [rows, 4]
@@ -1096,8 +968,7 @@ def bbox_crop_draw(block: Tensor, in_hw: Tensor, gt: PackedGT) -> Tuple[Tensor, 
     device (``StagedImages.in_hw``).  One wave per image plus the counter's single-wave launch, on the current stream, no host
     synchronisation (capturable: each replay draws anew)."""
     dev = _need_dev(block, in_hw, gt.gt_boxes, gt.gt_off)
-    if block.dtype != torch.uint8 or block.numel() != BBOX_CROP_STATE_BYTES or block.data_ptr() % 8:
-        raise ValueError("block must be an rn_bbox_crop_state made by bbox_crop_state()")
+    draw_state.check(BBOX_CROP, block)
     if in_hw.dtype != torch.int32 or tuple(in_hw.shape) != (gt.B, 2) or not in_hw.is_contiguous():
         raise ValueError(f"in_hw must be a contiguous int32 [{gt.B}, 2] tensor, got {tuple(in_hw.shape)} {in_hw.dtype}")
     if gt.gt_boxes.dtype != torch.float32 or not gt.gt_boxes.is_contiguous() or gt.gt_boxes.data_ptr() % 16:
@@ -1145,57 +1016,7 @@ def bbox_crop_staged(crop, staged: StagedImages, packed: PackedGT) -> Tuple[Stag
 
 
 # ---- train-time shift / scale / rotate (augment.ShiftScaleRotate): a second staging pass --------------------------------------
-# include/retinanet_hip.h: rn_affine_state = seed u64, counter i64, p f32, min_visibility f32, lo f32[4], hi f32[4] with the ranges
-# of (angle, scale, dx, dy); rn_affine_coef = m f32[6], inv f32[6], applied i32, kept i32, reserved i32[2]
-AFFINE_STATE_BYTES = 56
-AFFINE_COEF_WORDS = 16
-
-
-def _check_affine_block(block: Tensor) -> torch.device:
-    dev = _need_dev(block)
-    if block.dtype != torch.uint8 or block.numel() != AFFINE_STATE_BYTES or block.data_ptr() % 8:
-        raise ValueError("block must be an rn_affine_state made by affine_state()")
-    return dev
-
-
-def affine_state(dev: torch.device, seed: int, counter: int, p: float, min_visibility: float, lo: Sequence[float],
-                 hi: Sequence[float]) -> Tensor:
-    "A new ``rn_affine_state`` block (uint8 [56]) on ``dev``: one host->device copy, outside any capture."
-    block = torch.empty((AFFINE_STATE_BYTES,), dtype=torch.uint8, device=dev)
-    affine_state_write(block, seed=seed, counter=counter, p=p, min_visibility=min_visibility, lo=lo, hi=hi)
-    return block
-
-
-def affine_state_write(block: Tensor, seed: Optional[int] = None, counter: Optional[int] = None, p: Optional[float] = None,
-                       min_visibility: Optional[float] = None, lo: Optional[Sequence[float]] = None,
-                       hi: Optional[Sequence[float]] = None) -> None:
-    """Overwrite the given fields of an ``rn_affine_state`` block (the others keep their device values): host->device copies on the
-    current stream, ordered with the draws around them.  Not inside a capture: the values would be baked into the graph."""
-    _check_affine_block(block)
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("affine_state_write inside a stream capture")
-    parts = []
-    if seed is not None:
-        parts.append((0, struct.pack("<Q", int(seed) & (2 ** 64 - 1))))
-    if counter is not None:
-        parts.append((8, struct.pack("<q", int(counter))))
-    if p is not None:
-        parts.append((16, struct.pack("<f", float(p))))
-    if min_visibility is not None:
-        parts.append((20, struct.pack("<f", float(min_visibility))))
-    if lo is not None:
-        parts.append((24, struct.pack("<4f", *[float(v) for v in lo])))
-    if hi is not None:
-        parts.append((40, struct.pack("<4f", *[float(v) for v in hi])))
-    for off, raw in parts:
-        block[off:off + len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
-
-
-def affine_state_read(block: Tensor) -> Tuple[int, int, float, float, Tuple[float, ...], Tuple[float, ...]]:
-    "(seed, counter, p, min_visibility, lo, hi) of an ``rn_affine_state`` block: one device->host copy (synchronises)."
-    _check_affine_block(block)
-    v = struct.unpack("<Qqff4f4f", bytes(block.cpu().numpy().tobytes()))
-    return v[0], v[1], v[2], v[3], tuple(v[4:8]), tuple(v[8:12])
+AFFINE_COEF_WORDS = 16                 # rn_affine_coef: m f32[6], inv f32[6], applied i32, kept i32, reserved i32[2]
 
 
 def affine_coef_views(coef: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
@@ -1210,7 +1031,7 @@ def affine_draw(block: Tensor, in_hw: Tensor, gt: PackedGT) -> Tuple[Tensor, Pac
     ``in_hw``: int32 [B, 2] on the device (``StagedImages.in_hw``).  Three launches on the current stream, no atomics, no host
     synchronisation (capturable: each replay draws anew)."""
     dev = _need_dev(block, in_hw, gt.gt_boxes, gt.gt_labels, gt.gt_off)
-    _check_affine_block(block)
+    draw_state.check(AFFINE, block)
     if in_hw.dtype != torch.int32 or tuple(in_hw.shape) != (gt.B, 2) or not in_hw.is_contiguous():
         raise ValueError(f"in_hw must be a contiguous int32 [{gt.B}, 2] tensor, got {tuple(in_hw.shape)} {in_hw.dtype}")
     if gt.gt_boxes.dtype != torch.float32 or not gt.gt_boxes.is_contiguous() or gt.gt_boxes.data_ptr() % 16:

@@ -70,29 +70,29 @@ def batch():
 
 # ---- 1. the draw ------------------------------------------------------------------------------------------------------
 def test_draw_equals_the_restatement_and_advances_the_counter(batch):
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     ims, boxes, rects = batch
     staged, gt = _stage(ims, boxes)
-    block = ops.bbox_crop_state(torch.device(DEV), SEED, 0, P)
+    block = draw_state.new(draw_state.BBOX_CROP, torch.device(DEV), seed=SEED, counter=0, p=P)
     for k in range(3):
         rect, crop_hw, out = ops.bbox_crop_draw(block, staged.in_hw, gt)
         # (a fresh buffer per call: prefilled here through the allocator is not possible, so the untouched rows are checked in the next test)
         assert [tuple(r) for r in rect.tolist()] == rects[k], k
         assert crop_hw.tolist() == [[r[2], r[3]] for r in rects[k]]
         _check_boxes(out, boxes, rects[k])
-        assert ops.bbox_crop_state_read(block)[1] == k + 1                                 # the counter = the number of calls
+        assert draw_state.read(draw_state.BBOX_CROP, block)[1] == k + 1                                 # the counter = the number of calls
     assert torch.equal(gt.gt_boxes[: sum(b.shape[0] for b in boxes)].cpu(), torch.cat(boxes))  # out of place: the input is not written
 
 
 def test_rows_past_the_last_image_are_not_written(batch):
     "The library call itself, on an output buffer prefilled with a sentinel."
     import ctypes as C
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     from pytorch_retinanet_amd._lib import check, lib
     ims, boxes, rects = batch
     staged, gt = _stage(ims, boxes)
     dev = torch.device(DEV)
-    block = ops.bbox_crop_state(dev, SEED, 1, P)
+    block = draw_state.new(draw_state.BBOX_CROP, dev, seed=SEED, counter=1, p=P)
     rect = torch.full((5, 4), -1, dtype=torch.int32, device=dev)
     crop_hw = torch.full((5, 2), -1, dtype=torch.int32, device=dev)
     out = torch.full_like(gt.gt_boxes, SENTINEL)
@@ -104,7 +104,7 @@ def test_rows_past_the_last_image_are_not_written(batch):
 
 
 def test_identity_for_a_non_finite_box_an_empty_image_and_p_zero(batch):
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     from pytorch_retinanet_amd.augment import BBoxSafeRandomCrop
     ims, boxes, _ = batch
     broken = [b.clone() for b in boxes]
@@ -113,7 +113,7 @@ def test_identity_for_a_non_finite_box_an_empty_image_and_p_zero(batch):
     staged, gt = _stage(ims, broken)
     staged.in_hw[3] = 0                                                                    # an empty image: (0, 0)
     sizes = [s if b != 3 else (0, 0) for b, s in enumerate(SIZES)]
-    block = ops.bbox_crop_state(torch.device(DEV), SEED, 0, 1.0)
+    block = draw_state.new(draw_state.BBOX_CROP, torch.device(DEV), seed=SEED, counter=0, p=1.0)
     want = BBoxSafeRandomCrop.draw_rects(SEED, 0, sizes, broken, 1.0)
     assert want[1] == FULL[1] and want[4] == FULL[4] and want[3] == (0, 0, 0, 0) and want[0] != FULL[0]
     rect, crop_hw, out = ops.bbox_crop_draw(block, staged.in_hw, gt)
@@ -124,7 +124,7 @@ def test_identity_for_a_non_finite_box_an_empty_image_and_p_zero(batch):
     dst = ops.StagedImages(torch.full_like(staged.arena, SENTINEL), torch.empty_like(staged.in_hw))
     res = ops.image_crop_stage(staged, rect, crop_hw, out=dst)
     assert bool((res.arena[3] == SENTINEL).all()) and res.in_hw.tolist()[3] == [0, 0]
-    ops.bbox_crop_state_write(block, p=0.0)
+    draw_state.write(draw_state.BBOX_CROP, block, p=0.0)
     rect, _, out = ops.bbox_crop_draw(block, staged.in_hw, gt)
     assert [tuple(r) for r in rect.tolist()] == [f if b != 3 else (0, 0, 0, 0) for b, f in enumerate(FULL)]
     assert torch.equal(_bits(out[:n]), _bits(gt.gt_boxes[:n]))
@@ -132,7 +132,7 @@ def test_identity_for_a_non_finite_box_an_empty_image_and_p_zero(batch):
 
 def test_draw_does_not_depend_on_64_images():
     "B = 130: more images than a wave has lanes, every third one without boxes."
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     from pytorch_retinanet_amd.augment import BBoxSafeRandomCrop
     dev = torch.device(DEV)
     rng = np.random.default_rng(2)
@@ -146,10 +146,10 @@ def test_draw_does_not_depend_on_64_images():
     gt = ops.PackedGT.empty(B, CAP, dev)
     ops.gt_stage([b.to(dev) for b in boxes], [torch.ones((b.shape[0],), dtype=torch.int64, device=dev) for b in boxes], gt)
     in_hw = torch.tensor(sizes, dtype=torch.int32).to(dev)
-    block = ops.bbox_crop_state(dev, 5, 7, 0.9)
+    block = draw_state.new(draw_state.BBOX_CROP, dev, seed=5, counter=7, p=0.9)
     rect, crop_hw, out = ops.bbox_crop_draw(block, in_hw, gt)
     want = BBoxSafeRandomCrop.draw_rects(5, 7, sizes, boxes, 0.9)
-    assert [tuple(r) for r in rect.tolist()] == want and ops.bbox_crop_state_read(block)[1] == 8
+    assert [tuple(r) for r in rect.tolist()] == want and draw_state.read(draw_state.BBOX_CROP, block)[1] == 8
     _check_boxes(out, boxes, want)
 
 

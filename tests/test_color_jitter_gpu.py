@@ -47,19 +47,19 @@ def _ulp_apart(a, b):
 # ---- 1. the draw ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", [1, 3, 64, 65])
 def test_draw_equals_the_restatement_bit_for_bit_and_advances_the_counter(B):
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     from pytorch_retinanet_amd.augment import ColorJitter
     cj = ColorJitter(p=0.8, seed=SEED, **RANGES)
     lo, hi = cj._lo_hi()
-    block = ops.color_jitter_state(torch.device(DEV), SEED, 0, 0.8, lo, hi, 0xF)
-    assert ops.color_jitter_state_read(block) == (SEED, 0, float(np.float32(0.8)), tuple(lo), tuple(hi), 0xF)
+    block = draw_state.new(draw_state.COLOR_JITTER, torch.device(DEV), seed=SEED, counter=0, p=0.8, lo=lo, hi=hi, enabled_mask=0xF)
+    assert draw_state.read(draw_state.COLOR_JITTER, block) == (SEED, 0, float(np.float32(0.8)), tuple(lo), tuple(hi), 0xF)
     for k in range(4):
         coef = ops.color_jitter_draw(block, B)
         assert coef.shape == (B, 8) and coef.dtype == torch.float32
         got, want = _rows(coef), cj.draw(k, B)
         assert [(f, o) for f, o, _ in got] == want, k                             # fp32 values as Python floats: equal = equal bits
         assert all(m == 0.0 for _, _, m in got) and not coef[:, 6:].any()
-        assert ops.color_jitter_state_read(block)[1] == k + 1                     # the counter = the number of calls
+        assert draw_state.read(draw_state.COLOR_JITTER, block)[1] == k + 1                     # the counter = the number of calls
 
 
 def test_rewritten_ranges_and_p_change_the_next_draw_without_a_new_object():

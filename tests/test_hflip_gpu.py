@@ -21,18 +21,18 @@ def _restated(seed, counter, B, p):
 # ---- 1. the draw ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", [1, 64, 65, 130])
 def test_draw_equals_the_restatement_and_advances_the_counter(B):
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     seed = 0x1234_5678_9ABC_DEF0 + B
-    block = ops.hflip_state(torch.device(DEV), seed, 0, 0.5)
+    block = draw_state.new(draw_state.HFLIP, torch.device(DEV), seed=seed, counter=0, p=0.5)
     for k in range(6):
         flags = ops.hflip_draw(block, B)
         assert flags.tolist() == _restated(seed, k, B, 0.5), k
-        assert ops.hflip_state_read(block) == (seed, k + 1, 0.5)
-    ops.hflip_state_write(block, p=0.0)
+        assert draw_state.read(draw_state.HFLIP, block) == (seed, k + 1, 0.5)
+    draw_state.write(draw_state.HFLIP, block, p=0.0)
     assert int(ops.hflip_draw(block, B).sum()) == 0
-    ops.hflip_state_write(block, p=1.0)
+    draw_state.write(draw_state.HFLIP, block, p=1.0)
     assert int(ops.hflip_draw(block, B).sum()) == B
-    assert ops.hflip_state_read(block) == (seed, 8, 1.0)
+    assert draw_state.read(draw_state.HFLIP, block) == (seed, 8, 1.0)
 
 
 def test_flip_object_state_dict_reads_the_device_counter():

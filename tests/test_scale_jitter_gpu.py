@@ -32,9 +32,9 @@ def _bits(t):
 
 # ---- 1. the draw ------------------------------------------------------------------------------------------------------
 def test_draw_equals_the_restatement_bit_for_bit_and_advances_the_counter():
-    from pytorch_retinanet_amd import ops
-    block = ops.short_side_state(torch.device(DEV), SEED, 0, SIZES)
-    assert ops.short_side_state_read(block) == (SEED, 0, SIZES)
+    from pytorch_retinanet_amd import draw_state, ops
+    block = draw_state.new(draw_state.SHORT_SIDE, torch.device(DEV), seed=SEED, counter=0, sizes=SIZES)
+    assert draw_state.read(draw_state.SHORT_SIDE, block) == (SEED, 0, SIZES)
     seen = set()
     for k in range(6):
         out_hw, ratios = ops.short_side_draw(block, SHAPES, MAX_SIZE)
@@ -42,27 +42,27 @@ def test_draw_equals_the_restatement_bit_for_bit_and_advances_the_counter():
         assert out_hw.dtype == torch.int32 and [tuple(r) for r in out_hw.tolist()] == hw, k
         want = torch.tensor([v for r in rr for v in r], dtype=torch.float32)
         assert torch.equal(_bits(ratios.cpu()), _bits(want)), k
-        assert ops.short_side_state_read(block)[1] == k + 1                  # the counter = the number of calls
+        assert draw_state.read(draw_state.SHORT_SIDE, block)[1] == k + 1                  # the counter = the number of calls
         seen.add(tuple(hw))
     assert len(seen) >= 4
-    ops.short_side_state_write(block, sizes=(32,), counter=0)                # one candidate: every image gets it, the seed is kept
+    draw_state.write(draw_state.SHORT_SIDE, block, sizes=(32,), counter=0)                # one candidate: every image gets it, the seed is kept
     out_hw, _ = ops.short_side_draw(block, SHAPES, MAX_SIZE)
     assert [tuple(r) for r in out_hw.tolist()] == _restated(SEED, 0, sizes=(32,))[0]
-    assert ops.short_side_state_read(block) == (SEED, 1, (32,))
+    assert draw_state.read(draw_state.SHORT_SIDE, block) == (SEED, 1, (32,))
 
 
 def test_draw_across_the_64_image_launch_table():
     "B = 66: two launches share one counter value; the images past the table boundary get their own sizes, the counter moves once."
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     shapes = [(8, 8)] * 66
-    block = ops.short_side_state(torch.device(DEV), 7, 0, (4, 8))
+    block = draw_state.new(draw_state.SHORT_SIDE, torch.device(DEV), seed=7, counter=0, sizes=(4, 8))
     for k in range(3):
         out_hw, ratios = ops.short_side_draw(block, shapes, 8)
         hw, rr = _restated(7, k, shapes, (4, 8), 8)
         assert [tuple(r) for r in out_hw.tolist()] == hw, k
         assert ratios.tolist() == [v for r in rr for v in r]
         assert {hw[64], hw[65]} <= {(4, 4), (8, 8)} and len(set(hw)) == 2
-        assert ops.short_side_state_read(block)[1] == k + 1
+        assert draw_state.read(draw_state.SHORT_SIDE, block)[1] == k + 1
     assert len({_restated(7, k, shapes, (4, 8), 8)[0][64] for k in range(3)} |
                {_restated(7, k, shapes, (4, 8), 8)[0][65] for k in range(3)}) == 2      # both sizes occur past the boundary
 
@@ -93,10 +93,10 @@ def test_object_state_lives_on_the_device():
 @pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
 @pytest.mark.parametrize("flip", [False, True], ids=["plain", "flip"])
 def test_transform_with_device_sizes_equals_the_transform_with_host_sizes(dtype, channels_last, flip):
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     images = _images()
     flags = torch.tensor([1, 0, 1, 1, 0], dtype=torch.uint8, device=DEV) if flip else None
-    block = ops.short_side_state(torch.device(DEV), SEED, 0, SIZES)
+    block = draw_state.new(draw_state.SHORT_SIDE, torch.device(DEV), seed=SEED, counter=0, sizes=SIZES)
     identity = 0
     for k in range(2):
         out_hw, _ = ops.short_side_draw(block, SHAPES, MAX_SIZE)
@@ -133,7 +133,7 @@ def _boxes(rng, counts, W=64, H=48):
 @pytest.mark.parametrize("flip", [False, True], ids=["plain", "flip"])
 @pytest.mark.parametrize("counts", [[3, 0, 5, 1, 2], [0, 0, 0, 0, 0]], ids=["B5", "no-boxes"])
 def test_box_kernels_with_device_ratios_equal_their_host_ratio_forms_and_torch(counts, flip):
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     from pytorch_retinanet_amd.transform import hflip_boxes, resize_boxes
     rng = np.random.default_rng(1 + sum(counts))
     B = len(SHAPES)
@@ -141,7 +141,7 @@ def test_box_kernels_with_device_ratios_equal_their_host_ratio_forms_and_torch(c
     widths = [float(w) for _, w in SHAPES]
     flags_l = [True, False, True, True, False] if flip else [False] * B
     flags = torch.tensor(flags_l, dtype=torch.uint8, device=DEV)
-    block = ops.short_side_state(torch.device(DEV), SEED, 1, SIZES)          # counter 1: two images keep their size (ratio 1)
+    block = draw_state.new(draw_state.SHORT_SIDE, torch.device(DEV), seed=SEED, counter=1, sizes=SIZES)          # counter 1: two images keep their size (ratio 1)
     _, ratios_dev = ops.short_side_draw(block, SHAPES, MAX_SIZE)
     sizes, ratios = _restated(SEED, 1)
     assert (1.0, 1.0) in ratios

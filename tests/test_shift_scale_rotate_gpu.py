@@ -108,7 +108,7 @@ def test_draw_equals_the_restatement_and_advances_the_counter(batch):
 def test_rows_past_the_last_image_are_not_written_and_two_calls_give_the_same_bits(batch):
     "The library call itself, on output buffers prefilled with a sentinel."
     import ctypes as C
-    from pytorch_retinanet_amd import ops
+    from pytorch_retinanet_amd import draw_state, ops
     from pytorch_retinanet_amd._lib import check, lib
     from pytorch_retinanet_amd.augment import AffineCoefs
     ims, boxes, labels, _ = batch
@@ -116,7 +116,7 @@ def test_rows_past_the_last_image_are_not_written_and_two_calls_give_the_same_bi
     dev = torch.device(DEV)
     res = []
     for _ in range(2):
-        block = ops.affine_state(dev, SEED, 0, 1.0, 0.0, (-45.0, 0.9, -0.0625, -0.0625), (45.0, 1.1, 0.0625, 0.0625))
+        block = draw_state.new(draw_state.AFFINE, dev, seed=SEED, counter=0, p=1.0, min_visibility=0.0, lo=(-45.0, 0.9, -0.0625, -0.0625), hi=(45.0, 1.1, 0.0625, 0.0625))
         coef = torch.full((5, ops.AFFINE_COEF_WORDS), -1, dtype=torch.int32, device=dev)
         ob, ol, oo = torch.full_like(gt.gt_boxes, SENTINEL), torch.full_like(gt.gt_labels, -9), torch.full_like(gt.gt_off, -1)
         check(lib.rn_affine_draw(block.data_ptr(), gt.gt_boxes.data_ptr(), gt.gt_labels.data_ptr(), gt.gt_off.data_ptr(), staged.in_hw.data_ptr(),

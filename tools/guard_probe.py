@@ -265,7 +265,7 @@ def main() -> None:
         # rn_affine_draw + rn_image_warp_stage (csrc/affine.hip) on hostile device data: the state block, the packed GT, the offsets,
         # the sizes, the coefficients, both arenas and every output end EXACTLY at the end of their mappings.  Image 1 claims h = 0,
         # image 3 a size no slot holds; gt_off starts below 0 and ends past rows.  Everything else must come out as the restatement says.
-        from pytorch_retinanet_amd import ops
+        from pytorch_retinanet_amd import draw_state, ops
         from pytorch_retinanet_amd.augment import AffineCoefs, ShiftScaleRotate
 
         def exact_end(n: int, dtype, fill=0x7f):
@@ -299,7 +299,7 @@ def main() -> None:
         gt_off.copy_(torch.tensor(off, dtype=torch.int32))
         clamped = [min(max(v, 0), R) for v in off]
         block = exact_end(ops.AFFINE_STATE_BYTES, torch.uint8)
-        ops.affine_state_write(block, seed=2, counter=0, p=1.0, min_visibility=0.0, lo=(-45.0, 0.9, -0.0625, -0.0625), hi=(45.0, 1.1, 0.0625, 0.0625))
+        draw_state.write(draw_state.AFFINE, block, seed=2, counter=0, p=1.0, min_visibility=0.0, lo=(-45.0, 0.9, -0.0625, -0.0625), hi=(45.0, 1.1, 0.0625, 0.0625))
         coef = exact_end(B * ops.AFFINE_COEF_WORDS, torch.int32).view(B, ops.AFFINE_COEF_WORDS)
         out_boxes, out_labels, out_off = exact_end(4 * R, torch.float32).view(R, 4), exact_end(R, torch.int64), exact_end(B + 1, torch.int32)
         out_boxes.fill_(-7.25)
@@ -321,7 +321,7 @@ def main() -> None:
         total = out_off.tolist()[-1]
         assert torch.equal(out_boxes.cpu()[:total].view(torch.int32), torch.cat([w[0] for w in want])[:total].view(torch.int32))
         assert torch.equal(out_labels.cpu()[:total], torch.cat([w[1] for w in want])[:total])
-        assert bool((out_boxes[total:] == -7.25).all()) and ops.affine_state_read(block)[1] == 1
+        assert bool((out_boxes[total:] == -7.25).all()) and draw_state.read(draw_state.AFFINE, block)[1] == 1
         for b, im in enumerate(ims):
             if b in (1, 3):                                                        # skipped: the slot is as it was
                 assert bool((dst[b] == -7.25).all()), b
