@@ -958,7 +958,7 @@ int rn_resize_plan_dev(rn_short_side_state *state_or_null, const int32_t *in_hw_
  * or arena / slot / in_hw_dev as for rn_color_mean (the staged form only with out_hw_dev), exactly one of out_hw (HOST) and out_hw_dev
  * (DEVICE), flags_or_null.  An order of all 0xF gives rn_transform_batch's bits. */
 typedef struct rn_color_jitter_state { uint64_t seed; int64_t counter; float p; float lo[4]; float hi[4]; int32_t enabled_mask; } rn_color_jitter_state;
-typedef struct rn_color_coef { float f[4]; float mean; int32_t order; int32_t pad[2]; } rn_color_coef;
+typedef struct rn_color_coef { float f[4]; float mean; int32_t order; float bc_mul; float bc_add; } rn_color_coef;   /* bc_*: see below */
 int rn_color_jitter_draw(rn_color_jitter_state *state, int B, rn_color_coef *coef, void *stream);
 size_t rn_color_mean_workspace_bytes(int B);
 int rn_color_mean(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev, int B,
@@ -967,6 +967,40 @@ int rn_transform_batch_color(const void *const *images, const int32_t *in_hw, co
                              const int32_t *out_hw, const int32_t *out_hw_dev, int B, const float mean[3], const float std[3], int Hp,
                              int Wp, void *out, int out_dtype, int channels_last, const uint8_t *flags_or_null, const rn_color_coef *coef,
                              void *stream);
+
+/* ---- train-time augmentation: brightness / contrast (augment.RandomBrightnessContrast), drawn and applied on the device -----------
+ * albumentations' RandomBrightnessContrast -- x' = alpha x + beta ref, ref the value range or the image mean -- on fp32 RGB in [0, 1],
+ * with the clip of albumentations' 256-entry LUT and without its uint8 quantisation: the same intent, not the same bits.  The rule,
+ * every step one correctly rounded fp32 operation in the written order (no FMA), u_k = the hash of rn_hflip_draw on
+ * (seed ^ salt_k, counter, b); salts: apply 0xB7C0A991B7C0A991, contrast 0xC0A7C0A7C0A7C0A7, brightness 0xB419B419B419B419:
+ *   1. applied = u_apply < p.
+ *   2. alpha = 1 + (clo + u_contrast * (chi - clo)),  beta = blo + u_brightness * (bhi - blo); drawn whatever ``applied`` is; the
+ *      counter advances once per batch.
+ *   3. ref = 1 when by_max != 0.  Otherwise ref = float(sum of double(v) over all 3 h w values v of the image / double(3 h w)), the
+ *      image taken as it stands when this operation's turn comes: after the operations of coef[b].order (rn_color_jitter_draw).
+ *   4. add = beta * ref.
+ *   5. every channel value x becomes clamp(alpha * x + add) to [0, 1]: one multiply, one add, the clamp.
+ * The coefficients travel in the rn_color_coef row, so rn_transform_batch_color carries them on every path: bc_mul = alpha and
+ * bc_add = add in the two words that are zero in a row rn_color_jitter_draw wrote, bit 16 of ``order`` = "brightness / contrast
+ * present" (step 5 runs after the four nibbles' operations; clear: the row means what it always meant), bit 17 = "bc_add still holds
+ * beta: the mean of step 3 is pending".
+ * rn_brightness_contrast_state: a DEVICE block (8-byte aligned) owned by augment.RandomBrightnessContrast, written by the host outside
+ * any capture.
+ * rn_brightness_contrast_draw: one single-wave launch for any B, then counter += 1.  fresh != 0: no colour jitter wrote the rows, and
+ * each row is first made the identity (f = 1, 1, 1, 0; mean = 0; order = 0xFFFF); fresh == 0: the six words of the colour jitter are
+ * left as they are.  An applied image gets bc_mul = alpha, bc_add = beta (by_max: that is add), bit 16 and, without by_max, bit 17; an
+ * image left alone gets bc_mul = 1, bc_add = 0 and no bit.
+ * rn_brightness_contrast_mean: for every row with bit 17 set, step 3 over the pixels after the colour operations, then
+ * bc_add = beta * ref and bit 17 cleared -- a second call changes nothing.  rn_color_mean's structure and arguments (launch it after
+ * rn_color_mean: the contrast's mean is read): no atomics, a fixed number of blocks per image, fixed-order sums in double, a
+ * single-wave finish; an image no slot can hold contributes nothing and gets ref = 0.  workspace:
+ * rn_brightness_contrast_mean_workspace_bytes(B), 8-byte aligned: the partial sums and, behind them at byte B * 256, f32[B] where the
+ * finish leaves ref of every row it served (the other entries are not written). */
+typedef struct rn_brightness_contrast_state { uint64_t seed; int64_t counter; float p; float blo, bhi, clo, chi; int32_t by_max; } rn_brightness_contrast_state;
+int rn_brightness_contrast_draw(rn_brightness_contrast_state *state, int B, rn_color_coef *coef, int fresh, void *stream);
+size_t rn_brightness_contrast_mean_workspace_bytes(int B);
+int rn_brightness_contrast_mean(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev,
+                                int B, rn_color_coef *coef, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- train-time augmentation: bbox-safe random crop (augment.BBoxSafeRandomCrop), a second staging pass ------------------
  * albumentations' BBoxSafeRandomCrop with erosion_rate = 0 in intent -- each margin drawn uniformly between the image edge and the

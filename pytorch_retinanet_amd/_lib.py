@@ -207,6 +207,9 @@ SIGNATURES = {
     "rn_color_mean": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_int, _vp, _vp, _sz, _vp]),
     "rn_transform_batch_color": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_int, C.POINTER(_f32), C.POINTER(_f32), C.c_int, C.c_int,
                                            _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "rn_brightness_contrast_draw": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
+    "rn_brightness_contrast_mean_workspace_bytes": (_sz, [C.c_int]),
+    "rn_brightness_contrast_mean": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_int, _vp, _vp, _sz, _vp]),
     "rn_bbox_crop_draw": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _i64, _vp]),
     "rn_image_crop_stage": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _vp, _i64, _vp]),
     "rn_affine_draw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -39,6 +39,11 @@ bit-identical to running on the sliced tensors.  Other inputs draw the same rect
 border in intent, not bit for bit.  It is a second staging pass as well -- ``rn_affine_draw`` draws a matrix per image and packs the GT
 rows that survive it (rows can disappear: the offsets change), ``rn_image_warp_stage`` gathers each image into a second arena -- and
 its Python restatement (``draw_coefs``, ``warp_boxes``, ``warp_image``) serves every other input on the host.
+
+``RandomBrightnessContrast`` is the third (``GeneralizedRCNNTransform.brightness_contrast``): albumentations' ``alpha x + beta ref`` on
+fp32 RGB in [0, 1], with the LUT's clip and without its uint8 quantisation.  Its two coefficients per image ride in the colour jitter's
+``rn_color_coef`` rows (``rn_brightness_contrast_draw``; by-mean: ``rn_brightness_contrast_mean``) and the transform kernel applies them
+behind the jitter's operations.  It is opt-in from the hparams (``SimpleTrainer(device_brightness_contrast=True)``).
 """
 import logging
 import math
@@ -51,7 +56,8 @@ from torch import Tensor
 from . import draw_state
 from .draw_state import COLOR_IDENTITY, COLOR_OPS, SHORT_SIDE_MAX
 
-__all__ = ["RandomHorizontalFlip", "RandomShortSide", "ColorJitter", "BBoxSafeRandomCrop", "ShiftScaleRotate", "hflip_u", "apply_color_ops"]
+__all__ = ["RandomHorizontalFlip", "RandomShortSide", "ColorJitter", "BBoxSafeRandomCrop", "ShiftScaleRotate", "RandomBrightnessContrast",
+           "hflip_u", "apply_color_ops", "apply_brightness_contrast"]
 
 _M64 = 2 ** 64 - 1
 
@@ -563,8 +569,155 @@ class ColorJitter(_ProbStream):
         super().load_state_dict(state)
 
 
+# ---- brightness / contrast ------------------------------------------------------------------------------------------------
+BC_SALT_APPLY, BC_SALT_CONTRAST, BC_SALT_BRIGHTNESS = 0xB7C0A991B7C0A991, 0xC0A7C0A7C0A7C0A7, 0xB419B419B419B419
+COLOR_BC_PRESENT, COLOR_BC_PENDING = 1 << 16, 1 << 17      # bits of rn_color_coef.order above the four nibbles
+
+
+def image_mean_of(image: Tensor) -> float:
+    "Step 3's mean: all values of an fp32 ``[3, h, w]`` image summed in double, over 3 h w, rounded to fp32."
+    return float(np.float32(float(image.to(torch.float64).sum()) / float(image.numel())))
+
+
+def apply_brightness_contrast(image: Tensor, alpha: float, beta: float, ref: Optional[float] = None) -> Tensor:
+    """Steps 3-5 of the rule of ``rn_brightness_contrast_draw`` (``include/retinanet_hip.h``) on one fp32 RGB ``[3, h, w]`` image in
+    [0, 1], in torch: ``clamp(alpha * x + beta * ref, 0, 1)``, one fp32 rounding per operation.  ``ref``: 1 for ``brightness_by_max``,
+    the image mean when the caller has it, or None to compute it here (``image_mean_of``)."""
+    if image.dim() != 3 or image.shape[0] != 3 or image.dtype != torch.float32:
+        raise ValueError(f"brightness / contrast takes fp32 RGB [3, h, w] images in [0, 1], got {tuple(image.shape)} {image.dtype}")
+    ref = image_mean_of(image) if ref is None else float(ref)
+    add = np.float32(beta) * np.float32(ref)
+    return (image.new_tensor(float(np.float32(alpha))) * image + image.new_tensor(float(add))).clamp(0.0, 1.0)
+
+
+def _bc_limit(v, name: str) -> Tuple[float, float]:
+    "``_limit`` with every given number checked first: min / max would hide a NaN in a pair."
+    for x in (v if isinstance(v, (list, tuple)) else (v,)):
+        if isinstance(x, bool) or not math.isfinite(float(x)):
+            raise ValueError(f"{name} must be finite numbers, got {v!r}")
+    return _limit(v, name)
+
+
+class RandomBrightnessContrast(_ProbStream):
+    """albumentations' ``RandomBrightnessContrast`` for fp32 RGB training images in [0, 1], drawn and applied on the device, with
+    albumentations' argument meanings and defaults: a scalar limit v is the range (-v, v), a pair is taken as given.  With probability
+    ``p`` an image becomes ``clamp(alpha * x + beta * ref, 0, 1)`` with ``alpha`` drawn from ``1 + contrast_limit``, ``beta`` from
+    ``brightness_limit`` and ``ref`` = 1 (``brightness_by_max``: the value range) or the mean of all of the image's values.  The
+    numbered rule of ``rn_brightness_contrast_draw`` in ``include/retinanet_hip.h`` is the definition; ``draw_coefs`` and
+    ``apply_brightness_contrast`` restate it.  The deviation from albumentations: there the reference's uint8 images go through a
+    256-entry LUT and the result is truncated to uint8; here the arithmetic is fp32 on [0, 1] with the LUT's clip and without its
+    quantisation -- the same intent, not the same bits.  ``ColorJitter`` does not cover this transform: torchvision's brightness is a
+    pure multiply and its contrast blends towards the mean gray.
+
+    Install it as ``net.transform.brightness_contrast``; it acts only in training mode and only when targets are given, on the raw image
+    after the crop, the warp and the colour jitter's operations and before the normalisation, the resize and the flip.  On the fused
+    paths the coefficients ride in the colour jitter's ``rn_color_coef`` rows (``rn_brightness_contrast_draw``; with
+    ``brightness_by_max=False`` one more pass over the images, ``rn_brightness_contrast_mean``) and the transform kernel applies them
+    to every source pixel it reads -- inside the captured step, each replay a new draw.  ``p`` and the limits can be rewritten between
+    replays; ``brightness_by_max`` decides which kernels a step launches and is fixed once the device block exists.  Not an
+    ``nn.Module``: it adds no key to the model's state dict.  ``seed``: the stream of draws (``SimpleTrainer`` adds the rank under
+    ``torch.distributed``)."""
+    _layout = draw_state.BRIGHTNESS_CONTRAST
+
+    def __init__(self, brightness_limit=0.2, contrast_limit=0.2, brightness_by_max: bool = True, p: float = 0.5, seed: int = 0):
+        super().__init__(p, seed)
+        self._brightness, self._contrast = _bc_limit(brightness_limit, "brightness_limit"), _bc_limit(contrast_limit, "contrast_limit")
+        self._by_max = bool(brightness_by_max)
+        self.coef: Optional[Tensor] = None            # the last device batch's rn_color_coef rows (f32 [B, 8])
+        self.drawn: Optional[List[Tuple[bool, float, float]]] = None      # the last host-drawn batch's (applied, alpha, beta)
+
+    def __repr__(self) -> str:
+        return (f"RandomBrightnessContrast(brightness_limit={self._brightness}, contrast_limit={self._contrast}, "
+                f"brightness_by_max={self._by_max}, p={self._p}, seed={self._seed})")
+
+    def _fields(self) -> Dict[str, object]:
+        return {"p": self._p, "brightness": self._brightness, "contrast": self._contrast, "by_max": self._by_max}
+
+    # -- the draws ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def draw_coefs(seed: int, counter: int, B: int, p: float, brightness: Sequence[float], contrast: Sequence[float]) -> List[Tuple[bool, float, float]]:
+        """Pure-Python restatement of steps 1 and 2 of ``rn_brightness_contrast_draw``, bit for bit: per image (applied, alpha, beta),
+        the two as fp32 values, drawn whatever ``applied`` is.  ``brightness`` / ``contrast``: (lo, hi) of beta and of alpha - 1."""
+        seed, counter, f32 = int(seed) & _M64, int(counter), np.float32
+        p32, (blo, bhi), (clo, chi) = f32(p), (f32(v) for v in brightness), (f32(v) for v in contrast)
+        out = []
+        for b in range(int(B)):
+            applied = bool(f32(hflip_u(seed ^ BC_SALT_APPLY, counter, b)) < p32)
+            alpha = f32(1.0) + (clo + f32(hflip_u(seed ^ BC_SALT_CONTRAST, counter, b)) * (chi - clo))
+            beta = blo + f32(hflip_u(seed ^ BC_SALT_BRIGHTNESS, counter, b)) * (bhi - blo)
+            out.append((applied, float(alpha), float(beta)))
+        return out
+
+    def draw(self, counter: int, B: int) -> List[Tuple[bool, float, float]]:
+        "The (applied, alpha, beta) this object draws for a batch of B images at ``counter`` (no state change)."
+        return self.draw_coefs(self._seed, counter, B, self._p, self._brightness, self._contrast)
+
+    def next_draw(self, B: int) -> List[Tuple[bool, float, float]]:
+        """The next batch's (applied, alpha, beta) on the HOST, and the counter advanced by one: what CPU tensors and images the fused
+        transform does not take use (``apply_brightness_contrast``).  With a device block the counter is read back and written (a
+        synchronisation); not inside a capture."""
+        self.drawn = self._host_draw(lambda n: self.draw(n, B))
+        return self.drawn
+
+    def next_coef(self, images, coef: Optional[Tensor] = None) -> Tensor:
+        """The next batch's ``rn_color_coef`` rows (f32 [B, 8]) on the images' device, and the counter advanced by one: one
+        ``rn_brightness_contrast_draw`` launch into ``coef`` -- the rows a ``ColorJitter.next_coef`` returned, contrast mean included
+        -- or into fresh identity rows, and with ``brightness_by_max=False`` ``rn_brightness_contrast_mean`` over the images
+        (capturable; the block is created at the first call, which must not be inside a capture).  ``images``: CUDA f32 ``[3, h, w]``
+        tensors or ``ops.StagedImages``."""
+        ops = _ops()
+        staged = isinstance(images, ops.StagedImages)
+        device, B = (images.device, images.B) if staged else (images[0].device, len(images))
+        if device.type != "cuda":
+            raise RuntimeError("RandomBrightnessContrast.next_coef draws on the GPU; CPU batches use next_draw()")
+        coef = ops.brightness_contrast_draw(self._device_block(device), B, coef)
+        if not self._by_max:                           # (by-max launches nothing more: ref = 1)
+            ops.brightness_contrast_mean(images, coef)
+        self.coef = coef
+        return coef
+
+    # -- settings and state ---------------------------------------------------------------------------------------------
+    @property
+    def brightness_limit(self) -> Tuple[float, float]:
+        return self._brightness
+
+    @property
+    def contrast_limit(self) -> Tuple[float, float]:
+        return self._contrast
+
+    @property
+    def brightness_by_max(self) -> bool:
+        return self._by_max
+
+    @brightness_by_max.setter
+    def brightness_by_max(self, value: bool) -> None:
+        "Which kernels a step launches depends on it, so a change is refused once the device block exists."
+        value = bool(value)
+        if self._block is not None and value != self._by_max:
+            raise ValueError(f"RandomBrightnessContrast: brightness_by_max was {self._by_max} when this object's device state was created; "
+                             "changing it changes which kernels a (captured) step launches -- install a new RandomBrightnessContrast instead")
+        self._by_max = value
+
+    def set_limits(self, brightness_limit=None, contrast_limit=None) -> None:
+        "New ranges (the ones not given stay): written into the device block (no re-capture needed; not inside a capture)."
+        if brightness_limit is not None:
+            self._brightness = _bc_limit(brightness_limit, "brightness_limit")
+        if contrast_limit is not None:
+            self._contrast = _bc_limit(contrast_limit, "contrast_limit")
+        self._write(brightness=self._brightness, contrast=self._contrast)
+
+    def state_dict(self) -> Dict[str, object]:
+        return {**super().state_dict(), "brightness_limit": list(self._brightness), "contrast_limit": list(self._contrast),
+                "brightness_by_max": self._by_max}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.brightness_by_max = state["brightness_by_max"]
+        self.set_limits(tuple(state["brightness_limit"]), tuple(state["contrast_limit"]))
+        super().load_state_dict(state)
+
+
 # ---- bbox-safe random crop ------------------------------------------------------------------------------------------------
-CROP_SALT_APPLY = 0xC409C409C409C40B                                 # include/retinanet_hip.h: rn_bbox_crop_draw, step 1
+CROP_SALT_APPLY =0xC409C409C409C40B                                 # include/retinanet_hip.h: rn_bbox_crop_draw, step 1
 CROP_SALT_LEFT, CROP_SALT_TOP, CROP_SALT_RIGHT, CROP_SALT_BOTTOM = 0x1EF71EF71EF71EF7, 0x70B070B070B070B1, 0x4167416741674169, 0xB077B077B077B079
 _I32_MIN, _I32_MAX = -2 ** 31, 2 ** 31 - 1
 
@@ -998,10 +1151,31 @@ def color_jitter_from_transforms(entries, seed: int = 0, log=None) -> Optional[C
     return found
 
 
-def from_transforms(entries, seed: int = 0, log=None) -> Optional[RandomHorizontalFlip]:
+_BRIGHTNESS_CONTRAST_NAMES = ("albumentations.RandomBrightnessContrast", "RandomBrightnessContrast")
+
+
+def brightness_contrast_from_transforms(entries, seed: int = 0, log=None) -> Optional[RandomBrightnessContrast]:
+    """The brightness / contrast an hparams ``transforms`` list asks for, or None.  ``albumentations.RandomBrightnessContrast`` and a
+    bare ``RandomBrightnessContrast`` (``brightness_limit`` 0.2, ``contrast_limit`` 0.2, ``brightness_by_max`` true, ``p`` 0.5:
+    albumentations' defaults; ``always_apply: true`` means p = 1) map onto ``RandomBrightnessContrast``, which works on fp32 without the
+    uint8 LUT's quantisation and is not bit-compatible with albumentations.  A second entry is skipped with a warning.  The mapping is
+    opt-in: ``SimpleTrainer(device_brightness_contrast=True)`` or ``trainer.device_brightness_contrast`` in the hparams calls it."""
+    log = log or logging.getLogger(__name__)
+    found = None
+    for name, params in _named(entries, _BRIGHTNESS_CONTRAST_NAMES, "brightness / contrast", log):
+        as_limit = lambda v: tuple(v) if isinstance(v, (list, tuple)) else v
+        found = RandomBrightnessContrast(brightness_limit=as_limit(params.get("brightness_limit", 0.2)),
+                                         contrast_limit=as_limit(params.get("contrast_limit", 0.2)),
+                                         brightness_by_max=bool(params.get("brightness_by_max", True)), p=_entry_p(params, 0.5), seed=seed)
+    return found
+
+
+def from_transforms(entries, seed: int = 0, log=None, brightness_contrast: bool = False) -> Optional[RandomHorizontalFlip]:
     """The flip an hparams ``transforms`` list asks for (reference ``hparams.yaml:55-58``), or None.  ``albumentations.HorizontalFlip``
     (``p``, default 0.5; ``always_apply: true`` means p = 1) and ``RandomHorizontalFlip`` (``prob``, default 0.5; any module path) map
-    onto ``RandomHorizontalFlip``.  albumentations itself is not used: every other entry is skipped with one warning naming it."""
+    onto ``RandomHorizontalFlip``.  albumentations itself is not used: every other entry is skipped with one warning naming it.
+    ``brightness_contrast``: the caller maps a ``RandomBrightnessContrast`` entry itself (``brightness_contrast_from_transforms``: the
+    ``device_brightness_contrast`` switch), so it is not warned about here."""
     log = log or logging.getLogger(__name__)
     found = None
     for name, params in _entries(entries):
@@ -1012,6 +1186,12 @@ def from_transforms(entries, seed: int = 0, log=None) -> Optional[RandomHorizont
             p = float(params.get("prob", params.get("p", 0.5)))
         elif name in _COLOR_JITTER_NAMES or name in _BBOX_CROP_NAMES or name in _SHIFT_SCALE_ROTATE_NAMES:
             continue                                   # color_jitter_ / bbox_crop_ / shift_scale_rotate_from_transforms map these
+        elif name in _BRIGHTNESS_CONTRAST_NAMES and brightness_contrast:
+            continue                                   # brightness_contrast_from_transforms maps it
+        elif name in _BRIGHTNESS_CONTRAST_NAMES:
+            log.warning("transforms: %s is skipped: it is implemented on the GPU (augment.RandomBrightnessContrast) but stays off unless "
+                        "SimpleTrainer(device_brightness_contrast=True) or trainer.device_brightness_contrast in the hparams installs it", name)
+            continue
         else:
             log.warning("transforms: %s is not supported (albumentations is not available; only the horizontal flip, ColorJitter, "
                         "BBoxSafeRandomCrop and ShiftScaleRotate are implemented, on the GPU): skipped", name)

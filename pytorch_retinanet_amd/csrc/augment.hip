@@ -65,6 +65,15 @@
 // block k adds the pixels k * 256 + t + j * 8192 in order of j, the block adds its 256 sums as a fixed tree, and a second single-wave
 // launch adds an image's 32 partials in index order -- two calls give the same bits.
 //
+// Brightness / contrast (augment.RandomBrightnessContrast: albumentations' alpha x + beta ref on fp32 RGB in [0, 1]) rides in the same
+// rows, behind the four operations (the numbered rule in include/retinanet_hip.h):
+//
+//   rn_brightness_contrast_draw   coef[b].bc_mul = alpha, .bc_add = beta, order bits 16 (present) and 17 (mean pending); counter += 1
+//   rn_brightness_contrast_mean   for the rows with bit 17: bc_add = beta * float(sum of double(every channel value) / double(3 h w)),
+//                                 the values taken after the row's colour operations; bit 17 cleared
+//
+// with rn_color_mean's structure: the same blocks, the same order of every sum, the same single-wave finish.
+//
 // The bbox-safe random crop (augment.BBoxSafeRandomCrop: albumentations' BBoxSafeRandomCrop with erosion_rate = 0 in intent, on integer
 // pixels) is a second staging pass over staged images and packed GT (the image capacity mode), so nothing downstream changes:
 //
@@ -223,7 +232,7 @@ __global__ __launch_bounds__(HF_BLOCK) void color_jitter_draw_kernel(rn_color_ji
 #pragma unroll
         for (int k = 0; k < 4; ++k) c.f[k] = lo[k] + hflip_u(seed ^ salt[k], counter, b) * (hi[k] - lo[k]);
         c.mean = 0.0f;
-        c.pad[0] = c.pad[1] = 0;
+        c.bc_mul = c.bc_add = 0.0f;                                      // (no brightness / contrast: the two words stay zero bits)
         coef[b] = c;
     }
     // (one wave: every lane read the counter above, in program order before this store)
@@ -294,6 +303,99 @@ __global__ __launch_bounds__(HF_BLOCK) void color_mean_finish_kernel(const Color
     double sum = 0.0;
     for (int k = 0; k < CM_BLOCKS; ++k) sum += a.partial[(int64_t)b * CM_BLOCKS + k];
     a.coef[b].mean = (float)(sum / (double)((int64_t)ih * iw));
+}
+
+// ---- brightness / contrast: the draw and the image mean (augment.RandomBrightnessContrast) -------------------------------------------
+constexpr uint64_t RB_SALT_APPLY = 0xB7C0A991B7C0A991ull, RB_SALT_CONTRAST = 0xC0A7C0A7C0A7C0A7ull, RB_SALT_BRIGHTNESS = 0xB419B419B419B419ull;
+
+static_assert(sizeof(rn_brightness_contrast_state) == 40 && offsetof(rn_brightness_contrast_state, seed) == 0 &&
+                  offsetof(rn_brightness_contrast_state, counter) == 8 && offsetof(rn_brightness_contrast_state, p) == 16 &&
+                  offsetof(rn_brightness_contrast_state, blo) == 20 && offsetof(rn_brightness_contrast_state, bhi) == 24 &&
+                  offsetof(rn_brightness_contrast_state, clo) == 28 && offsetof(rn_brightness_contrast_state, chi) == 32 &&
+                  offsetof(rn_brightness_contrast_state, by_max) == 36, "draw_state.BRIGHTNESS_CONTRAST");
+static_assert(sizeof(rn_color_coef) == 32 && offsetof(rn_color_coef, order) == 20 && offsetof(rn_color_coef, bc_mul) == 24 &&
+                  offsetof(rn_color_coef, bc_add) == 28, "rn_color_coef: ops.COLOR_COEF_FLOATS and the columns the Python side reads");
+
+// fresh: no colour jitter wrote the rows -- each is made the identity first; else its six colour words stay as they are
+__global__ __launch_bounds__(HF_BLOCK) void brightness_contrast_draw_kernel(rn_brightness_contrast_state *st, const int B,
+                                                                           rn_color_coef *__restrict__ coef, const int fresh)
+{
+    const uint64_t seed = st->seed;
+    const int64_t counter = st->counter;
+    const float p = st->p, blo = st->blo, bhi = st->bhi, clo = st->clo, chi = st->chi;
+    const int pending = st->by_max != 0 ? 0 : rn::COLOR_BC_PENDING;
+    for (int b = (int)threadIdx.x; b < B; b += HF_BLOCK) {
+        rn_color_coef c;
+        if (fresh) {
+            c.f[0] = c.f[1] = c.f[2] = 1.0f;
+            c.f[3] = 0.0f;
+            c.mean = 0.0f;
+            c.order = 0xFFFF;
+        } else {
+            c = coef[b];
+        }
+        const bool applied = hflip_u(seed ^ RB_SALT_APPLY, counter, b) < p;
+        const float alpha = 1.0f + (clo + hflip_u(seed ^ RB_SALT_CONTRAST, counter, b) * (chi - clo));
+        const float beta = blo + hflip_u(seed ^ RB_SALT_BRIGHTNESS, counter, b) * (bhi - blo);
+        c.order = (c.order & ~(rn::COLOR_BC_PRESENT | rn::COLOR_BC_PENDING)) | (applied ? (rn::COLOR_BC_PRESENT | pending) : 0);
+        c.bc_mul = applied ? alpha : 1.0f;
+        c.bc_add = applied ? beta : 0.0f;
+        coef[b] = c;
+    }
+    // (one wave: every lane read the counter above, in program order before this store)
+    if (threadIdx.x == 0) st->counter = counter + 1;
+}
+
+// partial[b][blockIdx.x] = the sum in double, in a fixed order, of the three channel values after the colour operations over the pixels
+// blockIdx.x * 256 + t + j * 8192, for the rows whose image mean is pending
+template <bool VAR>
+__global__ __launch_bounds__(CM_BLOCK) void bc_mean_partial_kernel(const ColorMeanArgs a)
+{
+    __shared__ double sums[CM_BLOCK];
+    const int b = blockIdx.y;
+    rn_color_coef c = a.coef[b];
+    if (!(c.order & rn::COLOR_BC_PENDING)) return;
+    c.order &= 0xFFFF;                                                          // (the operations that come before this one)
+    int ih, iw;
+    const bool fits = color_mean_size<VAR>(a, b, ih, iw);
+    double acc = 0.0;
+    if (fits) {
+        const float *__restrict__ src = VAR ? a.arena + (int64_t)b * a.slot : a.img[b];
+        const int64_t plane = (int64_t)ih * iw;
+        for (int64_t i = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x; i < plane; i += (int64_t)CM_BLOCKS * CM_BLOCK) {
+            float r = src[i], g = src[plane + i], bl = src[2 * plane + i];
+            rn::color_apply<false>(r, g, bl, c);
+            acc += ((double)r + (double)g) + (double)bl;
+        }
+    }
+    sums[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = CM_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sums[threadIdx.x] += sums[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.partial[(int64_t)b * CM_BLOCKS + blockIdx.x] = sums[0];
+}
+
+// lane i: image i of the launch -- ref = float(its partials added in index order / double(3 h w)), 0 for an image no slot holds;
+// bc_add = beta * ref and the pending bit cleared, so a second call finds nothing to do
+template <bool VAR>
+__global__ __launch_bounds__(HF_BLOCK) void bc_mean_finish_kernel(const ColorMeanArgs a, float *__restrict__ ref_out, const int cnt)
+{
+    const int b = (int)threadIdx.x;
+    if (b >= cnt) return;
+    const int order = a.coef[b].order;
+    if (!(order & rn::COLOR_BC_PENDING)) return;
+    int ih, iw;
+    float ref = 0.0f;
+    if (color_mean_size<VAR>(a, b, ih, iw)) {
+        double sum = 0.0;
+        for (int k = 0; k < CM_BLOCKS; ++k) sum += a.partial[(int64_t)b * CM_BLOCKS + k];
+        ref = (float)(sum / (double)(3 * (int64_t)ih * iw));
+    }
+    ref_out[b] = ref;
+    a.coef[b].bc_add = a.coef[b].bc_add * ref;
+    a.coef[b].order = order & ~rn::COLOR_BC_PENDING;
 }
 
 // ---- bbox-safe random crop: the draw and the copy (augment.BBoxSafeRandomCrop) ---------------------------------------------------------
@@ -502,13 +604,20 @@ RN_API size_t rn_color_mean_workspace_bytes(int B)
     return B > 0 ? (size_t)B * CM_BLOCKS * sizeof(double) : 0;
 }
 
-RN_API int rn_color_mean(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev, int B,
-                         rn_color_coef *coef, void *workspace, size_t workspace_bytes, void *stream)
+// (the partial sums, and behind them f32[B] for ref, rounded up to 8 bytes)
+RN_API size_t rn_brightness_contrast_mean_workspace_bytes(int B)
+{
+    return B > 0 ? (size_t)B * CM_BLOCKS * sizeof(double) + (((size_t)B * sizeof(float) + 7) & ~(size_t)7) : 0;
+}
+
+// rn_color_mean (bc false) and rn_brightness_contrast_mean (bc true): the same arguments, checks and launch table
+static int mean_launch(const bool bc, const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev,
+                       int B, rn_color_coef *coef, void *workspace, size_t workspace_bytes, void *stream)
 {
     const bool var = arena != nullptr;
     if (!coef || !workspace || B <= 0) return RN_EINVAL;
     if (var ? (images || in_hw || !in_hw_dev || slot < 3) : (!images || !in_hw || in_hw_dev)) return RN_EINVAL;
-    if (workspace_bytes < rn_color_mean_workspace_bytes(B)) return RN_EINVAL;
+    if (workspace_bytes < (bc ? rn_brightness_contrast_mean_workspace_bytes(B) : rn_color_mean_workspace_bytes(B))) return RN_EINVAL;
     if (!rn::aligned(coef, 4) || !rn::aligned(workspace, 8)) return RN_EALIGN;
     if (var && (!rn::aligned(arena, 16) || !rn::aligned(in_hw_dev, 4))) return RN_EALIGN;
     for (int b = 0; b < B && !var; ++b) {
@@ -516,6 +625,7 @@ RN_API int rn_color_mean(const void *const *images, const int32_t *in_hw, const 
         if (!rn::aligned(images[b], 4)) return RN_EALIGN;
     }
     hipStream_t st = (hipStream_t)stream;
+    float *ref = (float *)((double *)workspace + (int64_t)B * CM_BLOCKS);        // bc: behind the partial sums
     for (int b0 = 0; b0 < B; b0 += CM_MAX_IMAGES) {
         const int cnt = (B - b0) < CM_MAX_IMAGES ? (B - b0) : CM_MAX_IMAGES;
         ColorMeanArgs a;
@@ -530,16 +640,45 @@ RN_API int rn_color_mean(const void *const *images, const int32_t *in_hw, const 
         a.slot = slot;
         a.coef = coef + b0;                                      // (this launch's first image: the kernels index from 0)
         a.partial = (double *)workspace + (int64_t)b0 * CM_BLOCKS;
-        if (var) {
-            hipLaunchKernelGGL(color_mean_partial_kernel<true>, dim3(CM_BLOCKS, (unsigned)cnt), dim3(CM_BLOCK), 0, st, a);
+        const dim3 grid(CM_BLOCKS, (unsigned)cnt);
+        if (bc && var) {
+            hipLaunchKernelGGL(bc_mean_partial_kernel<true>, grid, dim3(CM_BLOCK), 0, st, a);
+            hipLaunchKernelGGL(bc_mean_finish_kernel<true>, dim3(1), dim3(HF_BLOCK), 0, st, a, ref + b0, cnt);
+        } else if (bc) {
+            hipLaunchKernelGGL(bc_mean_partial_kernel<false>, grid, dim3(CM_BLOCK), 0, st, a);
+            hipLaunchKernelGGL(bc_mean_finish_kernel<false>, dim3(1), dim3(HF_BLOCK), 0, st, a, ref + b0, cnt);
+        } else if (var) {
+            hipLaunchKernelGGL(color_mean_partial_kernel<true>, grid, dim3(CM_BLOCK), 0, st, a);
             hipLaunchKernelGGL(color_mean_finish_kernel<true>, dim3(1), dim3(HF_BLOCK), 0, st, a, cnt);
         } else {
-            hipLaunchKernelGGL(color_mean_partial_kernel<false>, dim3(CM_BLOCKS, (unsigned)cnt), dim3(CM_BLOCK), 0, st, a);
+            hipLaunchKernelGGL(color_mean_partial_kernel<false>, grid, dim3(CM_BLOCK), 0, st, a);
             hipLaunchKernelGGL(color_mean_finish_kernel<false>, dim3(1), dim3(HF_BLOCK), 0, st, a, cnt);
         }
         RN_LAUNCH_CHECK();
     }
     return RN_OK;
+}
+
+RN_API int rn_color_mean(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot, const int32_t *in_hw_dev, int B,
+                         rn_color_coef *coef, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return mean_launch(false, images, in_hw, arena, slot, in_hw_dev, B, coef, workspace, workspace_bytes, stream);
+}
+
+RN_API int rn_brightness_contrast_draw(rn_brightness_contrast_state *state, int B, rn_color_coef *coef, int fresh, void *stream)
+{
+    if (!state || !coef || B <= 0) return RN_EINVAL;
+    if (!rn::aligned(state, 8) || !rn::aligned(coef, 4)) return RN_EALIGN;
+    hipLaunchKernelGGL(brightness_contrast_draw_kernel, dim3(1), dim3(HF_BLOCK), 0, (hipStream_t)stream, state, B, coef, fresh ? 1 : 0);
+    RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
+RN_API int rn_brightness_contrast_mean(const void *const *images, const int32_t *in_hw, const float *arena, int64_t slot,
+                                       const int32_t *in_hw_dev, int B, rn_color_coef *coef, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    return mean_launch(true, images, in_hw, arena, slot, in_hw_dev, B, coef, workspace, workspace_bytes, stream);
 }
 
 RN_API int rn_hflip_draw(rn_hflip_state *state, int B, uint8_t *flags, void *stream)

@@ -9,6 +9,9 @@
 namespace rn {
 
 constexpr int COLOR_BRIGHTNESS = 0, COLOR_CONTRAST = 1, COLOR_SATURATION = 2, COLOR_HUE = 3, COLOR_SKIP = 0xF;
+// bits of rn_color_coef.order above the four nibbles: brightness / contrast present (bc_mul, bc_add are applied), and bc_add still
+// holds beta because the image mean it is to be multiplied with is pending (rn_brightness_contrast_mean clears it)
+constexpr int COLOR_BC_PRESENT = 1 << 16, COLOR_BC_PENDING = 1 << 17;
 
 __device__ __forceinline__ float color_clamp(const float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }
 
@@ -73,6 +76,12 @@ __device__ __forceinline__ void color_apply(float &r, float &g, float &b, const 
         } else if (op == COLOR_HUE) {
             color_hue(r, g, b, c.f[COLOR_HUE]);
         }
+    }
+    // brightness / contrast (augment.RandomBrightnessContrast; the header's step 5) behind the four operations: one multiply, one add,
+    // the clamp.  A row of rn_color_jitter_draw has the bit clear and takes the code above alone.
+    if (!UNTIL_CONTRAST && (c.order & COLOR_BC_PRESENT)) {
+        const float m = c.bc_mul, a = c.bc_add;
+        r = color_clamp(m * r + a); g = color_clamp(m * g + a); b = color_clamp(m * b + a);
     }
 }
 

@@ -42,7 +42,8 @@
 // inside a captured step, rn_color_mean the contrast mean).  With COLOR every tap loads its three channels, runs the operations of
 // coef[b].order on the triple (rn_color.hpp; b = blockIdx.z, so the branches are wave-uniform) and is then normalised and blended as
 // above.  The jitter is per pixel apart from the mean, so it commutes with the flip; an order of all 0xF gives the plain launch's bits.
-// The COLOR = false instantiations are the code they were.
+// The COLOR = false instantiations are the code they were.  Brightness / contrast (augment.RandomBrightnessContrast) rides in the same
+// rows -- bc_mul, bc_add and bit 16 of the order -- and is the last step of color_apply<false>: no flag, no argument and no branch here.
 #include "rn_color.hpp"
 #include "rn_common.hpp"
 

@@ -59,6 +59,10 @@ COLOR_JITTER = Layout("rn_color_jitter_state", 56, {**_HEAD, "p": _field(16, "<f
 AFFINE = Layout("rn_affine_state", 56, {**_HEAD, "p": _field(16, "<f"), "min_visibility": _field(20, "<f"),
                                         "lo": _field(24, "<4f"), "hi": _field(40, "<4f")})       # lo / hi of (angle, scale, dx, dy)
 LAYOUTS = (HFLIP, SHORT_SIDE, COLOR_JITTER, BBOX_CROP, AFFINE)
+# ``brightness`` / ``contrast``: (lo, hi) of beta and of alpha - 1 -- the struct's blo, bhi and clo, chi; ``by_max``: ref = 1, else the mean
+BRIGHTNESS_CONTRAST = Layout("rn_brightness_contrast_state", 40,
+                             {**_HEAD, "p": _field(16, "<f"), "brightness": _field(20, "<2f"), "contrast": _field(28, "<2f"),
+                              "by_max": _field(36, "<i", lambda v: (1 if v else 0,), lambda t: bool(t[0]))})
 
 
 def check(layout: Layout, block: Tensor) -> torch.device:

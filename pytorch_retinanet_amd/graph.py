@@ -55,6 +55,8 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     packed on the device -- the GT counts change from replay to replay, which only packed GT can hold -- and the images are warped
     into another arena, so one graph replays while the draws vary; p and the ranges may change between replays.  A batch no class
     holds runs eagerly with the draw on the host.
+    Brightness / contrast (``net.transform.brightness_contrast``, ``augment.RandomBrightnessContrast``) is keyed by the installed object
+    as well: its coefficients are drawn inside the step from its device block, so its limits and p may change between replays.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -556,7 +558,12 @@ class CapturedTrainStep:
         # shift / scale / rotate (transform.shift_scale_rotate): matrices, surviving rows and warped images all come from the object's
         # device block inside the step -- the object again.  Without one nothing is added.
         ssr = getattr(getattr(self.net, "transform", None), "shift_scale_rotate", None)
-        return key if ssr is None else key + (("shift_scale_rotate", ssr),)
+        if ssr is not None:
+            key = key + (("shift_scale_rotate", ssr),)
+        # brightness / contrast (transform.brightness_contrast): its coefficients are drawn inside the step from the object's device block
+        # into the colour rows -- the object again: new limits or a new p replay the same graph.  Without one nothing is added.
+        bc = getattr(getattr(self.net, "transform", None), "brightness_contrast", None)
+        return key if bc is None else key + (("brightness_contrast", bc),)
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."

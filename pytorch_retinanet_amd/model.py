@@ -73,6 +73,12 @@ class RetinaNetModel(_Base):
         self.test_evaluator = None
         self.predictor = None         # a callable images -> detections used by test_step instead of net.predict (graph.CapturedPredict)
         self.device_eval = False      # test_dataloader: score on the GPU (coco_eval.DeviceBBoxEval) when the net is on CUDA; SimpleTrainer sets it
+        self.device_brightness_contrast = False      # prepare_data: map a RandomBrightnessContrast entry of the transforms; SimpleTrainer sets it
+
+    def device_brightness_contrast_enabled(self) -> bool:
+        "This model's ``device_brightness_contrast`` (``SimpleTrainer`` sets it) or ``trainer.device_brightness_contrast`` of its hparams."
+        section = self.conf.get("trainer") if hasattr(self.conf, "get") else None
+        return bool(self.device_brightness_contrast or (section or {}).get("device_brightness_contrast") or False)
 
     def forward(self, xb, *args, **kwargs):
         # reference model.py:33-35 calls self.net(xb) with no targets (a TypeError there, Q19);
@@ -93,7 +99,12 @@ class RetinaNetModel(_Base):
             from .datasets import CSVDetectionDataset
             # the training set's transforms (reference model.py:51-52, hparams.yaml:55-58): the horizontal flip runs on the GPU,
             # inside the model's transform (augment.RandomHorizontalFlip); validation / test never flip (eval mode, no targets)
-            self.net.transform.hflip = from_transforms(self.conf.get("transforms"))
+            # (RandomBrightnessContrast is opt-in: with the switch its entry is mapped below, without it the flip's mapping warns about it)
+            bc_on = self.device_brightness_contrast_enabled()
+            self.net.transform.hflip = from_transforms(self.conf.get("transforms"), brightness_contrast=bc_on)
+            if bc_on:
+                from .augment import brightness_contrast_from_transforms
+                self.net.transform.brightness_contrast = brightness_contrast_from_transforms(self.conf.get("transforms"))
             # ColorJitter entries (albumentations' or torchvision's) become the GPU colour jitter of the model's transform as well
             self.net.transform.color_jitter = color_jitter_from_transforms(self.conf.get("transforms"))
             # an albumentations.BBoxSafeRandomCrop entry becomes the transform's bbox-safe random crop (augment.BBoxSafeRandomCrop)
@@ -238,7 +249,8 @@ class SimpleTrainer:
                  channels_last: bool = True, max_steps: Optional[int] = None, log_every: int = 10, capture: bool = True,
                  gt_capacity=None, gradient_clip_val: float = 0.0, accumulate_grad_batches: int = 1,
                  weight_ema_decay: float = 0.0, weight_ema_warmup: float = 0.0, device_scale_jitter: bool = False,
-                 scale_jitter_seed: int = 0, image_capacity=None, predict_image_capacity=None, device_eval: bool = False):
+                 scale_jitter_seed: int = 0, image_capacity=None, predict_image_capacity=None, device_eval: bool = False,
+                 device_brightness_contrast: bool = False):
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
@@ -297,7 +309,13 @@ class SimpleTrainer:
         detections on the GPU -- the model's ``test_evaluator`` becomes a ``CocoEvaluator(device=...)`` whose ``coco_eval["bbox"]`` is a
         ``coco_eval.DeviceBBoxEval``: the detections stay on the device as tensors, the greedy matching and the precision / recall rows run
         as two HIP kernels (``rn_eval_match`` / ``rn_eval_accumulate``), and the 12 statistics are the host evaluator's bit for bit.  CUDA
-        only: on another device the host evaluator is used as before."""
+        only: on another device the host evaluator is used as before.
+
+        ``device_brightness_contrast`` (off by default; left False, an optional ``trainer.device_brightness_contrast`` in the hparams is
+        honoured): the third transform of the reference's published recipe.  An ``albumentations.RandomBrightnessContrast`` entry of the
+        hparams' ``transforms`` is mapped onto ``augment.RandomBrightnessContrast`` (albumentations' defaults) and installed as
+        ``net.transform.brightness_contrast`` (``self.brightness_contrast``; under ``torch.distributed`` rank r draws from seed + r): drawn
+        and applied on the device inside the captured step.  Without the switch the entry is skipped with one warning, as it always was."""
         from .graph import gt_capacity_classes, image_capacity_classes
         from .optim import check_accumulate_grad_batches
         self.accumulate_grad_batches = check_accumulate_grad_batches(accumulate_grad_batches)
@@ -324,6 +342,8 @@ class SimpleTrainer:
         self.predict_image_capacity = predict_image_capacity
         self.predictor = None                             # the graph.CapturedPredict of the last test()
         self.device_eval = bool(device_eval)
+        self.device_brightness_contrast = bool(device_brightness_contrast)
+        self.brightness_contrast = None                   # the augment.RandomBrightnessContrast of the last fit()
         self.max_epochs, self.max_steps, self.log_every, self.capture = max_epochs, max_steps, log_every, capture
         self.captured_steps = 0
         self.captured_graphs = 0                          # captures of the last fit() (one per input signature that reached a replay)
@@ -405,6 +425,25 @@ class SimpleTrainer:
         section = conf.get("trainer") if hasattr(conf, "get") else None
         return bool((section or {}).get("device_eval") or False)
 
+    def resolve_device_brightness_contrast(self, conf) -> bool:
+        "The constructor's ``device_brightness_contrast`` or, when that is False, ``trainer.device_brightness_contrast`` of the hparams (absent: off)."
+        if self.device_brightness_contrast:
+            return True
+        section = conf.get("trainer") if hasattr(conf, "get") else None
+        return bool((section or {}).get("device_brightness_contrast") or False)
+
+    def _install_brightness_contrast(self, model, rank: Optional[int]) -> None:
+        """``fit``'s part of ``device_brightness_contrast``: the object ``prepare_data`` mapped from the hparams' ``transforms`` -- or,
+        for a csv model that was prepared before the switch was known, the mapping made here."""
+        transform = model.net.transform
+        if (self.resolve_device_brightness_contrast(model.conf) and getattr(transform, "brightness_contrast", None) is None
+                and getattr(getattr(model.conf, "dataset", None), "kind", None) == "csv"):
+            from .augment import brightness_contrast_from_transforms
+            transform.brightness_contrast = brightness_contrast_from_transforms(model.conf.get("transforms"))
+        self.brightness_contrast = getattr(transform, "brightness_contrast", None)
+        if self.brightness_contrast is not None and rank is not None:
+            self.brightness_contrast.set_rank(rank)       # seed = base seed + rank: each rank draws its own coefficients
+
     def _install_scale_jitter(self, model, rank: Optional[int]) -> None:
         "``fit``'s part of ``device_scale_jitter``: a ``RandomShortSide`` over the transform's ``min_size`` tuple, or one log line."
         transform = model.net.transform
@@ -433,6 +472,8 @@ class SimpleTrainer:
     def fit(self, model: RetinaNetModel):
         import torch.distributed as dist
         from .parallel import BucketedGradAllReduce
+        if self.resolve_device_brightness_contrast(model.conf):
+            model.device_brightness_contrast = True       # (prepare_data maps the RandomBrightnessContrast entry and does not warn about it)
         model.prepare_data() if model.trn_ds is None else None
         model.to(self.device)
         if self.channels_last:
@@ -459,6 +500,7 @@ class SimpleTrainer:
         if ssr is not None and ddp is not None:
             ssr.set_rank(dist.get_rank())                 # seed = base seed + rank: each rank draws its own matrices
         self._install_scale_jitter(model, dist.get_rank() if ddp is not None else None)
+        self._install_brightness_contrast(model, dist.get_rank() if ddp is not None else None)
         # precision "16" = fp16 autocast WITH dynamic loss scaling, like the reference's native-AMP run (Lightning precision=16):
         # fp16 gradients of a focal loss normalised by num_fg underflow without it
         # (under a gradient exchange: parallel.ExchangeGradScaler -- found_inf from the exchanged buckets, one decision for all ranks)

@@ -673,7 +673,7 @@ def hflip_draw(block: Tensor, B: int) -> Tensor:
 
 
 # ---- train-time colour jitter (augment.ColorJitter) ----------------------------------------------------------------------------
-COLOR_COEF_FLOATS = 8                  # rn_color_coef: f f32[4], mean f32, order i32, pad i32[2]
+COLOR_COEF_FLOATS = 8                  # rn_color_coef: f f32[4], mean f32, order i32, bc_mul f32, bc_add f32 (zero without brightness / contrast)
 
 
 def _check_coef(coef: Tensor, B: int, dev: torch.device) -> None:
@@ -723,6 +723,65 @@ def color_mean(images, coef: Tensor, workspace: Optional[Tensor] = None) -> Tens
             in_hw = (C.c_int32 * (2 * B))(*[int(v) for im in imgs for v in im.shape[1:]])
             check(lib.rn_color_mean(ptrs, in_hw, None, 0, None, B, _ptr(coef), _ptr(workspace),
                                     int(workspace.numel() * workspace.element_size()), _stream(dev)), "rn_color_mean")
+    return coef
+
+
+# ---- train-time brightness / contrast (augment.RandomBrightnessContrast) -----------------------------------------------------------
+BRIGHTNESS_CONTRAST_STATE_BYTES = draw_state.BRIGHTNESS_CONTRAST.nbytes
+COLOR_BC_PRESENT, COLOR_BC_PENDING = 1 << 16, 1 << 17      # bits of column 5 (``order``): bc_mul / bc_add apply; bc_add still holds beta
+
+
+def brightness_contrast_draw(block: Tensor, B: int, coef: Optional[Tensor] = None) -> Tensor:
+    """``rn_brightness_contrast_draw``: ``bc_mul`` / ``bc_add`` (columns 6 and 7) and bits 16 / 17 of the order (column 5) of the
+    ``rn_color_coef`` rows, drawn from the block, then the block's counter advances by one -- one launch on the current stream for any
+    B, no host synchronisation (capturable: each replay draws anew).  ``coef``: the rows a ``color_jitter_draw`` wrote (in place; its
+    six words stay), or None for fresh rows whose colour part is the identity.  Returns the rows."""
+    dev = _need_dev(block)
+    draw_state.check(draw_state.BRIGHTNESS_CONTRAST, block)
+    B = int(B)
+    if B <= 0:
+        raise ValueError(f"B must be positive, got {B}")
+    fresh = coef is None
+    if fresh:
+        coef = torch.empty((B, COLOR_COEF_FLOATS), dtype=torch.float32, device=dev)
+    _check_coef(coef, B, dev)
+    with torch.cuda.device(dev), _timed("brightness_contrast_draw", dev):
+        check(lib.rn_brightness_contrast_draw(_ptr(block), B, _ptr(coef), int(fresh), _stream(dev)), "rn_brightness_contrast_draw")
+    return coef
+
+
+def brightness_contrast_mean(images, coef: Tensor, workspace: Optional[Tensor] = None, return_ref: bool = False):
+    """``rn_brightness_contrast_mean``: for the rows whose bit 17 is set, ``bc_add`` = beta times the mean of all values of image b as
+    it is after its colour operations, and the bit cleared (in place; returns ``coef``) -- launch it after ``color_mean``.  ``images``:
+    CUDA f32 ``[3, h, w]`` tensors, or ``StagedImages``.  No atomics, a fixed order of every sum; a second call changes nothing.
+    ``workspace``: uint8, >= ``rn_brightness_contrast_mean_workspace_bytes(B)``.  ``return_ref``: also the f32 [B] view of the workspace
+    where the launch left the mean of every row it served (the other entries are not written)."""
+    staged = isinstance(images, StagedImages)
+    dev = _need_dev(coef, *((images.arena, images.in_hw) if staged else images))
+    B = images.B if staged else len(images)
+    _check_coef(coef, B, dev)
+    need = int(lib.rn_brightness_contrast_mean_workspace_bytes(B))
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    _need_dev(workspace)
+    nbytes = int(workspace.numel() * workspace.element_size())
+    with torch.cuda.device(dev), _timed("brightness_contrast_mean", dev):
+        if staged:
+            check(lib.rn_brightness_contrast_mean(None, None, _ptr(images.arena), images.slot, _ptr(images.in_hw), B, _ptr(coef),
+                                                  _ptr(workspace), nbytes, _stream(dev)), "rn_brightness_contrast_mean")
+        else:
+            imgs = []
+            for im in images:
+                if im.dim() != 3 or im.shape[0] != 3 or im.dtype != torch.float32:
+                    raise ValueError(f"brightness_contrast_mean expects f32 [3, h, w] images, got {tuple(im.shape)} {im.dtype}")
+                imgs.append(im if im.is_contiguous() else im.contiguous())
+            ptrs = (C.c_void_p * B)(*[im.data_ptr() for im in imgs])
+            in_hw = (C.c_int32 * (2 * B))(*[int(v) for im in imgs for v in im.shape[1:]])
+            check(lib.rn_brightness_contrast_mean(ptrs, in_hw, None, 0, None, B, _ptr(coef), _ptr(workspace), nbytes, _stream(dev)),
+                  "rn_brightness_contrast_mean")
+    if return_ref:
+        at = int(lib.rn_color_mean_workspace_bytes(B))
+        return coef, workspace.view(torch.uint8).reshape(-1)[at:at + 4 * B].view(torch.float32)
     return coef
 
 

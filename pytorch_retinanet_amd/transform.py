@@ -44,6 +44,15 @@ over the source images when a contrast is enabled (``rn_color_mean``), and the o
 source pixel it reads (``rn_transform_batch_color``); the rows stay on the device as ``color_jitter.coef``.  The PyTorch path draws the
 same stream from the Python restatement and applies ``augment.apply_color_ops``.  ``color_jitter`` is a plain attribute too.
 
+Train-time brightness / contrast (``brightness_contrast``: an ``augment.RandomBrightnessContrast``, None by default): in training mode
+and when targets are given, each image becomes ``clamp(alpha x + beta ref)`` with probability p -- albumentations'
+``RandomBrightnessContrast`` on the raw fp32 RGB image in [0, 1], after the crop, the warp and the colour jitter's operations, before the
+normalisation, the resize and the flip.  On the fused paths its two coefficients are drawn into the colour jitter's rows
+(``rn_brightness_contrast_draw``; fresh identity rows without a jitter), the by-mean reference is one more pair of launches over the
+source images (``rn_brightness_contrast_mean``, only with ``brightness_by_max=False``), and the transform kernel applies them to every
+source pixel it reads; the rows stay on the device as ``brightness_contrast.coef``.  The PyTorch path draws the same stream from the
+Python restatement and applies ``augment.apply_brightness_contrast``.  A plain attribute too.
+
 Staged images (``forward(ops.StagedImages, packed GT, canvas=(Hp, Wp))``: the image capacity mode of ``graph.CapturedTrainStep``):
 the batch lies in a fixed device arena with its sizes next to it (``ops.image_stage``), and nothing this call launches takes an
 image's address or size as an argument -- the resize plan (``rn_resize_plan_dev``: the fixed short side, or the ``scale_jitter``'s
@@ -157,6 +166,7 @@ class GeneralizedRCNNTransform(nn.Module):
         self.hflip = None             # augment.RandomHorizontalFlip: the train-time flip (module docstring)
         self.scale_jitter = None      # augment.RandomShortSide: the short side drawn on the device (module docstring)
         self.color_jitter = None      # augment.ColorJitter: the colour jitter drawn and applied on the device (module docstring)
+        self.brightness_contrast = None   # augment.RandomBrightnessContrast: alpha x + beta ref behind the colour jitter (module docstring)
         self.crop = None              # augment.BBoxSafeRandomCrop: the bbox-safe random crop, before everything else (module docstring)
         self.shift_scale_rotate = None    # augment.ShiftScaleRotate: shift / scale / rotate, after the crop (module docstring)
 
@@ -225,12 +235,15 @@ class GeneralizedRCNNTransform(nn.Module):
         return self.scale_jitter if self.scale_jitter is not None and self.training and targets is not None else None
 
     def _color(self, images, targets) -> Optional[Tensor]:
-        """This batch's ``rn_color_coef`` rows (f32 [B, 8] on the images' device; the jitter's counter advances), or None when no
-        ``color_jitter`` acts on this call.  ``images``: fusable CUDA images or ``ops.StagedImages``."""
-        cj = getattr(self, "color_jitter", None)
-        if cj is None or not self.training or targets is None:
+        """This batch's ``rn_color_coef`` rows (f32 [B, 8] on the images' device; the counters of the objects that act advance), or
+        None when neither ``color_jitter`` nor ``brightness_contrast`` acts on this call.  The jitter draws first (its contrast mean
+        included); brightness / contrast writes its two coefficients into the same rows, or into fresh identity rows.  ``images``:
+        fusable CUDA images or ``ops.StagedImages``."""
+        if not self.training or targets is None:
             return None
-        return cj.next_coef(images)
+        cj, bc = getattr(self, "color_jitter", None), getattr(self, "brightness_contrast", None)
+        coef = cj.next_coef(images) if cj is not None else None
+        return bc.next_coef(images, coef) if bc is not None else coef
 
     def _forward_fused_jitter(self, jitter, images: List[Tensor], targets, out_dtype: torch.dtype, channels_last: bool, flags, coef=None):
         "The fused path with the sizes drawn on the device: nothing about the draw reaches the host, the canvas is the bound's."
@@ -484,6 +497,13 @@ class GeneralizedRCNNTransform(nn.Module):
             # the same draw from the Python restatement, applied with torch ops (augment.apply_color_ops) to the raw image
             from .augment import apply_color_ops
             images = [apply_color_ops(im, fac, order) for im, (fac, order) in zip(images, cj.next_draw(len(images)))]
+        bc = getattr(self, "brightness_contrast", None)
+        if bc is not None and self.training and targets is not None:
+            # likewise (augment.apply_brightness_contrast), behind the jitter's operations: the by-mean reference sees their result
+            from .augment import apply_brightness_contrast
+            ref = 1.0 if bc.brightness_by_max else None
+            images = [apply_brightness_contrast(im, alpha, beta, ref) if applied else im
+                      for im, (applied, alpha, beta) in zip(images, bc.next_draw(len(images)))]
         jitter = self._jitter(targets)
         shorts = bounds = None
         if jitter is not None:
