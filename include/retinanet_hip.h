@@ -904,6 +904,25 @@ int rn_image_stage(const void *const *images, const int32_t *in_hw, int B, float
 int rn_transform_batch_var(const float *arena, int64_t slot, const int32_t *in_hw_dev, const int32_t *out_hw_dev, int B,
                            const float mean[3], const float std[3], int Hp, int Wp, void *out, int out_dtype, int channels_last,
                            const uint8_t *flags_or_null, void *stream);
+/* rn_image_stage_u8: rn_image_stage for the images a decoder gives -- uint8, planes or interleaved -- converted on the way into the
+ * SAME fp32 [3][h][w] arena, so that everything downstream (rn_resize_plan_dev, rn_color_mean, rn_transform_batch_var / _color, the
+ * crop and warp stages, rn_detect_finish_var) runs unchanged.  The rule:
+ *   1. images: HOST array of B DEVICE pointers to dense uint8 images, ANY byte alignment; in_hw: HOST i32[B][2] = (h, w);
+ *      layout: HOST i32[B], 0 = planes [3][h][w], 1 = interleaved [h][w][3].  Layouts may differ within one call.
+ *   2. Slot b (arena + b * slot) gets out[c][p] = q(in[c h w + p]) (planes) or q(in[3 p + c]) (interleaved) for c < 3, p < h w, and
+ *      in_hw_dev[b] = (h, w).  Exactly 3 h w source bytes are read and 3 h w floats written; floats [3 h w, slot) are left untouched.
+ *   3. q(v) = float(v) / 255.0f: the correctly rounded fp32 QUOTIENT, one IEEE division -- what numpy's float32(v) / float32(255) and
+ *      torchvision's to_tensor give.  It is NOT float(v) * (1.0f / 255.0f): that product differs from the quotient in the last bit
+ *      for 126 of the 256 values (3, 6, 7, 12, 13, ...).  The slot is therefore bit for bit what rn_image_stage leaves for the image
+ *      converted on the CPU.
+ *   4. One launch per 64 images (pointers, sizes and layouts by value in the kernel arguments), at most 256 blocks of 256 threads per
+ *      image and a grid-stride loop; a thread converts 16 pixels per step from 16-byte loads (after a head that brings the source
+ *      address to 16 bytes, then a tail, both byte-wise) and stores 16 bytes per lane where the destination plane is 16-byte aligned.
+ *   5. Every check is made on the host before anything is launched: a rejected call leaves the arena as it was.  RN_EINVAL: a null
+ *      pointer, B <= 0, slot <= 0, h or w <= 0, h w > slot / 3 (no overflow), a layout other than 0 or 1; RN_EALIGN: the arena not
+ *      16-byte aligned, in_hw_dev not 4-byte aligned. */
+int rn_image_stage_u8(const void *const *images, const int32_t *in_hw, const int32_t *layout, int B, float *arena, int64_t slot,
+                      int32_t *in_hw_dev, void *stream);
 
 /* ---- train-time augmentation: the horizontal-flip decision, drawn on the device ------------------------------------
  * rn_hflip_state: a DEVICE block (8-byte aligned) owned by augment.RandomHorizontalFlip, written by the host outside any capture.

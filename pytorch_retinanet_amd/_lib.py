@@ -197,6 +197,7 @@ SIGNATURES = {
     "rn_transform_batch_dev": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_f32), C.POINTER(_f32), C.c_int, C.c_int, _vp,
                                          C.c_int, C.c_int, _vp, _vp, _vp]),
     "rn_image_stage": (C.c_int, [_vp, C.POINTER(_i32), C.c_int, _vp, _i64, _vp, _vp]),
+    "rn_image_stage_u8": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.c_int, _vp, _i64, _vp, _vp]),
     "rn_transform_batch_var": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, C.POINTER(_f32), C.POINTER(_f32), C.c_int, C.c_int, _vp,
                                          C.c_int, C.c_int, _vp, _vp]),
     "rn_hflip_draw": (C.c_int, [_vp, C.c_int, _vp, _vp]),

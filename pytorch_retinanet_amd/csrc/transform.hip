@@ -37,6 +37,11 @@
 // images with the pointers and sizes passed BY VALUE in the kernel arguments (like rn_gt_stage), 16-byte vector copies when the
 // source is 16-byte aligned (a slot always is) and 4-byte copies otherwise and for the tail.
 //
+// rn_image_stage_u8 is that launch for uint8 sources, planes [3][h][w] or interleaved [h][w][3] (what image decoders give), converted
+// on the way: slot b holds float(v) / 255.0f -- ONE correctly rounded division, never the product with 1 / 255, which differs in the
+// last bit for 126 of the 256 bytes -- as dense [3][h][w], i.e. the bits rn_image_stage leaves for the image converted on the CPU.
+// Per step a thread turns 16 pixels (48 or 16 source bytes as 16-byte loads) into 16 floats per channel.
+//
 // rn_transform_batch_color is any of the launches above with the train-time colour jitter (augment.ColorJitter) applied to the raw
 // pixels: template flag COLOR, and per image a rn_color_coef on the device (rn_color_jitter_draw writes the factors and the order
 // inside a captured step, rn_color_mean the contrast mean).  With COLOR every tap loads its three channels, runs the operations of
@@ -305,7 +310,120 @@ __global__ __launch_bounds__(IS_BLOCK) void image_stage_kernel(const ImageStageT
     }
 }
 
+// ---- the same for the uint8 images a decoder gives: planes or interleaved, converted on the way into the fp32 arena -----------------
+constexpr int IS_U8_PX = 16;        // pixels per thread and step: C 16-byte loads of a C-channel source
+
+struct ImageStageU8Table {
+    const uint8_t *src[IS_MAX];
+    int32_t h[IS_MAX], w[IS_MAX], layout[IS_MAX];      // layout 0: [3][h][w], 1: [h][w][3]
+};
+
+// the correctly rounded quotient (this file is built without contraction and with the IEEE divide): NOT v * (1 / 255)
+__device__ __forceinline__ float u8_unit(const uint32_t v) { return (float)v / 255.0f; }
+
+// n pixels of C interleaved bytes each at s (any alignment) -> channel c of pixel p to d[c * plane + p].  Reads exactly C * n bytes and
+// writes exactly n floats per channel.  The first ``head`` pixels bring the source to a 16-byte boundary (C is odd, so C * head =
+// -s mod 16 has one solution below 16: head = -s * C^-1 mod 16); from there a thread takes IS_U8_PX pixels per step as C 16-byte
+// loads, and the pixels after the last whole step are the tail.  Head and tail go byte by byte.  A channel whose first stepped float
+// d + c * plane + head is 16-byte aligned is stored 16 bytes per lane, any other 4 bytes per lane (the test is per image and channel:
+// wave-uniform).
+template <int C>
+__device__ __forceinline__ void stage_u8_run(const uint8_t *__restrict__ s, float *__restrict__ d, const int64_t plane, const int64_t n,
+                                             const int64_t tid, const int64_t step)
+{
+    static_assert(C == 1 || C == 3, "C^-1 mod 16 below");
+    constexpr int CINV = C == 3 ? 11 : 1;
+    int64_t head = (int64_t)((((16 - ((uintptr_t)s & 15)) & 15) * CINV) & 15);
+    head = head < n ? head : n;
+    const int64_t steps = (n - head) / IS_U8_PX;
+    const int64_t tail = head + steps * IS_U8_PX, rest = head + (n - tail);
+    for (int64_t e = tid; e < rest; e += step) {
+        const int64_t p = e < head ? e : tail + (e - head);
+#pragma unroll
+        for (int c = 0; c < C; ++c) d[c * plane + p] = u8_unit(s[C * p + c]);
+    }
+    const rn::u32x4 *__restrict__ sv = (const rn::u32x4 *)(s + C * head);
+    for (int64_t j = tid; j < steps; j += step) {
+        rn::u32x4 q[C];
+#pragma unroll
+        for (int i = 0; i < C; ++i) q[i] = sv[C * j + i];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            float v[IS_U8_PX];
+#pragma unroll
+            for (int p = 0; p < IS_U8_PX; ++p) {
+                const int k = C * p + c;                           // byte k of the C * 16 loaded
+                v[p] = u8_unit((q[k >> 4][(k >> 2) & 3] >> ((k & 3) * 8)) & 0xffu);
+            }
+            float *__restrict__ o = d + c * plane + head + j * IS_U8_PX;
+            if ((((uintptr_t)o) & 15) == 0) {
+#pragma unroll
+                for (int g = 0; g < IS_U8_PX / 4; ++g) {
+                    rn::f32x4 f; f.x = v[4 * g]; f.y = v[4 * g + 1]; f.z = v[4 * g + 2]; f.w = v[4 * g + 3];
+                    ((rn::f32x4 *)o)[g] = f;
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < IS_U8_PX; ++p) o[p] = v[p];
+            }
+        }
+    }
+}
+
+// (launch shape and table as image_stage_kernel; the layout is per image, so the branch is block-uniform)
+__global__ __launch_bounds__(IS_BLOCK) void image_stage_u8_kernel(const ImageStageU8Table t, float *__restrict__ arena, const int64_t slot,
+                                                                 int32_t *__restrict__ in_hw, const int base)
+{
+    const int i = blockIdx.y;
+    const uint8_t *__restrict__ s = t.src[i];
+    float *__restrict__ d = arena + (int64_t)(base + i) * slot;
+    const int64_t plane = (int64_t)t.h[i] * t.w[i];                // (3 * plane <= slot: checked on the host)
+    const int64_t tid = (int64_t)blockIdx.x * IS_BLOCK + threadIdx.x, step = (int64_t)gridDim.x * IS_BLOCK;
+    if (t.layout[i] == 1) {
+        stage_u8_run<3>(s, d, plane, plane, tid, step);
+    } else {
+        for (int c = 0; c < 3; ++c) stage_u8_run<1>(s + c * plane, d + c * plane, plane, plane, tid, step);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        in_hw[2 * (base + i)] = t.h[i];
+        in_hw[2 * (base + i) + 1] = t.w[i];
+    }
+}
+
 }  // namespace
+
+RN_API int rn_image_stage_u8(const void *const *images, const int32_t *in_hw, const int32_t *layout, int B, float *arena, int64_t slot,
+                             int32_t *in_hw_dev, void *stream)
+{
+    if (!images || !in_hw || !layout || !arena || !in_hw_dev || B <= 0 || slot <= 0) return RN_EINVAL;
+    if (!rn::aligned(arena, 16) || !rn::aligned(in_hw_dev, 4)) return RN_EALIGN;
+    // every argument is checked before anything is launched: a rejected call leaves the arena as it was (a source needs no alignment)
+    for (int b = 0; b < B; ++b) {
+        const int64_t h = in_hw[2 * b], w = in_hw[2 * b + 1];
+        if (!images[b] || h <= 0 || w <= 0 || h * w > slot / 3) return RN_EINVAL;      // (3 * h * w > slot, without the overflow)
+        if (layout[b] != 0 && layout[b] != 1) return RN_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int base = 0; base < B; base += IS_MAX) {
+        const int cnt = (B - base) < IS_MAX ? (B - base) : IS_MAX;
+        ImageStageU8Table t;
+        int64_t most = 0;
+        for (int i = 0; i < IS_MAX; ++i) {
+            const bool on = i < cnt;
+            t.src[i] = on ? (const uint8_t *)images[base + i] : nullptr;
+            t.h[i] = on ? in_hw[2 * (base + i)] : 0;
+            t.w[i] = on ? in_hw[2 * (base + i) + 1] : 0;
+            t.layout[i] = on ? layout[base + i] : 0;
+            const int64_t px = (int64_t)t.h[i] * t.w[i];
+            if (px > most) most = px;
+        }
+        int64_t bx = (most / IS_U8_PX + IS_BLOCK - 1) / IS_BLOCK;
+        bx = bx < 1 ? 1 : (bx > IS_GRID_X ? IS_GRID_X : bx);
+        hipLaunchKernelGGL(image_stage_u8_kernel, dim3((unsigned)bx, (unsigned)cnt), dim3(IS_BLOCK), 0, st, t, arena, slot, in_hw_dev, base);
+        RN_LAUNCH_CHECK();
+    }
+    return RN_OK;
+}
 
 RN_API int rn_image_stage(const void *const *images, const int32_t *in_hw, int B, float *arena, int64_t slot, int32_t *in_hw_dev, void *stream)
 {

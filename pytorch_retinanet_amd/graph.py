@@ -81,7 +81,8 @@ sizes written on the device); the step then runs on that ``ops.StagedImages``.  
 kernel read every input size from device memory (``rn_resize_plan_dev``, ``rn_gt_flip_scale_packed_var``, ``rn_transform_batch_var``)
 and write the class canvas.  The cost: the conv stack processes the class canvas whatever the batch's own canvas was; a finer class
 list trades captures for compute.  A batch that fits no class -- or whose GT fits no capacity class -- keeps the exact-shape key
-and path.  fp32 CHW CUDA images only (uint8 / HWC input is not implemented).
+and path.  CUDA images, all fp32 ``[3, h, w]`` (copied: ``ops.image_stage``) or all uint8 ``[3, h, w]``, planes or interleaved (converted on the way in:
+``ops.image_stage_u8``); the arena is fp32 either way, so both kinds of batch share one graph per class.
 
 Inference (``CapturedPredict``, at the end of this file): ``net.predict(images)`` as one graph replay per batch, for batches whose image sizes
 vary.  A batch is keyed by B, its canvas class and pixel class (the same ``image_capacity_classes`` / ``image_canvas_class`` / ``image_pixel_class``,
@@ -192,6 +193,23 @@ def image_pixel_class(in_hw: Sequence[Tuple[int, int]]) -> int:
     "The smallest power of two >= the largest h x w of the batch, at least ``IMAGE_PIXEL_CLASS_FLOOR``."
     most = max((int(h) * int(w) for h, w in in_hw), default=0)
     return max(IMAGE_PIXEL_CLASS_FLOOR, 1 << max(most - 1, 0).bit_length())
+
+
+def _all_u8(images) -> bool:
+    "Every image a CUDA uint8 ``[3, h, w]`` tensor: what ``ops.image_stage_u8`` stages (planes, interleaved or any other strides)."
+    return len(images) > 0 and all(im.is_cuda and im.dim() == 3 and im.shape[0] == 3 and im.dtype == torch.uint8 for im in images)
+
+
+def _stageable(tr, images) -> bool:
+    """A batch the staged path takes: images the fused transform takes (fp32, ``ops.image_stage``), or -- under the same conditions on
+    the transform -- an all-uint8 batch (``ops.image_stage_u8`` converts it on the way into the same fp32 arena)."""
+    images = list(images)
+    return tr._fusable(images) or (_all_u8(images) and tr._fused_config())
+
+
+def _stage(images, staged, bounds) -> None:
+    "This batch's images into the entry's arena: fp32 images are copied, uint8 ones converted (classed batches are all one or the other)."
+    (ops.image_stage_u8 if images[0].dtype == torch.uint8 else ops.image_stage)(images, staged, bounds=bounds)
 
 
 def _gt_counts(targets) -> List[int]:
@@ -494,7 +512,7 @@ class CapturedTrainStep:
         if self.image_capacity is None or (self._capacity_of(targets) if cap is _UNSET else cap) is None:
             return None
         tr = self.net.transform
-        if not tr._fusable(list(images)) or (getattr(tr, "scale_jitter", None) is None and tr.staged_short_side() is None):
+        if not _stageable(tr, images) or (getattr(tr, "scale_jitter", None) is None and tr.staged_short_side() is None):
             return None
         in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
         bounds = tr.staged_bounds(in_hw)
@@ -515,7 +533,9 @@ class CapturedTrainStep:
         if icls is _UNSET:
             icls = self._image_class_of(images, targets, cap)
         if icls is not None:
-            ims = ("img_cap", len(images), icls[0], icls[1], images[0].dtype, images[0].device)      # (the entry's arena: B slots)
+            # (the entry's arena: B slots.  The dtype is the ARENA's: staging happens outside the graph, so a uint8 batch --
+            # ``ops.image_stage_u8`` -- and an fp32 batch of the same classes share one graph)
+            ims = ("img_cap", len(images), icls[0], icls[1], torch.float32, images[0].device)
         else:
             ims = tuple((tuple(im.shape), im.dtype, im.device) for im in images)
         if cap is not None:
@@ -710,7 +730,7 @@ class CapturedTrainStep:
         if sig.staged is not None:
             # image capacity mode: this batch's images into the signature's arena and their sizes next to them (one launch per 64
             # images, current stream), for eager steps, the capture and replays alike; the step reads nothing but sig.staged
-            ops.image_stage(images, sig.staged, bounds=icls[2])
+            _stage(images, sig.staged, icls[2])
             images = sig.staged
         if e.failed or e.calls <= self.eager_steps:
             return self._step(images, targets, final)
@@ -838,15 +858,19 @@ class CapturedPredict:
     def _autocast(self, dtype):
         return torch.autocast("cuda", dtype=dtype, enabled=dtype is not None, cache_enabled=False)
 
-    def _class_of(self, images) -> Optional[Tuple[Tuple[int, int], int, List[Tuple[int, int]]]]:
+    def _class_of(self, images, u8: bool = False) -> Optional[Tuple[Tuple[int, int], int, List[Tuple[int, int]]]]:
         """The batch's (canvas class, pixel class, per-image resized sizes), or None -- the batch goes to plain ``net.predict``: no
         images, images the fused transform does not take, a net or transform in training mode, a short side the device plan cannot
-        take, or a canvas no class contains.  Host arithmetic on the image shapes; nothing synchronises."""
+        take, or a canvas no class contains.  Host arithmetic on the image shapes; nothing synchronises.  ``u8``: class an all-uint8
+        ``[3, h, w]`` CUDA batch like an fp32 one (``__call__`` does: ``ops.image_stage_u8`` converts it on the way into the same
+        fp32 arena); by default only what the fused transform takes is classed."""
         net = self.net
         tr = net.transform
         if not isinstance(images, (list, tuple)) or not images or net.training or tr.training:
             return None
-        if not all(isinstance(im, Tensor) for im in images) or not tr._fusable(list(images)) or tr.staged_eval_short_side() is None:
+        if not all(isinstance(im, Tensor) for im in images) or tr.staged_eval_short_side() is None:
+            return None
+        if not (_stageable(tr, images) if u8 else tr._fusable(list(images))):
             return None
         if any(im.device != images[0].device for im in images):
             return None
@@ -911,7 +935,7 @@ class CapturedPredict:
         if to not in ("cpu", "device"):
             raise ValueError(f"to: expected 'cpu' or 'device', got {to!r}")
         dtype = self._autocast_dtype()
-        icls = self._class_of(images)
+        icls = self._class_of(images, u8=True)
         if icls is None:
             out = self._fallback(images, dtype)
             return out if to == "device" else [{k: v.cpu() for k, v in d.items()} for d in out]
@@ -941,7 +965,7 @@ class CapturedPredict:
             self._entries.move_to_end(key)
         e.calls += 1
         # this batch's images into the entry's arena and their sizes next to them: eager calls, the capture and replays alike
-        ops.image_stage(images, e.staged, bounds=icls[2])
+        _stage(images, e.staged, icls[2])
         if e.graph is None and not e.failed and e.calls > self.eager_calls:
             try:
                 torch.cuda.synchronize()

@@ -111,9 +111,12 @@ class RetinaNetModel(_Base):
             self.net.transform.crop = bbox_crop_from_transforms(self.conf.get("transforms"))
             # an albumentations.ShiftScaleRotate entry becomes the transform's shift / scale / rotate (augment.ShiftScaleRotate)
             self.net.transform.shift_scale_rotate = shift_scale_rotate_from_transforms(self.conf.get("transforms"))
-            self.trn_ds = CSVDetectionDataset(d.trn_paths)
-            self.val_ds = CSVDetectionDataset(d.val_paths) if d.get("val_paths") else None
-            self.test_ds = CSVDetectionDataset(d.test_paths) if d.get("test_paths") else None
+            # dataset.image_dtype (optional; "float32" or "uint8"): "uint8" hands the decoder's bytes to the model, which converts them
+            # on the device (ops.image_stage_u8 on the staged path, ops.images_u8_to_f32 in the transform)
+            dt = d.get("image_dtype") or "float32"
+            self.trn_ds = CSVDetectionDataset(d.trn_paths, image_dtype=dt)
+            self.val_ds = CSVDetectionDataset(d.val_paths, image_dtype=dt) if d.get("val_paths") else None
+            self.test_ds = CSVDetectionDataset(d.test_paths, image_dtype=dt) if d.get("test_paths") else None
         elif d.kind in ("coco", "pascal"):
             raise NotImplementedError(
                 f"dataset.kind={d.kind!r}: the reference's COCO-json / Pascal-xml readers (utils/coco, utils/pascal; "

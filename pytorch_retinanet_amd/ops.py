@@ -926,7 +926,8 @@ def new_image_arena(B: int, pixel_class: int, dev: torch.device, canvas: Optiona
 def image_stage(images: Sequence[Tensor], out: StagedImages, bounds: Optional[Sequence[Tuple[int, int]]] = None) -> StagedImages:
     """The images (CUDA f32 ``[3, h_b, w_b]`` on ``out``'s device) into ``out``'s arena, ``in_hw`` = their sizes: one launch per 64
     images (``rn_image_stage``) on the current stream; no host copy, no synchronisation.  Strided images are made dense first.
-    ValueError for another dtype or layout (uint8 / HWC input is not implemented), a zero size or an image above the slot.
+    ValueError for another dtype or layout (this op takes f32 CHW only: uint8 images, planes or interleaved, go through
+    ``image_stage_u8`` below, which fills the same arena), a zero size or an image above the slot.
     ``bounds``: the per-image sizes after the resize, when the caller has them (kept as ``out.bounds`` for the transform)."""
     dev = _need_dev(out.arena, *images)
     B = len(images)
@@ -948,6 +949,97 @@ def image_stage(images: Sequence[Tensor], out: StagedImages, bounds: Optional[Se
         raise ValueError(f"{len(bounds)} bounds for {B} images")
     out.hw, out.bounds = hw, (None if bounds is None else [(int(h), int(w)) for h, w in bounds])
     return out
+
+
+U8_PLANES, U8_INTERLEAVED = 0, 1          # rn_image_stage_u8's layout codes
+
+
+def _u8_image(im: Tensor, who: str) -> Tuple[Tensor, int, Tuple[int, int]]:
+    """One uint8 ``[3, h, w]`` image -> (a dense tensor, its layout code, (h, w)).  The layout is read from the strides: contiguous is
+    planes; strides ``(1, 3 w, 3)`` -- ``torch.from_numpy(hwc).permute(2, 0, 1)``, which ``.to(device)`` preserves -- are interleaved
+    (the stride of a dimension of size 1 is free); anything else is made contiguous (planes)."""
+    if im.dim() != 3 or im.shape[0] != 3 or im.dtype != torch.uint8:
+        raise ValueError(f"{who} expects uint8 [3, h, w] images, got {tuple(im.shape)} {im.dtype}")
+    h, w = int(im.shape[1]), int(im.shape[2])
+    if im.is_contiguous():
+        return im, U8_PLANES, (h, w)
+    s = im.stride()
+    if h > 0 and w > 0 and s[0] == 1 and (h == 1 or s[1] == 3 * w) and (w == 1 or s[2] == 3):
+        return im, U8_INTERLEAVED, (h, w)
+    return im.contiguous(), U8_PLANES, (h, w)
+
+
+def _u8_check(im: Tensor, who: str) -> None:
+    "``_u8_image``'s dtype / shape check plus: no empty image (the conversions; the stager words that as \"does not fit\")."
+    if im.dim() != 3 or im.shape[0] != 3 or im.dtype != torch.uint8:
+        raise ValueError(f"{who} expects uint8 [3, h, w] images, got {tuple(im.shape)} {im.dtype}")
+    if im.shape[1] <= 0 or im.shape[2] <= 0:
+        raise ValueError(f"{who}: an empty {int(im.shape[1])} x {int(im.shape[2])} image")
+
+
+def _image_stage_u8(imgs: Sequence[Tensor], layouts: Sequence[int], hw: Sequence[Tuple[int, int]], arena: Tensor, slot: int, in_hw: Tensor,
+                    dev: torch.device) -> None:
+    B = len(imgs)
+    with torch.cuda.device(dev), _timed("image_stage_u8", dev):
+        check(lib.rn_image_stage_u8((C.c_void_p * B)(*[im.data_ptr() for im in imgs]), (C.c_int32 * (2 * B))(*[v for s in hw for v in s]),
+                                    (C.c_int32 * B)(*layouts), B, _ptr(arena), slot, _ptr(in_hw), _stream(dev)), "rn_image_stage_u8")
+
+
+def image_stage_u8(images: Sequence[Tensor], out: StagedImages, bounds: Optional[Sequence[Tuple[int, int]]] = None) -> StagedImages:
+    """``image_stage`` for the images a decoder gives: CUDA uint8 ``[3, h_b, w_b]`` tensors on ``out``'s device, planes (contiguous) or
+    interleaved (strides ``(1, 3 w, 3)``: an HWC array permuted to the code base's shape), converted on the way into the same fp32
+    arena (``rn_image_stage_u8``): slot b holds ``float(v) / 255`` -- the correctly rounded quotient, bit for bit what ``image_stage``
+    leaves for ``im.to(float32) / 255`` computed on the CPU.  One launch per 64 images on the current stream; no host copy, no
+    synchronisation; other strides are made contiguous first.  ValueError for another dtype or shape, a zero size, an image above
+    the slot or a wrong count; nothing is written then."""
+    dev = _need_dev(out.arena, *images)
+    B = len(images)
+    if B != out.B:
+        raise ValueError(f"{B} images for an arena of {out.B} slots")
+    if bounds is not None and len(bounds) != B:
+        raise ValueError(f"{len(bounds)} bounds for {B} images")
+    imgs, layouts, hw = [], [], []
+    for im in images:
+        im, layout, (h, w) = _u8_image(im, "image_stage_u8")
+        if h <= 0 or w <= 0 or 3 * h * w > out.slot:
+            raise ValueError(f"a {h} x {w} image does not fit an arena slot of {out.slot} floats")
+        imgs.append(im)
+        layouts.append(layout)
+        hw.append((h, w))
+    _image_stage_u8(imgs, layouts, hw, out.arena, out.slot, out.in_hw, dev)
+    out.hw, out.bounds = hw, (None if bounds is None else [(int(h), int(w)) for h, w in bounds])
+    return out
+
+
+def images_u8_to_f32(images: Sequence[Tensor]) -> List[Tensor]:
+    """uint8 ``[3, h, w]`` images (planes or interleaved, as ``image_stage_u8`` takes them) -> dense fp32 ``[3, h, w]`` images in [0, 1],
+    ``float(v) / 255`` with ONE correctly rounded division: the conversion of ``image_stage_u8`` for images that are not staged.  CUDA
+    images: one ``rn_image_stage_u8`` call per 64 images into a fresh buffer (slot: 3 x the largest ``h w``, rounded up to a multiple
+    of 4), the results are views of it.  CPU images: ``im.to(float32) / 255`` -- a true division; both give the same bits.  (Never
+    ``x.div(255)`` on the device: torch computes that with the rounded reciprocal, which is off by one bit for 126 of the 256 bytes.)"""
+    images = list(images)
+    if not images:
+        return []
+    if all(not im.is_cuda for im in images):
+        for im in images:
+            _u8_check(im, "images_u8_to_f32")
+        return [(im.to(torch.float32) / 255).contiguous() for im in images]
+    dev = _need_dev(*images)
+    imgs, layouts, hw = [], [], []
+    for im in images:
+        _u8_check(im, "images_u8_to_f32")
+        im, layout, (h, w) = _u8_image(im, "images_u8_to_f32")
+        imgs.append(im)
+        layouts.append(layout)
+        hw.append((h, w))
+    B = len(imgs)
+    slot = (3 * max(h * w for h, w in hw) + 3) // 4 * 4
+    arena = torch.empty((B, slot), dtype=torch.float32, device=dev)
+    in_hw = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    for lo in range(0, B, 64):
+        hi = min(lo + 64, B)
+        _image_stage_u8(imgs[lo:hi], layouts[lo:hi], hw[lo:hi], arena[lo:hi], slot, in_hw[lo:hi], dev)
+    return [arena[b, : 3 * h * w].view(3, h, w) for b, (h, w) in enumerate(hw)]
 
 
 def resize_plan_dev(block: Optional[Tensor], in_hw: Tensor, short: Optional[int], max_size: int) -> Tuple[Tensor, Tensor]:

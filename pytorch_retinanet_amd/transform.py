@@ -14,7 +14,10 @@ For CUDA fp32 images the normalise / resize / pad / batch sequence is ONE HIP la
 directly in the layout and dtype the conv stack consumes (channels-last, autocast dtype), so the
 per-image elementwise kernels, the batch memset + copies, the ``contiguous(channels_last)`` pass
 and autocast's cast of the conv1 input all disappear.  Anything else (CPU tensors, other dtypes)
-takes the PyTorch ops below, which implement the same arithmetic.
+takes the PyTorch ops below, which implement the same arithmetic.  uint8 ``[3, h, w]`` images -- planes or
+interleaved, what image decoders give -- are converted to fp32 in [0, 1] first (``ops.images_u8_to_f32``:
+``float(v) / 255`` with one correctly rounded division; ``rn_image_stage_u8`` on CUDA, a true division on the
+CPU, the same bits) and then take the same two paths.
 
 Train-time horizontal flip (``hflip``: an ``augment.RandomHorizontalFlip``, None by default): in training mode and when targets
 are given, each image is flipped with probability p before the normalise / resize, and its boxes with it (x1' = W - x2,
@@ -219,10 +222,13 @@ class GeneralizedRCNNTransform(nn.Module):
         return out
 
     # -- fused path ----------------------------------------------------------------------
+    def _fused_config(self) -> bool:
+        "What the HIP transform kernels need of THIS module, whatever the images: three channels, a canvas in multiples of 4."
+        return len(self.image_mean) == 3 and len(self.image_std) == 3 and self.size_divisible % 4 == 0
+
     def _fusable(self, images: List[Tensor]) -> bool:
-        return (len(self.image_mean) == 3 and len(self.image_std) == 3 and
-                all(im.is_cuda and im.dim() == 3 and im.shape[0] == 3 and im.dtype == torch.float32 for im in images)
-                and self.size_divisible % 4 == 0)
+        return (self._fused_config() and
+                all(im.is_cuda and im.dim() == 3 and im.shape[0] == 3 and im.dtype == torch.float32 for im in images))
 
     def _flips(self, images: List[Tensor], targets) -> Optional[Tensor]:
         "This batch's flip decisions (uint8 [B], on the images' device; the flip's counter advances), or None when nothing flips."
@@ -464,6 +470,19 @@ class GeneralizedRCNNTransform(nn.Module):
                 t["labels"] = lb
         return images, targets
 
+    @staticmethod
+    def _u8_to_f32(images: List[Tensor]) -> List[Tensor]:
+        """uint8 ``[3, h, w]`` images (planes or interleaved: what image decoders give) become fp32 in [0, 1] first -- ``float(v) / 255``,
+        ``ops.images_u8_to_f32``: one HIP launch per 64 CUDA images, a true division on the CPU, the same bits -- and then take the
+        paths below like any fp32 image.  All at once when the whole list is uint8, image by image in a mixed list."""
+        u8 = [im.dtype == torch.uint8 and im.shape[0] == 3 for im in images]
+        if not any(u8):
+            return images
+        from . import ops
+        if all(u8):
+            return ops.images_u8_to_f32(images)
+        return [ops.images_u8_to_f32([im])[0] if u else im for im, u in zip(images, u8)]
+
     # -- whole transform -----------------------------------------------------------------
     def forward(self, images: List[Tensor], targets: Optional[List[Dict[str, Tensor]]] = None,
                 out_dtype: Optional[torch.dtype] = None, channels_last: bool = False, canvas: Optional[Tuple[int, int]] = None):
@@ -485,6 +504,7 @@ class GeneralizedRCNNTransform(nn.Module):
         for im in images:
             if im.dim() != 3:
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(im.shape)}")
+        images = self._u8_to_f32(images)
         if getattr(self, "crop", None) is not None and self.training and targets is not None:
             images, targets = self._crop_on_host(images, targets)
         if getattr(self, "shift_scale_rotate", None) is not None and self.training and targets is not None:
