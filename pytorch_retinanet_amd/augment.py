@@ -852,6 +852,11 @@ def _entry_p(params: dict, default: float) -> float:
     return 1.0 if params.get("always_apply") else float(params.get("p", default))
 
 
+def _as_limit(v):
+    "An entry's limit as the classes take it: YAML's list as a tuple (a range), a scalar as it is."
+    return tuple(v) if isinstance(v, (list, tuple)) else v
+
+
 _BBOX_CROP_NAMES = ("albumentations.BBoxSafeRandomCrop", "BBoxSafeRandomCrop")
 
 
@@ -1127,9 +1132,8 @@ def shift_scale_rotate_from_transforms(entries, seed: int = 0, log=None) -> Opti
             if params.get(key) not in defaults:
                 log.warning("transforms: %s %s=%s is not implemented and is ignored (bilinear interpolation, the reflect-101 border and "
                             "one shift_limit for both axes are)", name, key, params.get(key))
-        as_limit = lambda v: tuple(v) if isinstance(v, (list, tuple)) else v
-        found = ShiftScaleRotate(shift_limit=as_limit(params.get("shift_limit", 0.0625)), scale_limit=as_limit(params.get("scale_limit", 0.1)),
-                                 rotate_limit=as_limit(params.get("rotate_limit", 45)), p=_entry_p(params, 0.5), seed=seed)
+        found = ShiftScaleRotate(shift_limit=_as_limit(params.get("shift_limit", 0.0625)), scale_limit=_as_limit(params.get("scale_limit", 0.1)),
+                                 rotate_limit=_as_limit(params.get("rotate_limit", 45)), p=_entry_p(params, 0.5), seed=seed)
     return found
 
 
@@ -1146,8 +1150,7 @@ def color_jitter_from_transforms(entries, seed: int = 0, log=None) -> Optional[C
     for name, params in _named(entries, _COLOR_JITTER_NAMES, "colour jitter", log):
         alb = name.startswith("albumentations.")
         default = 0.2 if alb else 0
-        kw = {n: params.get(n, default) for n in COLOR_OPS}
-        found = ColorJitter(p=_entry_p(params, 0.5 if alb else 1.0), seed=seed, **{n: (tuple(v) if isinstance(v, (list, tuple)) else v) for n, v in kw.items()})
+        found = ColorJitter(p=_entry_p(params, 0.5 if alb else 1.0), seed=seed, **{n: _as_limit(params.get(n, default)) for n in COLOR_OPS})
     return found
 
 
@@ -1163,11 +1166,20 @@ def brightness_contrast_from_transforms(entries, seed: int = 0, log=None) -> Opt
     log = log or logging.getLogger(__name__)
     found = None
     for name, params in _named(entries, _BRIGHTNESS_CONTRAST_NAMES, "brightness / contrast", log):
-        as_limit = lambda v: tuple(v) if isinstance(v, (list, tuple)) else v
-        found = RandomBrightnessContrast(brightness_limit=as_limit(params.get("brightness_limit", 0.2)),
-                                         contrast_limit=as_limit(params.get("contrast_limit", 0.2)),
+        found = RandomBrightnessContrast(brightness_limit=_as_limit(params.get("brightness_limit", 0.2)),
+                                         contrast_limit=_as_limit(params.get("contrast_limit", 0.2)),
                                          brightness_by_max=bool(params.get("brightness_by_max", True)), p=_entry_p(params, 0.5), seed=seed)
     return found
+
+
+# (slot of the transform, the class names its mapper owns, the mapper) for every slot but the flip's.  A new mapper registers here, once:
+# ``from_transforms`` leaves these entries to their mappers instead of calling them unsupported, and ``RetinaNetModel.prepare_data``
+# installs what the mappers return.
+SLOT_MAPPERS = (("brightness_contrast", _BRIGHTNESS_CONTRAST_NAMES, brightness_contrast_from_transforms),
+                ("color_jitter", _COLOR_JITTER_NAMES, color_jitter_from_transforms),
+                ("crop", _BBOX_CROP_NAMES, bbox_crop_from_transforms),
+                ("shift_scale_rotate", _SHIFT_SCALE_ROTATE_NAMES, shift_scale_rotate_from_transforms))
+_NAME_OWNER = {name: slot for slot, names, _ in SLOT_MAPPERS for name in names}
 
 
 def from_transforms(entries, seed: int = 0, log=None, brightness_contrast: bool = False) -> Optional[RandomHorizontalFlip]:
@@ -1184,11 +1196,9 @@ def from_transforms(entries, seed: int = 0, log=None, brightness_contrast: bool 
             p = _entry_p(params, 0.5)
         elif short == "RandomHorizontalFlip":
             p = float(params.get("prob", params.get("p", 0.5)))
-        elif name in _COLOR_JITTER_NAMES or name in _BBOX_CROP_NAMES or name in _SHIFT_SCALE_ROTATE_NAMES:
-            continue                                   # color_jitter_ / bbox_crop_ / shift_scale_rotate_from_transforms map these
-        elif name in _BRIGHTNESS_CONTRAST_NAMES and brightness_contrast:
-            continue                                   # brightness_contrast_from_transforms maps it
-        elif name in _BRIGHTNESS_CONTRAST_NAMES:
+        elif name in _NAME_OWNER and (brightness_contrast or _NAME_OWNER[name] != "brightness_contrast"):
+            continue                                   # the slot's own mapper maps it (SLOT_MAPPERS)
+        elif name in _NAME_OWNER:
             log.warning("transforms: %s is skipped: it is implemented on the GPU (augment.RandomBrightnessContrast) but stays off unless "
                         "SimpleTrainer(device_brightness_contrast=True) or trainer.device_brightness_contrast in the hparams installs it", name)
             continue

@@ -31,32 +31,23 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
     Optimizers with device-resident hyperparameters (``optim.MasterAdam`` / ``MasterAdamW``: ``_rn_device_hparams``) are the
     exception: their kernels read lr / betas / eps / weight_decay from device blocks, which ``sync_device_hparams()`` refreshes
     before every replay, so those values are left out of the signature and a per-step LR schedule replays one graph.
-    The train-time flip (``net.transform.hflip``, ``augment.RandomHorizontalFlip``) is keyed by the installed object alone: its
-    decisions are drawn inside the step from the object's device block, so eager steps and replays advance one counter and a
-    new p needs no capture.  Gradient clipping (``optimizer.grad_clip``, ``optim.GradClip``) is keyed the same way: ``max_norm`` is
-    read from the object's device block, whose first (eager) step creates it.
+    The augmentations of the net's transform (``transform.AUGMENT_SLOTS``: ``net.transform.hflip``, ``scale_jitter``, ``color_jitter``,
+    ``crop``, ``shift_scale_rotate``, ``brightness_contrast``), gradient clipping (``optimizer.grad_clip``, ``optim.GradClip``) and a
+    weight average (``optimizer.weight_ema``, ``optim.WeightEMA``) are each keyed by the installed object alone: what they draw or
+    compute happens inside the step and reads its settings, seed and counter from the object's device block (created by the first,
+    eager, step), so eager steps and replays advance one counter, a new p, range or ``max_norm`` needs no capture, and a graph
+    captured without an object is never replayed once one is installed, and the reverse; with none the key is the plain one.  With a
+    ``scale_jitter`` the padded canvas depends on the image shapes alone, so one graph replays while the scales vary (the host-side
+    draw from a ``min_size`` tuple makes nearly every batch a new signature).
     Gradient accumulation (``accumulate=optim.GradAccumulator``) is keyed by the installed object too, and the window position is NOT
     part of the key: it lives in the object's device block.  A signature then holds up to two graphs -- the micro step and the final
     step (``_Signature.steps``) -- each warmed by its own ``eager_steps`` eager calls; ``max_graphs`` still counts signatures.
-    A weight average (``optimizer.weight_ema``, ``optim.WeightEMA``) is keyed by the installed object as well: its update is part of
-    ``optimizer.step`` and reads its factor and count from the object's device block, so a graph captured without one is never
-    replayed once one is installed, and the reverse; without one the key is the plain one.
-    Multi-scale training (``net.transform.scale_jitter``, ``augment.RandomShortSide``) is keyed by the installed object too: the short
-    sides are drawn inside the step from the object's device block and the padded canvas depends on the image shapes alone, so one
-    graph replays while the scales vary (the host-side draw from a ``min_size`` tuple makes nearly every batch a new signature).
-    The colour jitter (``net.transform.color_jitter``, ``augment.ColorJitter``) is keyed by the installed object as well: factors and
-    order are drawn inside the step from its device block, so its ranges and p may change between replays.
-    The bbox-safe random crop (``net.transform.crop``, ``augment.BBoxSafeRandomCrop``) is keyed by the installed object too, and needs
-    the image capacity mode (a ``ValueError`` says so): the rectangles are drawn inside the step from the staged GT and the windows
-    copied into a second arena, so one graph replays while the crops vary and p may change between replays.  A batch no class holds
-    runs eagerly with the crop drawn on the host.
-    Shift / scale / rotate (``net.transform.shift_scale_rotate``, ``augment.ShiftScaleRotate``) is keyed by the installed object too,
-    and needs both capacity modes (a ``ValueError`` says so): the matrices are drawn inside the step, the rows that survive are
+    The bbox-safe random crop (``crop``) needs the image capacity mode (a ``ValueError`` says so): the rectangles are drawn inside
+    the step from the staged GT and the windows copied into a second arena.  A batch no class holds runs eagerly with the crop drawn
+    on the host.
+    Shift / scale / rotate (``shift_scale_rotate``) needs both capacity modes (a ``ValueError`` says so): the rows that survive are
     packed on the device -- the GT counts change from replay to replay, which only packed GT can hold -- and the images are warped
-    into another arena, so one graph replays while the draws vary; p and the ranges may change between replays.  A batch no class
-    holds runs eagerly with the draw on the host.
-    Brightness / contrast (``net.transform.brightness_contrast``, ``augment.RandomBrightnessContrast``) is keyed by the installed object
-    as well: its coefficients are drawn inside the step from its device block, so its limits and p may change between replays.
+    into another arena.  A batch no class holds runs eagerly with the draw on the host.
 
 ``__call__(images, targets)`` performs exactly one optimisation step and returns the loss dict (static tensors: read them
 before the next call).  The first ``eager_steps`` calls with a new signature run eagerly (they are real steps and they warm
@@ -108,6 +99,7 @@ from torch import Tensor
 from . import ops
 from ._lib import check, lib
 from .norm import RAW_WRITES, note_raw_write
+from .transform import augments_of
 
 _log = logging.getLogger(__name__)
 
@@ -499,6 +491,10 @@ class CapturedTrainStep:
         return {"classification_loss": losses["classification_loss"].detach(), "regression_loss": losses["regression_loss"].detach(),
                 "loss": total.detach()}
 
+    def _augments(self) -> Dict[str, object]:
+        "The augmentations installed in the net's transform, by slot name, in ``AUGMENT_SLOTS`` order (a net without a transform: none)."
+        return dict(augments_of(getattr(self.net, "transform", None)))
+
     def _capacity_of(self, targets) -> Optional[int]:
         "The batch's capacity class, or None (mode off, or a count above the last class: exact-shape keying)."
         return None if self.gt_capacity is None else gt_capacity_class(_gt_counts(targets), self.gt_capacity)
@@ -512,7 +508,7 @@ class CapturedTrainStep:
         if self.image_capacity is None or (self._capacity_of(targets) if cap is _UNSET else cap) is None:
             return None
         tr = self.net.transform
-        if not _stageable(tr, images) or (getattr(tr, "scale_jitter", None) is None and tr.staged_short_side() is None):
+        if not _stageable(tr, images) or ("scale_jitter" not in self._augments() and tr.staged_short_side() is None):
             return None
         in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
         bounds = tr.staged_bounds(in_hw)
@@ -542,48 +538,23 @@ class CapturedTrainStep:
             tgs = ("gt_cap", cap)          # (the entry's packed buffers are B x cap rows; B is in the image shapes)
         else:
             tgs = tuple(tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in t.items() if isinstance(v, Tensor))) for t in targets)
-        # the train-time flip (transform.hflip): the draw is part of the step and reads p / seed / counter from the object's device
-        # block, so only WHICH object is installed matters (the key holds it: its block outlives every graph that reads it)
-        hflip = getattr(getattr(self.net, "transform", None), "hflip", None)
-        # global-norm clipping (optim.GradClip on a master optimizer): the norm kernels are part of the step and read max_norm from the
-        # object's device block, so -- as for the flip -- the key holds the object, not its value; installing or removing a clip re-captures
-        clip = getattr(self.optimizer, "grad_clip", None)
+        # Everything below is keyed by the installed OBJECT, never by its settings: the transform's augmentations, the global-norm clip
+        # (optim.GradClip), the accumulator (optim.GradAccumulator) and the weight average (optim.WeightEMA) all do their work inside
+        # the step and read what they need -- p, seed, counter, ranges, max_norm, the window position, the decay -- from the object's
+        # device block.  A new setting therefore replays the same graph, installing, removing or swapping an object re-captures, and
+        # the key keeps the object (and with it the block) alive as long as a graph reads it.  The flip has its place in the base key,
+        # None when there is none; the accumulator, the average and the other slots (in ``AUGMENT_SLOTS`` order, tagged with their
+        # names) follow only when installed, so without them the key is the base key.
+        aug = self._augments()
         mode = tuple(m.training for m in self.net.modules())
         frozen = tuple(p.requires_grad for p in self.net.parameters())       # (freezing / unfreezing layers changes the launch sequence)
-        key = (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype, hflip, clip)
-        # gradient accumulation (optim.GradAccumulator): the object, as for the clip -- its window position, 1 / n and found_inf are
-        # read from its device block.  Without one the key is exactly the one above.
+        key = (ims, tgs, groups, hash(mode), hash(frozen), self.amp_dtype, aug.pop("hflip", None), getattr(self.optimizer, "grad_clip", None))
         if self.accumulate is not None:
-            key = key + (self.accumulate,)
-        # the weight average (optim.WeightEMA on a master optimizer): its update is part of the optimizer step and reads its factor and
-        # count from the object's device block -- the object again; installing or removing one re-captures.  Without one nothing is added.
+            key += (self.accumulate,)
         ema = getattr(self.optimizer, "weight_ema", None)
         if ema is not None:
-            key = key + (("weight_ema", ema),)
-        # the short side drawn on the device (transform.scale_jitter): the draw is part of the step and reads seed / counter / sizes from
-        # the object's device block, and the canvas follows from the image shapes -- the object again.  Without one nothing is added.
-        jitter = getattr(getattr(self.net, "transform", None), "scale_jitter", None)
-        if jitter is not None:
-            key = key + (("scale_jitter", jitter),)
-        # the colour jitter (transform.color_jitter): drawn inside the step from the object's device block and applied by the transform
-        # kernel -- the object once more: new ranges or a new p replay the same graph.  Without one nothing is added.
-        color = getattr(getattr(self.net, "transform", None), "color_jitter", None)
-        if color is not None:
-            key = key + (("color_jitter", color),)
-        # the bbox-safe random crop (transform.crop): the rectangles are drawn inside the step from the object's device block and the
-        # staged GT, and the canvas class follows from the image shapes (``crop.bound``) -- the object again.  Without one nothing is added.
-        crop = getattr(getattr(self.net, "transform", None), "crop", None)
-        if crop is not None:
-            key = key + (("crop", crop),)
-        # shift / scale / rotate (transform.shift_scale_rotate): matrices, surviving rows and warped images all come from the object's
-        # device block inside the step -- the object again.  Without one nothing is added.
-        ssr = getattr(getattr(self.net, "transform", None), "shift_scale_rotate", None)
-        if ssr is not None:
-            key = key + (("shift_scale_rotate", ssr),)
-        # brightness / contrast (transform.brightness_contrast): its coefficients are drawn inside the step from the object's device block
-        # into the colour rows -- the object again: new limits or a new p replay the same graph.  Without one nothing is added.
-        bc = getattr(getattr(self.net, "transform", None), "brightness_contrast", None)
-        return key if bc is None else key + (("brightness_contrast", bc),)
+            key += (("weight_ema", ema),)
+        return key + tuple(aug.items())
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."
@@ -688,14 +659,15 @@ class CapturedTrainStep:
         final = bool(final)
         if not self.enabled or not images or not images[0].is_cuda:
             return self._step(images, targets, final)
-        ssr = getattr(getattr(self.net, "transform", None), "shift_scale_rotate", None)
+        aug = self._augments()
+        ssr = aug.get("shift_scale_rotate")
         if ssr is not None and (self.image_capacity is None or self.gt_capacity is None):
             raise ValueError("a shift / scale / rotate (net.transform.shift_scale_rotate) warps every image and drops boxes from step to "
                              "step: CapturedTrainStep needs gt_capacity= and image_capacity= for it -- the staged path draws and applies "
                              "it on the device; without them call the net directly (it is then drawn on the host)")
         cap = self._capacity_of(targets)
         icls = self._image_class_of(images, targets, cap)          # (once per step: the key, the arena and the transform's bounds)
-        if getattr(getattr(self.net, "transform", None), "crop", None) is not None:
+        if "crop" in aug:
             if self.image_capacity is None:
                 raise ValueError("a bbox-safe random crop (net.transform.crop) changes every image's size from step to step: "
                                  "CapturedTrainStep needs image_capacity= (and gt_capacity=) for it -- the staged path draws the crop on "

@@ -21,7 +21,9 @@ import torch
 from torch import nn
 from torch.utils.data import DataLoader, Dataset
 
+from .graph import gt_capacity_classes, image_capacity_classes
 from .models import Retinanet
+from .optim import check_accumulate_grad_batches
 from .utils import AttrDict, collate_fn, load_obj
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -77,8 +79,7 @@ class RetinaNetModel(_Base):
 
     def device_brightness_contrast_enabled(self) -> bool:
         "This model's ``device_brightness_contrast`` (``SimpleTrainer`` sets it) or ``trainer.device_brightness_contrast`` of its hparams."
-        section = self.conf.get("trainer") if hasattr(self.conf, "get") else None
-        return bool(self.device_brightness_contrast or (section or {}).get("device_brightness_contrast") or False)
+        return bool(self.device_brightness_contrast or _hparam(self.conf, "device_brightness_contrast"))
 
     def forward(self, xb, *args, **kwargs):
         # reference model.py:33-35 calls self.net(xb) with no targets (a TypeError there, Q19);
@@ -95,22 +96,18 @@ class RetinaNetModel(_Base):
             self.val_ds = SyntheticDetectionDataset(**{**kw, "seed": kw.get("seed", 0) + 1})
             self.test_ds = SyntheticDetectionDataset(**{**kw, "seed": kw.get("seed", 0) + 2})
         elif d.kind == "csv":             # README.md:103-125: trn_paths / val_paths (optional) / test_paths are csv files
-            from .augment import bbox_crop_from_transforms, color_jitter_from_transforms, from_transforms, shift_scale_rotate_from_transforms
+            from functools import partial
+            from .augment import SLOT_MAPPERS, from_transforms
             from .datasets import CSVDetectionDataset
-            # the training set's transforms (reference model.py:51-52, hparams.yaml:55-58): the horizontal flip runs on the GPU,
-            # inside the model's transform (augment.RandomHorizontalFlip); validation / test never flip (eval mode, no targets)
-            # (RandomBrightnessContrast is opt-in: with the switch its entry is mapped below, without it the flip's mapping warns about it)
+            # the training set's transforms (reference model.py:51-52, hparams.yaml:55-58) run on the GPU, inside the model's transform:
+            # each mapper turns the entries it owns into the object of its slot (the flip, albumentations' or torchvision's ColorJitter,
+            # BBoxSafeRandomCrop, ShiftScaleRotate: augment.py); validation / test never augment (eval mode, no targets)
+            # (RandomBrightnessContrast is opt-in: with the switch its entry is mapped too, without it the flip's mapping warns about it)
             bc_on = self.device_brightness_contrast_enabled()
-            self.net.transform.hflip = from_transforms(self.conf.get("transforms"), brightness_contrast=bc_on)
-            if bc_on:
-                from .augment import brightness_contrast_from_transforms
-                self.net.transform.brightness_contrast = brightness_contrast_from_transforms(self.conf.get("transforms"))
-            # ColorJitter entries (albumentations' or torchvision's) become the GPU colour jitter of the model's transform as well
-            self.net.transform.color_jitter = color_jitter_from_transforms(self.conf.get("transforms"))
-            # an albumentations.BBoxSafeRandomCrop entry becomes the transform's bbox-safe random crop (augment.BBoxSafeRandomCrop)
-            self.net.transform.crop = bbox_crop_from_transforms(self.conf.get("transforms"))
-            # an albumentations.ShiftScaleRotate entry becomes the transform's shift / scale / rotate (augment.ShiftScaleRotate)
-            self.net.transform.shift_scale_rotate = shift_scale_rotate_from_transforms(self.conf.get("transforms"))
+            mappers = (("hflip", partial(from_transforms, brightness_contrast=bc_on)),) + tuple((slot, mapper) for slot, _, mapper in SLOT_MAPPERS)
+            for slot, mapper in mappers:
+                if slot != "brightness_contrast" or bc_on:
+                    setattr(self.net.transform, slot, mapper(self.conf.get("transforms")))
             # dataset.image_dtype (optional; "float32" or "uint8"): "uint8" hands the decoder's bytes to the model, which converts them
             # on the device (ops.image_stage_u8 on the staged path, ops.images_u8_to_f32 in the transform)
             dt = d.get("image_dtype") or "float32"
@@ -239,6 +236,52 @@ def _to_device(batch, device):
     return images, targets, ids
 
 
+def _hparam(conf, name: str):
+    "``trainer.<name>`` of the hparams, or None: no hparams, no ``trainer`` section, no such key."
+    section = conf.get("trainer") if hasattr(conf, "get") else None
+    return (section or {}).get(name)
+
+
+def _number(allowed, rule: str):
+    "A parser of ``TRAINER_OPTIONS`` for a float option: ``allowed(v)`` or a ValueError ``<label> must be <rule>, got ...``."
+    def parse(value, label: str) -> float:
+        v = float(value or 0.0)
+        if not allowed(v):
+            raise ValueError(f"{label} must be {rule}, got {value}")
+        return v
+    return parse
+
+
+def _switch(value, label: str) -> bool:
+    return bool(value)
+
+
+def _canvases(value, label: str):
+    """None, "auto" or a list of padded canvases (Hp, Wp), checked by ``graph.image_capacity_classes`` (bad values fail here, not at
+    the first step; divisibility by the net's ``size_divisible`` is checked once the net is known).  YAML's [Hp, Wp] lists, whose
+    numbers may come as whole floats, become tuples of ints first."""
+    if isinstance(value, (list, tuple)):
+        value = [tuple(int(v) if isinstance(v, float) and v == int(v) else v for v in c) if isinstance(c, list) else c for c in value]
+    image_capacity_classes(value)
+    return value
+
+
+# The options of ``SimpleTrainer`` that the hparams' optional ``trainer`` section may also set: name -> (the off value, the parser).
+# ``parse(value, label)`` returns the value as the trainer keeps it or raises ValueError; ``label`` is the name for a constructor
+# argument and ``trainer.<name>`` for an hparams entry.  The constructor's value wins unless it is the off value (``_resolve``).
+TRAINER_OPTIONS = {
+    "gradient_clip_val": (0.0, _number(lambda v: v >= 0.0, ">= 0 (0 = off)")),
+    "accumulate_grad_batches": (1, check_accumulate_grad_batches),
+    "weight_ema_decay": (0.0, _number(lambda v: 0.0 <= v < 1.0, "in [0, 1) (0 = off)")),
+    "weight_ema_warmup": (0.0, _number(lambda v: 0.0 <= v < float("inf"), "a finite number >= 0 (0 = no warm-up)")),
+    "device_scale_jitter": (False, _switch),
+    "image_capacity": (None, _canvases),
+    "predict_image_capacity": (None, _canvases),
+    "device_eval": (False, _switch),
+    "device_brightness_contrast": (False, _switch),
+}
+
+
 class SimpleTrainer:
     """Minimal stand-in for ``pl.Trainer`` driving the hooks above on ONE device per process:
     ``fit`` (train + optional validation, scheduler stepping per the hparams contract) and ``test``.
@@ -319,33 +362,19 @@ class SimpleTrainer:
         hparams' ``transforms`` is mapped onto ``augment.RandomBrightnessContrast`` (albumentations' defaults) and installed as
         ``net.transform.brightness_contrast`` (``self.brightness_contrast``; under ``torch.distributed`` rank r draws from seed + r): drawn
         and applied on the device inside the captured step.  Without the switch the entry is skipped with one warning, as it always was."""
-        from .graph import gt_capacity_classes, image_capacity_classes
-        from .optim import check_accumulate_grad_batches
-        self.accumulate_grad_batches = check_accumulate_grad_batches(accumulate_grad_batches)
+        given = locals()                                  # (the arguments by name: every option of the table is one)
+        for name, (_, parse) in TRAINER_OPTIONS.items():
+            setattr(self, name, parse(given[name], name))
         self.grad_accumulator = None                      # the optim.GradAccumulator of the last fit() (master optimizers on CUDA)
-        self.gradient_clip_val = float(gradient_clip_val or 0.0)
-        if not self.gradient_clip_val >= 0.0:
-            raise ValueError(f"gradient_clip_val must be >= 0 (0 = off), got {gradient_clip_val}")
         self.grad_clip = None                             # the optim.GradClip of the last fit() (master optimizers)
-        self.weight_ema_decay, self.weight_ema_warmup = float(weight_ema_decay or 0.0), float(weight_ema_warmup or 0.0)
-        if not 0.0 <= self.weight_ema_decay < 1.0:
-            raise ValueError(f"weight_ema_decay must be in [0, 1) (0 = off), got {weight_ema_decay}")
-        if not 0.0 <= self.weight_ema_warmup < float("inf"):
-            raise ValueError(f"weight_ema_warmup must be a finite number >= 0 (0 = no warm-up), got {weight_ema_warmup}")
         self.weight_ema = None                            # the optim.WeightEMA of the last fit() (master optimizers on CUDA)
-        self.device_scale_jitter, self.scale_jitter_seed = bool(device_scale_jitter), int(scale_jitter_seed)
+        self.scale_jitter_seed = int(scale_jitter_seed)
         self.scale_jitter = None                          # the augment.RandomShortSide of the last fit()
         gt_capacity_classes(gt_capacity)                  # (bad values fail here, not at the first step)
         self.gt_capacity = gt_capacity
-        image_capacity_classes(image_capacity)            # (the same: divisibility by the net's size_divisible is checked in fit())
         if image_capacity is not None and gt_capacity is None:
             raise ValueError("image_capacity needs gt_capacity as well (\"auto\" or a class list)")
-        self.image_capacity = image_capacity
-        image_capacity_classes(predict_image_capacity)    # (the same)
-        self.predict_image_capacity = predict_image_capacity
         self.predictor = None                             # the graph.CapturedPredict of the last test()
-        self.device_eval = bool(device_eval)
-        self.device_brightness_contrast = bool(device_brightness_contrast)
         self.brightness_contrast = None                   # the augment.RandomBrightnessContrast of the last fit()
         self.max_epochs, self.max_steps, self.log_every, self.capture = max_epochs, max_steps, log_every, capture
         self.captured_steps = 0
@@ -355,87 +384,45 @@ class SimpleTrainer:
         self.channels_last = channels_last
         self.log = logging.getLogger("lightning")
 
+    def _resolve(self, name: str, conf):
+        """The constructor's value of the option ``name`` or, when that is the off value, ``trainer.<name>`` of the hparams, parsed
+        and checked like the constructor's (``TRAINER_OPTIONS``); absent: the off value."""
+        off, parse = TRAINER_OPTIONS[name]
+        mine = getattr(self, name)
+        if mine != off:
+            return mine
+        value = _hparam(conf, name)
+        return off if value is None else parse(value, f"trainer.{name}")
+
+    # (the public face of ``_resolve``: one method per option, each "the constructor's value or ``trainer.<option>`` of the hparams")
     def resolve_gradient_clip_val(self, conf) -> float:
-        "The constructor's ``gradient_clip_val`` or, when that is 0, ``trainer.gradient_clip_val`` of the hparams (absent: 0 = off)."
-        if self.gradient_clip_val > 0:
-            return self.gradient_clip_val
-        section = conf.get("trainer") if hasattr(conf, "get") else None
-        value = float((section or {}).get("gradient_clip_val") or 0.0)
-        if not value >= 0.0:
-            raise ValueError(f"trainer.gradient_clip_val must be >= 0 (0 = off), got {value}")
-        return value
+        return self._resolve("gradient_clip_val", conf)
 
     def resolve_accumulate_grad_batches(self, conf) -> int:
-        "The constructor's ``accumulate_grad_batches`` or, when that is 1, ``trainer.accumulate_grad_batches`` of the hparams (absent: 1)."
-        from .optim import check_accumulate_grad_batches
-        if self.accumulate_grad_batches > 1:
-            return self.accumulate_grad_batches
-        section = conf.get("trainer") if hasattr(conf, "get") else None
-        value = (section or {}).get("accumulate_grad_batches")
-        return 1 if value is None else check_accumulate_grad_batches(value, "trainer.accumulate_grad_batches")
+        return self._resolve("accumulate_grad_batches", conf)
 
     def resolve_weight_ema_decay(self, conf) -> float:
-        "The constructor's ``weight_ema_decay`` or, when that is 0, ``trainer.weight_ema_decay`` of the hparams (absent: 0 = off)."
-        if self.weight_ema_decay > 0:
-            return self.weight_ema_decay
-        section = conf.get("trainer") if hasattr(conf, "get") else None
-        value = float((section or {}).get("weight_ema_decay") or 0.0)
-        if not 0.0 <= value < 1.0:
-            raise ValueError(f"trainer.weight_ema_decay must be in [0, 1) (0 = off), got {value}")
-        return value
+        return self._resolve("weight_ema_decay", conf)
 
     def resolve_weight_ema_warmup(self, conf) -> float:
-        "The constructor's ``weight_ema_warmup`` or, when that is 0, ``trainer.weight_ema_warmup`` of the hparams (absent: 0 = no warm-up)."
-        if self.weight_ema_warmup > 0:
-            return self.weight_ema_warmup
-        section = conf.get("trainer") if hasattr(conf, "get") else None
-        value = float((section or {}).get("weight_ema_warmup") or 0.0)
-        if not 0.0 <= value < float("inf"):
-            raise ValueError(f"trainer.weight_ema_warmup must be a finite number >= 0 (0 = no warm-up), got {value}")
-        return value
+        return self._resolve("weight_ema_warmup", conf)
 
     def resolve_device_scale_jitter(self, conf) -> bool:
-        "The constructor's ``device_scale_jitter`` or, when that is False, ``trainer.device_scale_jitter`` of the hparams (absent: off)."
-        if self.device_scale_jitter:
-            return True
-        section = conf.get("trainer") if hasattr(conf, "get") else None
-        return bool((section or {}).get("device_scale_jitter") or False)
+        return self._resolve("device_scale_jitter", conf)
 
     def resolve_image_capacity(self, conf):
-        "The constructor's ``image_capacity`` or, when that is None, ``trainer.image_capacity`` of the hparams (absent: off)."
-        if self.image_capacity is not None:
-            return self.image_capacity
-        section = conf.get("trainer") if hasattr(conf, "get") else None
-        value = (section or {}).get("image_capacity")
-        if value is None or isinstance(value, str):
-            return value
-        return [tuple(int(v) if int(v) == v else v for v in c) for c in value]      # (a YAML list of [Hp, Wp] lists)
+        return self._resolve("image_capacity", conf)
 
     def resolve_predict_image_capacity(self, conf):
-        "The constructor's ``predict_image_capacity`` or, when that is None, ``trainer.predict_image_capacity`` of the hparams (absent: off)."
-        if self.predict_image_capacity is not None:
-            return self.predict_image_capacity
-        section = conf.get("trainer") if hasattr(conf, "get") else None
-        value = (section or {}).get("predict_image_capacity")
-        if value is None or isinstance(value, str):
-            return value
-        return [tuple(int(v) if int(v) == v else v for v in c) for c in value]      # (a YAML list of [Hp, Wp] lists)
+        return self._resolve("predict_image_capacity", conf)
 
     def resolve_device_eval(self, conf) -> bool:
-        "The constructor's ``device_eval`` or, when that is False, ``trainer.device_eval`` of the hparams (absent: off)."
-        if self.device_eval:
-            return True
-        section = conf.get("trainer") if hasattr(conf, "get") else None
-        return bool((section or {}).get("device_eval") or False)
+        return self._resolve("device_eval", conf)
 
     def resolve_device_brightness_contrast(self, conf) -> bool:
-        "The constructor's ``device_brightness_contrast`` or, when that is False, ``trainer.device_brightness_contrast`` of the hparams (absent: off)."
-        if self.device_brightness_contrast:
-            return True
-        section = conf.get("trainer") if hasattr(conf, "get") else None
-        return bool((section or {}).get("device_brightness_contrast") or False)
+        return self._resolve("device_brightness_contrast", conf)
 
-    def _install_brightness_contrast(self, model, rank: Optional[int]) -> None:
+    def _install_brightness_contrast(self, model) -> None:
         """``fit``'s part of ``device_brightness_contrast``: the object ``prepare_data`` mapped from the hparams' ``transforms`` -- or,
         for a csv model that was prepared before the switch was known, the mapping made here."""
         transform = model.net.transform
@@ -444,10 +431,8 @@ class SimpleTrainer:
             from .augment import brightness_contrast_from_transforms
             transform.brightness_contrast = brightness_contrast_from_transforms(model.conf.get("transforms"))
         self.brightness_contrast = getattr(transform, "brightness_contrast", None)
-        if self.brightness_contrast is not None and rank is not None:
-            self.brightness_contrast.set_rank(rank)       # seed = base seed + rank: each rank draws its own coefficients
 
-    def _install_scale_jitter(self, model, rank: Optional[int]) -> None:
+    def _install_scale_jitter(self, model) -> None:
         "``fit``'s part of ``device_scale_jitter``: a ``RandomShortSide`` over the transform's ``min_size`` tuple, or one log line."
         transform = model.net.transform
         self.scale_jitter = getattr(transform, "scale_jitter", None)
@@ -458,8 +443,6 @@ class SimpleTrainer:
                 self.scale_jitter = transform.scale_jitter = RandomShortSide(sizes, seed=self.scale_jitter_seed)
             else:
                 self.log.info("device_scale_jitter: min_size %s has a single entry, there is nothing to draw: no RandomShortSide installed", sizes)
-        if self.scale_jitter is not None and rank is not None:
-            self.scale_jitter.set_rank(rank)              # seed = base seed + rank: each rank draws its own scales
 
     def _ema_weights(self, model):
         """The context validation and testing run in: ``model``'s weights exchanged with the average that the last fit() kept, else
@@ -490,20 +473,11 @@ class SimpleTrainer:
             raise ValueError(f"accumulate_grad_batches={n_acc} under torch.distributed is not supported: gradient accumulation is "
                              "single-process only (skipping the exchange on micro steps is not implemented)")
         ddp = BucketedGradAllReduce(model.net) if dist.is_available() and dist.is_initialized() else None
-        hflip = getattr(model.net.transform, "hflip", None)
-        if hflip is not None and ddp is not None:
-            hflip.set_rank(dist.get_rank())               # seed = base seed + rank: each rank flips its own choice of images
-        color = getattr(model.net.transform, "color_jitter", None)
-        if color is not None and ddp is not None:
-            color.set_rank(dist.get_rank())               # seed = base seed + rank: each rank draws its own factors and orders
-        crop = getattr(model.net.transform, "crop", None)
-        if crop is not None and ddp is not None:
-            crop.set_rank(dist.get_rank())                # seed = base seed + rank: each rank draws its own windows
-        ssr = getattr(model.net.transform, "shift_scale_rotate", None)
-        if ssr is not None and ddp is not None:
-            ssr.set_rank(dist.get_rank())                 # seed = base seed + rank: each rank draws its own matrices
-        self._install_scale_jitter(model, dist.get_rank() if ddp is not None else None)
-        self._install_brightness_contrast(model, dist.get_rank() if ddp is not None else None)
+        self._install_scale_jitter(model)
+        self._install_brightness_contrast(model)
+        if ddp is not None:
+            # every installed augmentation draws from seed = its base seed + rank: each rank makes its own flips, scales, factors, windows ...
+            model.net.transform.set_rank(dist.get_rank())
         # precision "16" = fp16 autocast WITH dynamic loss scaling, like the reference's native-AMP run (Lightning precision=16):
         # fp16 gradients of a focal loss normalised by num_fg underflow without it
         # (under a gradient exchange: parallel.ExchangeGradScaler -- found_inf from the exchanged buckets, one decision for all ranks)

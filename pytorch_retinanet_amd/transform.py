@@ -92,6 +92,25 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 
+# The train-time augmentation slots of ``GeneralizedRCNNTransform`` (module docstring): plain attributes, None by default, each acting
+# in training mode when targets are given.  The order is the one ``graph.CapturedTrainStep`` lists them in its key.  Adding one:
+# DESIGN.md, "Adding an augmentation".
+AUGMENT_SLOTS = (
+    "hflip",                  # augment.RandomHorizontalFlip: the train-time flip
+    "scale_jitter",           # augment.RandomShortSide: the short side drawn on the device
+    "color_jitter",           # augment.ColorJitter: the colour jitter drawn and applied on the device
+    "crop",                   # augment.BBoxSafeRandomCrop: the bbox-safe random crop, before everything else
+    "shift_scale_rotate",     # augment.ShiftScaleRotate: shift / scale / rotate, after the crop
+    "brightness_contrast",    # augment.RandomBrightnessContrast: alpha x + beta ref behind the colour jitter
+)
+
+
+def augments_of(transform) -> List[Tuple[str, object]]:
+    """The augmentations installed in ``transform``'s slots, as (name, object) pairs in ``AUGMENT_SLOTS`` order.  THE way to read a
+    slot: a transform unpickled from before a slot existed has no such attribute, and neither has a foreign transform or None."""
+    return [(name, obj) for name in AUGMENT_SLOTS for obj in (getattr(transform, name, None),) if obj is not None]
+
+
 class ImageList(object):
     """A padded batch plus each image's (h, w) before padding."""
 
@@ -156,6 +175,51 @@ def _flip_where(flag: Tensor, image: Tensor, target: Optional[Dict[str, Tensor]]
     return image, target
 
 
+def _boxes_into(targets: List[Dict[str, Tensor]], rows: Tensor) -> None:
+    "One buffer with every image's boxes (what a flip + resize launch over the whole batch writes) into the target dicts: each gets its rows as a view."
+    counts = [int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets]
+    for t, r in zip(targets, rows.split(counts)):
+        t["boxes"] = r
+
+
+def _gt_rows(targets, with_labels: bool):
+    """GT as per-image rows, for the augmentations drawn on the host -> (boxes, labels, put).  ``boxes[b]`` [n_b, 4] and ``labels[b]``
+    [n_b] are the target dicts' own tensors, or each image's range of ONE host copy of packed GT (``ops.PackedGT``: a synchronisation
+    on CUDA); ``labels`` is None unless ``with_labels``, and a dict without labels gives None.  ``put(boxes, labels=None)`` -> the
+    targets holding these rows instead: the dicts themselves, or a new PackedGT on the old one's device with buffers of the old size.
+    Without ``labels`` no row was dropped: the labels and the offsets stay as they are."""
+    if not _is_packed(targets):
+        boxes = [t["boxes"].reshape(-1, 4) for t in targets]
+        labels = [t["labels"].reshape(-1) if "labels" in t else None for t in targets] if with_labels else None
+
+        def put(new_boxes, new_labels=None):
+            for b, (t, bx) in enumerate(zip(targets, new_boxes)):
+                t["boxes"] = bx.to(boxes[b].device)
+                if new_labels is not None and new_labels[b] is not None:
+                    t["labels"] = new_labels[b]
+            return targets
+        return boxes, labels, put
+    off = [int(v) for v in targets.gt_off.tolist()]
+    ranges = list(zip(off[:-1], off[1:]))
+    rows = targets.gt_boxes.detach().cpu()
+    row_labels = targets.gt_labels.detach().cpu() if with_labels else None
+
+    def put(new_boxes, new_labels=None):
+        dev = targets.gt_boxes.device
+        out_b = rows.clone()
+        if new_labels is None:
+            for (lo, hi), bx in zip(ranges, new_boxes):
+                out_b[lo:hi] = bx
+            return targets.with_boxes(out_b.to(dev))
+        out_l, new_off = row_labels.clone(), [0]
+        for bx, lb in zip(new_boxes, new_labels):         # the rows that are left, packed from row 0
+            at, n = new_off[-1], int(bx.shape[0])
+            out_b[at:at + n], out_l[at:at + n] = bx, lb
+            new_off.append(at + n)
+        return targets.with_rows(out_b.to(dev), out_l.to(dev), torch.tensor(new_off, dtype=torch.int32).to(dev))
+    return [rows[lo:hi] for lo, hi in ranges], None if row_labels is None else [row_labels[lo:hi] for lo, hi in ranges], put
+
+
 class GeneralizedRCNNTransform(nn.Module):
     def __init__(self, min_size, max_size: int, image_mean: Sequence[float], image_std: Sequence[float],
                  size_divisible: int = 32):
@@ -166,12 +230,26 @@ class GeneralizedRCNNTransform(nn.Module):
         self.image_std = list(image_std)
         self.size_divisible = size_divisible
         self._stats = {}
-        self.hflip = None             # augment.RandomHorizontalFlip: the train-time flip (module docstring)
-        self.scale_jitter = None      # augment.RandomShortSide: the short side drawn on the device (module docstring)
-        self.color_jitter = None      # augment.ColorJitter: the colour jitter drawn and applied on the device (module docstring)
-        self.brightness_contrast = None   # augment.RandomBrightnessContrast: alpha x + beta ref behind the colour jitter (module docstring)
-        self.crop = None              # augment.BBoxSafeRandomCrop: the bbox-safe random crop, before everything else (module docstring)
-        self.shift_scale_rotate = None    # augment.ShiftScaleRotate: shift / scale / rotate, after the crop (module docstring)
+        for name in AUGMENT_SLOTS:
+            setattr(self, name, None)
+
+    # -- the augmentation slots ----------------------------------------------------------
+    def augments(self) -> List[Tuple[str, object]]:
+        "The installed augmentations as (name, object) pairs in ``AUGMENT_SLOTS`` order (``augments_of``)."
+        return augments_of(self)
+
+    def _acting(self, targets) -> bool:
+        "Whether the augmentations act on this call: in training mode and when targets are given."
+        return self.training and targets is not None
+
+    def _slot(self, name: str, targets):
+        "The object installed in slot ``name`` when it acts on this call, else None."
+        return getattr(self, name, None) if self._acting(targets) else None
+
+    def set_rank(self, rank: int) -> None:
+        "One stream of draws per data-parallel rank: every installed object's seed = its base seed + rank, its counter kept."
+        for _, obj in self.augments():
+            obj.set_rank(rank)
 
     # -- pieces ------------------------------------------------------------------------
     def normalize(self, image: Tensor) -> Tensor:
@@ -232,22 +310,19 @@ class GeneralizedRCNNTransform(nn.Module):
 
     def _flips(self, images: List[Tensor], targets) -> Optional[Tensor]:
         "This batch's flip decisions (uint8 [B], on the images' device; the flip's counter advances), or None when nothing flips."
-        if self.hflip is None or not self.training or targets is None:
-            return None
-        return self.hflip.next_flags(len(images), images[0].device)
+        hflip = self._slot("hflip", targets)
+        return None if hflip is None else hflip.next_flags(len(images), images[0].device)
 
     def _jitter(self, targets):
         "The installed ``scale_jitter`` when it acts on this call (training mode, targets given), else None."
-        return self.scale_jitter if self.scale_jitter is not None and self.training and targets is not None else None
+        return self._slot("scale_jitter", targets)
 
     def _color(self, images, targets) -> Optional[Tensor]:
         """This batch's ``rn_color_coef`` rows (f32 [B, 8] on the images' device; the counters of the objects that act advance), or
         None when neither ``color_jitter`` nor ``brightness_contrast`` acts on this call.  The jitter draws first (its contrast mean
         included); brightness / contrast writes its two coefficients into the same rows, or into fresh identity rows.  ``images``:
         fusable CUDA images or ``ops.StagedImages``."""
-        if not self.training or targets is None:
-            return None
-        cj, bc = getattr(self, "color_jitter", None), getattr(self, "brightness_contrast", None)
+        cj, bc = self._slot("color_jitter", targets), self._slot("brightness_contrast", targets)
         coef = cj.next_coef(images) if cj is not None else None
         return bc.next_coef(images, coef) if bc is not None else coef
 
@@ -261,10 +336,7 @@ class GeneralizedRCNNTransform(nn.Module):
         if _is_packed(targets):
             targets = ops.gt_flip_scale_packed_dev(targets, widths, ratios, flags)
         else:
-            counts = [int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets]
-            rows = ops.gt_flip_scale_many_dev([t["boxes"] for t in targets], widths, ratios, flags).split(counts)
-            for t, r in zip(targets, rows):
-                t["boxes"] = r
+            _boxes_into(targets, ops.gt_flip_scale_many_dev([t["boxes"] for t in targets], widths, ratios, flags))
         hp, wp = self._canvas(bounds)
         batch = ops.transform_batch_dev(images, out_hw, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags,
                                         coef=coef)
@@ -293,10 +365,7 @@ class GeneralizedRCNNTransform(nn.Module):
             targets = _resize_packed(targets, ratios) if flags is None else ops.gt_flip_scale_packed(targets, widths, ratios, flags)
         elif flags is not None:
             # every image's flip + resize in one launch into one buffer; each target gets its rows as a view
-            counts = [int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets]
-            rows = ops.gt_flip_scale_many([t["boxes"] for t in targets], widths, ratios, flags).split(counts)
-            for t, r in zip(targets, rows):
-                t["boxes"] = r
+            _boxes_into(targets, ops.gt_flip_scale_many([t["boxes"] for t in targets], widths, ratios, flags))
         hp, wp = self._canvas(sizes)
         batch = ops.transform_batch(images, sizes, self.image_mean, self.image_std, hp, wp, out_dtype, channels_last, flags=flags, coef=coef)
         return ImageList(batch, sizes), targets
@@ -312,12 +381,12 @@ class GeneralizedRCNNTransform(nn.Module):
     def staged_bounds(self, in_hw: Sequence[Tuple[int, int]]) -> List[Tuple[int, int]]:
         """Host arithmetic on the raw sizes alone: per image the size after the resize -- with a ``scale_jitter`` installed the upper
         bound of every size it can draw (``jitter.bound``).  The natural canvas of a staged batch is ``_canvas`` over these."""
-        jitter = self.scale_jitter
+        installed = dict(self.augments())
+        jitter, crop = installed.get("scale_jitter"), installed.get("crop")
         short = None if jitter is not None else self.staged_short_side()      # (the value the device plan gets: bound and plan cannot drift apart)
         if jitter is None and short is None:
             raise ValueError(f"staged images need one integer min_size and an integer max_size (got {self.min_size}, {self.max_size}), "
                              "or an augment.RandomShortSide as scale_jitter")
-        crop = getattr(self, "crop", None)
         if crop is not None:
             # the window is drawn on the device: the bound is that of every window of the image's orientation (``crop.bound``)
             most = max((jitter.canvas_short,) + tuple(jitter.sizes)) if jitter is not None else short
@@ -387,17 +456,19 @@ class GeneralizedRCNNTransform(nn.Module):
         if targets.B != staged.B or len(staged.hw) != staged.B:
             raise ValueError(f"packed GT of {targets.B} images for {len(staged.hw)} staged images in an arena of {staged.B}")
         (hp, wp), bounds = self._check_staged_canvas(canvas, staged, self.staged_bounds)
-        crop = getattr(self, "crop", None)
+        # (training mode, packed GT: every installed augmentation acts here)
+        crop = self._slot("crop", targets)
         if crop is not None:
             # a second staging pass: from here on ``staged`` is the arena of the windows and its sizes are the cropped ones
             staged, targets = ops.bbox_crop_staged(crop, staged, targets)
-        ssr = getattr(self, "shift_scale_rotate", None)
+        ssr = self._slot("shift_scale_rotate", targets)
         if ssr is not None:
             # one more staging pass: the warped images at the same sizes, and the packed GT of the rows that survive
             staged, targets = ops.shift_scale_rotate_staged(ssr, staged, targets)
-        flags = self.hflip.next_flags(staged.B, staged.device) if self.hflip is not None else None
+        hflip = self._slot("hflip", targets)
+        flags = hflip.next_flags(staged.B, staged.device) if hflip is not None else None
         coef = self._color(staged, targets)
-        jitter = self.scale_jitter
+        jitter = self._jitter(targets)
         if jitter is not None:
             out_hw, ratios = jitter.next_sizes_dev(staged.in_hw, self.max_size)
         else:
@@ -409,66 +480,30 @@ class GeneralizedRCNNTransform(nn.Module):
                                         coef=coef)
         return ImageList(batch, bounds), targets
 
-    def _crop_on_host(self, images: List[Tensor], targets):
-        """The installed ``crop`` for images that are not staged: the rectangles from the Python restatement (``crop.next_rects`` reads
+    def _crop_on_host(self, crop, images: List[Tensor], targets):
+        """``crop`` for images that are not staged: the rectangles from the Python restatement (``crop.next_rects`` reads
         the boxes and the counter on the host: one synchronisation on CUDA), the images sliced (views) and the boxes shifted with
         torch -- one fp32 subtraction each, as the kernel does -- for target dicts and packed GT alike."""
         in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
-        packed = _is_packed(targets)
-        if packed:
-            off = [int(v) for v in targets.gt_off.tolist()]
-            rows = targets.gt_boxes.detach().cpu()
-            boxes = [rows[lo:hi] for lo, hi in zip(off[:-1], off[1:])]
-        else:
-            boxes = [t["boxes"].reshape(-1, 4) for t in targets]
-        rects = self.crop.next_rects(in_hw, boxes)
+        boxes, _, put = _gt_rows(targets, with_labels=False)
+        rects = crop.next_rects(in_hw, boxes)
         images = [im[:, y0:y0 + ch, x0:x0 + cw] for im, (y0, x0, ch, cw) in zip(images, rects)]
         shifted = []
-        for b, (bx, (y0, x0, _, _)) in enumerate(zip(boxes, rects)):
+        for bx, (y0, x0, _, _) in zip(boxes, rects):
             moved = (y0, x0) != (0, 0) and bx.shape[0] > 0
             shifted.append(bx - bx.new_tensor([x0, y0, x0, y0], dtype=torch.float32) if moved else bx)
-        if packed:
-            out = rows.clone()
-            for lo, hi, bx in zip(off[:-1], off[1:], shifted):
-                out[lo:hi] = bx
-            return images, targets.with_boxes(out.to(targets.gt_boxes.device))
-        for t, bx in zip(targets, shifted):
-            t["boxes"] = bx
-        return images, targets
+        return images, put(shifted)
 
-    def _shift_scale_rotate_on_host(self, images: List[Tensor], targets):
-        """The installed ``shift_scale_rotate`` for images that are not staged: the coefficients from the Python restatement
+    def _shift_scale_rotate_on_host(self, ssr, images: List[Tensor], targets):
+        """``ssr`` for images that are not staged: the coefficients from the Python restatement
         (``next_coefs`` reads the boxes and the counter on the host: one synchronisation on CUDA), the images warped with torch ops
         (``warp_image``) and the rows moved, clipped and dropped by ``warp_boxes`` -- for target dicts and packed GT alike."""
-        ssr = self.shift_scale_rotate
         in_hw = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
-        packed = _is_packed(targets)
-        if packed:
-            off = [int(v) for v in targets.gt_off.tolist()]
-            rows, row_labels = targets.gt_boxes.detach().cpu(), targets.gt_labels.detach().cpu()
-            boxes = [rows[lo:hi] for lo, hi in zip(off[:-1], off[1:])]
-            labels = [row_labels[lo:hi] for lo, hi in zip(off[:-1], off[1:])]
-        else:
-            boxes = [t["boxes"].reshape(-1, 4) for t in targets]
-            labels = [t["labels"].reshape(-1) if "labels" in t else None for t in targets]
+        boxes, labels, put = _gt_rows(targets, with_labels=True)
         coefs = ssr.next_coefs(in_hw, boxes)
         images = [ssr.warp_image(im, coefs.inv[b], coefs.applied[b]) for b, im in enumerate(images)]
         moved = ssr.warp_boxes(coefs, in_hw, boxes, labels, ssr.min_visibility)
-        if packed:
-            out_b, out_l, at = rows.clone(), row_labels.clone(), 0
-            new_off = [0]
-            for bx, lb in moved:
-                n = int(bx.shape[0])
-                out_b[at:at + n], out_l[at:at + n] = bx, lb
-                at += n
-                new_off.append(at)
-            dev = targets.gt_boxes.device
-            return images, targets.with_rows(out_b.to(dev), out_l.to(dev), torch.tensor(new_off, dtype=torch.int32).to(dev))
-        for t, bx0, (bx, lb) in zip(targets, boxes, moved):
-            t["boxes"] = bx.to(bx0.device)
-            if lb is not None:
-                t["labels"] = lb
-        return images, targets
+        return images, put([bx for bx, _ in moved], [lb for _, lb in moved])
 
     @staticmethod
     def _u8_to_f32(images: List[Tensor]) -> List[Tensor]:
@@ -505,20 +540,20 @@ class GeneralizedRCNNTransform(nn.Module):
             if im.dim() != 3:
                 raise ValueError(f"images is expected to be a list of 3d tensors of shape [C, H, W], got {tuple(im.shape)}")
         images = self._u8_to_f32(images)
-        if getattr(self, "crop", None) is not None and self.training and targets is not None:
-            images, targets = self._crop_on_host(images, targets)
-        if getattr(self, "shift_scale_rotate", None) is not None and self.training and targets is not None:
-            images, targets = self._shift_scale_rotate_on_host(images, targets)
+        crop, ssr = self._slot("crop", targets), self._slot("shift_scale_rotate", targets)
+        if crop is not None:
+            images, targets = self._crop_on_host(crop, images, targets)
+        if ssr is not None:
+            images, targets = self._shift_scale_rotate_on_host(ssr, images, targets)
         if self._fusable(images):
             return self._forward_fused(images, targets, out_dtype or torch.float32, channels_last)
         flags = self._flips(images, targets)
-        cj = getattr(self, "color_jitter", None)
-        if cj is not None and self.training and targets is not None:
+        cj, bc = self._slot("color_jitter", targets), self._slot("brightness_contrast", targets)
+        if cj is not None:
             # the same draw from the Python restatement, applied with torch ops (augment.apply_color_ops) to the raw image
             from .augment import apply_color_ops
             images = [apply_color_ops(im, fac, order) for im, (fac, order) in zip(images, cj.next_draw(len(images)))]
-        bc = getattr(self, "brightness_contrast", None)
-        if bc is not None and self.training and targets is not None:
+        if bc is not None:
             # likewise (augment.apply_brightness_contrast), behind the jitter's operations: the by-mean reference sees their result
             from .augment import apply_brightness_contrast
             ref = 1.0 if bc.brightness_by_max else None

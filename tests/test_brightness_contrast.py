@@ -288,7 +288,8 @@ def test_prepare_data_installs_it_only_with_the_switch(tmp_path, caplog):
         # a model prepared before the switch was known: fit()'s own part installs the mapping
         model = _model("csv", path, DEMO)
         assert model.net.transform.brightness_contrast is None
-        trainer._install_brightness_contrast(model, 2)
+        trainer._install_brightness_contrast(model)
+        model.net.transform.set_rank(2)                                            # (what fit() does as rank 2 of a process group)
         assert trainer.brightness_contrast is model.net.transform.brightness_contrast and trainer.brightness_contrast.seed == 2
     import os
     assert "device_brightness_contrast" in open(os.path.join(os.path.dirname(P.__file__), "hparams.yaml")).read()

@@ -279,16 +279,17 @@ def test_trainer_resolves_the_argument_and_the_hparams_key(caplog):
     model.conf = {}
     model.net = torch.nn.Module()
     model.net.transform = GeneralizedRCNNTransform(SIZES, MAX_SIZE, MEAN, STD)
-    t._install_scale_jitter(model, None)                                  # off: nothing is installed
+    t._install_scale_jitter(model)                                        # off: nothing is installed
     assert model.net.transform.scale_jitter is None and t.scale_jitter is None
     on = P.SimpleTrainer(device="cpu", device_scale_jitter=True, scale_jitter_seed=5)
-    on._install_scale_jitter(model, 3)                                    # (rank 3 of a process group)
+    on._install_scale_jitter(model)
+    model.net.transform.set_rank(3)                                       # (what fit() does as rank 3 of a process group)
     sj = model.net.transform.scale_jitter
     assert isinstance(sj, RandomShortSide) and on.scale_jitter is sj and sj.sizes == SIZES and sj.base_seed == 5 and sj.seed == 8
     model.conf = {"trainer": {"device_scale_jitter": True}}
     model.net.transform = GeneralizedRCNNTransform(48, MAX_SIZE, MEAN, STD)
     with caplog.at_level(logging.INFO, logger="lightning"):
-        t._install_scale_jitter(model, None)                              # a single-entry min_size: one log line, nothing installed
+        t._install_scale_jitter(model)                                    # a single-entry min_size: one log line, nothing installed
     assert model.net.transform.scale_jitter is None and t.scale_jitter is None
     assert sum("single entry" in r.getMessage() for r in caplog.records) == 1
 
