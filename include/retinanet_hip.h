@@ -757,6 +757,32 @@ int rn_sgd_master_step(float *const *masters, float *const *momenta, const void 
                        float weight_decay, int nesterov, int first_step, const float *grad_scale, const float *found_inf,
                        const float *clip_coef, void *stream);
 
+/* ---- the same step with its hyperparameters and step count in a device block, capturable ----------------------
+ * hparams: a DEVICE block of RN_SGD_HPARAMS 32-bit words per parameter group (16-byte aligned), zero when created:
+ *   word 0  f32 lr            word 1  f32 momentum      word 2  f32 dampening     word 3  f32 weight_decay
+ *   word 4  i32 nesterov (0 | 1)
+ *   word 5  i32 steps: the steps this group has taken, skipped ones not counted (saturates at 2^31 - 1)
+ *   word 6  i32 first (0 | 1): whether the step being taken is the group's first, written by each call's prologue
+ *   word 7  reserved
+ * Words 0 .. 4 are the values rn_sgd_master_step takes by value, as the same f32 / int bits; rn_sgd_hparams_set (one single-wave
+ * launch, the host's only way in) writes them, and word 5 too when step >= 0.  Nothing of the update is passed by value, so a
+ * captured step follows whatever the host last wrote into the block.
+ * rn_sgd_master_step_dev enqueues, per call: one single-wave prologue that -- unless found_inf[0] != 0 -- sets first = (steps == 0)
+ * and then steps += 1, and one launch per 48 tensors of the update above with every scalar and first_step read from the block:
+ * the branches (weight_decay != 0, momentum != 0, first, nesterov) and the order of operations of rn_sgd_master_step, so equal
+ * hyperparameters give equal bits.  When found_inf[0] != 0 nothing changes: no parameter, buffer, counter or `first`.
+ * has_momentum (by value: it decides which pointers exist) != 0: every momenta[i] is a buffer, read unless first and written in
+ * every step; with momentum == 0 in the block it takes buf = g (g after weight decay).  has_momentum == 0: momenta's entries may
+ * be null, no buffer is touched, and momentum in the block must be 0 (a non-zero value would have no buffer to use: the caller's
+ * contract; optim.MasterSGD refuses it).  Every other argument as for rn_sgd_master_step; every tensor is checked before the
+ * first launch.  Plain stores only, no atomics; no host synchronisation. */
+#define RN_SGD_HPARAMS 8
+int rn_sgd_hparams_set(void *hparams, float lr, float momentum, float dampening, float weight_decay, int nesterov, int64_t step,
+                       void *stream);
+int rn_sgd_master_step_dev(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
+                           const int64_t *numels, int n_tensors, int grads16, int dtype16, int has_momentum, void *hparams,
+                           const float *grad_scale, const float *found_inf, const float *clip_coef, void *stream);
+
 /* ---- optimizer step: Adam / AdamW on fp32 masters with a 16-bit working copy, capturable --------------------
  * hparams: a DEVICE block of RN_ADAM_HPARAMS doubles per parameter group (8-byte aligned) holding lr, beta1, beta2, eps,
  * weight_decay (written by rn_adam_hparams_set, the host's only way in), the step counter and two per-step scalars.  Nothing

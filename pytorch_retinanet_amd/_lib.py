@@ -117,6 +117,8 @@ SIGNATURES = {
     "rn_maxpool3x3s2_backward_bn": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "rn_sgd_master_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _f32, _f32, _f32, C.c_int, C.c_int, _vp, _vp,
                                      _vp, _vp]),
+    "rn_sgd_hparams_set": (C.c_int, [_vp, _f32, _f32, _f32, _f32, C.c_int, _i64, _vp]),
+    "rn_sgd_master_step_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "rn_adam_hparams_set": (C.c_int, [_vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     "rn_adam_master_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "rn_grad_clip_set": (C.c_int, [_vp, _f32, _vp]),

@@ -8,6 +8,10 @@
 //   g = float(grad) + weight_decay * w;  buf = first ? g : momentum * buf + (1 - dampening) * g;
 //   g = nesterov ? g + momentum * buf : buf;  w -= lr * g;  w16 = bf16(w)
 // The same kernel updates plain fp32 parameters (BN, biases): no 16-bit copy, fp32 gradient.
+// rn_sgd_master_step takes lr .. first by value; rn_sgd_master_step_dev (optim.MasterSGD(capturable=True)) is the same kernel template
+// reading them from a per-group device block, behind a single-wave prologue that keeps the step count and `first` on the device.
+#include <type_traits>
+
 #include "rn_multi.hpp"
 
 namespace {
@@ -31,7 +35,37 @@ struct SgdTable {
     const float *clip_coef;
 };
 
-__device__ __forceinline__ float sgd_one(const SgdTable &t, const float gin, float &wi, float &mi)
+// The device-block form of the launch (rn_sgd_master_step_dev): t's own lr .. first are unused, every scalar of the update and
+// `first` come from the group's RN_SGD_HPARAMS block (include/retinanet_hip.h), which the call's prologue has just advanced.
+struct SgdDevTable : SgdTable {
+    const uint32_t *hp;
+    int has_momentum;                       // the tensors have momentum buffers: read unless this is the first step, written in every step
+};
+
+enum { SHP_LR = 0, SHP_MOMENTUM, SHP_DAMPENING, SHP_WD, SHP_NESTEROV, SHP_STEPS, SHP_FIRST };      // the block's 32-bit words
+static_assert(SHP_FIRST < RN_SGD_HPARAMS, "the block holds every word");
+
+// What sgd_one reads.  By value: the table itself (kernel arguments, as before the two forms shared a kernel).  Device block: six
+// loads at one address for the whole grid, from memory the kernel never writes and before its first store -- scalar loads, once per
+// wave, outside the element loop.
+struct SgdHp {
+    float lr, momentum, dampening, weight_decay;
+    int nesterov, first;
+};
+
+__device__ __forceinline__ SgdHp sgd_block_scalars(const uint32_t *__restrict__ hp)
+{
+    SgdHp h;
+    h.lr = __uint_as_float(hp[SHP_LR]); h.momentum = __uint_as_float(hp[SHP_MOMENTUM]);
+    h.dampening = __uint_as_float(hp[SHP_DAMPENING]); h.weight_decay = __uint_as_float(hp[SHP_WD]);
+    h.nesterov = (int)hp[SHP_NESTEROV]; h.first = (int)hp[SHP_FIRST];
+    return h;
+}
+
+// KEEP_BUF (device block only; a group with momentum buffers whose momentum is 0 right now): the buffer takes g, so that a later
+// non-zero momentum finds the last gradient there
+template <bool KEEP_BUF, class Hp>
+__device__ __forceinline__ float sgd_one(const Hp &t, const float gin, float &wi, float &mi)
 {
     float g = gin;
     if (t.weight_decay != 0.0f) g = g + t.weight_decay * wi;
@@ -39,16 +73,22 @@ __device__ __forceinline__ float sgd_one(const SgdTable &t, const float gin, flo
         const float b = t.first ? g : t.momentum * mi + (1.0f - t.dampening) * g;
         mi = b;
         g = t.nesterov ? g + t.momentum * b : b;
+    } else if (KEEP_BUF) {
+        mi = g;
     }
     wi = wi - t.lr * g;
     return wi;
 }
 
-template <bool F16>
-__global__ __launch_bounds__(256) void sgd_master_kernel(const SgdTable t)
+// Table: SgdTable (rn_sgd_master_step) | SgdDevTable (rn_sgd_master_step_dev)
+template <bool F16, class Table>
+__global__ __launch_bounds__(256) void sgd_master_kernel(const Table t)
 {
     constexpr int DT = F16 ? RN_F16 : RN_BF16;
+    constexpr bool DEV = std::is_same<Table, SgdDevTable>::value;
     if (t.found_inf && *t.found_inf != 0.0f) return;             // (GradScaler: a non-finite gradient somewhere -> no parameter moves)
+    [[maybe_unused]] SgdHp hv;                                   // (device block only)
+    if constexpr (DEV) hv = sgd_block_scalars(t.hp);
     const float inv_scale = t.grad_scale ? 1.0f / *t.grad_scale : 1.0f;
     const float coef = t.clip_coef ? *t.clip_coef : 1.0f;
     const int ti = blockIdx.y;
@@ -56,21 +96,25 @@ __global__ __launch_bounds__(256) void sgd_master_kernel(const SgdTable t)
     float *__restrict__ m = t.mom[ti];
     uint16_t *__restrict__ p16 = (uint16_t *)t.p16[ti];
     const bool g16 = p16 && t.grad16;
-    const bool has_m = t.momentum != 0.0f;
+    // whether the tensors have momentum buffers: by value, exactly when momentum != 0; device block: the caller's structural flag
+    bool has_m;
+    if constexpr (DEV) has_m = t.has_momentum != 0;
+    else has_m = t.momentum != 0.0f;
     const int64_t n = t.n[ti], n4 = n >> 2;
     // 4 elements per thread and iteration: 16-byte accesses on the fp32 arrays, 8-byte on the bf16 ones (every array starts
     // 16- / 8-byte aligned: checked on the host); the < 4 leftover elements go through the scalar tail below
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n4; v += (int64_t)gridDim.x * 256) {
         rn::f32x4 wv = ((const rn::f32x4 *)w)[v];
         rn::f32x4 mv = {0.f, 0.f, 0.f, 0.f};
-        if (has_m && !t.first) mv = ((const rn::f32x4 *)m)[v];
+        if (has_m && !(DEV ? hv.first : t.first)) mv = ((const rn::f32x4 *)m)[v];
         const rn::f32x4 gv = rn::load_grad4<DT>(t, ti, v, g16);
         const float g[4] = {gv.x, gv.y, gv.z, gv.w};
         float ww[4] = {wv.x, wv.y, wv.z, wv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float gj = rn::unscale_clip(g[j], t.grad_scale, inv_scale, t.clip_coef, coef);
-            sgd_one(t, gj, ww[j], mm[j]);
+            if constexpr (DEV) sgd_one<true>(hv, gj, ww[j], mm[j]);
+            else sgd_one<false>(t, gj, ww[j], mm[j]);
         }
         wv.x = ww[0]; wv.y = ww[1]; wv.z = ww[2]; wv.w = ww[3];
         mv.x = mm[0]; mv.y = mm[1]; mv.z = mm[2]; mv.w = mm[3];
@@ -81,12 +125,43 @@ __global__ __launch_bounds__(256) void sgd_master_kernel(const SgdTable t)
     if (blockIdx.x == 0) {                                       // < 4 leftover elements
         const int64_t i = n4 * 4 + threadIdx.x;
         if (threadIdx.x < 4 && i < n) {
-            float wi = w[i], mi = (has_m && !t.first) ? m[i] : 0.0f;
-            sgd_one(t, rn::unscale_clip(rn::load_grad1<DT>(t, ti, i, g16), t.grad_scale, inv_scale, t.clip_coef, coef), wi, mi);
+            float wi = w[i], mi = (has_m && !(DEV ? hv.first : t.first)) ? m[i] : 0.0f;
+            const float gi = rn::unscale_clip(rn::load_grad1<DT>(t, ti, i, g16), t.grad_scale, inv_scale, t.clip_coef, coef);
+            if constexpr (DEV) sgd_one<true>(hv, gi, wi, mi);
+            else sgd_one<false>(t, gi, wi, mi);
             w[i] = wi;
             if (has_m) m[i] = mi;
             if (p16) p16[i] = rn::mma<DT>::dn(wi);
         }
+    }
+}
+
+// one wave per call: this call's `first`, then the counter -- unless the step is skipped
+__global__ __launch_bounds__(64) void sgd_prologue_kernel(uint32_t *__restrict__ hp, const float *__restrict__ found_inf)
+{
+    if (threadIdx.x != 0) return;
+    if (found_inf && *found_inf != 0.0f) return;                 // a skipped step advances nothing: a skipped first step stays first
+    const uint32_t steps = hp[SHP_STEPS];
+    hp[SHP_FIRST] = steps == 0u ? 1u : 0u;
+    hp[SHP_STEPS] = steps < 0x7fffffffu ? steps + 1u : steps;
+}
+
+__global__ __launch_bounds__(64) void sgd_hparams_set_kernel(uint32_t *__restrict__ hp, const float lr, const float momentum, const float dampening,
+                                                             const float weight_decay, const int nesterov, const int64_t step)
+{
+    if (threadIdx.x != 0) return;
+    hp[SHP_LR] = __float_as_uint(lr); hp[SHP_MOMENTUM] = __float_as_uint(momentum); hp[SHP_DAMPENING] = __float_as_uint(dampening);
+    hp[SHP_WD] = __float_as_uint(weight_decay); hp[SHP_NESTEROV] = nesterov ? 1u : 0u;
+    if (step >= 0) hp[SHP_STEPS] = step < 0x7fffffff ? (uint32_t)step : 0x7fffffffu;
+}
+
+// the kernel-argument table of one launch: tensors base .. base + cnt - 1 of the call
+inline void sgd_fill_table(SgdTable &t, float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
+                           const int64_t *numels, const int base, const int cnt)
+{
+    for (int i = 0; i < cnt; ++i) {
+        t.master[i] = masters[base + i]; t.mom[i] = momenta[base + i]; t.grad[i] = grads[base + i];
+        t.p16[i] = params16[base + i]; t.n[i] = numels[base + i];
     }
 }
 
@@ -106,17 +181,54 @@ RN_API int rn_sgd_master_step(float *const *masters, float *const *momenta, cons
     for (int base = 0; base < n_tensors; base += SGD_MAX_TENSORS) {
         SgdTable t;
         const int cnt = (n_tensors - base) < SGD_MAX_TENSORS ? (n_tensors - base) : SGD_MAX_TENSORS;
-        for (int i = 0; i < cnt; ++i) {
-            t.master[i] = masters[base + i]; t.mom[i] = momenta[base + i]; t.grad[i] = grads[base + i];
-            t.p16[i] = params16[base + i]; t.n[i] = numels[base + i];
-        }
+        sgd_fill_table(t, masters, momenta, grads, params16, numels, base, cnt);
         t.lr = lr; t.momentum = momentum; t.dampening = dampening; t.weight_decay = weight_decay;
         t.nesterov = nesterov; t.first = first_step; t.grad16 = grads16;
         t.f16 = dtype16 == RN_F16; t.grad_scale = grad_scale; t.found_inf = found_inf;
         t.clip_coef = clip_coef;
         const dim3 grid = rn::step_grid(t.n, cnt);
-        if (t.f16) hipLaunchKernelGGL(sgd_master_kernel<true>, grid, dim3(256), 0, st, t);
-        else hipLaunchKernelGGL(sgd_master_kernel<false>, grid, dim3(256), 0, st, t);
+        if (t.f16) hipLaunchKernelGGL((sgd_master_kernel<true, SgdTable>), grid, dim3(256), 0, st, t);
+        else hipLaunchKernelGGL((sgd_master_kernel<false, SgdTable>), grid, dim3(256), 0, st, t);
+        RN_LAUNCH_CHECK();
+    }
+    return RN_OK;
+}
+
+RN_API int rn_sgd_hparams_set(void *hparams, float lr, float momentum, float dampening, float weight_decay, int nesterov, int64_t step,
+                              void *stream)
+{
+    if (!hparams) return RN_EINVAL;
+    if (!rn::aligned(hparams, 16)) return RN_EALIGN;
+    hipLaunchKernelGGL(sgd_hparams_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t *)hparams, lr, momentum, dampening,
+                       weight_decay, nesterov, step);
+    RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
+RN_API int rn_sgd_master_step_dev(float *const *masters, float *const *momenta, const void *const *grads, void *const *params16,
+                                  const int64_t *numels, int n_tensors, int grads16, int dtype16, int has_momentum, void *hparams,
+                                  const float *grad_scale, const float *found_inf, const float *clip_coef, void *stream)
+{
+    if (dtype16 != RN_BF16 && dtype16 != RN_F16) return RN_EUNSUPPORTED;
+    if (!masters || !momenta || !grads || !params16 || !numels || !hparams || n_tensors < 0) return RN_EINVAL;
+    if (!rn::aligned(hparams, 16)) return RN_EALIGN;
+    const int rc = rn::check_step_tensors<1>(masters, {momenta}, has_momentum != 0, grads, params16, numels, n_tensors, grads16, 16);
+    if (rc != RN_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sgd_prologue_kernel, dim3(1), dim3(64), 0, st, (uint32_t *)hparams, found_inf);
+    RN_LAUNCH_CHECK();
+    for (int base = 0; base < n_tensors; base += SGD_MAX_TENSORS) {
+        SgdDevTable t;
+        const int cnt = (n_tensors - base) < SGD_MAX_TENSORS ? (n_tensors - base) : SGD_MAX_TENSORS;
+        sgd_fill_table(t, masters, momenta, grads, params16, numels, base, cnt);
+        t.hp = (const uint32_t *)hparams; t.has_momentum = has_momentum;
+        t.lr = t.momentum = t.dampening = t.weight_decay = 0.0f;              // (unused: the kernel reads the block)
+        t.nesterov = t.first = 0; t.grad16 = grads16;
+        t.f16 = dtype16 == RN_F16; t.grad_scale = grad_scale; t.found_inf = found_inf;
+        t.clip_coef = clip_coef;
+        const dim3 grid = rn::step_grid(t.n, cnt);
+        if (t.f16) hipLaunchKernelGGL((sgd_master_kernel<true, SgdDevTable>), grid, dim3(256), 0, st, t);
+        else hipLaunchKernelGGL((sgd_master_kernel<false, SgdDevTable>), grid, dim3(256), 0, st, t);
         RN_LAUNCH_CHECK();
     }
     return RN_OK;

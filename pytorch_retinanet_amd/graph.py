@@ -28,8 +28,8 @@ Rules the capture relies on (all true of this package; checked by ``tests/test_g
   * every pointer the kernels receive is a static input buffer, a parameter / optimizer state, or memory allocated from
     the graph's private pool during capture (same address at every replay);
   * scalars passed by value (learning rate, momentum, weight decay) are part of the signature: a change re-captures.
-    Optimizers with device-resident hyperparameters (``optim.MasterAdam`` / ``MasterAdamW``: ``_rn_device_hparams``) are the
-    exception: their kernels read lr / betas / eps / weight_decay from device blocks, which ``sync_device_hparams()`` refreshes
+    Optimizers with device-resident hyperparameters (``optim.MasterAdam`` / ``MasterAdamW`` and ``MasterSGD(capturable=True)``:
+    ``_rn_device_hparams``) are the exception: their kernels read lr and the rest from device blocks, which ``sync_device_hparams()`` refreshes
     before every replay, so those values are left out of the signature and a per-step LR schedule replays one graph.
     The augmentations of the net's transform (``transform.AUGMENT_SLOTS``: ``net.transform.hflip``, ``scale_jitter``, ``color_jitter``,
     ``crop``, ``shift_scale_rotate``, ``brightness_contrast``), gradient clipping (``optimizer.grad_clip``, ``optim.GradClip``) and a
@@ -518,7 +518,7 @@ class CapturedTrainStep:
     def _signature(self, images, targets, cap=_UNSET, icls=_UNSET) -> tuple:
         "``cap`` / ``icls``: the batch's GT class and image class when the caller has computed them (``__call__``); else computed here."
         if getattr(self.optimizer, "_rn_device_hparams", False):
-            # (optim.MasterAdam / MasterAdamW: the kernels read lr / betas / eps / weight_decay from device blocks that
+            # (optim.MasterAdam / MasterAdamW / MasterSGD(capturable=True): the kernels read their hyperparameters from device blocks that
             # sync_device_hparams() refreshes before every replay -- a per-step LR schedule keeps one graph)
             groups = ("device_hparams", len(self.optimizer.param_groups))
         else:
@@ -740,7 +740,7 @@ class CapturedTrainStep:
                                        (C.c_int64 * n)(*[t.numel() * t.element_size() for t in dsts]), n,
                                        torch.cuda.current_stream(dsts[0].device).cuda_stream), "rn_copy_many")
         if getattr(self.optimizer, "_rn_device_hparams", False):
-            self.optimizer.sync_device_hparams()              # the groups' current lr / betas / eps / weight_decay, read by the graph
+            self.optimizer.sync_device_hparams()              # the groups' current hyperparameters (lr, ...), read by the graph
         if e.segments is not None:
             self._replay_segments(e)
         else:

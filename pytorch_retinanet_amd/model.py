@@ -300,9 +300,10 @@ class SimpleTrainer:
         """``capture``: replay each step as one hipGraph (``graph.CapturedTrainStep`` -- what ``bench.py``'s headline number is
         measured through: ~0.4 ms of host time per step instead of ~20 ms of Python enqueueing ~640 kernels) whenever the step
         is the plain one: one GPU, ``training_step`` not overridden, and no scheduler that changes the learning rate every step
-        unless the optimizer reads its hyperparameters on the device (``optim.MasterAdam`` / ``MasterAdamW``: the step reads lr
-        from a device block refreshed before each replay).  ``MasterSGD`` and torch's optimizers take lr by value, which is part of
-        a graph's signature: each new value would re-capture, so a per-step schedule runs them eagerly.  Batches of a new shape run
+        unless the optimizer reads its hyperparameters on the device (``optim.MasterAdam`` / ``MasterAdamW``, and ``MasterSGD`` with
+        ``optimizer.params.capturable: true``: the step reads lr from a device block refreshed before each replay).  ``MasterSGD``
+        without that flag and torch's optimizers take lr by value, which is part of a graph's signature: each new value would
+        re-capture, so a per-step schedule runs them eagerly.  Batches of a new shape run
         eagerly twice, then replay; the results are the eager step's (``tests/test_graph_gpu.py``).  ``gt_capacity``: passed to the
         ``CapturedTrainStep`` -- "auto" keys batches by GT capacity class instead of by their exact box counts, so data with a
         different number of boxes per image still replays (None: exact keying).

@@ -13,6 +13,7 @@ give and take fp32 checkpoints with the reference's keys.
 
 ``MasterAdam`` / ``MasterAdamW`` do the same for ``torch.optim.Adam`` / ``AdamW`` (``rn_adam_master_step``, ``csrc/adam.hip``), with every
 hyperparameter and the step counter in a device block per parameter group: a captured step follows a per-step LR schedule.
+``MasterSGD(capturable=True)`` does the same for SGD (``rn_sgd_master_step_dev``): the bits of the by-value step, read from a block.
 
 ``GradClip`` -- ``torch.nn.utils.clip_grad_norm_`` for the three of them (``rn_grad_norm_clip``, ``csrc/clip.hip``): one read of every
 gradient gives the global L2 norm and the clip coefficient in a device block, and the step kernels multiply the coefficient into each
@@ -822,17 +823,57 @@ class _MasterOptimizer(torch.optim.Optimizer):
         raise NotImplementedError
 
 
+RN_SGD_HPARAMS = 8                      # 32-bit words per group in MasterSGD's device block (include/retinanet_hip.h)
+_SHP_STEPS = 5                          # the step counter's word in it
+
+
 class MasterSGD(_MasterOptimizer):
+    """``torch.optim.SGD`` on fp32 masters with 16-bit conv working copies, one HIP launch per 48 tensors and parameter group.
+
+    By default lr, momentum, dampening, weight_decay, nesterov and "this is the first step" go to ``rn_sgd_master_step`` by value: they
+    are part of a captured graph's key, and the host counts the steps.
+
+    ``capturable=True``: the same update through ``rn_sgd_master_step_dev`` -- bit for bit at equal hyperparameters -- with those values
+    and the step count in a device block per group that the kernels read, so a step captured in a graph follows whatever the host
+    wrote last.  ``sync_device_hparams()`` writes each group's current values there (``step()`` calls it when the stream is not
+    capturing; ``graph.CapturedTrainStep`` calls it before every replay): a per-step LR schedule keeps replaying one graph.  The step
+    count advances on the device, and not at all in a step that ``torch.amp.GradScaler`` skips (found_inf), so a skipped first step
+    stays first and ``dampening != 0`` works under loss scaling.  What decides which memory exists is fixed once a group's block
+    exists -- whether it has momentum buffers (``momentum != 0`` at that time) and ``nesterov``; changing either raises a
+    ``ValueError``.  lr, dampening, weight_decay and momentum (any value for a group with buffers; with ``momentum == 0`` the buffer
+    keeps the last gradient) are rewritable between replays.  The blocks and buffers are created by the first step -- not inside a
+    capture -- and kept for good.
+
+    ``state_dict()`` / ``load_state_dict()`` use torch's SGD format (``momentum_buffer`` per parameter) plus ``steps``, the number of
+    steps taken: checkpoints move between both modes of this class and ``torch.optim.SGD`` in every direction (torch's state with a
+    ``momentum_buffer`` present loads as "not the first step"; weights: ``master_state_dict`` / ``load_master_state_dict``).  In
+    capturable mode ``state_dict()`` and ``group_steps()`` read the count back from the device (they synchronise)."""
     _handles = "CUDA fp32 parameters and bf16 parameters converted by use_bf16_conv_weights"
 
     def __init__(self, params: Iterable, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False, max_grad_norm: Optional[float] = None):
+                 weight_decay: float = 0.0, nesterov: bool = False, max_grad_norm: Optional[float] = None, *, capturable: bool = False):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if not isinstance(capturable, (bool, np.bool_)):
+            raise TypeError(f"capturable must be a bool, got {capturable!r}")
+        self._capturable = bool(capturable)
+        if self._capturable:
+            self._check_values(lr, momentum, dampening, weight_decay)
+            self._rn_device_hparams = True               # lr .. nesterov are read on the device: no part of a captured graph's key
+            self._blocks: Dict[int, Tensor] = {}         # group index -> its device block (RN_SGD_HPARAMS 32-bit words)
+            self._written: Dict[int, tuple] = {}         # group index -> the values last written into it
+            self._structure: Dict[int, tuple] = {}       # group index -> (has momentum buffers, nesterov), fixed with the block
         _install_clip(self, max_grad_norm)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov))
 
+    @property
+    def capturable(self) -> bool:
+        return self._capturable
+
+    # -- by value (the default) ----------------------------------------------------------------------------------
     def _state(self, rec: dict, p: Tensor, w: Optional[Tensor]) -> None:
+        if self._capturable:
+            return self._state_dev(rec, p, w)
         if w is None:
             return
         group, st = rec["group"], self.state[p]
@@ -852,12 +893,172 @@ class MasterSGD(_MasterOptimizer):
         rec.setdefault("moms", []).append(st["momentum_buffer"].data_ptr() if st["momentum_buffer"] is not None else 0)
 
     def _launch(self, rec: dict, scale: Optional[int], found: Optional[int], coef: Optional[int]) -> None:
+        if self._capturable:
+            return self._launch_dev(rec, scale, found, coef)
         group, n = rec["group"], len(rec["ns"])
         check(lib.rn_sgd_master_step(_ptrs(rec["masters"]), _ptrs(rec["moms"]), _ptrs(rec["gptrs"]), _ptrs(rec["p16s"]), (C.c_int64 * n)(*rec["ns"]), n,
                                      int(bool(rec["grads16"])), _dt16(rec["dt16"]), float(group["lr"]), float(group["momentum"]),
                                      float(group["dampening"]), float(group["weight_decay"]), int(group["nesterov"]), int(bool(rec["first"])),
                                      scale, found, coef, torch.cuda.current_stream().cuda_stream), "rn_sgd_master_step")
 
+    # -- capturable: the device blocks ---------------------------------------------------------------------------
+    @staticmethod
+    def _check_values(lr, momentum, dampening, weight_decay) -> None:
+        if isinstance(lr, Tensor):
+            raise ValueError("MasterSGD(capturable=True): lr is a float (the device block holds it), not a Tensor")
+        for name, v, lo in (("lr", lr, 0.0), ("momentum", momentum, 0.0), ("dampening", dampening, None), ("weight_decay", weight_decay, 0.0)):
+            v = float(v)
+            if not abs(v) <= float(np.finfo(np.float32).max) or (lo is not None and v < lo):      # (NaN fails the first test)
+                raise ValueError(f"Invalid {name} value: {v} (a finite fp32 number" + (f" >= {lo})" if lo is not None else ")"))
+
+    def _hparams(self, i: int, group) -> tuple:
+        "The values of group ``i`` as the block takes them, checked: (lr, momentum, dampening, weight_decay, nesterov)."
+        self._check_values(group["lr"], group["momentum"], group["dampening"], group["weight_decay"])
+        vals = (float(group["lr"]), float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]), int(bool(group["nesterov"])))
+        if vals[4] and (vals[1] <= 0 or vals[2] != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        fixed = self._structure.get(i)
+        if fixed is not None:
+            has_m, nesterov = fixed
+            if bool(vals[4]) != nesterov:
+                raise ValueError(f"MasterSGD(capturable=True): nesterov of parameter group {i} is fixed at {nesterov} once its device block "
+                                 "exists; construct a new optimizer to change it")
+            if not has_m and vals[1] != 0.0:
+                raise ValueError(f"MasterSGD(capturable=True): momentum of parameter group {i} cannot become non-zero: the group started "
+                                 "with momentum == 0 and has no momentum buffers; construct the optimizer with a non-zero momentum")
+        return vals
+
+    def _block(self, i: int, group, dev: torch.device) -> Tensor:
+        blk = _device_block(self._blocks.get(i), RN_SGD_HPARAMS // 2, dev,
+                            "MasterSGD: take one step (or call sync_device_hparams()) before capturing a step: "
+                            "the device blocks and momentum buffers cannot be created inside a capture",
+                            f"MasterSGD: the state of parameter group {i} lives on {{have}}, not {{want}}; a group stays on one device")
+        if i not in self._blocks:
+            self._blocks[i] = blk
+            self._written.pop(i, None)
+            self._structure[i] = (float(group["momentum"]) != 0.0, bool(group["nesterov"]))
+        return blk
+
+    def _write_block(self, i: int, group, step: int = -1) -> None:
+        dev = group["params"][0].device
+        vals = self._hparams(i, group)
+        blk = self._block(i, group, dev)
+        with torch.cuda.device(dev):
+            check(lib.rn_sgd_hparams_set(blk.data_ptr(), *vals, int(step), torch.cuda.current_stream(dev).cuda_stream), "rn_sgd_hparams_set")
+        self._written[i] = vals
+
+    def sync_device_hparams(self) -> None:
+        """Capturable mode: write each group's current lr / momentum / dampening / weight_decay / nesterov into its device block on the
+        current stream: one small launch per group whose values changed since the last write, none otherwise.  Never synchronises;
+        does nothing while the current stream is capturing (a write recorded into a graph would replay the values of capture time)
+        and nothing in the default mode (no value lives on the device)."""
+        if not self._capturable or _is_capturing():
+            return
+        for i, group in enumerate(self.param_groups):
+            if not group["params"] or not group["params"][0].is_cuda:
+                continue
+            if i not in self._blocks or self._written.get(i) != self._hparams(i, group):
+                self._write_block(i, group)
+
+    def _before_collect(self) -> None:
+        self.sync_device_hparams()                   # (does nothing by value, or while the stream is capturing)
+
+    def _state_dev(self, rec: dict, p: Tensor, w: Optional[Tensor]) -> None:
+        has_state = "momentum_buffer" in self.state.get(p, {})
+        if w is None:
+            if has_state:
+                raise RuntimeError("MasterSGD(capturable=True): a parameter with optimizer state has no gradient in this step: the step "
+                                   "counter is one per group, so every parameter of a group must step together")
+            return
+        st = self.state[p]
+        if not has_state:
+            if _is_capturing():
+                raise RuntimeError("MasterSGD: take one step before capturing one: the momentum buffers cannot be created inside a capture")
+            fixed = self._structure.get(rec["gi"])
+            has_m = fixed[0] if fixed is not None else float(rec["group"]["momentum"]) != 0.0
+            # same memory order as the master (empty_like keeps the strides); a fill kernel, not a memset (graph.py).  The first step
+            # does not read it; zeros rather than garbage for a checkpoint taken after a skipped first step
+            st["momentum_buffer"] = torch.empty_like(w).fill_(0) if has_m else None
+        if rec.setdefault("had_state", has_state) != has_state:
+            raise RuntimeError("MasterSGD(capturable=True): a parameter joined a group that has already stepped: the step counter is one per group")
+        rec.setdefault("moms", []).append(st["momentum_buffer"].data_ptr() if st["momentum_buffer"] is not None else 0)
+
+    def _launch_dev(self, rec: dict, scale: Optional[int], found: Optional[int], coef: Optional[int]) -> None:
+        n = len(rec["ns"])
+        blk = self._block(rec["gi"], rec["group"], rec["dev"])               # (raises under capture when it is not there yet)
+        check(lib.rn_sgd_master_step_dev(_ptrs(rec["masters"]), _ptrs(rec["moms"]), _ptrs(rec["gptrs"]), _ptrs(rec["p16s"]), (C.c_int64 * n)(*rec["ns"]),
+                                         n, int(bool(rec["grads16"])), _dt16(rec["dt16"]), int(self._structure[rec["gi"]][0]), blk.data_ptr(),
+                                         scale, found, coef, torch.cuda.current_stream().cuda_stream), "rn_sgd_master_step_dev")
+
+    # -- checkpoints in torch's SGD format, plus the count ---------------------------------------------------------
+    def group_steps(self) -> List[int]:
+        "The steps every parameter group has taken (capturable mode: reads the device blocks, which synchronises)."
+        if self._capturable:
+            return [int(self._blocks[i].view(torch.int32)[_SHP_STEPS]) if i in self._blocks else 0 for i in range(len(self.param_groups))]
+        return [max((self.state[p].get("steps", 0) for p in g["params"] if p in self.state), default=0) for g in self.param_groups]
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if not self._capturable:
+            return sd
+        steps = self.group_steps()
+        idx = 0
+        for gi, group in enumerate(self.param_groups):
+            for _ in group["params"]:
+                st = sd["state"].get(idx)
+                if st is not None:
+                    sd["state"][idx] = {"momentum_buffer": st["momentum_buffer"], "steps": steps[gi]}
+                idx += 1
+        return sd
+
+    def load_state_dict(self, state_dict) -> None:
+        """Load a checkpoint of this class (either mode) or of ``torch.optim.SGD``: the momentum buffers are copied in fp32 into the
+        masters' memory order, ``steps`` (torch's state has none: 1 where a ``momentum_buffer`` is present, else 0) into the host's
+        count or the device block.  Parameters of one group must carry one count."""
+        saved_state, saved_groups = state_dict["state"], state_dict["param_groups"]
+        counts = []
+        for g in saved_groups:
+            if g.get("maximize"):
+                raise ValueError("MasterSGD cannot resume a maximize=True checkpoint")
+            vals = set()
+            for i in g["params"]:
+                if i in saved_state:
+                    st = saved_state[i]
+                    vals.add(int(st["steps"]) if "steps" in st else int(st.get("momentum_buffer") is not None))
+            if len(vals) > 1:
+                raise RuntimeError(f"MasterSGD: the parameters of one group took different numbers of steps ({sorted(vals)}): the count is one per group")
+            counts.append(vals.pop() if vals else 0)
+        # torch's loader restores the groups' hyperparameters; it would cast the buffers to the PARAMETER's dtype (bf16 for a
+        # converted conv weight), so they are left out of it and copied below
+        super().load_state_dict({"state": {}, "param_groups": saved_groups})
+        idx = 0
+        with torch.no_grad():
+            for gi, group in enumerate(self.param_groups):
+                if self._capturable:
+                    self._hparams(gi, group)                                 # (a checkpoint that contradicts the fixed settings is refused)
+                    fixed = self._structure.get(gi)
+                    has_m = fixed[0] if fixed is not None else float(group["momentum"]) != 0.0
+                else:
+                    has_m = float(group["momentum"]) != 0.0
+                for p in group["params"]:
+                    saved = saved_state.get(idx)
+                    idx += 1
+                    if saved is None:
+                        continue
+                    buf = saved.get("momentum_buffer")
+                    w = p.master if hasattr(p, "master") else p.data
+                    if has_m and buf is None:
+                        if self._capturable:
+                            self.state[p]["momentum_buffer"] = torch.empty_like(w).fill_(0)
+                        continue                                             # (by value: the next step creates the buffer, as a first step)
+                    st = self.state[p]
+                    st["momentum_buffer"] = torch.empty_like(w).copy_(buf) if has_m else None
+                    if not self._capturable:
+                        st["steps"] = counts[gi]
+        if self._capturable:
+            for gi, group in enumerate(self.param_groups):
+                if group["params"] and group["params"][0].is_cuda:
+                    self._write_block(gi, group, counts[gi])
 
 RN_ADAM_HPARAMS = 16                    # doubles per group in the device block (include/retinanet_hip.h)
 _HP_STEP = 5                            # the step counter's slot in it

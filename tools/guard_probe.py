@@ -7,7 +7,7 @@ mapping and the GPU raises a memory access fault (the process aborts) instead of
 usage: guard_probe.py stem B H W | w3 N H W C | n3 N H W | dense | pw | pool | bottleneck | step KIND MIN MAX | detect DT B H W K [MEAN] |
        loss DT B H W K T | gt | affine | adam [bf16|f16] | clip [bf16|f16] | accum [bf16|f16]        (driven by tests/test_guard_gpu.py;
        gt: by tests/test_gt_capacity_gpu.py; affine: by tests/test_shift_scale_rotate_gpu.py; adam: by tests/test_master_adam_gpu.py; clip: by tests/test_grad_clip_gpu.py;
-       accum: by tests/test_grad_accum_gpu.py)
+       accum: by tests/test_grad_accum_gpu.py; sgd_dev [bf16|f16]: by tests/test_master_sgd_capturable_gpu.py)
 Prints one "ok ..." line per case; a fault kills the process (non-zero exit status, no "ok" line for the case)."""
 import ctypes as C
 import os
@@ -378,6 +378,45 @@ def main() -> None:
         assert worst < 1e-4, worst
         assert float(hp[5]) == 3.0, float(hp[5])
         print("ok adam", str(dt), n_t, f"{worst:.2e}", flush=True)
+    elif which == "sgd_dev":
+        # rn_sgd_master_step_dev (csrc/optim.hip): 52 tensors (two launches of 48 + 4), every master / momentum buffer / gradient /
+        # 16-bit copy, the 32-byte hparams block and the GradScaler scalars at the end of their own mappings; sizes through the
+        # scalar tail path.  Three steps (the first reads no buffer) against rn_sgd_master_step on ordinary copies, bit for bit.
+        from pytorch_retinanet_amd._lib import RN_F16
+        sizes = [1, 3, 4, 5, 1023, 4097, 64 * 3 * 7 * 7 + 2] + [(i * 37) % 301 + 1 for i in range(45)]
+        dt = torch.bfloat16 if len(sys.argv) < 3 or sys.argv[2] == "bf16" else torch.float16
+        dt16 = RN_F16 if dt == torch.float16 else RN_BF16
+        g = torch.Generator(device=DEV).manual_seed(15)
+
+        def at_end(src: torch.Tensor) -> torch.Tensor:
+            t = raw_at_end(src.numel() * src.element_size()).view(src.dtype)
+            t.copy_(src.reshape(-1))
+            return t
+        n_t = len(sizes)
+        with16 = [i % 3 != 0 for i in range(n_t)]
+        w32 = [torch.randn(n, device=DEV, generator=g) for n in sizes]
+        masters, ref_m = [at_end(w) for w in w32], [w.clone() for w in w32]
+        p16 = [at_end(w.to(dt)) if h else None for w, h in zip(w32, with16)]
+        ref_p16 = [w.to(dt) if h else None for w, h in zip(w32, with16)]
+        moms, ref_moms = [at_end(torch.zeros(n, device=DEV)) for n in sizes], [torch.zeros(n, device=DEV) for n in sizes]
+        hp = at_end(torch.zeros(8, dtype=torch.int32, device=DEV))
+        scale, found = at_end(torch.full((1,), 8.0, device=DEV)), at_end(torch.zeros(1, device=DEV))
+        ptrs = lambda ts: (C.c_void_p * n_t)(*[t.data_ptr() if t is not None else 0 for t in ts])
+        for step in range(3):
+            lr = 1e-2 * (1.0 + 0.5 * step)
+            gs = [torch.randn(n, device=DEV, generator=g) for n in sizes]
+            gs = [(x.to(dt) if h else x) * 8.0 for x, h in zip(gs, with16)]       # (scaled by the GradScaler's 8: exact)
+            gd = [at_end(x) for x in gs]
+            check(lib.rn_sgd_hparams_set(hp.data_ptr(), lr, 0.9, 0.1, 1e-4, 0, -1, st), "rn_sgd_hparams_set")
+            check(lib.rn_sgd_master_step_dev(ptrs(masters), ptrs(moms), ptrs(gd), ptrs(p16), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, 1,
+                                             hp.data_ptr(), scale.data_ptr(), found.data_ptr(), None, st), "rn_sgd_master_step_dev")
+            check(lib.rn_sgd_master_step(ptrs(ref_m), ptrs(ref_moms), ptrs(gs), ptrs(ref_p16), (C.c_int64 * n_t)(*sizes), n_t, 1, dt16, lr, 0.9,
+                                         0.1, 1e-4, 0, int(step == 0), scale.data_ptr(), found.data_ptr(), None, st), "rn_sgd_master_step")
+        torch.cuda.synchronize()
+        for a, b in zip(masters + moms + [c for c in p16 if c is not None], ref_m + ref_moms + [c for c in ref_p16 if c is not None]):
+            assert torch.equal(a, b), "device-block step != by-value step"
+        assert hp.tolist()[5:7] == [3, 0], hp.tolist()
+        print("ok sgd_dev", str(dt), n_t, flush=True)
     elif which == "clip":
         # rn_grad_norm_clip + rn_sgd_master_step + rn_adam_master_step with a clip_coef (csrc/clip.hip, optim.hip, adam.hip): 230 tensors (two
         # norm launches of 224 + 6), every gradient ENDING at the last byte its alignment contract allows in its own mapping (16-bit
