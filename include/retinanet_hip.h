@@ -129,6 +129,42 @@ int rn_iou_match_special_ex(const float *anchors, int64_t anchor_bstride,
                             float fg_thr, float bg_thr, int64_t *matches, int32_t *num_fg,
                             uint64_t *special_rows, int64_t total_gt, int flags, void *stream);
 
+/* ---- ATSS matcher -----------------------------------------------------------
+ * Adaptive Training Sample Selection (Zhang et al., CVPR 2020) as a second matcher that fills K2's three outputs -- matches,
+ * num_fg, special_rows -- so the loss kernel reads its results exactly as it reads K2's.  The official code compares
+ * iou >= mean + std in fp32 with library reductions, which leaves the last bit open; this rule fixes every rounding.  Inputs as
+ * rn_iou_match_special_ex, plus the level layout: level_off i64[L + 1] (HOST; level l owns anchors [level_off[l], level_off[l + 1]),
+ * level_off[0] = 0, level_off[L] = A), cells i32[L] (HOST; anchors per grid location) and topk.  Every fp32 / fp64 step is one
+ * correctly rounded operation (no FMA contraction).
+ *   1. Centres.     acx = (x1 + x2) * 0.5f, acy = (y1 + y2) * 0.5f for anchors and GT boxes alike; dx = acx - gcx, dy = acy - gcy;
+ *                   d2 = dx * dx + dy * dy: two products and one sum, fp32.
+ *   2. Candidates.  For GT row g and level l: k_l = min(topk * cells[l], A_l); the candidates are the k_l anchors of the level that
+ *                   are smallest under the order (d2, anchor index) -- ties in d2 go to the lower index.  The candidate list of g is
+ *                   the levels in order, each ascending in that order; n = sum of k_l.
+ *   3. Statistics.  iou_c of a candidate = K2's fp32 pair arithmetic, widened to double.  mean = (sum of iou_c) / n, the sum in double,
+ *                   serially in list order; var = (sum of (iou_c - mean)^2) / (n - 1), a second serial pass in the same order, 0 when
+ *                   n == 1.  No square root is taken.
+ *   4. Positive.    A candidate is positive for g iff dev = iou_c - mean has dev >= 0 && dev * dev >= var (double) and
+ *                   min(acx - gx1, acy - gy1, gx2 - acx, gy2 - acy) > 0.01f (fp32).
+ *   5. Conflicts.   An anchor positive for several GT rows of its image takes the one with the largest fp32 IoU; ties go to the
+ *                   lowest GT index (K2's tie rule).
+ *   6. Output.      matches[b][a] = that GT index within the image, else -1 (there is no ignored band: -2 never appears);
+ *                   num_fg[b] = the count of positives; special_rows bit = [matches != -1].  An image without GT rows is all
+ *                   background.  Boxes are finite, as K2 requires.
+ * flags: RN_MATCH_NUM_FG_ZEROED / RN_MATCH_FLAGGED_ONLY as above (FLAGGED_ONLY needs special_rows); num_fg / special_rows nullable.
+ * total_gt >= 0: a HOST upper bound on gt_off[B] - gt_off[0] (the grids and the workspace are sized by it; rows beyond it are not
+ * matched).  gt_off is read on the device only and the call never syncs.  workspace: caller-owned, 16-byte aligned, at least
+ * rn_atss_match_workspace_bytes(...) (0 for arguments the call would refuse).  Its first B * A 64-bit words are the conflict table:
+ * they must be ZERO on entry and are zero again when the call has run, so a buffer that is zero-filled once serves every later call
+ * with the same B and A (one call at a time).  RN_EUNSUPPORTED: a k_l above 2048. */
+size_t rn_atss_match_workspace_bytes(int B, int64_t A, int64_t total_gt, const int64_t *level_off, const int32_t *cells,
+                                     int L, int topk);
+int rn_atss_match(const float *anchors, int64_t anchor_bstride,
+                  const float *gt_boxes, const int32_t *gt_off, int B, int64_t A,
+                  const int64_t *level_off, const int32_t *cells, int L, int topk,
+                  int64_t *matches, int32_t *num_fg, uint64_t *special_rows, int64_t total_gt, int flags,
+                  void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- K3 loss_fwd_bwd --------------------------------------------------------
  * Replaces RetinaNetLosses.forward / calc_loss / focal_loss / smooth_l1_loss,
  * retinanet/losses.py:19-145, and bbox_2_activ, retinanet/box_utils.py:25-34:

@@ -45,6 +45,93 @@ def activ_2_bbox(activations: Tensor, anchors: Tensor) -> Tensor:
     return ops.decode_clip(activations, anchors, None)
 
 
+def _iou_pairs_f32(t, a):
+    "K2's pair arithmetic (csrc/rn_match.hpp, iou_pair) of one GT box against anchors [n,4], operation for operation in numpy fp32."
+    import numpy as np
+    area_t = (t[2] - t[0]) * (t[3] - t[1])
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    w = np.minimum(t[2], a[:, 2]) - np.maximum(t[0], a[:, 0])
+    h = np.minimum(t[3], a[:, 3]) - np.maximum(t[1], a[:, 1])
+    w = np.where(w > 0, w, np.float32(0))
+    h = np.where(h > 0, h, np.float32(0))
+    inter = w * h
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return inter / ((area_t + area_a) - inter)
+
+
+def atss_candidates(anchors, target, level_sizes, cells, topk: int = 9):
+    """Steps 1-2 of the ATSS rule for ONE GT box: the candidate list (anchor indices, levels in order, each ascending in
+    (d2, index)) as a numpy int64 array.  ``anchors`` / ``target``: numpy fp32 [A,4] / [4]."""
+    import numpy as np
+    half = np.float32(0.5)
+    acx, acy = (anchors[:, 0] + anchors[:, 2]) * half, (anchors[:, 1] + anchors[:, 3]) * half
+    gcx, gcy = (target[0] + target[2]) * half, (target[1] + target[3]) * half
+    dx, dy = acx - gcx, acy - gcy
+    xx, yy = dx * dx, dy * dy
+    d2 = xx + yy                                           # two products and one sum, each rounded to fp32
+    cells = [int(cells)] * len(level_sizes) if isinstance(cells, int) else [int(c) for c in cells]
+    out, lo = [], 0
+    for size, c in zip(level_sizes, cells):
+        k = min(int(topk) * c, int(size))
+        order = np.argsort(d2[lo:lo + size], kind="stable")[:k]      # stable: ties in d2 go to the lower index
+        out.append(order.astype(np.int64) + lo)
+        lo += int(size)
+    return np.concatenate(out) if out else np.zeros((0,), np.int64)
+
+
+def atss_matcher(anchors: Tensor, targets: Tensor, level_sizes, cells, topk: int = 9) -> Tensor:
+    """ATSS (Zhang et al., CVPR 2020): match `anchors` [A,4] to `targets` [T,4] -> i64 [A], -1 background, else the target index
+    (there is no ignored band).  ``level_sizes``: anchors per pyramid level, in anchor order; ``cells``: anchors per grid location
+    (an int or one per level).  CUDA tensors go to the HIP kernel (``ops.atss_match``); CPU tensors run this restatement of the
+    numbered rule in include/retinanet_hip.h, operation for operation, in numpy fp32 and Python doubles:
+      1. centres (x1 + x2) * 0.5f, d2 = dx * dx + dy * dy in fp32;
+      2. per level the k_l = min(topk * cells, A_l) anchors smallest under (d2, index); the list is the levels in order;
+      3. iou_c in K2's fp32 pair arithmetic, widened to double; mean and var = sum((iou_c - mean)^2) / (n - 1) (0 for n == 1) as
+         two serial double sums in list order; no square root;
+      4. positive iff dev = iou_c - mean has dev >= 0 and dev * dev >= var, and the anchor centre lies inside the box by more than
+         0.01f on every side (fp32);
+      5. an anchor positive for several targets takes the largest fp32 IoU, ties to the lowest target index."""
+    targets = targets.reshape(-1, 4)
+    level_sizes = [int(s) for s in level_sizes]
+    if sum(level_sizes) != anchors.shape[0]:
+        raise ValueError(f"level sizes {level_sizes} do not sum to the {anchors.shape[0]} anchors")
+    if anchors.is_cuda:
+        off = ops.gt_offsets([targets.shape[0]], anchors.device)
+        matches, _ = ops.atss_match(anchors, targets, off, 1, level_sizes, cells, topk, want_num_fg=False)
+        return matches[0]
+    import numpy as np
+    a = anchors.detach().to(torch.float32).contiguous().numpy()
+    t = targets.detach().to(torch.float32).contiguous().numpy()
+    half, margin = np.float32(0.5), np.float32(0.01)
+    acx, acy = (a[:, 0] + a[:, 2]) * half, (a[:, 1] + a[:, 3]) * half
+    matches = np.full((a.shape[0],), -1, np.int64)
+    best = np.full((a.shape[0],), -1.0, np.float32)
+    for g in range(t.shape[0]):
+        cand = atss_candidates(a, t[g], level_sizes, cells, topk)
+        n = len(cand)
+        if n == 0:
+            continue
+        iou = _iou_pairs_f32(t[g], a[cand])
+        vals = [float(v) for v in iou]                      # widened to double
+        s = 0.0
+        for v in vals:                                      # (a plain loop: the built-in sum() compensates its rounding)
+            s += v
+        mean = s / n
+        ss = 0.0
+        for v in vals:
+            d = v - mean
+            ss += d * d
+        var = ss / (n - 1) if n > 1 else 0.0
+        inside = np.minimum(np.minimum(acx[cand] - t[g, 0], acy[cand] - t[g, 1]), np.minimum(t[g, 2] - acx[cand], t[g, 3] - acy[cand]))
+        for j in range(n):
+            dev = vals[j] - mean
+            if dev >= 0.0 and dev * dev >= var and inside[j] > margin:
+                i = cand[j]
+                if iou[j] > best[i]:                        # strict: an equal IoU keeps the lower target index
+                    best[i], matches[i] = iou[j], g
+    return torch.from_numpy(matches)
+
+
 def matcher(anchors: Tensor, targets: Tensor, match_thr: Optional[float] = None, back_thr: Optional[float] = None) -> Tensor:
     """Match `anchors` [A,4] to `targets` [T,4]: -2 ignore, -1 background, else the
     target index (box_utils.py:51-80), HIP kernel K2 (fused IoU + arg-max + thresholds)."""

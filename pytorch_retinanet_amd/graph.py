@@ -219,10 +219,13 @@ def _net_targets(targets):
 
 class _Entry:
     "One kind of step of one signature: the calls seen so far and, once captured, the graph(s), their static inputs and the losses they write."
-    __slots__ = ("calls", "failed", "graph", "segments", "bucket_ids", "pool", "images", "targets", "losses", "match_state")
+    __slots__ = ("calls", "failed", "graph", "segments", "bucket_ids", "pool", "images", "targets", "losses", "match_state", "atss_ws")
 
     def __init__(self):
         self.calls, self.failed = 0, False
+        # the ATSS matcher's workspaces (``ops.use_atss_workspaces``): allocated and zero-filled by this entry's eager steps, read by
+        # its capture and replays, which leave the conflict table zero -- the graph never clears it
+        self.atss_ws = {}
         self.clear()
 
     def clear(self) -> None:
@@ -554,7 +557,12 @@ class CapturedTrainStep:
         ema = getattr(self.optimizer, "weight_ema", None)
         if ema is not None:
             key += (("weight_ema", ema),)
-        return key + tuple(aug.items())
+        key += tuple(aug.items())
+        # the matcher's launches are part of the step: another kind or another topk is another graph.  The default ("iou") adds nothing.
+        crit = getattr(getattr(self.net, "retinanet_head", None), "losses", None)
+        if getattr(crit, "matcher", "iou") != "iou":
+            key += (("matcher", crit.matcher, int(crit.atss_topk)),)
+        return key
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:
         "Four linear graphs sharing one memory pool; the exchange calls between them run eagerly, here as at every replay."
@@ -584,7 +592,7 @@ class CapturedTrainStep:
             # (i == 2: ddp.finish() runs next -- eager: the compute stream waits for the communication stream -- and begins the
             # optimizer's segment, see finish_then_begin below)
 
-        with ops.use_match_state(e.match_state), torch.cuda.stream(side):
+        with ops.use_match_state(e.match_state), ops.use_atss_workspaces(e.atss_ws), torch.cuda.stream(side):
             orig_finish = ddp.finish
 
             def finish_then_begin():
@@ -640,7 +648,7 @@ class CapturedTrainStep:
         e.hold_inputs(images, targets)
         torch.cuda.synchronize()
         g = _new_graph()
-        with ops.use_match_state(e.match_state), torch.cuda.graph(g, capture_error_mode="thread_local"):
+        with ops.use_match_state(e.match_state), ops.use_atss_workspaces(e.atss_ws), torch.cuda.graph(g, capture_error_mode="thread_local"):
             e.losses = self._step(e.images, e.targets, final)
         _repair_memset_nodes(g)
         e.graph = g
@@ -705,7 +713,8 @@ class CapturedTrainStep:
             _stage(images, sig.staged, icls[2])
             images = sig.staged
         if e.failed or e.calls <= self.eager_steps:
-            return self._step(images, targets, final)
+            with ops.use_atss_workspaces(e.atss_ws):
+                return self._step(images, targets, final)
         if e.graph is None and e.segments is None:
             try:
                 self._capture(e, images, targets, final)
@@ -720,7 +729,9 @@ class CapturedTrainStep:
                 if stuck is not None:
                     raise CaptureUnwindError(f"the failed capture ({type(exc).__name__}: {exc}) left the device in stream-capture mode "
                                              f"({type(stuck).__name__}: {stuck}); this process cannot run further GPU work") from exc
-                return self._step(images, targets, final)
+                e.atss_ws.clear()                             # (an unfinished capture never ran the kernels that put the table back to zero)
+                with ops.use_atss_workspaces(e.atss_ws):
+                    return self._step(images, targets, final)
         else:
             # the step's inputs into the graph's static buffers: one multi-tensor launch per dtype for what already lives on the
             # device (24 separate copies cost 0.19 ms per step), plain copies for the rest

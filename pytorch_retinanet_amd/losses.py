@@ -155,7 +155,8 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
             loss, gcls, gbox = fused[0], fused[1], fused[2]
         else:
             if ahead is not None:
-                torch.cuda.current_stream(cls_levels[0].device).wait_event(ahead.done)        # K2 ran beside the head convolutions
+                if ahead.done is not None:
+                    torch.cuda.current_stream(cls_levels[0].device).wait_event(ahead.done)    # K2 ran beside the head convolutions
                 matches, num_fg, special = ahead.matches, ahead.num_fg, ahead.special
             else:
                 # `matches` goes nowhere but into the loss kernel, which reads it through the flag words: K2 writes the flagged rows only
@@ -208,9 +209,27 @@ def _stack_anchors(anchors) -> Tensor:
     return torch.stack(list(anchors))
 
 
+def _check_matcher(matcher: str, atss_topk: int) -> None:
+    if matcher not in ops.ATSS_MATCHERS:
+        raise ValueError(f"matcher must be one of {ops.ATSS_MATCHERS}, got {matcher!r}")
+    if int(atss_topk) <= 0:
+        raise ValueError(f"atss_topk must be a positive int, got {atss_topk!r}")
+    if matcher == "atss" and FUSE_MATCH:
+        raise ValueError('RN_FUSE_MATCH=1 runs the max-IoU matcher inside the loss kernel and cannot be combined with matcher="atss": '
+                         "there is no ATSS form of the fused kernel; unset RN_FUSE_MATCH or use matcher=\"iou\"")
+
+
 class RetinaNetLosses(nn.Module):
-    def __init__(self, num_classes: int) -> None:
+    def __init__(self, num_classes: int, matcher: str = "iou", atss_topk: int = 9, cells=None) -> None:
+        """``matcher``: "iou" (K2: the reference's max-IoU rule with its 0.5 / 0.4 thresholds) or "atss" (``ops.atss_match``: a
+        per-object threshold from the IoU statistics of the ``atss_topk`` nearest locations of every pyramid level; no ignored band).
+        ATSS applies to the per-level path (``forward_levels`` / ``match_ahead``, what ``Retinanet.forward`` runs; ``forward`` /
+        ``calc_loss`` on concatenated outputs raise a ``ValueError`` with it); ``cells``: anchors
+        per grid location (an int or one per level; ``Retinanet`` passes its anchor generator's), default 9."""
         super().__init__()
+        _check_matcher(matcher, atss_topk)
+        self.matcher, self.atss_topk = matcher, int(atss_topk)
+        self.cells = 9 if cells is None else cells
         self.n_c = num_classes
         self.alpha = FOCAL_LOSS_ALPHA
         self.gamma = FOCAL_LOSS_GAMMA
@@ -239,6 +258,9 @@ class RetinaNetLosses(nn.Module):
         return ops.make_loss_params(self.alpha, self.gamma, self.beta, LOGIT_SHIFT, ENCODE_LOG_EPS, BBOX_REG_WEIGHTS)
 
     def _fused(self, cls: Tensor, box: Tensor, anchors, boxes: Sequence[Tensor], labels: Sequence[Tensor]) -> Tensor:
+        if self.matcher == "atss":
+            # (the concatenated outputs carry no level layout, and matching them with K2 instead would be a silent change of rule)
+            raise ValueError('matcher="atss" runs on the per-level head outputs: use forward_levels / Retinanet.forward, not forward / calc_loss')
         dev = cls.device
         counts = [int(b.reshape(-1, 4).shape[0]) for b in boxes]
         gt_boxes = torch.cat([b.reshape(-1, 4).to(device=dev, dtype=torch.float32) for b in boxes]) \
@@ -260,13 +282,35 @@ class RetinaNetLosses(nn.Module):
         (see ``FUSE_MATCH``)."""
         return FUSE_MATCH and _max_gt_per_image(targets) <= 64
 
-    def match_ahead(self, targets: List[Dict[str, Tensor]], anchors) -> MatchAhead:
+    def _atss_level_sizes(self, level_sizes, A: int) -> List[int]:
+        if level_sizes is None:
+            raise ValueError('matcher="atss" needs the anchors per pyramid level (level_sizes)')
+        sizes = [int(v) for v in level_sizes]
+        if sum(sizes) != A:
+            raise ValueError(f"level sizes {sizes} do not sum to the {A} anchors")
+        return sizes
+
+    def _atss_now(self, anchors_t: Tensor, gt_boxes: Tensor, gt_labels: Tensor, gt_off: Tensor, B: int, level_sizes, num_fg0) -> MatchAhead:
+        "The ATSS matcher on the CURRENT stream, as a handle the loss Function reads like ``match_ahead``'s (nothing to wait for)."
+        _check_matcher(self.matcher, self.atss_topk)
+        h = MatchAhead()
+        h.anchors, h.gt_boxes, h.gt_labels, h.gt_off, h.done = anchors_t, gt_boxes, gt_labels, gt_off, None
+        h.matches, h.num_fg, h.special = ops.atss_match(anchors_t, gt_boxes, gt_off, B, self._atss_level_sizes(level_sizes, int(anchors_t.shape[-2])),
+                                                        self.cells, self.atss_topk, want_special=True, flagged_only=True, zeroed_num_fg=num_fg0)
+        return h
+
+    def match_ahead(self, targets: List[Dict[str, Tensor]], anchors, level_sizes=None) -> MatchAhead:
         """Launch K2 (IoU + matcher, box_utils.py:51-80) NOW, on a side stream: it depends only on the anchors and the GT boxes,
         both known as soon as the feature-map shapes are, and then runs beside the head convolutions instead of between the
         class-output conv and K3.  Pass the result to ``forward_levels(..., ahead=...)``, which makes the loss kernel wait
-        for it.  The outputs belong to the CALLING stream (allocated before the fork, consumed after the join)."""
+        for it.  The outputs belong to the CALLING stream (allocated before the fork, consumed after the join).
+        ``matcher="atss"``: the same with ``ops.atss_match``; ``level_sizes`` (anchors per pyramid level) is needed then."""
         anchors = _stack_anchors(anchors)
         dev = anchors.device
+        sizes = None
+        if self.matcher == "atss":
+            _check_matcher(self.matcher, self.atss_topk)
+            sizes = self._atss_level_sizes(level_sizes, int(anchors.shape[-2]))
         h = MatchAhead()
         h.anchors = anchors
         packed = isinstance(targets, ops.PackedGT)
@@ -281,8 +325,12 @@ class RetinaNetLosses(nn.Module):
         main, side = torch.cuda.current_stream(dev), _side_stream(dev)
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            ops.iou_match(anchors, h.gt_boxes, h.gt_off, B, IOU_THRESHOLDS_FOREGROUND, IOU_THRESHOLDS_BACKGROUND,
-                          out=(h.matches, h.num_fg, h.special), zeroed_num_fg=h.num_fg if packed else None)
+            if sizes is not None:
+                ops.atss_match(anchors, h.gt_boxes, h.gt_off, B, sizes, self.cells, self.atss_topk,
+                               out=(h.matches, h.num_fg, h.special), zeroed_num_fg=h.num_fg if packed else None)
+            else:
+                ops.iou_match(anchors, h.gt_boxes, h.gt_off, B, IOU_THRESHOLDS_FOREGROUND, IOU_THRESHOLDS_BACKGROUND,
+                              out=(h.matches, h.num_fg, h.special), zeroed_num_fg=h.num_fg if packed else None)
             h.done = torch.cuda.Event()
             h.done.record(side)
         # the tensors were allocated on the calling stream but are written / read on the side stream: if the head raises before
@@ -301,8 +349,19 @@ class RetinaNetLosses(nn.Module):
         dev = cls_levels[0].device
         if isinstance(targets, ops.PackedGT) and targets.B != int(cls_levels[0].shape[0]):
             raise ValueError(f"packed GT of {targets.B} images for a batch of {int(cls_levels[0].shape[0])}")
+        atss = self.matcher == "atss"
         if ahead is not None:
             gt_boxes, gt_labels, gt_off, anchors_t = ahead.gt_boxes, ahead.gt_labels, ahead.gt_off, ahead.anchors
+        elif atss:
+            # the ATSS matcher fills K2's three buffers on this stream (the level sizes: the per-level head outputs'); K3 reads them
+            # through the handle as it reads match_ahead's.  Packed GT: the staged arrays and their zeroed num_fg as they are.
+            anchors_t = _stack_anchors(anchors)
+            if isinstance(targets, ops.PackedGT):
+                gt_boxes, gt_labels, gt_off, nfg0 = targets.gt_boxes, targets.gt_labels, targets.gt_off, targets.num_fg
+            else:
+                gt_boxes, gt_labels, gt_off, nfg0 = ops.gt_pack([t["boxes"] for t in targets], [t["labels"] for t in targets], dev)
+            ahead = self._atss_now(anchors_t, gt_boxes, gt_labels, gt_off, int(cls_levels[0].shape[0]),
+                                   [int(c.shape[1]) for c in cls_levels], nfg0)
         elif isinstance(targets, ops.PackedGT):
             # packed GT (graph.CapturedTrainStep's capacity mode): the staged arrays as they are.  Every host-side GT figure is an
             # upper bound here: K2's kernel choice sees R rows (ops.iou_match passes gt_boxes.shape[0]), K3's form comes from R

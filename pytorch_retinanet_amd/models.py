@@ -51,8 +51,14 @@ class Retinanet(nn.Module):
         image_std: Optional[List[float]] = None,
         anchor_generator: Optional[AnchorGenerator] = None,
         logger=None,
+        matcher: Optional[str] = None,
+        atss_topk: Optional[int] = None,
     ) -> None:
+        """``matcher``: how anchors are labelled -- None / "iou" (the reference's max-IoU rule, K2) or "atss" (``ops.atss_match``,
+        with ``atss_topk`` nearest locations per level and object, None -> 9); ``model: {matcher: atss}`` in the hparams."""
         super().__init__()
+        matcher = ifnone(matcher, "iou")
+        atss_topk = ifnone(atss_topk, 9)
         num_classes = ifnone(num_classes, NUM_CLASSES)
         backbone_kind = ifnone(backbone_kind, BACKBONE)
         prior = ifnone(prior, PRIOR)
@@ -79,7 +85,8 @@ class Retinanet(nn.Module):
         self.fpn = FeaturePyramid(c3, c4, c5, 256)
         self.anchor_generator = anchor_generator
         num_anchors = self.anchor_generator.num_cell_anchors[0]
-        self.retinanet_head = RetinaNetHead(256, 256, num_anchors, num_classes, prior)
+        self.retinanet_head = RetinaNetHead(256, 256, num_anchors, num_classes, prior, matcher=matcher, atss_topk=atss_topk,
+                                            cells=self.anchor_generator.num_anchors)
 
         self.score_thres = score_thres
         self.nms_thres = nms_thres
@@ -148,7 +155,10 @@ class Retinanet(nn.Module):
         # the linear graph of the same step, bench.py host_enqueue_ms_per_step) -- 25 us of GPU time are not worth that.
         ahead = None
         if batch.is_cuda and not torch.cuda.is_current_stream_capturing() and not self.retinanet_head.losses.fuses_match(targets):
-            ahead = self.retinanet_head.losses.match_ahead(targets, anchors)      # (<= 64 GT per image: K2 runs inside K3, no launch at all)
+            sizes = None
+            if self.retinanet_head.losses.matcher == "atss":                      # (its candidates are chosen per pyramid level)
+                sizes = [int(f.shape[-2]) * int(f.shape[-1]) * n for f, n in zip(feature_maps, self.anchor_generator.num_anchors)]
+            ahead = self.retinanet_head.losses.match_ahead(targets, anchors, sizes)   # (<= 64 GT per image: K2 runs inside K3, no launch at all)
         # same losses as compute_loss(targets, retinanet_head(feature_maps), anchors), but the loss kernel
         # reads the five per-level conv outputs in place instead of their torch.cat (layers.py:195, :259)
         outputs = self.retinanet_head.forward_levels(feature_maps)

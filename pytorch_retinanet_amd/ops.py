@@ -304,6 +304,114 @@ def iou_match_outputs(B: int, A: int, dev: torch.device, want_num_fg: bool = Tru
     return matches, num_fg, special
 
 
+# ---- ATSS matcher ------------------------------------------------------------------------------------------------------------
+# rn_atss_match's workspace starts with its [B][A] conflict table, which must be ZERO on entry and is zero again after every completed
+# call: it is zero-filled once here and then reused, so no step clears its B * A * 8 bytes.  One buffer per device, stream and anchor
+# layout (two streams must not share a table); a hipGraph capture uses the buffers of its own holder (``use_atss_workspaces``: a dict
+# owned by the captured entry, filled by that entry's eager steps, so the capture allocates -- and zero-fills -- nothing).
+_ATSS_WS = {}
+_ATSS_WS_OVERRIDE = None
+ATSS_MATCHERS = ("iou", "atss")
+
+
+class use_atss_workspaces:
+    "``with use_atss_workspaces(holder):`` -- ``atss_match`` calls inside the block keep their workspaces in the dict ``holder``."
+
+    def __init__(self, holder: Optional[dict]):
+        self.holder = holder
+
+    def __enter__(self):
+        global _ATSS_WS_OVERRIDE
+        self.prev, _ATSS_WS_OVERRIDE = _ATSS_WS_OVERRIDE, self.holder
+        return self
+
+    def __exit__(self, *exc):
+        global _ATSS_WS_OVERRIDE
+        _ATSS_WS_OVERRIDE = self.prev
+        return False
+
+
+def reset_atss_workspaces() -> None:
+    "Drop the cached workspaces: the next call allocates zero-filled ones (for after a call that did not complete)."
+    _ATSS_WS.clear()
+
+
+def atss_layout(level_sizes: Sequence[int], cells, topk: int):
+    "(level_off i64[L + 1], cells i32[L], L) as ctypes arrays, plus the hashable form of the same."
+    sizes = [int(s) for s in level_sizes]
+    L = len(sizes)
+    if L == 0 or L > _lib.RN_MAX_LEVELS:
+        raise ValueError(f"need 1..{_lib.RN_MAX_LEVELS} levels, got {L}")
+    cells = [int(cells)] * L if isinstance(cells, int) else [int(c) for c in cells]
+    if len(cells) != L:
+        raise ValueError(f"{len(cells)} cell counts for {L} levels")
+    if int(topk) <= 0 or any(c <= 0 for c in cells) or any(s < 0 for s in sizes):
+        raise ValueError(f"topk and cells must be positive and level sizes non-negative, got topk={topk} cells={cells} sizes={sizes}")
+    off = [0]
+    for s in sizes:
+        off.append(off[-1] + s)
+    return (C.c_int64 * (L + 1))(*off), (C.c_int32 * L)(*cells), L, (tuple(sizes), tuple(cells), int(topk))
+
+
+def atss_workspace(dev: torch.device, B: int, A: int, rows: int, level_sizes: Sequence[int], cells, topk: int) -> Tensor:
+    """The (cached) workspace of ``atss_match`` for these shapes on the current stream: uint8, its conflict table zero.  Sized for a
+    power-of-two row capacity >= ``rows``, so batches with other GT counts reuse it."""
+    off, cl, L, lkey = atss_layout(level_sizes, cells, topk)
+    holder = _ATSS_WS_OVERRIDE
+    key = (dev.index, B, A) + lkey
+    if holder is None:
+        holder, key = _ATSS_WS, key + (torch.cuda.current_stream(dev).cuda_stream,)
+    hit = holder.get(key)
+    if hit is not None and hit[1] >= rows:
+        return hit[0]
+    cap = 64
+    while cap < rows:
+        cap *= 2
+    nbytes = lib.rn_atss_match_workspace_bytes(B, A, cap, off, cl, L, int(topk))
+    if nbytes == 0:
+        raise ValueError(f"rn_atss_match takes no such layout: B={B} A={A} levels={lkey}")
+    if holder is _ATSS_WS and len(holder) >= 8:
+        holder.clear()
+    ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+    holder[key] = (ws, cap)
+    return ws
+
+
+def atss_match(anchors: Tensor, gt_boxes: Tensor, gt_off: Tensor, B: int, level_sizes: Sequence[int], cells, topk: int = 9,
+               want_num_fg: bool = True, want_special: bool = False, out: Optional[tuple] = None, flagged_only: bool = False,
+               zeroed_num_fg: Optional[Tensor] = None, workspace: Optional[Tensor] = None):
+    """The ATSS matcher (``rn_atss_match``; the rule: include/retinanet_hip.h, restated by ``box_utils.atss_matcher``).  Arguments and
+    results as ``iou_match`` -- (matches i64 [B,A] with -1 background / GT index, num_fg i32 [B][, special]) -- with the level layout
+    in place of the thresholds: ``level_sizes`` = anchors per pyramid level (in anchor order, summing to A), ``cells`` = anchors per
+    grid location (an int or one per level).  ``gt_boxes.shape[0]`` is the host's upper bound on the rows (packed GT: its capacity);
+    the counts are read from ``gt_off`` on the device.  ``workspace``: a uint8 tensor from ``atss_workspace`` (default: the cached
+    one for these shapes and the current stream); its conflict table is zero before and after the call."""
+    dev = _need_dev(anchors, gt_boxes, gt_off)
+    A = anchors.shape[-2]
+    anchors, bstride = _anchor_args(anchors, B, A)
+    gt_boxes = _c(gt_boxes.float()).reshape(-1, 4)
+    off, cl, L, lkey = atss_layout(level_sizes, cells, topk)
+    if sum(lkey[0]) != A:
+        raise ValueError(f"level sizes {lkey[0]} do not sum to the {A} anchors")
+    if out is not None:
+        matches, num_fg, special = out
+    else:
+        matches, num_fg, special = iou_match_outputs(B, A, dev, want_num_fg and zeroed_num_fg is None, want_special)
+    flags = 0
+    if zeroed_num_fg is not None:
+        num_fg, flags = zeroed_num_fg, flags | RN_MATCH_NUM_FG_ZEROED
+    if flagged_only:
+        if special is None:
+            raise ValueError("flagged_only needs the flag words (want_special=True)")
+        flags |= RN_MATCH_FLAGGED_ONLY
+    rows = int(gt_boxes.shape[0])
+    ws = workspace if workspace is not None else atss_workspace(dev, B, A, rows, lkey[0], lkey[1], topk)
+    with torch.cuda.device(dev), _timed("atss_match", dev):
+        check(lib.rn_atss_match(_ptr(anchors), bstride, _ptr(gt_boxes), _ptr(gt_off), B, A, off, cl, L, int(topk), _ptr(matches),
+                                _ptr(num_fg), _ptr(special), rows, flags, _ptr(ws), ws.numel(), _stream(dev)), "rn_atss_match")
+    return (matches, num_fg, special) if (want_special or out is not None) else (matches, num_fg)
+
+
 def make_loss_params(alpha: float, gamma: float, beta: float, logit_shift: float = 1.0, log_eps: float = 1e-8,
                      reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0)) -> RnLossParams:
     return RnLossParams(alpha, gamma, beta, logit_shift, log_eps, (C.c_float * 4)(*reg_w))
