@@ -256,6 +256,56 @@ int rn_loss_fwd_bwd_levels_rp(const void *const *cls_levels, const void *const *
                               const float *grad_prescale, int form, float *out_loss, void *const *grad_cls_levels,
                               void *const *grad_box_levels, void *workspace, size_t workspace_bytes, void *state,
                               void *stream, void *event_start, void *event_stop);
+/* ---- IoU-type box regression losses (round 28; not in the reference) ----------
+ * GIoU (Rezatofighi et al., CVPR 2019) and DIoU (Zheng et al., AAAI 2020) in place of K3's encode-then-smooth-L1, as torchvision's
+ * detection heads offer them.  rn_box_iou_loss runs BEHIND a K3 call on the same stream: K3 has written grad_box for every row and
+ * out_loss[1]; this call recomputes the loss of the MATCHED rows, overwrites those rows of grad_box_levels and replaces out_loss[1].
+ * out_loss[0], the class gradients and every row that is not matched keep what K3 wrote.
+ * A matched row is a row whose flag bit is set in special_rows and whose matches[b][a] = m >= 0.  Its GT box is
+ * g = gt_boxes[gt_off[b] + m] (m clamped into the image's rows), its anchor an, its deltas d[0..3] widened from the I/O dtype to fp32.
+ * Every fp32 step below is one correctly rounded operation (no FMA contraction); expf is the device library's.
+ *   1. Decode.    The inverse of bbox_2_activ (the meaning the training targets give the four outputs; NOT K4's decode, which keeps the
+ *                 reference's quirk Q4).  t[j] = d[j] / reg_w[j]; acx = (an.x1 + an.x2) / 2, acy likewise, aw = an.x2 - an.x1,
+ *                 ah = an.y2 - an.y1 (as K3's encode); cx = aw * t0 + acx, cy = ah * t1 + acy; sw = min(t2, CLIP), sh = min(t3, CLIP)
+ *                 with CLIP = RN_BOX_XFORM_CLIP = logf(1000.0f / 16.0f) (torchvision's bbox_xform_clip: without it a 16-bit outlier
+ *                 makes exp infinite and the loss NaN); w = aw * expf(sw), h = ah * expf(sh); the box is
+ *                 (px1, py1, px2, py2) = (cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2).  A slot is CLIPPED iff t2 > CLIP (t3 > CLIP):
+ *                 its gradient is zero; at t2 == CLIP the derivative still goes to t2.
+ *   2. IoU.       iw = min(px2, gx2) - max(px1, gx1), ih likewise; a value that is not > 0 becomes 0 and its derivative is then 0;
+ *                 inter = iw * ih; union = (w * h + (gx2 - gx1) * (gy2 - gy1)) - inter; iou = union > 0 ? inter / union : 0.
+ *   3. Penalty.   The enclosing box is (min x1, min y1, max x2, max y2), ew = its width, eh = its height.
+ *                 RN_BOX_LOSS_GIOU: c = ew * eh; pen = c > 0 ? (c - union) / c : 0.
+ *                 RN_BOX_LOSS_DIOU: c2 = ew * ew + eh * eh; rho2 = dx * dx + dy * dy with dx = cx - (gx1 + gx2) / 2,
+ *                 dy = cy - (gy1 + gy2) / 2; pen = c2 > 0 ? rho2 / c2 : 0.
+ *                 The row loss is l = (1 - iou) + pen.
+ *   4. Gradient.  dl / dd[j] is the analytic derivative of steps 1-3 in fp32 (the order of its operations is not part of the rule:
+ *                 it is held to the fp32 bar against a float64 evaluation, not bit for bit).  Every min / max of steps 2 and 3 has
+ *                 one predicted and one GT argument: the PREDICTED coordinate is selected, and takes the derivative, only when the
+ *                 strict comparison holds (px2 < gx2 for a min, px1 > gx1 for a max, ...); a tie goes to the GT coordinate, whose
+ *                 derivative is zero.  The gradient is multiplied by loss_weight * scale_b, scale_b = (1.0f / max(num_fg[b], 1)) *
+ *                 (1.0f / B) (K3's image scale without alpha; an image without GT rows has no matched row), then by *grad_prescale when
+ *                 that is non-NULL, and only then rounded ONCE to the I/O dtype (K3's contract for fp16).
+ *   5. Sum.       out_loss[1] = (float)(loss_weight * sum over matched rows of (double)l * (double)scale_b), accumulated in double in
+ *                 a fixed order -- one partial per workgroup in its own workspace slot, a fixed-order final sum, no atomics -- so two
+ *                 calls give the same bits.
+ * Inputs as rn_loss_fwd_bwd_levels_rp.  special_rows is REQUIRED, and `matches` is read through its bits and nowhere else (with
+ * RN_MATCH_FLAGGED_ONLY it is valid nowhere else).  reg_w: HOST float[4], each > 0.  loss_weight > 0.  grad_box_levels: NULL = value
+ * only.  Counts, offsets and num_fg are read on the device; nothing synchronises, nothing is cleared, no workspace word needs a value
+ * on entry: the call is capturable as it stands.  workspace: 16-byte aligned, rn_box_iou_loss_workspace_bytes(B, A) bytes (0 for
+ * arguments the call refuses).  Two launches: the row kernel (at most 128 workgroups of 4 waves, a wave per 64 flag words of one
+ * image, grid-strided beyond that) and a one-wave sum.  RN_EINVAL: a null pointer, L outside 1..RN_MAX_LEVELS, B <= 0, an unknown
+ * dtype or kind, a non-positive or non-finite reg_w / loss_weight; RN_EALIGN: boxes not 8-byte (16-bit) / 16-byte (fp32), anchors or
+ * GT boxes not 16-byte, 64-bit arrays not 8-byte aligned; RN_EWORKSPACE: workspace_bytes too small. */
+#define RN_BOX_LOSS_GIOU 1
+#define RN_BOX_LOSS_DIOU 2
+#define RN_BOX_XFORM_CLIP 4.135166556742356f
+size_t rn_box_iou_loss_workspace_bytes(int B, int64_t A);
+int rn_box_iou_loss(const void *const *box_levels, const int64_t *level_anchors, int L, int dtype, int B,
+                    const float *anchors, int64_t anchor_bstride, const float *gt_boxes, const int32_t *gt_off,
+                    const int64_t *matches, const uint64_t *special_rows, const int32_t *num_fg,
+                    const float *reg_w, int kind, float loss_weight, const float *grad_prescale,
+                    float *out_loss, void *const *grad_box_levels, void *workspace, size_t workspace_bytes, void *stream);
+
 /* K2 + K3 in ONE launch (round 4): the matcher of retinanet/box_utils.py:51-80 runs in the loss kernel's prologue -- every wave
  * matches the anchor rows of its own range against the image's GT boxes (one box per lane, so max_gt_per_image <= 64), the
  * per-image foreground counts meet in device-scope counters behind a grid barrier (the launch uses the resident grid only), and

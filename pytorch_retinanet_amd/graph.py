@@ -562,6 +562,9 @@ class CapturedTrainStep:
         crit = getattr(getattr(self.net, "retinanet_head", None), "losses", None)
         if getattr(crit, "matcher", "iou") != "iou":
             key += (("matcher", crit.matcher, int(crit.atss_topk)),)
+        # so is the box loss: an IoU kind adds ops.box_iou_loss's launches, and its weight is baked into them.  "smooth_l1" adds nothing.
+        if getattr(crit, "box_loss", "smooth_l1") != "smooth_l1":
+            key += (("box_loss", crit.box_loss, float(crit.box_loss_weight)),)
         return key
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:

@@ -136,14 +136,18 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
     """Per-level head outputs (cls_0..cls_{L-1}, box_0..box_{L-1}) -> f32[2]; no concatenation."""
 
     @staticmethod
-    def forward(ctx, anchors, gt_boxes, gt_labels, gt_off, params, fg_thr, bg_thr, L, ahead, *levels):
+    def forward(ctx, anchors, gt_boxes, gt_labels, gt_off, params, fg_thr, bg_thr, L, ahead, box_loss, *levels):
+        """``box_loss``: None (K3's smooth-L1 as it is) or (kind, weight): ``ops.box_iou_loss`` then runs right behind K3, on the same
+        stream and with the same gradient pre-scale, and replaces the regression loss and the matched rows' box gradients."""
         cls_levels, box_levels = levels[:L], levels[L:]
         B = cls_levels[0].shape[0]
-        want_grad = any(ctx.needs_input_grad[9:])
+        want_grad = any(ctx.needs_input_grad[10:])
         fused = None
         pack = None
         if isinstance(ahead, GtPack):
             pack, ahead = ahead, None
+        if ahead is not None and not isinstance(ahead, MatchAhead) and box_loss is not None:
+            raise ValueError("the fused matcher (RN_FUSE_MATCH=1) keeps its match codes on chip: an IoU box loss needs K2's or ATSS's buffers")
         if ahead is not None and not isinstance(ahead, MatchAhead):
             # ``ahead`` = the largest per-image GT count: K2 runs INSIDE the loss kernel (one launch; box_utils.py:51-80 in the
             # prologue of rn_loss_match_fwd_bwd_levels) unless the library declines the shape
@@ -167,6 +171,9 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
                                                        num_fg, params, want_grad, special=special, in_kernel_finalize=IN_KERNEL_FINALIZE,
                                                        grad_prescale=pre, form=k3_form(int(gt_boxes.shape[0]), B) if special is not None else None)
             ctx.prescale = pre
+            if box_loss is not None:
+                ops.box_iou_loss(box_levels, anchors, gt_boxes, gt_off, matches, num_fg, special, loss, gbox, box_loss[0],
+                                 reg_w=tuple(params.reg_w), weight=box_loss[1], grad_prescale=pre)
         ctx.grads = (gcls, gbox)
         ctx.meta = [(c.shape, c.dtype) for c in cls_levels] + [(b.shape, b.dtype) for b in box_levels]
         # two scalar outputs (views of the kernel's f32[2]): backward then receives the two upstream scalars directly, without
@@ -188,7 +195,7 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
             g0, g1 = g0.float() / pre.reshape(1), g1.float() / pre.reshape(1)
         ops.scale_inplace_batched(list(gcls) + list(gbox), [g0] * len(gcls) + [g1] * len(gbox))      # one launch
         outs = [t.view(shape) if t.dtype == dt else t.to(dt).view(shape) for t, (shape, dt) in zip(list(gcls) + list(gbox), ctx.meta)]
-        return (None,) * 9 + tuple(outs)
+        return (None,) * 10 + tuple(outs)
 
 
 def _max_gt_per_image(targets) -> int:
@@ -219,15 +226,69 @@ def _check_matcher(matcher: str, atss_topk: int) -> None:
                          "there is no ATSS form of the fused kernel; unset RN_FUSE_MATCH or use matcher=\"iou\"")
 
 
+def _check_box_loss(box_loss: str, box_loss_weight: float) -> None:
+    if box_loss not in ops.BOX_LOSSES:
+        raise ValueError(f"box_loss must be one of {ops.BOX_LOSSES}, got {box_loss!r}")
+    if not float(box_loss_weight) > 0.0:
+        raise ValueError(f"box_loss_weight must be positive, got {box_loss_weight!r}")
+    if box_loss != "smooth_l1" and FUSE_MATCH:
+        raise ValueError(f'RN_FUSE_MATCH=1 keeps the match codes inside the loss kernel and cannot be combined with box_loss="{box_loss}": '
+                         'the IoU box losses read the matcher\'s buffers; unset RN_FUSE_MATCH or use box_loss="smooth_l1"')
+
+
+def box_iou_loss_reference(deltas: Tensor, anchors: Tensor, gt: Tensor, kind: str, reg_w: Sequence[float] = BBOX_REG_WEIGHTS) -> Tensor:
+    """The rule of ``rn_box_iou_loss`` (include/retinanet_hip.h, steps 1-3) as differentiable torch code in ``deltas``' dtype: the row
+    losses l [N] of N matched rows -- ``deltas`` [N,4] the head's outputs, ``anchors`` / ``gt`` [N,4] each row's anchor and GT box.
+    Autograd through it is the gradient of step 4: every min / max is a ``torch.where`` on the strict comparison that selects the
+    predicted coordinate, so a tie goes to the GT coordinate and carries no derivative; a slot above the clip has zero gradient.
+    The per-image scale, the weight and the sum (steps 4-5) are the caller's."""
+    if kind not in ops.BOX_LOSS_KINDS:
+        raise ValueError(f"kind must be one of {tuple(ops.BOX_LOSS_KINDS)}, got {kind!r}")
+    dt = deltas.dtype
+    an, g = anchors.to(dt), gt.to(dt)
+    t = deltas / torch.tensor([float(v) for v in reg_w], dtype=dt, device=deltas.device)
+    acx, acy, aw, ah = (an[:, 0] + an[:, 2]) / 2, (an[:, 1] + an[:, 3]) / 2, an[:, 2] - an[:, 0], an[:, 3] - an[:, 1]
+    cx, cy = aw * t[:, 0] + acx, ah * t[:, 1] + acy
+    clip = torch.full_like(t[:, 2], ops.BOX_XFORM_CLIP)
+    sw, sh = torch.where(t[:, 2] > clip, clip, t[:, 2]), torch.where(t[:, 3] > clip, clip, t[:, 3])
+    w, h = aw * torch.exp(sw), ah * torch.exp(sh)
+    px1, py1, px2, py2 = cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2
+    gx1, gy1, gx2, gy2 = g[:, 0], g[:, 1], g[:, 2], g[:, 3]
+    zero = torch.zeros_like(px1)
+    iw = torch.where(px2 < gx2, px2, gx2) - torch.where(px1 > gx1, px1, gx1)
+    ih = torch.where(py2 < gy2, py2, gy2) - torch.where(py1 > gy1, py1, gy1)
+    iw, ih = torch.where(iw > 0, iw, zero), torch.where(ih > 0, ih, zero)
+    inter = iw * ih
+    union = (w * h + (gx2 - gx1) * (gy2 - gy1)) - inter
+    iou = torch.where(union > 0, inter / torch.where(union > 0, union, torch.ones_like(union)), zero)
+    ew = torch.where(px2 > gx2, px2, gx2) - torch.where(px1 < gx1, px1, gx1)
+    eh = torch.where(py2 > gy2, py2, gy2) - torch.where(py1 < gy1, py1, gy1)
+    if kind == "giou":
+        c = ew * eh
+        pen = torch.where(c > 0, (c - union) / torch.where(c > 0, c, torch.ones_like(c)), zero)
+    else:
+        c2 = ew * ew + eh * eh
+        dx, dy = cx - (gx1 + gx2) / 2, cy - (gy1 + gy2) / 2
+        pen = torch.where(c2 > 0, (dx * dx + dy * dy) / torch.where(c2 > 0, c2, torch.ones_like(c2)), zero)
+    return (1 - iou) + pen
+
+
 class RetinaNetLosses(nn.Module):
-    def __init__(self, num_classes: int, matcher: str = "iou", atss_topk: int = 9, cells=None) -> None:
+    def __init__(self, num_classes: int, matcher: str = "iou", atss_topk: int = 9, cells=None, box_loss: str = "smooth_l1",
+                 box_loss_weight: float = 1.0) -> None:
         """``matcher``: "iou" (K2: the reference's max-IoU rule with its 0.5 / 0.4 thresholds) or "atss" (``ops.atss_match``: a
         per-object threshold from the IoU statistics of the ``atss_topk`` nearest locations of every pyramid level; no ignored band).
         ATSS applies to the per-level path (``forward_levels`` / ``match_ahead``, what ``Retinanet.forward`` runs; ``forward`` /
         ``calc_loss`` on concatenated outputs raise a ``ValueError`` with it); ``cells``: anchors
-        per grid location (an int or one per level; ``Retinanet`` passes its anchor generator's), default 9."""
+        per grid location (an int or one per level; ``Retinanet`` passes its anchor generator's), default 9.
+        ``box_loss``: "smooth_l1" (the reference's encode-then-smooth-L1 inside K3; no further launch) or "giou" / "diou"
+        (``ops.box_iou_loss`` behind K3: the loss of the decoded box against its GT box, times ``box_loss_weight``).  Like ATSS the IoU
+        kinds apply to the per-level path and refuse ``RN_FUSE_MATCH=1``.  Inference is not affected: detections are still decoded by
+        the reference-compatible K4."""
         super().__init__()
         _check_matcher(matcher, atss_topk)
+        _check_box_loss(box_loss, box_loss_weight)
+        self.box_loss, self.box_loss_weight = box_loss, float(box_loss_weight)
         self.matcher, self.atss_topk = matcher, int(atss_topk)
         self.cells = 9 if cells is None else cells
         self.n_c = num_classes
@@ -261,6 +322,9 @@ class RetinaNetLosses(nn.Module):
         if self.matcher == "atss":
             # (the concatenated outputs carry no level layout, and matching them with K2 instead would be a silent change of rule)
             raise ValueError('matcher="atss" runs on the per-level head outputs: use forward_levels / Retinanet.forward, not forward / calc_loss')
+        if self.box_loss != "smooth_l1":
+            # (the concatenated path has no flag words, and answering with smooth-L1 instead would be a silent change of loss)
+            raise ValueError(f'box_loss="{self.box_loss}" runs on the per-level head outputs: use forward_levels / Retinanet.forward, not forward / calc_loss')
         dev = cls.device
         counts = [int(b.reshape(-1, 4).shape[0]) for b in boxes]
         gt_boxes = torch.cat([b.reshape(-1, 4).to(device=dev, dtype=torch.float32) for b in boxes]) \
@@ -350,6 +414,10 @@ class RetinaNetLosses(nn.Module):
         if isinstance(targets, ops.PackedGT) and targets.B != int(cls_levels[0].shape[0]):
             raise ValueError(f"packed GT of {targets.B} images for a batch of {int(cls_levels[0].shape[0])}")
         atss = self.matcher == "atss"
+        box_loss = None
+        if self.box_loss != "smooth_l1":
+            _check_box_loss(self.box_loss, self.box_loss_weight)
+            box_loss = (self.box_loss, self.box_loss_weight)
         if ahead is not None:
             gt_boxes, gt_labels, gt_off, anchors_t = ahead.gt_boxes, ahead.gt_labels, ahead.gt_off, ahead.anchors
         elif atss:
@@ -377,7 +445,7 @@ class RetinaNetLosses(nn.Module):
             elif nfg0 is not None:
                 ahead = GtPack(nfg0)
         out = _FusedDenseHeadLossLevels.apply(anchors_t, gt_boxes, gt_labels, gt_off, self._params(),
-                                              IOU_THRESHOLDS_FOREGROUND, IOU_THRESHOLDS_BACKGROUND, len(cls_levels), ahead,
+                                              IOU_THRESHOLDS_FOREGROUND, IOU_THRESHOLDS_BACKGROUND, len(cls_levels), ahead, box_loss,
                                               *cls_levels, *box_levels)
         return {"classification_loss": out[0], "regression_loss": out[1]}
 

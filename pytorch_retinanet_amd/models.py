@@ -53,12 +53,19 @@ class Retinanet(nn.Module):
         logger=None,
         matcher: Optional[str] = None,
         atss_topk: Optional[int] = None,
+        box_loss: Optional[str] = None,
+        box_loss_weight: Optional[float] = None,
     ) -> None:
         """``matcher``: how anchors are labelled -- None / "iou" (the reference's max-IoU rule, K2) or "atss" (``ops.atss_match``,
-        with ``atss_topk`` nearest locations per level and object, None -> 9); ``model: {matcher: atss}`` in the hparams."""
+        with ``atss_topk`` nearest locations per level and object, None -> 9); ``model: {matcher: atss}`` in the hparams.
+        ``box_loss``: the box regression loss -- None / "smooth_l1" (the reference's, inside K3) or "giou" / "diou" (``ops.box_iou_loss``
+        behind K3), times ``box_loss_weight`` (None -> 1.0); ``model: {box_loss: giou, box_loss_weight: 2.0}`` in the hparams.  Training
+        only: detections are decoded by the reference-compatible K4 whatever the loss."""
         super().__init__()
         matcher = ifnone(matcher, "iou")
         atss_topk = ifnone(atss_topk, 9)
+        box_loss = ifnone(box_loss, "smooth_l1")
+        box_loss_weight = ifnone(box_loss_weight, 1.0)
         num_classes = ifnone(num_classes, NUM_CLASSES)
         backbone_kind = ifnone(backbone_kind, BACKBONE)
         prior = ifnone(prior, PRIOR)
@@ -86,7 +93,7 @@ class Retinanet(nn.Module):
         self.anchor_generator = anchor_generator
         num_anchors = self.anchor_generator.num_cell_anchors[0]
         self.retinanet_head = RetinaNetHead(256, 256, num_anchors, num_classes, prior, matcher=matcher, atss_topk=atss_topk,
-                                            cells=self.anchor_generator.num_anchors)
+                                            cells=self.anchor_generator.num_anchors, box_loss=box_loss, box_loss_weight=box_loss_weight)
 
         self.score_thres = score_thres
         self.nms_thres = nms_thres

@@ -525,6 +525,60 @@ def loss_fwd_bwd_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tenso
     return out, gcls, gbox
 
 
+# ---- IoU-type box regression losses -----------------------------------------------------------------------------------------
+BOX_LOSSES = ("smooth_l1", "giou", "diou")
+BOX_LOSS_KINDS = {"giou": 1, "diou": 2}                       # RN_BOX_LOSS_GIOU / RN_BOX_LOSS_DIOU
+BOX_XFORM_CLIP = float(torch.tensor(4.135166556742356, dtype=torch.float32))      # RN_BOX_XFORM_CLIP: the fp32 nearest log(1000 / 16)
+
+
+def box_iou_loss(box_levels: Sequence[Tensor], anchors: Tensor, gt_boxes: Tensor, gt_off: Tensor, matches: Tensor, num_fg: Tensor,
+                 special: Tensor, loss: Tensor, gbox: Optional[Sequence[Tensor]], kind: str, reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0),
+                 weight: float = 1.0, grad_prescale: Optional[Tensor] = None) -> Tensor:
+    """GIoU / DIoU on the matched rows, BEHIND ``loss_fwd_bwd_levels`` on the same stream (``rn_box_iou_loss``; the rule:
+    include/retinanet_hip.h, restated by ``losses.box_iou_loss_reference``).  Takes K3's outputs -- ``loss`` f32[2] and the ``gbox``
+    list (None: value only) -- and the matcher's three buffers, and updates IN PLACE: ``loss[1]`` is replaced, the matched rows of
+    ``gbox`` are overwritten; ``loss[0]`` and every other row keep what K3 wrote.  ``box_levels``: the head's box outputs, [B,A_l,4]
+    in ``gbox``'s dtype; ``special`` (the flag words) is required: ``matches`` is read through them only.  ``grad_prescale`` as K3's.
+    No synchronisation, nothing cleared: capturable.  Returns ``loss``."""
+    if kind not in BOX_LOSS_KINDS:
+        raise ValueError(f"kind must be one of {tuple(BOX_LOSS_KINDS)}, got {kind!r}")
+    if not float(weight) > 0.0:
+        raise ValueError(f"weight must be positive, got {weight!r}")
+    L = len(box_levels)
+    if L == 0 or L > _lib.RN_MAX_LEVELS or (gbox is not None and len(gbox) != L):
+        raise ValueError("need 1..8 levels of box outputs (and as many gradient tensors)")
+    dev = _need_dev(*box_levels, anchors, gt_boxes, gt_off, matches, num_fg, special, loss, *(gbox or ()))
+    dt = box_levels[0].dtype if gbox is None else gbox[0].dtype
+    box_levels = [_c(b if b.dtype == dt else b.to(dt)) for b in box_levels]
+    B = int(box_levels[0].shape[0])
+    counts = [int(b.shape[1]) for b in box_levels]
+    for l, b in enumerate(box_levels):
+        if b.dim() != 3 or b.shape[0] != B or b.shape[2] != 4:
+            raise ValueError(f"bad box level shape {tuple(b.shape)}")
+        if gbox is not None and (gbox[l].shape != b.shape or gbox[l].dtype != dt or not gbox[l].is_contiguous()):
+            raise ValueError(f"gbox[{l}]: expected a contiguous {dt} {tuple(b.shape)}, got {gbox[l].dtype} {tuple(gbox[l].shape)}")
+    A = sum(counts)
+    anchors, bstride = _anchor_args(anchors, B, A)
+    gt_boxes = _c(gt_boxes.float()).reshape(-1, 4)
+    if special.dtype != torch.int64 or tuple(special.shape) != (B, (A + 63) // 64) or not special.is_contiguous():
+        raise ValueError(f"special-row words: expected int64 [{B}, {(A + 63) // 64}], got {special.dtype} {tuple(special.shape)}")
+    if matches.dtype != torch.int64 or matches.numel() != B * A or not matches.is_contiguous():
+        raise ValueError(f"matches: expected a contiguous int64 [{B}, {A}], got {matches.dtype} {tuple(matches.shape)}")
+    if loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
+        raise ValueError("loss: expected K3's float32[2]")
+    if grad_prescale is not None and not (grad_prescale.is_cuda and grad_prescale.dtype == torch.float32 and grad_prescale.numel() == 1):
+        raise TypeError("grad_prescale must be a CUDA fp32 scalar")
+    ws_bytes = lib.rn_box_iou_loss_workspace_bytes(B, A)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+    arr = lambda ts: (C.c_void_p * L)(*[t.data_ptr() for t in ts])
+    with torch.cuda.device(dev), _timed("box_iou_loss", dev):
+        check(lib.rn_box_iou_loss(arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(box_levels[0]), B,
+                                  _ptr(anchors), bstride, _ptr(gt_boxes), _ptr(gt_off), _ptr(matches), _ptr(special), _ptr(num_fg),
+                                  (C.c_float * 4)(*[float(v) for v in reg_w]), BOX_LOSS_KINDS[kind], float(weight), _ptr(grad_prescale),
+                                  _ptr(loss), arr(gbox) if gbox is not None else None, _ptr(ws), ws.numel(), _stream(dev)), "rn_box_iou_loss")
+    return loss
+
+
 # ---- K2 + K3 in one launch -------------------------------------------------------------------------------------------------
 # State words of rn_loss_match_fwd_bwd_levels (grid-barrier counter + per-image foreground counters): zero-filled ONCE, left
 # zero-filled by every completed call, never shared by two streams (one buffer per device and stream).  A hipGraph capture gets
