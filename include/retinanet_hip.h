@@ -556,6 +556,9 @@ int rn_conv3x3_wgrad_narrow(const void *g, const void *x, void *dw, int dtype, i
  * pixels outside the image read).  RN_EUNSUPPORTED for other C or dtypes. */
 int rn_conv3x3_narrow_forward(const void *x, const void *w, const float *bias, void *y, int dtype, int N, int H, int W, int C, int relu,
                               const void *zero_page, void *stream);
+/* Read-only: the output rows one workgroup of rn_conv3x3_narrow_forward walks (one band of one 128-pixel strip) at this shape on the
+ * current device -- ceil(H / rows) bands per strip, the last one may be shorter.  0 for a shape the entry point refuses. */
+int rn_conv3x3_narrow_rows_per_band(int N, int H, int W);
 
 /* n device-to-device copies (dsts[i] <- srcs[i], nbytes[i] bytes, non-overlapping) in one launch per 64: the inputs of a step
  * into the static buffers of its captured hipGraph (graph.CapturedTrainStep).  srcs / dsts / nbytes are HOST arrays. */

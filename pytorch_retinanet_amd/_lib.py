@@ -175,6 +175,7 @@ SIGNATURES = {
     "rn_conv3x3_wgrad_narrow_workspace_bytes": (_sz, [C.c_int, C.c_int]),
     "rn_conv3x3_wgrad_narrow": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _sz, _vp]),
     "rn_conv3x3_narrow_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "rn_conv3x3_narrow_rows_per_band": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "rn_copy_many": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "rn_gt_stage": (C.c_int, [_vp, _vp, C.POINTER(_i64), C.c_int, _vp, _vp, _i64, _vp, _vp, _vp]),
     "rn_gt_scale_packed": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), C.c_int, _i64, _i64, _vp]),

@@ -221,7 +221,25 @@ __global__ __launch_bounds__(N3_THREADS, 2) void conv3x3_narrow64_kernel(const N
     }
 }
 
+// Output rows a workgroup walks.  Two workgroups per CU: bands so that (images x strips x bands) fills them once (a band re-stages
+// two halo rows)
+int n3_rows_per_band(const int N, const int H, const int strips)
+{
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    int bands = (2 * cus) / (N * strips);
+    if (bands < 1) bands = 1;
+    if (bands > H) bands = H;
+    return (H + bands - 1) / bands;
+}
+
 }  // namespace
+
+RN_API int rn_conv3x3_narrow_rows_per_band(int N, int H, int W)
+{
+    if (N <= 0 || H <= 0 || W <= 0 || (int64_t)N * H * W >= ((int64_t)1 << 31)) return 0;
+    return n3_rows_per_band(N, H, (W + N3_TW - 1) / N3_TW);
+}
 
 // x, y [N][H][W][C] bf16 channels-last; w [C][3][3][C] (channels-last memory of [C, C, 3, 3]); C = 64.
 RN_API int rn_conv3x3_narrow_forward(const void *x, const void *w, const float *bias, void *y, int dtype, int N, int H, int W, int C, int relu,
@@ -236,13 +254,7 @@ RN_API int rn_conv3x3_narrow_forward(const void *x, const void *w, const float *
     a.zeros = zero_page; a.bias = bias; a.relu = (bias && relu) ? 1 : 0;
     a.N = N; a.H = H; a.W = W;
     a.strips = (W + N3_TW - 1) / N3_TW;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    // two workgroups per CU: bands so that (images x strips x bands) fills them once (a band re-stages two halo rows)
-    int bands = (2 * cus) / (N * a.strips);
-    if (bands < 1) bands = 1;
-    if (bands > H) bands = H;
-    a.rows_per_band = (H + bands - 1) / bands;
+    a.rows_per_band = n3_rows_per_band(N, H, a.strips);
     a.bands = (H + a.rows_per_band - 1) / a.rows_per_band;
 #define N3_LAUNCH(DT)                                                                                                                  \
     {   static rn::DynLdsOptIn opt_in = {};                                                                                            \
