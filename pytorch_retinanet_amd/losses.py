@@ -48,18 +48,15 @@ class _FusedDenseHeadLoss(torch.autograd.Function):
         return gcls.view(ctx.cls_shape), gbox.view(ctx.box_shape), None, None, None, None, None, None, None
 
 
-class GtPack:
-    "What ``ops.gt_pack`` prepared beside the GT arrays: the zeroed ``num_fg`` K2 adds into (None: K2 clears its own)."
-    __slots__ = ("num_fg",)
-
-    def __init__(self, num_fg):
-        self.num_fg = num_fg
-
-
 class MatchAhead:
-    """K2's results, launched ahead of the head convolutions on a side stream (``RetinaNetLosses.match_ahead``): the matcher needs
-    only the anchors and the GT boxes, so it does not have to sit on the critical path between the class-output conv and K3."""
-    __slots__ = ("gt_boxes", "gt_labels", "gt_off", "matches", "num_fg", "special", "done", "anchors")
+    """The one object between ``RetinaNetLosses`` and the loss Function: the anchors, the GT arrays as the library takes them (``B``
+    images) and the matcher (``rule``: the ``ops`` call and its arguments behind B), in one of three states --
+    launched ahead of the head convolutions on a side stream (``RetinaNetLosses.match_ahead``: the matcher needs only the anchors and
+    the GT boxes, so it does not have to sit between the class-output conv and K3): ``matches`` / ``num_fg`` / ``special`` are its
+    buffers and ``done`` the event the loss stream waits for;
+    to launch on the loss's stream: ``matches`` is None, ``num_fg0`` a zeroed i32 [B] the matcher adds into (None: it clears its own);
+    to try INSIDE the loss kernel first (``FUSE_MATCH``): as before, with ``max_gt`` the bound on the boxes per image (else None)."""
+    __slots__ = ("anchors", "gt_boxes", "gt_labels", "gt_off", "B", "num_fg0", "max_gt", "rule", "matches", "num_fg", "special", "done")
 
 
 _SIDE_STREAMS = {}
@@ -96,24 +93,8 @@ def k3_form(total_gt: int, B: int) -> int:
 # 0.25 p^3 / (num_fg B) ~ 4e-10, below fp16's smallest subnormal (6e-8): stored unscaled it is zero whatever backward multiplies in
 # later.  The reference's native-AMP run scales the fp32 loss first and keeps them (~2.6e-5 at a scale of 65 536).  backward then
 # multiplies by upstream / prescale (exactly 1 under ``scaler.scale(loss).backward()``).
-_GRAD_PRESCALE = None
-
-
-class grad_prescale:
+class grad_prescale(ops._Override):
     "``with grad_prescale(scaler_scale_tensor):`` -- fused loss calls inside the block pre-scale their gradients by it."
-
-    def __init__(self, scale: Optional[Tensor]):
-        self.scale = scale
-
-    def __enter__(self):
-        global _GRAD_PRESCALE
-        self.prev, _GRAD_PRESCALE = _GRAD_PRESCALE, self.scale
-        return self
-
-    def __exit__(self, *exc):
-        global _GRAD_PRESCALE
-        _GRAD_PRESCALE = self.prev
-        return False
 
 
 def scaler_prescale(scaler, dev) -> Optional[Tensor]:
@@ -136,43 +117,36 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
     """Per-level head outputs (cls_0..cls_{L-1}, box_0..box_{L-1}) -> f32[2]; no concatenation."""
 
     @staticmethod
-    def forward(ctx, anchors, gt_boxes, gt_labels, gt_off, params, fg_thr, bg_thr, L, ahead, box_loss, *levels):
-        """``box_loss``: None (K3's smooth-L1 as it is) or (kind, weight): ``ops.box_iou_loss`` then runs right behind K3, on the same
-        stream and with the same gradient pre-scale, and replaces the regression loss and the matched rows' box gradients."""
+    def forward(ctx, h, params, L, box_loss, *levels):
+        """``h``: the ``MatchAhead`` of the batch.  ``box_loss``: None (K3's smooth-L1 as it is) or (kind, weight): ``ops.box_iou_loss``
+        then runs right behind K3, on the same stream and with the same gradient pre-scale, and replaces the regression loss and the
+        matched rows' box gradients."""
         cls_levels, box_levels = levels[:L], levels[L:]
-        B = cls_levels[0].shape[0]
-        want_grad = any(ctx.needs_input_grad[10:])
+        dev = cls_levels[0].device
+        want_grad = any(ctx.needs_input_grad[4:])
         fused = None
-        pack = None
-        if isinstance(ahead, GtPack):
-            pack, ahead = ahead, None
-        if ahead is not None and not isinstance(ahead, MatchAhead) and box_loss is not None:
-            raise ValueError("the fused matcher (RN_FUSE_MATCH=1) keeps its match codes on chip: an IoU box loss needs K2's or ATSS's buffers")
-        if ahead is not None and not isinstance(ahead, MatchAhead):
-            # ``ahead`` = the largest per-image GT count: K2 runs INSIDE the loss kernel (one launch; box_utils.py:51-80 in the
-            # prologue of rn_loss_match_fwd_bwd_levels) unless the library declines the shape
-            fused = ops.loss_match_fwd_bwd_levels(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off, int(ahead), fg_thr,
-                                                  bg_thr, params, want_grad)
-            ahead = None
+        if h.matches is None and h.max_gt is not None:
+            # K2 runs INSIDE the loss kernel (one launch; box_utils.py:51-80 in the prologue of rn_loss_match_fwd_bwd_levels) unless
+            # the library declines the shape
+            fused = ops.loss_match_fwd_bwd_levels(cls_levels, box_levels, h.anchors, h.gt_boxes, h.gt_labels, h.gt_off, h.max_gt,
+                                                  *h.rule[1:], params, want_grad)
         ctx.prescale = None
         if fused is not None:
             loss, gcls, gbox = fused[0], fused[1], fused[2]
         else:
-            if ahead is not None:
-                if ahead.done is not None:
-                    torch.cuda.current_stream(cls_levels[0].device).wait_event(ahead.done)    # K2 ran beside the head convolutions
-                matches, num_fg, special = ahead.matches, ahead.num_fg, ahead.special
-            else:
-                # `matches` goes nowhere but into the loss kernel, which reads it through the flag words: K2 writes the flagged rows only
-                matches, num_fg, special = ops.iou_match(anchors, gt_boxes, gt_off, B, fg_thr, bg_thr, want_special=True, flagged_only=True,
-                                                         zeroed_num_fg=pack.num_fg if pack is not None else None)
-            pre = _GRAD_PRESCALE if (want_grad and _GRAD_PRESCALE is not None and _GRAD_PRESCALE.device == cls_levels[0].device) else None
-            loss, gcls, gbox = ops.loss_fwd_bwd_levels(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off, matches,
-                                                       num_fg, params, want_grad, special=special, in_kernel_finalize=IN_KERNEL_FINALIZE,
-                                                       grad_prescale=pre, form=k3_form(int(gt_boxes.shape[0]), B) if special is not None else None)
+            if h.matches is None:
+                _launch_matcher(h)
+            elif h.done is not None:
+                torch.cuda.current_stream(dev).wait_event(h.done)    # the matcher ran beside the head convolutions
+            pre = grad_prescale.value
+            if not (want_grad and pre is not None and pre.device == dev):
+                pre = None
+            loss, gcls, gbox = ops.loss_fwd_bwd_levels(cls_levels, box_levels, h.anchors, h.gt_boxes, h.gt_labels, h.gt_off, h.matches,
+                                                       h.num_fg, params, want_grad, special=h.special, in_kernel_finalize=IN_KERNEL_FINALIZE,
+                                                       grad_prescale=pre, form=k3_form(int(h.gt_boxes.shape[0]), h.B))
             ctx.prescale = pre
             if box_loss is not None:
-                ops.box_iou_loss(box_levels, anchors, gt_boxes, gt_off, matches, num_fg, special, loss, gbox, box_loss[0],
+                ops.box_iou_loss(box_levels, h.anchors, h.gt_boxes, h.gt_off, h.matches, h.num_fg, h.special, loss, gbox, box_loss[0],
                                  reg_w=tuple(params.reg_w), weight=box_loss[1], grad_prescale=pre)
         ctx.grads = (gcls, gbox)
         ctx.meta = [(c.shape, c.dtype) for c in cls_levels] + [(b.shape, b.dtype) for b in box_levels]
@@ -195,14 +169,29 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
             g0, g1 = g0.float() / pre.reshape(1), g1.float() / pre.reshape(1)
         ops.scale_inplace_batched(list(gcls) + list(gbox), [g0] * len(gcls) + [g1] * len(gbox))      # one launch
         outs = [t.view(shape) if t.dtype == dt else t.to(dt).view(shape) for t, (shape, dt) in zip(list(gcls) + list(gbox), ctx.meta)]
-        return (None,) * 10 + tuple(outs)
+        return (None,) * 4 + tuple(outs)
 
 
-def _max_gt_per_image(targets) -> int:
-    "The largest per-image GT count (packed GT: its capacity per image, an upper bound)."
+def _resolve_gt(targets, dev: Optional[torch.device]):
+    """Targets -- the reference's list of dicts or an ``ops.PackedGT`` -- as (gt_boxes, gt_labels, gt_off, zeroed num_fg or None, B,
+    bound on the GT boxes per image).  A list is packed by ``ops.gt_pack`` on ``dev`` (one launch; ``dev`` None: the two host figures
+    only, the arrays None).  Packed GT: the staged arrays as they are, ``gt_stage``'s zeroed ``num_fg``, and every host-side figure an
+    upper bound -- K2's kernel choice and K3's form (``k3_form``) see the R rows, the bound is the capacity per image; the kernels read
+    each image's range from ``gt_off``."""
     if isinstance(targets, ops.PackedGT):
-        return targets.cap_per_image
-    return max([int(t["boxes"].reshape(-1, 4).shape[0]) for t in targets] or [0])
+        return targets.gt_boxes, targets.gt_labels, targets.gt_off, targets.num_fg, targets.B, targets.cap_per_image
+    boxes = [t["boxes"] for t in targets]
+    arrays = (None,) * 4 if dev is None else ops.gt_pack(boxes, [t["labels"] for t in targets], dev)
+    return arrays + (len(boxes), max([b.numel() // 4 for b in boxes] or [0]))
+
+
+def _launch_matcher(h: MatchAhead, out: Optional[tuple] = None) -> None:
+    """The matcher of ``h.rule`` on the CURRENT stream, into ``h.matches`` / ``h.num_fg`` / ``h.special``.  ``out``: buffers the caller
+    allocated (``match_ahead``: they belong to its main stream), written in full.  Without it fresh ones, and ``matches`` written at the
+    flagged rows only: it goes nowhere but into the loss kernel, which reads it through the flag words."""
+    kw = dict(want_special=True, flagged_only=True) if out is None else dict(out=out)
+    match = ops.atss_match if h.rule[0] == "atss" else ops.iou_match
+    h.matches, h.num_fg, h.special = match(h.anchors, h.gt_boxes, h.gt_off, h.B, *h.rule[1:], zeroed_num_fg=h.num_fg0, **kw)
 
 
 def _stack_anchors(anchors) -> Tensor:
@@ -336,31 +325,26 @@ class RetinaNetLosses(nn.Module):
                                          self._params(), IOU_THRESHOLDS_FOREGROUND, IOU_THRESHOLDS_BACKGROUND)
 
     @staticmethod
-    def _gt_arrays(targets, dev):
-        return ops.gt_pack([t["boxes"] for t in targets], [t["labels"] for t in targets], dev)[:3]
-
-    @staticmethod
     def fuses_match(targets) -> bool:
         """``RN_FUSE_MATCH=1``: the matcher runs inside the loss kernel (one launch, ``rn_loss_match_fwd_bwd_levels``) when no image has
         more than 64 GT boxes (packed GT: when its capacity per image is at most 64).  Off by default: measured slower than K2 + K3
         (see ``FUSE_MATCH``)."""
-        return FUSE_MATCH and _max_gt_per_image(targets) <= 64
+        return FUSE_MATCH and _resolve_gt(targets, None)[5] <= 64
 
-    def _atss_level_sizes(self, level_sizes, A: int) -> List[int]:
-        if level_sizes is None:
-            raise ValueError('matcher="atss" needs the anchors per pyramid level (level_sizes)')
-        sizes = [int(v) for v in level_sizes]
-        if sum(sizes) != A:
-            raise ValueError(f"level sizes {sizes} do not sum to the {A} anchors")
-        return sizes
-
-    def _atss_now(self, anchors_t: Tensor, gt_boxes: Tensor, gt_labels: Tensor, gt_off: Tensor, B: int, level_sizes, num_fg0) -> MatchAhead:
-        "The ATSS matcher on the CURRENT stream, as a handle the loss Function reads like ``match_ahead``'s (nothing to wait for)."
-        _check_matcher(self.matcher, self.atss_topk)
+    def _handle(self, targets, anchors, level_sizes) -> MatchAhead:
+        """The handle of these targets and anchors: the GT resolved (``_resolve_gt``), the matcher named, nothing of it launched.
+        ``level_sizes`` (anchors per pyramid level) is what ``matcher="atss"`` needs beside them; ``ops.atss_match`` checks its sum."""
+        _check_matcher(self.matcher, self.atss_topk)              # (RN_FUSE_MATCH may have been switched on after construction)
         h = MatchAhead()
-        h.anchors, h.gt_boxes, h.gt_labels, h.gt_off, h.done = anchors_t, gt_boxes, gt_labels, gt_off, None
-        h.matches, h.num_fg, h.special = ops.atss_match(anchors_t, gt_boxes, gt_off, B, self._atss_level_sizes(level_sizes, int(anchors_t.shape[-2])),
-                                                        self.cells, self.atss_topk, want_special=True, flagged_only=True, zeroed_num_fg=num_fg0)
+        if self.matcher == "atss":
+            if level_sizes is None:
+                raise ValueError('matcher="atss" needs the anchors per pyramid level (level_sizes)')
+            h.rule = ("atss", list(level_sizes), self.cells, self.atss_topk)
+        else:
+            h.rule = ("iou", IOU_THRESHOLDS_FOREGROUND, IOU_THRESHOLDS_BACKGROUND)
+        h.anchors = _stack_anchors(anchors)
+        h.gt_boxes, h.gt_labels, h.gt_off, h.num_fg0, h.B, h.max_gt = _resolve_gt(targets, h.anchors.device)
+        h.matches = h.num_fg = h.special = h.done = None
         return h
 
     def match_ahead(self, targets: List[Dict[str, Tensor]], anchors, level_sizes=None) -> MatchAhead:
@@ -369,39 +353,22 @@ class RetinaNetLosses(nn.Module):
         class-output conv and K3.  Pass the result to ``forward_levels(..., ahead=...)``, which makes the loss kernel wait
         for it.  The outputs belong to the CALLING stream (allocated before the fork, consumed after the join).
         ``matcher="atss"``: the same with ``ops.atss_match``; ``level_sizes`` (anchors per pyramid level) is needed then."""
-        anchors = _stack_anchors(anchors)
-        dev = anchors.device
-        sizes = None
-        if self.matcher == "atss":
-            _check_matcher(self.matcher, self.atss_topk)
-            sizes = self._atss_level_sizes(level_sizes, int(anchors.shape[-2]))
-        h = MatchAhead()
-        h.anchors = anchors
-        packed = isinstance(targets, ops.PackedGT)
-        if packed:      # the staged arrays as they are; gt_stage zeroed num_fg (no clear launch)
-            h.gt_boxes, h.gt_labels, h.gt_off = targets.gt_boxes, targets.gt_labels, targets.gt_off
-        else:
-            h.gt_boxes, h.gt_labels, h.gt_off = self._gt_arrays(targets, dev)
-        B = targets.B if packed else len(targets)
-        h.matches, h.num_fg, h.special = ops.iou_match_outputs(B, int(anchors.shape[-2]), dev, want_num_fg=not packed)
-        if packed:
-            h.num_fg = targets.num_fg
+        h = self._handle(targets, anchors, level_sizes)
+        dev = h.anchors.device
+        h.max_gt = None
+        if not isinstance(targets, ops.PackedGT):
+            h.num_fg0 = None        # (only gt_stage's zeroed num_fg is used here; with a list the matcher clears its own)
+        out = ops.iou_match_outputs(h.B, int(h.anchors.shape[-2]), dev, want_num_fg=h.num_fg0 is None)
         main, side = torch.cuda.current_stream(dev), _side_stream(dev)
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            if sizes is not None:
-                ops.atss_match(anchors, h.gt_boxes, h.gt_off, B, sizes, self.cells, self.atss_topk,
-                               out=(h.matches, h.num_fg, h.special), zeroed_num_fg=h.num_fg if packed else None)
-            else:
-                ops.iou_match(anchors, h.gt_boxes, h.gt_off, B, IOU_THRESHOLDS_FOREGROUND, IOU_THRESHOLDS_BACKGROUND,
-                              out=(h.matches, h.num_fg, h.special), zeroed_num_fg=h.num_fg if packed else None)
+            _launch_matcher(h, out)
             h.done = torch.cuda.Event()
             h.done.record(side)
         # the tensors were allocated on the calling stream but are written / read on the side stream: if the head raises before
         # the loss joins the streams and the handle is dropped, the allocator must not hand the blocks out while K2 still runs
-        for t in (h.matches, h.num_fg, h.special, h.gt_boxes, h.gt_off, anchors):
-            if t is not None:
-                t.record_stream(side)
+        for t in (h.matches, h.num_fg, h.special, h.gt_boxes, h.gt_off, h.anchors):
+            t.record_stream(side)
         return h
 
     def forward_levels(self, targets: List[Dict[str, Tensor]], cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor],
@@ -410,43 +377,22 @@ class RetinaNetLosses(nn.Module):
         (the loss kernel reads the per-level conv outputs where they are).  ``ahead``: ``match_ahead``'s
         handle for these targets / anchors (K2 already in flight on a side stream).  ``targets`` may be an ``ops.PackedGT``
         (``ops.gt_stage``'s buffers; one loss call per staging: K2 adds into its zeroed ``num_fg``)."""
-        dev = cls_levels[0].device
-        if isinstance(targets, ops.PackedGT) and targets.B != int(cls_levels[0].shape[0]):
-            raise ValueError(f"packed GT of {targets.B} images for a batch of {int(cls_levels[0].shape[0])}")
-        atss = self.matcher == "atss"
         box_loss = None
         if self.box_loss != "smooth_l1":
             _check_box_loss(self.box_loss, self.box_loss_weight)
             box_loss = (self.box_loss, self.box_loss_weight)
-        if ahead is not None:
-            gt_boxes, gt_labels, gt_off, anchors_t = ahead.gt_boxes, ahead.gt_labels, ahead.gt_off, ahead.anchors
-        elif atss:
-            # the ATSS matcher fills K2's three buffers on this stream (the level sizes: the per-level head outputs'); K3 reads them
-            # through the handle as it reads match_ahead's.  Packed GT: the staged arrays and their zeroed num_fg as they are.
-            anchors_t = _stack_anchors(anchors)
-            if isinstance(targets, ops.PackedGT):
-                gt_boxes, gt_labels, gt_off, nfg0 = targets.gt_boxes, targets.gt_labels, targets.gt_off, targets.num_fg
+        h = ahead
+        if h is None:
+            # the matcher runs on this stream, from the Function (the level sizes: the per-level head outputs'); with RN_FUSE_MATCH it
+            # is tried inside the loss kernel first, and K2 clears its own num_fg if the library declines
+            h = self._handle(targets, anchors, [int(c.shape[1]) for c in cls_levels])
+            if cls_levels[0].is_cuda and FUSE_MATCH and h.max_gt <= 64:
+                h.num_fg0 = None
             else:
-                gt_boxes, gt_labels, gt_off, nfg0 = ops.gt_pack([t["boxes"] for t in targets], [t["labels"] for t in targets], dev)
-            ahead = self._atss_now(anchors_t, gt_boxes, gt_labels, gt_off, int(cls_levels[0].shape[0]),
-                                   [int(c.shape[1]) for c in cls_levels], nfg0)
-        elif isinstance(targets, ops.PackedGT):
-            # packed GT (graph.CapturedTrainStep's capacity mode): the staged arrays as they are.  Every host-side GT figure is an
-            # upper bound here: K2's kernel choice sees R rows (ops.iou_match passes gt_boxes.shape[0]), K3's form comes from R
-            # (k3_form), the fused form's max_gt is the capacity per image; the kernels read each image's range from gt_off
-            gt_boxes, gt_labels, gt_off = targets.gt_boxes, targets.gt_labels, targets.gt_off
-            anchors_t = _stack_anchors(anchors)
-            ahead = targets.cap_per_image if (cls_levels[0].is_cuda and self.fuses_match(targets)) else GtPack(targets.num_fg)
-        else:
-            gt_boxes, gt_labels, gt_off, nfg0 = ops.gt_pack([t["boxes"] for t in targets], [t["labels"] for t in targets], dev)
-            anchors_t = _stack_anchors(anchors)
-            if cls_levels[0].is_cuda and self.fuses_match(targets):
-                ahead = _max_gt_per_image(targets)      # (an int: see the Function)
-            elif nfg0 is not None:
-                ahead = GtPack(nfg0)
-        out = _FusedDenseHeadLossLevels.apply(anchors_t, gt_boxes, gt_labels, gt_off, self._params(),
-                                              IOU_THRESHOLDS_FOREGROUND, IOU_THRESHOLDS_BACKGROUND, len(cls_levels), ahead, box_loss,
-                                              *cls_levels, *box_levels)
+                h.max_gt = None
+        if h.B != int(cls_levels[0].shape[0]):       # (the kernels read gt_off[0 .. B] of the head outputs' B)
+            raise ValueError(f"targets (packed GT or a list) of {h.B} images for a batch of {int(cls_levels[0].shape[0])}")
+        out = _FusedDenseHeadLossLevels.apply(h, self._params(), len(cls_levels), box_loss, *cls_levels, *box_levels)
         return {"classification_loss": out[0], "regression_loss": out[1]}
 
     def calc_loss(self, anchors: Tensor, clas_pred: Tensor, bbox_pred: Tensor, clas_tgt: Tensor,

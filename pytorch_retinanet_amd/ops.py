@@ -54,6 +54,43 @@ class _timed:
         return False
 
 
+class _KernelEvents:
+    """With timing on, a pair of events that the LIBRARY records right around the streaming kernel of a loss launch (the dominant
+    kernel: what bench.py's roofline is quoted on; the ``_timed`` pair around the call also covers the one-block finalize).
+    ``args``: the two handles for the C call (None, None with timing off); ``note``: file the pair under timer names."""
+
+    def __init__(self, dev: torch.device):
+        self.pair = None
+        if _TIMERS is not None:
+            self.pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            for e in self.pair:
+                e.record(torch.cuda.current_stream(dev))      # creates the handles
+        self.args = tuple(e.cuda_event for e in self.pair) if self.pair else (None, None)
+
+    def note(self, *names: str) -> None:
+        if self.pair is not None:
+            for name in names:
+                _TIMERS.setdefault(name, []).append(self.pair)
+
+
+class _Override:
+    """``with name(value):`` -- a process-wide value that the block replaces and its exit puts back; ``name.value`` reads it (None
+    outside every block).  One subclass per value: ``use_atss_workspaces``, ``use_match_state``, ``losses.grad_prescale``."""
+    value = None
+
+    def __init__(self, value):
+        self.new = value
+
+    def __enter__(self):
+        cls = type(self)
+        self.prev, cls.value = cls.value, self.new
+        return self
+
+    def __exit__(self, *exc):
+        type(self).value = self.prev
+        return False
+
+
 def _need_dev(*tensors: Tensor) -> torch.device:
     dev = None
     for t in tensors:
@@ -271,29 +308,37 @@ def iou_match(anchors: Tensor, gt_boxes: Tensor, gt_off: Tensor, B: int, fg_thr:
     ``flagged_only`` (needs ``want_special``): ``matches`` is written only where a flag bit is set -- every other entry is
     UNINITIALISED; for results that go straight into ``loss_fwd_bwd_levels(special=...)`` (RN_MATCH_FLAGGED_ONLY).
     ``zeroed_num_fg``: an i32 [B] tensor that already holds zeros (``gt_pack``): used as ``num_fg``, no clear launch."""
-    dev = _need_dev(anchors, gt_boxes, gt_off)
-    A = anchors.shape[-2]
-    anchors, bstride = _anchor_args(anchors, B, A)
-    gt_boxes = _c(gt_boxes.float()).reshape(-1, 4)
     if not fg_thr > bg_thr:
         raise AssertionError("match_thr must be greater than back_thr")   # box_utils.py:66
-    if out is not None:
-        matches, num_fg, special = out
-    else:
-        matches, num_fg, special = iou_match_outputs(B, A, dev, want_num_fg and zeroed_num_fg is None, want_special)
-    flags = 0
-    if zeroed_num_fg is not None:
-        num_fg, flags = zeroed_num_fg, flags | RN_MATCH_NUM_FG_ZEROED
-    if flagged_only:
-        if special is None:
-            raise ValueError("flagged_only needs the flag words (want_special=True)")
-        flags |= RN_MATCH_FLAGGED_ONLY
+    dev, A, anchors, bstride, gt_boxes, (matches, num_fg, special), flags, ret = _match_args(
+        anchors, gt_boxes, gt_off, B, want_num_fg, want_special, out, flagged_only, zeroed_num_fg)
     with torch.cuda.device(dev), _timed("iou_match", dev):
         # gt_off[B] - gt_off[0] == the row count of gt_boxes (host-known): lets the library pick the batch-shaped kernel
         check(lib.rn_iou_match_special_ex(_ptr(anchors), bstride, _ptr(gt_boxes), _ptr(gt_off), B, A, fg_thr, bg_thr,
                                           _ptr(matches), _ptr(num_fg), _ptr(special), int(gt_boxes.shape[0]), flags, _stream(dev)),
               "rn_iou_match_special_ex")
-    return (matches, num_fg, special) if (want_special or out is not None) else (matches, num_fg)
+    return ret
+
+
+def _match_args(anchors: Tensor, gt_boxes: Tensor, gt_off: Tensor, B: int, want_num_fg: bool, want_special: bool, out: Optional[tuple],
+                flagged_only: bool, zeroed_num_fg: Optional[Tensor]):
+    """What ``iou_match`` and ``atss_match`` share: the converted inputs, the three output buffers (``out`` or fresh ones; ``zeroed_num_fg``
+    in place of ``num_fg``), the RN_MATCH_* flag bits and the tuple to return -- three tensors with ``want_special`` or ``out``, else two.
+    -> (dev, A, anchors, bstride, gt_boxes, (matches, num_fg, special), flags, ret)."""
+    dev = _need_dev(anchors, gt_boxes, gt_off)
+    A = anchors.shape[-2]
+    anchors, bstride = _anchor_args(anchors, B, A)
+    gt_boxes = _c(gt_boxes.float()).reshape(-1, 4)
+    matches, num_fg, special = out if out is not None else iou_match_outputs(B, A, dev, want_num_fg and zeroed_num_fg is None, want_special)
+    flags = 0
+    if zeroed_num_fg is not None:
+        num_fg, flags = zeroed_num_fg, RN_MATCH_NUM_FG_ZEROED
+    if flagged_only:
+        if special is None:
+            raise ValueError("flagged_only needs the flag words (want_special=True)")
+        flags |= RN_MATCH_FLAGGED_ONLY
+    bufs = (matches, num_fg, special)
+    return dev, A, anchors, bstride, gt_boxes, bufs, flags, bufs if (want_special or out is not None) else bufs[:2]
 
 
 def iou_match_outputs(B: int, A: int, dev: torch.device, want_num_fg: bool = True, want_special: bool = True):
@@ -310,25 +355,11 @@ def iou_match_outputs(B: int, A: int, dev: torch.device, want_num_fg: bool = Tru
 # layout (two streams must not share a table); a hipGraph capture uses the buffers of its own holder (``use_atss_workspaces``: a dict
 # owned by the captured entry, filled by that entry's eager steps, so the capture allocates -- and zero-fills -- nothing).
 _ATSS_WS = {}
-_ATSS_WS_OVERRIDE = None
 ATSS_MATCHERS = ("iou", "atss")
 
 
-class use_atss_workspaces:
+class use_atss_workspaces(_Override):
     "``with use_atss_workspaces(holder):`` -- ``atss_match`` calls inside the block keep their workspaces in the dict ``holder``."
-
-    def __init__(self, holder: Optional[dict]):
-        self.holder = holder
-
-    def __enter__(self):
-        global _ATSS_WS_OVERRIDE
-        self.prev, _ATSS_WS_OVERRIDE = _ATSS_WS_OVERRIDE, self.holder
-        return self
-
-    def __exit__(self, *exc):
-        global _ATSS_WS_OVERRIDE
-        _ATSS_WS_OVERRIDE = self.prev
-        return False
 
 
 def reset_atss_workspaces() -> None:
@@ -357,7 +388,7 @@ def atss_workspace(dev: torch.device, B: int, A: int, rows: int, level_sizes: Se
     """The (cached) workspace of ``atss_match`` for these shapes on the current stream: uint8, its conflict table zero.  Sized for a
     power-of-two row capacity >= ``rows``, so batches with other GT counts reuse it."""
     off, cl, L, lkey = atss_layout(level_sizes, cells, topk)
-    holder = _ATSS_WS_OVERRIDE
+    holder = use_atss_workspaces.value
     key = (dev.index, B, A) + lkey
     if holder is None:
         holder, key = _ATSS_WS, key + (torch.cuda.current_stream(dev).cuda_stream,)
@@ -386,30 +417,17 @@ def atss_match(anchors: Tensor, gt_boxes: Tensor, gt_off: Tensor, B: int, level_
     grid location (an int or one per level).  ``gt_boxes.shape[0]`` is the host's upper bound on the rows (packed GT: its capacity);
     the counts are read from ``gt_off`` on the device.  ``workspace``: a uint8 tensor from ``atss_workspace`` (default: the cached
     one for these shapes and the current stream); its conflict table is zero before and after the call."""
-    dev = _need_dev(anchors, gt_boxes, gt_off)
-    A = anchors.shape[-2]
-    anchors, bstride = _anchor_args(anchors, B, A)
-    gt_boxes = _c(gt_boxes.float()).reshape(-1, 4)
     off, cl, L, lkey = atss_layout(level_sizes, cells, topk)
-    if sum(lkey[0]) != A:
-        raise ValueError(f"level sizes {lkey[0]} do not sum to the {A} anchors")
-    if out is not None:
-        matches, num_fg, special = out
-    else:
-        matches, num_fg, special = iou_match_outputs(B, A, dev, want_num_fg and zeroed_num_fg is None, want_special)
-    flags = 0
-    if zeroed_num_fg is not None:
-        num_fg, flags = zeroed_num_fg, flags | RN_MATCH_NUM_FG_ZEROED
-    if flagged_only:
-        if special is None:
-            raise ValueError("flagged_only needs the flag words (want_special=True)")
-        flags |= RN_MATCH_FLAGGED_ONLY
+    if sum(lkey[0]) != anchors.shape[-2]:          # (the one place the level sizes are checked: a host argument, so before the device is)
+        raise ValueError(f"level sizes {lkey[0]} do not sum to the {anchors.shape[-2]} anchors")
+    dev, A, anchors, bstride, gt_boxes, (matches, num_fg, special), flags, ret = _match_args(
+        anchors, gt_boxes, gt_off, B, want_num_fg, want_special, out, flagged_only, zeroed_num_fg)
     rows = int(gt_boxes.shape[0])
     ws = workspace if workspace is not None else atss_workspace(dev, B, A, rows, lkey[0], lkey[1], topk)
     with torch.cuda.device(dev), _timed("atss_match", dev):
         check(lib.rn_atss_match(_ptr(anchors), bstride, _ptr(gt_boxes), _ptr(gt_off), B, A, off, cl, L, int(topk), _ptr(matches),
                                 _ptr(num_fg), _ptr(special), rows, flags, _ptr(ws), ws.numel(), _stream(dev)), "rn_atss_match")
-    return (matches, num_fg, special) if (want_special or out is not None) else (matches, num_fg)
+    return ret
 
 
 def make_loss_params(alpha: float, gamma: float, beta: float, logit_shift: float = 1.0, log_eps: float = 1e-8,
@@ -444,6 +462,65 @@ def loss_fwd_bwd(cls: Tensor, box: Tensor, anchors: Tensor, gt_boxes: Tensor, gt
     return out, gcls, gbox
 
 
+class _LevelArgs:
+    """What the per-level entry points share: ``box_levels[l]`` [B,A_l,4] and, unless None, ``cls_levels[l]`` [B,A_l,K] validated and
+    made contiguous in one dtype (``dt``, default the first level's), with the device of all tensors (``more``: further ones that must
+    live there), L, B, K (None without class outputs), A, ``counts`` (ctypes i64[L]), the fp32 anchors with their batch stride, and the
+    GT arrays as the library takes them."""
+
+    def __init__(self, cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off, *more, dt=None):
+        L = len(box_levels)
+        if L == 0 or L > _lib.RN_MAX_LEVELS or (cls_levels is not None and len(cls_levels) != L):
+            raise ValueError("need 1..8 levels of (cls, box) outputs")
+        self.dev = _need_dev(*(cls_levels or ()), *box_levels, anchors, gt_boxes, gt_labels, gt_off, *more)
+        first = (cls_levels or box_levels)[0]
+        if first.dim() != 3:
+            raise ValueError(f"bad level shape {tuple(first.shape)}")
+        dt = dt or first.dtype
+        self.L, self.B, self.K = L, int(first.shape[0]), int(first.shape[2]) if cls_levels is not None else None
+        counts = [int(t.shape[1]) for t in (cls_levels or box_levels)]
+        for l, b in enumerate(box_levels):
+            c = cls_levels[l] if cls_levels is not None else None
+            if b.shape != (self.B, counts[l], 4) or (c is not None and (c.shape != (self.B, counts[l], self.K) or c.dtype != dt)):
+                raise ValueError(f"bad level shapes {None if c is None else tuple(c.shape)} / {tuple(b.shape)}")
+        self.cls = None if cls_levels is None else [_c(c) for c in cls_levels]
+        self.box = [_c(b if b.dtype == dt else b.to(dt)) for b in box_levels]
+        self.code, self.A, self.counts = _dtype_code(self.box[0]), sum(counts), (C.c_int64 * L)(*counts)
+        self.anchors, self.bstride = _anchor_args(anchors, self.B, self.A)
+        self.gt_boxes = _c(gt_boxes.float()).reshape(-1, 4)
+        self.gt_labels = None if gt_labels is None else _c(gt_labels.to(torch.int64)).reshape(-1)
+        self.gt_off = gt_off
+
+    def arr(self, ts: Optional[Sequence[Tensor]]):
+        "The per-level base pointers of ``ts`` as a ctypes array (None for None)."
+        return None if ts is None else (C.c_void_p * self.L)(*[t.data_ptr() for t in ts])
+
+    def k3_head(self) -> tuple:
+        "The leading arguments of every per-level K3 entry point."
+        return (self.arr(self.cls), self.arr(self.box), self.counts, self.L, self.code, self.B, self.K, _ptr(self.anchors), self.bstride,
+                _ptr(self.gt_boxes), _ptr(self.gt_labels), _ptr(self.gt_off))
+
+    def k3_outputs(self, want_grad: bool):
+        "(loss f32[2], [grad_cls_l], [grad_box_l], workspace) of a K3 launch, uninitialised; the lists are None without ``want_grad``."
+        out = torch.empty((2,), dtype=torch.float32, device=self.dev)
+        gcls = [torch.empty_like(c) for c in self.cls] if want_grad else None
+        gbox = [torch.empty_like(b) for b in self.box] if want_grad else None
+        ws = torch.empty((lib.rn_loss_workspace_bytes(self.B, self.A, self.K),), dtype=torch.uint8, device=self.dev)
+        return out, gcls, gbox, ws
+
+
+def _check_special(special: Tensor, B: int, A: int) -> None:
+    if special.dtype != torch.int64 or tuple(special.shape) != (B, (A + 63) // 64) or not special.is_contiguous():
+        raise ValueError(f"special-row words: expected int64 [{B}, {(A + 63) // 64}], got {special.dtype} {tuple(special.shape)}")
+
+
+def _check_prescale(grad_prescale: Optional[Tensor], like: Tensor) -> None:
+    if grad_prescale is not None:
+        if not (grad_prescale.is_cuda and grad_prescale.dtype == torch.float32 and grad_prescale.numel() == 1):
+            raise TypeError("grad_prescale must be a CUDA fp32 scalar")
+        _need_dev(grad_prescale, like)
+
+
 def loss_fwd_bwd_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], anchors: Tensor, gt_boxes: Tensor,
                         gt_labels: Tensor, gt_off: Tensor, matches: Tensor, num_fg: Tensor, params: RnLossParams,
                         want_grad: bool = True, special: Optional[Tensor] = None, in_kernel_finalize: bool = False,
@@ -457,71 +534,31 @@ def loss_fwd_bwd_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tenso
     scale: fp16 class gradients of ~4e-10 would otherwise flush to zero).  ``form`` (``rn_loss_fwd_bwd_levels_rp``):
     ``LOSS_FORM_CHUNKS`` (default; the one-launch kernel repairing its special rows chunk by chunk), ``LOSS_FORM_LIST`` (one launch, the
     special rows of a wave through one compact list: faster from ~32 GT boxes per image on) or ``LOSS_FORM_REPAIR_PASS`` (= ``repair_pass``;
-    needs ``special``: a pure background stream + a repair kernel over the flag words; slower, kept for A/B)."""
+    needs ``special``: a pure background stream + a repair kernel over the flag words; slower, kept for A/B).
+    ``in_kernel_finalize=False`` has no effect once ``grad_prescale`` is set or ``form != LOSS_FORM_CHUNKS``: those calls go through the
+    ``_rp`` entry, which always finalizes in the kernel."""
     if form is None:
         form = LOSS_FORM_REPAIR_PASS if repair_pass else LOSS_FORM_CHUNKS
-    repair_pass = form == LOSS_FORM_REPAIR_PASS
-    L = len(cls_levels)
-    if L == 0 or L > _lib.RN_MAX_LEVELS or len(box_levels) != L:
-        raise ValueError("need 1..8 levels of (cls, box) outputs")
-    dev = _need_dev(*cls_levels, *box_levels, anchors, gt_boxes, gt_labels, gt_off, matches, num_fg)
-    dt = cls_levels[0].dtype
-    cls_levels = [_c(c) for c in cls_levels]
-    box_levels = [_c(b if b.dtype == dt else b.to(dt)) for b in box_levels]
-    B, _, K = cls_levels[0].shape
-    counts = [int(c.shape[1]) for c in cls_levels]
-    for c, b in zip(cls_levels, box_levels):
-        if c.dim() != 3 or b.shape != (B, c.shape[1], 4) or c.shape[0] != B or c.shape[2] != K or c.dtype != dt:
-            raise ValueError(f"bad level shapes {tuple(c.shape)} / {tuple(b.shape)}")
-    A = sum(counts)
-    anchors, bstride = _anchor_args(anchors, B, A)
-    gt_boxes = _c(gt_boxes.float()).reshape(-1, 4)
-    gt_labels = _c(gt_labels.to(torch.int64)).reshape(-1)
-    out = torch.empty((2,), dtype=torch.float32, device=dev)
-    gcls = [torch.empty_like(c) for c in cls_levels] if want_grad else None
-    gbox = [torch.empty_like(b) for b in box_levels] if want_grad else None
-    ws_bytes = lib.rn_loss_workspace_bytes(B, A, K)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    arr = lambda ts: (C.c_void_p * L)(*[t.data_ptr() for t in ts])
-    # with timing on, the library itself records a pair of events right around the streaming kernel (the dominant kernel:
-    # what bench.py's roofline is quoted on); the outer pair also covers the one-block finalize
-    k0 = k1 = None
-    if _TIMERS is not None:
-        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        k0.record(torch.cuda.current_stream(dev)); k1.record(torch.cuda.current_stream(dev))      # creates the handles
-    with torch.cuda.device(dev), _timed("loss_fwd_bwd" if want_grad else "loss_fwd", dev):
-        if special is not None and (special.dtype != torch.int64 or tuple(special.shape) != (B, (A + 63) // 64) or not special.is_contiguous()):
-            raise ValueError(f"special-row words: expected int64 [{B}, {(A + 63) // 64}], got {special.dtype} {tuple(special.shape)}")
-        if repair_pass and special is None:
-            raise ValueError("repair_pass needs the flag words of iou_match(want_special=True)")
-        if grad_prescale is not None:
-            if not (grad_prescale.is_cuda and grad_prescale.dtype == torch.float32 and grad_prescale.numel() == 1):
-                raise TypeError("grad_prescale must be a CUDA fp32 scalar")
-            _need_dev(grad_prescale, cls_levels[0])
+    a = _LevelArgs(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off, matches, num_fg)
+    if special is not None:
+        _check_special(special, a.B, a.A)
+    elif form == LOSS_FORM_REPAIR_PASS:
+        raise ValueError("repair_pass needs the flag words of iou_match(want_special=True)")
+    _check_prescale(grad_prescale, a.box[0])
+    out, gcls, gbox, ws = a.k3_outputs(want_grad)
+    ev = _KernelEvents(a.dev)
+    with torch.cuda.device(a.dev), _timed("loss_fwd_bwd" if want_grad else "loss_fwd", a.dev):
+        # the three entry points differ in what stands between the inputs and the outputs, and in the state words behind them
+        head = a.k3_head() + (_ptr(matches), _ptr(special), _ptr(num_fg), C.byref(params))
+        tail = (_ptr(out), a.arr(gcls), a.arr(gbox), _ptr(ws), ws.numel())
         if form != LOSS_FORM_CHUNKS or grad_prescale is not None:
-            check(lib.rn_loss_fwd_bwd_levels_rp(arr(cls_levels), arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(cls_levels[0]),
-                                                 B, K, _ptr(anchors), bstride, _ptr(gt_boxes), _ptr(gt_labels), _ptr(gt_off),
-                                                 _ptr(matches), _ptr(special), _ptr(num_fg), C.byref(params), _ptr(grad_prescale),
-                                                 int(form), _ptr(out),
-                                                 arr(gcls) if want_grad else None, arr(gbox) if want_grad else None,
-                                                 _ptr(ws), ws_bytes, _ptr(_match_state(dev)), _stream(dev), k0.cuda_event if k0 else None,
-                                                 k1.cuda_event if k1 else None), "rn_loss_fwd_bwd_levels_rp")
+            name, args = "rn_loss_fwd_bwd_levels_rp", head + (_ptr(grad_prescale), int(form)) + tail + (_ptr(_match_state(a.dev)),)
         elif in_kernel_finalize:
-            check(lib.rn_loss_fwd_bwd_levels_fin(arr(cls_levels), arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(cls_levels[0]),
-                                                  B, K, _ptr(anchors), bstride, _ptr(gt_boxes), _ptr(gt_labels), _ptr(gt_off),
-                                                  _ptr(matches), _ptr(special), _ptr(num_fg), C.byref(params), _ptr(out),
-                                                  arr(gcls) if want_grad else None, arr(gbox) if want_grad else None,
-                                                  _ptr(ws), ws_bytes, _ptr(_match_state(dev)), _stream(dev), k0.cuda_event if k0 else None,
-                                                  k1.cuda_event if k1 else None), "rn_loss_fwd_bwd_levels_fin")
+            name, args = "rn_loss_fwd_bwd_levels_fin", head + tail + (_ptr(_match_state(a.dev)),)
         else:
-            check(lib.rn_loss_fwd_bwd_levels_ex(arr(cls_levels), arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(cls_levels[0]),
-                                                 B, K, _ptr(anchors), bstride, _ptr(gt_boxes), _ptr(gt_labels), _ptr(gt_off),
-                                                 _ptr(matches), _ptr(special), _ptr(num_fg), C.byref(params), _ptr(out),
-                                                 arr(gcls) if want_grad else None, arr(gbox) if want_grad else None,
-                                                 _ptr(ws), ws_bytes, _stream(dev), k0.cuda_event if k0 else None,
-                                                 k1.cuda_event if k1 else None), "rn_loss_fwd_bwd_levels_ex")
-    if k0 is not None:
-        _TIMERS.setdefault("loss_stream_kernel" if want_grad else "loss_stream_kernel_fwd", []).append((k0, k1))
+            name, args = "rn_loss_fwd_bwd_levels_ex", head + tail
+        check(getattr(lib, name)(*args, _stream(a.dev), *ev.args), name)
+    ev.note("loss_stream_kernel" if want_grad else "loss_stream_kernel_fwd")
     return out, gcls, gbox
 
 
@@ -544,38 +581,26 @@ def box_iou_loss(box_levels: Sequence[Tensor], anchors: Tensor, gt_boxes: Tensor
         raise ValueError(f"kind must be one of {tuple(BOX_LOSS_KINDS)}, got {kind!r}")
     if not float(weight) > 0.0:
         raise ValueError(f"weight must be positive, got {weight!r}")
-    L = len(box_levels)
-    if L == 0 or L > _lib.RN_MAX_LEVELS or (gbox is not None and len(gbox) != L):
-        raise ValueError("need 1..8 levels of box outputs (and as many gradient tensors)")
-    dev = _need_dev(*box_levels, anchors, gt_boxes, gt_off, matches, num_fg, special, loss, *(gbox or ()))
-    dt = box_levels[0].dtype if gbox is None else gbox[0].dtype
-    box_levels = [_c(b if b.dtype == dt else b.to(dt)) for b in box_levels]
-    B = int(box_levels[0].shape[0])
-    counts = [int(b.shape[1]) for b in box_levels]
-    for l, b in enumerate(box_levels):
-        if b.dim() != 3 or b.shape[0] != B or b.shape[2] != 4:
-            raise ValueError(f"bad box level shape {tuple(b.shape)}")
-        if gbox is not None and (gbox[l].shape != b.shape or gbox[l].dtype != dt or not gbox[l].is_contiguous()):
-            raise ValueError(f"gbox[{l}]: expected a contiguous {dt} {tuple(b.shape)}, got {gbox[l].dtype} {tuple(gbox[l].shape)}")
-    A = sum(counts)
-    anchors, bstride = _anchor_args(anchors, B, A)
-    gt_boxes = _c(gt_boxes.float()).reshape(-1, 4)
-    if special.dtype != torch.int64 or tuple(special.shape) != (B, (A + 63) // 64) or not special.is_contiguous():
-        raise ValueError(f"special-row words: expected int64 [{B}, {(A + 63) // 64}], got {special.dtype} {tuple(special.shape)}")
+    if gbox is not None and len(gbox) != len(box_levels):
+        raise ValueError("need as many gradient tensors as levels of box outputs")
+    a = _LevelArgs(None, box_levels, anchors, gt_boxes, None, gt_off, matches, num_fg, special, loss, *(gbox or ()),
+                   dt=None if gbox is None else gbox[0].dtype)
+    B, A = a.B, a.A
+    for l, (b, g) in enumerate(zip(a.box, gbox or ())):
+        if g.shape != b.shape or g.dtype != b.dtype or not g.is_contiguous():
+            raise ValueError(f"gbox[{l}]: expected a contiguous {b.dtype} {tuple(b.shape)}, got {g.dtype} {tuple(g.shape)}")
+    _check_special(special, B, A)
     if matches.dtype != torch.int64 or matches.numel() != B * A or not matches.is_contiguous():
         raise ValueError(f"matches: expected a contiguous int64 [{B}, {A}], got {matches.dtype} {tuple(matches.shape)}")
     if loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
         raise ValueError("loss: expected K3's float32[2]")
-    if grad_prescale is not None and not (grad_prescale.is_cuda and grad_prescale.dtype == torch.float32 and grad_prescale.numel() == 1):
-        raise TypeError("grad_prescale must be a CUDA fp32 scalar")
-    ws_bytes = lib.rn_box_iou_loss_workspace_bytes(B, A)
-    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
-    arr = lambda ts: (C.c_void_p * L)(*[t.data_ptr() for t in ts])
-    with torch.cuda.device(dev), _timed("box_iou_loss", dev):
-        check(lib.rn_box_iou_loss(arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(box_levels[0]), B,
-                                  _ptr(anchors), bstride, _ptr(gt_boxes), _ptr(gt_off), _ptr(matches), _ptr(special), _ptr(num_fg),
-                                  (C.c_float * 4)(*[float(v) for v in reg_w]), BOX_LOSS_KINDS[kind], float(weight), _ptr(grad_prescale),
-                                  _ptr(loss), arr(gbox) if gbox is not None else None, _ptr(ws), ws.numel(), _stream(dev)), "rn_box_iou_loss")
+    _check_prescale(grad_prescale, loss)
+    ws = torch.empty((max(lib.rn_box_iou_loss_workspace_bytes(B, A), 16),), dtype=torch.uint8, device=a.dev)
+    with torch.cuda.device(a.dev), _timed("box_iou_loss", a.dev):
+        check(lib.rn_box_iou_loss(a.arr(a.box), a.counts, a.L, a.code, B, _ptr(a.anchors), a.bstride, _ptr(a.gt_boxes), _ptr(gt_off),
+                                  _ptr(matches), _ptr(special), _ptr(num_fg), (C.c_float * 4)(*[float(v) for v in reg_w]),
+                                  BOX_LOSS_KINDS[kind], float(weight), _ptr(grad_prescale), _ptr(loss), a.arr(gbox), _ptr(ws), ws.numel(),
+                                  _stream(a.dev)), "rn_box_iou_loss")
     return loss
 
 
@@ -587,28 +612,14 @@ def box_iou_loss(box_levels: Sequence[Tensor], anchors: Tensor, gt_boxes: Tensor
 MATCH_STATE_IMAGES = 4096
 RN_EUNSUPPORTED = -4
 _MATCH_STATE = {}
-_MATCH_STATE_OVERRIDE = None
 
 
 def new_match_state(dev: torch.device) -> Tensor:
     return torch.zeros((16 + MATCH_STATE_IMAGES,), dtype=torch.int32, device=dev)
 
 
-class use_match_state:
+class use_match_state(_Override):
     "``with use_match_state(buf):`` -- fused loss calls on ``buf.device`` inside the block use ``buf`` (graph capture)."
-
-    def __init__(self, buf: Optional[Tensor]):
-        self.buf = buf
-
-    def __enter__(self):
-        global _MATCH_STATE_OVERRIDE
-        self.prev, _MATCH_STATE_OVERRIDE = _MATCH_STATE_OVERRIDE, self.buf
-        return self
-
-    def __exit__(self, *exc):
-        global _MATCH_STATE_OVERRIDE
-        _MATCH_STATE_OVERRIDE = self.prev
-        return False
 
 
 def reset_match_state(dev: Optional[torch.device] = None) -> None:
@@ -620,8 +631,8 @@ def reset_match_state(dev: Optional[torch.device] = None) -> None:
 
 
 def _match_state(dev: torch.device) -> Tensor:
-    if _MATCH_STATE_OVERRIDE is not None and _MATCH_STATE_OVERRIDE.device == dev:
-        return _MATCH_STATE_OVERRIDE
+    if use_match_state.value is not None and use_match_state.value.device == dev:
+        return use_match_state.value
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
     st = _MATCH_STATE.get(key)
     if st is None:
@@ -636,52 +647,24 @@ def loss_match_fwd_bwd_levels(cls_levels: Sequence[Tensor], box_levels: Sequence
     written only when ``want_matches``.  -> (loss f32[2], [grad_cls_l], [grad_box_l], num_fg i32[B], matches or None), or
     ``None`` when the library declines the shape (more than 64 GT boxes in an image, ranges that do not fit its lists): the
     caller then runs ``iou_match`` + ``loss_fwd_bwd_levels``.  ``max_gt``: the largest per-image GT count (host-known)."""
-    L = len(cls_levels)
-    if L == 0 or L > _lib.RN_MAX_LEVELS or len(box_levels) != L:
-        raise ValueError("need 1..8 levels of (cls, box) outputs")
-    dev = _need_dev(*cls_levels, *box_levels, anchors, gt_boxes, gt_labels, gt_off)
     if not fg_thr > bg_thr:
         raise AssertionError("match_thr must be greater than back_thr")   # box_utils.py:66
-    B, _, K = cls_levels[0].shape
-    if max_gt > 64 or B > MATCH_STATE_IMAGES:
+    a = _LevelArgs(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off)
+    if max_gt > 64 or a.B > MATCH_STATE_IMAGES:
         return None
-    dt = cls_levels[0].dtype
-    cls_levels = [_c(c) for c in cls_levels]
-    box_levels = [_c(b if b.dtype == dt else b.to(dt)) for b in box_levels]
-    counts = [int(c.shape[1]) for c in cls_levels]
-    for c, b in zip(cls_levels, box_levels):
-        if c.dim() != 3 or b.shape != (B, c.shape[1], 4) or c.shape[0] != B or c.shape[2] != K or c.dtype != dt:
-            raise ValueError(f"bad level shapes {tuple(c.shape)} / {tuple(b.shape)}")
-    A = sum(counts)
-    anchors, bstride = _anchor_args(anchors, B, A)
-    gt_boxes = _c(gt_boxes.float()).reshape(-1, 4)
-    gt_labels = _c(gt_labels.to(torch.int64)).reshape(-1)
-    out = torch.empty((2,), dtype=torch.float32, device=dev)
-    gcls = [torch.empty_like(c) for c in cls_levels] if want_grad else None
-    gbox = [torch.empty_like(b) for b in box_levels] if want_grad else None
-    num_fg = torch.empty((B,), dtype=torch.int32, device=dev)
-    matches = torch.empty((B, A), dtype=torch.int64, device=dev) if want_matches else None
-    ws_bytes = lib.rn_loss_workspace_bytes(B, A, K)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    state = _match_state(dev)
-    arr = lambda ts: (C.c_void_p * L)(*[t.data_ptr() for t in ts])
-    k0 = k1 = None
-    if _TIMERS is not None:
-        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        k0.record(torch.cuda.current_stream(dev)); k1.record(torch.cuda.current_stream(dev))      # creates the handles
-    with torch.cuda.device(dev), _timed("loss_fwd_bwd" if want_grad else "loss_fwd", dev):
-        rc = lib.rn_loss_match_fwd_bwd_levels(arr(cls_levels), arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(cls_levels[0]),
-                                              B, K, _ptr(anchors), bstride, _ptr(gt_boxes), _ptr(gt_labels), _ptr(gt_off), int(max_gt),
-                                              fg_thr, bg_thr, _ptr(matches), _ptr(num_fg), C.byref(params), _ptr(out),
-                                              arr(gcls) if want_grad else None, arr(gbox) if want_grad else None, _ptr(ws), ws_bytes,
-                                              _ptr(state), state.numel() * 4, _stream(dev), k0.cuda_event if k0 else None,
-                                              k1.cuda_event if k1 else None)
+    out, gcls, gbox, ws = a.k3_outputs(want_grad)
+    num_fg = torch.empty((a.B,), dtype=torch.int32, device=a.dev)
+    matches = torch.empty((a.B, a.A), dtype=torch.int64, device=a.dev) if want_matches else None
+    state = _match_state(a.dev)
+    ev = _KernelEvents(a.dev)
+    with torch.cuda.device(a.dev), _timed("loss_fwd_bwd" if want_grad else "loss_fwd", a.dev):
+        rc = lib.rn_loss_match_fwd_bwd_levels(*a.k3_head(), int(max_gt), fg_thr, bg_thr, _ptr(matches), _ptr(num_fg), C.byref(params),
+                                              _ptr(out), a.arr(gcls), a.arr(gbox), _ptr(ws), ws.numel(), _ptr(state), state.numel() * 4,
+                                              _stream(a.dev), *ev.args)
         if rc == RN_EUNSUPPORTED:
             return None
         check(rc, "rn_loss_match_fwd_bwd_levels")
-    if k0 is not None:
-        _TIMERS.setdefault("loss_stream_kernel" if want_grad else "loss_stream_kernel_fwd", []).append((k0, k1))
-        _TIMERS.setdefault("loss_stream_kernel_fused_match", []).append((k0, k1))
+    ev.note("loss_stream_kernel" if want_grad else "loss_stream_kernel_fwd", "loss_stream_kernel_fused_match")
     return out, gcls, gbox, num_fg, matches
 
 

@@ -119,11 +119,11 @@ def test_fused_matching_refuses_atss(monkeypatch):
 
 
 def test_match_ahead_needs_the_level_sizes_for_atss():
-    from pytorch_retinanet_amd import losses
+    from pytorch_retinanet_amd import losses, ops
     with pytest.raises(ValueError, match="level"):
-        losses.RetinaNetLosses(3, matcher="atss")._atss_level_sizes(None, 10)
-    with pytest.raises(ValueError, match="sum"):
-        losses.RetinaNetLosses(3, matcher="atss")._atss_level_sizes([4, 4], 10)
+        losses.RetinaNetLosses(3, matcher="atss").match_ahead([], torch.zeros(10, 4))
+    with pytest.raises(ValueError, match="sum"):               # (the sizes themselves are checked in one place: where the matcher is launched)
+        ops.atss_match(torch.zeros(10, 4), torch.zeros(0, 4), torch.zeros(1, dtype=torch.int32), 0, [4, 4], 9)
 
 
 def test_the_concatenated_path_refuses_atss_instead_of_matching_by_iou():
