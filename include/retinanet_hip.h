@@ -624,6 +624,31 @@ int rn_decode_clip(const void *deltas, int dtype, int B, int64_t A,
                    const float *anchors, int64_t anchor_bstride, const int32_t *image_hw,
                    const float reg_w[4], float *out, void *stream);
 
+/* ---- K4 with a decode kind (not in the reference) -----------------------------
+ * RN_BOX_DECODE_REFERENCE is K4 as above: the sizes come from exp(dx), exp(dy) (Q4) and d[2], d[3], reg_w[2], reg_w[3] are never
+ * read.  It stays the default of every entry point without a kind.  RN_BOX_DECODE_STANDARD is the inverse of bbox_2_activ, the
+ * meaning the training targets (K3's encode) and rn_box_iou_loss give the four outputs: step 1 of rn_box_iou_loss's rule.  The
+ * rule of the standard kind, for a row's deltas d[0..3] (widened from the I/O dtype to fp32 first) and its anchor an; every fp32
+ * step is one correctly rounded operation (no FMA contraction), expf is the device library's:
+ *   1. t[j] = d[j] / reg_w[j] for j = 0..3;
+ *   2. acx = (an.x1 + an.x2) / 2, acy = (an.y1 + an.y2) / 2, aw = an.x2 - an.x1, ah = an.y2 - an.y1;
+ *   3. cx = aw * t0 + acx, cy = ah * t1 + acy;
+ *   4. sw = t2 > CLIP ? CLIP : t2, sh = t3 > CLIP ? CLIP : t3 with CLIP = RN_BOX_XFORM_CLIP (a NaN stays NaN);
+ *   5. w = aw * expf(sw), h = ah * expf(sh);
+ *   6. the box is (cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2);
+ *   7. the rest of the chain is the reference kind's: clip to the image, remove_small_boxes, NMS, top-k.
+ * Steps 2, 3, 5 and 6 are the reference kind's operations in its operand order, so a row with d[2] == d[0], d[3] == d[1],
+ * reg_w[2] == reg_w[0], reg_w[3] == reg_w[1] and t2, t3 <= CLIP gives the reference kind's bits.  What follows from the rule:
+ * a NaN box fails `>= min_box`; a box at dw = -inf has width 0; a box whose centre is +-inf clips to zero width (both corners
+ * land on the same image edge) -- all three die in the size filter, as they do with the reference kind; and w <= 62.5 * aw.
+ * rn_decode_clip_kind: rn_decode_clip with `decode` one of the two kinds.  RN_EINVAL also for an unknown kind, and for the
+ * standard kind when a reg_w[j] is not finite and > 0 (the reference kind checks no weight, as before). */
+#define RN_BOX_DECODE_REFERENCE 0
+#define RN_BOX_DECODE_STANDARD 1
+int rn_decode_clip_kind(const void *deltas, int dtype, int B, int64_t A,
+                        const float *anchors, int64_t anchor_bstride, const int32_t *image_hw,
+                        const float reg_w[4], int decode, float *out, void *stream);
+
 /* ---- conv epilogue: bias (+ ReLU) (+ position mask), channels-last ------------------------------
  * y = mask[m % HW] ? act(x + bias[c]) : 0 on [M][C] activations (C % 8 == 0), act = ReLU when relu != 0;
  * replaces the bias add + nn.ReLU pairs of the reference's head towers (retinanet/layers.py:143-171,
@@ -1311,6 +1336,17 @@ int rn_detect_levels(const void *const *cls_levels, const void *const *box_level
                      const rn_detect_params *params, int64_t max_candidates,
                      float *out_boxes, float *out_scores, int64_t *out_labels, int32_t *out_count,
                      int32_t *out_status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* rn_detect_levels with the box decode `decode` (RN_BOX_DECODE_REFERENCE / RN_BOX_DECODE_STANDARD, the rule next to K4): the
+ * candidates' boxes are decoded by that kind; the score scan, the scatter, NMS and the top-k are the same launches.  rn_detect and
+ * rn_detect_levels are this call with RN_BOX_DECODE_REFERENCE.  RN_EINVAL also for an unknown kind, and for the standard kind
+ * when a params->reg_w[j] is not finite and > 0.  rn_detect_params is unchanged. */
+int rn_detect_levels_kind(const void *const *cls_levels, const void *const *box_levels,
+                          const int64_t *level_anchors, int L, int dtype, int B, int K,
+                          const float *anchors, int64_t anchor_bstride, const int32_t *image_hw,
+                          const rn_detect_params *params, int decode, int64_t max_candidates,
+                          float *out_boxes, float *out_scores, int64_t *out_labels, int32_t *out_count,
+                          int32_t *out_status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- the end of predict on the device (graph.CapturedPredict, csrc/finish.hip) ---------------------------------------------
  * rn_detect_finish_var: transform.postprocess for the batch -- the padded outputs of rn_detect / rn_detect_levels (out_boxes

@@ -110,6 +110,7 @@ SIGNATURES = {
     "rn_pw_wgrad_workspace_bytes": (_sz, [C.POINTER(RnPwConv)]),
     "rn_pw_conv_wgrad": (C.c_int, [C.POINTER(RnPwConv), _vp, _vp, _vp, C.POINTER(RnPwPrologue), C.POINTER(RnPwPrologue), _vp, _sz, _vp]),
     "rn_decode_clip": (C.c_int, [_vp, C.c_int, C.c_int, _i64, _vp, _i64, _vp, C.POINTER(_f32), _vp, _vp]),
+    "rn_decode_clip_kind": (C.c_int, [_vp, C.c_int, C.c_int, _i64, _vp, _i64, _vp, C.POINTER(_f32), C.c_int, _vp, _vp]),
     "rn_bias_act_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _i64, C.c_int, _i64, C.c_int, _vp]),
     "rn_bias_act_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, C.c_int, _i64, C.c_int, _vp, _sz, _vp]),
     "rn_conv3x3_canvas": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
@@ -233,6 +234,8 @@ SIGNATURES = {
                             _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rn_detect_levels": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp,
                                    C.POINTER(RnDetectParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rn_detect_levels_kind": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp,
+                                        C.POINTER(RnDetectParams), C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rn_detect_result_bytes": (_sz, [C.c_int, C.c_int]),
     "rn_detect_finish_var": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _sz, _vp]),
 }

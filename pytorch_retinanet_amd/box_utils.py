@@ -34,15 +34,63 @@ def bbox_2_activ(bboxes: Tensor, anchors: Tensor) -> Tensor:
     return torch.cat([centers, sizes], -1).mul_(b.new_tensor([BBOX_REG_WEIGHTS]))
 
 
-def activ_2_bbox(activations: Tensor, anchors: Tensor) -> Tensor:
+def activ_2_bbox(activations: Tensor, anchors: Tensor, decode: str = "reference") -> Tensor:
     """Model activations -> XYXY boxes (box_utils.py:37-48), HIP kernel K4.
 
-    Keeps the reference's behaviour: sizes come from ``exp(activations[..., :2])``
-    (SURVEY Q4), and the activations are divided IN PLACE by ``BBOX_REG_WEIGHTS``
+    ``decode="reference"`` keeps the reference's behaviour: sizes come from ``exp(activations[..., :2])``
+    (SURVEY Q4); ``decode="standard"`` takes them from ``activations[..., 2:]`` (the inverse of ``bbox_2_activ``,
+    ``decode_boxes_reference``).  Either way the activations are divided IN PLACE by ``BBOX_REG_WEIGHTS``
     (Q5; a value no-op with the default unit weights)."""
+    if decode not in ops.BOX_DECODES:
+        raise ValueError(f"decode must be one of {ops.BOX_DECODES}, got {decode!r}")
     if any(w != 1.0 for w in BBOX_REG_WEIGHTS):
         activations.div_(activations.new_tensor([BBOX_REG_WEIGHTS]))
-    return ops.decode_clip(activations, anchors, None)
+    return ops.decode_clip(activations, anchors, None, decode=decode)
+
+
+def decode_boxes_reference(deltas, anchors, reg_w=BBOX_REG_WEIGHTS, decode: str = "standard", image_hw=None):
+    """K4's two decodes restated in numpy fp32, operation for operation (the tests' yardstick; CPU tensors or arrays).  ``deltas``
+    [..., 4] (any float dtype: widened to fp32 first), ``anchors`` [A, 4] or ``deltas``' shape, ``reg_w`` four weights -> XYXY boxes,
+    a torch tensor when ``deltas`` is one, else a numpy array.  The rule (include/retinanet_hip.h, K4):
+      1. t[j] = d[j] / reg_w[j];
+      2. acx = (x1 + x2) / 2, acy likewise, aw = x2 - x1, ah = y2 - y1;
+      3. cx = aw * t0 + acx, cy = ah * t1 + acy;
+      4. "standard": sw = t2 > CLIP ? CLIP : t2, sh likewise (a NaN stays NaN); "reference": sw = t0, sh = t1 (Q4), no clip;
+      5. w = aw * exp(sw), h = ah * exp(sh);
+      6. the box is (cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2);
+    ``image_hw`` ([B, 2] rows of (h, w) for deltas [B, A, 4], or one (h, w)): then clipped to the image as K4 clips.  ``exp`` is
+    numpy's fp32 one, which may differ from the device library's by an ulp: compare with the K4 bar, not bit for bit."""
+    import numpy as np
+    if decode not in ops.BOX_DECODES:
+        raise ValueError(f"decode must be one of {ops.BOX_DECODES}, got {decode!r}")
+    as_torch = isinstance(deltas, Tensor)
+    d = deltas.detach().to(torch.float32).cpu().numpy() if as_torch else np.asarray(deltas, dtype=np.float32)
+    a = anchors.detach().to(torch.float32).cpu().numpy() if isinstance(anchors, Tensor) else np.asarray(anchors, dtype=np.float32)
+    rw = np.asarray([float(v) for v in reg_w], dtype=np.float32)
+    if rw.shape != (4,):
+        raise ValueError(f"reg_w must hold four weights, got {reg_w!r}")
+    two = np.float32(2.0)
+    with np.errstate(all="ignore"):
+        t = d / rw
+        acx, acy = (a[..., 0] + a[..., 2]) / two, (a[..., 1] + a[..., 3]) / two
+        aw, ah = a[..., 2] - a[..., 0], a[..., 3] - a[..., 1]
+        cx, cy = aw * t[..., 0] + acx, ah * t[..., 1] + acy
+        if decode == "standard":
+            clip = np.float32(ops.BOX_XFORM_CLIP)
+            sw, sh = np.where(t[..., 2] > clip, clip, t[..., 2]), np.where(t[..., 3] > clip, clip, t[..., 3])
+        else:
+            sw, sh = t[..., 0], t[..., 1]
+        w, h = aw * np.exp(sw), ah * np.exp(sh)
+        out = np.stack([cx - w / two, cy - h / two, cx + w / two, cy + h / two], -1).astype(np.float32)
+        if image_hw is not None:
+            hw = np.asarray(image_hw, dtype=np.int64).astype(np.float32)
+            hh, ww = (hw[..., 0], hw[..., 1]) if hw.ndim == 1 else (hw[:, 0][:, None], hw[:, 1][:, None])
+            zero = np.float32(0.0)
+            for j, hi in ((0, ww), (1, hh), (2, ww), (3, hh)):
+                v = out[..., j]
+                v = np.where(v < zero, zero, v)              # K4's clampf: a NaN fails both comparisons and stays
+                out[..., j] = np.where(v > hi, hi, v)
+    return torch.from_numpy(out) if as_torch else out
 
 
 def _iou_pairs_f32(t, a):

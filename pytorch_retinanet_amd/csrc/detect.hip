@@ -39,19 +39,29 @@ __device__ __forceinline__ float clampf(float v, const float lo, const float hi)
     return v > hi ? hi : v;
 }
 
+// KIND (compile time): RN_BOX_DECODE_REFERENCE -- the code above, which never reads d[2], d[3], rw.w[2] or rw.w[3] -- or
+// RN_BOX_DECODE_STANDARD (the numbered rule next to K4 in retinanet_hip.h): the sizes come from (dw, dh) clipped at
+// RN_BOX_XFORM_CLIP, i.e. two more divisions, two selects, and other arguments to the two expf; same operand order otherwise.
+template <int KIND>
 __device__ __forceinline__ rn::f32x4 decode_one(const float (&d)[4], const rn::f32x4 an, const RegW rw)
 {
     const float dx = d[0] / rw.w[0], dy = d[1] / rw.w[1];
     const float acx = (an.x + an.z) / 2.0f, acy = (an.y + an.w) / 2.0f;
     const float aw = an.z - an.x, ah = an.w - an.y;
     const float cx = aw * dx + acx, cy = ah * dy + acy;
-    const float w = aw * expf(dx), h = ah * expf(dy);
+    float sw = dx, sh = dy;
+    if constexpr (KIND == RN_BOX_DECODE_STANDARD) {
+        const float dw = d[2] / rw.w[2], dh = d[3] / rw.w[3];
+        sw = dw > RN_BOX_XFORM_CLIP ? RN_BOX_XFORM_CLIP : dw;     // (a NaN fails the comparison and stays)
+        sh = dh > RN_BOX_XFORM_CLIP ? RN_BOX_XFORM_CLIP : dh;
+    }
+    const float w = aw * expf(sw), h = ah * expf(sh);
     rn::f32x4 o;
     o.x = cx - w / 2.0f; o.y = cy - h / 2.0f; o.z = cx + w / 2.0f; o.w = cy + h / 2.0f;
     return o;
 }
 
-template <int DT>
+template <int DT, int KIND>
 // deltas: one pyramid level [B][A_l][4]; its anchors are rows base .. base+A_l of the A per image.
 __global__ __launch_bounds__(256) void decode_clip_kernel(const void *__restrict__ deltas, const int64_t A_l, const int64_t base,
                                                           const int64_t A, const int64_t R,
@@ -64,7 +74,7 @@ __global__ __launch_bounds__(256) void decode_clip_kernel(const void *__restrict
         const int64_t ai = base + (r - (int64_t)b * A_l);
         float d[4];
         delta4<DT>::ld(deltas, r, d);
-        rn::f32x4 o = decode_one(d, anchors[(int64_t)b * anchor_bstride4 + ai], rw);
+        rn::f32x4 o = decode_one<KIND>(d, anchors[(int64_t)b * anchor_bstride4 + ai], rw);
         if (image_hw) {
             const float hh = (float)image_hw[2 * b], ww = (float)image_hw[2 * b + 1];
             o.x = clampf(o.x, 0.0f, ww); o.z = clampf(o.z, 0.0f, ww);
@@ -74,6 +84,7 @@ __global__ __launch_bounds__(256) void decode_clip_kernel(const void *__restrict
     }
 }
 
+template <int KIND>
 int launch_decode(const void *deltas, const int dtype, const int B, const int64_t A_l, const int64_t base, const int64_t A,
                   const float *anchors, const int64_t anchor_bstride, const int32_t *image_hw, const RegW rw, float *out,
                   hipStream_t st)
@@ -83,12 +94,23 @@ int launch_decode(const void *deltas, const int dtype, const int B, const int64_
     if (blocks > 4096) blocks = 4096;
     const dim3 g((unsigned)blocks), blk(256);
     switch (dtype) {
-        case RN_F32: hipLaunchKernelGGL((decode_clip_kernel<RN_F32>), g, blk, 0, st, deltas, A_l, base, A, R, (const rn::f32x4 *)anchors, anchor_bstride / 4, image_hw, rw, (rn::f32x4 *)out); break;
-        case RN_BF16: hipLaunchKernelGGL((decode_clip_kernel<RN_BF16>), g, blk, 0, st, deltas, A_l, base, A, R, (const rn::f32x4 *)anchors, anchor_bstride / 4, image_hw, rw, (rn::f32x4 *)out); break;
-        case RN_F16: hipLaunchKernelGGL((decode_clip_kernel<RN_F16>), g, blk, 0, st, deltas, A_l, base, A, R, (const rn::f32x4 *)anchors, anchor_bstride / 4, image_hw, rw, (rn::f32x4 *)out); break;
+        case RN_F32: hipLaunchKernelGGL((decode_clip_kernel<RN_F32, KIND>), g, blk, 0, st, deltas, A_l, base, A, R, (const rn::f32x4 *)anchors, anchor_bstride / 4, image_hw, rw, (rn::f32x4 *)out); break;
+        case RN_BF16: hipLaunchKernelGGL((decode_clip_kernel<RN_BF16, KIND>), g, blk, 0, st, deltas, A_l, base, A, R, (const rn::f32x4 *)anchors, anchor_bstride / 4, image_hw, rw, (rn::f32x4 *)out); break;
+        case RN_F16: hipLaunchKernelGGL((decode_clip_kernel<RN_F16, KIND>), g, blk, 0, st, deltas, A_l, base, A, R, (const rn::f32x4 *)anchors, anchor_bstride / 4, image_hw, rw, (rn::f32x4 *)out); break;
         default: return RN_EINVAL;
     }
     RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
+// The decode kind of a call: RN_EINVAL for an unknown kind, and for the standard kind with a weight that is not finite and > 0
+// (the reference kind keeps accepting what it always did: it divides by reg_w[0] and reg_w[1] whatever they are).
+int check_decode(const int decode, const float *reg_w)
+{
+    if (decode != RN_BOX_DECODE_REFERENCE && decode != RN_BOX_DECODE_STANDARD) return RN_EINVAL;
+    if (decode == RN_BOX_DECODE_STANDARD)
+        for (int j = 0; j < 4; ++j)
+            if (!(reg_w[j] > 0.0f) || !(reg_w[j] < INFINITY)) return RN_EINVAL;
     return RN_OK;
 }
 
@@ -399,7 +421,7 @@ __device__ __forceinline__ int64_t seg_slot_of(const SegArgs &a, const int *s_sh
 
 // Pass 1 (grid: SEG_GROUPS x B): decode + clip + remove_small_boxes of this workgroup's slice of the candidates, boxes of the
 // survivors, DEAD_KEY over the rest, and the slice's per-class survivor counts -> hist[b][g][K].
-template <int DT>
+template <int DT, int KIND>
 __global__ __launch_bounds__(SEG_THREADS) void seg_count_kernel(const SegArgs a)
 {
     __shared__ int s_cnt[SEG_MAXK];
@@ -445,7 +467,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_count_kernel(const SegArgs a)
         for (int u = 0; u < SEG_UNROLL; ++u) {
             const int64_t i = i0 + u * SEG_THREADS + t;
             if (i >= sl.hi) continue;
-            rn::f32x4 o = decode_one(d[u], an[u], a.rw);
+            rn::f32x4 o = decode_one<KIND>(d[u], an[u], a.rw);
             if (a.image_hw) {
                 o.x = clampf(o.x, 0.0f, ww); o.z = clampf(o.z, 0.0f, ww);
                 o.y = clampf(o.y, 0.0f, hh); o.w = clampf(o.w, 0.0f, hh);
@@ -820,17 +842,26 @@ DetectWs carve(void *base, int B, int64_t A, int K, int64_t C)
 
 }  // namespace
 
-RN_API int rn_decode_clip(const void *deltas, int dtype, int B, int64_t A, const float *anchors, int64_t anchor_bstride,
-                          const int32_t *image_hw, const float reg_w[4], float *out, void *stream)
+RN_API int rn_decode_clip_kind(const void *deltas, int dtype, int B, int64_t A, const float *anchors, int64_t anchor_bstride,
+                               const int32_t *image_hw, const float reg_w[4], int decode, float *out, void *stream)
 {
     if (!deltas || !anchors || !out || !reg_w || B <= 0 || A <= 0) return RN_EINVAL;
+    if (check_decode(decode, reg_w) != RN_OK) return RN_EINVAL;
     const int64_t R = (int64_t)B * A;
     if (R >= ((int64_t)1 << 31)) return RN_EUNSUPPORTED;
     if (!rn::aligned(deltas, dtype == RN_F32 ? 16 : 8) || !rn::aligned(anchors, 16) || !rn::aligned(out, 16) ||
         (anchor_bstride & 3))
         return RN_EALIGN;
     RegW rw = {{reg_w[0], reg_w[1], reg_w[2], reg_w[3]}};
-    return launch_decode(deltas, dtype, B, A, 0, A, anchors, anchor_bstride, image_hw, rw, out, (hipStream_t)stream);
+    if (decode == RN_BOX_DECODE_STANDARD)
+        return launch_decode<RN_BOX_DECODE_STANDARD>(deltas, dtype, B, A, 0, A, anchors, anchor_bstride, image_hw, rw, out, (hipStream_t)stream);
+    return launch_decode<RN_BOX_DECODE_REFERENCE>(deltas, dtype, B, A, 0, A, anchors, anchor_bstride, image_hw, rw, out, (hipStream_t)stream);
+}
+
+RN_API int rn_decode_clip(const void *deltas, int dtype, int B, int64_t A, const float *anchors, int64_t anchor_bstride,
+                          const int32_t *image_hw, const float reg_w[4], float *out, void *stream)
+{
+    return rn_decode_clip_kind(deltas, dtype, B, A, anchors, anchor_bstride, image_hw, reg_w, RN_BOX_DECODE_REFERENCE, out, stream);
 }
 
 RN_API size_t rn_detect_workspace_bytes(int B, int64_t A, int K, int64_t max_candidates)
@@ -839,17 +870,18 @@ RN_API size_t rn_detect_workspace_bytes(int B, int64_t A, int K, int64_t max_can
     return carve(nullptr, B, A, K, max_candidates).total;
 }
 
-RN_API int rn_detect_levels(const void *const *cls_levels, const void *const *box_levels, const int64_t *level_anchors, int L,
-                            int dtype, int B, int K, const float *anchors, int64_t anchor_bstride, const int32_t *image_hw,
-                            const rn_detect_params *params, int64_t max_candidates, float *out_boxes, float *out_scores,
-                            int64_t *out_labels, int32_t *out_count, int32_t *out_status, void *workspace,
-                            size_t workspace_bytes, void *stream)
+RN_API int rn_detect_levels_kind(const void *const *cls_levels, const void *const *box_levels, const int64_t *level_anchors, int L,
+                                 int dtype, int B, int K, const float *anchors, int64_t anchor_bstride, const int32_t *image_hw,
+                                 const rn_detect_params *params, int decode, int64_t max_candidates, float *out_boxes,
+                                 float *out_scores, int64_t *out_labels, int32_t *out_count, int32_t *out_status, void *workspace,
+                                 size_t workspace_bytes, void *stream)
 {
     if (!cls_levels || !box_levels || !level_anchors || !anchors || !params || !out_boxes || !out_scores || !out_labels ||
         !out_count || !out_status || !workspace)
         return RN_EINVAL;
     if (L <= 0 || L > RN_MAX_LEVELS || B <= 0 || K <= 0 || max_candidates <= 0 || params->max_det <= 0) return RN_EINVAL;
     if (dtype != RN_F32 && dtype != RN_BF16 && dtype != RN_F16) return RN_EINVAL;
+    if (check_decode(decode, params->reg_w) != RN_OK) return RN_EINVAL;
     int64_t A = 0;
     for (int l = 0; l < L; ++l) {
         if (!cls_levels[l] || !box_levels[l] || level_anchors[l] <= 0) return RN_EINVAL;
@@ -936,10 +968,19 @@ RN_API int rn_detect_levels(const void *const *cls_levels, const void *const *bo
     {
         static_assert(SEG_GROUPS == 16, "carve() sizes the class histograms for 16 workgroups per image");
         const dim3 fg(SEG_GROUPS, (unsigned)B), fb(SEG_THREADS);
-        switch (dtype) {
-            case RN_F32: hipLaunchKernelGGL((seg_count_kernel<RN_F32>), fg, fb, 0, st, fa); hipLaunchKernelGGL((seg_scatter_kernel<RN_F32>), fg, fb, 0, st, fa); break;
-            case RN_BF16: hipLaunchKernelGGL((seg_count_kernel<RN_BF16>), fg, fb, 0, st, fa); hipLaunchKernelGGL((seg_scatter_kernel<RN_BF16>), fg, fb, 0, st, fa); break;
-            default: hipLaunchKernelGGL((seg_count_kernel<RN_F16>), fg, fb, 0, st, fa); hipLaunchKernelGGL((seg_scatter_kernel<RN_F16>), fg, fb, 0, st, fa); break;
+        constexpr int REF = RN_BOX_DECODE_REFERENCE, STD = RN_BOX_DECODE_STANDARD;
+        if (decode == STD) {                                  // (the scatter pass decodes nothing: one form)
+            switch (dtype) {
+                case RN_F32: hipLaunchKernelGGL((seg_count_kernel<RN_F32, STD>), fg, fb, 0, st, fa); hipLaunchKernelGGL((seg_scatter_kernel<RN_F32>), fg, fb, 0, st, fa); break;
+                case RN_BF16: hipLaunchKernelGGL((seg_count_kernel<RN_BF16, STD>), fg, fb, 0, st, fa); hipLaunchKernelGGL((seg_scatter_kernel<RN_BF16>), fg, fb, 0, st, fa); break;
+                default: hipLaunchKernelGGL((seg_count_kernel<RN_F16, STD>), fg, fb, 0, st, fa); hipLaunchKernelGGL((seg_scatter_kernel<RN_F16>), fg, fb, 0, st, fa); break;
+            }
+        } else {
+            switch (dtype) {
+                case RN_F32: hipLaunchKernelGGL((seg_count_kernel<RN_F32, REF>), fg, fb, 0, st, fa); hipLaunchKernelGGL((seg_scatter_kernel<RN_F32>), fg, fb, 0, st, fa); break;
+                case RN_BF16: hipLaunchKernelGGL((seg_count_kernel<RN_BF16, REF>), fg, fb, 0, st, fa); hipLaunchKernelGGL((seg_scatter_kernel<RN_BF16>), fg, fb, 0, st, fa); break;
+                default: hipLaunchKernelGGL((seg_count_kernel<RN_F16, REF>), fg, fb, 0, st, fa); hipLaunchKernelGGL((seg_scatter_kernel<RN_F16>), fg, fb, 0, st, fa); break;
+            }
         }
         RN_LAUNCH_CHECK();
     }
@@ -960,6 +1001,17 @@ RN_API int rn_detect_levels(const void *const *cls_levels, const void *const *bo
     return RN_OK;
 }
 
+RN_API int rn_detect_levels(const void *const *cls_levels, const void *const *box_levels, const int64_t *level_anchors, int L,
+                            int dtype, int B, int K, const float *anchors, int64_t anchor_bstride, const int32_t *image_hw,
+                            const rn_detect_params *params, int64_t max_candidates, float *out_boxes, float *out_scores,
+                            int64_t *out_labels, int32_t *out_count, int32_t *out_status, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    return rn_detect_levels_kind(cls_levels, box_levels, level_anchors, L, dtype, B, K, anchors, anchor_bstride, image_hw, params,
+                                 RN_BOX_DECODE_REFERENCE, max_candidates, out_boxes, out_scores, out_labels, out_count, out_status,
+                                 workspace, workspace_bytes, stream);
+}
+
 RN_API int rn_detect(const void *cls, const void *deltas, int dtype, int B, int64_t A, int K, const float *anchors,
                      int64_t anchor_bstride, const int32_t *image_hw, const rn_detect_params *params,
                      int64_t max_candidates, float *out_boxes, float *out_scores, int64_t *out_labels,
@@ -968,6 +1020,7 @@ RN_API int rn_detect(const void *cls, const void *deltas, int dtype, int B, int6
     if (!cls || !deltas || A <= 0) return RN_EINVAL;
     const void *c1[1] = {cls}, *d1[1] = {deltas};
     const int64_t a1[1] = {A};
-    return rn_detect_levels(c1, d1, a1, 1, dtype, B, K, anchors, anchor_bstride, image_hw, params, max_candidates, out_boxes,
-                            out_scores, out_labels, out_count, out_status, workspace, workspace_bytes, stream);
+    return rn_detect_levels_kind(c1, d1, a1, 1, dtype, B, K, anchors, anchor_bstride, image_hw, params, RN_BOX_DECODE_REFERENCE,
+                                 max_candidates, out_boxes, out_scores, out_labels, out_count, out_status, workspace,
+                                 workspace_bytes, stream);
 }

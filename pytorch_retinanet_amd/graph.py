@@ -891,9 +891,10 @@ class CapturedPredict:
         if mode is None:
             mode = self._walk()[0]
         # (what the pass takes BY VALUE: the eval short side, max_size, mean and std are kernel arguments of the plan and the transform,
-        # the thresholds and max_det of the detect chain)
+        # the thresholds, the box decode and max_det of the detect chain: a graph captured with one decode never serves the other)
         return ("predict", len(images), icls[0], icls[1], dtype, cl, images[0].device, mode, tr.staged_eval_short_side(), int(tr.max_size),
-                tuple(tr.image_mean), tuple(tr.image_std), net.score_thres, net.nms_thres, net.detections_per_img)
+                tuple(tr.image_mean), tuple(tr.image_std), net.score_thres, net.nms_thres, getattr(net, "box_decode", "reference"),
+                net.detections_per_img)
 
     def _weights_stamp(self) -> tuple:
         return self._walk()[1]

@@ -272,8 +272,8 @@ class RetinaNetLosses(nn.Module):
         per grid location (an int or one per level; ``Retinanet`` passes its anchor generator's), default 9.
         ``box_loss``: "smooth_l1" (the reference's encode-then-smooth-L1 inside K3; no further launch) or "giou" / "diou"
         (``ops.box_iou_loss`` behind K3: the loss of the decoded box against its GT box, times ``box_loss_weight``).  Like ATSS the IoU
-        kinds apply to the per-level path and refuse ``RN_FUSE_MATCH=1``.  Inference is not affected: detections are still decoded by
-        the reference-compatible K4."""
+        kinds apply to the per-level path and refuse ``RN_FUSE_MATCH=1``.  Inference is not affected by this argument: what decodes the
+        detections is ``Retinanet(box_decode=...)``, whose "standard" kind is the decode these losses train."""
         super().__init__()
         _check_matcher(matcher, atss_topk)
         _check_box_loss(box_loss, box_loss_weight)

@@ -55,13 +55,22 @@ class Retinanet(nn.Module):
         atss_topk: Optional[int] = None,
         box_loss: Optional[str] = None,
         box_loss_weight: Optional[float] = None,
+        box_decode: Optional[str] = None,
     ) -> None:
         """``matcher``: how anchors are labelled -- None / "iou" (the reference's max-IoU rule, K2) or "atss" (``ops.atss_match``,
         with ``atss_topk`` nearest locations per level and object, None -> 9); ``model: {matcher: atss}`` in the hparams.
         ``box_loss``: the box regression loss -- None / "smooth_l1" (the reference's, inside K3) or "giou" / "diou" (``ops.box_iou_loss``
         behind K3), times ``box_loss_weight`` (None -> 1.0); ``model: {box_loss: giou, box_loss_weight: 2.0}`` in the hparams.  Training
-        only: detections are decoded by the reference-compatible K4 whatever the loss."""
+        only: what decodes the detections is ``box_decode``, whatever the loss.
+        ``box_decode``: how ``predict`` / ``predict_staged`` / ``process_detections*`` turn the four box outputs into a box -- None /
+        "reference" (K4 with the reference's quirk Q4: the sizes come from ``exp(dx)``, ``exp(dy)`` and ``dw``, ``dh`` are never read) or
+        "standard" (the inverse of the training targets' encode, which is also what "giou" / "diou" optimise: sizes from ``dw``,
+        ``dh``, clipped at ``ops.BOX_XFORM_CLIP``); ``model: {box_decode: standard}`` in the hparams.  Stored as ``net.box_decode`` and
+        read at every call.  A model trained with "giou" / "diou" and inferred with the reference decode logs a warning here."""
         super().__init__()
+        box_decode = ifnone(box_decode, "reference")
+        if box_decode not in ops.BOX_DECODES:
+            raise ValueError(f"box_decode must be one of {ops.BOX_DECODES}, got {box_decode!r}")
         matcher = ifnone(matcher, "iou")
         atss_topk = ifnone(atss_topk, 9)
         box_loss = ifnone(box_loss, "smooth_l1")
@@ -99,6 +108,11 @@ class Retinanet(nn.Module):
         self.nms_thres = nms_thres
         self.detections_per_img = max_detections_per_images
         self.num_classes = num_classes
+        self.box_decode = box_decode
+        if box_loss in ("giou", "diou") and box_decode == "reference":
+            logger.warning(f'box_loss="{box_loss}" trains the box that box_decode="standard" decodes, but this model infers with the '
+                           'reference decode (sizes from exp(dx), exp(dy)): pass box_decode="standard" (model: {box_decode: standard}) '
+                           "to evaluate what was trained")
 
         logger.info(f"BACKBONE     : {backbone_kind}")
         logger.info(f"INPUT_PARAMS : MAX_SIZE={max_size}, MIN_SIZE={min_size}")
@@ -175,20 +189,21 @@ class Retinanet(nn.Module):
     def process_detections(self, outputs: Dict[str, Tensor], anchors: List[Tensor],
                            im_szs: List[Tuple[int, int]]) -> List[Dict[str, Tensor]]:
         """Raw head outputs -> per-image detections (models.py:160-243): one HIP call
-        (``rn_detect``) for the whole batch instead of B*K sequential NMS launches."""
+        (``rn_detect``) for the whole batch instead of B*K sequential NMS launches.  Boxes are decoded as ``self.box_decode`` says."""
         class_logits = outputs.pop("cls_preds")
         bboxes = outputs.pop("bbox_preds")
         if any(w != 1.0 for w in BBOX_REG_WEIGHTS):
             bboxes.div_(bboxes.new_tensor([BBOX_REG_WEIGHTS]))          # box_utils.py:43 (in place, Q5)
         return ops.detect(class_logits, bboxes, anchors, im_szs, self.score_thres, MIN_BOX_SIZE, self.nms_thres,
-                          self.detections_per_img)
+                          self.detections_per_img, decode=self.box_decode)
 
     def process_detections_levels(self, outputs: Dict[str, List[Tensor]], anchors: List[Tensor],
                                   im_szs: List[Tuple[int, int]]) -> List[Dict[str, Tensor]]:
         """``process_detections`` on the per-level head outputs of ``retinanet_head.forward_levels``: the scan
         and decode kernels read the five conv outputs in place (no ``torch.cat``, layers.py:195, :259)."""
         return ops.detect_levels(outputs["cls_levels"], outputs["bbox_levels"], anchors, im_szs, self.score_thres,
-                                 MIN_BOX_SIZE, self.nms_thres, self.detections_per_img, reg_w=BBOX_REG_WEIGHTS)
+                                 MIN_BOX_SIZE, self.nms_thres, self.detections_per_img, reg_w=BBOX_REG_WEIGHTS,
+                                 decode=self.box_decode)
 
     def predict(self, images: List[Tensor]) -> List[Dict[str, Tensor]]:
         """Detections in original image coordinates (models.py:245-272).  Like the
@@ -235,5 +250,5 @@ class Retinanet(nn.Module):
             outputs = self.retinanet_head.forward_levels(feature_maps)
             padded = ops.detect_levels(outputs["cls_levels"], outputs["bbox_levels"], anchors, None, self.score_thres, MIN_BOX_SIZE,
                                        self.nms_thres, self.detections_per_img, reg_w=BBOX_REG_WEIGHTS, max_candidates=max_candidates,
-                                       image_hw_dev=images.image_sizes_dev, padded=True)
+                                       image_hw_dev=images.image_sizes_dev, padded=True, decode=self.box_decode)
             return ops.detect_finish_var(*padded, staged.in_hw, images.image_sizes_dev)

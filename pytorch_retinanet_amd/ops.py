@@ -1375,9 +1375,21 @@ def shift_scale_rotate_staged(ssr, staged: StagedImages, packed: PackedGT) -> Tu
     return image_warp_stage(staged, coef), gt
 
 
+BOX_DECODES = ("reference", "standard")                        # RN_BOX_DECODE_REFERENCE / RN_BOX_DECODE_STANDARD, by index
+
+
+def _decode_code(decode: str) -> int:
+    if decode not in BOX_DECODES:
+        raise ValueError(f"decode must be one of {BOX_DECODES}, got {decode!r}")
+    return BOX_DECODES.index(decode)
+
+
 def decode_clip(deltas: Tensor, anchors: Tensor, image_hw: Optional[Tensor],
-                reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0)) -> Tensor:
-    """K4.  deltas [B,A,4] or [A,4]; image_hw i32 [B,2] (device) or None.  -> f32 boxes, same leading shape."""
+                reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0), decode: str = "reference") -> Tensor:
+    """K4.  deltas [B,A,4] or [A,4]; image_hw i32 [B,2] (device) or None.  -> f32 boxes, same leading shape.
+    ``decode``: "reference" (sizes from ``exp(dx)``, ``exp(dy)``: the reference's quirk Q4) or "standard" (sizes from ``dw``, ``dh``
+    clipped at ``BOX_XFORM_CLIP``: the inverse of ``bbox_2_activ``; the numbered rule is in include/retinanet_hip.h)."""
+    kind = _decode_code(decode)
     dev = _need_dev(deltas, anchors, image_hw)
     squeeze = deltas.dim() == 2
     d = _c(deltas[None] if squeeze else deltas)
@@ -1386,8 +1398,8 @@ def decode_clip(deltas: Tensor, anchors: Tensor, image_hw: Optional[Tensor],
     out = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
     rw = (C.c_float * 4)(*reg_w)
     with torch.cuda.device(dev):
-        check(lib.rn_decode_clip(_ptr(d), _dtype_code(d), B, A, _ptr(anchors), bstride, _ptr(image_hw), rw,
-                                 _ptr(out), _stream(dev)), "rn_decode_clip")
+        check(lib.rn_decode_clip_kind(_ptr(d), _dtype_code(d), B, A, _ptr(anchors), bstride, _ptr(image_hw), rw, kind,
+                                      _ptr(out), _stream(dev)), "rn_decode_clip_kind")
     return out[0] if squeeze else out
 
 
@@ -1422,26 +1434,31 @@ def nms(boxes: Tensor, scores: Tensor, iou_threshold: float) -> Tensor:
 
 def detect(cls: Tensor, deltas: Tensor, anchors, image_sizes: Sequence[Tuple[int, int]], score_thr: float,
            min_box: float, nms_thr: float, max_det: int, reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0),
-           max_candidates: Optional[int] = None) -> List[dict]:
+           max_candidates: Optional[int] = None, decode: str = "reference") -> List[dict]:
     """K4-K7 for a batch: -> [{"boxes" f32[n,4], "scores" f32[n], "labels" i64[n]}], n <= max_det.
+    ``decode``: the box decode of the chain, one of ``BOX_DECODES`` (``decode_clip``).
 
     One host sync at the end (the ragged result sizes have to reach Python, as in the
     reference's list-of-dicts contract).  If an image has more candidates than the workspace
     was sized for, the call is repeated once with the exact worst case (A*K)."""
-    return detect_levels([cls], [deltas], anchors, image_sizes, score_thr, min_box, nms_thr, max_det, reg_w, max_candidates)
+    return detect_levels([cls], [deltas], anchors, image_sizes, score_thr, min_box, nms_thr, max_det, reg_w, max_candidates,
+                         decode=decode)
 
 
 def detect_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], anchors, image_sizes: Sequence[Tuple[int, int]],
                   score_thr: float, min_box: float, nms_thr: float, max_det: int,
                   reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0), max_candidates: Optional[int] = None,
-                  enqueue_only: Optional[list] = None, image_hw_dev: Optional[Tensor] = None, padded: bool = False):
+                  enqueue_only: Optional[list] = None, image_hw_dev: Optional[Tensor] = None, padded: bool = False,
+                  decode: str = "reference"):
     """``detect`` on per-level head outputs (cls_levels[l] [B,A_l,K], box_levels[l] [B,A_l,4]) without
     concatenating them; identical results to ``detect(torch.cat(cls_levels, 1), torch.cat(box_levels, 1), ...)``.
     ``image_hw_dev`` (int32 [B, 2] on the outputs' device, e.g. ``resize_plan_dev``'s sizes): the image sizes the boxes are clipped to,
     used instead of an upload of ``image_sizes`` (which may then be None).  ``padded``: enqueue the chain ONCE and return the padded
     device outputs ``(out_boxes [B, max_det, 4], out_scores, out_labels, meta i32 [2, B] = counts | status)`` without reading
     anything back -- no synchronisation and no retry: ``status[b] != 0`` tells the caller that ``max_candidates`` (an int, None for the
-    default, or "all" for the worst case A * K) was too small for image b."""
+    default, or "all" for the worst case A * K) was too small for image b.  ``decode``: the box decode, one of ``BOX_DECODES``
+    (``decode_clip``); every form of the call -- padded, enqueue-only, the overflow retry -- runs the chain with it."""
+    kind = _decode_code(decode)
     L = len(cls_levels)
     if L == 0 or L > _lib.RN_MAX_LEVELS or len(box_levels) != L:
         raise ValueError("need 1..8 levels of (cls, box) outputs")
@@ -1485,10 +1502,10 @@ def detect_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], an
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
 
         def enqueue():
-            check(lib.rn_detect_levels(arr(cls_levels), arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(cls_levels[0]),
-                                       B, K, _ptr(anchors), bstride, _ptr(hw), C.byref(params), cap, _ptr(out_boxes),
-                                       _ptr(out_scores), _ptr(out_labels), _ptr(meta[0]), _ptr(meta[1]), _ptr(ws), ws_bytes,
-                                       _stream(dev)), "rn_detect_levels")
+            check(lib.rn_detect_levels_kind(arr(cls_levels), arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(cls_levels[0]),
+                                            B, K, _ptr(anchors), bstride, _ptr(hw), C.byref(params), kind, cap, _ptr(out_boxes),
+                                            _ptr(out_scores), _ptr(out_labels), _ptr(meta[0]), _ptr(meta[1]), _ptr(ws), ws_bytes,
+                                            _stream(dev)), "rn_detect_levels_kind")
         if enqueue_only is not None:          # (bench.py: the chain's launches as a closure -- for a hipGraph capture -- instead of running them)
             enqueue_only.append(enqueue)
             enqueue_only.append((out_boxes, out_scores, out_labels, meta, ws, hw, anchors, cls_levels, box_levels))     # keep-alive
