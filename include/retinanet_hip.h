@@ -1309,6 +1309,44 @@ int rn_nms_segments(const float *boxes, const float *scores, const int32_t *seg_
                     float iou_thr, int64_t *keep, int32_t *keep_count,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- K6, the soft kinds: Soft-NMS (Bodla et al., ICCV 2017; mmcv's soft_nms, detectron2's SOFT_NMS_*) ------------------------
+ * Hard NMS (above) drops a box that overlaps a kept one; the soft kinds lower its score instead and let it compete again.  Off by
+ * default: the chain runs them only when rn_detect_levels_nms is given a soft method.  The rule, per segment, whose entries are
+ * (score, box, payload) -- payload = the index relative to the segment start at the op boundary, the anchor index in the chain:
+ *   0. Areas and IoU are K6's, each one fp32 operation, no FMA contraction:  area = (x2 - x1) * (y2 - y1);
+ *      inter = max(0, xx2 - xx1) * max(0, yy2 - yy1) with xx1 = max(x1_i, x1_j), xx2 = min(x2_i, x2_j), yy likewise;
+ *      iou = inter / ((area_i + area_j) - inter).
+ *   Repeat:
+ *   1. Among the live entries pick the one with the smallest 64-bit key (inv_ordered(current score) << 32) | payload, inv_ordered
+ *      being the order-reversing map of the score's bits that K6 and K7 sort by: the highest current score, ties to the lower payload.
+ *   2. Stop if there is no live entry, or its current score is not > min_score, or max_keep entries have been kept.
+ *   3. Emit its key, carrying the CURRENT score, as the next survivor.  Mark it dead.
+ *   4. For every live entry j compute iou against the picked box.  If !(iou > 0) leave the score alone (NaN and empty unions
+ *      too).  Otherwise
+ *        RN_NMS_SOFT_LINEAR:    if iou > iou_thr,  s_j = s_j * (1.0f - iou)                        (two fp32 operations);
+ *        RN_NMS_SOFT_GAUSSIAN:  w = (float)exp(-((double)iou * (double)iou) / (double)sigma),  s_j = s_j * w    (no threshold).
+ * Scores are expected >= 0 (the chain's are sigmoids above score_thr); this is not checked.  Then every weight is in [0, 1], the
+ * emitted scores never increase, the survivors come out in key order, and the first max_det survivors of a class are all the
+ * image's top max_det can need (K6's max_keep argument).  box_utils.soft_nms_reference restates the rule in numpy.
+ * One workgroup per segment, no atomics: the same bits on every call; no synchronisation (capturable). */
+#define RN_NMS_HARD 0
+#define RN_NMS_SOFT_LINEAR 1
+#define RN_NMS_SOFT_GAUSSIAN 2
+typedef struct rn_nms_params {
+    int32_t method;          /* RN_NMS_* */
+    float sigma, min_score;  /* mmcv's defaults: 0.5, 1e-3 */
+    int32_t max_keep;        /* op boundary: <= 0 = no cap; ignored by the chain, which uses max_det */
+} rn_nms_params;
+
+/* rn_nms_segments' arguments and layout with a soft method (nms->method RN_NMS_SOFT_LINEAR, whose threshold is iou_thr, or
+ * RN_NMS_SOFT_GAUSSIAN): keep i64[N] as there -- per segment the survivors' indices relative to the segment start, in the order they
+ * were picked; keep_scores f32[N]: the rescored values at the same positions, 0 in the rest of each segment.
+ * workspace: rn_nms_workspace_bytes(N, S).  RN_EINVAL: nms null, RN_NMS_HARD (that is rn_nms_segments) or an unknown method, sigma not
+ * finite or not > 0 under the Gaussian method, a non-finite min_score. */
+int rn_soft_nms_segments(const float *boxes, const float *scores, const int32_t *seg_off, int S, int64_t N,
+                         float iou_thr, const rn_nms_params *nms, int64_t *keep, float *keep_scores, int32_t *keep_count,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- K4-K7 detect -----------------------------------------------------------
  * Replaces Retinanet.process_detections, retinanet/models.py:160-243: sigmoid,
  * decode + clip, per class {score > thr, remove_small_boxes, nms}, class-major
@@ -1347,6 +1385,19 @@ int rn_detect_levels_kind(const void *const *cls_levels, const void *const *box_
                           const rn_detect_params *params, int decode, int64_t max_candidates,
                           float *out_boxes, float *out_scores, int64_t *out_labels, int32_t *out_count,
                           int32_t *out_status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* rn_detect_levels_kind with the NMS kind `nms` (the rule next to K6): NULL or method RN_NMS_HARD is rn_detect_levels_kind launch
+ * for launch (greedy hard NMS at params->nms_thr; the other fields are not read), and rn_detect_levels_kind is this call with NULL.
+ * A soft method replaces the two NMS launches by the two Soft-NMS launches on the same segments -- RN_NMS_SOFT_LINEAR with
+ * params->nms_thr as its threshold -- with max_keep = params->max_det (nms->max_keep is ignored); the score scan, the scatter, the
+ * top-k and the outputs' layout are unchanged, and out_scores holds the rescored values.  RN_EINVAL also for an unknown method, and
+ * under a soft method for sigma not finite or not > 0 (Gaussian) and for a non-finite min_score.  rn_detect_params is unchanged. */
+int rn_detect_levels_nms(const void *const *cls_levels, const void *const *box_levels,
+                         const int64_t *level_anchors, int L, int dtype, int B, int K,
+                         const float *anchors, int64_t anchor_bstride, const int32_t *image_hw,
+                         const rn_detect_params *params, int decode, const rn_nms_params *nms, int64_t max_candidates,
+                         float *out_boxes, float *out_scores, int64_t *out_labels, int32_t *out_count,
+                         int32_t *out_status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- the end of predict on the device (graph.CapturedPredict, csrc/finish.hip) ---------------------------------------------
  * rn_detect_finish_var: transform.postprocess for the batch -- the padded outputs of rn_detect / rn_detect_levels (out_boxes

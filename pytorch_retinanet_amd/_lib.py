@@ -28,6 +28,10 @@ class RnDetectParams(C.Structure):
                 ("max_det", C.c_int32), ("reg_w", C.c_float * 4)]
 
 
+class RnNmsParams(C.Structure):
+    _fields_ = [("method", C.c_int32), ("sigma", C.c_float), ("min_score", C.c_float), ("max_keep", C.c_int32)]
+
+
 class RnPwConv(C.Structure):
     _fields_ = [("M", C.c_int64), ("Cin", C.c_int32), ("N", C.c_int32), ("taps", C.c_int32), ("stride", C.c_int32),
                 ("pad", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
@@ -229,6 +233,7 @@ SIGNATURES = {
     "rn_eval_accumulate": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "rn_nms_workspace_bytes":(_sz, [_i64, C.c_int]),
     "rn_nms_segments": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "rn_soft_nms_segments": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _f32, C.POINTER(RnNmsParams), _vp, _vp, _vp, _vp, _sz, _vp]),
     "rn_detect_workspace_bytes": (_sz, [C.c_int, _i64, C.c_int, _i64]),
     "rn_detect": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i64, C.c_int, _vp, _i64, _vp, C.POINTER(RnDetectParams),
                             _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -236,6 +241,9 @@ SIGNATURES = {
                                    C.POINTER(RnDetectParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rn_detect_levels_kind": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp,
                                         C.POINTER(RnDetectParams), C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rn_detect_levels_nms": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp,
+                                       C.POINTER(RnDetectParams), C.c_int, C.POINTER(RnNmsParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _sz, _vp]),
     "rn_detect_result_bytes": (_sz, [C.c_int, C.c_int]),
     "rn_detect_finish_var": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _sz, _vp]),
 }

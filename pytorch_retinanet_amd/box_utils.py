@@ -93,6 +93,66 @@ def decode_boxes_reference(deltas, anchors, reg_w=BBOX_REG_WEIGHTS, decode: str 
     return torch.from_numpy(out) if as_torch else out
 
 
+def soft_nms_reference(boxes, scores, iou_thr, method, sigma=0.5, min_score=1e-3, max_keep=None, on_pick=None):
+    """Soft-NMS of ONE segment restated in numpy fp32, operation for operation (the rule next to K6 in include/retinanet_hip.h; the
+    tests' yardstick; CPU tensors or arrays).  ``boxes`` [n, 4] XYXY, ``scores`` [n] (expected >= 0), payload = index:
+      0. area = (x2 - x1) * (y2 - y1); inter = max(0, xx2 - xx1) * max(0, yy2 - yy1); iou = inter / ((area_i + area_j) - inter);
+      1. pick the live entry with the smallest key (inv_ordered(current score) << 32) | index: the highest score, ties to the lower index;
+      2. stop if there is none, its score is not > ``min_score``, or ``max_keep`` (None / <= 0: no cap) entries are kept;
+      3. emit it with its current score; it is dead;
+      4. every live entry with iou > 0 against it: "soft_linear": if iou > ``iou_thr``, s = s * (1 - iou); "soft_gaussian":
+         s = s * float32(exp(-(float64(iou) * float64(iou)) / float64(float32(sigma)))).
+    ``on_pick(i, scores, live)``: called at every step 3 with the picked index, the current scores and the live mask (the pick still
+    live) -- for tests that look at how close the runner-up was.
+    -> (kept indices int64 [m], their scores float32 [m]), in pick order.  ``exp`` is numpy's double one, which may differ from the
+    device library's in the last place: a Gaussian weight may differ by one fp32 unit."""
+    import numpy as np
+    if method not in ops.NMS_KINDS[1:]:
+        raise ValueError(f"method must be one of {ops.NMS_KINDS[1:]}, got {method!r}")
+    b = boxes.detach().to(torch.float32).cpu().numpy() if isinstance(boxes, Tensor) else np.asarray(boxes, dtype=np.float32)
+    s = scores.detach().to(torch.float32).cpu().numpy() if isinstance(scores, Tensor) else np.asarray(scores, dtype=np.float32)
+    b, s = b.reshape(-1, 4), s.reshape(-1).copy()
+    n = s.shape[0]
+    thr, floor, one, zero = np.float32(iou_thr), np.float32(min_score), np.float32(1.0), np.float32(0.0)
+    sig = np.float64(np.float32(sigma))
+    cap = int(max_keep) if max_keep is not None and int(max_keep) > 0 else n
+    idx = np.arange(n, dtype=np.uint64)
+
+    def keys(v):                                             # rn::inv_ordered(score) << 32 | index
+        u = v.view(np.uint32)
+        u = u ^ np.where(u >> np.uint32(31), np.uint32(0xffffffff), np.uint32(0x80000000))
+        return ((~u).astype(np.uint64) << np.uint64(32)) | idx
+
+    live = np.ones(n, dtype=bool)
+    keep, out = [], []
+    with np.errstate(all="ignore"):
+        area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+        while len(keep) < cap and live.any():
+            k = keys(s)
+            k[~live] = np.uint64(0xffffffffffffffff)
+            i = int(np.argmin(k))
+            if not s[i] > floor:
+                break
+            if on_pick is not None:
+                on_pick(i, s, live)
+            keep.append(i)
+            out.append(s[i])
+            live[i] = False
+            w = np.where(b[i, 2] < b[:, 2], b[i, 2], b[:, 2]) - np.where(b[i, 0] > b[:, 0], b[i, 0], b[:, 0])
+            h = np.where(b[i, 3] < b[:, 3], b[i, 3], b[:, 3]) - np.where(b[i, 1] > b[:, 1], b[i, 1], b[:, 1])
+            w, h = np.where(w > zero, w, zero), np.where(h > zero, h, zero)
+            inter = w * h
+            iou = inter / ((area[i] + area) - inter)
+            if method == "soft_linear":
+                hit = live & (iou > zero) & (iou > thr)
+                s[hit] = s[hit] * (one - iou[hit])
+            else:
+                hit = live & (iou > zero)
+                d = iou[hit].astype(np.float64)
+                s[hit] = s[hit] * np.exp(-(d * d) / sig).astype(np.float32)
+    return np.asarray(keep, dtype=np.int64), np.asarray(out, dtype=np.float32)
+
+
 def _iou_pairs_f32(t, a):
     "K2's pair arithmetic (csrc/rn_match.hpp, iou_pair) of one GT box against anchors [n,4], operation for operation in numpy fp32."
     import numpy as np

@@ -876,12 +876,24 @@ RN_API int rn_detect_levels_kind(const void *const *cls_levels, const void *cons
                                  float *out_scores, int64_t *out_labels, int32_t *out_count, int32_t *out_status, void *workspace,
                                  size_t workspace_bytes, void *stream)
 {
+    return rn_detect_levels_nms(cls_levels, box_levels, level_anchors, L, dtype, B, K, anchors, anchor_bstride, image_hw, params, decode,
+                                nullptr, max_candidates, out_boxes, out_scores, out_labels, out_count, out_status, workspace,
+                                workspace_bytes, stream);
+}
+
+RN_API int rn_detect_levels_nms(const void *const *cls_levels, const void *const *box_levels, const int64_t *level_anchors, int L,
+                                int dtype, int B, int K, const float *anchors, int64_t anchor_bstride, const int32_t *image_hw,
+                                const rn_detect_params *params, int decode, const rn_nms_params *nms, int64_t max_candidates,
+                                float *out_boxes, float *out_scores, int64_t *out_labels, int32_t *out_count, int32_t *out_status,
+                                void *workspace, size_t workspace_bytes, void *stream)
+{
     if (!cls_levels || !box_levels || !level_anchors || !anchors || !params || !out_boxes || !out_scores || !out_labels ||
         !out_count || !out_status || !workspace)
         return RN_EINVAL;
     if (L <= 0 || L > RN_MAX_LEVELS || B <= 0 || K <= 0 || max_candidates <= 0 || params->max_det <= 0) return RN_EINVAL;
     if (dtype != RN_F32 && dtype != RN_BF16 && dtype != RN_F16) return RN_EINVAL;
     if (check_decode(decode, params->reg_w) != RN_OK) return RN_EINVAL;
+    if (nms && rn::check_nms_params(nms) != RN_OK) return RN_EINVAL;
     int64_t A = 0;
     for (int l = 0; l < L; ++l) {
         if (!cls_levels[l] || !box_levels[l] || level_anchors[l] <= 0) return RN_EINVAL;
@@ -993,7 +1005,8 @@ RN_API int rn_detect_levels_kind(const void *const *cls_levels, const void *cons
     // them): a long segment's greedy scan stops once it has kept that many -- the reference (no pre-NMS top-k, models.py:193-219) runs
     // O(n^2) over ~7 k boxes per class in SURVEY 8d's stress regime; the detections are the same rows
     na.max_keep = params->max_det;
-    rc = rn::launch_nms(na, st);
+    if (nms && nms->method != RN_NMS_HARD) rc = rn::launch_soft_nms(na, nms->method, nms->sigma, nms->min_score, st);     // (the rule next to K6)
+    else rc = rn::launch_nms(na, st);
     if (rc != RN_OK) return rc;
     hipLaunchKernelGGL(topk_kernel, dim3((unsigned)B), dim3(TOPK_THREADS), 0, st, w.cand, w.seg_start, w.kept_count, w.boxes,
                        K, A, params->max_det, (rn::f32x4 *)out_boxes, out_scores, out_labels, out_count);

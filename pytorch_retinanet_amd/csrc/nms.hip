@@ -710,8 +710,16 @@ RN_API int rn_nms_segments(const float *boxes, const float *scores, const int32_
     if (N >= ((int64_t)1 << 31)) return RN_EUNSUPPORTED;
     if (!workspace || workspace_bytes < rn_nms_workspace_bytes(N, S)) return RN_EWORKSPACE;
     if ((boxes && !rn::aligned(boxes, 16)) || !rn::aligned(workspace, 16)) return RN_EALIGN;
-    unsigned char *w = (unsigned char *)workspace;
     rn::NmsLaunch a;
+    const int rc = rn::nms_op_prepare(boxes, scores, seg_off, S, N, iou_thr, keep, keep_count, workspace, a, (hipStream_t)stream);
+    if (rc != RN_OK) return rc;
+    return rn::launch_nms(a, (hipStream_t)stream);
+}
+
+int rn::nms_op_prepare(const float *boxes, const float *scores, const int32_t *seg_off, int S, int64_t N, float iou_thr, int64_t *keep,
+                       int32_t *keep_count, void *workspace, rn::NmsLaunch &a, hipStream_t st)
+{
+    unsigned char *w = (unsigned char *)workspace;
     a.keys = (uint64_t *)w; w += al256((size_t)N * 8);
     a.kept = (uint64_t *)w; w += al256((size_t)N * 8);
     int64_t *seg_start = (int64_t *)w; w += al256((size_t)S * 8);
@@ -722,10 +730,9 @@ RN_API int rn_nms_segments(const float *boxes, const float *scores, const int32_
     a.boxes = (const rn::f32x4 *)boxes;
     a.seg_start = seg_start; a.seg_len = seg_len; a.kept_count = keep_count;
     a.S = S; a.box_mode = 0; a.K = 1; a.A = 0; a.iou_thr = iou_thr; a.max_keep = 0;
-    hipStream_t st = (hipStream_t)stream;
     const int64_t work = N > S ? N : S;
     hipLaunchKernelGGL(nms_prep_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, scores, seg_off, S, N,
                        a.keys, seg_start, seg_len);
     RN_LAUNCH_CHECK();
-    return rn::launch_nms(a, st);
+    return RN_OK;
 }

@@ -46,4 +46,25 @@ struct NmsLaunch {
 };
 int launch_nms(const NmsLaunch &a, hipStream_t st);
 
+// The soft kinds of K6 (softnms.hip; the numbered rule is next to K6 in the header): the same struct, buffers and workspace; `method`
+// RN_NMS_SOFT_LINEAR (a.iou_thr is its threshold) or RN_NMS_SOFT_GAUSSIAN (`sigma`); kept[] holds the survivors' keys WITH THE SCORE
+// EACH HAD WHEN IT WAS PICKED, in pick order (= key order), kept_count their number (<= max_keep when max_keep > 0).  a.keys is
+// clobbered; scratch_boxes is used by segments longer than 2048, scratch_supp not at all.
+int launch_soft_nms(const NmsLaunch &a, int method, float sigma, float min_score, hipStream_t st);
+
+// The op entries' common start (nms.hip): carves `workspace` (rn_nms_workspace_bytes(N, S), checked by the caller), builds keys,
+// seg_start and seg_len from (scores, seg_off) in one launch, and fills `a` for launch_nms / launch_soft_nms with max_keep = 0.
+int nms_op_prepare(const float *boxes, const float *scores, const int32_t *seg_off, int S, int64_t N, float iou_thr, int64_t *keep,
+                   int32_t *keep_count, void *workspace, NmsLaunch &a, hipStream_t st);
+
+// RN_EINVAL for an unknown method; for a soft method also for a non-finite min_score, and for sigma not finite or not > 0 under the
+// Gaussian one.  (A hard method's other fields are never read.)
+static inline int check_nms_params(const rn_nms_params *p) {
+    if (p->method == RN_NMS_HARD) return RN_OK;
+    if (p->method != RN_NMS_SOFT_LINEAR && p->method != RN_NMS_SOFT_GAUSSIAN) return RN_EINVAL;
+    if (!__builtin_isfinite(p->min_score)) return RN_EINVAL;
+    if (p->method == RN_NMS_SOFT_GAUSSIAN && !(__builtin_isfinite(p->sigma) && p->sigma > 0.0f)) return RN_EINVAL;
+    return RN_OK;
+}
+
 }  // namespace rn

@@ -891,9 +891,11 @@ class CapturedPredict:
         if mode is None:
             mode = self._walk()[0]
         # (what the pass takes BY VALUE: the eval short side, max_size, mean and std are kernel arguments of the plan and the transform,
-        # the thresholds, the box decode and max_det of the detect chain: a graph captured with one decode never serves the other)
+        # the thresholds, the box decode, the NMS kind with its two constants and max_det of the detect chain: a graph captured with one
+        # decode or one NMS kind never serves another)
         return ("predict", len(images), icls[0], icls[1], dtype, cl, images[0].device, mode, tr.staged_eval_short_side(), int(tr.max_size),
                 tuple(tr.image_mean), tuple(tr.image_std), net.score_thres, net.nms_thres, getattr(net, "box_decode", "reference"),
+                getattr(net, "nms", "hard"), getattr(net, "soft_nms_sigma", 0.5), getattr(net, "soft_nms_min_score", 1e-3),
                 net.detections_per_img)
 
     def _weights_stamp(self) -> tuple:

@@ -56,6 +56,9 @@ class Retinanet(nn.Module):
         box_loss: Optional[str] = None,
         box_loss_weight: Optional[float] = None,
         box_decode: Optional[str] = None,
+        nms: Optional[str] = None,
+        soft_nms_sigma: Optional[float] = None,
+        soft_nms_min_score: Optional[float] = None,
     ) -> None:
         """``matcher``: how anchors are labelled -- None / "iou" (the reference's max-IoU rule, K2) or "atss" (``ops.atss_match``,
         with ``atss_topk`` nearest locations per level and object, None -> 9); ``model: {matcher: atss}`` in the hparams.
@@ -66,8 +69,18 @@ class Retinanet(nn.Module):
         "reference" (K4 with the reference's quirk Q4: the sizes come from ``exp(dx)``, ``exp(dy)`` and ``dw``, ``dh`` are never read) or
         "standard" (the inverse of the training targets' encode, which is also what "giou" / "diou" optimise: sizes from ``dw``,
         ``dh``, clipped at ``ops.BOX_XFORM_CLIP``); ``model: {box_decode: standard}`` in the hparams.  Stored as ``net.box_decode`` and
-        read at every call.  A model trained with "giou" / "diou" and inferred with the reference decode logs a warning here."""
+        read at every call.  A model trained with "giou" / "diou" and inferred with the reference decode logs a warning here.
+        ``nms``: the per-class NMS of the same calls -- None / "hard" (K6: greedy NMS at ``nms_thres``, the reference's) or Soft-NMS,
+        which lowers the score of a box that overlaps a picked one instead of dropping it: "soft_linear" (by 1 - IoU where IoU >
+        ``nms_thres``) or "soft_gaussian" (by exp(-IoU^2 / ``soft_nms_sigma``), None -> 0.5); a class ends when its best remaining score
+        is not above ``soft_nms_min_score`` (None -> 1e-3); ``model: {nms: soft_gaussian}`` in the hparams.  Stored as ``net.nms``,
+        ``net.soft_nms_sigma`` and ``net.soft_nms_min_score`` and read at every call (``ops.detect_levels``)."""
         super().__init__()
+        nms = ifnone(nms, "hard")
+        if nms not in ops.NMS_KINDS:
+            raise ValueError(f"nms must be one of {ops.NMS_KINDS}, got {nms!r}")
+        soft_nms_sigma = ifnone(soft_nms_sigma, 0.5)
+        soft_nms_min_score = ifnone(soft_nms_min_score, 1e-3)
         box_decode = ifnone(box_decode, "reference")
         if box_decode not in ops.BOX_DECODES:
             raise ValueError(f"box_decode must be one of {ops.BOX_DECODES}, got {box_decode!r}")
@@ -109,6 +122,9 @@ class Retinanet(nn.Module):
         self.detections_per_img = max_detections_per_images
         self.num_classes = num_classes
         self.box_decode = box_decode
+        self.nms = nms
+        self.soft_nms_sigma = float(soft_nms_sigma)
+        self.soft_nms_min_score = float(soft_nms_min_score)
         if box_loss in ("giou", "diou") and box_decode == "reference":
             logger.warning(f'box_loss="{box_loss}" trains the box that box_decode="standard" decodes, but this model infers with the '
                            'reference decode (sizes from exp(dx), exp(dy)): pass box_decode="standard" (model: {box_decode: standard}) '
@@ -189,13 +205,14 @@ class Retinanet(nn.Module):
     def process_detections(self, outputs: Dict[str, Tensor], anchors: List[Tensor],
                            im_szs: List[Tuple[int, int]]) -> List[Dict[str, Tensor]]:
         """Raw head outputs -> per-image detections (models.py:160-243): one HIP call
-        (``rn_detect``) for the whole batch instead of B*K sequential NMS launches.  Boxes are decoded as ``self.box_decode`` says."""
+        (``rn_detect``) for the whole batch instead of B*K sequential NMS launches.  Boxes are decoded as ``self.box_decode`` says and
+        suppressed as ``self.nms`` says."""
         class_logits = outputs.pop("cls_preds")
         bboxes = outputs.pop("bbox_preds")
         if any(w != 1.0 for w in BBOX_REG_WEIGHTS):
             bboxes.div_(bboxes.new_tensor([BBOX_REG_WEIGHTS]))          # box_utils.py:43 (in place, Q5)
         return ops.detect(class_logits, bboxes, anchors, im_szs, self.score_thres, MIN_BOX_SIZE, self.nms_thres,
-                          self.detections_per_img, decode=self.box_decode)
+                          self.detections_per_img, decode=self.box_decode, **self._nms_args())
 
     def process_detections_levels(self, outputs: Dict[str, List[Tensor]], anchors: List[Tensor],
                                   im_szs: List[Tuple[int, int]]) -> List[Dict[str, Tensor]]:
@@ -203,7 +220,11 @@ class Retinanet(nn.Module):
         and decode kernels read the five conv outputs in place (no ``torch.cat``, layers.py:195, :259)."""
         return ops.detect_levels(outputs["cls_levels"], outputs["bbox_levels"], anchors, im_szs, self.score_thres,
                                  MIN_BOX_SIZE, self.nms_thres, self.detections_per_img, reg_w=BBOX_REG_WEIGHTS,
-                                 decode=self.box_decode)
+                                 decode=self.box_decode, **self._nms_args())
+
+    def _nms_args(self) -> Dict[str, object]:
+        "The NMS kind of the detect chain as ``ops.detect*`` takes it, read from the attributes at every call."
+        return {"nms": self.nms, "nms_sigma": self.soft_nms_sigma, "nms_min_score": self.soft_nms_min_score}
 
     def predict(self, images: List[Tensor]) -> List[Dict[str, Tensor]]:
         """Detections in original image coordinates (models.py:245-272).  Like the
@@ -250,5 +271,6 @@ class Retinanet(nn.Module):
             outputs = self.retinanet_head.forward_levels(feature_maps)
             padded = ops.detect_levels(outputs["cls_levels"], outputs["bbox_levels"], anchors, None, self.score_thres, MIN_BOX_SIZE,
                                        self.nms_thres, self.detections_per_img, reg_w=BBOX_REG_WEIGHTS, max_candidates=max_candidates,
-                                       image_hw_dev=images.image_sizes_dev, padded=True, decode=self.box_decode)
+                                       image_hw_dev=images.image_sizes_dev, padded=True, decode=self.box_decode,
+                                       **self._nms_args())
             return ops.detect_finish_var(*padded, staged.in_hw, images.image_sizes_dev)

@@ -14,7 +14,7 @@ from torch import Tensor
 from . import _lib, draw_state
 from ._launch import zero_page
 from .draw_state import AFFINE, BBOX_CROP, COLOR_IDENTITY, COLOR_JITTER, COLOR_OPS, HFLIP, SHORT_SIDE, SHORT_SIDE_MAX  # noqa: F401
-from ._lib import RN_BF16, RN_F16, RN_F32, RnDetectParams, RnLevel, RnLossParams, check, lib
+from ._lib import RN_BF16, RN_F16, RN_F32, RnDetectParams, RnLevel, RnLossParams, RnNmsParams, check, lib
 
 RN_MATCH_NUM_FG_ZEROED, RN_MATCH_FLAGGED_ONLY = 1, 2          # include/retinanet_hip.h
 LOSS_FORM_CHUNKS, LOSS_FORM_REPAIR_PASS, LOSS_FORM_LIST = 0, 1, 2   # RN_LOSS_FORM_*
@@ -1421,6 +1421,41 @@ def nms_segments(boxes: Tensor, scores: Tensor, seg_off: Tensor, iou_thr: float)
     return keep[:N], count
 
 
+NMS_KINDS = ("hard", "soft_linear", "soft_gaussian")            # RN_NMS_HARD / RN_NMS_SOFT_LINEAR / RN_NMS_SOFT_GAUSSIAN, by index
+
+
+def _nms_params(nms: str, sigma: float, min_score: float, max_keep: Optional[int] = None) -> RnNmsParams:
+    if nms not in NMS_KINDS:
+        raise ValueError(f"nms must be one of {NMS_KINDS}, got {nms!r}")
+    return RnNmsParams(NMS_KINDS.index(nms), float(sigma), float(min_score), int(max_keep) if max_keep else 0)
+
+
+def soft_nms_segments(boxes: Tensor, scores: Tensor, seg_off: Tensor, iou_thr: float, method: str, sigma: float = 0.5,
+                      min_score: float = 1e-3, max_keep: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Soft-NMS (the rule next to K6 in include/retinanet_hip.h; ``box_utils.soft_nms_reference``) batched over segments, with
+    ``nms_segments``' inputs.  ``method``: "soft_linear" (scores of boxes overlapping a picked one by more than ``iou_thr`` are
+    multiplied by 1 - IoU) or "soft_gaussian" (by exp(-IoU^2 / ``sigma``), no threshold); a segment ends when its best remaining
+    score is not above ``min_score`` or ``max_keep`` (None: no cap) entries are kept.  Scores are expected >= 0; not checked.
+    -> (keep i64 [N] (per segment: indices relative to the segment start, in pick order), keep_scores f32 [N] (the rescored values
+    at the same positions, 0 elsewhere), keep_count i32 [S])."""
+    if method == "hard":
+        raise ValueError('method must be "soft_linear" or "soft_gaussian": the hard kind is nms_segments')
+    params = _nms_params(method, sigma, min_score, max_keep)
+    dev = _need_dev(boxes, scores, seg_off)
+    boxes = _c(boxes.float()).reshape(-1, 4)
+    scores = _c(scores.float()).reshape(-1)
+    N, S = boxes.shape[0], seg_off.numel() - 1
+    keep = torch.empty((max(N, 1),), dtype=torch.int64, device=dev)
+    keep_scores = torch.empty((max(N, 1),), dtype=torch.float32, device=dev)
+    count = torch.empty((S,), dtype=torch.int32, device=dev)
+    ws_bytes = lib.rn_nms_workspace_bytes(N, S)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.rn_soft_nms_segments(_ptr(boxes), _ptr(scores), _ptr(seg_off), S, N, iou_thr, C.byref(params), _ptr(keep),
+                                       _ptr(keep_scores), _ptr(count), _ptr(ws), ws_bytes, _stream(dev)), "rn_soft_nms_segments")
+    return keep[:N], keep_scores[:N], count
+
+
 def nms(boxes: Tensor, scores: Tensor, iou_threshold: float) -> Tensor:
     """Drop-in for ``torchvision.ops.nms(boxes, scores, iou_threshold) -> int64[k]`` (one segment).
     Reading the kept count is the one host sync, exactly as in the op it replaces."""
@@ -1434,22 +1469,24 @@ def nms(boxes: Tensor, scores: Tensor, iou_threshold: float) -> Tensor:
 
 def detect(cls: Tensor, deltas: Tensor, anchors, image_sizes: Sequence[Tuple[int, int]], score_thr: float,
            min_box: float, nms_thr: float, max_det: int, reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0),
-           max_candidates: Optional[int] = None, decode: str = "reference") -> List[dict]:
+           max_candidates: Optional[int] = None, decode: str = "reference", nms: str = "hard", nms_sigma: float = 0.5,
+           nms_min_score: float = 1e-3) -> List[dict]:
     """K4-K7 for a batch: -> [{"boxes" f32[n,4], "scores" f32[n], "labels" i64[n]}], n <= max_det.
-    ``decode``: the box decode of the chain, one of ``BOX_DECODES`` (``decode_clip``).
+    ``decode``: the box decode of the chain, one of ``BOX_DECODES`` (``decode_clip``).  ``nms``: the chain's NMS, one of ``NMS_KINDS``
+    (``detect_levels``).
 
     One host sync at the end (the ragged result sizes have to reach Python, as in the
     reference's list-of-dicts contract).  If an image has more candidates than the workspace
     was sized for, the call is repeated once with the exact worst case (A*K)."""
     return detect_levels([cls], [deltas], anchors, image_sizes, score_thr, min_box, nms_thr, max_det, reg_w, max_candidates,
-                         decode=decode)
+                         decode=decode, nms=nms, nms_sigma=nms_sigma, nms_min_score=nms_min_score)
 
 
 def detect_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], anchors, image_sizes: Sequence[Tuple[int, int]],
                   score_thr: float, min_box: float, nms_thr: float, max_det: int,
                   reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0), max_candidates: Optional[int] = None,
                   enqueue_only: Optional[list] = None, image_hw_dev: Optional[Tensor] = None, padded: bool = False,
-                  decode: str = "reference"):
+                  decode: str = "reference", nms: str = "hard", nms_sigma: float = 0.5, nms_min_score: float = 1e-3):
     """``detect`` on per-level head outputs (cls_levels[l] [B,A_l,K], box_levels[l] [B,A_l,4]) without
     concatenating them; identical results to ``detect(torch.cat(cls_levels, 1), torch.cat(box_levels, 1), ...)``.
     ``image_hw_dev`` (int32 [B, 2] on the outputs' device, e.g. ``resize_plan_dev``'s sizes): the image sizes the boxes are clipped to,
@@ -1457,8 +1494,13 @@ def detect_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], an
     device outputs ``(out_boxes [B, max_det, 4], out_scores, out_labels, meta i32 [2, B] = counts | status)`` without reading
     anything back -- no synchronisation and no retry: ``status[b] != 0`` tells the caller that ``max_candidates`` (an int, None for the
     default, or "all" for the worst case A * K) was too small for image b.  ``decode``: the box decode, one of ``BOX_DECODES``
-    (``decode_clip``); every form of the call -- padded, enqueue-only, the overflow retry -- runs the chain with it."""
+    (``decode_clip``); every form of the call -- padded, enqueue-only, the overflow retry -- runs the chain with it.
+    ``nms``: the per-class NMS, one of ``NMS_KINDS`` -- "hard" (greedy NMS at ``nms_thr``: the reference's, the same launches as
+    before the kinds existed), "soft_linear" (Soft-NMS with ``nms_thr`` as the linear threshold) or "soft_gaussian" (``nms_sigma``);
+    the soft kinds end a class at ``nms_min_score`` and return the rescored values as ``scores`` (``soft_nms_segments``; the rule is
+    next to K6 in the header).  Every form of the call runs the chain with it."""
     kind = _decode_code(decode)
+    nms_params = _nms_params(nms, nms_sigma, nms_min_score)
     L = len(cls_levels)
     if L == 0 or L > _lib.RN_MAX_LEVELS or len(box_levels) != L:
         raise ValueError("need 1..8 levels of (cls, box) outputs")
@@ -1502,10 +1544,10 @@ def detect_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], an
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
 
         def enqueue():
-            check(lib.rn_detect_levels_kind(arr(cls_levels), arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(cls_levels[0]),
-                                            B, K, _ptr(anchors), bstride, _ptr(hw), C.byref(params), kind, cap, _ptr(out_boxes),
-                                            _ptr(out_scores), _ptr(out_labels), _ptr(meta[0]), _ptr(meta[1]), _ptr(ws), ws_bytes,
-                                            _stream(dev)), "rn_detect_levels_kind")
+            check(lib.rn_detect_levels_nms(arr(cls_levels), arr(box_levels), (C.c_int64 * L)(*counts), L, _dtype_code(cls_levels[0]),
+                                           B, K, _ptr(anchors), bstride, _ptr(hw), C.byref(params), kind, C.byref(nms_params), cap,
+                                           _ptr(out_boxes), _ptr(out_scores), _ptr(out_labels), _ptr(meta[0]), _ptr(meta[1]), _ptr(ws),
+                                           ws_bytes, _stream(dev)), "rn_detect_levels_nms")
         if enqueue_only is not None:          # (bench.py: the chain's launches as a closure -- for a hipGraph capture -- instead of running them)
             enqueue_only.append(enqueue)
             enqueue_only.append((out_boxes, out_scores, out_labels, meta, ws, hw, anchors, cls_levels, box_levels))     # keep-alive

@@ -7,7 +7,8 @@ mapping and the GPU raises a memory access fault (the process aborts) instead of
 usage: guard_probe.py stem B H W | w3 N H W C | n3 N H W | dense | pw | pool | bottleneck | step KIND MIN MAX | detect DT B H W K [MEAN] |
        loss DT B H W K T | gt | affine | adam [bf16|f16] | clip [bf16|f16] | accum [bf16|f16]        (driven by tests/test_guard_gpu.py;
        gt: by tests/test_gt_capacity_gpu.py; affine: by tests/test_shift_scale_rotate_gpu.py; adam: by tests/test_master_adam_gpu.py; clip: by tests/test_grad_clip_gpu.py;
-       accum: by tests/test_grad_accum_gpu.py; sgd_dev [bf16|f16]: by tests/test_master_sgd_capturable_gpu.py)
+       accum: by tests/test_grad_accum_gpu.py; sgd_dev [bf16|f16]: by tests/test_master_sgd_capturable_gpu.py;
+       softnms: by tests/test_soft_nms_gpu.py)
 Prints one "ok ..." line per case; a fault kills the process (non-zero exit status, no "ok" line for the case)."""
 import ctypes as C
 import os
@@ -549,6 +550,41 @@ def main() -> None:
         assert blk.view(torch.int32)[1:3].tolist() == [N, 0] and float(blk.view(torch.float32)[3]) == 0.0
         assert blk.view(torch.int64)[2:5].tolist() == [1, 0, N]
         print("ok accum", str(dt), n_t, sum(sizes), flush=True)
+    elif which == "softnms":
+        # Soft-NMS at the op boundary (rn_soft_nms_segments, csrc/softnms.hip): boxes, scores, segment offsets, the three outputs and the
+        # workspace at the end of their own mappings; a 65-entry segment (the first length of the block kernel's register form) and a
+        # 2049-entry one (the first of its HBM form), both methods, against the numpy restatement
+        import numpy as np
+        import soft_nms_cases as cases
+        from pytorch_retinanet_amd._lib import RnNmsParams
+        boxes, scores, off = cases.segments(92, (65, 2049))
+        N, S = len(scores), len(off) - 1
+
+        def at_end(a):
+            src = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+            t = raw_at_end(src.numel() * src.element_size()).view(src.dtype).view(src.shape)
+            t.copy_(src)
+            return t
+        db, ds, do = at_end(boxes), at_end(scores), at_end(off)
+        need = lib.rn_nms_workspace_bytes(N, S)
+        for code, method in ((1, "soft_linear"), (2, "soft_gaussian")):
+            keep, ks, cnt, ws = raw_at_end(N * 8, 0), raw_at_end(N * 4, 0), raw_at_end(S * 4, 0), raw_at_end(need)
+            params = RnNmsParams(code, 0.5, 1e-3, cases.CAP)
+            check(lib.rn_soft_nms_segments(db.data_ptr(), ds.data_ptr(), do.data_ptr(), S, N, cases.IOU_THR, C.byref(params), keep.data_ptr(),
+                                           ks.data_ptr(), cnt.data_ptr(), ws.data_ptr(), need, st), "rn_soft_nms_segments")
+            torch.cuda.synchronize()
+            wk, wsc, wc, _ = cases.expected(boxes, scores, off, method, cases.CAP)
+            got_c = cnt.view(torch.int32).cpu().numpy()
+            assert np.array_equal(got_c, wc), (method, got_c, wc)
+            got_k, got_s = keep.view(torch.int64).cpu().numpy(), ks.view(torch.float32).cpu().numpy()
+            for i in range(S):
+                lo, hi = int(off[i]), int(off[i]) + int(wc[i])
+                assert np.array_equal(got_k[lo:hi], wk[lo:hi]), (method, i)
+                if code == 1:
+                    assert np.array_equal(got_s[lo:hi].view(np.uint32), wsc[lo:hi].view(np.uint32)), (method, i)
+                else:
+                    np.testing.assert_allclose(got_s[lo:hi], wsc[lo:hi], rtol=cases.gaussian_bound(wc[i]), atol=0)
+        print("ok softnms", N, S, flush=True)
     else:
         raise SystemExit(f"unknown probe {which!r}")
 
