@@ -306,6 +306,52 @@ int rn_box_iou_loss(const void *const *box_levels, const int64_t *level_anchors,
                     const float *reg_w, int kind, float loss_weight, const float *grad_prescale,
                     float *out_loss, void *const *grad_box_levels, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Quality Focal Loss (round 34; not in the reference) ----------------------
+ * QFL (Li et al., "Generalized Focal Loss", NeurIPS 2020) in place of K3's focal loss against a hard 0 / 1 target: the target of a
+ * matched row's LABEL element is the IoU between the row's decoded box and its GT box, every other element keeps the target 0.
+ * rn_quality_focal_loss runs BEHIND a K3 call on the same stream, and is only meaningful behind one made with alpha = 1 and
+ * gamma = beta.  THE K3 CONTRACT: with those two values K3 gives every background element exactly QFL's negative term,
+ * sigma^beta * BCE(sigma, 0), and every matched label element the weight alpha_pos = 1 - alpha = 0, so that element's loss is
+ * 0 * bce = 0 and its gradient -0 (for finite logits): K3's own contribution of a matched label element is exactly zero, in
+ * out_loss[0] and in grad_cls.  This call supplies what is missing: it adds the label elements' soft-target terms to out_loss[0] and
+ * stores their gradients.  out_loss[1], grad_box, every other class gradient element and ignored rows stay K3's business.
+ * A matched row is rn_box_iou_loss's: its flag bit is set in special_rows and matches[b][a] = m >= 0; its GT box is
+ * g = gt_boxes[gt_off[b] + m] (m clamped into the image's rows) and its label c = gt_labels[gt_off[b] + m] - 1.  A row whose label
+ * is outside 1..K adds nothing and writes nothing.  Every fp32 step below is one correctly rounded operation (no FMA contraction);
+ * expf, log1pf and powf are the device library's.
+ *   1. Quality.   Steps 1 and 2 of rn_box_iou_loss's rule, unchanged (the same code): the standard decode with RN_BOX_XFORM_CLIP,
+ *                 then the IoU.  q = iou, in [0, 1].  q is a CONSTANT: no gradient flows into the box deltas through it, as in GFL,
+ *                 and grad_box is not touched.
+ *   2. Element.   x = cls[b][a][c] widened to fp32; z = x + logit_shift (the reference's quirk Q1, kept because K3's negatives and
+ *                 the inference scores carry it); e = expf(-|z|), r = 1 / (1 + e), sigma = z >= 0 ? r : e * r (focal_elem's form:
+ *                 no overflow, no cancellation for a small sigma); bce = (max(z, 0) - q * z) + log1pf(e); d = sigma - q;
+ *                 w = beta == 2 ? d * d : (beta == 0 ? 1 : powf(|d|, beta)); the row loss is l = w * bce.
+ *   3. Gradient.  dl / dx = w * (sigma - q) = w * d: the modulating weight is DETACHED, as K3 detaches it for every other class
+ *                 element (quirk Q3) -- the label element must not be the only one with another gradient form.  This DEVIATES from
+ *                 mmdet's quality_focal_loss, which differentiates through the weight.  The gradient is multiplied by
+ *                 scale_b = (1.0f / max(num_fg[b], 1)) * (1.0f / B), then by *grad_prescale when that is non-NULL, rounded ONCE to the
+ *                 I/O dtype and stored to that single element of grad_cls_levels.  No other class gradient element is written.
+ *   4. Sum.       out_loss[0] = (float)((double)out_loss[0] + sum over matched rows of (double)l * (double)scale_b), accumulated in
+ *                 double in a fixed order -- one partial per workgroup in its own workspace slot, then a one-wave final sum, no
+ *                 atomics -- so two calls on the same inputs give the same bits.  The normalisation stays K3's num_fg[b] (the count
+ *                 of matched rows), NOT GFL's sum of the qualities: the negatives K3 wrote are normalised by it already.
+ * Inputs as rn_box_iou_loss, plus cls_levels (as K3's) and gt_labels (i64, 1..K).  special_rows is REQUIRED and `matches` is read
+ * through its bits only.  reg_w: HOST float[4], each > 0.  beta finite and >= 0; logit_shift finite; K >= 1.  grad_cls_levels: NULL =
+ * value only.  Counts, offsets, labels and num_fg are read on the device; nothing synchronises, nothing is cleared, no workspace
+ * word needs a value on entry: the call is capturable as it stands.  workspace: 16-byte aligned,
+ * rn_quality_focal_loss_workspace_bytes(B, A) bytes (0 for arguments the call refuses).  Two launches: the row kernel (at most 128
+ * workgroups of 4 waves, a wave per 64 flag words of one image, grid-strided beyond that) and a one-wave sum.  RN_EINVAL: a null
+ * pointer, L outside 1..RN_MAX_LEVELS, B <= 0, K < 1, an unknown dtype, a negative or non-finite beta, a non-positive or non-finite
+ * reg_w; RN_EALIGN: boxes not 8-byte (16-bit) / 16-byte (fp32), class tensors not element aligned, anchors or GT boxes not 16-byte,
+ * 64-bit arrays not 8-byte aligned; RN_EWORKSPACE: workspace_bytes too small. */
+size_t rn_quality_focal_loss_workspace_bytes(int B, int64_t A);
+int rn_quality_focal_loss(const void *const *cls_levels, const void *const *box_levels, const int64_t *level_anchors, int L,
+                          int dtype, int B, int K, const float *anchors, int64_t anchor_bstride, const float *gt_boxes,
+                          const int64_t *gt_labels, const int32_t *gt_off, const int64_t *matches,
+                          const uint64_t *special_rows, const int32_t *num_fg, const float *reg_w, float beta,
+                          float logit_shift, const float *grad_prescale, float *out_loss, void *const *grad_cls_levels,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 /* K2 + K3 in ONE launch (round 4): the matcher of retinanet/box_utils.py:51-80 runs in the loss kernel's prologue -- every wave
  * matches the anchor rows of its own range against the image's GT boxes (one box per lane, so max_gt_per_image <= 64), the
  * per-image foreground counts meet in device-scope counters behind a grid barrier (the launch uses the resident grid only), and

@@ -73,6 +73,9 @@ SIGNATURES = {
     "rn_box_iou_loss_workspace_bytes": (_sz, [C.c_int, _i64]),
     "rn_box_iou_loss": (C.c_int, [C.POINTER(_vp), C.POINTER(_i64), C.c_int, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                   C.POINTER(_f32), C.c_int, _f32, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "rn_quality_focal_loss_workspace_bytes": (_sz, [C.c_int, _i64]),
+    "rn_quality_focal_loss": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i64,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _f32, _f32, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "rn_loss_workspace_bytes": (_sz, [C.c_int, _i64, C.c_int]),
     "rn_loss_fwd_bwd_levels_ex": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), C.c_int, C.c_int, C.c_int, C.c_int,
                                             _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(RnLossParams), _vp,

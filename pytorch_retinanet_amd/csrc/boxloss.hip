@@ -12,9 +12,7 @@
 //
 // Sum: every workgroup writes ONE double into its own slot of the workspace (always, zero included: no slot needs clearing), and a
 // one-wave kernel behind it adds the slots in a fixed order.  No atomics, so two calls give the same bits.
-#include "rn_common.hpp"
-
-#include <math.h>
+#include "rn_boxiou.hpp"
 
 namespace {
 
@@ -24,38 +22,7 @@ constexpr int BL_WORDS = RN_WAVE;                 // flag words per strip (one p
 constexpr int BL_ROWS = BL_WORDS * 64;            // rows per strip: 4 096, the capacity of a wave's list (offsets fit 16 bits)
 constexpr int BL_MAX_BLOCKS = 128;                // grid cap: 512 strips = 2 097 152 rows per pass (the train shape, B = 8, A = 201 600, is 400 strips)
 
-template <int DT> struct box4;                    // one row of four I/O elements <-> float[4] (as loss.hip's)
-template <> struct box4<RN_F32> {
-    static __device__ __forceinline__ void ld(const void *p, int64_t row, float (&f)[4]) {
-        const rn::f32x4 v = ((const rn::f32x4 *)p)[row];
-        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-    }
-    static __device__ __forceinline__ void st(void *p, int64_t row, const float (&f)[4]) {
-        rn::f32x4 v; v.x = f[0]; v.y = f[1]; v.z = f[2]; v.w = f[3];
-        ((rn::f32x4 *)p)[row] = v;
-    }
-};
-template <> struct box4<RN_BF16> {
-    static __device__ __forceinline__ void ld(const void *p, int64_t row, float (&f)[4]) {
-        const rn::u32x2 v = ((const rn::u32x2 *)p)[row];
-        f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-        f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-    }
-    static __device__ __forceinline__ void st(void *p, int64_t row, const float (&f)[4]) {
-        rn::u32x2 v; v.x = rn::dt<RN_BF16>::pk(f[0], f[1]); v.y = rn::dt<RN_BF16>::pk(f[2], f[3]);
-        ((rn::u32x2 *)p)[row] = v;
-    }
-};
-template <> struct box4<RN_F16> {
-    static __device__ __forceinline__ void ld(const void *p, int64_t row, float (&f)[4]) {
-        const rn::u32x2 v = ((const rn::u32x2 *)p)[row];
-        f[0] = rn::half_lo(v.x); f[1] = rn::half_hi(v.x); f[2] = rn::half_lo(v.y); f[3] = rn::half_hi(v.y);
-    }
-    static __device__ __forceinline__ void st(void *p, int64_t row, const float (&f)[4]) {
-        rn::u32x2 v; v.x = rn::dt<RN_F16>::pk(f[0], f[1]); v.y = rn::dt<RN_F16>::pk(f[2], f[3]);
-        ((rn::u32x2 *)p)[row] = v;
-    }
-};
+using rn::box4;
 
 struct BoxLossLevel { const void *box; void *gbox; int64_t base, A_l; };
 
@@ -77,28 +44,15 @@ struct BoxLossArgs {
     int32_t strips_per_image, total_strips;
 };
 
-// Steps 1-4 of the rule for one matched row: returns l, writes dl / dd[j] (unscaled).
+// Steps 1-4 of the rule for one matched row (1 and 2: rn::box_decode_iou): returns l, writes dl / dd[j] (unscaled).
 __device__ __forceinline__ float iou_row(const rn::f32x4 g, const rn::f32x4 an, const float (&d)[4], const float (&reg_w)[4],
                                          const int kind, float (&grad)[4])
 {
-    // 1. decode
-    const float t0 = d[0] / reg_w[0], t1 = d[1] / reg_w[1], t2 = d[2] / reg_w[2], t3 = d[3] / reg_w[3];
-    const float acx = (an.x + an.z) / 2.0f, acy = (an.y + an.w) / 2.0f, aw = an.z - an.x, ah = an.w - an.y;
-    const float cx = aw * t0 + acx, cy = ah * t1 + acy;
-    const bool clip_w = t2 > RN_BOX_XFORM_CLIP, clip_h = t3 > RN_BOX_XFORM_CLIP;
-    const float sw = clip_w ? RN_BOX_XFORM_CLIP : t2, sh = clip_h ? RN_BOX_XFORM_CLIP : t3;
-    const float w = aw * expf(sw), h = ah * expf(sh);
-    const float hw = w / 2.0f, hh = h / 2.0f;
-    const float px1 = cx - hw, py1 = cy - hh, px2 = cx + hw, py2 = cy + hh;
-    // 2. IoU (the predicted coordinate is selected -- and takes the derivative -- only on a strict comparison; a tie goes to the GT box)
-    const bool sx2 = px2 < g.z, sx1 = px1 > g.x, sy2 = py2 < g.w, sy1 = py1 > g.y;
-    const float iw0 = (sx2 ? px2 : g.z) - (sx1 ? px1 : g.x), ih0 = (sy2 ? py2 : g.w) - (sy1 ? py1 : g.y);
-    const bool pw = iw0 > 0.0f, ph = ih0 > 0.0f;
-    const float iw = pw ? iw0 : 0.0f, ih = ph ? ih0 : 0.0f;
-    const float inter = iw * ih;
-    const float uni = (w * h + (g.z - g.x) * (g.w - g.y)) - inter;
-    const bool pu = uni > 0.0f;
-    const float iou = pu ? inter / uni : 0.0f;
+    // 1. decode and 2. IoU: rn_boxiou.hpp (shared with qfl.hip)
+    const rn::BoxIou q = rn::box_decode_iou(g, an, d, reg_w);
+    const float aw = q.aw, ah = q.ah, cx = q.cx, cy = q.cy, w = q.w, h = q.h, px1 = q.px1, py1 = q.py1, px2 = q.px2, py2 = q.py2;
+    const bool clip_w = q.clip_w, clip_h = q.clip_h, sx2 = q.sx2, sx1 = q.sx1, sy2 = q.sy2, sy1 = q.sy1, pw = q.pw, ph = q.ph, pu = q.pu;
+    const float iw = q.iw, ih = q.ih, uni = q.uni, iou = q.iou;
     // 3. penalty (enclosing box: again the predicted coordinate only on a strict comparison)
     const bool ex2p = px2 > g.z, ex1p = px1 < g.x, ey2p = py2 > g.w, ey1p = py1 < g.y;
     const float ew = (ex2p ? px2 : g.z) - (ex1p ? px1 : g.x), eh = (ey2p ? py2 : g.w) - (ey1p ? py1 : g.y);

@@ -565,6 +565,9 @@ class CapturedTrainStep:
         # so is the box loss: an IoU kind adds ops.box_iou_loss's launches, and its weight is baked into them.  "smooth_l1" adds nothing.
         if getattr(crit, "box_loss", "smooth_l1") != "smooth_l1":
             key += (("box_loss", crit.box_loss, float(crit.box_loss_weight)),)
+        # and the class loss: "qfl" adds ops.quality_focal_loss's launches, and its beta is baked into them and into K3's.  "focal" adds nothing.
+        if getattr(crit, "cls_loss", "focal") != "focal":
+            key += (("cls_loss", crit.cls_loss, float(crit.qfl_beta)),)
         return key
 
     def _capture_segments(self, e: _Entry, images, targets) -> None:

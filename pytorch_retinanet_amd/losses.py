@@ -120,10 +120,17 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
     def forward(ctx, h, params, L, box_loss, *levels):
         """``h``: the ``MatchAhead`` of the batch.  ``box_loss``: None (K3's smooth-L1 as it is) or (kind, weight): ``ops.box_iou_loss``
         then runs right behind K3, on the same stream and with the same gradient pre-scale, and replaces the regression loss and the
-        matched rows' box gradients."""
-        cls_levels, box_levels = levels[:L], levels[L:]
+        matched rows' box gradients.  ``levels``: the L class and the L box outputs, optionally followed by ONE more argument, the
+        class loss: None (K3's focal loss as it is) or ("qfl", beta) -- ``params`` then carries ``alpha = 1, gamma = beta`` and
+        ``ops.quality_focal_loss`` runs behind K3 (and behind ``ops.box_iou_loss``) the same way, adding the matched label elements'
+        soft-target terms to the classification loss and storing their gradients."""
+        cls_levels, box_levels = levels[:L], levels[L:2 * L]
+        cls_loss = levels[2 * L] if len(levels) > 2 * L else None
+        ctx.extra = len(levels) - 2 * L
+        if cls_loss is not None and h.matches is None and h.max_gt is not None:
+            raise ValueError('cls_loss="qfl" reads the matcher\'s buffers and cannot run behind the fused match-and-loss kernel')
         dev = cls_levels[0].device
-        want_grad = any(ctx.needs_input_grad[4:])
+        want_grad = any(ctx.needs_input_grad[4:4 + 2 * L])
         fused = None
         if h.matches is None and h.max_gt is not None:
             # K2 runs INSIDE the loss kernel (one launch; box_utils.py:51-80 in the prologue of rn_loss_match_fwd_bwd_levels) unless
@@ -148,6 +155,10 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
             if box_loss is not None:
                 ops.box_iou_loss(box_levels, h.anchors, h.gt_boxes, h.gt_off, h.matches, h.num_fg, h.special, loss, gbox, box_loss[0],
                                  reg_w=tuple(params.reg_w), weight=box_loss[1], grad_prescale=pre)
+            if cls_loss is not None:
+                ops.quality_focal_loss(cls_levels, box_levels, h.anchors, h.gt_boxes, h.gt_labels, h.gt_off, h.matches, h.num_fg, h.special,
+                                       loss, gcls, beta=cls_loss[1], reg_w=tuple(params.reg_w), logit_shift=params.logit_shift,
+                                       grad_prescale=pre)
         ctx.grads = (gcls, gbox)
         ctx.meta = [(c.shape, c.dtype) for c in cls_levels] + [(b.shape, b.dtype) for b in box_levels]
         # two scalar outputs (views of the kernel's f32[2]): backward then receives the two upstream scalars directly, without
@@ -169,7 +180,7 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
             g0, g1 = g0.float() / pre.reshape(1), g1.float() / pre.reshape(1)
         ops.scale_inplace_batched(list(gcls) + list(gbox), [g0] * len(gcls) + [g1] * len(gbox))      # one launch
         outs = [t.view(shape) if t.dtype == dt else t.to(dt).view(shape) for t, (shape, dt) in zip(list(gcls) + list(gbox), ctx.meta)]
-        return (None,) * 4 + tuple(outs)
+        return (None,) * 4 + tuple(outs) + (None,) * ctx.extra
 
 
 def _resolve_gt(targets, dev: Optional[torch.device]):
@@ -225,14 +236,19 @@ def _check_box_loss(box_loss: str, box_loss_weight: float) -> None:
                          'the IoU box losses read the matcher\'s buffers; unset RN_FUSE_MATCH or use box_loss="smooth_l1"')
 
 
-def box_iou_loss_reference(deltas: Tensor, anchors: Tensor, gt: Tensor, kind: str, reg_w: Sequence[float] = BBOX_REG_WEIGHTS) -> Tensor:
-    """The rule of ``rn_box_iou_loss`` (include/retinanet_hip.h, steps 1-3) as differentiable torch code in ``deltas``' dtype: the row
-    losses l [N] of N matched rows -- ``deltas`` [N,4] the head's outputs, ``anchors`` / ``gt`` [N,4] each row's anchor and GT box.
-    Autograd through it is the gradient of step 4: every min / max is a ``torch.where`` on the strict comparison that selects the
-    predicted coordinate, so a tie goes to the GT coordinate and carries no derivative; a slot above the clip has zero gradient.
-    The per-image scale, the weight and the sum (steps 4-5) are the caller's."""
-    if kind not in ops.BOX_LOSS_KINDS:
-        raise ValueError(f"kind must be one of {tuple(ops.BOX_LOSS_KINDS)}, got {kind!r}")
+def _check_cls_loss(cls_loss: str, qfl_beta: float) -> None:
+    if cls_loss not in ops.CLS_LOSSES:
+        raise ValueError(f"cls_loss must be one of {ops.CLS_LOSSES}, got {cls_loss!r}")
+    if not (float(qfl_beta) >= 0.0 and float(qfl_beta) < float("inf")):
+        raise ValueError(f"qfl_beta must be finite and >= 0, got {qfl_beta!r}")
+    if cls_loss != "focal" and FUSE_MATCH:
+        raise ValueError(f'RN_FUSE_MATCH=1 keeps the match codes inside the loss kernel and cannot be combined with cls_loss="{cls_loss}": '
+                         'Quality Focal Loss reads the matcher\'s buffers; unset RN_FUSE_MATCH or use cls_loss="focal"')
+
+
+def _decode_iou(deltas: Tensor, anchors: Tensor, gt: Tensor, reg_w: Sequence[float]):
+    """Steps 1 and 2 of ``rn_box_iou_loss``'s rule in ``deltas``' dtype, ONE copy for ``box_iou_loss_reference`` and
+    ``box_quality_reference``: ((cx, cy), the decoded box (px1, py1, px2, py2), the GT coordinates, union, iou)."""
     dt = deltas.dtype
     an, g = anchors.to(dt), gt.to(dt)
     t = deltas / torch.tensor([float(v) for v in reg_w], dtype=dt, device=deltas.device)
@@ -250,6 +266,43 @@ def box_iou_loss_reference(deltas: Tensor, anchors: Tensor, gt: Tensor, kind: st
     inter = iw * ih
     union = (w * h + (gx2 - gx1) * (gy2 - gy1)) - inter
     iou = torch.where(union > 0, inter / torch.where(union > 0, union, torch.ones_like(union)), zero)
+    return (cx, cy), (px1, py1, px2, py2), (gx1, gy1, gx2, gy2), union, iou
+
+
+def box_quality_reference(deltas: Tensor, anchors: Tensor, gt: Tensor, reg_w: Sequence[float] = BBOX_REG_WEIGHTS) -> Tensor:
+    """Step 1 of ``rn_quality_focal_loss``'s rule (include/retinanet_hip.h) in ``deltas``' dtype: the quality q [N] of N matched rows,
+    the IoU of the standard-decoded box with the GT box -- steps 1 and 2 of ``box_iou_loss_reference``, the same code.  Detached: the
+    quality is a constant of the class loss, no gradient reaches the deltas through it."""
+    return _decode_iou(deltas, anchors, gt, reg_w)[4].detach()
+
+
+def quality_focal_loss_reference(logits: Tensor, quality: Tensor, beta: float = 2.0, logit_shift: float = LOGIT_SHIFT) -> Tensor:
+    """Steps 2 and 3 of ``rn_quality_focal_loss``'s rule as differentiable torch code in ``logits``' dtype: the losses l [N] of N label
+    elements ``logits`` [N] against their qualities ``quality`` [N] in [0, 1].  z = x + logit_shift; sigma from e = exp(-|z|) as the
+    kernel forms it; l = w * bce with bce = (max(z, 0) - q z) + log1p(e) and w = |sigma - q|^beta DETACHED (the library's quirk Q3;
+    mmdet differentiates through it), so autograd gives dl / dx = w * (sigma - q).  The per-image scale and the sum (steps 3-4)
+    are the caller's."""
+    q = quality.detach().to(logits.dtype)
+    z = logits + logit_shift
+    e = torch.exp(-z.abs())
+    r = 1 / (1 + e)
+    sigma = torch.where(z >= 0, r, e * r)
+    bce = (torch.clamp(z, min=0) - q * z) + torch.log1p(e)
+    d = (sigma - q).detach()
+    w = d * d if beta == 2 else (torch.ones_like(d) if beta == 0 else d.abs().pow(beta))
+    return w * bce
+
+
+def box_iou_loss_reference(deltas: Tensor, anchors: Tensor, gt: Tensor, kind: str, reg_w: Sequence[float] = BBOX_REG_WEIGHTS) -> Tensor:
+    """The rule of ``rn_box_iou_loss`` (include/retinanet_hip.h, steps 1-3) as differentiable torch code in ``deltas``' dtype: the row
+    losses l [N] of N matched rows -- ``deltas`` [N,4] the head's outputs, ``anchors`` / ``gt`` [N,4] each row's anchor and GT box.
+    Autograd through it is the gradient of step 4: every min / max is a ``torch.where`` on the strict comparison that selects the
+    predicted coordinate, so a tie goes to the GT coordinate and carries no derivative; a slot above the clip has zero gradient.
+    The per-image scale, the weight and the sum (steps 4-5) are the caller's."""
+    if kind not in ops.BOX_LOSS_KINDS:
+        raise ValueError(f"kind must be one of {tuple(ops.BOX_LOSS_KINDS)}, got {kind!r}")
+    (cx, cy), (px1, py1, px2, py2), (gx1, gy1, gx2, gy2), union, iou = _decode_iou(deltas, anchors, gt, reg_w)
+    zero = torch.zeros_like(px1)
     ew = torch.where(px2 > gx2, px2, gx2) - torch.where(px1 < gx1, px1, gx1)
     eh = torch.where(py2 > gy2, py2, gy2) - torch.where(py1 < gy1, py1, gy1)
     if kind == "giou":
@@ -264,7 +317,7 @@ def box_iou_loss_reference(deltas: Tensor, anchors: Tensor, gt: Tensor, kind: st
 
 class RetinaNetLosses(nn.Module):
     def __init__(self, num_classes: int, matcher: str = "iou", atss_topk: int = 9, cells=None, box_loss: str = "smooth_l1",
-                 box_loss_weight: float = 1.0) -> None:
+                 box_loss_weight: float = 1.0, cls_loss: str = "focal", qfl_beta: float = 2.0) -> None:
         """``matcher``: "iou" (K2: the reference's max-IoU rule with its 0.5 / 0.4 thresholds) or "atss" (``ops.atss_match``: a
         per-object threshold from the IoU statistics of the ``atss_topk`` nearest locations of every pyramid level; no ignored band).
         ATSS applies to the per-level path (``forward_levels`` / ``match_ahead``, what ``Retinanet.forward`` runs; ``forward`` /
@@ -273,10 +326,18 @@ class RetinaNetLosses(nn.Module):
         ``box_loss``: "smooth_l1" (the reference's encode-then-smooth-L1 inside K3; no further launch) or "giou" / "diou"
         (``ops.box_iou_loss`` behind K3: the loss of the decoded box against its GT box, times ``box_loss_weight``).  Like ATSS the IoU
         kinds apply to the per-level path and refuse ``RN_FUSE_MATCH=1``.  Inference is not affected by this argument: what decodes the
-        detections is ``Retinanet(box_decode=...)``, whose "standard" kind is the decode these losses train."""
+        detections is ``Retinanet(box_decode=...)``, whose "standard" kind is the decode these losses train.
+        ``cls_loss``: "focal" (the reference's sigmoid focal loss against a 0 / 1 target inside K3; no further launch) or "qfl"
+        (Quality Focal Loss, Li et al., NeurIPS 2020: K3 runs with ``alpha = 1, gamma = qfl_beta`` and ``ops.quality_focal_loss`` behind
+        it gives every matched row's label element the IoU of its decoded box with its GT box as target; the weight stays detached
+        and the normaliser ``num_fg``, see include/retinanet_hip.h).  Per-level path only, refuses ``RN_FUSE_MATCH=1``; composes with
+        both matchers and all three box losses.  CPU tensors with "qfl" go through the torch restatement (``matcher="atss"`` only:
+        the max-IoU matcher has no CPU form)."""
         super().__init__()
         _check_matcher(matcher, atss_topk)
         _check_box_loss(box_loss, box_loss_weight)
+        _check_cls_loss(cls_loss, qfl_beta)
+        self.cls_loss, self.qfl_beta = cls_loss, float(qfl_beta)
         self.box_loss, self.box_loss_weight = box_loss, float(box_loss_weight)
         self.matcher, self.atss_topk = matcher, int(atss_topk)
         self.cells = 9 if cells is None else cells
@@ -305,6 +366,10 @@ class RetinaNetLosses(nn.Module):
 
     # -- fused path ----------------------------------------------------------------------
     def _params(self):
+        if self.cls_loss == "qfl":
+            # K3 as QFL's negative term: alpha = 1 weighs every background element sigma^beta * BCE(sigma, 0) and every matched label
+            # element 1 - alpha = 0 (the contract rn_quality_focal_loss rests on)
+            return ops.make_loss_params(1.0, self.qfl_beta, self.beta, LOGIT_SHIFT, ENCODE_LOG_EPS, BBOX_REG_WEIGHTS)
         return ops.make_loss_params(self.alpha, self.gamma, self.beta, LOGIT_SHIFT, ENCODE_LOG_EPS, BBOX_REG_WEIGHTS)
 
     def _fused(self, cls: Tensor, box: Tensor, anchors, boxes: Sequence[Tensor], labels: Sequence[Tensor]) -> Tensor:
@@ -314,6 +379,9 @@ class RetinaNetLosses(nn.Module):
         if self.box_loss != "smooth_l1":
             # (the concatenated path has no flag words, and answering with smooth-L1 instead would be a silent change of loss)
             raise ValueError(f'box_loss="{self.box_loss}" runs on the per-level head outputs: use forward_levels / Retinanet.forward, not forward / calc_loss')
+        if self.cls_loss != "focal":
+            # (the concatenated path has no flag words, and answering with the focal loss instead would be a silent change of loss)
+            raise ValueError(f'cls_loss="{self.cls_loss}" runs on the per-level head outputs: use forward_levels / Retinanet.forward, not forward / calc_loss')
         dev = cls.device
         counts = [int(b.reshape(-1, 4).shape[0]) for b in boxes]
         gt_boxes = torch.cat([b.reshape(-1, 4).to(device=dev, dtype=torch.float32) for b in boxes]) \
@@ -381,6 +449,12 @@ class RetinaNetLosses(nn.Module):
         if self.box_loss != "smooth_l1":
             _check_box_loss(self.box_loss, self.box_loss_weight)
             box_loss = (self.box_loss, self.box_loss_weight)
+        extra = ()
+        if self.cls_loss != "focal":
+            _check_cls_loss(self.cls_loss, self.qfl_beta)
+            if not cls_levels[0].is_cuda:
+                return self._qfl_torch(targets, cls_levels, box_levels, anchors)
+            extra = ((self.cls_loss, self.qfl_beta),)
         h = ahead
         if h is None:
             # the matcher runs on this stream, from the Function (the level sizes: the per-level head outputs'); with RN_FUSE_MATCH it
@@ -392,8 +466,48 @@ class RetinaNetLosses(nn.Module):
                 h.max_gt = None
         if h.B != int(cls_levels[0].shape[0]):       # (the kernels read gt_off[0 .. B] of the head outputs' B)
             raise ValueError(f"targets (packed GT or a list) of {h.B} images for a batch of {int(cls_levels[0].shape[0])}")
-        out = _FusedDenseHeadLossLevels.apply(h, self._params(), len(cls_levels), box_loss, *cls_levels, *box_levels)
+        out = _FusedDenseHeadLossLevels.apply(h, self._params(), len(cls_levels), box_loss, *cls_levels, *box_levels, *extra)
         return {"classification_loss": out[0], "regression_loss": out[1]}
+
+    def _qfl_torch(self, targets, cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], anchors) -> Dict[str, Tensor]:
+        """``cls_loss="qfl"`` on CPU tensors, in plain differentiable torch from the restatements: what K3 (``alpha = 1,
+        gamma = qfl_beta``), ``ops.box_iou_loss`` and ``ops.quality_focal_loss`` compute on the device, in the outputs' dtype.  The
+        matcher is ``box_utils.atss_matcher``'s CPU restatement; the max-IoU matcher has none, so ``matcher="iou"`` is refused here."""
+        from .box_utils import atss_matcher, bbox_2_activ
+        if self.matcher != "atss":
+            raise ValueError('cls_loss="qfl" on CPU tensors needs matcher="atss": the max-IoU matcher runs on the device only')
+        if isinstance(targets, ops.PackedGT):
+            raise TypeError("packed GT (ops.PackedGT) lives on the device")
+        cls, box = torch.cat(list(cls_levels), 1), torch.cat(list(box_levels), 1)
+        anc = _stack_anchors(anchors)
+        sizes, B, dt = [int(c.shape[1]) for c in cls_levels], int(cls.shape[0]), cls.dtype
+        if len(targets) != B:
+            raise ValueError(f"targets of {len(targets)} images for a batch of {B}")
+        cls_total, reg_total = cls.new_zeros(()), cls.new_zeros(())
+        for b, t in enumerate(targets):
+            an = anc if anc.dim() == 2 else anc[b]
+            gt = t["boxes"].reshape(-1, 4).to(torch.float32)
+            m = atss_matcher(an, gt, sizes, self.cells, self.atss_topk) if gt.shape[0] else torch.full((an.shape[0],), -1, dtype=torch.int64)
+            rows = (m >= 0).nonzero().flatten()
+            scale = 1.0 / max(int(rows.numel()), 1)
+            z = cls[b] + LOGIT_SHIFT
+            neg = torch.sigmoid(z.detach()).pow(self.qfl_beta) * F.softplus(z)          # sigma^beta * BCE(sigma, 0), the weight detached
+            if rows.numel():
+                g, d = gt[m[rows]], box[b, rows]
+                c = t["labels"].reshape(-1).to(torch.int64)[m[rows]] - 1
+                keep = torch.ones_like(neg, dtype=torch.bool)
+                keep[rows, c] = False                                                    # the label elements: K3's weight there is 0
+                q = box_quality_reference(d, an[rows], g, BBOX_REG_WEIGHTS)
+                pos = quality_focal_loss_reference(cls[b, rows, c], q, self.qfl_beta, LOGIT_SHIFT)
+                cls_total = cls_total + ((neg * keep).sum() + pos.sum()) * scale
+                if self.box_loss == "smooth_l1":
+                    reg = self.smooth_l1_loss(d, bbox_2_activ(g.to(dt), an[rows].to(dt)))
+                else:
+                    reg = box_iou_loss_reference(d, an[rows], g, self.box_loss, BBOX_REG_WEIGHTS).sum() * self.box_loss_weight
+                reg_total = reg_total + reg * scale
+            else:
+                cls_total = cls_total + neg.sum() * scale
+        return {"classification_loss": cls_total / B, "regression_loss": reg_total / B}
 
     def calc_loss(self, anchors: Tensor, clas_pred: Tensor, bbox_pred: Tensor, clas_tgt: Tensor,
                   bbox_tgt: Tensor) -> Tuple[Tensor, Tensor]:

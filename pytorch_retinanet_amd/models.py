@@ -59,6 +59,8 @@ class Retinanet(nn.Module):
         nms: Optional[str] = None,
         soft_nms_sigma: Optional[float] = None,
         soft_nms_min_score: Optional[float] = None,
+        cls_loss: Optional[str] = None,
+        qfl_beta: Optional[float] = None,
     ) -> None:
         """``matcher``: how anchors are labelled -- None / "iou" (the reference's max-IoU rule, K2) or "atss" (``ops.atss_match``,
         with ``atss_topk`` nearest locations per level and object, None -> 9); ``model: {matcher: atss}`` in the hparams.
@@ -74,8 +76,17 @@ class Retinanet(nn.Module):
         which lowers the score of a box that overlaps a picked one instead of dropping it: "soft_linear" (by 1 - IoU where IoU >
         ``nms_thres``) or "soft_gaussian" (by exp(-IoU^2 / ``soft_nms_sigma``), None -> 0.5); a class ends when its best remaining score
         is not above ``soft_nms_min_score`` (None -> 1e-3); ``model: {nms: soft_gaussian}`` in the hparams.  Stored as ``net.nms``,
-        ``net.soft_nms_sigma`` and ``net.soft_nms_min_score`` and read at every call (``ops.detect_levels``)."""
+        ``net.soft_nms_sigma`` and ``net.soft_nms_min_score`` and read at every call (``ops.detect_levels``).
+        ``cls_loss``: the classification loss -- None / "focal" (the reference's, inside K3) or "qfl" (Quality Focal Loss:
+        ``ops.quality_focal_loss`` behind K3; the label element's target is the IoU of the row's standard-decoded box with its GT
+        box, the exponent ``qfl_beta``, None -> 2.0); ``model: {cls_loss: qfl, qfl_beta: 2.0}`` in the hparams.  Training only: the
+        score already is what NMS and the evaluator rank.  The quality is the IoU of the box ``box_decode="standard"`` decodes, so
+        "qfl" with the reference decode logs a warning here, as "giou" / "diou" do."""
         super().__init__()
+        cls_loss = ifnone(cls_loss, "focal")
+        if cls_loss not in ops.CLS_LOSSES:
+            raise ValueError(f"cls_loss must be one of {ops.CLS_LOSSES}, got {cls_loss!r}")
+        qfl_beta = ifnone(qfl_beta, 2.0)
         nms = ifnone(nms, "hard")
         if nms not in ops.NMS_KINDS:
             raise ValueError(f"nms must be one of {ops.NMS_KINDS}, got {nms!r}")
@@ -115,7 +126,8 @@ class Retinanet(nn.Module):
         self.anchor_generator = anchor_generator
         num_anchors = self.anchor_generator.num_cell_anchors[0]
         self.retinanet_head = RetinaNetHead(256, 256, num_anchors, num_classes, prior, matcher=matcher, atss_topk=atss_topk,
-                                            cells=self.anchor_generator.num_anchors, box_loss=box_loss, box_loss_weight=box_loss_weight)
+                                            cells=self.anchor_generator.num_anchors, box_loss=box_loss, box_loss_weight=box_loss_weight,
+                                            cls_loss=cls_loss, qfl_beta=qfl_beta)
 
         self.score_thres = score_thres
         self.nms_thres = nms_thres
@@ -129,6 +141,10 @@ class Retinanet(nn.Module):
             logger.warning(f'box_loss="{box_loss}" trains the box that box_decode="standard" decodes, but this model infers with the '
                            'reference decode (sizes from exp(dx), exp(dy)): pass box_decode="standard" (model: {box_decode: standard}) '
                            "to evaluate what was trained")
+        if cls_loss == "qfl" and box_decode == "reference":
+            logger.warning('cls_loss="qfl" trains the class score towards the IoU of the box that box_decode="standard" decodes, but this '
+                           'model infers with the reference decode (sizes from exp(dx), exp(dy)): pass box_decode="standard" '
+                           "(model: {box_decode: standard}) so that the score ranks the box it was trained on")
 
         logger.info(f"BACKBONE     : {backbone_kind}")
         logger.info(f"INPUT_PARAMS : MAX_SIZE={max_size}, MIN_SIZE={min_size}")

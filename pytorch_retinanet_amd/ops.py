@@ -604,6 +604,47 @@ def box_iou_loss(box_levels: Sequence[Tensor], anchors: Tensor, gt_boxes: Tensor
     return loss
 
 
+# ---- Quality Focal Loss ------------------------------------------------------------------------------------------------------
+CLS_LOSSES = ("focal", "qfl")
+
+
+def quality_focal_loss(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], anchors: Tensor, gt_boxes: Tensor, gt_labels: Tensor,
+                       gt_off: Tensor, matches: Tensor, num_fg: Tensor, special: Tensor, loss: Tensor, gcls: Optional[Sequence[Tensor]],
+                       beta: float = 2.0, reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0), logit_shift: float = 1.0,
+                       grad_prescale: Optional[Tensor] = None) -> Tensor:
+    """The soft-target term of Quality Focal Loss on the matched rows' label elements, BEHIND a ``loss_fwd_bwd_levels`` call made with
+    ``alpha = 1, gamma = beta`` on the same stream (``rn_quality_focal_loss``; the rule: include/retinanet_hip.h, restated by
+    ``losses.box_quality_reference`` and ``losses.quality_focal_loss_reference``).  Takes K3's outputs -- ``loss`` f32[2] and the
+    ``gcls`` list (None: value only) -- and the matcher's three buffers, and updates IN PLACE: the label elements' sum is added to
+    ``loss[0]`` and their one gradient element each is stored into ``gcls``; ``loss[1]`` and every other element keep what K3 wrote.
+    ``cls_levels`` / ``box_levels``: the head's outputs, [B,A_l,K] / [B,A_l,4] in ``gcls``'s dtype; ``special`` (the flag words) is
+    required: ``matches`` is read through them only.  ``grad_prescale`` as K3's.  No synchronisation, nothing cleared: capturable.
+    Returns ``loss``."""
+    beta = float(beta)
+    if not (beta >= 0.0 and beta < float("inf")):
+        raise ValueError(f"beta must be finite and >= 0, got {beta!r}")
+    if gcls is not None and len(gcls) != len(cls_levels):
+        raise ValueError("need as many gradient tensors as levels of class outputs")
+    a = _LevelArgs(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off, matches, num_fg, special, loss, *(gcls or ()))
+    B, A = a.B, a.A
+    for l, (c, g) in enumerate(zip(a.cls, gcls or ())):
+        if g.shape != c.shape or g.dtype != c.dtype or not g.is_contiguous():
+            raise ValueError(f"gcls[{l}]: expected a contiguous {c.dtype} {tuple(c.shape)}, got {g.dtype} {tuple(g.shape)}")
+    _check_special(special, B, A)
+    if matches.dtype != torch.int64 or matches.numel() != B * A or not matches.is_contiguous():
+        raise ValueError(f"matches: expected a contiguous int64 [{B}, {A}], got {matches.dtype} {tuple(matches.shape)}")
+    if loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
+        raise ValueError("loss: expected K3's float32[2]")
+    _check_prescale(grad_prescale, loss)
+    ws = torch.empty((max(lib.rn_quality_focal_loss_workspace_bytes(B, A), 16),), dtype=torch.uint8, device=a.dev)
+    with torch.cuda.device(a.dev), _timed("quality_focal_loss", a.dev):
+        check(lib.rn_quality_focal_loss(a.arr(a.cls), a.arr(a.box), a.counts, a.L, a.code, B, a.K, _ptr(a.anchors), a.bstride,
+                                        _ptr(a.gt_boxes), _ptr(a.gt_labels), _ptr(gt_off), _ptr(matches), _ptr(special), _ptr(num_fg),
+                                        (C.c_float * 4)(*[float(v) for v in reg_w]), beta, float(logit_shift), _ptr(grad_prescale),
+                                        _ptr(loss), a.arr(gcls), _ptr(ws), ws.numel(), _stream(a.dev)), "rn_quality_focal_loss")
+    return loss
+
+
 # ---- K2 + K3 in one launch -------------------------------------------------------------------------------------------------
 # State words of rn_loss_match_fwd_bwd_levels (grid-barrier counter + per-image foreground counters): zero-filled ONCE, left
 # zero-filled by every completed call, never shared by two streams (one buffer per device and stream).  A hipGraph capture gets
