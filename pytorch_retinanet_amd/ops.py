@@ -562,6 +562,30 @@ def loss_fwd_bwd_levels(cls_levels: Sequence[Tensor], box_levels: Sequence[Tenso
     return out, gcls, gbox
 
 
+def _matched_rows_args(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off, matches: Tensor, num_fg,
+                       special: Tensor, loss: Tensor, grads: Optional[Sequence[Tensor]], reg_w: Sequence[float],
+                       grad_prescale: Optional[Tensor], workspace_bytes):
+    """What the ops behind K3 that walk the matcher's flagged rows share: the checks of their common arguments -- ``grads`` (None:
+    value only) goes level by level with the class outputs when there are any, otherwise with the box outputs -- and
+    (the ``_LevelArgs``, ``reg_w`` as ctypes f32[4], the workspace)."""
+    preds, what, gname = (box_levels, "box", "gbox") if cls_levels is None else (cls_levels, "class", "gcls")
+    if grads is not None and len(grads) != len(preds):
+        raise ValueError(f"need as many gradient tensors as levels of {what} outputs")
+    a = _LevelArgs(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off, matches, num_fg, special, loss, *(grads or ()),
+                   dt=grads[0].dtype if grads is not None and cls_levels is None else None)
+    for l, (p, g) in enumerate(zip(a.box if cls_levels is None else a.cls, grads or ())):
+        if g.shape != p.shape or g.dtype != p.dtype or not g.is_contiguous():
+            raise ValueError(f"{gname}[{l}]: expected a contiguous {p.dtype} {tuple(p.shape)}, got {g.dtype} {tuple(g.shape)}")
+    _check_special(special, a.B, a.A)
+    if matches.dtype != torch.int64 or matches.numel() != a.B * a.A or not matches.is_contiguous():
+        raise ValueError(f"matches: expected a contiguous int64 [{a.B}, {a.A}], got {matches.dtype} {tuple(matches.shape)}")
+    if loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
+        raise ValueError("loss: expected K3's float32[2]")
+    _check_prescale(grad_prescale, loss)
+    ws = torch.empty((max(workspace_bytes(a.B, a.A), 16),), dtype=torch.uint8, device=a.dev)
+    return a, (C.c_float * 4)(*[float(v) for v in reg_w]), ws
+
+
 # ---- IoU-type box regression losses -----------------------------------------------------------------------------------------
 BOX_LOSSES = ("smooth_l1", "giou", "diou")
 BOX_LOSS_KINDS = {"giou": 1, "diou": 2}                       # RN_BOX_LOSS_GIOU / RN_BOX_LOSS_DIOU
@@ -581,26 +605,12 @@ def box_iou_loss(box_levels: Sequence[Tensor], anchors: Tensor, gt_boxes: Tensor
         raise ValueError(f"kind must be one of {tuple(BOX_LOSS_KINDS)}, got {kind!r}")
     if not float(weight) > 0.0:
         raise ValueError(f"weight must be positive, got {weight!r}")
-    if gbox is not None and len(gbox) != len(box_levels):
-        raise ValueError("need as many gradient tensors as levels of box outputs")
-    a = _LevelArgs(None, box_levels, anchors, gt_boxes, None, gt_off, matches, num_fg, special, loss, *(gbox or ()),
-                   dt=None if gbox is None else gbox[0].dtype)
-    B, A = a.B, a.A
-    for l, (b, g) in enumerate(zip(a.box, gbox or ())):
-        if g.shape != b.shape or g.dtype != b.dtype or not g.is_contiguous():
-            raise ValueError(f"gbox[{l}]: expected a contiguous {b.dtype} {tuple(b.shape)}, got {g.dtype} {tuple(g.shape)}")
-    _check_special(special, B, A)
-    if matches.dtype != torch.int64 or matches.numel() != B * A or not matches.is_contiguous():
-        raise ValueError(f"matches: expected a contiguous int64 [{B}, {A}], got {matches.dtype} {tuple(matches.shape)}")
-    if loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
-        raise ValueError("loss: expected K3's float32[2]")
-    _check_prescale(grad_prescale, loss)
-    ws = torch.empty((max(lib.rn_box_iou_loss_workspace_bytes(B, A), 16),), dtype=torch.uint8, device=a.dev)
+    a, reg_w, ws = _matched_rows_args(None, box_levels, anchors, gt_boxes, None, gt_off, matches, num_fg, special, loss, gbox,
+                                      reg_w, grad_prescale, lib.rn_box_iou_loss_workspace_bytes)
     with torch.cuda.device(a.dev), _timed("box_iou_loss", a.dev):
-        check(lib.rn_box_iou_loss(a.arr(a.box), a.counts, a.L, a.code, B, _ptr(a.anchors), a.bstride, _ptr(a.gt_boxes), _ptr(gt_off),
-                                  _ptr(matches), _ptr(special), _ptr(num_fg), (C.c_float * 4)(*[float(v) for v in reg_w]),
-                                  BOX_LOSS_KINDS[kind], float(weight), _ptr(grad_prescale), _ptr(loss), a.arr(gbox), _ptr(ws), ws.numel(),
-                                  _stream(a.dev)), "rn_box_iou_loss")
+        check(lib.rn_box_iou_loss(a.arr(a.box), a.counts, a.L, a.code, a.B, _ptr(a.anchors), a.bstride, _ptr(a.gt_boxes), _ptr(gt_off),
+                                  _ptr(matches), _ptr(special), _ptr(num_fg), reg_w, BOX_LOSS_KINDS[kind], float(weight),
+                                  _ptr(grad_prescale), _ptr(loss), a.arr(gbox), _ptr(ws), ws.numel(), _stream(a.dev)), "rn_box_iou_loss")
     return loss
 
 
@@ -623,25 +633,13 @@ def quality_focal_loss(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor
     beta = float(beta)
     if not (beta >= 0.0 and beta < float("inf")):
         raise ValueError(f"beta must be finite and >= 0, got {beta!r}")
-    if gcls is not None and len(gcls) != len(cls_levels):
-        raise ValueError("need as many gradient tensors as levels of class outputs")
-    a = _LevelArgs(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off, matches, num_fg, special, loss, *(gcls or ()))
-    B, A = a.B, a.A
-    for l, (c, g) in enumerate(zip(a.cls, gcls or ())):
-        if g.shape != c.shape or g.dtype != c.dtype or not g.is_contiguous():
-            raise ValueError(f"gcls[{l}]: expected a contiguous {c.dtype} {tuple(c.shape)}, got {g.dtype} {tuple(g.shape)}")
-    _check_special(special, B, A)
-    if matches.dtype != torch.int64 or matches.numel() != B * A or not matches.is_contiguous():
-        raise ValueError(f"matches: expected a contiguous int64 [{B}, {A}], got {matches.dtype} {tuple(matches.shape)}")
-    if loss.dtype != torch.float32 or loss.numel() != 2 or not loss.is_contiguous():
-        raise ValueError("loss: expected K3's float32[2]")
-    _check_prescale(grad_prescale, loss)
-    ws = torch.empty((max(lib.rn_quality_focal_loss_workspace_bytes(B, A), 16),), dtype=torch.uint8, device=a.dev)
+    a, reg_w, ws = _matched_rows_args(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off, matches, num_fg, special,
+                                      loss, gcls, reg_w, grad_prescale, lib.rn_quality_focal_loss_workspace_bytes)
     with torch.cuda.device(a.dev), _timed("quality_focal_loss", a.dev):
-        check(lib.rn_quality_focal_loss(a.arr(a.cls), a.arr(a.box), a.counts, a.L, a.code, B, a.K, _ptr(a.anchors), a.bstride,
+        check(lib.rn_quality_focal_loss(a.arr(a.cls), a.arr(a.box), a.counts, a.L, a.code, a.B, a.K, _ptr(a.anchors), a.bstride,
                                         _ptr(a.gt_boxes), _ptr(a.gt_labels), _ptr(gt_off), _ptr(matches), _ptr(special), _ptr(num_fg),
-                                        (C.c_float * 4)(*[float(v) for v in reg_w]), beta, float(logit_shift), _ptr(grad_prescale),
-                                        _ptr(loss), a.arr(gcls), _ptr(ws), ws.numel(), _stream(a.dev)), "rn_quality_focal_loss")
+                                        reg_w, beta, float(logit_shift), _ptr(grad_prescale), _ptr(loss), a.arr(gcls), _ptr(ws),
+                                        ws.numel(), _stream(a.dev)), "rn_quality_focal_loss")
     return loss
 
 
