@@ -165,6 +165,54 @@ int rn_atss_match(const float *anchors, int64_t anchor_bstride,
                   int64_t *matches, int32_t *num_fg, uint64_t *special_rows, int64_t total_gt, int flags,
                   void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Task-aligned matcher (round 36; not in the reference) --------------------
+ * Task-aligned assignment (TAL: Feng et al., "TOOD", ICCV 2021; the assigner of PP-YOLOE, YOLOv8 and RTMDet-style heads) as a third
+ * matcher that fills K2's three outputs.  Unlike K2 and ATSS it reads the head's OUTPUTS: the positives of an object are the anchors
+ * whose predicted class score and predicted box are best for it.  Inputs: the per-level head outputs as rn_quality_focal_loss takes
+ * them (cls_levels / box_levels / level_anchors / L / dtype / B / K), the anchors and GT arrays as K3 takes them, cells i32[L] (HOST;
+ * anchors per grid location) and level_w i32[L] (HOST, nullable; see "Walk").  Every fp32 step is one correctly rounded operation
+ * (no FMA contraction); expf is the device library's.
+ *   1. Candidates.  acx = (x1 + x2) * 0.5f, acy = (y1 + y2) * 0.5f (the ATSS rule's centres).  For GT row g (box G, label c =
+ *                   gt_labels[g] in 1..K) of image b, anchor a is a candidate iff gx1 < acx && acx < gx2 && gy1 < acy && acy < gy2
+ *                   (strict: a centre on the edge is outside).  A row whose label is outside 1..K, or whose box has a non-finite
+ *                   coordinate or !(gx2 > gx1) or !(gy2 > gy1), has no candidates; it is never an error.
+ *   2. Metric.      x = cls[b][a][c - 1] widened to fp32; z = x + logit_shift; e = expf(-|z|), r = 1 / (1 + e), s = z >= 0 ? r : e * r
+ *                   (step 2 of rn_quality_focal_loss's rule: focal_elem's sigmoid).  u = the IoU of steps 1 and 2 of rn_box_iou_loss's
+ *                   rule, unchanged (the same code): the standard decode of box[b][a][0..3] with reg_w and RN_BOX_XFORM_CLIP against G.
+ *                   m = 1.0f; alpha times m = m * s; then beta times m = m * u: a fixed left-to-right chain of fp32 products, no
+ *                   powf.  alpha, beta: integers in 0..8 (TOOD's and mmdet's 1 and 6 are the defaults of the Python surface).
+ *                   A candidate is DROPPED unless m > 0 && m < inf && u >= 0 (a NaN fails).
+ *   3. Selection.   Per GT row the topk candidates with the largest m over all levels together, ties to the lower anchor index:
+ *                   the topk smallest 64-bit keys (~bits(m) << 32) | anchor index (the ATSS key construction with the complemented
+ *                   metric bits in place of d2's: positive floats order as their bit patterns).  Fewer than topk candidates: all.
+ *   4. Conflicts.   An anchor selected for several rows of its image goes to the row with the largest fp32 u, ties to the lowest
+ *                   GT index: rn_atss_match's [B][A] table of (bits(u) << 32) | ~gt index under a 64-bit atomicMax, and its emit.
+ *   5. Output.      matches[b][a] = that GT index within the image, else -1 (there is no ignored band: -2 never appears);
+ *                   num_fg[b] = the count of positives; special_rows bit = [matches != -1].  An image without GT rows is all
+ *                   background.  The predictions are read as constants: nothing is differentiated through the assignment.
+ * Two deviations from mmdet's TaskAlignedAssigner: the centre test (step 1) comes BEFORE the top-k, which is ultralytics' order
+ * (mmdet selects the top-k first and then drops selected anchors whose centre lies outside) -- it is what bounds the walk to the
+ * cells under the box; and the class target stays rn_quality_focal_loss's IoU: TOOD's per-object normalised metric as soft target
+ * is not part of this matcher.
+ * Walk.  level_w[l] > 0 promises that level l is a grid of level_w[l] columns, row-major in (y, x) with the cells[l] anchors of a
+ * location adjacent, whose centres are cell (0, 0)'s plus (x * step_x, y * step_y) to within one cell (every grid anchor generator,
+ * shifted per image or not).  A (GT row, level) workgroup then visits only the cells under its box, widened by one cell on every
+ * side, and applies step 1 to every anchor it visits, so the promise bounds the walk and never decides a candidate.  level_w NULL
+ * or level_w[l] == 0: level l is walked whole, for any anchor layout.  level_anchors[l] must be a multiple of level_w[l] * cells[l].
+ * flags, total_gt, gt_off, the workspace's zeroed conflict table: as rn_atss_match; workspace at least
+ * rn_tal_match_workspace_bytes(...) (0 for arguments the call refuses).  Four launches, no synchronisation, no float atomics, no
+ * [T, A] matrix; capturable; two calls give the same bits.  rn_tal_match_list_keys(): the capacity of a workgroup's candidate list
+ * (a box over more candidates is compacted on the way; for tests).  RN_EUNSUPPORTED: topk above 64.  RN_EINVAL: a null pointer,
+ * L outside 1..RN_MAX_LEVELS, B outside 1..65535, K < 1, topk < 1, alpha or beta outside 0..8, an unknown dtype, a non-finite
+ * logit_shift, a non-positive or non-finite reg_w, a level that is not a multiple of its grid row. */
+int rn_tal_match_list_keys(void);
+size_t rn_tal_match_workspace_bytes(int B, int64_t A, int64_t total_gt, int L, int topk);
+int rn_tal_match(const void *const *cls_levels, const void *const *box_levels, const int64_t *level_anchors, const int32_t *cells,
+                 const int32_t *level_w, int L, int dtype, int B, int K, const float *anchors, int64_t anchor_bstride,
+                 const float *gt_boxes, const int64_t *gt_labels, const int32_t *gt_off, int topk, int alpha, int beta,
+                 const float *reg_w, float logit_shift, int64_t *matches, int32_t *num_fg, uint64_t *special_rows,
+                 int64_t total_gt, int flags, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- K3 loss_fwd_bwd --------------------------------------------------------
  * Replaces RetinaNetLosses.forward / calc_loss / focal_loss / smooth_l1_loss,
  * retinanet/losses.py:19-145, and bbox_2_activ, retinanet/box_utils.py:25-34:

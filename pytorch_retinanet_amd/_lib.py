@@ -70,6 +70,11 @@ SIGNATURES = {
     "rn_atss_match_workspace_bytes": (_sz, [C.c_int, _i64, _i64, C.POINTER(_i64), C.POINTER(_i32), C.c_int, C.c_int]),
     "rn_atss_match": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _i64, C.POINTER(_i64), C.POINTER(_i32), C.c_int, C.c_int,
                                 _vp, _vp, _vp, _i64, C.c_int, _vp, _sz, _vp]),
+    "rn_tal_match_list_keys": (C.c_int, []),
+    "rn_tal_match_workspace_bytes": (_sz, [C.c_int, _i64, _i64, C.c_int, C.c_int]),
+    "rn_tal_match": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32), C.c_int, C.c_int, C.c_int,
+                               C.c_int, _vp, _i64, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_f32), _f32, _vp, _vp, _vp, _i64,
+                               C.c_int, _vp, _sz, _vp]),
     "rn_box_iou_loss_workspace_bytes": (_sz, [C.c_int, _i64]),
     "rn_box_iou_loss": (C.c_int, [C.POINTER(_vp), C.POINTER(_i64), C.c_int, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                   C.POINTER(_f32), C.c_int, _f32, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),

@@ -11,7 +11,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .config import BBOX_REG_WEIGHTS, ENCODE_LOG_EPS, IOU_THRESHOLDS_BACKGROUND, IOU_THRESHOLDS_FOREGROUND
+from .config import BBOX_REG_WEIGHTS, ENCODE_LOG_EPS, IOU_THRESHOLDS_BACKGROUND, IOU_THRESHOLDS_FOREGROUND, LOGIT_SHIFT
 from .utilities import ifnone
 
 
@@ -237,6 +237,123 @@ def atss_matcher(anchors: Tensor, targets: Tensor, level_sizes, cells, topk: int
                 i = cand[j]
                 if iou[j] > best[i]:                        # strict: an equal IoU keeps the lower target index
                     best[i], matches[i] = iou[j], g
+    return torch.from_numpy(matches)
+
+
+def _exp_f32(v):
+    "exp of an fp32 array computed through double and rounded once (what the device library's expf gives, up to an ulp)."
+    import numpy as np
+    with np.errstate(all="ignore"):
+        return np.exp(v.astype(np.float64)).astype(np.float32)
+
+
+def task_aligned_metric(logits, deltas, anchors, target, alpha: int = 1, beta: int = 6, reg_w=BBOX_REG_WEIGHTS, logit_shift: float = LOGIT_SHIFT):
+    """Step 2 of the task-aligned rule for ONE GT box against n anchors, every step one rounded numpy fp32 operation: ``logits`` [n]
+    (the label's logit of every anchor), ``deltas`` [n,4], ``anchors`` [n,4], ``target`` [4], all numpy fp32 -> (m [n], u [n], s [n]):
+    the metric, the IoU of the standard-decoded box and the score.  The two ``exp`` go through double and are rounded once."""
+    import numpy as np
+    one, two, zero = np.float32(1.0), np.float32(2.0), np.float32(0.0)
+    with np.errstate(all="ignore"):
+        z = logits + np.float32(logit_shift)
+        e = _exp_f32(-np.abs(z))
+        r = one / (one + e)
+        s = np.where(z >= zero, r, e * r)
+        rw = np.asarray([float(v) for v in reg_w], dtype=np.float32)
+        t = deltas / rw
+        acx, acy = (anchors[:, 0] + anchors[:, 2]) / two, (anchors[:, 1] + anchors[:, 3]) / two
+        aw, ah = anchors[:, 2] - anchors[:, 0], anchors[:, 3] - anchors[:, 1]
+        cx, cy = aw * t[:, 0] + acx, ah * t[:, 1] + acy
+        clip = np.float32(ops.BOX_XFORM_CLIP)
+        sw, sh = np.where(t[:, 2] > clip, clip, t[:, 2]), np.where(t[:, 3] > clip, clip, t[:, 3])
+        w, h = aw * _exp_f32(sw), ah * _exp_f32(sh)
+        hw, hh = w / two, h / two
+        px1, py1, px2, py2 = cx - hw, cy - hh, cx + hw, cy + hh
+        gx1, gy1, gx2, gy2 = target
+        iw = np.where(px2 < gx2, px2, gx2) - np.where(px1 > gx1, px1, gx1)
+        ih = np.where(py2 < gy2, py2, gy2) - np.where(py1 > gy1, py1, gy1)
+        iw, ih = np.where(iw > zero, iw, zero), np.where(ih > zero, ih, zero)
+        inter = iw * ih
+        union = (w * h + (gx2 - gx1) * (gy2 - gy1)) - inter
+        u = np.where(union > zero, inter / np.where(union > zero, union, one), zero).astype(np.float32)
+        m = np.ones_like(s)
+        for _ in range(int(alpha)):
+            m = m * s
+        for _ in range(int(beta)):
+            m = m * u
+    return m.astype(np.float32), u, s.astype(np.float32)
+
+
+def task_aligned_candidates(cls, box, anchors, target, label: int, topk: int = 13, alpha: int = 1, beta: int = 6,
+                            reg_w=BBOX_REG_WEIGHTS, logit_shift: float = LOGIT_SHIFT):
+    """Steps 1-3 of the task-aligned rule for ONE GT row: (the selected anchors, best first; their u; ALL candidates in rank order;
+    their m) as numpy arrays.  ``cls`` [A,K] / ``box`` [A,4] / ``anchors`` [A,4] / ``target`` [4]: numpy fp32; ``label`` in 1..K."""
+    import numpy as np
+    none = (np.zeros((0,), np.int64), np.zeros((0,), np.float32), np.zeros((0,), np.int64), np.zeros((0,), np.float32))
+    K = cls.shape[1]
+    if not (1 <= int(label) <= K) or not np.isfinite(target).all() or not (target[2] > target[0]) or not (target[3] > target[1]):
+        return none
+    half = np.float32(0.5)
+    acx, acy = (anchors[:, 0] + anchors[:, 2]) * half, (anchors[:, 1] + anchors[:, 3]) * half
+    cand = np.nonzero((acx > target[0]) & (acx < target[2]) & (acy > target[1]) & (acy < target[3]))[0]
+    if cand.size == 0:
+        return none
+    m, u, _ = task_aligned_metric(cls[cand, int(label) - 1], box[cand], anchors[cand], target, alpha, beta, reg_w, logit_shift)
+    with np.errstate(all="ignore"):
+        keep = (m > 0) & (m < np.inf) & (u >= 0)
+    cand, m, u = cand[keep], m[keep], u[keep]
+    key = ((~m.view(np.uint32)).astype(np.uint64) << np.uint64(32)) | cand.astype(np.uint64)     # largest m first, ties to the lower index
+    order = np.argsort(key, kind="stable")
+    sel = order[:int(topk)]
+    return cand[sel].astype(np.int64), u[sel], cand[order].astype(np.int64), m[order]
+
+
+def task_aligned_matcher(cls: Tensor, box: Tensor, anchors: Tensor, targets: Tensor, labels: Tensor, topk: int = 13, alpha: int = 1,
+                         beta: int = 6, reg_w=BBOX_REG_WEIGHTS, logit_shift: float = LOGIT_SHIFT, level_sizes=None, cells=9) -> Tensor:
+    """Task-aligned assignment (TOOD, Feng et al., ICCV 2021) of ONE image: the head's outputs ``cls`` [A,K] / ``box`` [A,4] (any float
+    dtype: widened to fp32), ``anchors`` [A,4], ``targets`` [T,4], ``labels`` [T] in 1..K -> i64 [A], -1 background, else the target
+    index (there is no ignored band).  CUDA tensors go to the HIP kernel (``ops.tal_match``; ``level_sizes`` / ``cells`` are its level
+    layout, default one level); CPU tensors run this restatement of the numbered rule in include/retinanet_hip.h, operation for
+    operation in numpy fp32:
+      1. candidates of a row: the anchors whose centre ((x1 + x2) * 0.5f, (y1 + y2) * 0.5f) lies strictly inside the box; none for a
+         label outside 1..K or a non-finite / empty box;
+      2. s = the sigmoid of the label's logit + logit_shift from e = exp(-|z|) (r = 1 / (1 + e), s = z >= 0 ? r : e * r); u = the IoU
+         of the standard-decoded box (``rn_box_iou_loss``'s steps 1-2); m = 1 * s * ... * s * u * ... * u (``alpha`` then ``beta``
+         factors, left to right); dropped unless m > 0, m < inf and u >= 0;
+      3. the ``topk`` largest m of the row over all levels together, ties to the lower anchor index;
+      4. an anchor selected for several rows takes the largest fp32 u, ties to the lower row.
+    The predictions are constants: nothing is differentiated.  ``exp`` is computed through double and rounded once; the device's
+    ``expf`` may differ by an ulp, so a near-tie can fall the other way (the tests assert a margin)."""
+    alpha, beta, topk = ops.tal_exponent(alpha, "alpha"), ops.tal_exponent(beta, "beta"), ops.tal_topk(topk)
+    targets = targets.reshape(-1, 4)
+    labels = labels.reshape(-1)
+    if labels.shape[0] != targets.shape[0]:
+        raise ValueError(f"{labels.shape[0]} labels for {targets.shape[0]} boxes")
+    if cls.shape[0] != anchors.shape[0] or box.shape[0] != anchors.shape[0]:
+        raise ValueError(f"head outputs of {cls.shape[0]} / {box.shape[0]} rows for {anchors.shape[0]} anchors")
+    if anchors.is_cuda:
+        sizes = [int(anchors.shape[0])] if level_sizes is None else [int(s) for s in level_sizes]
+        off = ops.gt_offsets([targets.shape[0]], anchors.device)
+        lo, cl, bl = 0, [], []
+        for s in sizes:
+            cl.append(cls[None, lo:lo + s].contiguous())
+            bl.append(box[None, lo:lo + s].contiguous())
+            lo += s
+        matches, _ = ops.tal_match(cl, bl, anchors, targets, labels, off, 1, sizes, cells, topk, alpha, beta, reg_w=reg_w,
+                                   logit_shift=logit_shift, want_num_fg=False)
+        return matches[0]
+    import numpy as np
+    c = cls.detach().to(torch.float32).contiguous().numpy()
+    d = box.detach().to(torch.float32).contiguous().numpy()
+    a = anchors.detach().to(torch.float32).contiguous().numpy()
+    t = targets.detach().to(torch.float32).contiguous().numpy()
+    lab = labels.detach().to(torch.int64).numpy()
+    matches = np.full((a.shape[0],), -1, np.int64)
+    best = np.full((a.shape[0],), -1.0, np.float32)
+    for g in range(t.shape[0]):
+        sel, u, _, _ = task_aligned_candidates(c, d, a, t[g], int(lab[g]), topk, alpha, beta, reg_w, logit_shift)
+        for i, v in zip(sel, u):
+            if v > best[i]:                                  # strict: an equal IoU keeps the lower target index
+                best[i], matches[i] = v, g
     return torch.from_numpy(matches)
 
 

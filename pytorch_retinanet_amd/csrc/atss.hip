@@ -4,7 +4,7 @@
 //
 // Four launches, no synchronisation, gt_off read on the device only; the grids are sized by the host's upper bound on the GT rows
 // and a workgroup whose row lies beyond gt_off[B] exits:
-//   atss_prep_kernel    the flag words = 0, num_fg = 0 (unless the caller zeroed it), matches = -1 (unless FLAGGED_ONLY).
+//   assign_prep_kernel  (rn_assign.hpp) the flag words = 0, num_fg = 0 (unless the caller zeroed it), matches = -1 (unless FLAGGED_ONLY).
 //   atss_select_kernel  one workgroup per (GT row, level): the k_l anchors of the level that are smallest under (d2, index).  The key
 //                       is 64-bit -- d2's bit pattern (non-negative floats order as unsigned integers) above the anchor's index inside
 //                       the level -- so keys are unique and the tie rule is part of the order.  ONE walk over the level's anchors: a key
@@ -17,16 +17,20 @@
 //                       the same order, fetched with v_readlane from a 64-candidate register), then the candidates across lanes: a
 //                       positive one goes into the [B][A] key table with a 64-bit integer atomicMax of (IoU bits << 32) | ~gt index
 //                       -- order-independent, so the same bits on every call -- and every other record's index becomes -1.
-//   atss_emit_kernel    one thread per record: the record whose key IS the table's entry won the anchor: it writes matches, sets the
-//                       flag bit, counts into num_fg and puts the entry back to zero.  The table is zero on entry and zero again on
+//   assign_emit_kernel  (rn_assign.hpp, shared with tal.hip) one thread per record: the record whose key IS the table's entry won
+//                       the anchor: it writes matches, sets the flag bit, counts into num_fg and puts the entry back to zero.  The table is zero on entry and zero again on
 //                       exit without a clear of its B * A * 8 bytes.
 // Compiled without FMA contraction (EXACT in the Makefile): every fp32 and fp64 step below is one correctly rounded operation.
+#include "rn_assign.hpp"
 #include "rn_common.hpp"
 #include "rn_match.hpp"
 
 namespace {
 
-typedef unsigned long long u64;
+using rn_assign::append;
+using rn_assign::centre;
+using rn_assign::image_of_row;
+using rn_assign::u64;
 
 constexpr int SEL_BLOCK = 1024;
 constexpr int SEL_U = 4;                                // anchors per thread and step: four independent 16-byte loads in flight
@@ -34,7 +38,6 @@ constexpr int SEL_STEP = SEL_BLOCK * SEL_U;
 constexpr int SEL_KMAX = 2048;                          // largest k_l; the buffer is compacted once it holds more
 constexpr int SEL_CAP = SEL_KMAX + SEL_STEP;            // (48 KiB of keys: a step appends at most SEL_STEP)
 constexpr int SEL_PER = SEL_CAP / SEL_BLOCK;
-constexpr int EMIT_BLOCK = 256;
 
 struct Levels {
     int64_t off[RN_MAX_LEVELS + 1];                     // anchor range of level l inside A
@@ -43,18 +46,7 @@ struct Levels {
     int idx_bytes[RN_MAX_LEVELS];                       // bytes of an index inside the level that can be non-zero
 };
 
-// image of GT row `row` (gt_off[0] <= row < gt_off[B]): the number of i in 1..B with gt_off[i] <= row.  Every lane of the wave calls it.
-__device__ __forceinline__ int image_of_row(const int32_t *__restrict__ gt_off, const int B, const int row)
-{
-    const int lane = threadIdx.x & (RN_WAVE - 1);
-    int cnt = 0;
-    for (int i = 1 + lane; i <= B; i += RN_WAVE) cnt += gt_off[i] <= row ? 1 : 0;
-    cnt = rn::wave_sum_i(cnt);
-    return min(__builtin_amdgcn_readfirstlane(cnt), B - 1);
-}
-
-// step 1 of the rule, and the key of the order (d2, index)
-__device__ __forceinline__ float centre(const float lo, const float hi) { return (lo + hi) * 0.5f; }
+// the key of the order (d2, index) of step 2 (the centres of step 1: rn_assign::centre)
 __device__ __forceinline__ u64 d2_key(const rn::f32x4 a, const float gcx, const float gcy, const uint32_t i)
 {
     const float dx = centre(a.x, a.z) - gcx, dy = centre(a.y, a.w) - gcy;
@@ -63,78 +55,11 @@ __device__ __forceinline__ u64 d2_key(const rn::f32x4 a, const float gcx, const 
     return ((u64)__float_as_uint(d2) << 32) | i;
 }
 
-// One LDS counter bump per wave: the lanes that take a slot are numbered by their position in the ballot.  Called by whole waves.
-__device__ __forceinline__ void append(u64 *__restrict__ s_key, int *__restrict__ s_n, const bool take, const u64 key)
+// the select's compaction at this kernel's block size (rn_assign.hpp)
+__device__ __forceinline__ void shrink(u64 *__restrict__ s_key, int *__restrict__ s_hist, int *__restrict__ s_ctl, u64 *__restrict__ s_thr,
+                                       const int n, const int k, const int idx_bytes)
 {
-    const u64 m = __ballot(take);
-    if (!m) return;
-    const int lane = threadIdx.x & (RN_WAVE - 1), leader = __builtin_ctzll(m);
-    int base = 0;
-    if (lane == leader) base = atomicAdd(s_n, __popcll(m));
-    base = __shfl(base, leader, RN_WAVE);
-    if (take) s_key[base + __popcll(m & ((1ull << lane) - 1ull))] = key;
-}
-
-// The buffer's n keys -> its k smallest (k <= n, keys unique), *s_thr = the k-th.  Radix select from the top byte: the histogram of
-// the current byte over the keys that match the prefix found so far, wave 0 finds the bin that holds the k-th key.  The bytes of the
-// index that are zero in every key are skipped, and the walk ends early when the bin is taken whole.  Ends with a barrier.
-__device__ void shrink(u64 *__restrict__ s_key, int *__restrict__ s_hist, int *__restrict__ s_ctl, u64 *__restrict__ s_thr,
-                       const int n, const int k, const int idx_bytes)
-{
-    const int tid = threadIdx.x, lane = tid & (RN_WAVE - 1);
-    u64 prefix = 0ull, mask = 0ull, thr = 0ull;
-    int need = k;
-    bool done = false;
-    for (int byte = 7; byte >= 0 && !done; --byte) {
-        if (byte < 4 && byte >= idx_bytes) continue;
-        const int shift = byte * 8;
-        if (tid < 256) s_hist[tid] = 0;
-        __syncthreads();
-        for (int j = tid; j < n; j += SEL_BLOCK) {
-            const u64 key = s_key[j];
-            if ((key & mask) == prefix) atomicAdd(&s_hist[(int)(key >> shift) & 255], 1);
-        }
-        __syncthreads();
-        if (tid < RN_WAVE) {
-            int c[4], s = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { c[q] = s_hist[4 * lane + q]; s += c[q]; }
-            int incl = s;
-#pragma unroll
-            for (int o = 1; o < RN_WAVE; o <<= 1) {
-                const int t = __shfl_up(incl, o, RN_WAVE);
-                if (lane >= o) incl += t;
-            }
-            int run = incl - s;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (run < need && need <= run + c[q]) { s_ctl[1] = 4 * lane + q; s_ctl[2] = run; s_ctl[3] = c[q]; }
-                run += c[q];
-            }
-        }
-        __syncthreads();
-        const int bin = s_ctl[1], cnt = s_ctl[3];
-        need -= s_ctl[2];
-        prefix |= (u64)bin << shift;
-        mask |= 0xffull << shift;
-        if (cnt == need) {                              // the whole bin is taken: every key below prefix | (all ones under the byte)
-            thr = prefix | ((1ull << shift) - 1ull);
-            done = true;
-        }
-    }
-    if (!done) thr = prefix;
-    u64 mine[SEL_PER];
-#pragma unroll
-    for (int q = 0; q < SEL_PER; ++q) {
-        const int j = tid + q * SEL_BLOCK;
-        mine[q] = j < n ? s_key[j] : 0ull;
-    }
-    __syncthreads();
-    if (tid == 0) { s_ctl[0] = 0; *s_thr = thr; }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < SEL_PER; ++q) append(s_key, &s_ctl[0], tid + q * SEL_BLOCK < n && mine[q] <= thr, mine[q]);
-    __syncthreads();
+    rn_assign::shrink<SEL_BLOCK, SEL_PER>(s_key, s_hist, s_ctl, s_thr, n, k, idx_bytes);
 }
 
 __global__ __launch_bounds__(SEL_BLOCK) void atss_select_kernel(
@@ -245,51 +170,9 @@ __global__ __launch_bounds__(RN_WAVE) void atss_stats_kernel(
             const float inside = fminf(fminf(acx - g.x, acy - g.y), fminf(g.z - acx, g.w - acy));
             pos = inside > 0.01f;
         }
-        if (pos) atomicMax(&keys[(int64_t)b * A + a_idx], ((u64)__float_as_uint(v) << 32) | (uint32_t)~gi);
+        if (pos) rn_assign::table_post(keys, (int64_t)b * A + a_idx, v, gi);
         else idx[c] = -1;
     }
-}
-
-// step 6: the record whose key is the table's entry owns the anchor
-__global__ __launch_bounds__(EMIT_BLOCK) void atss_emit_kernel(
-    const int32_t *__restrict__ gt_off, const int B, const int64_t A, const int n, const int32_t *__restrict__ cand_idx,
-    const float *__restrict__ cand_iou, u64 *__restrict__ keys, int64_t *__restrict__ matches, int32_t *__restrict__ num_fg,
-    u64 *__restrict__ special)
-{
-    const int r = blockIdx.x;
-    const int row = gt_off[0] + r;
-    if (row >= gt_off[B]) return;
-    const int b = image_of_row(gt_off, B, row);
-    const uint32_t gi = (uint32_t)(row - gt_off[b]);
-    const int c = blockIdx.y * EMIT_BLOCK + threadIdx.x;
-    bool win = false;
-    if (c < n) {
-        const int a_idx = cand_idx[(int64_t)r * n + c];
-        if (a_idx >= 0) {
-            const u64 key = ((u64)__float_as_uint(cand_iou[(int64_t)r * n + c]) << 32) | (uint32_t)~gi;
-            u64 *__restrict__ e = &keys[(int64_t)b * A + a_idx];
-            win = *e == key;
-            if (win) {
-                *e = 0ull;
-                matches[(int64_t)b * A + a_idx] = (int64_t)gi;
-                if (special) atomicOr(&special[(int64_t)b * ((A + 63) >> 6) + (a_idx >> 6)], 1ull << (a_idx & 63));
-            }
-        }
-    }
-    if (num_fg) {
-        const u64 w = __ballot(win);
-        if ((threadIdx.x & (RN_WAVE - 1)) == 0 && w) atomicAdd(&num_fg[b], __popcll(w));
-    }
-}
-
-// what the call clears, as ONE kernel (never hipMemsetAsync: a memset node in a captured step, see match.hip)
-__global__ __launch_bounds__(256) void atss_prep_kernel(u64 *__restrict__ special, const int64_t n_special, int32_t *__restrict__ num_fg,
-                                                        const int n_fg, int64_t *__restrict__ matches, const int64_t n_matches)
-{
-    const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
-    for (int64_t i = t0; i < n_special; i += step) special[i] = 0ull;
-    for (int64_t i = t0; i < n_fg; i += step) num_fg[i] = 0;
-    for (int64_t i = t0; i < n_matches; i += step) matches[i] = -1;
 }
 
 // the level layout -> per-level k_l and record offsets.  RN_OK, RN_EINVAL or RN_EUNSUPPORTED.
@@ -318,7 +201,7 @@ int layout(const int64_t A, const int64_t *level_off, const int32_t *cells, cons
     return RN_OK;
 }
 
-size_t align16(const size_t v) { return (v + 15) & ~(size_t)15; }
+using rn_assign::align16;
 
 }  // namespace
 
@@ -354,18 +237,8 @@ RN_API int rn_atss_match(const float *anchors, int64_t anchor_bstride, const flo
     float *cand_iou = (float *)((char *)workspace + key_bytes + rec_bytes);
     u64 *special = (u64 *)special_rows;
     hipStream_t st = (hipStream_t)stream;
-    const bool sparse = (flags & RN_MATCH_FLAGGED_ONLY) != 0;
-
-    const int64_t n_special = special ? (int64_t)B * ((A + 63) >> 6) : 0;
-    const int n_fg = (num_fg && !(flags & RN_MATCH_NUM_FG_ZEROED)) ? B : 0;
-    const int64_t n_matches = sparse ? 0 : (int64_t)B * A;
-    const int64_t most = n_matches > n_special ? n_matches : (n_special > n_fg ? n_special : n_fg);
-    if (most > 0) {
-        int64_t blocks = (most + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(atss_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, st, special, n_special, num_fg, n_fg, matches, n_matches);
-        RN_LAUNCH_CHECK();
-    }
+    const int prc = rn_assign::launch_prep(B, A, matches, num_fg, special, flags, st);
+    if (prc != RN_OK) return prc;
     if (total_gt == 0 || n_tot == 0) return RN_OK;         // no GT rows anywhere: all background
     hipLaunchKernelGGL(atss_select_kernel, dim3((unsigned)total_gt, (unsigned)L), dim3(SEL_BLOCK), 0, st, (const rn::f32x4 *)anchors,
                        anchor_bstride / 4, (const rn::f32x4 *)gt_boxes, gt_off, B, n_tot, lv, cand_idx, cand_iou);
@@ -373,8 +246,5 @@ RN_API int rn_atss_match(const float *anchors, int64_t anchor_bstride, const flo
     hipLaunchKernelGGL(atss_stats_kernel, dim3((unsigned)total_gt), dim3(RN_WAVE), 0, st, (const rn::f32x4 *)anchors, anchor_bstride / 4,
                        (const rn::f32x4 *)gt_boxes, gt_off, B, A, n_tot, cand_idx, cand_iou, keys);
     RN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(atss_emit_kernel, dim3((unsigned)total_gt, (unsigned)((n_tot + EMIT_BLOCK - 1) / EMIT_BLOCK)), dim3(EMIT_BLOCK), 0, st,
-                       gt_off, B, A, n_tot, cand_idx, cand_iou, keys, matches, num_fg, special);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
+    return rn_assign::launch_emit(total_gt, n_tot, gt_off, B, A, cand_idx, cand_iou, keys, matches, num_fg, special, st);
 }

@@ -560,7 +560,10 @@ class CapturedTrainStep:
         key += tuple(aug.items())
         # the matcher's launches are part of the step: another kind or another topk is another graph.  The default ("iou") adds nothing.
         crit = getattr(getattr(self.net, "retinanet_head", None), "losses", None)
-        if getattr(crit, "matcher", "iou") != "iou":
+        # "tal" carries its own topk and both exponents: they are baked into its launches.
+        if getattr(crit, "matcher", "iou") == "tal":
+            key += (("matcher", "tal", int(crit.tal_topk), int(crit.tal_alpha), int(crit.tal_beta)),)
+        elif getattr(crit, "matcher", "iou") != "iou":
             key += (("matcher", crit.matcher, int(crit.atss_topk)),)
         # so is the box loss: an IoU kind adds ops.box_iou_loss's launches, and its weight is baked into them.  "smooth_l1" adds nothing.
         if getattr(crit, "box_loss", "smooth_l1") != "smooth_l1":

@@ -204,12 +204,13 @@ class RetinaNetHead(nn.Module):
 
     def __init__(self, in_channels: int, out_channels: int, num_anchors: int, num_classes: int, prior: float,
                  matcher: str = "iou", atss_topk: int = 9, cells=None, box_loss: str = "smooth_l1", box_loss_weight: float = 1.0,
-                 cls_loss: str = "focal", qfl_beta: float = 2.0) -> None:
+                 cls_loss: str = "focal", qfl_beta: float = 2.0, tal_topk: int = 13, tal_alpha: int = 1, tal_beta: int = 6) -> None:
         super().__init__()
         self.classification_head = RetinaNetClassSubnet(in_channels, out_channels, num_anchors, num_classes, prior)
         self.regression_head = RetinaNetBoxSubnet(in_channels, out_channels, num_anchors)
         self.losses = RetinaNetLosses(num_classes, matcher=matcher, atss_topk=atss_topk, cells=num_anchors if cells is None else cells,
-                                      box_loss=box_loss, box_loss_weight=box_loss_weight, cls_loss=cls_loss, qfl_beta=qfl_beta)
+                                      box_loss=box_loss, box_loss_weight=box_loss_weight, cls_loss=cls_loss, qfl_beta=qfl_beta,
+                                      tal_topk=tal_topk, tal_alpha=tal_alpha, tal_beta=tal_beta)
         # bf16 canvas towers: "pair" = hand-written MFMA conv, cls + box tower batched per layer; "single" = the same kernel,
         # one launch per conv; "miopen" = MIOpen conv + fused epilogue kernel.  RN_TOWERS overrides (one of the three documented A/B switches, README).
         mode = os.environ.get("RN_TOWERS", "pair")

@@ -142,7 +142,9 @@ class _FusedDenseHeadLossLevels(torch.autograd.Function):
             loss, gcls, gbox = fused[0], fused[1], fused[2]
         else:
             if h.matches is None:
-                _launch_matcher(h)
+                # (the "tal" rule is launched HERE whatever the caller did: it reads the outputs that have just arrived -- as
+                # constants: a Function's forward records nothing -- and runs right in front of K3 on K3's stream)
+                _launch_matcher(h, heads=(cls_levels, box_levels, params))
             elif h.done is not None:
                 torch.cuda.current_stream(dev).wait_event(h.done)    # the matcher ran beside the head convolutions
             pre = grad_prescale.value
@@ -196,11 +198,20 @@ def _resolve_gt(targets, dev: Optional[torch.device]):
     return arrays + (len(boxes), max([b.numel() // 4 for b in boxes] or [0]))
 
 
-def _launch_matcher(h: MatchAhead, out: Optional[tuple] = None) -> None:
+def _launch_matcher(h: MatchAhead, out: Optional[tuple] = None, heads: Optional[tuple] = None) -> None:
     """The matcher of ``h.rule`` on the CURRENT stream, into ``h.matches`` / ``h.num_fg`` / ``h.special``.  ``out``: buffers the caller
     allocated (``match_ahead``: they belong to its main stream), written in full.  Without it fresh ones, and ``matches`` written at the
-    flagged rows only: it goes nowhere but into the loss kernel, which reads it through the flag words."""
+    flagged rows only: it goes nowhere but into the loss kernel, which reads it through the flag words.  ``heads``: (cls_levels,
+    box_levels, params) -- what the "tal" rule reads beside the anchors and the GT, so it can only be launched where they exist."""
     kw = dict(want_special=True, flagged_only=True) if out is None else dict(out=out)
+    if h.rule[0] == "tal":
+        if heads is None:
+            raise ValueError('matcher="tal" reads the head\'s outputs and cannot be launched ahead of them')
+        sizes, cells, topk, alpha, beta, level_w = h.rule[1:]
+        h.matches, h.num_fg, h.special = ops.tal_match(heads[0], heads[1], h.anchors, h.gt_boxes, h.gt_labels, h.gt_off, h.B, sizes, cells,
+                                                       topk, alpha, beta, reg_w=tuple(heads[2].reg_w), logit_shift=heads[2].logit_shift,
+                                                       zeroed_num_fg=h.num_fg0, level_w=level_w, **kw)
+        return
     match = ops.atss_match if h.rule[0] == "atss" else ops.iou_match
     h.matches, h.num_fg, h.special = match(h.anchors, h.gt_boxes, h.gt_off, h.B, *h.rule[1:], zeroed_num_fg=h.num_fg0, **kw)
 
@@ -216,11 +227,16 @@ def _stack_anchors(anchors) -> Tensor:
     return torch.stack(list(anchors))
 
 
-def _check_matcher(matcher: str, atss_topk: int) -> None:
-    if matcher not in ops.ATSS_MATCHERS:
-        raise ValueError(f"matcher must be one of {ops.ATSS_MATCHERS}, got {matcher!r}")
+def _check_matcher(matcher: str, atss_topk: int, tal: tuple = (13, 1, 6)) -> None:
+    if matcher not in ops.MATCHERS:
+        raise ValueError(f"matcher must be one of {ops.MATCHERS}, got {matcher!r}")
     if int(atss_topk) <= 0:
         raise ValueError(f"atss_topk must be a positive int, got {atss_topk!r}")
+    ops.tal_topk(tal[0]), ops.tal_exponent(tal[1], "tal_alpha"), ops.tal_exponent(tal[2], "tal_beta")
+    if matcher == "tal" and FUSE_MATCH:
+        raise ValueError('RN_FUSE_MATCH=1 runs the max-IoU matcher inside the loss kernel and cannot be combined with matcher="tal": '
+                         "the task-aligned matcher reads the head\'s outputs and fills the matcher\'s buffers; unset RN_FUSE_MATCH or use "
+                         'matcher="iou"')
     if matcher == "atss" and FUSE_MATCH:
         raise ValueError('RN_FUSE_MATCH=1 runs the max-IoU matcher inside the loss kernel and cannot be combined with matcher="atss": '
                          "there is no ATSS form of the fused kernel; unset RN_FUSE_MATCH or use matcher=\"iou\"")
@@ -317,7 +333,8 @@ def box_iou_loss_reference(deltas: Tensor, anchors: Tensor, gt: Tensor, kind: st
 
 class RetinaNetLosses(nn.Module):
     def __init__(self, num_classes: int, matcher: str = "iou", atss_topk: int = 9, cells=None, box_loss: str = "smooth_l1",
-                 box_loss_weight: float = 1.0, cls_loss: str = "focal", qfl_beta: float = 2.0) -> None:
+                 box_loss_weight: float = 1.0, cls_loss: str = "focal", qfl_beta: float = 2.0, tal_topk: int = 13, tal_alpha: int = 1,
+                 tal_beta: int = 6) -> None:
         """``matcher``: "iou" (K2: the reference's max-IoU rule with its 0.5 / 0.4 thresholds) or "atss" (``ops.atss_match``: a
         per-object threshold from the IoU statistics of the ``atss_topk`` nearest locations of every pyramid level; no ignored band).
         ATSS applies to the per-level path (``forward_levels`` / ``match_ahead``, what ``Retinanet.forward`` runs; ``forward`` /
@@ -332,9 +349,18 @@ class RetinaNetLosses(nn.Module):
         it gives every matched row's label element the IoU of its decoded box with its GT box as target; the weight stays detached
         and the normaliser ``num_fg``, see include/retinanet_hip.h).  Per-level path only, refuses ``RN_FUSE_MATCH=1``; composes with
         both matchers and all three box losses.  CPU tensors with "qfl" go through the torch restatement (``matcher="atss"`` only:
-        the max-IoU matcher has no CPU form)."""
+        the max-IoU matcher has no CPU form).
+        ``matcher="tal"`` (``ops.tal_match``, TOOD's task-aligned assignment): per object the ``tal_topk`` anchors with the largest
+        ``score^tal_alpha * IoU^tal_beta`` among those whose centre lies inside its box, the score and the IoU being what the head
+        predicts NOW (read as constants; integer exponents in 0..8, the metric is a chain of fp32 products).  It needs the head's
+        outputs, so it never runs ahead of the head: ``match_ahead`` only records the rule and the launch happens in
+        ``forward_levels``, right in front of K3 on the same stream.  Per-level path only, refuses ``RN_FUSE_MATCH=1``; composes with
+        every box and class loss.  ``matcher`` is a plain attribute read at every call: TOOD's schedule "ATSS for the first
+        epochs, then TAL" is ``losses.matcher = "tal"`` between two epochs (a captured step re-captures once: the matcher is part
+        of its key)."""
         super().__init__()
-        _check_matcher(matcher, atss_topk)
+        _check_matcher(matcher, atss_topk, (tal_topk, tal_alpha, tal_beta))
+        self.tal_topk, self.tal_alpha, self.tal_beta = int(tal_topk), int(tal_alpha), int(tal_beta)
         _check_box_loss(box_loss, box_loss_weight)
         _check_cls_loss(cls_loss, qfl_beta)
         self.cls_loss, self.qfl_beta = cls_loss, float(qfl_beta)
@@ -373,9 +399,9 @@ class RetinaNetLosses(nn.Module):
         return ops.make_loss_params(self.alpha, self.gamma, self.beta, LOGIT_SHIFT, ENCODE_LOG_EPS, BBOX_REG_WEIGHTS)
 
     def _fused(self, cls: Tensor, box: Tensor, anchors, boxes: Sequence[Tensor], labels: Sequence[Tensor]) -> Tensor:
-        if self.matcher == "atss":
+        if self.matcher in ("atss", "tal"):
             # (the concatenated outputs carry no level layout, and matching them with K2 instead would be a silent change of rule)
-            raise ValueError('matcher="atss" runs on the per-level head outputs: use forward_levels / Retinanet.forward, not forward / calc_loss')
+            raise ValueError(f'matcher="{self.matcher}" runs on the per-level head outputs: use forward_levels / Retinanet.forward, not forward / calc_loss')
         if self.box_loss != "smooth_l1":
             # (the concatenated path has no flag words, and answering with smooth-L1 instead would be a silent change of loss)
             raise ValueError(f'box_loss="{self.box_loss}" runs on the per-level head outputs: use forward_levels / Retinanet.forward, not forward / calc_loss')
@@ -399,12 +425,16 @@ class RetinaNetLosses(nn.Module):
         (see ``FUSE_MATCH``)."""
         return FUSE_MATCH and _resolve_gt(targets, None)[5] <= 64
 
-    def _handle(self, targets, anchors, level_sizes) -> MatchAhead:
+    def _handle(self, targets, anchors, level_sizes, level_w=None) -> MatchAhead:
         """The handle of these targets and anchors: the GT resolved (``_resolve_gt``), the matcher named, nothing of it launched.
         ``level_sizes`` (anchors per pyramid level) is what ``matcher="atss"`` needs beside them; ``ops.atss_match`` checks its sum."""
-        _check_matcher(self.matcher, self.atss_topk)              # (RN_FUSE_MATCH may have been switched on after construction)
+        _check_matcher(self.matcher, self.atss_topk, (self.tal_topk, self.tal_alpha, self.tal_beta))   # (RN_FUSE_MATCH may have been switched on after construction)
         h = MatchAhead()
-        if self.matcher == "atss":
+        if self.matcher == "tal":
+            if level_sizes is None:
+                raise ValueError('matcher="tal" needs the anchors per pyramid level (level_sizes)')
+            h.rule = ("tal", list(level_sizes), self.cells, self.tal_topk, self.tal_alpha, self.tal_beta, None if level_w is None else list(level_w))
+        elif self.matcher == "atss":
             if level_sizes is None:
                 raise ValueError('matcher="atss" needs the anchors per pyramid level (level_sizes)')
             h.rule = ("atss", list(level_sizes), self.cells, self.atss_topk)
@@ -415,15 +445,20 @@ class RetinaNetLosses(nn.Module):
         h.matches = h.num_fg = h.special = h.done = None
         return h
 
-    def match_ahead(self, targets: List[Dict[str, Tensor]], anchors, level_sizes=None) -> MatchAhead:
+    def match_ahead(self, targets: List[Dict[str, Tensor]], anchors, level_sizes=None, level_w=None) -> MatchAhead:
         """Launch K2 (IoU + matcher, box_utils.py:51-80) NOW, on a side stream: it depends only on the anchors and the GT boxes,
         both known as soon as the feature-map shapes are, and then runs beside the head convolutions instead of between the
         class-output conv and K3.  Pass the result to ``forward_levels(..., ahead=...)``, which makes the loss kernel wait
         for it.  The outputs belong to the CALLING stream (allocated before the fork, consumed after the join).
-        ``matcher="atss"``: the same with ``ops.atss_match``; ``level_sizes`` (anchors per pyramid level) is needed then."""
-        h = self._handle(targets, anchors, level_sizes)
+        ``matcher="atss"``: the same with ``ops.atss_match``; ``level_sizes`` (anchors per pyramid level) is needed then.
+        ``matcher="tal"``: nothing is launched -- the rule reads the head's outputs -- and the handle only RECORDS the rule, with
+        ``level_w`` (grid columns per level, optional: the kernel then visits only the cells under each box); ``forward_levels``
+        launches it when the outputs arrive."""
+        h = self._handle(targets, anchors, level_sizes, level_w)
         dev = h.anchors.device
         h.max_gt = None
+        if h.rule[0] == "tal":
+            return h
         if not isinstance(targets, ops.PackedGT):
             h.num_fg0 = None        # (only gt_stage's zeroed num_fg is used here; with a list the matcher clears its own)
         out = ops.iou_match_outputs(h.B, int(h.anchors.shape[-2]), dev, want_num_fg=h.num_fg0 is None)
@@ -450,6 +485,8 @@ class RetinaNetLosses(nn.Module):
             _check_box_loss(self.box_loss, self.box_loss_weight)
             box_loss = (self.box_loss, self.box_loss_weight)
         extra = ()
+        if self.matcher == "tal" and not cls_levels[0].is_cuda and isinstance(targets, ops.PackedGT):
+            raise ValueError('matcher="tal" on CPU tensors takes the list of target dicts: packed GT (ops.PackedGT) lives on the device')
         if self.cls_loss != "focal":
             _check_cls_loss(self.cls_loss, self.qfl_beta)
             if not cls_levels[0].is_cuda:
@@ -472,10 +509,10 @@ class RetinaNetLosses(nn.Module):
     def _qfl_torch(self, targets, cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], anchors) -> Dict[str, Tensor]:
         """``cls_loss="qfl"`` on CPU tensors, in plain differentiable torch from the restatements: what K3 (``alpha = 1,
         gamma = qfl_beta``), ``ops.box_iou_loss`` and ``ops.quality_focal_loss`` compute on the device, in the outputs' dtype.  The
-        matcher is ``box_utils.atss_matcher``'s CPU restatement; the max-IoU matcher has none, so ``matcher="iou"`` is refused here."""
-        from .box_utils import atss_matcher, bbox_2_activ
-        if self.matcher != "atss":
-            raise ValueError('cls_loss="qfl" on CPU tensors needs matcher="atss": the max-IoU matcher runs on the device only')
+        matcher is ``box_utils.atss_matcher``'s / ``box_utils.task_aligned_matcher``'s CPU restatement; the max-IoU matcher has none, so ``matcher="iou"`` is refused here."""
+        from .box_utils import atss_matcher, bbox_2_activ, task_aligned_matcher
+        if self.matcher not in ("atss", "tal"):
+            raise ValueError('cls_loss="qfl" on CPU tensors needs matcher="atss" or "tal": the max-IoU matcher runs on the device only')
         if isinstance(targets, ops.PackedGT):
             raise TypeError("packed GT (ops.PackedGT) lives on the device")
         cls, box = torch.cat(list(cls_levels), 1), torch.cat(list(box_levels), 1)
@@ -487,7 +524,13 @@ class RetinaNetLosses(nn.Module):
         for b, t in enumerate(targets):
             an = anc if anc.dim() == 2 else anc[b]
             gt = t["boxes"].reshape(-1, 4).to(torch.float32)
-            m = atss_matcher(an, gt, sizes, self.cells, self.atss_topk) if gt.shape[0] else torch.full((an.shape[0],), -1, dtype=torch.int64)
+            if not gt.shape[0]:
+                m = torch.full((an.shape[0],), -1, dtype=torch.int64)
+            elif self.matcher == "tal":
+                m = task_aligned_matcher(cls[b].detach(), box[b].detach(), an, gt, t["labels"], self.tal_topk, self.tal_alpha, self.tal_beta,
+                                         BBOX_REG_WEIGHTS, LOGIT_SHIFT)
+            else:
+                m = atss_matcher(an, gt, sizes, self.cells, self.atss_topk)
             rows = (m >= 0).nonzero().flatten()
             scale = 1.0 / max(int(rows.numel()), 1)
             z = cls[b] + LOGIT_SHIFT

@@ -61,9 +61,16 @@ class Retinanet(nn.Module):
         soft_nms_min_score: Optional[float] = None,
         cls_loss: Optional[str] = None,
         qfl_beta: Optional[float] = None,
+        tal_topk: Optional[int] = None,
+        tal_alpha: Optional[int] = None,
+        tal_beta: Optional[int] = None,
     ) -> None:
-        """``matcher``: how anchors are labelled -- None / "iou" (the reference's max-IoU rule, K2) or "atss" (``ops.atss_match``,
-        with ``atss_topk`` nearest locations per level and object, None -> 9); ``model: {matcher: atss}`` in the hparams.
+        """``matcher``: how anchors are labelled -- None / "iou" (the reference's max-IoU rule, K2), "atss" (``ops.atss_match``,
+        with ``atss_topk`` nearest locations per level and object, None -> 9) or "tal" (``ops.tal_match``, TOOD's task-aligned
+        assignment: per object the ``tal_topk`` (None -> 13) anchors with the largest ``score^tal_alpha * IoU^tal_beta`` (None -> 1
+        and 6; integers) among those whose centre lies inside the box, from what the head predicts at that step);
+        ``model: {matcher: atss}`` / ``model: {matcher: tal}`` in the hparams.  "tal" ranks by the IoU of the box
+        ``box_decode="standard"`` decodes, so with the reference decode it logs the warning "giou" / "diou" / "qfl" log.
         ``box_loss``: the box regression loss -- None / "smooth_l1" (the reference's, inside K3) or "giou" / "diou" (``ops.box_iou_loss``
         behind K3), times ``box_loss_weight`` (None -> 1.0); ``model: {box_loss: giou, box_loss_weight: 2.0}`` in the hparams.  Training
         only: what decodes the detections is ``box_decode``, whatever the loss.
@@ -97,6 +104,7 @@ class Retinanet(nn.Module):
             raise ValueError(f"box_decode must be one of {ops.BOX_DECODES}, got {box_decode!r}")
         matcher = ifnone(matcher, "iou")
         atss_topk = ifnone(atss_topk, 9)
+        tal_topk, tal_alpha, tal_beta = ifnone(tal_topk, 13), ifnone(tal_alpha, 1), ifnone(tal_beta, 6)
         box_loss = ifnone(box_loss, "smooth_l1")
         box_loss_weight = ifnone(box_loss_weight, 1.0)
         num_classes = ifnone(num_classes, NUM_CLASSES)
@@ -127,7 +135,7 @@ class Retinanet(nn.Module):
         num_anchors = self.anchor_generator.num_cell_anchors[0]
         self.retinanet_head = RetinaNetHead(256, 256, num_anchors, num_classes, prior, matcher=matcher, atss_topk=atss_topk,
                                             cells=self.anchor_generator.num_anchors, box_loss=box_loss, box_loss_weight=box_loss_weight,
-                                            cls_loss=cls_loss, qfl_beta=qfl_beta)
+                                            cls_loss=cls_loss, qfl_beta=qfl_beta, tal_topk=tal_topk, tal_alpha=tal_alpha, tal_beta=tal_beta)
 
         self.score_thres = score_thres
         self.nms_thres = nms_thres
@@ -141,6 +149,10 @@ class Retinanet(nn.Module):
             logger.warning(f'box_loss="{box_loss}" trains the box that box_decode="standard" decodes, but this model infers with the '
                            'reference decode (sizes from exp(dx), exp(dy)): pass box_decode="standard" (model: {box_decode: standard}) '
                            "to evaluate what was trained")
+        if matcher == "tal" and box_decode == "reference":
+            logger.warning('matcher="tal" picks the positives by the IoU of the box that box_decode="standard" decodes, but this model '
+                           'infers with the reference decode (sizes from exp(dx), exp(dy)): pass box_decode="standard" '
+                           "(model: {box_decode: standard}) so that inference decodes the box the labels were aligned to")
         if cls_loss == "qfl" and box_decode == "reference":
             logger.warning('cls_loss="qfl" trains the class score towards the IoU of the box that box_decode="standard" decodes, but this '
                            'model infers with the reference decode (sizes from exp(dx), exp(dy)): pass box_decode="standard" '
@@ -207,11 +219,17 @@ class Retinanet(nn.Module):
         # hipGraph: a graph with a forked branch costs hipGraphLaunch 20 ms of host time per replay on ROCm 7.0 (0.4 ms for
         # the linear graph of the same step, bench.py host_enqueue_ms_per_step) -- 25 us of GPU time are not worth that.
         ahead = None
-        if batch.is_cuda and not torch.cuda.is_current_stream_capturing() and not self.retinanet_head.losses.fuses_match(targets):
+        crit = self.retinanet_head.losses
+        if batch.is_cuda and crit.matcher == "tal":
+            # the task-aligned rule reads the head's outputs: the handle only records it (nothing is launched, so a capture may hold
+            # it too), with the grid width of every level -- its kernel then visits only the cells under each box
+            sizes = [int(f.shape[-2]) * int(f.shape[-1]) * n for f, n in zip(feature_maps, self.anchor_generator.num_anchors)]
+            ahead = crit.match_ahead(targets, anchors, sizes, level_w=[int(f.shape[-1]) for f in feature_maps])
+        elif batch.is_cuda and not torch.cuda.is_current_stream_capturing() and not crit.fuses_match(targets):
             sizes = None
-            if self.retinanet_head.losses.matcher == "atss":                      # (its candidates are chosen per pyramid level)
+            if crit.matcher == "atss":                                            # (its candidates are chosen per pyramid level)
                 sizes = [int(f.shape[-2]) * int(f.shape[-1]) * n for f, n in zip(feature_maps, self.anchor_generator.num_anchors)]
-            ahead = self.retinanet_head.losses.match_ahead(targets, anchors, sizes)   # (<= 64 GT per image: K2 runs inside K3, no launch at all)
+            ahead = crit.match_ahead(targets, anchors, sizes)                     # (<= 64 GT per image: K2 runs inside K3, no launch at all)
         # same losses as compute_loss(targets, retinanet_head(feature_maps), anchors), but the loss kernel
         # reads the five per-level conv outputs in place instead of their torch.cat (layers.py:195, :259)
         outputs = self.retinanet_head.forward_levels(feature_maps)

@@ -384,12 +384,11 @@ def atss_layout(level_sizes: Sequence[int], cells, topk: int):
     return (C.c_int64 * (L + 1))(*off), (C.c_int32 * L)(*cells), L, (tuple(sizes), tuple(cells), int(topk))
 
 
-def atss_workspace(dev: torch.device, B: int, A: int, rows: int, level_sizes: Sequence[int], cells, topk: int) -> Tensor:
-    """The (cached) workspace of ``atss_match`` for these shapes on the current stream: uint8, its conflict table zero.  Sized for a
-    power-of-two row capacity >= ``rows``, so batches with other GT counts reuse it."""
-    off, cl, L, lkey = atss_layout(level_sizes, cells, topk)
+def _assign_workspace(dev: torch.device, key: tuple, rows: int, nbytes_of, what: str) -> Tensor:
+    """The (cached) workspace of a matcher with a conflict table (``atss_match``, ``tal_match``) under ``key`` on the current stream:
+    uint8, zero-filled once.  ``nbytes_of(cap)``: the library's size for ``cap`` rows; the buffer is sized for a power-of-two row
+    capacity >= ``rows``, so batches with other GT counts reuse it.  Inside ``use_atss_workspaces(holder)`` it lives in ``holder``."""
     holder = use_atss_workspaces.value
-    key = (dev.index, B, A) + lkey
     if holder is None:
         holder, key = _ATSS_WS, key + (torch.cuda.current_stream(dev).cuda_stream,)
     hit = holder.get(key)
@@ -398,14 +397,22 @@ def atss_workspace(dev: torch.device, B: int, A: int, rows: int, level_sizes: Se
     cap = 64
     while cap < rows:
         cap *= 2
-    nbytes = lib.rn_atss_match_workspace_bytes(B, A, cap, off, cl, L, int(topk))
+    nbytes = nbytes_of(cap)
     if nbytes == 0:
-        raise ValueError(f"rn_atss_match takes no such layout: B={B} A={A} levels={lkey}")
+        raise ValueError(f"{what} takes no such layout: {key}")
     if holder is _ATSS_WS and len(holder) >= 8:
         holder.clear()
     ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
     holder[key] = (ws, cap)
     return ws
+
+
+def atss_workspace(dev: torch.device, B: int, A: int, rows: int, level_sizes: Sequence[int], cells, topk: int) -> Tensor:
+    """The (cached) workspace of ``atss_match`` for these shapes on the current stream: uint8, its conflict table zero.  Sized for a
+    power-of-two row capacity >= ``rows``, so batches with other GT counts reuse it."""
+    off, cl, L, lkey = atss_layout(level_sizes, cells, topk)
+    return _assign_workspace(dev, (dev.index, B, A) + lkey, rows,
+                             lambda cap: lib.rn_atss_match_workspace_bytes(B, A, cap, off, cl, L, int(topk)), "rn_atss_match")
 
 
 def atss_match(anchors: Tensor, gt_boxes: Tensor, gt_off: Tensor, B: int, level_sizes: Sequence[int], cells, topk: int = 9,
@@ -641,6 +648,79 @@ def quality_focal_loss(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor
                                         reg_w, beta, float(logit_shift), _ptr(grad_prescale), _ptr(loss), a.arr(gcls), _ptr(ws),
                                         ws.numel(), _stream(a.dev)), "rn_quality_focal_loss")
     return loss
+
+
+# ---- Task-aligned matcher ----------------------------------------------------------------------------------------------------
+MATCHERS = ATSS_MATCHERS + ("tal",)
+TAL_TOPK_MAX = 64
+TAL_EXP_MAX = 8
+
+
+def tal_list_keys() -> int:
+    "The capacity of a ``rn_tal_match`` workgroup's candidate list: a box over more candidates is compacted on the way (for tests)."
+    return int(lib.rn_tal_match_list_keys())
+
+
+def tal_exponent(value, name: str) -> int:
+    """``alpha`` / ``beta`` of the task-aligned metric as the int the kernel takes.  The metric is a fixed chain of fp32 products
+    (the rule has no ``powf``, so that it can be restated bit for bit), hence integers in 0..8 only."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or float(value) != int(value):
+        raise ValueError(f"{name} must be an integer: the task-aligned metric score^alpha * IoU^beta is evaluated as a chain of fp32 "
+                         f"products, not with powf (ultralytics' alpha = 0.5 has no such form), got {value!r}")
+    if not 0 <= int(value) <= TAL_EXP_MAX:
+        raise ValueError(f"{name} must lie in 0..{TAL_EXP_MAX}, got {value!r}")
+    return int(value)
+
+
+def tal_topk(value) -> int:
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= TAL_TOPK_MAX:
+        raise ValueError(f"tal_topk must be an int in 1..{TAL_TOPK_MAX}, got {value!r}")
+    return value
+
+
+def tal_workspace(dev: torch.device, B: int, A: int, rows: int, L: int, topk: int) -> Tensor:
+    """The (cached) workspace of ``tal_match`` for these shapes on the current stream: uint8, its conflict table zero.  Kept where
+    ``atss_workspace`` keeps its own (``use_atss_workspaces`` inside a capture), sized for a power-of-two row capacity >= ``rows``."""
+    return _assign_workspace(dev, ("tal", dev.index, B, A, L, int(topk)), rows,
+                             lambda cap: lib.rn_tal_match_workspace_bytes(B, A, cap, L, int(topk)), "rn_tal_match")
+
+
+def tal_match(cls_levels: Sequence[Tensor], box_levels: Sequence[Tensor], anchors: Tensor, gt_boxes: Tensor, gt_labels: Tensor,
+              gt_off: Tensor, B: int, level_sizes: Sequence[int], cells, topk: int = 13, alpha: int = 1, beta: int = 6,
+              reg_w: Sequence[float] = (1.0, 1.0, 1.0, 1.0), logit_shift: float = 1.0, want_num_fg: bool = True,
+              want_special: bool = False, out: Optional[tuple] = None, flagged_only: bool = False,
+              zeroed_num_fg: Optional[Tensor] = None, workspace: Optional[Tensor] = None, level_w: Optional[Sequence[int]] = None):
+    """The task-aligned matcher (``rn_tal_match``; the rule: include/retinanet_hip.h, restated by ``box_utils.task_aligned_matcher``):
+    per GT row the ``topk`` anchors with the largest ``score^alpha * IoU^beta`` among those whose centre lies inside the box, the
+    score and the IoU taken from the head's outputs ``cls_levels[l]`` [B,A_l,K] / ``box_levels[l]`` [B,A_l,4] (read as constants).
+    Results, ``out``, ``flagged_only``, ``zeroed_num_fg`` and ``workspace`` as ``atss_match``; ``level_sizes`` (anchors per level) must
+    be the outputs'; ``cells`` = anchors per grid location (an int or one per level).  ``level_w`` (optional): grid columns per
+    level -- the kernel then visits only the cells under each box instead of the whole level (same results for a grid anchor set).
+    ``alpha`` / ``beta``: integers in 0..8.  No synchronisation; capturable."""
+    topk, alpha, beta = tal_topk(topk), tal_exponent(alpha, "alpha"), tal_exponent(beta, "beta")
+    _, cl, L, lkey = atss_layout(level_sizes, cells, topk)
+    a = _LevelArgs(cls_levels, box_levels, anchors, gt_boxes, gt_labels, gt_off)
+    if a.L != L or [int(c) for c in a.counts] != list(lkey[0]):
+        raise ValueError(f"level sizes {lkey[0]} are not the head outputs' {[int(c) for c in a.counts]}")
+    if a.B != int(B):
+        raise ValueError(f"head outputs of {a.B} images for B = {B}")
+    if a.gt_labels.shape[0] != a.gt_boxes.shape[0]:
+        raise ValueError(f"{a.gt_labels.shape[0]} labels for {a.gt_boxes.shape[0]} GT boxes")
+    lw = None
+    if level_w is not None:
+        if len(level_w) != L or any(int(w) < 0 or (int(w) > 0 and s % (int(w) * c)) for w, s, c in zip(level_w, lkey[0], lkey[1])):
+            raise ValueError(f"level_w {list(level_w)}: one grid width per level that, times the cells, divides the level ({lkey[0]}, {lkey[1]})")
+        lw = (C.c_int32 * L)(*[int(w) for w in level_w])
+    dev, A, anc, bstride, gtb, (matches, num_fg, special), flags, ret = _match_args(
+        a.anchors, a.gt_boxes, gt_off, a.B, want_num_fg, want_special, out, flagged_only, zeroed_num_fg)
+    rows = int(gtb.shape[0])
+    ws = workspace if workspace is not None else tal_workspace(dev, a.B, A, rows, L, topk)
+    rw = (C.c_float * 4)(*[float(v) for v in reg_w])
+    with torch.cuda.device(dev), _timed("tal_match", dev):
+        check(lib.rn_tal_match(a.arr(a.cls), a.arr(a.box), a.counts, cl, lw, L, a.code, a.B, a.K, _ptr(anc), bstride, _ptr(gtb),
+                               _ptr(a.gt_labels), _ptr(gt_off), topk, alpha, beta, rw, float(logit_shift), _ptr(matches), _ptr(num_fg),
+                               _ptr(special), rows, flags, _ptr(ws), ws.numel(), _stream(dev)), "rn_tal_match")
+    return ret
 
 
 # ---- K2 + K3 in one launch -------------------------------------------------------------------------------------------------
